@@ -14,6 +14,12 @@ Launch: python bench.py --gpus 1 --steps K --warmup W
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 Data: synthetic (seeded LCG noise PCM per session; seeded random weights at aprilv0 dims --
 there is no real model/audio offline).  Override with APRIL_MODEL=/path/model.april.
+
+A plain run sets up, warms up, times the K steps and prints the result line.  Everything else
+(the steady series, the other ingest mode, the deeper pipeline, the gates roofline, the
+reference-API leg, the concurrency sweep, the offline minute, configs[4], the CPU baseline)
+runs only with --full.  --dump-outputs DIR writes what the sessions' callers hold after the
+last timed step as DIR/*.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -30,6 +36,99 @@ FP32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32
 FP16_MFMA_PEAK_TFLOPS = 2500.0     # dense fp16 MFMA peak (--precision f16 only)
 HBM_PEAK_GBS = 8000.0              # spec; ~6300 measured achievable
 TRAFFIC_JSON = "r06_gates_traffic.json"      # the committed PMC pass the roofline's `traffic` is taken from
+
+# --dump-outputs: a result handler in C that does what aprilx_counting_handler does (the line's `callbacks` / `tokens_in_callbacks`)
+# and also keeps each session's latest result.  A Python handler would take the GIL on the library's delivery thread inside the
+# timed steps.  One Rec per session (userdata); 72 = the most tokens one result carries (csrc/session.h kMaxActive).
+REC_TOKENS = 72
+RECORD_HANDLER_C = r"""
+#include <stddef.h>
+#include <stdint.h>
+typedef struct { const char *token; float logprob; int flags; size_t time_ms; void *reserved; } Tok;   /* AprilToken */
+typedef struct {
+    uint64_t *counts; uint64_t calls; int64_t type; int64_t n;
+    const char *tok[72]; float logprob[72]; int32_t flags[72]; uint64_t time_ms[72];
+} Rec;
+size_t rec_size(void) { return sizeof(Rec); }
+void record_handler(void *userdata, int type, size_t count, const Tok *tokens)
+{
+    Rec *r = (Rec *)userdata;
+    uint64_t *c = r->counts;
+    __atomic_fetch_add(&c[0], 1, __ATOMIC_RELAXED);
+    if (type >= 1 && type <= 4) __atomic_fetch_add(&c[type], 1, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&c[5], (uint64_t)count, __ATOMIC_RELAXED);
+    r->calls++;
+    r->type = type;
+    r->n = (int64_t)count;
+    for (size_t i = 0; i < count && i < 72; ++i) {
+        r->tok[i] = tokens[i].token; r->logprob[i] = tokens[i].logprob;
+        r->flags[i] = tokens[i].flags; r->time_ms[i] = tokens[i].time_ms;
+    }
+}
+"""
+REC_DTYPE = [("counts", "u8"), ("calls", "u8"), ("type", "i8"), ("n", "i8"), ("tok", "u8", REC_TOKENS),
+             ("logprob", "f4", REC_TOKENS), ("flags", "i4", REC_TOKENS), ("time_ms", "u8", REC_TOKENS)]
+
+
+class Recorder:
+    """`n` records filled by RECORD_HANDLER_C (built with the host C compiler into a temporary directory)."""
+
+    def __init__(self, n, counts, np):
+        import ctypes as C
+        d = tempfile.mkdtemp(prefix="april_rec_")
+        src, so = os.path.join(d, "rec.c"), os.path.join(d, "rec.so")
+        open(src, "w").write(RECORD_HANDLER_C)
+        subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", src, "-o", so], timeout=60)
+        self._so = C.CDLL(so)
+        self._so.rec_size.restype = C.c_size_t
+        self.rec = np.zeros(n, np.dtype(REC_DTYPE, align=True))
+        if self._so.rec_size() != self.rec.dtype.itemsize:
+            raise RuntimeError("record layout: C %d bytes, numpy %d" % (self._so.rec_size(), self.rec.dtype.itemsize))
+        self.rec["counts"] = counts.ctypes.data
+        self.handler = C.cast(self._so.record_handler, C.c_void_p).value
+
+    def userdata(self, i):
+        return self.rec.ctypes.data + i * self.rec.dtype.itemsize
+
+
+def recording_session(A, model, handler, userdata):
+    """A session whose results go to the C function `handler` with `userdata` (A.Session's `counters` fixes the library's own
+    counting handler)."""
+    import weakref
+    from april_asr_amd import _ffi
+    s = A.Session.__new__(A.Session)
+    s._L, s.model, s.callback, s._raw = model._L, model, None, False
+    cfg = _ffi.AprilConfig()
+    cfg.handler = _ffi.HANDLER(handler)
+    cfg.userdata = userdata
+    s._handle = s._L.aas_create_session(model._handle, cfg)
+    if not s._handle:
+        raise Exception("Failed to create session")
+    if not hasattr(model, "_sessions"):
+        model._sessions = weakref.WeakSet()
+    model._sessions.add(s)
+    return s
+
+
+def dump_outputs(out_dir, model, rec, np):
+    """What the timed path hands its callers, as of the end of the last timed step (every callback of it has been delivered then):
+    per session the latest result -- its type (1 partial, 2 final, 3 can't keep up, 4 silence; 0 = none yet) and its tokens (id,
+    raw joiner logit, flags, emission time; padded with id -1) -- and the number of results delivered during the timed steps.
+    Integers are stored as float64 (exact)."""
+    import ctypes as C
+    tok_addr = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int32)(C.cast(model._L.aprilx_model_token, C.c_void_p).value)
+    ids = {tok_addr(model._handle, i): i for i in range(model.dims.vocab)}
+    n = np.minimum(rec["n"], REC_TOKENS)
+    pad = np.arange(REC_TOKENS)[None, :] >= n[:, None]
+    tid = np.vectorize(lambda a: ids.get(int(a), -2), otypes=[np.float64])(rec["tok"]) if rec.size else np.zeros((0, REC_TOKENS))
+    out = {"result_type": rec["type"].astype(np.float64), "result_token_count": rec["n"].astype(np.float64),
+           "token_id": np.where(pad, -1.0, tid), "token_logit": np.where(pad, 0.0, rec["logprob"]).astype(np.float32),
+           "token_flags": np.where(pad, 0.0, rec["flags"]), "token_time_ms": np.where(pad, 0.0, rec["time_ms"].astype(np.float64)),
+           "callbacks_in_timed_steps": rec["calls"].astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return sorted(out)
 
 
 def config5_leg(args, A, SM, torch, np):
@@ -159,6 +258,12 @@ def main():
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="collective backend for the weight broadcast; gloo (host tensors, ranks may share a GPU) exists to "
                          "exercise the multi-process path on a one-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg (steady series, other ingest, deeper pipeline, roofline, reference-API "
+                         "leg, sweep, offline minute, configs[4], CPU baseline; the --no-* options and --steady-steps / --profile-steps select "
+                         "among them).  Off: the run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write each session's latest result after the last timed step (rank 0's sessions) as DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -303,7 +408,13 @@ def main():
         # one LCG stream per session: seed 12345 + global session id
         return [SM.lcg_pcm16(step_samples * nst, seed=12345 + seed0 + i) for i in range(nsess)]
 
-    sess, grp = make_group(B, rank * B)
+    recorder = None
+    if args.dump_outputs and rank == 0:
+        recorder = Recorder(B, counts, np)
+        sess = [recording_session(A, model, recorder.handler, recorder.userdata(i)) for i in range(B)]
+        grp = A.SessionGroup(sess)
+    else:
+        sess, grp = make_group(B, rank * B)
     pcm = pcm_for(B, n_steps, rank * B)
     if args.pre_roll > 0:                    # set-up: see --pre-roll
         pre = pcm_for(B, args.pre_roll, 50_000_000 + rank * B)
@@ -334,12 +445,17 @@ def main():
 
     run_steps(grp, pcm, 0, args.warmup)
     barrier()
+    if recorder is not None:
+        recorder.rec["calls"] = 0                # (every callback of the warm-up has been delivered: run_steps drains)
     model.feed_latencies(reset=True)
     t0 = time.perf_counter()
     run_steps(grp, pcm, args.warmup, n_steps, step_wall)
     barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    dumped = None
+    if recorder is not None:                     # before the --full legs feed the same sessions again
+        dumped = dump_outputs(args.dump_outputs, model, recorder.rec.copy(), np)
     # hand-over -> delivery latency of every tick of the timed region, stamped inside the library (aprilx_model_feed_latency): in
     # pipelined mode the feed CALL returns as soon as the samples are queued, so its duration is not the latency of a feed
     feed_lat = model.feed_latencies(reset=True)
@@ -353,7 +469,7 @@ def main():
     # is +-5 %): the same sessions keep streaming, `steady_steps` further feeds, per-step wall times on rank 0, the mean as the
     # max over ranks.  Not `value`: that stays the driver's K steps.
     steady = None
-    if args.steady_steps > 0:
+    if args.full and args.steady_steps > 0:
         more_s = pcm_for(B, args.steady_steps, 30_000_000 + rank * B)
         sw = []
         run_steps(grp, more_s, 0, 4)                     # (plan + the first feeds outside the series)
@@ -374,32 +490,34 @@ def main():
         del more_s
         st = model.stats()
     # the other ingest mode on the same sessions, same number of steps (never `value`)
-    other = "lockstep" if args.ingest == "pipelined" else "pipelined"
-    more_o = pcm_for(B, args.steps + 4, 40_000_000 + rank * B)
-    run_steps(grp, more_o, 0, 4, ingest=other)
-    barrier()
-    a = time.perf_counter()
-    ow = []
-    model.feed_latencies(reset=True)
-    run_steps(grp, more_o, 4, args.steps + 4, ow, ingest=other)
-    barrier()
-    el_o = time.perf_counter() - a
-    lat_o = model.feed_latencies(reset=True)
-    if world > 1:
-        tt = torch.tensor([el_o], dtype=torch.float64, device=cdev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        el_o = float(tt.item())
-    other_ingest = {"ingest": other, "steps": args.steps, "ms_per_step": round(el_o / args.steps * 1e3, 3), "rtf": round(el_o / (args.steps * 0.1), 5),
-                    "p50": round(float(np.percentile(ow, 50)) * 1e3, 3),
-                    "feed_latency_ms": None if lat_o.size == 0 else {"p50": round(float(np.percentile(lat_o, 50)), 3), "p99": round(float(np.percentile(lat_o, 99)), 3), "n": int(lat_o.size)},
-                    "what": "the same sessions, %d further feeds through %s" % (
-                        args.steps, "aprilx_feed_many (one blocking call per 100 ms feed: nothing of the next feed can start before the previous one has been delivered)"
-                        if other == "lockstep" else "aprilx_feed_many_pipelined depth 2")}
-    del more_o
+    other_ingest = None
+    if args.full:
+        other = "lockstep" if args.ingest == "pipelined" else "pipelined"
+        more_o = pcm_for(B, args.steps + 4, 40_000_000 + rank * B)
+        run_steps(grp, more_o, 0, 4, ingest=other)
+        barrier()
+        a = time.perf_counter()
+        ow = []
+        model.feed_latencies(reset=True)
+        run_steps(grp, more_o, 4, args.steps + 4, ow, ingest=other)
+        barrier()
+        el_o = time.perf_counter() - a
+        lat_o = model.feed_latencies(reset=True)
+        if world > 1:
+            tt = torch.tensor([el_o], dtype=torch.float64, device=cdev)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            el_o = float(tt.item())
+        other_ingest = {"ingest": other, "steps": args.steps, "ms_per_step": round(el_o / args.steps * 1e3, 3), "rtf": round(el_o / (args.steps * 0.1), 5),
+                        "p50": round(float(np.percentile(ow, 50)) * 1e3, 3),
+                        "feed_latency_ms": None if lat_o.size == 0 else {"p50": round(float(np.percentile(lat_o, 50)), 3), "p99": round(float(np.percentile(lat_o, 99)), 3), "n": int(lat_o.size)},
+                        "what": "the same sessions, %d further feeds through %s" % (
+                            args.steps, "aprilx_feed_many (one blocking call per 100 ms feed: nothing of the next feed can start before the previous one has been delivered)"
+                            if other == "lockstep" else "aprilx_feed_many_pipelined depth 2")}
+        del more_o
     # a deeper hand-over queue on the same sessions (never `value`): with depth 4 the stepping thread finds two feeds queued and steps
     # them as ONE wavefront of five chunks -- fewer, larger launches, one more feed of latency.  Reported so that the trade is visible.
     deeper = None
-    if args.ingest == "pipelined" and args.pipeline_depth < 4:
+    if args.full and args.ingest == "pipelined" and args.pipeline_depth < 4:
         more_d = pcm_for(B, args.steps + 8, 50_000_000 + rank * B)
         run_steps(grp, more_d, 0, 8, depth=4)                   # (the five-chunk wavefront's launch chains are captured here)
         barrier()
@@ -509,7 +627,7 @@ def main():
         return rl, sp_
 
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         roofline, sp = gates_roofline(model, grp, B, st, TRAFFIC_JSON)
     for s in sess:
         s.close()
@@ -520,7 +638,7 @@ def main():
     # handed over per block (an asynchronous session queues at most three, src/audio_provider.c:31), then the client waits for the block
     # (aprilx_session_drain: the only call here that is not one of the 12 symbols -- the reference client would wait for its callbacks).
     ref_api = None
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if rank == 0 and world == 1 and args.full and not args.no_sweep:
         try:
             cnt_a = np.zeros(6, np.uint64)
             sa = [A.Session(model, None, asynchronous=True, no_rt=True, counters=cnt_a) for _ in range(B)]
@@ -580,7 +698,7 @@ def main():
 
     # ---------------- concurrency sweep (outside the timed region): RTF at other batch sizes
     sweep = None
-    if rank == 0 and world == 1 and not args.no_sweep:          # single-GPU runs only (the driver computes scaling from per-N values)
+    if rank == 0 and world == 1 and args.full and not args.no_sweep:          # single-GPU runs only (the driver computes scaling from per-N values)
         sweep = {}
         sweep_runs = {}
         for nb in (1, 16, 64, 1024, 2048, 2304, 2432, 2560, 2816, 3072):
@@ -607,7 +725,7 @@ def main():
     # ---------------- BASELINE configs[1]: one session, 60 s of audio handed over in ONE feed (the reference's ./main use case):
     # long feeds take the layer-major schedule.  The first pass captures the launch chains, the second is timed.
     offline = None
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if rank == 0 and world == 1 and args.full and not args.no_sweep:
         secs = 60.0
         p60 = SM.lcg_pcm16(int(16000 * secs), seed=4321)
         for attempt in range(2):
@@ -634,7 +752,7 @@ def main():
 
     # ---------------- BASELINE configs[4]: larger encoder, 512 sessions, fp16 MFMA path (and the same model in fp32)
     config5 = None
-    if rank == 0 and world == 1 and not args.no_config5:
+    if rank == 0 and world == 1 and args.full and not args.no_config5:
         model.close()
         model = None
         # in a process of its own: the native library reports a failed device allocation or a missing kernel plan with abort(),
@@ -649,7 +767,7 @@ def main():
 
     # ---------------- CPU baseline: the oracle (plain-C port, 1 thread) on the host, bounded sample
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import orc_py as O          # checker/baseline only; never on the measured path
         path = os.environ.get("APRIL_MODEL") or os.path.join(tempfile.gettempdir(), "bench_aprilv0_synth.april")
         om = O.Model(path)
@@ -689,7 +807,12 @@ def main():
             avail_gb = [int(ln.split()[1]) for ln in open("/proc/meminfo") if ln.startswith("MemAvailable")][0] / 1048576.0
         except Exception:
             avail_gb = 64.0
-        k = max(1, min(int(os.environ.get("BENCH_CPU_PROCS", str(os.cpu_count() or 1))), (os.cpu_count() or 1), int(avail_gb / 2.5)))
+        # the CPUs this process may use: its affinity mask, capped by the thread budget OMP_NUM_THREADS (a shared host gives a job a
+        # slice of its CPUs; os.cpu_count() is the whole host's)
+        ncpu = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+        if os.environ.get("OMP_NUM_THREADS", "").isdigit():
+            ncpu = max(1, min(ncpu, int(os.environ["OMP_NUM_THREADS"])))
+        k = max(1, min(int(os.environ.get("BENCH_CPU_PROCS", str(ncpu))), ncpu, int(avail_gb / 2.5)))
         start = os.path.join(tempfile.gettempdir(), "bench_cpu_start_%d" % os.getpid())
         if os.path.exists(start):
             os.remove(start)
@@ -725,7 +848,7 @@ def main():
                                    "100 ms PCM16 feeds via %s (BASELINE configs[2]; configs[3] at 8 GPUs)" % (
                                        B, "aprilx_feed_many_pipelined (depth 2)" if args.ingest == "pipelined" else "aprilx_feed_many (one blocking call per feed)"),
                        "sessions_per_gpu": B, "feed_ms": 100, "params": int(d.param_count), "parallelism": "sessions sharded, dp%d" % world},
-            "rtf": round(rtf, 5), "sessions_total": world * B, "pre_roll_steps": args.pre_roll,
+            "rtf": round(rtf, 5), "sessions_total": world * B, "pre_roll_steps": args.pre_roll, "full": args.full, "dumped_outputs": dumped,
             "ingest": {"mode": args.ingest, "depth": args.pipeline_depth if args.ingest == "pipelined" else 1, "what": "aprilx_feed_many_pipelined, depth 2 by default: feed k + 1 is queued (samples copied) while feed k is on the GPU, every callback "
                                                      "of the K timed feeds is delivered inside the timed region (drain before the closing barrier)"
                        if args.ingest == "pipelined" else "aprilx_feed_many: one blocking call per feed"},

@@ -13,9 +13,14 @@ with the repo, the reference sources do not.
                       (400 = 4 4 5 5, 320 = 4 4 4 5, 480 = 2 4 4 3 5, 200 = 2 4 5 5 at 8 kHz, where the lowest of the 80 mel filters fall between FFT bins;
                       882 = 2 3 3 7 7, 1102 = 2 19 29, 441 = 3 3 7 7, 220 = 4 5 11: pocketfft's generic pass, lengths that are not multiples of 4), and for the 400-point
                       one the whole online fbank on 1 s of the LCG recipe (feed chunks + both flush phases).
+  reference_outputs.json : what the reference gave for the inputs of the reference comparisons in tests/test_oracle_fbank.py
+                      (every chunk array as shape + SHA-256 of its float32 bits) and the struct layout probe of tests/test_abi.py
+                      on the reference's april_api.h.  `make_golden.py reference_outputs` writes this file alone.
 """
+import json
 import os
 import sys
+import tempfile
 
 import numpy as np
 
@@ -24,6 +29,14 @@ sys.path.insert(0, ROOT)
 from oracle import orc_py as O  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def ref_tree():
+    """the reference tree oracle/Makefile compiles from: $REF, else the Makefile's default"""
+    if os.environ.get("REF"):
+        return os.environ["REF"]
+    with open(os.path.join(ROOT, "oracle", "Makefile")) as f:
+        return [ln.split("=", 1)[1].strip() for ln in f if ln.startswith("REF ?=")][0]
 
 
 def to_wave(pcm):
@@ -99,5 +112,33 @@ def main():
     print("wrote goldens:", feed1.shape, len(feed10), len(p1), len(p1) + len(p2), feed10.astype(np.float64).sum(), "| nonpow2", f400.shape, a400.shape, b400.shape)
 
 
+def reference_outputs():
+    assert O.ref_available(), "needs the reference tree (oracle/Makefile REF)"
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_abi as TA
+    import test_oracle_fbank as TF
+
+    def digests(fb_kw, pcm, seg):
+        return [TF.digest(x) for x in TF.run(O.RefFbank(**fb_kw), pcm, seg)]
+    out = {"fbank_chunkings": {"%d/%d" % (seg, seed): digests({}, TF.chunking_pcm(seed), seg) for seg, seed in TF.CHUNKINGS},
+           "fbank_other_geometry": digests(TF.OTHER_GEOMETRY, O.lcg_pcm16_fast(16000, seed=9), 800),
+           "fbank_nonpow2": {TF.geometry_key(kw): digests(kw, TF.nonpow2_pcm(), 1600) for kw in TF.NONPOW2_GEOMETRIES},
+           "fbank_every_frame_length": {}}
+    for n, kw, w in TF.every_frame_length_inputs():
+        fb = O.RefFbank(**kw)
+        fb.accept(w)
+        out["fbank_every_frame_length"][str(n)] = TF.digest(np.array(fb.pull_all()))
+    with tempfile.TemporaryDirectory() as d:
+        out["abi_layout"] = TA.layout_probe(d, ref_tree())
+    with open(os.path.join(HERE, "reference_outputs.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("wrote reference_outputs.json:", {k: len(v) for k, v in out.items()})
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["reference_outputs"]:
+        reference_outputs()
+    else:
+        main()
+        reference_outputs()

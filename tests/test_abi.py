@@ -2,6 +2,7 @@
 layouts and enum values equal the reference ABI (AprilToken 32 B {0,8,12,16,24},
 AprilConfig 40 B {0,16,24,32}; captured from the reference's april_api.h and its ctypes binding)."""
 import ctypes as C
+import json
 import os
 import re
 import subprocess
@@ -62,19 +63,25 @@ def test_struct_layouts_compiled_header(tmp_path):
     assert [int(x) for x in out] == [32, 0, 8, 12, 16, 24, 40, 0, 16, 24, 32, 1, 2, 3, 4, 1, 2, 1, 2, 1]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference tree not present")
+def layout_probe(tmp_dir, inc):
+    """sizes / offsets of AprilToken and AprilConfig as gcc sees the april_api.h under `inc`"""
+    src = os.path.join(str(tmp_dir), "p.c")
+    with open(src, "w") as f:
+        f.write('#include <stdio.h>\n#include <stddef.h>\n#include "april_api.h"\nint main(void){'
+                'printf("%zu %zu %zu %zu %zu %zu %zu %zu", sizeof(AprilToken), offsetof(AprilToken,logprob), offsetof(AprilToken,flags),'
+                ' offsetof(AprilToken,time_ms), sizeof(AprilConfig), offsetof(AprilConfig,handler), offsetof(AprilConfig,userdata),'
+                ' offsetof(AprilConfig,flags)); return 0;}\n')
+    exe = os.path.join(str(tmp_dir), "p")
+    subprocess.check_call(["gcc", "-I", inc, src, "-o", exe])
+    return subprocess.check_output([exe]).decode()
+
+
 def test_layout_equals_reference_header(tmp_path):
-    """Same probe against the reference's own april_api.h: identical numbers."""
-    def probe(inc):
-        src = tmp_path / "p.c"
-        src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "april_api.h"\nint main(void){'
-                       'printf("%zu %zu %zu %zu %zu %zu %zu %zu", sizeof(AprilToken), offsetof(AprilToken,logprob), offsetof(AprilToken,flags),'
-                       ' offsetof(AprilToken,time_ms), sizeof(AprilConfig), offsetof(AprilConfig,handler), offsetof(AprilConfig,userdata),'
-                       ' offsetof(AprilConfig,flags)); return 0;}\n')
-        exe = tmp_path / "p"
-        subprocess.check_call(["gcc", "-I", inc, str(src), "-o", str(exe)])
-        return subprocess.check_output([str(exe)]).decode()
-    assert probe(os.path.join(ROOT, "include")) == probe("/root/reference")
+    """Same probe as the reference's own april_api.h gave (tests/golden/reference_outputs.json, tests/golden/make_golden.py):
+    identical numbers."""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_outputs.json")) as f:
+        want = json.load(f)["abi_layout"]
+    assert layout_probe(tmp_path, os.path.join(ROOT, "include")) == want
 
 
 def test_fails_loudly_without_gpu(built, tiny_model, capfd):

@@ -25,7 +25,7 @@ def free_port():
 def test_bench_two_ranks_on_one_gpu(built, v0_model):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--sessions", "16",
-           "--steps", "3", "--warmup", "2", "--no-sweep", "--no-cpu-baseline", "--no-config5", "--steady-steps", "12", "--profile-steps", "2"]
+           "--steps", "3", "--warmup", "2", "--full", "--no-sweep", "--no-cpu-baseline", "--no-config5", "--steady-steps", "12", "--profile-steps", "2"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0", APRIL_MODEL=v0_model["path"],
                APRIL_MAX_SESSIONS="64", APRIL_MAX_BATCH="256")
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)

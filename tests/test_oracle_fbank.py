@@ -1,6 +1,9 @@
 """Pins the fbank oracle (oracle/orc_fbank.c): bit-exact against the committed golden vectors
-(generated from the reference's compiled fbank.c/pocketfft.c by tests/golden/make_golden.py) and,
-where /root/reference exists, against the compiled reference itself on more chunkings."""
+(generated from the reference's compiled fbank.c/pocketfft.c by tests/golden/make_golden.py), and on
+more chunkings and geometries against the digests of what the compiled reference produced for the
+same inputs (tests/golden/reference_outputs.json, same script)."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -33,6 +36,17 @@ def run(fb, pcm, seg):
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def digest(a):
+    """shape + SHA-256 of the float32 bits (the reference's outputs are stored this way)"""
+    a = np.ascontiguousarray(a, np.float32)
+    return "x".join(map(str, a.shape)) + ":" + hashlib.sha256(a.view(np.uint32).tobytes()).hexdigest()[:32]
+
+
+def reference_outputs(key):
+    with open(os.path.join(G, "reference_outputs.json")) as f:
+        return json.load(f)[key]
 
 
 def test_golden_lcg_chunks(built):
@@ -75,27 +89,26 @@ def test_chunking_invariance(built, seg):
         assert np.array_equal(bits(x), bits(y))
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="compiled reference (oracle/_ref) not present")
-@pytest.mark.parametrize("seg,seed", [(3200, 1), (1600, 2), (512, 3), (100, 4), (48000, 5)])
-def test_against_compiled_reference(built, seg, seed):
+CHUNKINGS = [(3200, 1), (1600, 2), (512, 3), (100, 4), (48000, 5)]
+OTHER_GEOMETRY = dict(rate=8000, nbins=40, seg_count=9, seg_step=4)
+
+
+def chunking_pcm(seed):
     rng = np.random.RandomState(seed)
-    pcm = np.concatenate([O.lcg_pcm16_fast(20000, seed=seed), np.zeros(3000, np.int16),
-                          rng.randint(-2000, 2000, size=9000).astype(np.int16)])
-    a = run(O.OrcFbank(), pcm, seg)
-    b = run(O.RefFbank(), pcm, seg)
-    for x, y in zip(a, b):
-        assert x.shape == y.shape and np.array_equal(bits(x), bits(y))
+    return np.concatenate([O.lcg_pcm16_fast(20000, seed=seed), np.zeros(3000, np.int16),
+                           rng.randint(-2000, 2000, size=9000).astype(np.int16)])
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="compiled reference (oracle/_ref) not present")
+@pytest.mark.parametrize("seg,seed", CHUNKINGS)
+def test_against_compiled_reference(built, seg, seed):
+    a = run(O.OrcFbank(), chunking_pcm(seed), seg)
+    assert [digest(x) for x in a] == reference_outputs("fbank_chunkings")["%d/%d" % (seg, seed)]
+
+
 def test_other_geometry_against_reference(built):
     """8 kHz (256-point FFT: factors 4,4,4,4) and 40 mel bins."""
-    kw = dict(rate=8000, nbins=40, seg_count=9, seg_step=4)
-    pcm = O.lcg_pcm16_fast(16000, seed=9)
-    a = run(O.OrcFbank(**kw), pcm, 800)
-    b = run(O.RefFbank(**kw), pcm, 800)
-    for x, y in zip(a, b):
-        assert x.shape == y.shape and np.array_equal(bits(x), bits(y))
+    a = run(O.OrcFbank(**OTHER_GEOMETRY), O.lcg_pcm16_fast(16000, seed=9), 800)
+    assert [digest(x) for x in a] == reference_outputs("fbank_other_geometry")
 
 
 # ------------------------------------------------------------------ round_pow2 = 0: the FFT length is the frame length
@@ -127,22 +140,29 @@ def test_golden_nonpow2_online_400(built):
         assert np.array_equal(bits(p1), bits(g["n400_flush1_1s"])) and np.array_equal(bits(p2), bits(g["n400_flush2_1s"]))
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="compiled reference (oracle/_ref) not present")
-@pytest.mark.parametrize("kw", [dict(round_pow2=0), dict(round_pow2=0, len_ms=20), dict(round_pow2=0, len_ms=30), dict(round_pow2=0, len_ms=10),
-                                dict(round_pow2=0, len_ms=15), dict(round_pow2=0, rate=8000, nbins=40), dict(round_pow2=0, rate=48000, nbins=80),
-                                dict(round_pow2=0, rate=8000, len_ms=30, nbins=23),
-                                dict(round_pow2=0, rate=44100, len_ms=20), dict(round_pow2=0, rate=44100), dict(round_pow2=0, rate=44100, len_ms=10),
-                                dict(round_pow2=0, rate=22050, len_ms=10), dict(round_pow2=0, rate=22050), dict(round_pow2=0, rate=11025, nbins=40),
-                                dict(round_pow2=0, rate=32000, len_ms=11), dict(round_pow2=0, len_ms=13)])
+NONPOW2_GEOMETRIES = [dict(round_pow2=0), dict(round_pow2=0, len_ms=20), dict(round_pow2=0, len_ms=30), dict(round_pow2=0, len_ms=10),
+                      dict(round_pow2=0, len_ms=15), dict(round_pow2=0, rate=8000, nbins=40), dict(round_pow2=0, rate=48000, nbins=80),
+                      dict(round_pow2=0, rate=8000, len_ms=30, nbins=23),
+                      dict(round_pow2=0, rate=44100, len_ms=20), dict(round_pow2=0, rate=44100), dict(round_pow2=0, rate=44100, len_ms=10),
+                      dict(round_pow2=0, rate=22050, len_ms=10), dict(round_pow2=0, rate=22050), dict(round_pow2=0, rate=11025, nbins=40),
+                      dict(round_pow2=0, rate=32000, len_ms=11), dict(round_pow2=0, len_ms=13)]
+
+
+def nonpow2_pcm():
+    return np.concatenate([O.lcg_pcm16_fast(20000, seed=5), np.zeros(1500, np.int16)])
+
+
+def geometry_key(kw):
+    return ",".join("%s=%s" % (k, kw[k]) for k in sorted(kw))
+
+
+@pytest.mark.parametrize("kw", NONPOW2_GEOMETRIES)
 def test_nonpow2_against_compiled_reference(built, kw):
     """FFT lengths 400, 320, 480, 160, 240, 200, 1200, 240 (8 kHz): every factor list of 4 / 2 / 3 / 5 that frame lengths produce; then
     882 = 2 3 3 7 7, 1102 = 2 19 29, 441 = 3 3 7 7 (odd), 220 = 4 5 11, 551 = 19 29 (odd), 275 = 5 5 11 (odd), 352 = 2 4 4 11, 208 = 4 4 13:
     pocketfft's generic pass and its three twiddle constructions (n mod 4 = 0, 2, odd)."""
-    pcm = np.concatenate([O.lcg_pcm16_fast(20000, seed=5), np.zeros(1500, np.int16)])
-    a = run(O.OrcFbank(**kw), pcm, 1600)
-    b = run(O.RefFbank(**kw), pcm, 1600)
-    for x, y in zip(a, b):
-        assert x.shape == y.shape and np.array_equal(bits(x), bits(y))
+    a = run(O.OrcFbank(**kw), nonpow2_pcm(), 1600)
+    assert [digest(x) for x in a] == reference_outputs("fbank_nonpow2")[geometry_key(kw)]
 
 
 def test_unsupported_fft_lengths_are_refused(built):
@@ -163,26 +183,29 @@ def test_unsupported_fft_lengths_are_refused(built):
         L.orc_fbank_free(h)
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="compiled reference (oracle/_ref) not present")
+def every_frame_length_inputs():
+    """(frame length n, fbank keywords, waveform) for n = 8 .. 1299"""
+    rng = np.random.RandomState(3)
+    for n in range(8, 1300):
+        yield n, dict(round_pow2=0, rate=40 * n, nbins=23), wave(rng.randint(-20000, 20000, size=n + 8 * (40 * n // 100)).astype(np.int16))
+
+
 def test_every_frame_length_against_compiled_reference(built):
     """round_pow2 = 0 with every frame length 8 .. 1299 (sample rate 40 n, 25 ms): wherever the oracle takes the length (whatever
     pocketfft runs through its radix passes: 1034 lengths, every factor list and all three twiddle constructions) its frames equal the
     compiled reference's bit for bit; the rest (258 lengths: primes from 191 and their small multiples) are the ones its restatement of
     make_rfft_plan's choice hands to Bluestein -- refused, never approximated."""
-    rng = np.random.RandomState(3)
+    want = reference_outputs("fbank_every_frame_length")
     same, refused = 0, []
-    for n in range(8, 1300):
-        kw = dict(round_pow2=0, rate=40 * n, nbins=23)
-        w = wave(rng.randint(-20000, 20000, size=n + 8 * (40 * n // 100)).astype(np.int16))
+    for n, kw, w in every_frame_length_inputs():
         try:
             a = O.OrcFbank(**kw)
         except Exception:
             refused.append(n)
             continue
-        b = O.RefFbank(**kw)
-        a.accept(w); b.accept(w)
-        x, y = np.array(a.pull_all()), np.array(b.pull_all())
-        assert x.shape == y.shape and x.size and np.array_equal(bits(x), bits(y)), n
+        a.accept(w)
+        x = np.array(a.pull_all())
+        assert x.size and digest(x) == want[str(n)], n
         same += 1
     assert same > 1000 and len(refused) < 300 and min(refused) > 150
     # a refused length has a prime factor above its square root (pocketfft.c:2162) -- necessary, not sufficient (the cost comparison decides)
