@@ -153,6 +153,14 @@ void orc_session_set_logit_trace(OrcSession *s, float *buf, size_t cap_floats, s
 void orc_session_set_chunk_trace(OrcSession *s, float *buf, size_t cap_floats, size_t *used_floats);
 uint64_t orc_session_chunks(const OrcSession *s);
 
+/* ---------------- input sample-rate conversion (orc_resample.c) ---------------- */
+/* One whole segment x[n] through the phase table taps[L][ldt]: writes ceil(n L / M) outputs to y (when not NULL) and returns
+   their count, -1 on bad arguments.  acc_out (optional): the sum before rounding; abs_out (optional): sum_i |tap x| in double.
+   variant: 0 the contract (fp32 fmaf chain in increasing tap order); tests only: 1 reversed order, 2 unfused fp32 multiply-add,
+   3 two interleaved partial sums, 4 float64 accumulator. */
+int64_t orc_resample(const float *taps, int L, int M, int K, int ldt, const int16_t *x, int64_t n, int variant,
+                     int16_t *y, double *acc_out, double *abs_out);
+
 #ifdef __cplusplus
 }
 #endif

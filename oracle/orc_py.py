@@ -31,6 +31,38 @@ def build(force=False):
         subprocess.check_call(["make", "-C", HERE, "ref"], stdout=subprocess.DEVNULL)
 
 
+def resample_lmk(in_rate, out_rate):
+    """(L, M, K) of the conversion in_rate -> out_rate by the contract's formulas, whether or not the library
+    accepts it: g = gcd, L = R_o / g, M = R_i / g, K = ceil(320 R_i / (9 min(R_i, R_o))); (1, 1, 0) for equal rates"""
+    if in_rate == out_rate:
+        return 1, 1, 0
+    g = int(np.gcd(in_rate, out_rate))
+    return out_rate // g, in_rate // g, -((-320 * in_rate) // (9 * min(in_rate, out_rate)))
+
+
+def resample(taps, in_rate, out_rate, x, variant=0, acc=False):
+    """One whole segment of int16 `x` at in_rate converted to out_rate by the contract (orc_resample.c) with the phase table `taps`
+    [L][2K] (aprilx_resampler_taps).  Returns y (int16, ceil(n L / M) outputs), or (y, sum before rounding, sum |tap x|) with acc.
+    variant: 0 the contract; 1-4 deliberately different summations (tests only, see orc.h)."""
+    L, M, K = resample_lmk(in_rate, out_rate)
+    t = np.ascontiguousarray(taps, np.float32)
+    if t.shape != (L, 2 * K):
+        raise ValueError("phase table of shape %s for (L, M, K) = %s" % (t.shape, (L, M, K)))
+    if K == 0:
+        xi = np.array(x, np.int16).ravel()
+        return (xi, xi.astype(np.float64), np.abs(xi.astype(np.float64))) if acc else xi
+    xs = np.ascontiguousarray(x, np.int16).ravel()
+    n_out = (xs.size * L + M - 1) // M
+    y = np.zeros(max(n_out, 1), np.int16)
+    a = np.zeros(max(n_out, 1), np.float64) if acc else None
+    b = np.zeros(max(n_out, 1), np.float64) if acc else None
+    got = lib().orc_resample(t.ctypes.data, L, M, K, 2 * K, xs.ctypes.data, xs.size, int(variant), y.ctypes.data,
+                             a.ctypes.data if acc else None, b.ctypes.data if acc else None)
+    if got != n_out:
+        raise RuntimeError("orc_resample returned %d, expected %d" % (got, n_out))
+    return (y[:n_out], a[:n_out], b[:n_out]) if acc else y[:n_out]
+
+
 class OrcToken(C.Structure):
     _fields_ = [("id", C.c_int32), ("logprob", C.c_float), ("flags", C.c_int32), ("time_ms", C.c_uint64)]
 
@@ -115,6 +147,9 @@ def lib():
         L.orc_session_set_chunk_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.orc_session_chunks.restype = C.c_uint64
         L.orc_session_chunks.argtypes = [C.c_void_p]
+        L.orc_resample.restype = C.c_int64
+        L.orc_resample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

@@ -134,7 +134,7 @@ EQUIVALENT = [
 def build_objects(tmp):
     """the oracle's other translation units, compiled once"""
     objs = []
-    for f in ("orc_fbank.c", "orc_file.c", "orc_onnx.c"):
+    for f in ("orc_fbank.c", "orc_file.c", "orc_onnx.c", "orc_resample.c"):
         o = os.path.join(tmp, f[:-2] + ".o")
         subprocess.check_call(["gcc"] + CFLAGS + ["-I", ORACLE, "-c", os.path.join(ORACLE, f), "-o", o])
         objs.append(o)

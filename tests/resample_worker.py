@@ -1,7 +1,9 @@
 """Worker for tests/test_gpu_resample.py: sessions with an input rate of their own (aprilx_session_set_input_rate) and the device
 resampler (aprilx_resample), one scenario per process.  Prints one line "RESULT <json>".
-usage: resample_worker.py model.april mode [rate]
-modes: kernel | equiv RATE | group | long | async | rules"""
+usage: resample_worker.py model.april mode [rate ...]
+modes: kernel | exact RATE... | equiv RATE | edges RATE | extremes | group | long | async | rules
+
+The conversion's expected output comes from the CPU model of the contract (oracle/orc_resample.c), never from the device kernel."""
 import hashlib
 import json
 import os
@@ -15,8 +17,71 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import april_asr_amd as A  # noqa: E402
 from conftest import speech_like_pcm  # noqa: E402
+from oracle import orc_py as O  # noqa: E402
 
 RATES = [8000, 11025, 22050, 32000, 44100, 48000, 96000]
+
+# bit-exact kernel matrix: model rate -> input rates.  16204 Hz at 16 kHz: L = 4000 > 1 with 2K = 78, not a multiple of 4 (the
+# scalar tail behind the float4 loop); 4004 / 383996 Hz: L = 4000 (the largest phase tables); 384000 Hz: K = 854 (the longest
+# chains); 328000 Hz at 8 kHz: 16 288 LDS floats, the largest span resample_plan accepts
+EXACT_MATRIX = {16000: [4000, 4004, 8000, 11025, 12000, 16204, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 192000, 383996, 384000],
+                44100: [8000, 16000, 48000, 384000],
+                8000: [16000, 48000, 328000]}
+EXACT_CONTENTS = ["noise", "square", "min", "max", "first", "last", "speech"]
+LONG_SECONDS = 3.0
+
+
+def exact_lengths(rate, sr):
+    """segment lengths of the bit-exact matrix: 0, 1, K - 1, K, K + 1, 2K, the lengths whose output count is (the nearest count
+    reachable to) 255, 256, 257, 511, 512, 513 -- the edges of the kernel's 256-output blocks -- and one long segment"""
+    L, M, K = O.resample_lmk(rate, sr)
+    ns = [0, 1, K - 1, K, K + 1, 2 * K] + [c * M // L for c in (255, 256, 257, 511, 512, 513)] + [int(LONG_SECONDS * rate)]
+    return sorted(set(n for n in ns if n >= 0))
+
+
+def exact_content(kind, n, seed, rate):
+    """int16 segment of n samples at `rate`: full-scale noise (half of it at the rails: the filtered sum clamps on both sides), a full-scale
+    square wave, constant -32768 / 32767, a single full-scale impulse at the first / last sample (the zero padding at either
+    segment edge), speech-like PCM"""
+    rng = np.random.RandomState(seed)
+    if kind == "noise":
+        # each value held for rate // 4000 samples: the noise keeps its power below 2 kHz, inside every passband, however far the
+        # input rate lies above the model's
+        hold = max(1, rate // 4000)
+        m = -(-n // hold)
+        x = rng.randint(-32768, 32768, size=m)
+        rails = rng.rand(m) < 0.5
+        x[rails] = np.where(rng.rand(int(rails.sum())) < 0.5, -32768, 32767)
+        return np.repeat(x, hold)[:n].astype(np.int16)
+    if kind == "square":
+        period = 2 * (7 + seed % 23)
+        return np.where((np.arange(n) // (period // 2)) % 2 == 0, 32767, -32768).astype(np.int16)
+    if kind in ("min", "max"):
+        return np.full(n, -32768 if kind == "min" else 32767, np.int16)
+    if kind in ("first", "last"):
+        x = np.zeros(n, np.int16)
+        if n:
+            x[0 if kind == "first" else n - 1] = -32768 if seed % 2 else 32767
+        return x
+    return speech_like_pcm(n / float(rate) + 0.01, seed=seed, rate=rate)[:n] * 2 if n else np.zeros(0, np.int16)
+
+
+def exact_cases(rate, sr):
+    """(length, content, samples) of the bit-exact kernel test at one (input rate, model rate) pair: every content at every short
+    length, noise and speech on the long segment"""
+    long_n = int(LONG_SECONDS * rate)
+    for n in exact_lengths(rate, sr):
+        for kind in EXACT_CONTENTS:
+            if n == long_n and kind not in ("noise", "speech"):
+                continue
+            yield n, kind, exact_content(kind, n, seed=(rate * 31 + n * 7 + EXACT_CONTENTS.index(kind)) % (2 ** 31), rate=rate)
+
+
+def oracle_resample(x, rate, sr):
+    """the segment converted by the CPU model of the contract with the library's exported table"""
+    if rate == sr:
+        return np.array(x, np.int16)
+    return O.resample(A.resampler_taps(rate, sr)[3], rate, sr, x)
 
 
 def reference(x, rate, out_rate):
@@ -109,16 +174,51 @@ def mode_kernel(m, sr):
     return out
 
 
-def equiv_ops(m, rate, sr):
+def mode_exact(m, sr, rates):
+    """the device kernel (aprilx_resample) against the CPU model of the contract, every output bit, over exact_cases; and the
+    entry point's edges: n = 0, a cap one below the output count (refused, buffer untouched), a refused rate"""
+    out = {}
+    for rate in rates:
+        L, M, K, taps = A.resampler_taps(rate, sr)
+        cases = []
+        for n, kind, x in exact_cases(rate, sr):
+            want = O.resample(taps, rate, sr, x)
+            got = m.resample(x, rate)
+            same = got.size == want.size
+            diff = int((got != want).sum()) if same else -1
+            clamp = (int((want == -32768).sum()), int((want == 32767).sum()))
+            cases.append([n, kind, int(want.size), int(got.size), diff, clamp[0], clamp[1]])
+        # aprilx_resample's edges
+        Lb = m._L
+        x = exact_content("noise", 4 * K + 3, seed=rate, rate=rate)
+        n_out = -((-x.size * L) // M)
+        buf = np.full(n_out + 8, 12345, np.int16)
+        e = dict(zero=int(Lb.aprilx_resample(m._handle, rate, x.ctypes.data, 0, buf.ctypes.data, buf.size)),
+                 short_cap=int(Lb.aprilx_resample(m._handle, rate, x.ctypes.data, x.size, buf.ctypes.data, n_out - 1)),
+                 untouched=bool((buf == 12345).all()),
+                 exact_cap=int(Lb.aprilx_resample(m._handle, rate, x.ctypes.data, x.size, buf.ctypes.data, n_out)),
+                 n_out=int(n_out))
+        e["exact_cap_equal"] = bool((buf[:n_out] == O.resample(taps, rate, sr, x)).all() and (buf[n_out:] == 12345).all())
+        out[str(rate)] = dict(lmk=[L, M, K], cases=cases, edges=e)
+    refused = 383996 if sr == 44100 else (336000 if sr == 8000 else 4001)
+    x = exact_content("noise", 1000, seed=1, rate=sr)
+    buf = np.zeros(1000, np.int16)
+    out["refused"] = [refused, int(m._L.aprilx_resample(m._handle, refused, x.ctypes.data, x.size, buf.ctypes.data, buf.size))]
+    return out
+
+
+def equiv_ops(m, rate, sr, segments=None):
     """A: the session at `rate`, random feed sizes (1-sample feeds included), flush, a second segment, flush.  B: the default session
-    fed after each of A's feeds exactly the model-rate samples that became available there (aprilx_resample of the segment cut by the
-    availability rule), with the same flush points."""
+    fed after each of A's feeds exactly the model-rate samples that became available there (the CPU model's conversion of the whole
+    segment cut by the availability rule), with the same flush points."""
     L, M, K, _ = A.resampler_taps(rate, sr)
-    rng = np.random.RandomState(rate)
+    rng = np.random.RandomState(rate % (2 ** 31))
     sizes = [1, 1, 2, 7, 160, rate // 50, rate // 10, rate // 10, rate // 4, rate // 2]
     ops_a, ops_b = [], []
-    for seg in (speech_like_pcm(2.6, seed=1, rate=rate), speech_like_pcm(1.7, seed=2, rate=rate)):
-        y = m.resample(seg, rate)
+    if segments is None:
+        segments = (speech_like_pcm(2.6, seed=1, rate=rate), speech_like_pcm(1.7, seed=2, rate=rate))
+    for seg in segments:
+        y = oracle_resample(seg, rate, sr)
         pos = given = 0
         while pos < seg.size:
             piece = seg[pos: pos + int(rng.choice(sizes))]
@@ -128,13 +228,14 @@ def equiv_ops(m, rate, sr):
             ops_b.append(y[given:av])
             given = av
         ops_a.append(None)
-        ops_b.append(y[given:])
+        if seg.size:                # (an empty feed still opens a segment, as in the reference: B feeds only where A did)
+            ops_b.append(y[given:])
         ops_b.append(None)
     return ops_a, ops_b
 
 
-def mode_equiv(m, sr, rate):
-    ops_a, ops_b = equiv_ops(m, rate, sr)
+def mode_equiv(m, sr, rate, segments=None):
+    ops_a, ops_b = equiv_ops(m, rate, sr, segments)
     a = Run(m, rate).play(ops_a)
     b = Run(m).play(ops_b)
     fa, fb = a.s.frames(), b.s.frames()
@@ -142,7 +243,56 @@ def mode_equiv(m, sr, rate):
     return dict(events_equal=a.ev == b.ev, n_events=len(a.ev), n_tokens=sum(len(t) for _, t in a.ev),
                 frames_equal=bool(fa.shape == fb.shape and (fa.view(np.uint32) == fb.view(np.uint32)).all()), n_frames=int(fa.shape[0]),
                 logits_equal=bool(la.shape == lb.shape and (la.view(np.uint32) == lb.view(np.uint32)).all()), n_logits=int(la.shape[0]),
+                n_frames_default=int(fb.shape[0]), n_logits_default=int(lb.shape[0]),
                 feeds=len(ops_a), rate=a.s.input_rate)
+
+
+def mode_edges(m, sr, rate):
+    """segments that stress FrameBook's framing and compaction: one shorter than K (5 samples), an empty one (two flushes in a row),
+    one of a single sample, and segments whose flush falls inside a filterbank window (lengths that are no multiple of the frame
+    shift at either rate), so that one window is filled from two descriptors and the zeros behind the first segment"""
+    def seg(seconds, seed):
+        return speech_like_pcm(seconds, seed=seed, rate=rate)
+    segments = [seg(0.01, 21)[:5], np.zeros(0, np.int16), seg(0.01, 22)[:1], seg(0.6, 23)[: int(0.6 * rate) - 3],
+                seg(0.01, 24)[:5], seg(1.3, 25)[: int(1.3 * rate) + 7], np.zeros(0, np.int16), seg(0.4, 26)[: int(0.4 * rate) - 1]]
+    return mode_equiv(m, sr, rate, segments)
+
+
+EXTREME_RATES = [4000, 4004, 384000, 383996, None, 48000]
+
+
+def mode_extremes(m, sr):
+    """one pipelined group whose sessions are at the extreme rates (the largest phase tables, the longest chains, upsampling with a
+    small L, a default session) mixed in one launch -- lds_floats is the maximum over descriptors of different (L, M, K) while every
+    block sizes its own span: each session gives the callbacks, feature rows and logits of the default session fed the CPU model's
+    conversion as it becomes available"""
+    n, steps = 2 * len(EXTREME_RATES), 12
+    rates = [EXTREME_RATES[i % len(EXTREME_RATES)] for i in range(n)]
+    pcm = [speech_like_pcm(1.2, seed=300 + i, rate=r or sr) for i, r in enumerate(rates)]
+    step = [(r or sr) // 10 for r in rates]
+    runs = [Run(m, r) for r in rates]
+    grp = A.SessionGroup([r.s for r in runs])
+    for k in range(steps):
+        grp.feed_pipelined([pcm[i][k * step[i]:(k + 1) * step[i]] for i in range(n)], 2)
+    grp.drain()
+    grp.flush()
+    grp.drain()
+    equal = []
+    for i, r in enumerate(rates):
+        rate = r or sr
+        seg = pcm[i][: steps * step[i]]
+        y = oracle_resample(seg, rate, sr)
+        L, M, K = O.resample_lmk(rate, sr)
+        ops, given = [], 0
+        for k in range(steps):
+            av = avail((k + 1) * step[i], L, M, K) if r not in (None, sr) else (k + 1) * step[i]
+            ops.append(y[given:av])
+            given = av
+        ops += [y[given:], None]
+        b = Run(m).play(ops)
+        equal.append(runs[i].digest() == b.digest())
+    return dict(rates=[r or 0 for r in rates], equal=equal, n_events=[len(r.ev) for r in runs],
+                n_frames=[int(r.s.frames().shape[0]) for r in runs])
 
 
 GROUP_RATES = [None, 16000, 8000, 22050, 44100, 48000, 11025, 32000]
@@ -265,8 +415,14 @@ def main():
     sr = int(m.dims.sample_rate)
     if mode == "kernel":
         res = mode_kernel(m, sr)
+    elif mode == "exact":
+        res = mode_exact(m, sr, [int(r) for r in sys.argv[3:]])
     elif mode == "equiv":
         res = mode_equiv(m, sr, int(sys.argv[3]))
+    elif mode == "edges":
+        res = mode_edges(m, sr, int(sys.argv[3]))
+    elif mode == "extremes":
+        res = mode_extremes(m, sr)
     else:
         res = dict(group=mode_group, long=mode_long, asynchronous=mode_async, rules=mode_rules)[mode](m, sr)
     print("RESULT " + json.dumps(res), flush=True)

@@ -6,7 +6,11 @@ import pytest
 import april_asr_amd as A
 
 TO_16K = [8000, 11025, 22050, 32000, 44100, 48000, 96000]
-PAIRS = [(r, 16000) for r in TO_16K] + [(48000, 44100)]
+# the edges of the accepted space: upsampling with a small L (4000, 12000 Hz), L = 4000 (4004, 16204, 383996 Hz: the largest phase
+# tables), K = 854 (384000 Hz), model rates other than 16 kHz, and 328000 Hz at an 8 kHz model (the largest LDS span accepted)
+EDGE_PAIRS = [(4000, 16000), (4004, 16000), (12000, 16000), (16204, 16000), (383996, 16000), (384000, 16000),
+              (8000, 44100), (16000, 44100), (384000, 44100), (16000, 8000), (48000, 8000), (328000, 8000)]
+PAIRS = [(r, 16000) for r in TO_16K] + [(48000, 44100)] + EDGE_PAIRS
 
 
 def contract_lmk(ri, ro):
@@ -48,7 +52,8 @@ def test_worked_numbers(built):
     assert A.resampler_taps(16000, 16000)[:3] == (1, 1, 0)        # no conversion
 
 
-@pytest.mark.parametrize("ri,ro", [(0, 16000), (3999, 16000), (384001, 16000), (4001, 16000), (383999, 16000)])
+@pytest.mark.parametrize("ri,ro", [(0, 16000), (3999, 16000), (384001, 16000), (4001, 16000), (383999, 16000),
+                                   (336000, 8000), (383996, 44100)])
 def test_refused(built, ri, ro):
     from april_asr_amd import _ffi
     lmk = np.zeros(3, np.int32)
@@ -76,6 +81,21 @@ def test_response(built, ri, ro):
     for p in range(0, L, max(1, L // 8)):
         g = np.abs(np.exp(-2j * np.pi * fp[:, None] * tau[p][None, :]) @ t[p])
         assert np.abs(20 * np.log10(g)).max() <= 0.01, (p, np.abs(20 * np.log10(g)).max())
-    fs = np.linspace(ny, L * ri / 2.0, 2048)
-    h = np.abs(np.exp(-2j * np.pi * fs[:, None] * tau.ravel()[None, :]) @ t.ravel()) / L
+    if t.size <= 100000:
+        fs = np.linspace(ny, L * ri / 2.0, 2048)
+        tr, taur = t.ravel(), tau.ravel()
+        h = np.zeros(fs.size, np.complex128)
+        for c in range(0, tr.size, 16384):          # (in pieces of taps: the same sum, a bounded matrix)
+            h += np.exp(-2j * np.pi * fs[:, None] * taur[None, c:c + 16384]) @ tr[c:c + 16384]
+        h = np.abs(h) / L
+    else:
+        # L = 4000: the prototype's taps sit on the grid m / (L R_i), m = p + L (K - 1 - i); its response on a zero-padded FFT
+        # grid (spacing below 100 Hz), every bin from the lower Nyquist frequency to L R_i / 2
+        proto = np.zeros(2 * L * K)
+        m = np.arange(L)[:, None] + L * (K - 1 - np.arange(2 * K))[None, :] + L * K
+        proto[m.ravel()] = t.ravel()
+        nfft = 1 << int(np.ceil(np.log2(max(proto.size, L * ri / 100.0))))
+        spec = np.abs(np.fft.rfft(proto, nfft)) / L
+        f = np.arange(spec.size) * (L * ri / float(nfft))
+        h = spec[f >= ny]
     assert 20 * np.log10(h.max()) <= -85.0, 20 * np.log10(h.max())
