@@ -15,6 +15,7 @@
 #include "../../include/april_api.h"
 #include "../../include/aprilx_engine.h"
 #include "common.h"
+#include "env.h"
 #include "session.h"
 #include "rccl_group.h"
 
@@ -29,12 +30,6 @@ namespace {
 bool g_inited = false;
 int g_client_version = 0;
 std::vector<int> g_devices;
-
-int env_int(const char *name, int def)
-{
-    const char *v = getenv(name);
-    return v && *v ? atoi(v) : def;
-}
 
 #define RCCL_TRY(expr)                                                                     \
     do {                                                                                   \
@@ -141,7 +136,7 @@ bool create_engines(Model &m, const float *blob_host, const float *blob_device)
     cfg.max_slots = env_int("APRIL_MAX_SESSIONS", 4096);
     // rows of the work buffers = sessions x chunks stepped together (a 100 ms feed of 2048 sessions is 3 x 2048 rows); < 1 GB at 8192
     cfg.max_batch = std::max(1, env_int("APRIL_MAX_BATCH", 8192));
-    if (const char *pv = getenv("APRIL_PRECISION")) {
+    if (const char *pv = env_str("APRIL_PRECISION")) {
         const std::string v(pv);
         if (v == "f16" || v == "fp16" || v == "half") cfg.precision = 1;
         else if (!(v.empty() || v == "f32" || v == "fp32")) { LOGE("aam: APRIL_PRECISION must be f32 or f16 (got '%s')", pv); return false; }
@@ -264,7 +259,7 @@ void aam_api_init(int version)
 {
     if (env_int("APRIL_BACKTRACE", 0)) { signal(SIGSEGV, crash_backtrace); signal(SIGABRT, crash_backtrace); }   // debugging aid
     g_client_version = version;                       // stored, never checked (reference src/init.c:34)
-    if (const char *lv = getenv("APRIL_LOG_LEVEL")) {
+    if (const char *lv = env_str("APRIL_LOG_LEVEL")) {
         static const char *names[5] = {"DEBUG", "INFO", "WARNING", "ERROR", "NONE"};
         for (int i = 0; i < 5; ++i) if (strcmp(lv, names[i]) == 0) g_loglevel = i;
     }
@@ -275,7 +270,7 @@ void aam_api_init(int version)
         g_inited = false;
         return;
     }
-    if (const char *dv = getenv("APRIL_GPU_DEVICES")) {
+    if (const char *dv = env_str("APRIL_GPU_DEVICES")) {
         std::stringstream ss(dv); std::string item;
         while (std::getline(ss, item, ',')) if (!item.empty()) { int d = atoi(item.c_str()); if (d >= 0 && d < count) g_devices.push_back(d); }
     }
@@ -489,7 +484,7 @@ AprilASRModel aprilx_model_load_blob(const char *path)
     if (buf.size() >= sizeof(BlobHeader) && memcmp(buf.data(), "APXBL16B", 8) == 0) {
         // expand to the fp32 blob; only the fp16-operand engine may use the rounded matrices
         if (g_inited) {
-            const char *pv = getenv("APRIL_PRECISION");
+            const char *pv = env_str("APRIL_PRECISION");
             if (!pv || !(std::string(pv) == "f16" || std::string(pv) == "fp16" || std::string(pv) == "half")) { LOGE("aprilx: '%s' is an fp16 cache file: set APRIL_PRECISION=f16 (the fp32 engine needs the fp32 file)", path); return nullptr; }
         }
         BlobHeader hd; memcpy(&hd, buf.data(), sizeof hd);

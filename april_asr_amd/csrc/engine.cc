@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "common.h"
+#include "env.h"
 
 namespace aprilx {
 
@@ -148,32 +149,12 @@ Engine::Engine(const EngineConfig &cfg, const PackedLayout &layout, const float 
 {
     HipLegacyLock legacy;                      // (allocations, memsets and copies on the legacy stream: not while another engine captures a graph)
     HIP_CHECK(hipSetDevice(cfg_.device));
-    {
-        // APRIL_STREAM_PRIO (measurement): 1 = the layer stream at the device's highest priority, front end and search at the lowest;
-        // 2 = the other way round; 0 = all at the default priority
-        const char *e = getenv("APRIL_STREAM_PRIO");
-        const int mode = e && *e ? atoi(e) : 0;
-        int least = 0, greatest = 0;
-        HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        if (mode == 0 || least == greatest) {
-            HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-            HIP_CHECK(hipStreamCreateWithFlags(&f_stream_, hipStreamNonBlocking));
-            HIP_CHECK(hipStreamCreateWithFlags(&s_stream_, hipStreamNonBlocking));
-        } else {
-            const int pm = mode == 1 ? greatest : least, po = mode == 1 ? least : greatest;
-            HIP_CHECK(hipStreamCreateWithPriority(&stream_, hipStreamNonBlocking, pm));
-            HIP_CHECK(hipStreamCreateWithPriority(&f_stream_, hipStreamNonBlocking, po));
-            HIP_CHECK(hipStreamCreateWithPriority(&s_stream_, hipStreamNonBlocking, po));
-        }
-    }
+    HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    HIP_CHECK(hipStreamCreateWithFlags(&f_stream_, hipStreamNonBlocking));
+    HIP_CHECK(hipStreamCreateWithFlags(&s_stream_, hipStreamNonBlocking));
     search_stream_ = stream_;
-    HIP_CHECK(hipStreamCreateWithFlags(&pf_stream_, hipStreamNonBlocking));
-    for (hipEvent_t &e : pf_ev_) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     for (int i = 0; i < 32; ++i) { hipEvent_t e; HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); join_ev_.push_back(e); }
-    {
-        const char *e = getenv("APRIL_SPLIT_STREAMS");
-        split_streams_ = e && *e ? std::max(0, std::min(2, atoi(e))) : 2;
-    }
+    split_streams_ = std::max(0, std::min(2, env_int("APRIL_SPLIT_STREAMS", 2)));
     const NetDims &d = L_.dims;
     w_ = dmalloc<float>(L_.total);
     if (blob_device) HIP_CHECK(hipMemcpy(w_, blob_device, L_.total * 4, hipMemcpyDeviceToDevice));
@@ -186,13 +167,10 @@ Engine::Engine(const EngineConfig &cfg, const PackedLayout &layout, const float 
     // (run_lm_wavefront) needs many more blocks of time steps than layers to fill: 8192 frames = ~80 s of audio per pass
     // (a minute of audio in one call is ONE wavefront: 65.7 ms against 68.8 ms in three passes of a 2048-frame ring),
     // 2.6 MB per slot (10.7 GB at 4096 slots, 3.7 % of this GPU's memory).  Results do not depend on the ring size.
-    {
-        const char *e = getenv("APRIL_RING_FRAMES");
-        ring_frames_ = std::max(P_.segment_size * 32, e && *e ? atoi(e) : 8192);
-    }
+    ring_frames_ = std::max(P_.segment_size * 32, env_int("APRIL_RING_FRAMES", 8192));
     h_ = dmalloc<float>((size_t)d.n_layers * S * d.d_model);
     c_ = dmalloc<float>((size_t)d.n_layers * S * d.hidden);
-    if (!(getenv("APRIL_RING_FRAMES") && *getenv("APRIL_RING_FRAMES"))) {
+    if (!env_str("APRIL_RING_FRAMES")) {
         // the default ring is sized for this GPU's 288 GB (10.7 GB at 4096 slots); where that is more than a quarter of what the
         // device has free right now -- several models / lanes / ranks on one device, a smaller GPU -- the ring shrinks (more
         // passes per long feed, same results), so that the allocations that FOLLOW it (state, work buffers, fp16 copies,
@@ -240,15 +218,8 @@ Engine::Engine(const EngineConfig &cfg, const PackedLayout &layout, const float 
     kz_proj_ = pick_kz(d.d_model, d.joiner);
     kz_out_ = pick_kz(d.joiner, L_.vocab_pad);
     {   // fp16 tile path: all four layer GEMMs must cut into 4 chunks of whole 32-k blocks (and the gates' y half into whole stages)
-        const char *e = getenv("APRIL_F16_TILE");
-        const bool want = cfg_.precision == 1 && !(e && *e && atoi(e) == 0);
+        const bool want = cfg_.precision == 1 && env_int("APRIL_F16_TILE", 1) != 0;
         f16_tile_ = want && d.d_model % 128 == 0 && d.hidden % 128 == 0 && d.ffn % 128 == 0 && d.hidden % 16 == 0;
-        {   // weight prefetch from a side stream: MEASUREMENT FORM, off (APRIL_PREFETCH=1).  Measured round 6: configs[4] fp16 1.78 -> 2.5 ms
-            // per step, 256 sessions fp32 1.334 -> 2.10 ms -- the two cross-stream edges per launch inside the captured graph cost far
-            // more than the ~3 us of HBM latency a launch saves (tools/pp_bench `cold`)
-            const char *pe = getenv("APRIL_PREFETCH");
-            prefetch_ = pe && *pe && atoi(pe) != 0;
-        }
         if (f16_tile_) {
             kzx_hr_ = pick_kz(d.hidden, d.d_model, 32); kzx_ff2_ = pick_kz(d.ffn, d.d_model, 32);
             for (int p = 0; p < 2; ++p) y16_buf_[p] = dmalloc<uint16_t>(MB * d.d_model);
@@ -262,20 +233,6 @@ Engine::Engine(const EngineConfig &cfg, const PackedLayout &layout, const float 
     const size_t ws_n = (size_t)std::max({kz_embed_ * d.d_model, kz_hr_ * d.d_model, kz_ff2_ * d.d_model, kz_proj_ * d.joiner, kz_out_ * L_.vocab_pad});
     ws_ = dmalloc<float>(ws_n * MB);
     ws_g_ = dmalloc<float>((size_t)std::max(kz_proj_ * d.joiner, kz_out_ * L_.vocab_pad) * MB);    // the search's own workspace: it runs beside encoder stages
-    {   // K-cut hand-over of the projection / FFN-down stream kernels (<= 16 rows): [layer][which][d_model / granule][kz][16 rows][granule columns]
-        // floats = d_model * kz * 16 per problem, one counter word per granule (zero between launches: the last workgroup re-arms it).
-        // Not in APRIL_CHAIN_STREAMS mode: there the chunks of one layer run beside each other on their own streams.
-        const bool chains = getenv("APRIL_CHAIN_STREAMS") && atoi(getenv("APRIL_CHAIN_STREAMS")) != 0;
-        const bool ks_on = getenv("APRIL_RECUR_KSPLIT") && atoi(getenv("APRIL_RECUR_KSPLIT")) != 0;      // (a measurement form, off by default: kernels_recur.hip recur_ksplit)
-        if (ks_on && !chains && cfg_.precision == 0) {
-            ks_ws_stride_ = (size_t)d.d_model * (size_t)std::max(kz_hr_, kz_ff2_) * 16;
-            ks_cnt_stride_ = (size_t)d.d_model / 16;
-            ks_ws_ = dmalloc<float>(2 * (size_t)d.n_layers * ks_ws_stride_);
-            ks_cnt_ = dmalloc<unsigned>(2 * (size_t)d.n_layers * ks_cnt_stride_);
-            HipLegacyLock legacy;
-            HIP_CHECK(hipMemset(ks_cnt_, 0, 2 * (size_t)d.n_layers * ks_cnt_stride_ * sizeof(unsigned)));
-        }
-    }
     xin_ = dmalloc<float>(MB * d.embed_in);
     a3_ = dmalloc<float>(MB * d.f_out * L_.k3);
     HIP_CHECK(hipMemset(a3_, 0, MB * d.f_out * L_.k3 * 4));      // padded k columns (if any) stay zero
@@ -311,7 +268,7 @@ Engine::Engine(const EngineConfig &cfg, const PackedLayout &layout, const float 
     HIP_CHECK(hipMemset(counter_d_, 0, 4));
 
     upload_tables(ft);
-    use_graphs_ = !(getenv("APRIL_NO_GRAPHS") && atoi(getenv("APRIL_NO_GRAPHS")));
+    use_graphs_ = env_int("APRIL_NO_GRAPHS", 0) == 0;
     free_.reserve(S);
     for (int i = cfg_.max_slots - 1; i >= 0; --i) free_.push_back(i);
     LOGI("engine: device %d, %d slots, max batch %d, weights %.1f MB, kz(embed,hr,ff2,proj,out)=%d,%d,%d,%d,%d",
@@ -360,8 +317,7 @@ void Engine::build_dec_table()
 {
     if (dec_table_) return;
     const NetDims &d = L_.dims;
-    const char *e = getenv("APRIL_DEC_TABLE_MB");
-    const size_t limit_mb = e && *e ? (size_t)std::max(0, atoi(e)) : 2048;
+    const size_t limit_mb = (size_t)std::max(0, env_int("APRIL_DEC_TABLE_MB", 2048));
     const size_t rows = (size_t)d.vocab * (size_t)d.vocab;
     if (d.context != 2 || rows * (size_t)d.joiner * 4 > limit_mb * 1024 * 1024 || rows * (size_t)d.joiner * 4 >= ((size_t)1 << 32)) return;   // (32-bit byte offsets in the GEMM's A addressing)
     const int MB = cfg_.max_batch;
@@ -392,23 +348,19 @@ Engine::~Engine()
     dump_stream_trace();
     for (StreamTrace &t : trace_) for (hipEvent_t e : t.ev) if (e) (void)hipEventDestroy(e);
     if (trace_base_) (void)hipEventDestroy(trace_base_);
-    for (hipStream_t cs : chain_streams_) (void)hipStreamDestroy(cs);
-    for (hipEvent_t e : chain_ev_) (void)hipEventDestroy(e);
     for (hipEvent_t e : join_ev_) (void)hipEventDestroy(e);
     for (auto &e : ev_pool_) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &g : step_graphs_) (void)hipGraphExecDestroy(g.second);
     for (auto &g : lm_graphs_) (void)hipGraphExecDestroy(g.second);
     for (auto &g : lm_search_graphs_) (void)hipGraphExecDestroy(g.second);
-    for (auto &p : sw_plans_) { if (p.second.graph) (void)hipGraphExecDestroy(p.second.graph); for (hipGraphExec_t x : p.second.g3) if (x) (void)hipGraphExecDestroy(x); if (p.second.dev) (void)hipFree(p.second.dev); if (p.second.rdev) (void)hipFree(p.second.rdev); if (p.second.pf_dev) (void)hipFree(p.second.pf_dev); }
+    for (auto &p : sw_plans_) { if (p.second.graph) (void)hipGraphExecDestroy(p.second.graph); for (hipGraphExec_t x : p.second.g3) if (x) (void)hipGraphExecDestroy(x); if (p.second.dev) (void)hipFree(p.second.dev); if (p.second.rdev) (void)hipFree(p.second.rdev); }
     if (lm_stream_) { (void)hipStreamSynchronize(lm_stream_); (void)hipStreamDestroy(lm_stream_); }
     for (hipEvent_t e : lm_events_) (void)hipEventDestroy(e);
     if (zargs_h_) { (void)hipHostFree(zargs_h_); (void)hipFree(zargs_d_); }
     for (int i = 0; i < 3; ++i) if (zargs_done_[i]) (void)hipEventDestroy(zargs_done_[i]);
     for (void *p : {(void *)lm_now_d_, (void *)lm_rows_d_, (void *)lm_rec_off_d_}) if (p) (void)hipFree(p);
     if (ws_g_) (void)hipFree(ws_g_);
-    if (ks_ws_) (void)hipFree(ks_ws_);
     if (conv_wt_) (void)hipFree(conv_wt_);
-    if (ks_cnt_) (void)hipFree(ks_cnt_);
     if (dec_table_) (void)hipFree(dec_table_);
     if (p_lm_) (void)hipFree(p_lm_);
     for (int p = 0; p < 2; ++p)
@@ -426,7 +378,7 @@ Engine::~Engine()
     for (int b = 0; b < 2; ++b) if (fb_done_[b]) (void)hipEventDestroy(fb_done_[b]);
     for (int b = 0; b < 2; ++b) if (flight_done_[b]) (void)hipEventDestroy(flight_done_[b]);
     for (void *p : table_allocs_) (void)hipFree(p);
-    (void)hipStreamDestroy(stream_); (void)hipStreamDestroy(f_stream_); (void)hipStreamDestroy(s_stream_); if (pf_stream_) (void)hipStreamDestroy(pf_stream_); for (hipEvent_t e : pf_ev_) if (e) (void)hipEventDestroy(e);
+    (void)hipStreamDestroy(stream_); (void)hipStreamDestroy(f_stream_); (void)hipStreamDestroy(s_stream_);
 }
 
 void Engine::upload_tables(const FbankHostTables &ft)
@@ -534,8 +486,8 @@ void Engine::sync()
 // parts overlap (rocprofv3's kernel trace serialises the queues, so it cannot show it).
 Engine::StreamTrace *Engine::trace_slot()
 {
-    static const char *path = getenv("APRIL_STREAM_TRACE");
-    if (!path || !*path) return nullptr;
+    static const char *path = env_str("APRIL_STREAM_TRACE");
+    if (!path) return nullptr;
     if (!trace_base_) { HIP_CHECK(hipEventCreate(&trace_base_)); HIP_CHECK(hipEventRecord(trace_base_, stream_)); }
     if (trace_.size() >= 4096) return nullptr;
     trace_.emplace_back();
@@ -546,8 +498,8 @@ Engine::StreamTrace *Engine::trace_slot()
 
 void Engine::dump_stream_trace()
 {
-    const char *path = getenv("APRIL_STREAM_TRACE");
-    if (!path || !*path || trace_.empty()) return;
+    const char *path = env_str("APRIL_STREAM_TRACE");
+    if (!path || trace_.empty()) return;
     FILE *f = fopen(path, "w");
     if (!f) return;
     fprintf(f, "# one line per split feed; times in us since the first split feed; FE = index fetch + conv + embed on stream F, LY = layer wavefront on M, SR = encoder_proj + search on S\n");
@@ -773,12 +725,11 @@ void Engine::run_encoder_rows(int n, const int *d_slots, const int *d_tails, con
         timed_begin(T_CONV); launch_gemm(g, stream_); timed_end(T_CONV);
     }
     // y = A x W + bias (+ residual) with sums of squares: fused into the GEMM where its tiles own all of K, else split-K + row kernel
-    auto resid_ssq = [&](const float *a, int K, size_t w_off, int kz, const float *bias, const float *resid, int ks_layer = -1) {
+    auto resid_ssq = [&](const float *a, int K, size_t w_off, int kz, const float *bias, const float *resid) {
         GemmArgs g; g.a0 = a; g.lda0 = K; g.K0 = K; lin(g, w_off);
         g.M = n; g.N = d.d_model; g.K = K; g.kz = kz; g.tile_ok = tile_ok();
         if (gemm_fullk(n, d.d_model, kz, false, 1, tile_ok())) {
             g.epi = EPI_RESID_SSQ; g.bias = bias; g.resid = resid; g.ldr = d.d_model; g.out = y_; g.ldo = d.d_model; g.ssq_out = ssq_;
-            if (ks_layer >= 0) attach_ksplit(g, ks_layer, 1);
             timed_begin(T_GEMM_OTHER); launch_gemm(g, stream_); timed_end(T_GEMM_OTHER);
             return;
         }
@@ -821,7 +772,6 @@ void Engine::run_encoder_rows(int n, const int *d_slots, const int *d_tails, con
             g.M = n; g.N = d.d_model; g.K = d.hidden; g.kz = kz_hr_; g.tile_ok = tile_ok();
             if (gemm_fullk(n, d.d_model, kz_hr_, false, 1, tile_ok())) {
                 g.epi = EPI_HR; g.state = h_l; g.ld_state = d.d_model; g.slot_idx = d_slots; g.resid = y_; g.ldr = d.d_model; g.r_scale = xs; g.out = xb_; g.ldo = d.d_model;
-                attach_ksplit(g, l, 0);
                 timed_begin(T_GEMM_OTHER); launch_gemm(g, stream_); timed_end(T_GEMM_OTHER);
             } else {
                 g.epi = EPI_PARTIAL; g.out = ws_; g.m_stride = ws_mstride_;
@@ -837,7 +787,7 @@ void Engine::run_encoder_rows(int n, const int *d_slots, const int *d_tails, con
             timed_begin(T_GEMM_OTHER); launch_gemm(g, stream_); timed_end(T_GEMM_OTHER);
         }
         // FFN down + bias + residual -> y (the last reader of the previous y was the projection above)
-        resid_ssq(ff_, d.ffn, o.wff2, kz_ff2_, w_ + o.bff2, xb_, l);
+        resid_ssq(ff_, d.ffn, o.wff2, kz_ff2_, w_ + o.bff2, xb_);
         eps_in = L_.norm_eps[(size_t)l];
     }
     {   // encoder_proj(norm(y)) -> eout[slot]
@@ -1033,20 +983,17 @@ GemmArgs Engine::lm_args_gates(int l, int m, int t) const
 // fp32 gates GEMM on the GM_TILE schedule (same chains, same bits as the hand-scheduled K-split tiles -- tests/test_gpu_gates_tile.py):
 // measured 2..5 % per feed faster from ~2000 rows per launch (1024 sessions: RTF 0.0533 vs 0.055..0.058, 2048: 0.096..0.097 vs
 // 0.099..0.104), slower at 256 sessions (53.5 vs 46.5 us per launch) and at one session.  APRIL_GATES_TILE: 0 never, 1 always,
-// 2 (default) from APRIL_GATES_TILE_ROWS (2048) rows per launch.
+// 2 (default) from GATES_TILE_MIN_ROWS rows per launch.
+constexpr long GATES_TILE_MIN_ROWS = 2048;
 bool Engine::gates_tile_rows(long rows) const
 {
-    static const int mode = getenv("APRIL_GATES_TILE") ? atoi(getenv("APRIL_GATES_TILE")) : 2;
-    static const long min_rows = getenv("APRIL_GATES_TILE_ROWS") ? atol(getenv("APRIL_GATES_TILE_ROWS")) : 2048;
-    return mode == 1 || (mode == 2 && rows >= min_rows);
+    static const int mode = env_int("APRIL_GATES_TILE", 2);
+    return mode == 1 || (mode == 2 && rows >= GATES_TILE_MIN_ROWS);
 }
 
-// (the same for the FFN-up GEMM; measurement knob APRIL_FF1_TILE_ROWS, default off)
-bool Engine::ff1_tile_rows(long rows) const
-{
-    static const long min_rows = getenv("APRIL_FF1_TILE_ROWS") ? atol(getenv("APRIL_FF1_TILE_ROWS")) : 0;
-    return min_rows > 0 && rows >= min_rows;
-}
+// (the same for the FFN-up GEMM: no row count from which it is on, 0 = never)
+constexpr long FF1_TILE_MIN_ROWS = 0;
+bool Engine::ff1_tile_rows(long rows) const { return FF1_TILE_MIN_ROWS > 0 && rows >= FF1_TILE_MIN_ROWS; }
 
 GemmArgs Engine::sw_args_gates(int l, int m, int t) const
 {   // the one-launch gates GEMM of a chunk step (run_encoder_rows) on the rows of chunk t: [norm(y) | h_prev] x Wg, fused LSTM cell
@@ -1068,13 +1015,6 @@ GemmArgs Engine::sw_args_gates(int l, int m, int t) const
     return g;
 }
 
-void Engine::attach_ksplit(GemmArgs &g, int l, int which) const
-{
-    if (!ks_ws_) return;
-    g.ks_ws = ks_ws_ + ((size_t)l * 2 + (size_t)which) * ks_ws_stride_;
-    g.ks_cnt = ks_cnt_ + ((size_t)l * 2 + (size_t)which) * ks_cnt_stride_;
-}
-
 GemmArgs Engine::lm_args_whr(int l, int m, int t) const
 {   // h' = u x Whr ; state write + residual, in one launch however few workgroups (sequential step)
     const NetDims &d = L_.dims;
@@ -1087,7 +1027,6 @@ GemmArgs Engine::lm_args_whr(int l, int m, int t) const
     g.epi = EPI_HR; g.state = h_ + (size_t)l * S * d.d_model; g.ld_state = d.d_model; g.slot_idx = step_d_; g.resid = y_ + r0 * d.d_model; g.ldr = d.d_model;
     g.r_scale.ssq = ssq_ + r0 * G; g.r_scale.groups = G; g.r_scale.inv_n = 1.0f / (float)(d.d_norm ? d.d_norm : d.d_model); g.r_scale.eps = l == 0 ? L_.embed_eps : L_.norm_eps[(size_t)l - 1];
     g.out = xb_ + r0 * d.d_model; g.ldo = d.d_model;
-    attach_ksplit(g, l, 0);
     if (f16_tile_) {
         g.a0 = reinterpret_cast<const float *>(u16_ + r0 * d.hidden); lin16(g, o.whr); g.kz = kzx_hr_;
         g.state16 = h16_ + (size_t)l * S * d.d_model; g.out16 = xb16_ + r0 * d.d_model;
@@ -1116,7 +1055,6 @@ GemmArgs Engine::lm_args_ff2(int l, int m, int t0, int t1) const
     GemmArgs g; g.a0 = ff_ + b0 * d.ffn; g.lda0 = d.ffn; g.K0 = d.ffn; lin(g, o.wff2);
     g.M = (t1 - t0) * m; g.N = d.d_model; g.K = d.ffn; g.kz = kz_ff2_; g.tile_ok = tile_ok(); g.force_fullk = 1;
     g.epi = EPI_RESID_SSQ; g.bias = w_ + o.bff2; g.resid = xb_ + b0 * d.d_model; g.ldr = d.d_model; g.out = y_ + b0 * d.d_model; g.ldo = d.d_model; g.ssq_out = ssq_ + b0 * G;
-    attach_ksplit(g, l, 1);
     if (f16_tile_) { g.a0 = reinterpret_cast<const float *>(ff16_ + b0 * d.ffn); lin16(g, o.wff2); g.kz = kzx_ff2_; g.out16 = y16_ + b0 * d.d_model; }
     return g;
 }
@@ -1215,25 +1153,19 @@ void Engine::lm_stage_proj(int m, int t0, int t1, hipStream_t st, float *ws)
 // streams that do not depend on the block length), and the wavefront runs NB + L + 1 macro steps, L + 1 of them fill / drain:
 // (T / blk + L + 1) (c_step blk + c_block) is smallest near blk = sqrt(T c_block / ((L + 1) c_step)) ~ 0.75 sqrt(T) at aprilv0
 // size.  Measured, 60 s in one call (T = 1498): blk 10 / 16 / 20 / 24 / 32 -> 65.5 / 61.6 / 61.2 / 60.6 / 60.2 ms.
-// APRIL_LM_BLOCK pins it.  Results do not depend on the block length (same chains in the same order).
-static int lm_block_env()
-{
-    static const int v = getenv("APRIL_LM_BLOCK") ? std::max(1, atoi(getenv("APRIL_LM_BLOCK"))) : 0;
-    return v;
-}
+// Results do not depend on the block length (same chains in the same order).
 static int lm_block_steps(int T)
 {
-    if (lm_block_env() > 0) return lm_block_env();
     const int b = (int)(0.75 * std::sqrt((double)std::max(1, T)) + 0.5);
     return std::max(6, std::min(32, b));
 }
 // (feeds up to this many chunks run as one layer-major chain, captured as a graph: too few blocks for a wavefront to fill)
-static int lm_wavefront_min_chunks() { return lm_block_env() > 0 ? lm_block_env() : 10; }
+constexpr int LM_WAVEFRONT_MIN_CHUNKS = 10;
 
 static bool lm_wavefront_on()
 {
-    static const int v = getenv("APRIL_LM_WAVEFRONT") ? atoi(getenv("APRIL_LM_WAVEFRONT")) : 1;
-    return v != 0;
+    static const bool on = env_int("APRIL_LM_WAVEFRONT", 1) != 0;
+    return on;
 }
 
 void Engine::run_lm_chain(int m, int T, bool dump_logits)
@@ -1294,7 +1226,7 @@ void Engine::run_lm_wavefront(int m, int T, bool dump_logits)
     if (zargs_busy_[zslot]) HIP_CHECK(hipEventSynchronize(zargs_done_[zslot]));
     zargs_pos_ = (size_t)zslot * zargs_region_;
 
-    static const bool timing = getenv("APRIL_LM_TIMING") != nullptr;        // measurement: host time of the enqueue by part
+    static const bool timing = env_str("APRIL_LM_TIMING") != nullptr;        // measurement: host time of the enqueue by part
     double tacc[6] = {0, 0, 0, 0, 0, 0};
     auto now = [&]() { return timing ? std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count() : 0.0; };
     struct Batch { size_t off; int n; };
@@ -1403,7 +1335,7 @@ void Engine::run_lm_wavefront(int m, int T, bool dump_logits)
 // The argument blocks depend on (m, T) only: built once per shape, kept in device memory, and the whole chain is one graph.
 static bool lm_gates_split_on()
 {
-    static const bool on = [] { const char *e = getenv("APRIL_GATES_SPLIT"); return !(e && *e && atoi(e) == 0); }();
+    static const bool on = env_int("APRIL_GATES_SPLIT", 1) != 0;
     return on;
 }
 
@@ -1417,7 +1349,7 @@ Engine::SwPlan &Engine::sw_plan(int m, int T)
     if (sw_plans_.size() >= 64) {
         sync();
         HipLegacyLock evict_guard;                    // (see fbank())
-        for (auto &p : sw_plans_) { if (p.second.graph) (void)hipGraphExecDestroy(p.second.graph); for (hipGraphExec_t x : p.second.g3) if (x) (void)hipGraphExecDestroy(x); if (p.second.dev) (void)hipFree(p.second.dev); if (p.second.rdev) (void)hipFree(p.second.rdev); if (p.second.pf_dev) (void)hipFree(p.second.pf_dev); }
+        for (auto &p : sw_plans_) { if (p.second.graph) (void)hipGraphExecDestroy(p.second.graph); for (hipGraphExec_t x : p.second.g3) if (x) (void)hipGraphExecDestroy(x); if (p.second.dev) (void)hipFree(p.second.dev); if (p.second.rdev) (void)hipFree(p.second.rdev); }
         sw_plans_.clear();
     }
     SwPlan &p = sw_plans_[key];
@@ -1471,8 +1403,6 @@ Engine::SwPlan &Engine::sw_plan(int m, int T)
                     ++gclk_used_;
                 }
                 SwPlan::Batch b; b.off = p.host.size(); b.n = gn; b.macro = W; b.kind = kind; b.roff = p.rhost.size(); b.rn = gi == 0 ? (int)rows.size() : 0;
-                b.pf_off = p.pf_host.size(); b.pf_n = b.n;
-                for (int i = 0; i < gn; ++i) { const GemmArgs &g = items[first + (size_t)i]; PrefetchItem pi; pi.ptr = g.wp; pi.bytes = (unsigned long long)g.N * (unsigned long long)g.K * (g.wt == 1 ? 2u : 4u); p.pf_host.push_back(pi); }
                 p.host.resize(p.host.size() + (size_t)gn);
                 stage_gemm_z(items.data() + first, gn, p.host.data() + b.off);
                 if (gi == 0) p.rhost.insert(p.rhost.end(), rows.begin(), rows.end());
@@ -1489,40 +1419,7 @@ Engine::SwPlan &Engine::sw_plan(int m, int T)
         p.rdev = dmalloc<RowArgs>(p.rhost.size());
         HIP_CHECK(hipMemcpyAsync(p.rdev, p.rhost.data(), p.rhost.size() * sizeof(RowArgs), hipMemcpyHostToDevice, stream_));
     }
-    if (prefetch_ && !p.pf_host.empty()) {
-        p.pf_dev = dmalloc<PrefetchItem>(p.pf_host.size());
-        HIP_CHECK(hipMemcpyAsync(p.pf_dev, p.pf_host.data(), p.pf_host.size() * sizeof(PrefetchItem), hipMemcpyHostToDevice, stream_));
-    }
     return p;
-}
-
-// Measurement (APRIL_CHAIN_STREAMS=1): the layer part of a split feed as T per-chunk chains on T streams instead of z-batched
-// wavefront launches on one.  Chunk t's chain is G -> P -> U -> D layer after layer on the rows of chunk t (one 256-row problem per
-// launch); the only coupling is the recurrent state: G(l, t) waits for P(l, t - 1) by an event.  Same kernels, same arguments,
-// same chains as the z-batched launches (row-partitioned work buffers), so the results are bit-identical; what changes is
-// that the chains' launches overlap each other's ramp, prologue and epilogue.  Eager launches (events cross the streams).
-void Engine::run_sw_layers_chains(int m, int T)
-{
-    const NetDims &d = L_.dims;
-    const int L = d.n_layers;
-    while ((int)chain_streams_.size() < T - 1) { hipStream_t s; HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); chain_streams_.push_back(s); }
-    while (chain_ev_.size() < (size_t)L * (size_t)T) { hipEvent_t e; HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); chain_ev_.push_back(e); }
-    auto st = [&](int t) { return t == 0 ? stream_ : chain_streams_[(size_t)t - 1]; };
-    for (int t = 1; t < T; ++t) join(st(t), stream_);                    // behind the front end (and the flight before)
-    for (int W = 1; W <= T + L - 1; ++W) {                               // issue in wavefront order so that no stream runs dry on the host's account
-        for (int l = 0; l < L; ++l) {
-            const int t = W - 1 - l;
-            if (t < 0 || t >= T) continue;
-            hipStream_t s = st(t);
-            if (t > 0) HIP_CHECK(hipStreamWaitEvent(s, chain_ev_[(size_t)l * T + (size_t)t - 1], 0));
-            launch_gemm(sw_args_gates(l, m, t), s);
-            launch_rowepi(lm_args_whr(l, m, t), (size_t)t * m, s);          // (fused, or planes + row kernel: the planner's choice for one problem)
-            if (t + 1 < T) HIP_CHECK(hipEventRecord(chain_ev_[(size_t)l * T + (size_t)t], s));
-            launch_gemm(lm_args_ff1(l, m, t, t + 1), s);
-            launch_rowepi(lm_args_ff2(l, m, t, t + 1), (size_t)t * m, s);
-        }
-    }
-    for (int t = 1; t < T; ++t) join(stream_, st(t));
 }
 
 // part 0: index fetch + front end (stream fe), 1: the layer wavefront + encoder_proj (stream ly), 2: the searches (stream sr);
@@ -1543,25 +1440,10 @@ void Engine::run_sw_chain(int m, int T, bool dump_logits, const SwPlan &p, int p
     }
     if (part < 0 || part == 1) {
         static const int cls_of[4] = {T_GATES, T_GEMM_OTHER, T_GEMM_OTHER, T_GEMM_OTHER};
-        // weight prefetch (kernels.h launch_prefetch): while batch i runs, the side stream touches the weights of batch i + 1 -- released
-        // by an event in front of batch i, so it is never more than one launch ahead (the cache holds a few launches' weights, not a step's)
-        const bool pf = prefetch_ && p.pf_dev && !profiling_;
         for (size_t bi = 0; bi < p.batches.size(); ++bi) {      // macro steps in order; inside one: gates, projection, FFN up, FFN down of the active layers
             const SwPlan::Batch &b = p.batches[bi];
-            if (pf && bi + 1 < p.batches.size()) {
-                const SwPlan::Batch &nx = p.batches[bi + 1];
-                hipEvent_t e = pf_ev_[pf_pos_++ & 7];
-                HIP_CHECK(hipEventRecord(e, st));
-                HIP_CHECK(hipStreamWaitEvent(pf_stream_, e, 0));
-                launch_prefetch(p.pf_dev + nx.pf_off, nx.pf_n, pf_stream_);
-            }
             timed_begin(cls_of[b.kind]); launch_gemm_z(p.host.data() + b.off, b.n, p.dev + b.off, st); timed_end(cls_of[b.kind]);
             if (b.rn > 0) { timed_begin(T_ROW); launch_row_z(p.rhost.data() + b.roff, b.rn, p.rdev + b.roff, st); timed_end(T_ROW); }
-        }
-        if (pf && p.batches.size() > 1) {
-            hipEvent_t e = pf_ev_[pf_pos_++ & 7];
-            HIP_CHECK(hipEventRecord(e, pf_stream_));
-            HIP_CHECK(hipStreamWaitEvent(st, e, 0));
         }
         if (part < 0) lm_stage_proj(m, 0, T, st);
     }
@@ -1664,9 +1546,7 @@ int Engine::lm_step(int m, int T, const int *slots, const int *ring_tails, const
             if (tr) HIP_CHECK(hipEventRecord(tr->ev[1], fe));
             if (fe == f_stream_) { join(stream_, f_stream_); f_unseen_by_m_ = false; }
             if (tr) HIP_CHECK(hipEventRecord(tr->ev[2], stream_));
-            static const bool chains = getenv("APRIL_CHAIN_STREAMS") && atoi(getenv("APRIL_CHAIN_STREAMS")) != 0;
-            if (chains && cfg_.precision == 0) run_sw_layers_chains(m, T);
-            else HIP_CHECK(hipGraphLaunch(p.g3[1], stream_));
+            HIP_CHECK(hipGraphLaunch(p.g3[1], stream_));
             if (tr) HIP_CHECK(hipEventRecord(tr->ev[3], stream_));
             join(s_stream_, stream_);
             if (tr) HIP_CHECK(hipEventRecord(tr->ev[4], s_stream_));
@@ -1687,7 +1567,7 @@ int Engine::lm_step(int m, int T, const int *slots, const int *ring_tails, const
     } else {
         general_prologue();
         const int tk = f16_tile_ ? 2 : tile_ok();
-        const bool wavefront = lm_wavefront_on() && !profiling_ && T > lm_wavefront_min_chunks() &&
+        const bool wavefront = lm_wavefront_on() && !profiling_ && T > LM_WAVEFRONT_MIN_CHUNKS &&
                                gemm_fullk(m, d.d_model, kz_hr(), true, 1, tk) && gemm_fullk(m, d.d_model, kz_ff2(), true, 1, tk);
         if (wavefront) {                 // long feed: all layers of a wavefront per launch (run_lm_wavefront)
             run_lm_wavefront(m, T, logits_out != nullptr);

@@ -202,17 +202,14 @@ private:
     void run_lm_chain(int m, int T, bool dump_logits);
     void run_lm_wavefront(int m, int T, bool dump_logits);
     struct SwPlan {                          // argument blocks + launch list of run_sw_chain for one (m, T), and its captured graph
-        struct Batch { size_t off; int n, macro, kind; size_t roff; int rn; size_t pf_off = 0; int pf_n = 0; };      // rn > 0: the GEMMs write partial planes, rn row problems finish them
+        struct Batch { size_t off; int n, macro, kind; size_t roff; int rn; };      // rn > 0: the GEMMs write partial planes, rn row problems finish them
         std::vector<GemmArgs> host; GemmArgs *dev = nullptr; std::vector<Batch> batches; hipGraphExec_t graph = nullptr; int uses = 0;
         hipGraphExec_t g3[3] = {nullptr, nullptr, nullptr};                      // split feed: front end / layers / search, one graph per stream
         std::vector<RowArgs> rhost; RowArgs *rdev = nullptr;
-        std::vector<PrefetchItem> pf_host; PrefetchItem *pf_dev = nullptr;      // weight regions of every batch (launch_prefetch of the batch AFTER the one that runs)
         std::vector<std::pair<int, long>> stamp_slots; std::vector<int> stamp_n;  // gates clock: (slot, rows) and problem count of every gates launch of a plan built while it was on
     };
     SwPlan &sw_plan(int m, int T);
     void run_sw_chain(int m, int T, bool dump_logits, const SwPlan &p, int part, hipStream_t st);
-    void run_sw_layers_chains(int m, int T);
-    std::vector<hipStream_t> chain_streams_; std::vector<hipEvent_t> chain_ev_;
     struct StreamTrace { hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; int m = 0, T = 0; bool used = false; };
     std::deque<StreamTrace> trace_; hipEvent_t trace_base_ = nullptr;
     StreamTrace *trace_slot();
@@ -268,7 +265,6 @@ private:
     bool flight_open_[2] = {false, false};     // flight_done_[p] has been recorded and not yet waited for by begin_flight (wait_flight leaves it set: waiting twice is free)
     // streams (engine.cc "streams"): front end / search beside the layer chain, the per-parity buffers that make it safe
     hipStream_t f_stream_ = nullptr, s_stream_ = nullptr, search_stream_ = nullptr;
-    hipStream_t pf_stream_ = nullptr; bool prefetch_ = false; hipEvent_t pf_ev_[8] = {}; unsigned pf_pos_ = 0;      // weight prefetch beside the layer launches (kernels.h launch_prefetch)
     std::vector<hipEvent_t> join_ev_; size_t join_pos_ = 0;
     bool f_unseen_by_m_ = false, s_unseen_by_m_ = false, m_unseen_by_f_ = false, m_unseen_by_s_ = false, flight_tail_s_ = false;
     bool overlap_hint_ = false;
@@ -309,9 +305,6 @@ private:
     int kz_embed_ = 1, kz_hr_ = 1, kz_ff2_ = 1, kz_proj_ = 1, kz_out_ = 1;
     int ws_mstride_ = 0;
     float *conv_wt_ = nullptr;      // transposed weights of the first two convolutions: [9][ch0] then [ch0 * 9][ch1] (finish_weights)
-    // workspace of the K-cut stream kernels at <= 16 rows (kernels.h GemmArgs::ks_ws / ks_cnt): per layer, projection and FFN down apart
-    float *ks_ws_ = nullptr; unsigned *ks_cnt_ = nullptr; size_t ks_ws_stride_ = 0, ks_cnt_stride_ = 0;
-    void attach_ksplit(GemmArgs &g, int l, int which) const;
     // chunk-step launch chains captured per batch size
     bool use_graphs_ = true;
     std::map<int, hipGraphExec_t> step_graphs_;

@@ -57,7 +57,7 @@ enum GemmMode { GM_SLAB = 0, GM_FULLK = 1, GM_TILE = 2, GM_KW = 3, GM_PP = 4 };
 //               zs < kz: kz / zs partial planes, finished by the row kernels exactly as for GM_SLAB.
 //     GM_KW     (kernels_gemm_kw.hip, round 5) the waves split K as in GM_FULLK (eight waves: one slab each at kz = 8), but every wave's
 //               activation rows arrive in full 128-byte lines through a wave-private LDS ring (no barrier in the K loop); 32 x 32 tiles.
-//               The N = d_model GEMMs (and FFN up) at a few hundred rows per launch.
+//               The N = d_model GEMMs at a few hundred rows per launch.
 
 //     GM_PP     (kernels_gemm_pp.hip, round 6) the fp16 gates / FFN-up GEMMs (kz = 1) from a few hundred rows per launch: 256 / 128 x 128
 //               tiles on eight waves = two groups of four that run one phase apart (one group's MFMAs beside the other's DMA issue and
@@ -127,13 +127,6 @@ struct GemmArgs {
     int tile_ok = 0;                       // the caller planned this GEMM with gemm_fullk / gemm_partials(..., tile_ok): 1 = GM_TILE may be chosen by
                                            // the planner's occupancy rule (fp32 A in one K segment, N % 64 == 0, row epilogue or partial planes);
                                            // 2 = GM_TILE always (the fp16 tile path of an fp16 engine: every batch size runs the same chains)
-    // (measurement form, APRIL_RECUR_KSPLIT, off by default) the row forms of kernels_recur.hip (<= 16 rows, EPI_HR / EPI_RESID_SSQ) cut K across `ksplit` workgroups per column granule when the caller
-    // lends them a workspace: ks_ws = [N / granule columns][kz][16][granule columns] floats, ks_cnt = one zeroed word per granule, both
-    // private to this problem among everything that can run beside it (the engine: per layer).  ksplit is set by launch_gemm / stage_gemm_z.
-    float *ks_ws = nullptr; unsigned *ks_cnt = nullptr; int ksplit = 1;
-    int skew = 0;                          // first-round start skew (x 4096 cycles; APRIL_GEMM_SKEW, off: device_utils.h first_round_skew; GM_KW: its own meaning, APRIL_KW_SKEW)
-    int skew_wgs = 0;                      // workgroups of the first round (the chip's slots for this kernel); set by launch_gemm with skew
-    int xcd_rc = 0;                        // GM_KW: 2 = tiles dealt to the XCDs as 2 row halves x 4 column quarters (APRIL_KW_XCD; 0 = column tiles round robin)
     int asm_loop = 0;                      // != 0: hand-scheduled K loop (gemm_mainloop_asm.inc) in the fused-epilogue 64x64 fp32 tiles
     unsigned long long *trace = nullptr;   // measurement only: per-workgroup s_memtime stamps [wg][8] (wave 0, lane 0)
     // Gates launches only (EPI_LSTM; the engine's "gates clock", aprilx_model_profile(model, 2)): one slot per LAUNCH (all problems
@@ -153,7 +146,7 @@ bool gemm_profile_pending();
 // (internal) GM_TILE launch, called by launch_gemm / launch_gemm_z once the plan is made: tile 16 * mt rows x 16 * nt columns; dev_args != null: n z-batched problems
 void launch_gemm_tile(const GemmArgs &g, int mt, int nt, const GemmArgs *dev_args, int n, hipStream_t s);
 // (internal) GM_KW launch (kernels_gemm_kw.hip): tile 16 * mt rows x 16 * nt columns, all of K in the workgroup; dev_args != null: n z-batched
-// problems.  gemm_kw_waves: 8 / 4 = the waves a GM_KW workgroup would use for this GEMM (operands, epilogue, chunk structure), 0 = not eligible
+// problems.  gemm_kw_waves: 8 = the waves a GM_KW workgroup would use for this GEMM (operands, epilogue, chunk structure), 0 = not eligible
 int gemm_kw_waves(const GemmArgs &g);
 // (internal) GM_PP launch (kernels_gemm_pp.hip): tile 16 * mt (256 / 128) rows x 128 columns; dev_args != null: n z-batched problems.
 // gemm_pp_ok: the operands of g fit the schedule (binary16 operands, kz = 1, LSTM / DoubleSwish / XPART epilogue, whole stages)
@@ -166,13 +159,11 @@ void launch_gemm_pw(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStrea
 void gemm_pp_pin(int enable, int mt);
 bool gemm_kw_has_kernel(const GemmArgs &g, int mt, int nt);      // a GM_KW kernel exists for this GEMM on 16 mt x 16 nt tiles
 void launch_gemm_kw(const GemmArgs &g, int mt, int nt, const GemmArgs *dev_args, int n, hipStream_t s);
-// measurement only (tools/kw_bench): enable / ff1 (FFN up on GM_KW): -1 = environment default, 0 / 1 = off / on; mt = 0 (planner) or pinned tile rows / 16
-void gemm_kw_pin(int enable, int mt, int ff1);
+// measurement only (tools/kw_bench): enable -1 = environment default (APRIL_GM_KW), 0 / 1 = off / on; mt = 0 (planner) or pinned tile rows / 16
+void gemm_kw_pin(int enable, int mt);
 // (internal) the recurrent GEMMs of a long feed at <= 16 rows as weight streams (kernels_recur.hip): recur_form says whether g is
 // one of them (1 gates h-half + cell, 2 projection), launch_recur runs n same-shape problems (dev_args) or g itself (dev_args == null)
 int recur_form(const GemmArgs &g);
-void recur_ksplit_pin(int s);                    // measurement only (tools/kw_bench): -1 = environment default (APRIL_RECUR_KSPLIT), 0 = off, 1 = planner, > 1 = that cut
-int recur_ksplit(const GemmArgs &g, int n);      // workgroups per column granule for the row forms (1 = whole K in one workgroup)
 void launch_recur(const GemmArgs &g, int form, const GemmArgs *dev_args, int n, hipStream_t s);
 // n independent GEMMs of ONE shape (same M, N, K, kz, epilogue; any pointers) in one launch.  stage_gemm_z finalizes the
 // argument blocks on the host; launch_gemm_z launches once they are in device memory at dev_args (in stream order).
@@ -343,15 +334,6 @@ void launch_conv_weight_transpose(const float *w0, const float *w1, int c0, int 
 // fp32 -> fp16 (round to nearest even), elementwise; used once at load for the fp16 weight copies
 void launch_cvt_f16(const float *src, void *dst, size_t n, hipStream_t s);
 
-// Weight prefetch into the memory-side cache (round 6).  The layer weights of a model do not fit the 256 MB Infinity Cache (aprilv0 fp32:
-// 0.33 GB, the larger encoder in binary16: 0.5 GB), so every launch of a step streams its weights from HBM and starts with the
-// latency of that (tools/pp_bench `cold`: +3 .. 4 us per launch against weights the launch before left behind).  launch_prefetch
-// reads one dword of every 128-byte line of n regions -- the NEXT launch's weights -- from a side stream while the current launch
-// computes: HBM is idle then (a launch's weights are in after its first third), the lines land in the memory-side cache, and the
-// next launch's first DMA stages arrive at cache latency.  No data dependency: a hint, joined only to close the graph capture.
-// MEASURED AND NOT KEPT (engine.cc, APRIL_PREFETCH=1): the cross-stream edges it needs inside the captured graph cost more than it saves.
-struct PrefetchItem { const void *ptr = nullptr; unsigned long long bytes = 0; };
-void launch_prefetch(const PrefetchItem *dev_items, int n, hipStream_t s);
 // fp32 packed weights (16-k blocks, kernels.h top) -> binary16 in the order of v_mfma_f32_16x16x32_f16's B fragment:
 //   dst[((ntile * (K / 32) + kb) * 64 + lane) * 8 + j] = W[kb * 32 + (lane >> 4) * 8 + j][ntile * 16 + (lane & 15)]
 // (one 16-byte read per lane and 32-k block; K a multiple of 32)

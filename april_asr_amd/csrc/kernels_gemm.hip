@@ -23,6 +23,7 @@
 // (reference call sites src/april_session.c:145,160,176).
 #include "kernels.h"
 #include "device_utils.h"
+#include "env.h"
 // the head of the hand-scheduled K loop on an 8-byte boundary: every instruction of the loop is an 8-byte encoding, so the phase of the
 // head is the phase of all of them (MI355X_MICROARCH.md: a hand-written stream loses up to 13 % at shifts of 4 mod 8; the round-5 build
 // had the gates kernel's head at 4 mod 8)
@@ -39,10 +40,10 @@
 namespace aprilx {
 
 
-template <int MT, int NT, int NW = 4>
+template <int MT, int NT>
 struct TileCfg {
     static constexpr int BM = MT * 16, BN = NT * 16, LDR = BN + 4;
-    static constexpr int LDS_FLOATS = NW * BM * LDR;      // one partial plane per wave; BM row scales follow (LDS_FLOATS + BM floats are requested)
+    static constexpr int LDS_FLOATS = 4 * BM * LDR;       // one partial plane per wave; BM row scales follow (LDS_FLOATS + BM floats are requested)
 };
 
 using h4 = __attribute__((ext_vector_type(4))) _Float16;
@@ -52,15 +53,11 @@ template <> struct WQuad<1> { using type = h4; };
 // ASM = 1: the K loop is the hand-scheduled one (fixed operand registers v112..v175, accumulators in AGPRs); a separate
 // instantiation, so that neither loop's registers weigh on the other (both forms must stay within 256 registers: two
 // workgroups per CU).  The compiler-scheduled 64-row tiles are told so (second launch-bound = waves per SIMD).
-// NW = waves per workgroup: 4, or 8 on the full-K schedule of a kz = 8 layer (every wave owns ONE slab).  With only 16 x 32
-// outputs per workgroup a wave has two accumulator tiles, i.e. chains of four DEPENDENT MFMAs back to back, which issue at
-// half rate (measured: 520 cycles per k-block instead of 256); a second wave on the same SIMD fills the gaps.
-template <int MT, int NT, int EPI, int AOP, int WT, int MODE, int ASM, int NW = 4>
+template <int MT, int NT, int EPI, int AOP, int WT, int MODE, int ASM>
 __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int zg, const unsigned wg_linear, const int bx, const int by, const bool one_m_block)
 {
-    using Cfg = TileCfg<MT, NT, NW>;
-    constexpr int NTH = NW * 64;
-    static_assert(NW == 4 || (NW == 8 && MODE == GM_FULLK), "8 waves only on the full-K schedule");
+    using Cfg = TileCfg<MT, NT>;
+    constexpr int NW = 4, NTH = NW * 64;                  // waves per workgroup (an eight-wave full-K form measured the same: LAB_NOTES.md)
     using BQ = typename WQuad<WT>::type;       // one lane's four consecutive k values of a weight tile
     extern __shared__ __attribute__((aligned(16))) float red[];
     constexpr bool FULLK = MODE == GM_FULLK;
@@ -91,7 +88,6 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int zg, const
     const int nt0 = bx * NT;
     const int m0 = by * Cfg::BM;
     // zg (GM_SLAB): this workgroup owns slabs [zg*zs, (zg+1)*zs)
-    first_round_skew(g.skew, (unsigned)wg_linear, (unsigned)g.skew_wgs);      // (measurement form, off by default: device_utils.h)
     const int KB = g.K >> 4;
 
     const int mrow = lane & 15, kq = lane >> 4;
@@ -201,11 +197,6 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int zg, const
     auto summed4 = [&](int o) {                        // GM_SLAB: ((p0+p1)+p2)+p3 of four consecutive columns; GM_FULLK: balanced tree over the waves' results
         const f32x4 p0 = *reinterpret_cast<const f32x4 *>(red + o), p1 = *reinterpret_cast<const f32x4 *>(red + PLANE + o);
         const f32x4 p2 = *reinterpret_cast<const f32x4 *>(red + 2 * PLANE + o), p3 = *reinterpret_cast<const f32x4 *>(red + 3 * PLANE + o);
-        if constexpr (NW == 8) {
-            const f32x4 p4 = *reinterpret_cast<const f32x4 *>(red + 4 * PLANE + o), p5 = *reinterpret_cast<const f32x4 *>(red + 5 * PLANE + o);
-            const f32x4 p6 = *reinterpret_cast<const f32x4 *>(red + 6 * PLANE + o), p7 = *reinterpret_cast<const f32x4 *>(red + 7 * PLANE + o);
-            return ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7));
-        }
         if (FULLK) return (p0 + p1) + (p2 + p3);
         return ((p0 + p1) + p2) + p3;
     };
@@ -688,11 +679,11 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int zg, const
     stamp(4);
 }
 
-template <int MT, int NT, int EPI, int AOP, int WT, int MODE, int ASM, int NW = 4>
-__global__ __launch_bounds__(NW * 64, (MT == 4 && !ASM) ? 2 : 1) void gemm_f32_kernel(GemmArgs g)
+template <int MT, int NT, int EPI, int AOP, int WT, int MODE, int ASM>
+__global__ __launch_bounds__(256, (MT == 4 && !ASM) ? 2 : 1) void gemm_f32_kernel(GemmArgs g)
 {
     if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp, (blockIdx.x | blockIdx.y | blockIdx.z) == 0);
-    gemm_body<MT, NT, EPI, AOP, WT, MODE, ASM, NW>(g, (int)blockIdx.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), (int)blockIdx.x, (int)blockIdx.y, gridDim.y == 1);
+    gemm_body<MT, NT, EPI, AOP, WT, MODE, ASM>(g, (int)blockIdx.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), (int)blockIdx.x, (int)blockIdx.y, gridDim.y == 1);
     if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp, gridDim.x * gridDim.y * gridDim.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
 }
 
@@ -709,7 +700,7 @@ __global__ __launch_bounds__(256, (MT == 4 && !ASM) ? 2 : 1) void gemm_f32_zkern
     // nor address-space round trips change that; measured against the by-value kernel at one problem per launch: no difference.)
     const GemmArgs g = zargs[zl];
     if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp, (blockIdx.x | blockIdx.y | blockIdx.z) == 0);
-    gemm_body<MT, NT, EPI, AOP, WT, MODE, ASM, 4>(g, (int)blockIdx.z - zl * zdiv, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), (int)blockIdx.x, (int)blockIdx.y, gridDim.y == 1);
+    gemm_body<MT, NT, EPI, AOP, WT, MODE, ASM>(g, (int)blockIdx.z - zl * zdiv, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), (int)blockIdx.x, (int)blockIdx.y, gridDim.y == 1);
     if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp, gridDim.x * gridDim.y * gridDim.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
 }
 
@@ -731,7 +722,7 @@ __global__ __launch_bounds__(256, (MT == 4 && !ASM) ? 2 : 1) void gemm_f32_zkern
         const int zl = bz / zdiv;
         const GemmArgs g = zargs[zl];
         if constexpr (EPI == EPI_LSTM) { stamp = g.stamp; stamp_begin(stamp, blockIdx.x == 0); }
-        gemm_body<MT, NT, EPI, AOP, WT, MODE, ASM, 4>(g, bz - zl * zdiv, (unsigned)tile, bx, by, gy == 1);
+        gemm_body<MT, NT, EPI, AOP, WT, MODE, ASM>(g, bz - zl * zdiv, (unsigned)tile, bx, by, gy == 1);
     }
     const int tile = (int)blockIdx.x + (int)gridDim.x;
     if (tile < ntiles) {
@@ -739,7 +730,7 @@ __global__ __launch_bounds__(256, (MT == 4 && !ASM) ? 2 : 1) void gemm_f32_zkern
         const int bx = tile % gx, r = tile / gx, by = r % gy, bz = r / gy;
         const int zl = bz / zdiv;
         const GemmArgs g = zargs[zl];
-        gemm_body<MT, NT, EPI, AOP, WT, MODE, ASM, 4>(g, bz - zl * zdiv, (unsigned)tile, bx, by, gy == 1);
+        gemm_body<MT, NT, EPI, AOP, WT, MODE, ASM>(g, bz - zl * zdiv, (unsigned)tile, bx, by, gy == 1);
     }
     if constexpr (EPI == EPI_LSTM) stamp_end(stamp, gridDim.x, blockIdx.x);
 }
@@ -756,12 +747,12 @@ __global__ __launch_bounds__(256, 1) void gemm_f32_zkernel_mixed(const GemmArgs 
     if (tile < nbig) {
         const int bx = tile % gx4, r = tile / gx4, by = r % gy, z = r / gy;
         const GemmArgs g = zargs[z];
-        gemm_body<4, 4, EPI, AOP, 0, MODE, 1, 4>(g, 0, (unsigned)tile, bx, by, gy == 1);
+        gemm_body<4, 4, EPI, AOP, 0, MODE, 1>(g, 0, (unsigned)tile, bx, by, gy == 1);
     } else {
         tile -= nbig;
         const int gx2 = 2 * gx4, bx = tile % gx2, by = tile / gx2;
         const GemmArgs g = zargs[nbig_problems];
-        gemm_body<4, 2, EPI, AOP, 0, MODE, 1, 4>(g, 0, (unsigned)(nbig + tile), bx, by, gy == 1);
+        gemm_body<4, 2, EPI, AOP, 0, MODE, 1>(g, 0, (unsigned)(nbig + tile), bx, by, gy == 1);
     }
 }
 
@@ -772,14 +763,12 @@ ProfileEvents &tl_profile_events() { static thread_local ProfileEvents pe; retur
 void gemm_profile_next_launch(hipEvent_t start, hipEvent_t stop) { ProfileEvents &pe = tl_profile_events(); pe.a = start; pe.b = stop; }
 bool gemm_profile_pending() { return tl_profile_events().a != nullptr; }
 
-static int env_int(const char *name, int def) { const char *v = getenv(name); return v && *v ? atoi(v) : def; }
-
 // The full-K schedule pays once output tiles alone occupy a good part of the chip.  Tiles: at most 64x32 (three
 // accumulator-sized register sets: chain, slab, tree level), at least 16x32 (a sum-of-squares granule is 32 columns).
 static bool plan_fullk(int M, int N, int kz, TilePlan &t, bool force = false, int zcount = 1)
 {
     static const int enabled = env_int("APRIL_FULLK", 1);
-    static const int min_wgs = env_int("APRIL_FULLK_MIN_WGS", 96);
+    constexpr int min_wgs = 96;
     if (!enabled || N % 32 != 0) return false;
     const int ncols = N / 32;
     int mt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
@@ -798,8 +787,8 @@ static bool plan_fullk(int M, int N, int kz, TilePlan &t, bool force = false, in
 //   hundred short workgroups is bound by its fixed costs -- pipeline fill, the second launch), so small launches keep the
 //   round-2 schedules.  Rule: no GM_TILE below 256 32-row tiles per launch; 64-row tiles once the launch holds 512 of them,
 //   32-row tiles otherwise; slabs per workgroup from a small cost model (below).
-// APRIL_TILE_MT / APRIL_TILE_ZS (or gemm_tile_pin) pin the choice for measurements.
-static int g_tile_pin_mt = env_int("APRIL_TILE_MT", 0), g_tile_pin_zs = env_int("APRIL_TILE_ZS", 0), g_tile_enable = -1;
+// gemm_tile_pin (tools/tile_bench) pins the choice for measurements.
+static int g_tile_pin_mt = 0, g_tile_pin_zs = 0, g_tile_enable = -1;
 void gemm_tile_pin(int enable, int mt, int zs) { g_tile_enable = enable; g_tile_pin_mt = mt; g_tile_pin_zs = zs; }
 
 // GM_PP (kernels_gemm_pp.hip): the fp16 gates / FFN-up GEMMs on 256 (128) x 128 ping-pong tiles.  One workgroup per CU (144 KB of stage
@@ -810,7 +799,8 @@ static int g_pp_enable = -1, g_pp_pin_mt = 0;
 void gemm_pp_pin(int enable, int mt) { g_pp_enable = enable; g_pp_pin_mt = mt; }
 static bool plan_pp(int M, int N, int zcount, TilePlan &t, bool wide_ok = false)
 {
-    static const int enabled = env_int("APRIL_GM_PP", 1), env_mt = env_int("APRIL_PP_MT", 0), min_tiles = env_int("APRIL_PP_MIN_TILES", 128);
+    static const int enabled = env_int("APRIL_GM_PP", 1), env_mt = env_int("APRIL_PP_MT", 0);
+    constexpr int min_tiles = 128;
     static const int wide = env_int("APRIL_PP_WIDE", 1);      // 256 x 192 tiles (kernels_gemm_pw.hip) where they save a round of workgroups
     if (!(g_pp_enable < 0 ? enabled : g_pp_enable) || N % 128 != 0) return false;
     const long zc = std::max(1, zcount);
@@ -837,38 +827,31 @@ static bool plan_pp(int M, int N, int zcount, TilePlan &t, bool wide_ok = false)
 static bool plan_tile(int M, int N, int kz, int zcount, bool force_full, TilePlan &t, bool always = false, bool big_ok = false, bool wide_ok = false, int pp_ok = 0)
 {
     static const int enabled = env_int("APRIL_GM_TILE", 1);
-    static const int min_rows = env_int("APRIL_TILE_MIN_ROWS", 32);
-    static const int fused_tiles = env_int("APRIL_TILE_FUSED_TILES", 512), split_tiles = env_int("APRIL_TILE_SPLIT_TILES", 256);
+    constexpr int min_rows = 32, fused_tiles = 512, split_tiles = 256;      // (the rule above)
     const int pin_mt = g_tile_pin_mt, pin_zs = g_tile_pin_zs;
     if (N % 64 != 0) return false;
     if (!always && (!(g_tile_enable < 0 ? enabled : g_tile_enable) || M < min_rows)) return false;
     const long zc = std::max(1, zcount);
     const long tiles4 = (long)(N / 64) * ((M + 63) / 64) * zc, tiles2 = (long)(N / 64) * ((M + 31) / 32) * zc;
     // (fp16 tile engines: 64-row tiles for the N = d_model GEMMs measured no better than 32-row ones at 512 sessions -- 13.2 vs 12.7 ms
-    // of projection + FFN time per 10 feeds -- so the same rule serves both precisions; APRIL_TILE_F16_MT pins it for measurements)
-    static const int f16_mt = env_int("APRIL_TILE_F16_MT", 0);
-    const int mt = pin_mt ? (pin_mt == 4 ? 4 : 2) : ((always && f16_mt) ? f16_mt : (tiles4 >= fused_tiles ? 4 : 2));
+    // of projection + FFN time per 10 feeds -- so the same rule serves both precisions)
+    const int mt = pin_mt ? (pin_mt == 4 ? 4 : 2) : (tiles4 >= fused_tiles ? 4 : 2);
     const long tiles = mt == 4 ? tiles4 : tiles2;
     if ((pp_ok & 1) && kz == 1 && pin_mt == 0 && plan_pp(M, N, zcount, t, (pp_ok & 2) != 0)) return true;
     if (big_ok && kz == 1 && N % 128 == 0 && pin_mt == 0) {
         // fp16 gates / FFN up: 128 x 128 tiles (eight waves) once they give most CUs a workgroup -- twice the flops per operand byte
-        static const int big = env_int("APRIL_TILE_BIG", 1), big_tiles = env_int("APRIL_TILE_BIG_TILES", 192), big_min_n = env_int("APRIL_TILE_BIG_MIN_N", 0);
+        static const int big = env_int("APRIL_TILE_BIG", 1);
+        constexpr int big_tiles = 192;
         const long tiles8 = (long)(N / 128) * ((M + 127) / 128) * zc;
-        if (big && tiles8 >= big_tiles && N >= big_min_n) {
-            t.mt = 8; t.nt = 8; t.zs = 1; t.mode = GM_TILE;
-            // APRIL_TILE_BIG_NT=12 (measurement): 128 x 192 tiles where N divides -- fewer, fatter workgroups: two 512-row problems of
-            // the larger encoder's gates are 256 tiles = one per CU (128 x 128: 384 tiles = one and a half rounds of one workgroup per CU)
-            static const int big_nt = env_int("APRIL_TILE_BIG_NT", 8);
-            if (big_nt == 12 && N % 192 == 0) t.nt = 12;
-            return true;
-        }
+        if (big && tiles8 >= big_tiles) { t.mt = 8; t.nt = 8; t.zs = 1; t.mode = GM_TILE; return true; }
     }
     int zs = kz;
     // fp16 N = d_model GEMMs (projection, FFN down) keep all of K in the workgroup, i.e. their fused row epilogue: the cost model below
     // prices a K cut at 5 % + 300, but the row kernel behind the planes and its launch boundary cost ~8 us at these sizes -- configs[4]
     // at 512 sessions 1.887 -> 1.820 ms per step with the cut forbidden (round 6; APRIL_TILE_F16_FULLK=0 restores the model's choice)
     // -- from 192 tiles per launch (one 512-row problem); below that the cut is what spreads the weights over the chip
-    static const int f16_fullk = env_int("APRIL_TILE_F16_FULLK", 1), f16_fullk_tiles = env_int("APRIL_TILE_F16_FULLK_TILES", 192);
+    static const int f16_fullk = env_int("APRIL_TILE_F16_FULLK", 1);
+    constexpr int f16_fullk_tiles = 192;
     if (always && f16_fullk && wide_ok && tiles >= f16_fullk_tiles) { }
     else if (pin_zs > 0) { if (!force_full) zs = std::min(kz, pin_zs); }
     else if (pin_mt > 0) { /* measurement: pinned tile rows, all of K */ }
@@ -888,41 +871,6 @@ static bool plan_tile(int M, int N, int kz, int zcount, bool force_full, TilePla
         }
     }
     t.mt = mt; t.nt = 4; t.zs = zs; t.mode = GM_TILE;
-    if (always && wide_ok && zs == kz && N % 96 == 0 && pin_mt == 0) {
-        // MEASUREMENT FORM, off (APRIL_TILE_NT6=1).  fp16 projection / FFN down, all of K in the workgroup: if these launches took as long as the
-        // operand bytes of their busiest CU (tools/pp_bench probe: 32 x 64 tiles three per CU, 128 x 128 and 256 x 128 ping-pong tiles one per
-        // CU all read ~63 GB/s per CU), 96-column tiles (N = 768 = 8 x 96: 192 / 256 tiles for three / two 512-row problems, one per CU,
-        // where 64 columns give 576 / 384) would take a third off them.  Built (64 x 96 / 32 x 96, four waves), bit-identical
-        // (tests/test_gpu_f16.py), measured: configs[4] 1.75 -> 1.81 ms per step (the N = d_model class 4.55 -> 4.80 ms per ten steps).
-        static const int nt6 = env_int("APRIL_TILE_NT6", 0);
-        if (nt6) {
-            long best = -1;
-            for (int cm : {2, 4}) for (int cn : {4, 6}) {
-                const long tl = (long)(N / (16 * cn)) * ((M + 16 * cm - 1) / (16 * cm)) * zc;
-                const long cost = ((tl + 255) / 256) * (16L * cm + 16L * cn) * 1000 + (cn == 4 && cm == mt ? 0 : 1);      // (ties keep the 64-column rule)
-                if (best < 0 || cost < best) { best = cost; t.mt = cm; t.nt = cn; }
-            }
-        }
-    }
-    if (wide_ok && N % 128 == 0 && M >= 48 && pin_mt == 0 && t.nt == 4) {
-        // fp16 projection / FFN down: 64 x 128 tiles, eight waves -- half the operand bytes per flop of 32 x 64; the cost model again,
-        // on those tiles
-        static const int wide = env_int("APRIL_TILE_WIDE", 0);      // measured: no gain (projection + FFN down 10.94 vs 11.02 ms per 10 feeds, more row-kernel work) -> off
-        if (wide) {
-            const long tw = (long)(N / 128) * ((M + 63) / 64) * zc;
-            int zw = kz;
-            if (!force_full && pin_zs == 0) {
-                long best = -1;
-                for (int z = kz; z >= 1; z >>= 1) {
-                    const long wgs = tw * (kz / z), per_cu = (wgs + 255) / 256;
-                    long cost = per_cu * (8L * z + 3) * 100;
-                    if (z < kz) cost += cost / 20 + 300;
-                    if (best < 0 || cost < best) { best = cost; zw = z; }
-                }
-            } else if (pin_zs > 0 && !force_full) zw = std::min(kz, pin_zs);
-            t.mt = 4; t.nt = 8; t.zs = zw;
-        }
-    }
     return true;
 }
 
@@ -939,14 +887,10 @@ bool gemm_fullk(int M, int N, int kz, bool force, int zcount, int tile_ok)
 // Tile shape and slabs per workgroup.  Depends on M only through occupancy; numerics are tile-independent.
 static TilePlan plan_tiles(int M, int N, int kz, int epi, bool force_fullk = false, int zcount = 1, int tile_ok = 0, int zcount_true = 1, bool f16 = false, int pp_ok = 0)
 {
-    // measurement knobs (default 0): 1/2 = smaller tiles for the fused-epilogue GEMMs (measured slower on MI355X:
-    // B=256 gates 27 -> 32..36 us, the kernel is limited by operand loads per MFMA, not by occupancy);
-    // 5 = 64x32 tiles for split-K GEMMs at M > 32
-    static const int tune = env_int("APRIL_GEMM_TUNE", 0);
     TilePlan t;
     if (tile_ok && (epi == EPI_PARTIAL || epi == EPI_HR || epi == EPI_RESID_SSQ || epi == EPI_SLOT_STORE || epi == EPI_LSTM || epi == EPI_BIAS_DSWISH || (epi == EPI_XPART && tile_ok == 2))) {
         // the caller asked gemm_fullk first: a row epilogue arrives only when that plan keeps all of K in the workgroup
-        if (plan_tile(M, N, kz, zcount_true, force_fullk || epi != EPI_PARTIAL, t, tile_ok == 2, (f16 || env_int("APRIL_TILE_BIG_F32", 0)) && tile_ok == 2 && (epi == EPI_LSTM || epi == EPI_BIAS_DSWISH || epi == EPI_XPART),
+        if (plan_tile(M, N, kz, zcount_true, force_fullk || epi != EPI_PARTIAL, t, tile_ok == 2, f16 && tile_ok == 2 && (epi == EPI_LSTM || epi == EPI_BIAS_DSWISH || epi == EPI_XPART),
                       tile_ok == 2 && (epi == EPI_PARTIAL || epi == EPI_HR || epi == EPI_RESID_SSQ), (f16 && tile_ok == 2) ? pp_ok : 0)) return t;
         if (tile_ok == 2) { fprintf(stderr, "libapril(mi355x): launch_gemm: no GM_TILE plan for an always-tile GEMM (M=%d N=%d kz=%d)\n", M, N, kz); abort(); }
     }
@@ -954,27 +898,12 @@ static TilePlan plan_tiles(int M, int N, int kz, int epi, bool force_fullk = fal
     const int ntiles = N / 16;
     t.mode = GM_SLAB;
     t.mt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
-    int mblocks = (M + t.mt * 16 - 1) / (t.mt * 16);
+    const int mblocks = (M + t.mt * 16 - 1) / (t.mt * 16);
     t.nt = 4;
     // (problems sharing a z-batched launch fill the chip together: wider tiles, i.e. the hand-scheduled 64x32 / 64x64 forms, at
     // fewer rows.  Only for 64-row tiles: the 16-row weight streams of the offline recurrence lose 12 % with 16x64 tiles.)
     const int zc = t.mt == 4 ? zcount : 1;
     while (t.nt > 1 && ((ntiles % t.nt) != 0 || (long)(ntiles / t.nt) * mblocks * kz * zc < 256)) t.nt >>= 1;
-    // FFN up (one slab, no walking form): a launch whose 64 x 64 tiles are one and a half per CU (three 256-row problems = 384) leaves half of
-    // the CUs with two workgroups and half with one; as 64 x 32 tiles it is three per CU.  APRIL_FF1_BALANCE (round 6): MEASUREMENT FORMS, off --
-    // 1 (three-problem launches as 64 x 32 tiles): 1.334 vs 1.333 ms per 256-session step; 2 (two-problem launches too: two workgroups per CU): 1.351 vs 1.334
-    static const int ff1_balance = env_int("APRIL_FF1_BALANCE", 0);
-    if (ff1_balance && epi == EPI_BIAS_DSWISH && t.mt == 4 && t.nt == 4 && kz == 1) {
-        const long tiles = (long)(ntiles / 4) * mblocks * zc;
-        if (tiles > 256 && tiles < 512 && tiles % 256 != 0 && (2 * tiles) % 256 == 0) t.nt = 2;
-        if (ff1_balance == 2 && tiles == 256) t.nt = 2;      // (two workgroups per CU instead of one)
-    }
-    if (tune && epi != EPI_PARTIAL && t.mt == 4 && (long)(ntiles / t.nt) * mblocks < 512) {
-        if (tune == 1) { t.mt = 2; mblocks = (M + 31) / 32; }
-        else if (tune == 2 && t.nt == 4) t.nt = 2;
-    }
-    if (tune == 5 && epi == EPI_PARTIAL && t.mt == 4 && t.nt == 4) t.nt = 2;
-    if (tune == 3 && epi != EPI_PARTIAL && t.mt == 4 && t.nt == 4) t.nt = 2;      // measurement: 64x32 fused tiles at every size (three workgroups per CU with the compiler loop)
     t.zs = 1;
     if (epi == EPI_PARTIAL) {
         // slabs per workgroup grow once the output tiles alone fill the chip; the 64x64 tile has registers for two
@@ -996,23 +925,10 @@ template <int MT, int NT, int EPI, int AOP, int MODE>
 static void launch_one(const GemmArgs &g, hipStream_t s)
 {
     constexpr bool HAS_ASM = MODE == GM_SLAB && MT == 4 && (NT == 4 || NT == 2) && AOP == AOP_NONE && (EPI == EPI_LSTM || EPI == EPI_BIAS_DSWISH);
-    if constexpr (MODE == GM_FULLK) {
-        static const int nw8 = env_int("APRIL_FULLK_NW8", 0);      // measured: no gain (the tiles are bound by L2 -> L1 bytes, ~24 B/clk/CU, not by MFMA issue)
-        if (g.kz == 8 && nw8) {       // one slab per wave
-            using Cfg8 = TileCfg<MT, NT, 8>;
-            dim3 grid8((unsigned)(g.N / Cfg8::BN), (unsigned)((g.M + Cfg8::BM - 1) / Cfg8::BM), 1);
-            const int sg8 = EPI == EPI_HR ? g.r_scale.groups : (EPI == EPI_SLOT_STORE && g.x_scale.ssq ? g.x_scale.groups : 0);
-            const size_t lds8 = (size_t)(Cfg8::LDS_FLOATS + Cfg8::BM + (sg8 ? Cfg8::BM * (sg8 + 1) : 0)) * sizeof(float);
-            if (g.wt == 1) APRIL_LAUNCH((gemm_f32_kernel<MT, NT, EPI, AOP, 1, MODE, 0, 8>), grid8, dim3(512), lds8, s, g);
-            else APRIL_LAUNCH((gemm_f32_kernel<MT, NT, EPI, AOP, 0, MODE, 0, 8>), grid8, dim3(512), lds8, s, g);
-            return;
-        }
-    }
     using Cfg = TileCfg<MT, NT>;
     dim3 grid((unsigned)(g.N / Cfg::BN), (unsigned)((g.M + Cfg::BM - 1) / Cfg::BM), (unsigned)(MODE == GM_FULLK ? 1 : g.kz / g.zs));
-    static const int ldspad = env_int("APRIL_GEMM_LDSPAD", 0);   // measurement: KiB of LDS to request at least (> 80 forces one workgroup per CU)
     const int sg = EPI == EPI_HR ? g.r_scale.groups : ((EPI == EPI_LSTM || EPI == EPI_SLOT_STORE || EPI == EPI_XPART) && g.x_scale.ssq ? g.x_scale.groups : 0);
-    const size_t lds = std::max((size_t)(Cfg::LDS_FLOATS + Cfg::BM + (sg ? Cfg::BM * (sg + 1) : 0)) * sizeof(float), (size_t)ldspad * 1024);
+    const size_t lds = (size_t)(Cfg::LDS_FLOATS + Cfg::BM + (sg ? Cfg::BM * (sg + 1) : 0)) * sizeof(float);
     if (g.wt == 1) { APRIL_LAUNCH((gemm_f32_kernel<MT, NT, EPI, AOP, 1, MODE, 0>), grid, dim3(256), lds, s, g); return; }
     if constexpr (HAS_ASM) {
         if (g.asm_loop && g.debug != 1) { APRIL_LAUNCH((gemm_f32_kernel<MT, NT, EPI, AOP, 0, MODE, 1>), grid, dim3(256), lds, s, g); return; }
@@ -1038,59 +954,41 @@ static bool dispatch(const GemmArgs &g, hipStream_t s)
 }
 
 // GM_KW (kernels_gemm_kw.hip) takes over a fused full-K plan of the K-split kernels -- the row-epilogue GEMMs on 16..64 x 32
-// GM_FULLK / GM_SLAB tiles, and (APRIL_KW_FF1) the FFN-up GEMM on its hand-scheduled slab tiles -- when the operands allow it
-// (gemm_kw_waves) and the launch is a few hundred rows: below APRIL_KW_MIN_ROWS the launch is latency-bound either way, above
-// the GM_TILE threshold plan_tile has already taken it.  The decision never changes a caller-visible property of the plan (all
-// of K in the workgroup, row work in the epilogue), so gemm_fullk / gemm_partials need not know.
-static int g_kw_enable = -1, g_kw_pin_mt = 0, g_kw_ff1 = -1;
-void gemm_kw_pin(int enable, int mt, int ff1) { g_kw_enable = enable; g_kw_pin_mt = mt; g_kw_ff1 = ff1; }
+// GM_FULLK / GM_SLAB tiles -- when the operands allow it (gemm_kw_waves) and the launch is a few hundred rows: below KW_MIN_ROWS
+// the launch is latency-bound either way, above the GM_TILE threshold plan_tile has already taken it.  The decision never changes a
+// caller-visible property of the plan (all of K in the workgroup, row work in the epilogue), so gemm_fullk / gemm_partials need not know.
+constexpr int KW_MIN_ROWS = 3;
+static int g_kw_enable = -1, g_kw_pin_mt = 0;
+void gemm_kw_pin(int enable, int mt) { g_kw_enable = enable; g_kw_pin_mt = mt; }
+static bool kw_enabled() { static const int enabled = env_int("APRIL_GM_KW", 1); return (g_kw_enable < 0 ? enabled : g_kw_enable) != 0; }
 static void plan_kw(const GemmArgs &g, TilePlan &t, int zc)
 {
-    static const int enabled = env_int("APRIL_GM_KW", 1), min_rows = env_int("APRIL_KW_MIN_ROWS", 3), max_rows = env_int("APRIL_KW_MAX_ROWS", 1 << 30);
-    static const int ff1 = env_int("APRIL_KW_FF1", 0), env_mt = env_int("APRIL_KW_MT", 0);
-    if (!(g_kw_enable < 0 ? enabled : g_kw_enable) || t.zs != g.kz) return;
+    static const int env_mt = env_int("APRIL_KW_MT", 0);
+    if (!kw_enabled() || t.zs != g.kz) return;
     if (t.mode == GM_TILE) {
         // a FUSED GM_TILE plan (all of K in the workgroup: the same caller-visible shape) keeps the launch unless its tiles fill the 512
         // resident slots badly: half a round or less, or a small remainder behind whole rounds (tools/kw_bench, FFN down: 512 x 2 rows
         // 31.3 (GM_TILE) vs 29.6 us (GM_KW); 768 x 3: 64.8 vs 59.0; 2300 x 2: 117 vs 112; but 1024 x 2: 47 vs 54, 2048 x 3: 123 vs 147)
         static const int over_tile = env_int("APRIL_KW_OVER_TILE", 1);
-        if (!over_tile || (g.epi != EPI_HR && g.epi != EPI_RESID_SSQ) || t.nt != 4) return;
+        if (!over_tile || t.nt != 4) return;
         const long tiles = (long)(g.N / 64) * ((g.M + 16 * t.mt - 1) / (16 * t.mt)) * zc;
         const long rem = tiles % 512;
         if (!(tiles <= 256 || (tiles > 512 && rem > 0 && rem <= 128))) return;
     }
-    if (g.M < min_rows || g.M > max_rows) return;
-    if (g.epi == EPI_LSTM) {
-        // MEASUREMENT FORM, off by default (APRIL_KW_GATES=1): the gates GEMM with its activation rows through the wave-private LDS rings, four
-        // waves = the four chunks, 32 / 64 x 32 tiles.  The idea: at one 64-row problem per launch the K-split 64 x 16 tiles spend 19.8 k cycles
-        // in a K loop of 8.2 k cycles of MFMA on their 16-row x 64-byte fragment loads (profiles/r05_gates_ffup_phase_trace.txt).  Bit-identical
-        // (tools/kw_bench), but the z-batched launches of the engine already run 64 x 32 / 64 x 64 hand-scheduled tiles that are within 25 % of
-        // their MFMA time: 64 rows x 1 / 2 / 3 problems 12.8 / 14.9 / 24.0 us (K-split) vs 9.5 / 15.0 / 23.8 (best GM_KW tile), 128 x 2:
-        // 22.8 vs 30.3, 256 x 2: 40.1 vs 55.3 -- a gain only for one-problem launches, a loss from 96 rows up.
-        static const int gates = env_int("APRIL_KW_GATES", 0), gates_max = env_int("APRIL_KW_GATES_MAX_ROWS", 96);
-        if (!gates || g.M < 17 || g.M > gates_max || gemm_kw_waves(g) != 4) return;
-        const int gmt = g_kw_pin_mt ? g_kw_pin_mt : (g.M > 32 ? 4 : 2);
-        if (!gemm_kw_has_kernel(g, gmt, 2)) return;         // (a pinned tile shape without a kernel: the previous plan stays)
-        t.mt = gmt; t.nt = 2; t.zs = 1; t.mode = GM_KW;
-        return;
-    }
-    if (g.epi == EPI_BIAS_DSWISH ? !(g_kw_ff1 < 0 ? ff1 : g_kw_ff1) : (g.epi != EPI_HR && g.epi != EPI_RESID_SSQ)) return;
-    const int nw = gemm_kw_waves(g);
-    if (!nw) return;
+    if (g.M < KW_MIN_ROWS || (g.epi != EPI_HR && g.epi != EPI_RESID_SSQ)) return;
+    if (!gemm_kw_waves(g)) return;
     int mt = g_kw_pin_mt ? g_kw_pin_mt : env_mt;
-    const int nt = (g.epi == EPI_BIAS_DSWISH && g.N % 64 == 0) ? 4 : 2;
     if (!mt) {
         // 32-row tiles are the efficient ones (one memory instruction per four MFMAs; 16-row tiles: three per eight), 16-row tiles the
         // finer grain: the launch takes ceil(tiles / 256 CUs) rounds, a 16-row round costs ~0.55 of a 32-row one (tools/kw_bench)
-        const long t32 = (long)(g.N / (16 * nt)) * ((g.M + 31) / 32) * zc, t16 = (long)(g.N / (16 * nt)) * ((g.M + 15) / 16) * zc;
-        mt = (nw == 8 && ((t16 + 255) / 256) * 55 < ((t32 + 255) / 256) * 100) ? 1 : 2;
+        const long t32 = (long)(g.N / 32) * ((g.M + 31) / 32) * zc, t16 = (long)(g.N / 32) * ((g.M + 15) / 16) * zc;
+        mt = ((t16 + 255) / 256) * 55 < ((t32 + 255) / 256) * 100 ? 1 : 2;
     }
-    if (nw == 4 && mt == 1) mt = 2;
-    const int knt = (mt == 4 && nw == 8 && g.N % 64 == 0) ? 4 : nt;      // (pinned 64-row tiles: 64 x 64, a wave tile of one memory instruction per eight MFMAs)
-    // environment knobs and pins can ask for shapes that were never instantiated (APRIL_KW_FF1 with N % 64 != 0, 64-row tiles on four
-    // waves or at N % 64 != 0 ...): the previous plan stays instead of an abort in launch_gemm_kw
-    if (!gemm_kw_has_kernel(g, mt, knt)) return;
-    t.mt = mt; t.nt = knt; t.zs = g.kz; t.mode = GM_KW;
+    const int nt = (mt == 4 && g.N % 64 == 0) ? 4 : 2;      // (pinned 64-row tiles: 64 x 64, a wave tile of one memory instruction per eight MFMAs)
+    // APRIL_KW_MT and gemm_kw_pin can ask for shapes that were never instantiated (64-row tiles at N % 64 != 0 ...): the previous plan
+    // stays instead of an abort in launch_gemm_kw
+    if (!gemm_kw_has_kernel(g, mt, nt)) return;
+    t.mt = mt; t.nt = nt; t.zs = g.kz; t.mode = GM_KW;
 }
 
 // plan + checks + measurement knobs: everything launch_gemm decides on the host
@@ -1098,7 +996,6 @@ static TilePlan finalize_gemm(GemmArgs &g)
 {
     static const int dbg = env_int("APRIL_GEMM_DEBUG", 0);
     g.debug = dbg;
-    static const int skew = env_int("APRIL_GEMM_SKEW", 0);        // first-round start skew, x 4096 cycles (below; measured neutral, off)
     static const int asm_loop = env_int("APRIL_GEMM_ASM", 1);     // 0 = compiler-scheduled loop everywhere (A/B)
     static const int z_tiles = env_int("APRIL_Z_TILES", 2);      // A/B: 0 = plan z-batched problems as if each had the chip to itself, 1 = hint everywhere, 2 = fused-epilogue slab tiles only, 3 = full-K tiles only
     const int zc = std::max(1, g.zcount);
@@ -1123,37 +1020,22 @@ static TilePlan finalize_gemm(GemmArgs &g)
     //   hand loop, no skew 42.2 / 85.6 / 159.2   hand loop, skew 2: 85.5 / 174.3   compiler loop, skew 2 (round-1 choice at two
     //   workgroups per CU): 91.3 / 170.4   compiler loop, no skew: 56.5 / 100.7 / 180.2;  FFN-up [2048,512]x[512,2048]: 42.3 vs 45.7
     g.asm_loop = asm_loop != 0;
-    // first-round start skew (device_utils.h first_round_skew; measured neutral, off): launches of several rounds of the fused-epilogue
-    // K-split tiles and of the four-wave GM_TILE tiles.  APRIL_GEMM_SKEW = delay in units of 4096 cycles, APRIL_SKEW_MIN_WGS = smallest launch.
-    {
-        static const int skew_min_wgs = env_int("APRIL_SKEW_MIN_WGS", 1536), skew_slots = env_int("APRIL_SKEW_SLOTS", 512);
-        const long wgs = (long)(g.N / (16 * t.nt)) * ((g.M + 16 * t.mt - 1) / (16 * t.mt)) * (t.mode == GM_FULLK ? 1 : g.kz / g.zs) * zc;
-        const bool several_per_cu = (t.mode == GM_TILE && t.nt == 4 && (t.mt == 4 || t.mt == 2)) || ((t.mode == GM_SLAB || t.mode == GM_FULLK) && is_slab_epi);
-        g.skew = (several_per_cu && wgs >= skew_min_wgs) ? skew : 0;
-        g.skew_wgs = skew_slots;
-    }
-    static const int kw_skew = env_int("APRIL_KW_SKEW", 0);      // GM_KW: start delay of the second half of a workgroup's waves, x 64 cycles (measured: no effect; kernels_gemm_kw.hip)
-    if (t.mode == GM_KW) g.skew = kw_skew;
-    if (t.mode == GM_PP) g.skew = 0;
-    static const int kw_xcd = env_int("APRIL_KW_XCD", 0);        // GM_KW: 2 = the 2 x 4 XCD order of the tiles (kernels_gemm_kw.hip kw_tile_of)
-    g.xcd_rc = t.mode == GM_KW ? kw_xcd : 0;
     return t;
 }
 
-// GM_KW instead of the weight-stream row kernel of kernels_recur.hip for the FFN-down GEMM from APRIL_KW_MIN_ROWS (3) rows:
+// GM_KW instead of the weight-stream row kernel of kernels_recur.hip for the FFN-down GEMM from KW_MIN_ROWS (3) rows:
 // 16 x 32 tiles on eight waves against two 16-column tiles on sixteen waves -- 4 / 8 / 16 sessions 0.499 / 0.537 / 0.602 -> 0.475 / 0.496 / 0.527 ms
 // per 100 ms feed, one or two rows the same within the noise (they stay on the stream kernels, as does the recurrent pair of a long feed)
 static bool kw_before_recur(const GemmArgs &g)
 {
-    static const int enabled = env_int("APRIL_GM_KW", 1), min_rows = env_int("APRIL_KW_MIN_ROWS", 3);
+    static_assert(KW_MIN_ROWS <= 16, "the row range below is [KW_MIN_ROWS, 16]");
     // (FFN down only: 9.5 .. 12.8 -> 8.2 us per launch at 8 .. 16 rows; the projection's stream kernel is the faster one there, 4.7 .. 5.4 vs 5.8 us)
-    return (g_kw_enable < 0 ? enabled : g_kw_enable) && min_rows <= 16 && g.M >= min_rows && g.M <= 16 && g.epi == EPI_RESID_SSQ && gemm_kw_waves(g) != 0;
+    return kw_enabled() && g.M >= KW_MIN_ROWS && g.M <= 16 && g.epi == EPI_RESID_SSQ && gemm_kw_waves(g) != 0;
 }
 
 void launch_gemm(const GemmArgs &g_in, hipStream_t s)
 {
     GemmArgs g = g_in;
-    g.ksplit = kw_before_recur(g) ? 1 : recur_ksplit(g, 1);
     if (!kw_before_recur(g)) if (const int rf = recur_form(g)) { launch_recur(g, rf, nullptr, 1, s); return; }
     const TilePlan t = finalize_gemm(g);
     if (t.mode == GM_PP) { if (t.nt == 12) launch_gemm_pw(g, nullptr, 0, s); else launch_gemm_pp(g, t.mt, nullptr, 0, s); return; }
@@ -1224,7 +1106,6 @@ void stage_gemm_z(const GemmArgs *items, int n, GemmArgs *staged)
     for (int i = 0; i < n; ++i) {
         staged[i] = items[i];
         staged[i].zcount = n;
-        staged[i].ksplit = 1;
         const TilePlan t = finalize_gemm(staged[i]);
         if (i == 0) t0 = t;
         const GemmArgs &a = staged[i], &b = staged[0];
@@ -1232,12 +1113,6 @@ void stage_gemm_z(const GemmArgs *items, int n, GemmArgs *staged)
             a.a_op != AOP_NONE || a.x_scale.groups != b.x_scale.groups || a.r_scale.groups != b.r_scale.groups || (a.x_scale.ssq == nullptr) != (b.x_scale.ssq == nullptr)) {
             fprintf(stderr, "libapril(mi355x): stage_gemm_z: the problems of one launch must have one shape\n"); abort();
         }
-    }
-    // the K cut of the <= 16-row stream kernels (kernels_recur.hip): one value for the launch, only when every problem brings its workspace
-    if (n > 0 && !kw_before_recur(staged[0])) {
-        int S = recur_ksplit(staged[0], n);
-        for (int i = 1; i < n && S > 1; ++i) if (recur_ksplit(staged[i], n) != S) S = 1;
-        for (int i = 0; i < n; ++i) staged[i].ksplit = S;
     }
 }
 
@@ -1249,21 +1124,6 @@ void launch_gemm_z(const GemmArgs *staged, int n, const GemmArgs *dev_args, hipS
     GemmArgs probe = g;
     const TilePlan t = finalize_gemm(probe);
     if (t.mode == GM_PP) {
-        // MEASUREMENT FORM, off by default (APRIL_PP_SPLIT=1).  One workgroup per CU, so a launch costs whole rounds of one tile time; when
-        // the n problems give more than one round of 256-row tiles but n - 1 of them exactly one (the larger encoder's gates at 512
-        // sessions: 96 tiles per problem, three problems = 288), the launch can be cut in two: n - 1 problems on 256-row tiles, the last
-        // one on the planner's choice for it alone (192 128-row tiles).  tools/pp_bench: 45.0 us against 50.6 (128-row tiles for all
-        // three) -- but inside the engine the three-problem launch already runs in 47.9 us and the pair costs 31.8 + 19: nothing gained
-        // (configs[4] step 1.881 vs 1.888 ms), so one launch stays the rule.
-        static const int split = env_int("APRIL_PP_SPLIT", 0);
-        const long per16 = (long)(g.N / 128) * ((g.M + 255) / 256);
-        if (split && t.nt != 12 && g_pp_pin_mt == 0 && n >= 2 && per16 * n > 256 && per16 * (n - 1) <= 256 && per16 * (n - 1) >= 160) {
-            launch_gemm_pp(g, 16, dev_args, n - 1, s);
-            TilePlan t1;
-            if (!plan_pp(g.M, g.N, 1, t1)) { t1.mt = 8; }
-            launch_gemm_pp(staged[n - 1], t1.mt, dev_args + (n - 1), 1, s);
-            return;
-        }
         if (t.nt == 12) launch_gemm_pw(g, dev_args, n, s);
         else launch_gemm_pp(g, t.mt, dev_args, n, s);
         return;

@@ -16,11 +16,11 @@
 // Canonical summation (kernels.h) is kept exactly: a chunk is one in-order MFMA chain over its k blocks, a slab is
 // ((c0 + c1) + c2) + c3, slabs meet pairwise in slab order.  Wave w owns chunks [w cpw, (w + 1) cpw), cpw = 4 kz / NW:
 //   cpw >= 4  whole slabs: folded in registers (S, then R = S0 + S1 for two slabs), the waves meet once as the balanced tree
-//             ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7))   (NW = 8)   or   (p0 + p1) + (p2 + p3)   (NW = 4)
-//   cpw == 1  one chunk per wave: the planes meet as ((p0 + p1) + p2) + p3 per slab, two slabs (NW = 8, kz = 2) as s0 + s1
+//             ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7))
+//   cpw == 1  one chunk per wave: the planes meet as ((p0 + p1) + p2) + p3 per slab, two slabs (kz = 2) as s0 + s1
 // => bit-identical to GM_SLAB / GM_FULLK / GM_TILE at any batch size (tools/kw_bench compares every output bitwise; the engine's
 // batch-invariance tests cross the schedule boundary).
-// Epilogues: EPI_HR (projection), EPI_RESID_SSQ (FFN down), EPI_BIAS_DSWISH (FFN up, four waves), term by term those of gemm_body.
+// Epilogues: EPI_HR (projection), EPI_RESID_SSQ (FFN down), term by term those of gemm_body.
 // Replaces the MatMul nodes of the encoder graph (reference call site src/april_session.c:131-148).
 #include "kernels.h"
 #include "device_utils.h"
@@ -43,8 +43,9 @@ template <int N> __device__ __forceinline__ void wait_vm()
 }
 __device__ __forceinline__ void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }      // lgkmcnt(0) only
 
-// Tile 16 MT x 16 NT per workgroup, NW waves splitting K, D ring stages per wave
-template <int MT, int NT, int NW, int D> struct KwGeom {
+// Tile 16 MT x 16 NT per workgroup, NW waves splitting K, D ring stages per wave (four stages measured the same at twice the LDS: LAB_NOTES.md)
+constexpr int NW = 8, D = 2;
+template <int MT, int NT> struct KwGeom {
     static constexpr int BM = 16 * MT, BN = 16 * NT, LDR = BN + 4, NTH = 64 * NW;
     static constexpr int STAGE_BYTES = BM * 128;                          // two k blocks of the tile's rows
     static constexpr int RING_BYTES = D * STAGE_BYTES, PLANE_BYTES = BM * LDR * 4;
@@ -55,16 +56,13 @@ template <int MT, int NT, int NW, int D> struct KwGeom {
     static constexpr int LX = NPIECE, LY = 2 * NT, GSZ = LX + LY;         // memory operations per stage: {DMA pieces}, {B of k blocks 0, 1}
 };
 
-template <int MT, int NT, int NW, int EPI, int D, int CPW>
+template <int MT, int NT, int EPI, int CPW>
 __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, const int by, const unsigned wg_linear)
 {
-    using G = KwGeom<MT, NT, NW, D>;
+    using G = KwGeom<MT, NT>;
     constexpr int BM = G::BM, BN = G::BN, LDR = G::LDR, NTH = G::NTH, PLANE = G::PLANE;
     constexpr bool ROW_EPI = EPI == EPI_HR || EPI == EPI_RESID_SSQ;
-    constexpr bool LSTM = EPI == EPI_LSTM;                // gates: A = [y | h(slot)] in two K segments, four waves = the four chunks, cell epilogue
-    static_assert(ROW_EPI || EPI == EPI_BIAS_DSWISH || LSTM, "no GM_KW form of this epilogue");
-    static_assert(!LSTM || (NW == 4 && CPW == 1), "the gates GEMM has one slab: a chunk per wave");
-    static_assert(NW == 4 || NW == 8, "four or eight waves");
+    static_assert(ROW_EPI, "no GM_KW form of this epilogue");
     static_assert(CPW == 1 || CPW == 4, "a wave owns one chunk or one slab");
     constexpr bool DB1 = MT * NT >= 16;                    // 64 x 64 wave tiles: the register-lean form of the K loop (below)
     extern __shared__ __attribute__((aligned(1024))) float red[];
@@ -94,9 +92,8 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
     const int cs = c >> 1;                                // stages per chunk
 
     // ---- BasicNorm scale of the residual rows (EPI_HR): partials fetched first thing, reduced through LDS after the K loop
-    // (EPI_LSTM: the scale of x = y * scale(y), folded into the sum of the y half: ((p0 + p1) * scale + p2) + p3)
-    const RowScale &rsc = LSTM ? g.x_scale : g.r_scale;
-    const bool NEED_SCL = (EPI == EPI_HR || LSTM) && rsc.ssq != nullptr;
+    const RowScale &rsc = g.r_scale;
+    const bool NEED_SCL = EPI == EPI_HR && rsc.ssq != nullptr;
     float *scl = red + G::LDS_MAIN / 4;
     float stg[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     constexpr int TPR = NTH / BM;
@@ -116,12 +113,10 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
     // (uniform 64-bit base that advances with the stage + one 32-bit byte offset per lane and piece: the saddr form of the load;
     // all operands are far below 4 GiB per array)
     uint32_t aoff[G::NPIECE];
-    // (EPI_LSTM: waves 0, 1 walk the two chunks of K segment 0 = the y rows, waves 2, 3 those of segment 1 = the h rows of the rows' slots)
-    const bool seg1 = LSTM && wave >= 2;                    // uniform
-    const char *abase = seg1 ? reinterpret_cast<const char *>(g.a1) + (size_t)(first_kb * 16 - g.K0) * 4 : reinterpret_cast<const char *>(g.a0) + (size_t)first_kb * 64;
+    const char *abase = reinterpret_cast<const char *>(g.a0) + (size_t)first_kb * 64;
     {
-        const int *aidx = seg1 ? g.aidx1 : g.aidx0;
-        const int lda = seg1 ? g.lda1 : g.lda0;
+        const int *aidx = g.aidx0;
+        const int lda = g.lda0;
         int arows[G::NPIECE];
 #pragma unroll
         for (int i = 0; i < G::NPIECE; ++i) {
@@ -187,33 +182,10 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
     // ---- what the epilogue reads besides the sums: fetched before the K loop (as in gemm_body); the 64 x 64 wave tiles have no registers
     // to park it in during the loop (accumulators + slab sums + a stage of weights = 224 of 256) and fetch it behind the loop instead
     constexpr int QROW = BN / 4, NQ = BM * QROW, QPT = (NQ + NTH - 1) / NTH;
-    f32x4 e_bias[QPT], e_res[ROW_EPI ? QPT : 1];
-    int e_slot[ROW_EPI ? QPT : 1];
+    f32x4 e_bias[QPT], e_res[QPT];
+    int e_slot[QPT];
     bool e_ok[QPT];
-    float *l_cptr[LSTM ? QPT : 1];                        // EPI_LSTM: this thread's (row, hidden unit) cells: slot -> previous cell value, fetched up front
-    float l_cprev[LSTM ? QPT : 1];
     auto fetch_epilogue_operands = [&]() {
-    if constexpr (LSTM) {
-        int qslot[QPT];
-#pragma unroll
-        for (int i = 0; i < QPT; ++i) {
-            const int q = threadIdx.x + i * NTH;
-            int r = m0 + q / QROW;
-            e_ok[i] = q < NQ && r < g.M;
-            if (r >= g.M) r = g.M - 1;
-            qslot[i] = gload<int>(g.slot_idx + r);
-        }
-#pragma unroll
-        for (int i = 0; i < QPT; ++i) {
-            const int q = threadIdx.x + i * NTH;
-            const int n = q < NQ ? n0 + (q % QROW) * 4 : n0;
-            l_cptr[i] = g.c_state + (size_t)qslot[i] * g.hidden + (n >> 2);      // (padding rows point at the last row's cell: read, never stored)
-            e_bias[i] = gload<f32x4>(g.bias + n);
-        }
-#pragma unroll
-        for (int i = 0; i < QPT; ++i) l_cprev[i] = gload<float>(l_cptr[i]);
-        return;
-    }
 #pragma unroll
     for (int i = 0; i < QPT; ++i) {
         const int q = threadIdx.x + i * NTH;
@@ -222,10 +194,8 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
         if (m >= g.M) m = g.M - 1;
         const int qn = q < NQ ? n0 + (q % QROW) * 4 : n0;
         e_bias[i] = (EPI != EPI_HR) ? gload<f32x4>(g.bias + qn) : f32x4{0.f, 0.f, 0.f, 0.f};
-        if (ROW_EPI) {
-            e_slot[i] = (EPI == EPI_HR && g.slot_idx) ? gload<int>(g.slot_idx + m) : m;
-            e_res[i] = (EPI == EPI_HR || (EPI == EPI_RESID_SSQ && g.resid)) ? gload<f32x4>(g.resid + (size_t)m * g.ldr + qn) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+        e_slot[i] = (EPI == EPI_HR && g.slot_idx) ? gload<int>(g.slot_idx + m) : m;
+        e_res[i] = (EPI == EPI_HR || (EPI == EPI_RESID_SSQ && g.resid)) ? gload<f32x4>(g.resid + (size_t)m * g.ldr + qn) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     };
     // (16-row projection tiles: 80 registers = six waves per SIMD = three workgroups per CU, so that the 768 workgroups of a three-problem
@@ -297,10 +267,7 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
     // LY(s + D) behind its second, and waits for LX(s + 1) in between -- (D - 1) GSZ younger operations stay in flight (the tail
     // counts down; the weights are register loads, which the compiler's own counts cover).  Nothing here is shared between waves:
     // no barrier.  The stage is [MFMA block][issue][MFMA block][issue] with the two issue halves about equal (FFN down, two problems:
-    // 17.0 -> 16.1 us against all issue behind the first block).  g.skew (APRIL_KW_SKEW, default 0) delays the second half of the waves
-    // by that many x 64 cycles at the start: measured 0 .. 14, no effect (profiles/r05_kw_phase_trace.txt) -- the two waves of a SIMD
-    // do not settle into alternating phases, and what a memory instruction costs beside MFMAs does not depend on which wave issues it
-    // (tools/vmem_mfma_probe); kept as a measurement knob.
+    // 17.0 -> 16.1 us against all issue behind the first block).
     f32x4 a0[MT], a1[MT];
 #ifdef APRIL_KW_ABLATE
 #pragma unroll
@@ -310,7 +277,6 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
         // one stage of weights in registers, two stages of activation rows in the ring (D == 2).  Issue order: DMA(0) DMA(1) Be(0) Bo(0) |
         // iteration s: {DMA(s + 2), Be(s + 1)} behind the first k block, {Bo(s + 1)} behind the second; the explicit wait in between is for
         // DMA(s + 1), younger than it: Be(s), Bo(s), DMA(s + 2), Be(s + 1) (the weights are register loads: the compiler's own counts)
-        static_assert(D == 2, "two ring stages");
         if (g.debug != 1) {
             issue_dma(0); issue_dma(1); load_b(be[0]); load_b(bo[0]);
             wait_vm<G::NPIECE + 2 * NT>();                 // DMA(0) has landed
@@ -359,7 +325,6 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
         wait_vm<(D - 1) * G::GSZ + G::LY>();               // LX(0) has landed
         __builtin_amdgcn_sched_barrier(0);
         read_frags(0, 0, a0);
-        if (wave >= NW / 2) for (int i = 0; i < g.skew; ++i) __builtin_amdgcn_s_sleep(1);
         stamp(1);
         auto stage = [&](const int slot, const bool more, auto wait_next) {
             read_frags(slot, 1, a1);
@@ -392,16 +357,9 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
         }
         // tail: stages nstage - D .. nstage - 1 (slots 0 .. D - 1), nothing left to issue; younger than LX(s + 1): LY(s + 1) and the
         // whole groups of stages s + 2 .. nstage - 1
-        static_assert(D == 2 || D == 4, "ring depth 2 or 4");
-        if constexpr (D == 4) {
-            stage(0, false, [] { wait_vm<G::LY + 2 * G::GSZ>(); });
-            stage(1, false, [] { wait_vm<G::LY + G::GSZ>(); });
-            stage(2, false, [] { wait_vm<G::LY>(); });
-            stage(3, false, [] {});
-        } else {
-            stage(0, false, [] { wait_vm<G::LY>(); });
-            stage(1, false, [] {});
-        }
+        static_assert(D == 2, "the tail below is that of a two-stage ring");
+        stage(0, false, [] { wait_vm<G::LY>(); });
+        stage(1, false, [] {});
     }
     if constexpr (LATE_EPI) fetch_epilogue_operands();
     stamp(2);
@@ -458,38 +416,11 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
     auto summed4 = [&](int o) {
         const f32x4 p0 = *reinterpret_cast<const f32x4 *>(red + o), p1 = *reinterpret_cast<const f32x4 *>(red + PLANE + o);
         const f32x4 p2 = *reinterpret_cast<const f32x4 *>(red + 2 * PLANE + o), p3 = *reinterpret_cast<const f32x4 *>(red + 3 * PLANE + o);
-        if constexpr (NW == 8) {
-            const f32x4 p4 = *reinterpret_cast<const f32x4 *>(red + 4 * PLANE + o), p5 = *reinterpret_cast<const f32x4 *>(red + 5 * PLANE + o);
-            const f32x4 p6 = *reinterpret_cast<const f32x4 *>(red + 6 * PLANE + o), p7 = *reinterpret_cast<const f32x4 *>(red + 7 * PLANE + o);
-            if (cpw >= 4) return ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7));        // eight tree nodes
-            return (((p0 + p1) + p2) + p3) + (((p4 + p5) + p6) + p7);                      // two slabs of four chunks
-        } else {
-            if (cpw >= 4) return (p0 + p1) + (p2 + p3);                                     // four tree nodes
-            return ((p0 + p1) + p2) + p3;                                                   // one slab of four chunks
-        }
+        const f32x4 p4 = *reinterpret_cast<const f32x4 *>(red + 4 * PLANE + o), p5 = *reinterpret_cast<const f32x4 *>(red + 5 * PLANE + o);
+        const f32x4 p6 = *reinterpret_cast<const f32x4 *>(red + 6 * PLANE + o), p7 = *reinterpret_cast<const f32x4 *>(red + 7 * PLANE + o);
+        if (cpw >= 4) return ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7));        // eight tree nodes
+        return (((p0 + p1) + p2) + p3) + (((p4 + p5) + p6) + p7);                      // two slabs of four chunks
     };
-    if constexpr (LSTM) {
-        // every load this epilogue depends on was issued before the K loop: settle them once, so that nothing in the loop below waits on
-        // the memory counter while the previous quad's stores are in flight (gemm_body)
-        wait_vm<0>();
-#pragma unroll
-        for (int i = 0; i < QPT; ++i) {
-            const int q = threadIdx.x + i * NTH;
-            const int row = q / QROW, col = (q % QROW) * 4;
-            const int o = row * LDR + col;
-            f32x4 gt = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (q < NQ) {
-                const f32x4 p0 = *reinterpret_cast<const f32x4 *>(red + o), p1 = *reinterpret_cast<const f32x4 *>(red + PLANE + o);
-                const f32x4 p2 = *reinterpret_cast<const f32x4 *>(red + 2 * PLANE + o), p3 = *reinterpret_cast<const f32x4 *>(red + 3 * PLANE + o);
-                // x = y * scale(y) entered the GEMM as y: the y half of the sum takes the row's scale; without a scale the plain slab
-                if (NEED_SCL) gt = (((p0 + p1) * scl[row] + p2) + p3) + e_bias[i];
-                else gt = (((p0 + p1) + p2) + p3) + e_bias[i];
-            }
-            const float c_new = fast_sigmoid(gt.y) * l_cprev[i] + fast_sigmoid(gt.x) * fast_tanh(gt.z);
-            const float u = fast_sigmoid(gt.w) * fast_tanh(c_new);
-            if (e_ok[i]) { gstore<float>(l_cptr[i], c_new); gstore<float>(g.out + (size_t)(m0 + row) * g.ldo + ((n0 + col) >> 2), u); }
-        }
-    } else
 #pragma unroll
     for (int i = 0; i < QPT; ++i) {
         const int q = threadIdx.x + i * NTH;
@@ -502,7 +433,7 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
                 gstore<f32x4>(g.state + (size_t)e_slot[i] * g.ld_state + n, v);
                 gstore<f32x4>(g.out + (size_t)m * g.ldo + n, e_res[i] * rs + v);
             }
-        } else if (EPI == EPI_RESID_SSQ) {
+        } else {   // EPI_RESID_SSQ
             const bool ok = e_ok[i];
             f32x4 y = f32x4{0.f, 0.f, 0.f, 0.f};
             if (ok) {
@@ -512,115 +443,32 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
             }
             const float ss = granule_ssq(y);               // all lanes take part in the shuffles
             if (ok && (q & 7) == 0) gstore<float>(g.ssq_out + (size_t)m * (g.N / SSQ_COLS) + n / SSQ_COLS, ss);
-        } else {   // EPI_BIAS_DSWISH
-            if (e_ok[i]) {
-                const f32x4 y = v + e_bias[i];
-                f32x4 o;
-                o.x = y.x * fast_sigmoid(y.x - 1.0f); o.y = y.y * fast_sigmoid(y.y - 1.0f);
-                o.z = y.z * fast_sigmoid(y.z - 1.0f); o.w = y.w * fast_sigmoid(y.w - 1.0f);
-                gstore<f32x4>(g.out + (size_t)m * g.ldo + n, o);
-            }
         }
     }
     stamp(4);
 #undef APRIL_KW_EACH
 }
 
-// waves per SIMD the register budget must allow: one eight-wave workgroup per CU (the 128 registers of two spill inside the K loop) -- three for the
-// 16-row projection tiles --, three four-wave ones
-// Which tile a workgroup takes.  Workgroups go to the eight XCDs round robin in dispatch order, so with the plain mapping (column tile =
-// blockIdx.x) an XCD owns two of the sixteen column tiles of an N = 512 problem and ALL of its rows: the weights cross the fabric once,
-// the activation rows eight times.  xcd_rc = 2 deals the tiles as 2 row halves x 4 column quarters instead: XCD x = 4 r + c
-// takes rows of half r and columns of quarter c, the j-th workgroup it receives walks its sub-block column-fastest -- weights twice, rows
-// four times across the fabric.  Needs grid.x % 4 == 0 and grid.y % 2 == 0 (then every problem of a z-batched launch starts at XCD 0).
-__device__ __forceinline__ void kw_tile_of(const int xcd_rc, int &bx, int &by)
+template <int MT, int NT, int EPI, int CPW>
+__global__ __launch_bounds__(64 * NW, (MT == 1 && EPI == EPI_HR) ? 6 : 2) void gemm_kw_kernel(GemmArgs g)
 {
-    const int gx = (int)gridDim.x, gy = (int)gridDim.y;
-    bx = (int)blockIdx.x; by = (int)blockIdx.y;
-    if (xcd_rc == 2 && (gx & 3) == 0 && (gy & 1) == 0) {
-        const int L = bx + gx * by;
-        const int x = L & 7, j = L >> 3, qx = gx >> 2, hy = gy >> 1;
-        by = (x >> 2) * hy + j / qx;
-        bx = (x & 3) * qx + j % qx;
-    }
-}
-
-template <int MT, int NT, int NW, int EPI, int D, int CPW>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? ((MT == 1 && EPI == EPI_HR) ? 6 : 2) : (MT == 4 ? 2 : 3)) void gemm_kw_kernel(GemmArgs g)
-{
-    int bx, by;
-    kw_tile_of(g.xcd_rc, bx, by);
-    gemm_kw_body<MT, NT, NW, EPI, D, CPW>(g, bx, by, blockIdx.x + gridDim.x * blockIdx.y);
+    gemm_kw_body<MT, NT, EPI, CPW>(g, (int)blockIdx.x, (int)blockIdx.y, blockIdx.x + gridDim.x * blockIdx.y);
 }
 
 // n independent same-shape problems in one launch (see gemm_f32_zkernel): blockIdx.z picks the argument block
-template <int MT, int NT, int NW, int EPI, int D, int CPW>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? ((MT == 1 && EPI == EPI_HR) ? 6 : 2) : (MT == 4 ? 2 : 3)) void gemm_kw_zkernel(const GemmArgs *__restrict__ zargs)
+template <int MT, int NT, int EPI, int CPW>
+__global__ __launch_bounds__(64 * NW, (MT == 1 && EPI == EPI_HR) ? 6 : 2) void gemm_kw_zkernel(const GemmArgs *__restrict__ zargs)
 {
     const GemmArgs g = zargs[blockIdx.z];
-    int bx, by;
-    kw_tile_of(g.xcd_rc, bx, by);
-    gemm_kw_body<MT, NT, NW, EPI, D, CPW>(g, bx, by, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+    gemm_kw_body<MT, NT, EPI, CPW>(g, (int)blockIdx.x, (int)blockIdx.y, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
 }
 
-// Mixed tiles for a z-batched launch whose 32-row tiles are not a whole number of rounds (three 256-row problems at N = 512: 384 tiles of
-// 32 x 32 = one and a half per CU; as 16-row tiles 768 = three per CU, the planner's choice so far): the first n - 1 problems on 32-row tiles,
-// the last one on 16-row tiles -- 256 + 256 workgroups, every CU one of each (a 16-row round costs ~0.55 of a 32-row one: 1.55 against
-// 1.65).  One-dimensional grid, the 32-row tiles first.  Same bodies, same arguments per tile: the sums do not depend on the tile shape.
-// MEASUREMENT FORM, off (APRIL_KW_MIXED=1): bit-identical, but 1.334-1.345 against 1.320 ms per 256-session step -- the 16-row workgroups of the
-// plain launch run up to six per CU and hide each other's latencies, two per CU beside a 32-row one do not (the FFN-up twin of this form pays: kernels_gemm.hip).
-template <int NT, int NW, int EPI, int D, int CPW>
-__global__ __launch_bounds__(64 * NW, 2) void gemm_kw_zkernel_mixed(const GemmArgs *__restrict__ zargs, int gx, int gy32, int nbig_problems)
-{
-    const int nbig = gx * gy32 * nbig_problems;
-    int tile = (int)blockIdx.x;
-    if (tile < nbig) {
-        const int bx = tile % gx, r = tile / gx, by = r % gy32, z = r / gy32;
-        const GemmArgs g = zargs[z];
-        gemm_kw_body<2, NT, NW, EPI, D, CPW>(g, bx, by, (unsigned)tile);
-    } else {
-        tile -= nbig;
-        const GemmArgs g = zargs[nbig_problems];
-        gemm_kw_body<1, NT, NW, EPI, D, CPW>(g, tile % gx, tile / gx, (unsigned)(nbig + tile));
-    }
-}
-
-// the mixed form applies (launch_kw_one<1, ...> asks): n problems whose 32-row tiles leave a partial round while n - 1 of them and the
-// last one's 16-row tiles are whole rounds
-template <int NT, int NW, int EPI, int D, int CPW>
-bool launch_kw_mixed(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t s)
-{
-    static const int mixed = [] { const char *v = getenv("APRIL_KW_MIXED"); return v && *v ? atoi(v) : 0; }();
-    if (!mixed || !dev_args || n < 2 || g.xcd_rc != 0 || g.M % 32 != 0) return false;
-    using G2 = KwGeom<2, NT, NW, D>;
-    using G1 = KwGeom<1, NT, NW, D>;
-    const long gx = g.N / G2::BN, gy32 = g.M / 32, t32 = gx * gy32, t16 = 2 * t32;
-    if ((t32 * n) % 256 == 0 || (t32 * (n - 1)) % 256 != 0 || t16 % 256 != 0) return false;
-    const int sg = (EPI == EPI_HR && g.r_scale.ssq) ? g.r_scale.groups : 0;
-    const size_t lds2 = (size_t)G2::LDS_MAIN + (size_t)(G2::BM + (sg ? G2::BM * (sg + 1) : 0)) * sizeof(float);
-    const size_t lds1 = (size_t)G1::LDS_MAIN + (size_t)(G1::BM + (sg ? G1::BM * (sg + 1) : 0)) * sizeof(float);
-    const size_t lds = lds2 > lds1 ? lds2 : lds1;
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_kw_zkernel_mixed<NT, NW, EPI, D, CPW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_devs.fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((gemm_kw_zkernel_mixed<NT, NW, EPI, D, CPW>), dim3((unsigned)(t32 * (n - 1) + t16)), dim3(G2::NTH), lds, s, dev_args, (int)gx, (int)gy32, n - 1);
-    return true;
-}
-
-template <int MT, int NT, int NW, int EPI, int D, int CPW>
+template <int MT, int NT, int EPI, int CPW>
 void launch_kw_one(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t s)
 {
-    if constexpr (MT == 1 && NW == 8 && NT == 2 && (EPI == EPI_HR || EPI == EPI_RESID_SSQ)) {
-        if (launch_kw_mixed<NT, NW, EPI, D, CPW>(g, dev_args, n, s)) return;
-    }
-    using G = KwGeom<MT, NT, NW, D>;
+    using G = KwGeom<MT, NT>;
     dim3 grid((unsigned)(g.N / G::BN), (unsigned)((g.M + G::BM - 1) / G::BM), (unsigned)std::max(1, n));
-    const int sg = (EPI == EPI_HR && g.r_scale.ssq) ? g.r_scale.groups : ((EPI == EPI_LSTM && g.x_scale.ssq) ? g.x_scale.groups : 0);
+    const int sg = (EPI == EPI_HR && g.r_scale.ssq) ? g.r_scale.groups : 0;
     const size_t lds = (size_t)G::LDS_MAIN + (size_t)(G::BM + (sg ? G::BM * (sg + 1) : 0)) * sizeof(float);
     // dynamic LDS beyond 64 KB has to be announced, per instantiation AND per device (see kernels_gemm_tile.hip)
     static std::atomic<uint64_t> attr_devs{0};
@@ -628,81 +476,53 @@ void launch_kw_one(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream
     (void)hipGetDevice(&dev);
     const uint64_t bit = 1ull << (dev & 63);
     if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_kw_kernel<MT, NT, NW, EPI, D, CPW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_kw_zkernel<MT, NT, NW, EPI, D, CPW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_kw_kernel<MT, NT, EPI, CPW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_kw_zkernel<MT, NT, EPI, CPW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_devs.fetch_or(bit, std::memory_order_release);
     }
-    if (dev_args) hipLaunchKernelGGL((gemm_kw_zkernel<MT, NT, NW, EPI, D, CPW>), grid, dim3(G::NTH), lds, s, dev_args);
-    else hipLaunchKernelGGL((gemm_kw_kernel<MT, NT, NW, EPI, D, CPW>), grid, dim3(G::NTH), lds, s, g);
+    if (dev_args) hipLaunchKernelGGL((gemm_kw_zkernel<MT, NT, EPI, CPW>), grid, dim3(G::NTH), lds, s, dev_args);
+    else hipLaunchKernelGGL((gemm_kw_kernel<MT, NT, EPI, CPW>), grid, dim3(G::NTH), lds, s, g);
 }
 
-template <int MT, int NT, int NW, int D>
+template <int MT, int NT>
 bool dispatch_kw(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t s, bool dry)
 {
     const int cpw = 4 * g.kz / NW;
-    if constexpr (NW == 8) {
-        if (g.epi == EPI_HR && cpw == 4) { if (!dry) launch_kw_one<MT, NT, NW, EPI_HR, D, 4>(g, dev_args, n, s); return true; }
-        if (g.epi == EPI_HR && cpw == 1) { if (!dry) launch_kw_one<MT, NT, NW, EPI_HR, D, 1>(g, dev_args, n, s); return true; }
-        if (g.epi == EPI_RESID_SSQ && cpw == 4) { if (!dry) launch_kw_one<MT, NT, NW, EPI_RESID_SSQ, D, 4>(g, dev_args, n, s); return true; }
-        if (g.epi == EPI_RESID_SSQ && cpw == 1) { if (!dry) launch_kw_one<MT, NT, NW, EPI_RESID_SSQ, D, 1>(g, dev_args, n, s); return true; }
-    } else {
-        if (g.epi == EPI_BIAS_DSWISH && cpw == 1) { if (!dry) launch_kw_one<MT, NT, NW, EPI_BIAS_DSWISH, D, 1>(g, dev_args, n, s); return true; }
-        if constexpr (NT == 2) { if (g.epi == EPI_LSTM && cpw == 1) { if (!dry) launch_kw_one<MT, NT, NW, EPI_LSTM, D, 1>(g, dev_args, n, s); return true; } }
-    }
+    if (g.epi == EPI_HR && cpw == 4) { if (!dry) launch_kw_one<MT, NT, EPI_HR, 4>(g, dev_args, n, s); return true; }
+    if (g.epi == EPI_HR && cpw == 1) { if (!dry) launch_kw_one<MT, NT, EPI_HR, 1>(g, dev_args, n, s); return true; }
+    if (g.epi == EPI_RESID_SSQ && cpw == 4) { if (!dry) launch_kw_one<MT, NT, EPI_RESID_SSQ, 4>(g, dev_args, n, s); return true; }
+    if (g.epi == EPI_RESID_SSQ && cpw == 1) { if (!dry) launch_kw_one<MT, NT, EPI_RESID_SSQ, 1>(g, dev_args, n, s); return true; }
     return false;
 }
 
 }  // namespace
 
 // GM_KW eligibility of a GEMM (shape + operands): the host-side rule launch_gemm's planner and the engine share.  Returns the
-// number of waves (8 or 4), or 0.
+// number of waves (8), or 0.
 int gemm_kw_waves(const GemmArgs &g)
 {
     if (g.wt != 0 || g.a_op != AOP_NONE || g.wave_mask != 0xF || g.p_add || g.N % 32 != 0 || g.K % 64 != 0) return 0;
-    if (g.epi == EPI_LSTM) {
-        // the one-launch gates GEMM of a chunk step: [y | h(slot)] in two equal K segments, one slab, the cell epilogue
-        if (g.kz != 1 || g.K1 != g.K0 || g.K0 * 2 != g.K || !g.a1 || !g.slot_idx || !g.c_state || !g.out || g.out16) return 0;
-        const int c = g.K / 16 / 4;
-        if (c % 2 != 0 || (c / 2) % 2 != 0) return 0;       // chunks of whole stages, whole rounds of the two-stage ring
-        return 4;
-    }
     if (g.K1 != 0) return 0;
-    if (g.epi != EPI_HR && g.epi != EPI_RESID_SSQ && g.epi != EPI_BIAS_DSWISH) return 0;
-    if (g.epi == EPI_BIAS_DSWISH && g.x_scale.ssq) return 0;
+    if (g.epi != EPI_HR && g.epi != EPI_RESID_SSQ) return 0;
     const int KB = g.K / 16;
     if (KB % (4 * g.kz) != 0) return 0;
     const int c = KB / (4 * g.kz);
     if (c % 2 != 0) return 0;                              // chunks of whole stages
-    int nw = 0;
-    if (g.epi == EPI_BIAS_DSWISH) nw = g.kz == 1 ? 4 : 0;  // one chunk per wave
-    else if (g.kz == 8 || g.kz == 2) nw = 8;               // one slab / one chunk per wave
-    if (!nw) return 0;
-    const int nstage = (4 * g.kz / nw) * c / 2;
-    if (nstage < 2 || nstage % 2 != 0) return 0;           // ring depth 2 (4 where nstage allows): whole rounds of the ring (the 64 x 64 form takes any nstage >= 2)
-    return nw;
+    if (g.kz != 8 && g.kz != 2) return 0;                  // one slab / one chunk per wave
+    const int nstage = (4 * g.kz / NW) * c / 2;
+    if (nstage < 2 || nstage % 2 != 0) return 0;           // whole rounds of the two-stage ring (the 64 x 64 form takes any nstage >= 2)
+    return NW;
 }
 
 // launch of a GEMM whose plan chose GM_KW: tile 16 mt x 16 nt, g.zs == g.kz
 // the kernel of (g, tile): launched, or (dry) only looked up -- ONE table for plan_kw's question and for the launch
 static bool kw_find(const GemmArgs &g, int mt, int nt, const GemmArgs *dev_args, int n, hipStream_t s, bool dry)
 {
-    const int nw = gemm_kw_waves(g);
-    bool ok = false;
-    static const int ring = [] { const char *v = getenv("APRIL_KW_RING"); return v && *v ? atoi(v) : 2; }();      // ring stages per wave: 2; 4 measured the same (tools/kw_bench: the loads are never waited for) at twice the LDS
-    const int nstage = nw ? (4 * g.kz / nw) * (g.K / 16 / (4 * g.kz)) / 2 : 0;
-    if (nw == 8 && ring == 4 && nstage % 4 == 0 && mt == 2 && nt == 2) ok = dispatch_kw<2, 2, 8, 4>(g, dev_args, n, s, dry);
-    else if (nw == 8) {
-        if (mt == 4 && nt == 4) ok = dispatch_kw<4, 4, 8, 2>(g, dev_args, n, s, dry);
-        else if (mt == 2 && nt == 2) ok = dispatch_kw<2, 2, 8, 2>(g, dev_args, n, s, dry);
-        else if (mt == 1 && nt == 2) ok = dispatch_kw<1, 2, 8, 2>(g, dev_args, n, s, dry);
-    } else if (nw == 4) {
-        if (g.epi == EPI_LSTM) {
-            if (mt == 4 && nt == 2) ok = dispatch_kw<4, 2, 4, 2>(g, dev_args, n, s, dry);
-            else if (mt == 2 && nt == 2) ok = dispatch_kw<2, 2, 4, 2>(g, dev_args, n, s, dry);
-        }
-        else if (mt == 2 && nt == 4) ok = dispatch_kw<2, 4, 4, 2>(g, dev_args, n, s, dry);
-    }
-    return ok;
+    if (!gemm_kw_waves(g)) return false;
+    if (mt == 4 && nt == 4) return dispatch_kw<4, 4>(g, dev_args, n, s, dry);
+    if (mt == 2 && nt == 2) return dispatch_kw<2, 2>(g, dev_args, n, s, dry);
+    if (mt == 1 && nt == 2) return dispatch_kw<1, 2>(g, dev_args, n, s, dry);
+    return false;
 }
 
 // is there a GM_KW kernel for this GEMM on 16 mt x 16 nt tiles?  (plan_kw asks before it commits to the schedule: pinned tile shapes and

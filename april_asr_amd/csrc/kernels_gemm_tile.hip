@@ -29,7 +29,7 @@
 // 128 bytes per activation row and 1 KB per weight piece and everything above holds unchanged.  The summation structure
 // (chunks, slabs, tree) is the same; the chains are MFMA-internal sums of 32 products instead of in-order fp32 FMAs.
 // Epilogues: the row epilogues and partial planes, plus (for the gates and FFN-up GEMMs of fp16 engines, and for
-// measurements in fp32) EPI_LSTM over two A segments [y | h(slot)] with the BasicNorm scale folded in after the second
+// measurements in fp32 on the four-wave tiles) EPI_LSTM over two A segments [y | h(slot)] with the BasicNorm scale folded in after the second
 // chunk, and EPI_BIAS_DSWISH.
 // Replaces the ORT MatMul nodes inside the encoder / joiner graphs (reference call sites src/april_session.c:145,176).
 #include "kernels.h"
@@ -50,7 +50,6 @@ constexpr int TILE_STAGES = APRIL_TILE_STAGES;
 
 // Tile shape: 16 MT rows x 16 NT columns per workgroup, NWM x NWN waves, each owning (MT / NWM) x (NT / NWN) MFMA tiles.
 //   <2, 4, 2, 2>, <4, 4, 2, 2>   32 / 64 rows x 64 columns, four waves (all epilogues, fp32 and fp16)
-//   <4, 8, 2, 4>                 64 x 128, eight waves (wave tile 32 x 32): the fp16 projection / FFN-down GEMMs (N = d_model)
 //   <8, 8, 2, 4>                 128 x 128, eight waves: twice the flops per operand byte -- the fp16 gates and FFN-up GEMMs, whose
 //                                k block is 64 SIMD cycles of MFMA against 8 KB of operands at 64 x 64 (bound by the CU's L2 -> LDS rate)
 template <int MT, int NT = 4, int NWM = 2, int NWN = 2, int NS_ = TILE_STAGES> struct TileGeom {
@@ -87,7 +86,6 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int zg)
     char *lds = reinterpret_cast<char *>(red);
 
     if (g.run_flag && *g.run_flag != g.run_gen) return;
-    if constexpr (NWM * NWN == 4) first_round_skew(g.skew, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), (unsigned)g.skew_wgs);      // (measurement form, off by default: device_utils.h)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave / NWN, wn = wave % NWN;
@@ -675,8 +673,8 @@ void launch_tile_one(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStre
 #ifndef APRIL_TILE_STAGES_F16_MT2
 #define APRIL_TILE_STAGES_F16_MT2 4
 #endif
-    // (32-row four-wave tiles: 12 KB per stage, so two workgroups per CU could hold six each; 128 x 192 tiles: 40 KB per stage, three fit the LDS)
-    constexpr int NSB = (WT && NT <= 8) ? ((MT == 2 && NWM * NWN == 4) ? APRIL_TILE_STAGES_F16_MT2 : APRIL_TILE_STAGES_F16) : TILE_STAGES;
+    // (32-row four-wave tiles: 12 KB per stage, so two workgroups per CU could hold six each)
+    constexpr int NSB = WT ? ((MT == 2 && NWM * NWN == 4) ? APRIL_TILE_STAGES_F16_MT2 : APRIL_TILE_STAGES_F16) : TILE_STAGES;
     using G = TileGeom<MT, NT, NWM, NWN, NSB>;
     const int zdiv = g.kz / g.zs;
     dim3 grid((unsigned)(g.N / G::BN), (unsigned)((g.M + G::BM - 1) / G::BM), (unsigned)(zdiv * std::max(1, n)));
@@ -717,32 +715,10 @@ bool dispatch_tile(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream
 void launch_gemm_tile(const GemmArgs &g, int mt, int nt, const GemmArgs *dev_args, int n, hipStream_t s)
 {
     bool ok = false;
-    if (mt == 4 && nt == 8) {        // 64 x 128, eight waves (wave tile 32 x 32): the fp16 N = d_model GEMMs (projection, FFN down)
-        if (g.wt == 1 && g.epi == EPI_PARTIAL) { launch_tile_one<4, EPI_PARTIAL, 1, 8, 2, 4>(g, dev_args, n, s); ok = true; }
-        else if (g.wt == 1 && g.epi == EPI_HR) { launch_tile_one<4, EPI_HR, 1, 8, 2, 4>(g, dev_args, n, s); ok = true; }
-        else if (g.wt == 1 && g.epi == EPI_RESID_SSQ) { launch_tile_one<4, EPI_RESID_SSQ, 1, 8, 2, 4>(g, dev_args, n, s); ok = true; }
-    }
-    else if (nt == 6) {                   // 64 x 96 / 32 x 96, four waves (wave tile 32 x 48 / 16 x 48): the fp16 N = d_model GEMMs where N is a multiple of 96 (plan_tile)
-        if (g.wt == 1 && mt == 4) {
-            if (g.epi == EPI_PARTIAL) { launch_tile_one<4, EPI_PARTIAL, 1, 6>(g, dev_args, n, s); ok = true; }
-            else if (g.epi == EPI_HR) { launch_tile_one<4, EPI_HR, 1, 6>(g, dev_args, n, s); ok = true; }
-            else if (g.epi == EPI_RESID_SSQ) { launch_tile_one<4, EPI_RESID_SSQ, 1, 6>(g, dev_args, n, s); ok = true; }
-        } else if (g.wt == 1 && mt == 2) {
-            if (g.epi == EPI_PARTIAL) { launch_tile_one<2, EPI_PARTIAL, 1, 6>(g, dev_args, n, s); ok = true; }
-            else if (g.epi == EPI_HR) { launch_tile_one<2, EPI_HR, 1, 6>(g, dev_args, n, s); ok = true; }
-            else if (g.epi == EPI_RESID_SSQ) { launch_tile_one<2, EPI_RESID_SSQ, 1, 6>(g, dev_args, n, s); ok = true; }
-        }
-    }
-    else if (mt == 8 && nt == 12) {       // 128 x 192, eight waves (wave tile 64 x 48): 77 flop per operand byte; N a multiple of 192
-        if (g.wt == 1 && g.epi == EPI_LSTM) { launch_tile_one<8, EPI_LSTM, 1, 12, 2, 4>(g, dev_args, n, s); ok = true; }
-        else if (g.wt == 1 && g.epi == EPI_BIAS_DSWISH) { launch_tile_one<8, EPI_BIAS_DSWISH, 1, 12, 2, 4>(g, dev_args, n, s); ok = true; }
-    }
-    else if (mt == 8) {                   // 128 x 128, eight waves: the fp16 gates / FFN-up GEMMs
+    if (mt == 8) {                        // 128 x 128, eight waves: the fp16 gates / FFN-up GEMMs
         if (g.wt == 1 && g.epi == EPI_LSTM) { launch_tile_one<8, EPI_LSTM, 1, 8, 2, 4>(g, dev_args, n, s); ok = true; }
         else if (g.wt == 1 && g.epi == EPI_BIAS_DSWISH) { launch_tile_one<8, EPI_BIAS_DSWISH, 1, 8, 2, 4>(g, dev_args, n, s); ok = true; }
         else if (g.wt == 1 && g.epi == EPI_XPART) { launch_tile_one<8, EPI_XPART, 1, 8, 2, 4>(g, dev_args, n, s); ok = true; }
-        else if (g.wt == 0 && g.epi == EPI_LSTM) { launch_tile_one<8, EPI_LSTM, 0, 8, 2, 4>(g, dev_args, n, s); ok = true; }
-        else if (g.wt == 0 && g.epi == EPI_BIAS_DSWISH) { launch_tile_one<8, EPI_BIAS_DSWISH, 0, 8, 2, 4>(g, dev_args, n, s); ok = true; }
     }
     else if (g.wt == 1) { if (mt == 4) ok = dispatch_tile<4, 1>(g, dev_args, n, s); else if (mt == 2) ok = dispatch_tile<2, 1>(g, dev_args, n, s); }
     else if (mt == 4) ok = dispatch_tile<4, 0>(g, dev_args, n, s);

@@ -5,6 +5,7 @@
 // fixed (independent of the batch).
 #include "kernels.h"
 #include "device_utils.h"
+#include "env.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -555,7 +556,7 @@ void launch_conv_weight_transpose(const float *w0, const float *w1, int c0, int 
 // conv12_kernel are what fills the chip)
 static bool conv_wide_ok(const ConvEmbedArgs &a)
 {
-    static const int min_chunks = [] { const char *e = getenv("APRIL_CONV_WIDE_MIN"); return e && *e ? atoi(e) : 48; }();
+    static const int min_chunks = env_int("APRIL_CONV_WIDE_MIN", 48);
     if (min_chunks < 0 || a.M < min_chunks || !a.w1t || !a.w0t) return false;
     const int H1 = (a.seg - 3) / a.stride[0] + 1, W1 = (a.mel - 3) / a.stride[0] + 1;
     const int H2 = (H1 - 3) / a.stride[1] + 1, W2 = (W1 - 3) / a.stride[1] + 1;
@@ -585,23 +586,6 @@ void launch_conv_embed(const ConvEmbedArgs &a, hipStream_t s)
 __global__ __launch_bounds__(256) void cvt_f16_kernel(const float *src, _Float16 *dst, size_t n)
 {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = (_Float16)src[i];
-}
-
-__global__ __launch_bounds__(256) void prefetch_kernel(const PrefetchItem *__restrict__ items)
-{
-    const PrefetchItem it = items[blockIdx.y];
-    const unsigned long long lines = it.bytes >> 7;
-    const char *p = reinterpret_cast<const char *>(it.ptr);
-    unsigned acc = 0;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < lines; i += (unsigned long long)gridDim.x * 256)
-        acc ^= *reinterpret_cast<const volatile unsigned *>(p + (i << 7));
-    asm volatile("" :: "v"(acc));
-}
-
-void launch_prefetch(const PrefetchItem *dev_items, int n, hipStream_t s)
-{
-    if (n <= 0) return;
-    hipLaunchKernelGGL(prefetch_kernel, dim3(48, (unsigned)n), dim3(256), 0, s, dev_items);
 }
 
 void launch_cvt_f16(const float *src, void *dst, size_t n, hipStream_t s)

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <chrono>
 #include "common.h"
+#include "env.h"
 
 namespace aprilx {
 
@@ -306,28 +307,21 @@ Model::~Model()
 
 static int host_helpers()
 {
-    const char *v = getenv("APRIL_HOST_THREADS");
     // default: one helper per 16 hardware threads, 3..8 (measured at 2048 sessions: 8 helpers 10.07 ms per step, 3 helpers 10.59)
     const int hw = (int)std::thread::hardware_concurrency();
-    const int n = v && *v ? atoi(v) : std::max(3, std::min(8, hw / 16));
+    const int n = env_int("APRIL_HOST_THREADS", std::max(3, std::min(8, hw / 16)));
     return n < 0 ? 0 : (n > 32 ? 32 : n);
 }
 
-static int env_us(const char *name, int def)
-{
-    const char *v = getenv(name);
-    const int n = v && *v ? atoi(v) : def;
-    return n < 0 ? 0 : (n > 1000000 ? 1000000 : n);
-}
+static int env_0_1M(const char *name, int def) { return std::max(0, std::min(1000000, env_int(name, def))); }
 
 Scheduler::Scheduler(Model *m, Engine *e) : model_(m), eng_(e), pool_(host_helpers())
 {
-    spin_step_us_ = env_us("APRIL_SPIN_STEP_US", 1000);     // (1 ms: a client that pauses for a barrier or a sync between two feeds finds the thread awake; 100 us until round 3)
-    spin_wait_us_ = env_us("APRIL_SPIN_WAIT_US", 3000);
-    lm_min_chunks_ = env_us("APRIL_LM_MIN_CHUNKS", 8);
-    wave_min_chunks_ = env_us("APRIL_WAVE_MIN_CHUNKS", 2);
-    wave_max_chunks_ = std::max(1, env_us("APRIL_WAVE_MAX_CHUNKS", 7));
-    pipeline_depth_ = std::max(1, std::min(2, env_us("APRIL_PIPELINE", 2)));
+    spin_step_us_ = env_0_1M("APRIL_SPIN_STEP_US", 1000);     // (1 ms: a client that pauses for a barrier or a sync between two feeds finds the thread awake; 100 us until round 3)
+    spin_wait_us_ = env_0_1M("APRIL_SPIN_WAIT_US", 3000);
+    lm_min_chunks_ = env_0_1M("APRIL_LM_MIN_CHUNKS", 8);
+    wave_min_chunks_ = env_0_1M("APRIL_WAVE_MIN_CHUNKS", 2);
+    pipeline_depth_ = std::max(1, std::min(2, env_0_1M("APRIL_PIPELINE", 2)));
     thread_ = std::thread([this] { loop(); });
 }
 
@@ -751,8 +745,8 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
     // (default 2^30; 1640 sessions x a full 8192-frame ring of backlog would pass 2^31) and carries the rest to the next pass
     // of launch_flight()'s loop.  APRIL_STAGE_LIMIT_SAMPLES exists for the test that crosses the limit with small numbers.
     static const size_t stage_limit = [] {
-        const char *v = getenv("APRIL_STAGE_LIMIT_SAMPLES");
-        const long n = v && *v ? atol(v) : (1L << 30);
+        const char *v = env_str("APRIL_STAGE_LIMIT_SAMPLES");
+        const long n = v ? atol(v) : (1L << 30);
         return (size_t)std::min(1L << 30, std::max(1L << 12, n));
     }();
     for (Session *s : work) {
@@ -933,7 +927,7 @@ bool Scheduler::step_chunks(std::vector<Session *> &ready)
     auto waiting = [](const Session *s) { return (int)((s->fb.avail - s->fb.seg_count) / s->fb.seg_step + 1); };
     // (fp16 tile engines: layer-major since round 4 -- the tile kernels have the two halves of the gate GEMM; APRIL_F16_LM=0 falls back
     // to successive feed wavefronts of up to wave_max_chunks_ chunks)
-    static const bool f16_lm = !(getenv("APRIL_F16_LM") && atoi(getenv("APRIL_F16_LM")) == 0);
+    static const bool f16_lm = env_int("APRIL_F16_LM", 1) != 0;
     const bool lm_ok = lm_min_chunks_ > 0 && lm_min_chunks_ <= MB && (!eng_->f16_tile() || f16_lm);
     for (Session *s : ready) ((lm_ok && waiting(s) >= lm_min_chunks_) ? lm : one).push_back(s);
     // ... a FEW sessions: layer-major pays while the rows of a time step are a handful (the recurrent pair of a step as weight streams,
@@ -941,7 +935,7 @@ bool Scheduler::step_chunks(std::vector<Session *> &ready)
     // chunks are faster (aprilv0 dims, 2 .. 10 s handed over at once, ms per 100 ms of all sessions, layer-major vs wavefronts: 1 session
     // 0.13 vs 0.33, 32: 0.33 vs 0.49, 64: 0.73 vs 0.60, 256: 1.74 vs 1.31 -- round 6; an asynchronous client that runs ahead of the GPU
     // is the case: bench.py `reference_api_async` 1.93 -> 1.45 ms per step)
-    static const size_t lm_max_sessions = (size_t)env_us("APRIL_LM_MAX_SESSIONS", 48);
+    constexpr size_t lm_max_sessions = 48;
     if (lm.size() > lm_max_sessions && wave_min_chunks_ > 0) { one.insert(one.end(), lm.begin(), lm.end()); lm.clear(); }
     if (!lm.empty()) {
         const int per = std::max(1, MB / lm_min_chunks_);

@@ -230,7 +230,8 @@ private:
     int spin_step_us_ = 1000, spin_wait_us_ = 3000;   // APRIL_SPIN_STEP_US / APRIL_SPIN_WAIT_US
     std::chrono::steady_clock::time_point prev_done_;   // when the previous flight completed (stepping thread only): start of the next flight's own span
     bool have_prev_done_ = false;
-    int wave_min_chunks_ = 2, wave_max_chunks_ = 7;  // APRIL_WAVE_MIN_CHUNKS (0 = chunk steps one by one) / APRIL_WAVE_MAX_CHUNKS: chunk steps of one feed as a wavefront
+    int wave_min_chunks_ = 2;                        // APRIL_WAVE_MIN_CHUNKS (0 = chunk steps one by one): chunk steps of one feed as a wavefront ...
+    static constexpr int wave_max_chunks_ = 7;       // ... of at most this many chunks
     int lm_min_chunks_ = 8;                          // APRIL_LM_MIN_CHUNKS: sessions with at least this many chunks waiting take the layer-major path (0 = never)
     void spin_for_done(uint64_t seen);
     std::vector<Session *> sessions_;

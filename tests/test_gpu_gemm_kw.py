@@ -31,20 +31,20 @@ def test_kw_schedule_is_bit_identical_on_whole_sessions(built, medium_model, v0_
     path = (medium_model if which == "medium" else v0_model)["path"]
     off = run(path, nsess, 5, APRIL_GM_KW=0)
     assert off[1] > 0 and off[2] == 0
-    for env in ({"APRIL_GM_KW": 1}, {"APRIL_GM_KW": 1, "APRIL_KW_MT": 1}, {"APRIL_GM_KW": 1, "APRIL_KW_MT": 2}, {"APRIL_GM_KW": 1, "APRIL_KW_RING": 4}):
+    for env in ({"APRIL_GM_KW": 1}, {"APRIL_GM_KW": 1, "APRIL_KW_MT": 1}, {"APRIL_GM_KW": 1, "APRIL_KW_MT": 2}):
         on = run(path, nsess, 5, **env)
         assert on[1] == off[1] and on[2] == 0
         assert on[0] == off[0], "GM_KW %r: logits or callbacks differ from the round-4 schedules" % env
 
 
-@pytest.mark.parametrize("xcd", ["0", "2"])
-def test_kw_bench_every_output_bitwise(built, xcd):
+def test_kw_bench_every_output_bitwise(built):
     exe = os.path.join(ROOT, "tools", "kw_bench")
     if not os.path.exists(exe):
         subprocess.check_call(["bash", os.path.join(ROOT, "tools", "build_kw_bench.sh")], timeout=900)
-    # (APRIL_KW_GATES: the gates form of GM_KW is a measurement form, off by default -- its outputs are still checked bit for bit here;
-    # APRIL_KW_XCD=2: the 2 x 4 XCD order of the tiles, measured neutral and off by default, likewise)
-    r = subprocess.run([exe, "20"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, env=dict(os.environ, APRIL_KW_GATES="1", APRIL_KW_GATES_MAX_ROWS="100000", APRIL_KW_XCD=xcd))
+    r = subprocess.run([exe, "20"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     out = r.stdout.decode()
     assert r.returncode == 0 and "all configurations bit-identical" in out, out[-3000:] + r.stderr.decode()[-1000:]
-    assert out.count("bit-identical") > 60 and "MISMATCH" not in out
+    # (floor = the "bit-identical" lines of the kept configurations in the recorded run profiles/r06_kw_bench.txt: 189 lines in all,
+    # less 48 K-cut lines of the stream kernels and 14 lines of the FFN-up shapes, forms the tool no longer has = 127; the gates
+    # shapes of that run print none)
+    assert out.count("bit-identical") >= 127 and "MISMATCH" not in out

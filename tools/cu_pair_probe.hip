@@ -1,6 +1,6 @@
-// Measurement aid: which workgroups of a launch share a CU, and what HW_ID says about them.  The first-round start skew of the
-// two-workgroups-per-CU GEMM kernels (device_utils.h first_round_skew) delays ONE of the two workgroups that start together on a
-// CU; it picks it by a bit of HW_ID.  This probe launches 4-wave workgroups that can only be co-resident in pairs (70 KB of LDS
+// Measurement aid: which workgroups of a launch share a CU, and what HW_ID says about them.  The first-round start skew that the
+// two-workgroups-per-CU GEMM kernels once had (LAB_NOTES.md) delayed ONE of the two workgroups that start together on a
+// CU; it picked it by a bit of HW_ID.  This probe launches 4-wave workgroups that can only be co-resident in pairs (70 KB of LDS
 // each), lets every one of them sleep ~8 us, and records (linear id, HW_ID, XCC_ID, start, end).  It prints, for the first
 // 2 x CUs workgroups: how many CUs got exactly two of them, which HW_ID bit fields differ inside a pair, and the linear-id
 // distance of the pair; then the same for the later rounds (does the parity of the field survive a replacement?).

@@ -1,6 +1,6 @@
 // Measurement + parity aid for the GM_KW schedule (csrc/kernels_gemm_kw.hip), linked against the product's objects:
 //   1. bitwise comparison of every output (rows, state rows, sums of squares) between the schedules the planner would pick with GM_KW
-//      off (GM_FULLK / GM_SLAB fused tiles, the hand-scheduled FFN-up tiles) and GM_KW at each tile height;
+//      off (GM_FULLK / GM_SLAB fused tiles, the stream kernels at <= 16 rows) and GM_KW at each tile height;
 //   2. back-to-back launch time of each, one problem per launch and z-batched (n problems of one shape, own weights and rows).
 // build: make -C april_asr_amd/csrc && hipcc --offload-arch=gfx950 -O2 -std=c++17 -Iapril_asr_amd/csrc tools/kw_bench.hip \
 //        april_asr_amd/csrc/build/kernels_gemm.o april_asr_amd/csrc/build/kernels_gemm_tile.o april_asr_amd/csrc/build/kernels_gemm_kw.o \
@@ -20,9 +20,8 @@ template <class T> static T *dalloc(size_t n) { T *p; CK(hipMalloc((void **)&p, 
 
 struct Problem {
     int M, N, K, kz, epi; bool a_indexed = false;      // a_indexed: the activation rows are reached through the row -> slot indirection (aidx0)
-    float *a, *w, *bias, *resid, *ssq_in, *out, *state, *ssq_out, *cst = nullptr, *cst0 = nullptr;      // cst: cell state (gates), cst0: its initial values
+    float *a, *w, *bias, *resid, *ssq_in, *out, *state, *ssq_out;
     int *slots;
-    float *ks_ws = nullptr; unsigned *ks_cnt = nullptr;      // workspace of the K-cut stream kernels (<= 16 rows; kernels_recur.hip)
 };
 static void fill(std::vector<float> &h, unsigned seed, float scale)
 {
@@ -43,29 +42,16 @@ static Problem make_problem(int M, int N, int K, int kz, int epi, unsigned seed)
     std::vector<int> perm((size_t)M); for (int i = 0; i < M; ++i) perm[(size_t)i] = i;
     unsigned s = seed; for (int i = M - 1; i > 0; --i) { s = s * 1664525u + 1013904223u; std::swap(perm[(size_t)i], perm[(size_t)((s >> 8) % (unsigned)(i + 1))]); }
     p.slots = dalloc<int>((size_t)M); CK(hipMemcpy(p.slots, perm.data(), (size_t)M * 4, hipMemcpyHostToDevice));
-    if (M <= 16 && (epi == EPI_HR || epi == EPI_RESID_SSQ)) { p.ks_ws = dalloc<float>((size_t)N * kz * 16); p.ks_cnt = dalloc<unsigned>((size_t)N / 16); CK(hipMemset(p.ks_cnt, 0, (size_t)N / 16 * 4)); }
-    if (epi == EPI_LSTM) {      // gates: A = [y (M x K/2, rows) | h (M x K/2, by slot)], c state [M][N/4]
-        h.resize((size_t)M * (N / 4)); fill(h, seed + 5, 1.0f); p.cst0 = upload(h); p.cst = dalloc<float>(h.size());
-        h.resize((size_t)M * (K / 64)); fill(h, seed + 6, 1.0f); for (auto &v : h) v = v * v + 0.1f;
-        CK(hipFree(p.ssq_in)); p.ssq_in = upload(h);
-    }
     return p;
 }
-static bool g_ks_attach = false;      // hand the K-cut workspace to the GEMMs (the engine always does; off for the reference runs)
 static GemmArgs gemm_of(const Problem &p, int zcount, int tile_ok = 0)
 {
     GemmArgs g; g.tile_ok = tile_ok;
     g.a0 = p.a; g.lda0 = p.K; g.K0 = p.K; g.aidx0 = p.a_indexed ? p.slots : nullptr; g.wp = p.w; g.M = p.M; g.N = p.N; g.K = p.K; g.kz = p.kz; g.zcount = zcount;
     g.epi = p.epi; g.out = p.out; g.ldo = p.N; g.bias = p.bias;
-    if (p.epi == EPI_LSTM) {
-        g.K0 = p.K / 2; g.lda0 = p.K / 2; g.a1 = p.a + (size_t)p.M * (p.K / 2); g.lda1 = p.K / 2; g.aidx1 = p.slots; g.K1 = p.K / 2; g.aidx0 = nullptr;
-        g.c_state = p.cst; g.slot_idx = p.slots; g.hidden = p.N / 4; g.ldo = p.N / 4;
-        g.x_scale.ssq = p.ssq_in; g.x_scale.groups = (p.K / 2) / 32; g.x_scale.inv_n = 1.0f / (p.K / 2); g.x_scale.eps = 0.25f;
-    }
-    else if (p.epi == EPI_HR) { g.state = p.state; g.ld_state = p.N; g.slot_idx = p.slots; g.resid = p.resid; g.ldr = p.N;
+    if (p.epi == EPI_HR) { g.state = p.state; g.ld_state = p.N; g.slot_idx = p.slots; g.resid = p.resid; g.ldr = p.N;
                            g.r_scale.ssq = p.ssq_in; g.r_scale.groups = p.N / 32; g.r_scale.inv_n = 1.0f / p.N; g.r_scale.eps = 0.25f; g.bias = nullptr; g.force_fullk = 1; }
     else if (p.epi == EPI_RESID_SSQ) { g.resid = p.resid; g.ldr = p.N; g.ssq_out = p.ssq_out; g.force_fullk = 1; }
-    if (g_ks_attach) { g.ks_ws = p.ks_ws; g.ks_cnt = p.ks_cnt; }
     return g;
 }
 struct Chain {
@@ -88,9 +74,8 @@ static std::vector<float> snapshot(const std::vector<Problem> &ps)
 {
     std::vector<float> all;
     for (const Problem &p : ps) {
-        std::vector<float> h((size_t)p.M * (p.epi == EPI_LSTM ? p.N / 4 : p.N));
+        std::vector<float> h((size_t)p.M * p.N);
         CK(hipMemcpy(h.data(), p.out, h.size() * 4, hipMemcpyDeviceToHost)); all.insert(all.end(), h.begin(), h.end());
-        if (p.epi == EPI_LSTM) { CK(hipMemcpy(h.data(), p.cst, h.size() * 4, hipMemcpyDeviceToHost)); all.insert(all.end(), h.begin(), h.end()); }
         if (p.epi == EPI_HR) { CK(hipMemcpy(h.data(), p.state, h.size() * 4, hipMemcpyDeviceToHost)); all.insert(all.end(), h.begin(), h.end()); }
         if (p.epi == EPI_RESID_SSQ) { h.resize((size_t)p.M * (p.N / 32)); CK(hipMemcpy(h.data(), p.ssq_out, h.size() * 4, hipMemcpyDeviceToHost)); all.insert(all.end(), h.begin(), h.end()); }
     }
@@ -98,8 +83,7 @@ static std::vector<float> snapshot(const std::vector<Problem> &ps)
 }
 static void clear_outputs(const std::vector<Problem> &ps)
 {
-    for (const Problem &p : ps) { if (p.cst) CK(hipMemcpy(p.cst, p.cst0, (size_t)p.M * (p.N / 4) * 4, hipMemcpyDeviceToDevice));      // (the cell state is updated in place: same start for every run)
-                                  CK(hipMemset(p.out, 0xff, (size_t)p.M * p.N * 4)); CK(hipMemset(p.state, 0xff, (size_t)p.M * p.N * 4)); CK(hipMemset(p.ssq_out, 0xff, (size_t)p.M * (p.N / 32) * 4)); }
+    for (const Problem &p : ps) { CK(hipMemset(p.out, 0xff, (size_t)p.M * p.N * 4)); CK(hipMemset(p.state, 0xff, (size_t)p.M * p.N * 4)); CK(hipMemset(p.ssq_out, 0xff, (size_t)p.M * (p.N / 32) * 4)); }
 }
 static double time_chain(const Chain &c, hipStream_t s, int iters)
 {
@@ -134,37 +118,21 @@ int main(int argc, char **argv)
         {"proj   16x3", 16, 512, 1024, 8, EPI_HR, 3},
         {"ffdn   16x3", 16, 512, 2048, 8, EPI_RESID_SSQ, 3},
         {"ffdn   13x1", 13, 512, 2048, 8, EPI_RESID_SSQ, 1},
-        {"gates  64x1", 64, 4096, 1024, 1, EPI_LSTM, 1},
-        {"gates  64x2", 64, 4096, 1024, 1, EPI_LSTM, 2},
-        {"gates  64x3", 64, 4096, 1024, 1, EPI_LSTM, 3},
-        {"gates  24x3", 24, 4096, 1024, 1, EPI_LSTM, 3},
-        {"gates  40x2", 40, 4096, 1024, 1, EPI_LSTM, 2},
-        {"gates  96x2", 96, 4096, 1024, 1, EPI_LSTM, 2},
-        {"gates 128x2", 128, 4096, 1024, 1, EPI_LSTM, 2},
-        {"gates 128x3", 128, 4096, 1024, 1, EPI_LSTM, 3},
-        {"gates 256x2", 256, 4096, 1024, 1, EPI_LSTM, 2},
-        {"gates  50x2 L", 50, 6144, 1536, 1, EPI_LSTM, 2},              // larger encoder dims
         {"proj  256x1", 256, 512, 1024, 8, EPI_HR, 1},
         {"proj  256x2", 256, 512, 1024, 8, EPI_HR, 2},
         {"proj  256x3", 256, 512, 1024, 8, EPI_HR, 3},
         {"ffdn  256x1", 256, 512, 2048, 8, EPI_RESID_SSQ, 1},
         {"ffdn  256x2", 256, 512, 2048, 8, EPI_RESID_SSQ, 2},
         {"ffdn  256x3", 256, 512, 2048, 8, EPI_RESID_SSQ, 3},
-        {"ffup  256x1", 256, 2048, 512, 1, EPI_BIAS_DSWISH, 1},
-        {"ffup  256x2", 256, 2048, 512, 1, EPI_BIAS_DSWISH, 2},
-        {"ffup  256x3", 256, 2048, 512, 1, EPI_BIAS_DSWISH, 3},
         {"proj  250x2", 250, 512, 1024, 8, EPI_HR, 2},                  // ragged rows
         {"ffdn   40x2", 40, 512, 2048, 8, EPI_RESID_SSQ, 2},
         {"proj  200x2 i", 200, 512, 1024, 8, EPI_HR, 2, true},          // activation rows through the slot indirection, ragged
-        {"ffup   70x3", 70, 2048, 512, 1, EPI_BIAS_DSWISH, 3},
         {"proj   64x3", 64, 512, 1024, 8, EPI_HR, 3},
         {"ffdn   64x3", 64, 512, 2048, 8, EPI_RESID_SSQ, 3},
         {"proj  128x3", 128, 512, 1024, 8, EPI_HR, 3},
         {"ffdn  128x3", 128, 512, 2048, 8, EPI_RESID_SSQ, 3},
-        {"ffup  128x3", 128, 2048, 512, 1, EPI_BIAS_DSWISH, 3},
         {"proj  512x2", 512, 512, 1024, 8, EPI_HR, 2},
         {"ffdn  512x2", 512, 512, 2048, 8, EPI_RESID_SSQ, 2},
-        {"ffup  512x2", 512, 2048, 512, 1, EPI_BIAS_DSWISH, 2},
         {"ffdn  768x3", 768, 512, 2048, 8, EPI_RESID_SSQ, 3},
         {"proj 1024x2", 1024, 512, 1024, 8, EPI_HR, 2},
         {"ffdn 1024x2", 1024, 512, 2048, 8, EPI_RESID_SSQ, 2},
@@ -175,7 +143,6 @@ int main(int argc, char **argv)
         {"ffdn 2048x3", 2048, 512, 2048, 8, EPI_RESID_SSQ, 3},
         {"proj  512x3 L", 512, 768, 1536, 2, EPI_HR, 3},                // larger encoder (configs[4] dims), fp32
         {"ffdn  512x3 L", 512, 768, 3072, 2, EPI_RESID_SSQ, 3},
-        {"ffup  512x3 L", 512, 3072, 768, 1, EPI_BIAS_DSWISH, 3},
     };
     int bad = 0;
     for (const Shape &sh : shapes) {
@@ -183,35 +150,15 @@ int main(int argc, char **argv)
         std::vector<Problem> ps;
         for (int i = 0; i < sh.n; ++i) { ps.push_back(make_problem(sh.M, sh.N, sh.K, sh.kz, sh.epi, 1000u * (unsigned)(&sh - shapes) + 10u * (unsigned)i)); ps.back().a_indexed = sh.idx; }
         const double flops = 2.0 * sh.M * sh.N * sh.K * sh.n;
-        gemm_kw_pin(0, 0, 0);
+        gemm_kw_pin(0, 0);
         Chain ref = make_chain(ps);
         clear_outputs(ps); ref.run(s); CK(hipStreamSynchronize(s));
         const std::vector<float> want = snapshot(ps);
         const double t_ref = time_chain(ref, s, iters);
         printf("%-13s M=%d N=%d K=%d kz=%d x%d | round-4 schedule (mode %d): %7.2f us (%.3f of peak)\n", sh.name, sh.M, sh.N, sh.K, sh.kz, sh.n, ref.gh[0].mode, t_ref, flops / (t_ref * 1e-6) / 157.3e12);
-        if (sh.M <= 16 && (sh.epi == EPI_HR || sh.epi == EPI_RESID_SSQ)) {
-            // the stream kernel with K cut across workgroups (in-launch hand-over, kernels_recur.hip): planner's cut, then every pinned one
-            for (int cut : {1, 2, 4, 8}) {
-                if (cut > sh.kz) continue;
-                g_ks_attach = true; recur_ksplit_pin(cut); gemm_kw_pin(0, 0, 0);
-                Chain c = make_chain(ps);
-                g_ks_attach = false;
-                const int got_cut = c.n == 1 ? recur_ksplit(c.gh[0], 1) : c.gh[0].ksplit;      // (launch_gemm plans a single problem again at every launch: the pin stays)
-                clear_outputs(ps); c.run(s); CK(hipStreamSynchronize(s));
-                const std::vector<float> got = snapshot(ps);
-                size_t diff = 0; for (size_t i = 0; i < want.size(); ++i) if (memcmp(&want[i], &got[i], 4) != 0) ++diff;
-                const double t = time_chain(c, s, iters);
-                clear_outputs(ps); for (int i = 0; i < 7; ++i) c.run(s); CK(hipStreamSynchronize(s));      // back-to-back: the counters re-arm
-                recur_ksplit_pin(-1);
-                const std::vector<float> got2 = snapshot(ps);
-                size_t diff2 = 0; for (size_t i = 0; i < want.size(); ++i) if (memcmp(&want[i], &got2[i], 4) != 0) ++diff2;
-                printf("    stream kernel, K cut %s-> %d workgroups per granule : %7.2f us (%.2fx)  %s\n", cut == 1 ? "(planner) " : "", got_cut, t, t_ref / t, (diff || diff2) ? "MISMATCH" : "bit-identical");
-                if (diff || diff2) { ++bad; printf("      mismatching floats: %zu / %zu of %zu\n", diff, diff2, want.size()); }
-            }
-        }
-        if (sh.epi != EPI_BIAS_DSWISH && gemm_tile_planned(sh.M, sh.N, sh.kz, sh.n) && gemm_fullk(sh.M, sh.N, sh.kz, true, sh.n, 1)) {
+        if (gemm_tile_planned(sh.M, sh.N, sh.kz, sh.n) && gemm_fullk(sh.M, sh.N, sh.kz, true, sh.n, 1)) {
             // GM_TILE with the row work fused, where the engine's planner would take it (for the crossover between the two)
-            gemm_kw_pin(0, 0, 0);
+            gemm_kw_pin(0, 0);
             Chain ct = make_chain(ps, 1);
             if (ct.gh[0].mode == GM_TILE) {
                 clear_outputs(ps); ct.run(s); CK(hipStreamSynchronize(s));
@@ -223,9 +170,7 @@ int main(int argc, char **argv)
             }
         }
         for (int mt : {0, 2, 1, 4}) {
-            if ((mt == 1 || mt == 4) && sh.epi == EPI_BIAS_DSWISH) continue;
-            if (mt == 1 && sh.epi == EPI_LSTM) continue;
-            gemm_kw_pin(1, mt, 1);
+            gemm_kw_pin(1, mt);
             Chain c = make_chain(ps, mt == 0 ? 1 : 0);      // (the planner's own choice as the engine makes it: GM_TILE allowed, GM_KW may take a fused GM_TILE plan over)
             if (c.gh[0].mode != GM_KW) { printf("    (GM_KW not planned for this shape, mt pin %d%s)\n", mt, c.gh[0].mode == GM_TILE ? ": the planner keeps GM_TILE" : ""); continue; }
             clear_outputs(ps); c.run(s); CK(hipStreamSynchronize(s));
@@ -233,7 +178,7 @@ int main(int argc, char **argv)
             size_t diff = 0; double maxd = 0;
             for (size_t i = 0; i < want.size(); ++i) if (memcmp(&want[i], &got[i], 4) != 0) { ++diff; maxd = std::max(maxd, (double)fabsf(want[i] - got[i])); }
             const double t = time_chain(c, s, iters);
-            clear_outputs(ps); for (int i = 0; i < (sh.epi == EPI_LSTM ? 1 : 5); ++i) c.run(s); CK(hipStreamSynchronize(s));      // (the gates update the cell state in place: one run)
+            clear_outputs(ps); for (int i = 0; i < 5; ++i) c.run(s); CK(hipStreamSynchronize(s));
             const std::vector<float> got2 = snapshot(ps);
             size_t diff2 = 0; for (size_t i = 0; i < want.size(); ++i) if (memcmp(&want[i], &got2[i], 4) != 0) ++diff2;
             if (getenv("KB_TRACE")) {      // (binary built with -DAPRIL_GEMM_TRACE) s_memtime stamps of wave 0: start, loop start, loop end, meet done, end
@@ -256,7 +201,7 @@ int main(int argc, char **argv)
         }
         fflush(stdout);
     }
-    gemm_kw_pin(-1, 0, -1);
+    gemm_kw_pin(-1, 0);
     printf(bad ? "FAILED: %d configurations differ\n" : "all configurations bit-identical\n", bad);
     return bad ? 1 : 0;
 }
