@@ -10,6 +10,7 @@ batched feeding of many sessions in one call, network-level parity entry points,
 weight-blob export/import for the RCCL broadcast at load time.
 """
 import ctypes as C
+import math
 import struct
 import weakref
 from enum import IntEnum
@@ -30,15 +31,29 @@ class Result(IntEnum):
 
 
 class Token:
-    """One emitted token: text carries its own spacing; `logprob` is the raw joiner logit."""
-    __slots__ = ("token", "logprob", "word_boundary", "sentence_end", "time")
+    """One emitted token: text carries its own spacing; `logprob` is the raw joiner logit.
 
-    def __init__(self, raw):
+    Sessions created with `alternatives=K` (Session.set_confidence) also get `log_softmax` (the token's log-probability over the
+    vocabulary of the joiner evaluation that produced it), `confidence` (= exp(log_softmax)), `blank_log_softmax` and
+    `alternatives`: up to K (text, log_softmax) pairs by descending probability, the token itself first.  None otherwise."""
+    __slots__ = ("token", "logprob", "word_boundary", "sentence_end", "time", "log_softmax", "confidence", "blank_log_softmax",
+                 "alternatives")
+
+    def __init__(self, raw, model=None):
         self.token = raw.token.decode("utf-8", "replace")
         self.logprob = float(raw.logprob)
         self.word_boundary = bool(raw.flags & 1)
         self.sentence_end = bool(raw.flags & 2)
         self.time = float(raw.time_ms) / 1000.0
+        self.log_softmax = self.confidence = self.blank_log_softmax = self.alternatives = None
+        if raw.reserved:
+            info = C.cast(raw.reserved, C.POINTER(_ffi.AprilxTokenInfo)).contents
+            self.log_softmax = float(info.token_logprob)
+            self.confidence = math.exp(self.log_softmax) if self.log_softmax == self.log_softmax else float("nan")
+            self.blank_log_softmax = float(info.blank_logprob)
+            lse = np.float32(info.lse)
+            self.alternatives = [(model.token(int(info.alt_id[i])) if model is not None else int(info.alt_id[i]),
+                                  float(np.float32(info.alt_logit[i]) - lse)) for i in range(int(info.n_alt))]
 
     def __repr__(self):
         return "Token(%r, %.3f, wb=%d, eos=%d, t=%.2f)" % (self.token, self.logprob, self.word_boundary,
@@ -227,6 +242,15 @@ class Model:
             raise ValueError("aprilx_resample refused %d samples at %d Hz" % (a.size, in_rate))
         return out[:n]
 
+    def run_confidence(self, logits, k: int):
+        """The side records of GIVEN logits rows [n][vocab] with k alternatives through the device code the search uses
+        (aprilx_run_confidence; tests): an array of n _ffi.AprilxTokenInfo."""
+        a = np.ascontiguousarray(logits, np.float32).reshape(-1, self.dims.vocab)
+        out = (_ffi.AprilxTokenInfo * a.shape[0])()
+        if self._L.aprilx_run_confidence(self._handle, a.shape[0], a.ctypes.data, int(k), out) != 0:
+            raise ValueError("aprilx_run_confidence refused n=%d k=%d" % (a.shape[0], k))
+        return out
+
     def stats(self, device_index: int = 0):
         s = _ffi.AprilxStats()
         self._L.aprilx_model_stats(self._handle, device_index, C.byref(s))
@@ -258,12 +282,16 @@ _HANDLER = _ffi.HANDLER(_dispatch)
 
 class Session:
     def __init__(self, model: Model, callback: Callable[[Result, List[Token]], None], asynchronous: bool = False,
-                 no_rt: bool = False, speaker_name: str = "", raw_events: bool = False, counters=None, input_sample_rate=None):
+                 no_rt: bool = False, speaker_name: str = "", raw_events: bool = False, counters=None, input_sample_rate=None,
+                 alternatives=None):
         """`counters`: a uint64 ndarray of 6 entries; when given, results are only counted by a C handler inside the
         library (calls, partial, final, cant_keep_up, silence, tokens) and `callback` is never invoked.
         `input_sample_rate`: the rate of the PCM this session will receive (converted to the model's rate on the GPU); None: the
-        model's rate."""
+        model's rate.
+        `alternatives`: K in 1..8: every delivered Token carries its log-softmax, the blank's and the K best candidates
+        (set_confidence); None / 0: off."""
         self._L = model._L
+        self.info_log = None      # tests: a list that receives (type, [the token's AprilxTokenInfo as bytes, or None]) per result
         self.model = model
         self.callback = callback
         self._raw = raw_events
@@ -286,14 +314,19 @@ class Session:
         model._sessions.add(self)
         if input_sample_rate is not None:
             self.set_input_rate(input_sample_rate)
+        if alternatives:
+            self.set_confidence(alternatives)
 
     def _on_result(self, result_type, count, tokens):
+        if self.info_log is not None:
+            self.info_log.append((int(result_type), [C.string_at(tokens[i].reserved, C.sizeof(_ffi.AprilxTokenInfo)) if tokens[i].reserved
+                                                     else None for i in range(count)]))
         if self._raw:
             # (type, [(token text, logprob, flags, time_ms)]) -- exact values, for parity tests
             self.callback(int(result_type), [(tokens[i].token, float(tokens[i].logprob), int(tokens[i].flags),
                                               int(tokens[i].time_ms)) for i in range(count)])
         else:
-            self.callback(Result(result_type), [Token(tokens[i]) for i in range(count)])
+            self.callback(Result(result_type), [Token(tokens[i], self.model) for i in range(count)])
 
     def get_rt_speedup(self) -> float:
         return float(self._L.aas_realtime_get_speedup(self._handle))
@@ -315,6 +348,17 @@ class Session:
         completed flush; the model's rate restores the default path."""
         if self._L.aprilx_session_set_input_rate(self._handle, int(rate_hz)) != 0:
             raise ValueError("input rate %d refused (outside 4000..384000 Hz / L > 4096, or audio fed since the last flush)" % rate_hz)
+
+    def set_confidence(self, n_alternatives: int) -> None:
+        """Tokens delivered from now on carry their log-softmax, the blank's and the `n_alternatives` (1..8) best candidates
+        (aprilx_session_set_confidence); 0 switches it off.  Allowed right after creation and after a completed flush.  It changes
+        no recognition result."""
+        if self._L.aprilx_session_set_confidence(self._handle, int(n_alternatives)) != 0:
+            raise ValueError("confidence with %d alternatives refused (0..8, and no audio fed since the last flush)" % n_alternatives)
+
+    @property
+    def alternatives(self) -> int:
+        return int(self._L.aprilx_session_confidence(self._handle))
 
     @property
     def input_rate(self) -> int:

@@ -43,7 +43,13 @@ class AprilxStats(C.Structure):
                 ("wave_steps", C.c_uint64), ("wave_chunks", C.c_uint64),
                 ("gates_clock_ms", C.c_double), ("gates_clock_launches", C.c_uint64), ("gates_clock_rows", C.c_uint64),
                 ("gates_clock_ms_by_n", C.c_double * 4), ("gates_clock_launches_by_n", C.c_uint64 * 4),
-                ("resample_ms", C.c_double), ("resample_launches", C.c_uint64)]
+                ("resample_ms", C.c_double), ("resample_launches", C.c_uint64), ("confidence_records", C.c_uint64)]
+
+
+class AprilxTokenInfo(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("n_alt", C.c_uint32), ("eval_index", C.c_uint64), ("lse", C.c_float),
+                ("token_logprob", C.c_float), ("blank_logprob", C.c_float), ("reserved0", C.c_float),
+                ("alt_id", C.c_int32 * 8), ("alt_logit", C.c_float * 8)]
 
 
 class AprilxLoadInfo(C.Structure):
@@ -64,6 +70,7 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_session_trace_logits", "aprilx_session_chunks", "aprilx_session_read_frames", "aprilx_session_context", "aprilx_model_stats", "aprilx_model_profile", "aprilx_model_feed_latency",
     "aprilx_greedy_create", "aprilx_greedy_step", "aprilx_greedy_finish", "aprilx_greedy_free", "aprilx_probe_file", "aprilx_model_load_host", "aprilx_model_fbank_tables", "aprilx_counting_handler",
     "aprilx_session_set_input_rate", "aprilx_session_input_rate", "aprilx_resampler_taps", "aprilx_resample",
+    "aprilx_session_set_confidence", "aprilx_session_confidence", "aprilx_run_confidence",
 ]
 
 _lib = None
@@ -133,6 +140,9 @@ def lib():
     L.aprilx_session_input_rate.argtypes = [vp]; L.aprilx_session_input_rate.restype = C.c_uint32
     L.aprilx_resampler_taps.argtypes = [C.c_uint32, C.c_uint32, vp, vp, sz]; L.aprilx_resampler_taps.restype = C.c_int
     L.aprilx_resample.argtypes = [vp, C.c_uint32, vp, sz, vp, sz]; L.aprilx_resample.restype = C.c_int64
+    L.aprilx_session_set_confidence.argtypes = [vp, C.c_int]; L.aprilx_session_set_confidence.restype = C.c_int
+    L.aprilx_session_confidence.argtypes = [vp]; L.aprilx_session_confidence.restype = C.c_int
+    L.aprilx_run_confidence.argtypes = [vp, C.c_int, vp, C.c_int, vp]; L.aprilx_run_confidence.restype = C.c_int
     _lib = L
     return L
 

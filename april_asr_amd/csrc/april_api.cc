@@ -817,6 +817,7 @@ void aprilx_model_stats(AprilASRModel model, int device_index, AprilxStats *out)
     Engine *e = model->m.engines[(size_t)device_index];
     out->kernels_per_step = (uint64_t)e->kernels_per_step();
     for (int i = 0; i < 6; ++i) { out->kernel_ms[i] = e->timing(i).ms; out->kernel_launches[i] = (uint64_t)e->timing(i).launches; }
+    out->confidence_records = e->confidence_records();
     out->resample_ms = e->timing(Engine::T_RESAMPLE).ms; out->resample_launches = (uint64_t)e->timing(Engine::T_RESAMPLE).launches;
     double gms = 0; long gl = 0, gr = 0;
     e->gates_clock(&gms, &gl, &gr);

@@ -359,6 +359,10 @@ Engine::~Engine()
     if (zargs_h_) { (void)hipHostFree(zargs_h_); (void)hipFree(zargs_d_); }
     for (int i = 0; i < 3; ++i) if (zargs_done_[i]) (void)hipEventDestroy(zargs_done_[i]);
     for (void *p : {(void *)lm_now_d_, (void *)lm_rows_d_, (void *)lm_rec_off_d_}) if (p) (void)hipFree(p);
+    if (conf_k_d_) (void)hipFree(conf_k_d_);
+    if (conf_d_) (void)hipFree(conf_d_);
+    if (conf_k_h_) (void)hipHostFree(conf_k_h_);
+    if (conf_h_) (void)hipHostFree(conf_h_);
     if (ws_g_) (void)hipFree(ws_g_);
     if (conv_wt_) (void)hipFree(conv_wt_);
     if (dec_table_) (void)hipFree(dec_table_);
@@ -442,6 +446,7 @@ void Engine::free_slot(int slot)
     // the slot goes back to the free list once it has been reset to the reference's calloc'd tensors (april_session.c:40-58)
     // and a [blank, blank] context -- in a batch: when 256 freed slots have gathered, when the free list runs dry, or before
     // the next flight is launched (begin_flight), stream-ordered ahead of any later use of the slot
+    if (conf_ever_.load(std::memory_order_relaxed)) set_slot_confidence(slot, 0);     // the next owner starts with confidences off
     std::lock_guard<std::mutex> g(slot_mu_);
     zero_pending_.push_back(slot);
     --live_;
@@ -869,6 +874,7 @@ void Engine::run_greedy_rounds(int n, const GreedyIo &io)
         a.logits_dump = io.dump ? io.dump + (size_t)round * n * d.vocab : nullptr;
         a.dec = dec_params(); a.de_out = dec_table_ ? nullptr : de_; a.ld_de = d.d_model;
         a.run_flags = flags_d_; a.rerun_flags = flags_d_ + 4;
+        a.conf_k = conf_k_d_; a.conf_ring = conf_d_;          // (null until a session of this engine asks for confidences)
         timed_begin(T_DEC); launch_decide(a, search_stream_); timed_end(T_DEC);
         if (!dec_table_) run_decproj(n, d_slots, dirty_d_, flags_d_ + 4 + round, gen);
     }
@@ -1483,6 +1489,7 @@ int Engine::lm_step(int m, int T, const int *slots, const int *ring_tails, const
     for (int t = 0; t < T; ++t) memcpy(blk + m + 2 * rows + (size_t)t * m, slots, (size_t)m * 4);
     step_off_h_[k] = (int)ring_pos_; rec_off_h_[k] = (int)rec_pos_;
     ring_pos_ += (size_t)m + 3 * (size_t)rows; rec_pos_ += (size_t)3 * rows;
+    if (conf_k_h_) note_conf_step(k, slots, m, (size_t)3 * rows);
     std::lock_guard<std::mutex> cg(capture_mu_);
     if (mode == 1) {                 // the chunk steps of one feed as a wavefront over the layers (run_sw_chain)
         // a shape is captured into graphs the SECOND time it is seen (by either flight parity): capturing costs a few
@@ -1605,6 +1612,54 @@ int Engine::lm_step(int m, int T, const int *slots, const int *ring_tails, const
 }
 
 
+// ---------------------------------------------------------------- confidences
+// Stepping thread, between two flights' enqueues.  The decision launches carry the per-slot K bytes and the side ring as kernel
+// arguments, null while nobody has opted in: graphs captured until then hold the null pointers, so the first opt-in drops every
+// captured graph (they are captured again at their next use) after the streams have drained.  From then on the pointers never change.
+void Engine::apply_confidence_pending()
+{
+    std::vector<std::pair<int, int>> todo;
+    { std::lock_guard<std::mutex> g(conf_mu_); todo.swap(conf_pending_); conf_has_pending_.store(false, std::memory_order_release); }
+    if (!conf_k_h_) {
+        bool any = false;
+        for (const auto &t : todo) any = any || t.second > 0;
+        if (!any) return;
+        std::lock_guard<std::mutex> cg(capture_mu_);
+        HipLegacyLock legacy;
+        sync();
+        for (auto &g : step_graphs_) (void)hipGraphExecDestroy(g.second);
+        step_graphs_.clear(); step_seen_.clear();
+        for (auto &g : lm_graphs_) (void)hipGraphExecDestroy(g.second);
+        lm_graphs_.clear();
+        for (auto &g : lm_search_graphs_) (void)hipGraphExecDestroy(g.second);
+        lm_search_graphs_.clear();
+        for (auto &p : sw_plans_) {
+            if (p.second.graph) { (void)hipGraphExecDestroy(p.second.graph); p.second.graph = nullptr; }
+            for (hipGraphExec_t &x : p.second.g3) if (x) { (void)hipGraphExecDestroy(x); x = nullptr; }
+        }
+        const size_t S = (size_t)cfg_.max_slots;
+        conf_k_d_ = dmalloc<uint8_t>(S); conf_k_h_ = hmalloc<uint8_t>(S);
+        memset(conf_k_h_, 0, S);
+        conf_d_ = dmalloc<ConfRecord>(2 * rec_cap_); conf_h_ = hmalloc<ConfRecord>(2 * rec_cap_);
+        LOGI("engine: confidences on (side ring %.0f MB on the device and pinned)", 2.0 * rec_cap_ * sizeof(ConfRecord) / 1e6);
+    }
+    for (const auto &t : todo) if (t.first >= 0 && t.first < cfg_.max_slots) conf_k_h_[t.first] = (uint8_t)t.second;
+    // whole table, stream-ordered ahead of this flight's steps.  Slots of other sessions keep their values (a flight still in
+    // the air reads the same bytes before and after); the slots that change belong to idle sessions.
+    std::lock_guard<std::mutex> cg(capture_mu_);
+    HIP_CHECK(hipMemcpyAsync(conf_k_d_, conf_k_h_, (size_t)cfg_.max_slots, hipMemcpyHostToDevice, stream_));
+}
+
+void Engine::note_conf_step(int k, const int *slots, int m, size_t records)
+{
+    bool any = false;
+    for (int i = 0; i < m && !any; ++i) any = conf_k_h_[slots[i]] != 0;
+    if (!any) return;
+    const size_t first = (size_t)rec_off_h_[k];
+    if (!conf_spans_.empty() && conf_spans_.back().first + conf_spans_.back().second == first) conf_spans_.back().second += records;
+    else conf_spans_.push_back(std::make_pair(first, records));
+}
+
 // Flights alternate between the two halves of the per-flight rings, so that the host can enqueue flight k + 1 while the GPU
 // still runs flight k and the records of flight k are still being read (Scheduler::loop).  The device step counter starts at
 // the half's first step index: the step tables are indexed by it, so the launch chains (graphs) do not depend on the parity.
@@ -1623,6 +1678,8 @@ void Engine::begin_flight()
     // previous one: it must have completed -- the scheduler keeps at most two flights open and completes them in order, so the event
     // is done long ago and this costs nothing; any other caller would silently overwrite an in-flight search
     if (flight_open_[p]) { HIP_CHECK(hipEventSynchronize(flight_done_[p])); flight_open_[p] = false; }
+    if (conf_has_pending_.load(std::memory_order_acquire)) apply_confidence_pending();
+    conf_spans_.clear();
     ring_base_ = (size_t)p * ring_cap_; rec_base_ = (size_t)p * rec_cap_;
     ring_pos_ = ring_base_; rec_pos_ = rec_base_; flight_steps_ = 0;
     select_parity(p);
@@ -1644,6 +1701,7 @@ int Engine::step(int m, const int *slots, const int *ring_tails, const int *now_
     memcpy(blk, slots, (size_t)m * 4); memcpy(blk + m, ring_tails, (size_t)m * 4); memcpy(blk + 2 * m, now_ms, (size_t)m * 4);
     step_off_h_[k] = (int)ring_pos_; rec_off_h_[k] = (int)rec_pos_;
     ring_pos_ += (size_t)3 * m; rec_pos_ += (size_t)3 * m;
+    if (conf_k_h_) note_conf_step(k, slots, m, (size_t)3 * m);
     // The whole per-chunk chain (index fetch + 58 kernels) is replayed from a hipGraph captured once per batch size (and flight
     // parity: the parity selects buffers): at small batches the chain is launch-bound on the host (~3.5 us per launch), the
     // replay is not.  Kernel arguments depend only on m; the step's indices and its record offset reach the kernels through
@@ -1724,6 +1782,11 @@ int Engine::close_flight()
         if (s_unseen_by_m_) { join(stream_, s_stream_); s_unseen_by_m_ = false; }
     }
     if (rec_pos_ > rec_base_) HIP_CHECK(hipMemcpyAsync(rec_h_ + rec_base_, rec_d_ + rec_base_, (rec_pos_ - rec_base_) * sizeof(StepRecord), hipMemcpyDeviceToHost, tail));
+    for (const auto &sp : conf_spans_) {          // side records: only the steps that hold a row of a session with confidences on
+        HIP_CHECK(hipMemcpyAsync(conf_h_ + sp.first, conf_d_ + sp.first, sp.second * sizeof(ConfRecord), hipMemcpyDeviceToHost, tail));
+        conf_copied_.fetch_add(sp.second, std::memory_order_relaxed);
+    }
+    conf_spans_.clear();
     HIP_CHECK(hipEventRecord(flight_done_[flight_parity_], tail));
     flight_open_[flight_parity_] = true;
     return flight_parity_;
@@ -1894,6 +1957,41 @@ void Engine::debug_decide(int n, int op, const float *logits, float early_emit, 
     sync();
     HIP_CHECK(hipMemcpy(state_io, gstate_, (size_t)n * sizeof(GreedyState), hipMemcpyDeviceToHost));
     (void)hipFree(slots_d); (void)hipFree(now_d); (void)hipFree(active_d); (void)hipFree(dirty_d); (void)hipFree(rec_d);
+    zero_slots(n);
+}
+
+void Engine::debug_confidence(int n, const float *logits, int k, ConfRecord *out)
+{
+    std::lock_guard<std::mutex> cg(capture_mu_);
+    HipLegacyLock legacy;
+    const NetDims &d = L_.dims;
+    HIP_CHECK(hipSetDevice(cfg_.device));
+    if (n > cfg_.max_batch || n > cfg_.max_slots) { LOGE("debug_confidence: n too large"); abort(); }
+    std::vector<int> slots((size_t)n), zeros((size_t)n, 0), gen((size_t)n, 1);
+    for (int i = 0; i < n; ++i) slots[(size_t)i] = i;
+    int *slots_d = dmalloc<int>((size_t)n), *now_d = dmalloc<int>((size_t)n), *active_d = dmalloc<int>((size_t)n), *dirty_d = dmalloc<int>((size_t)n);
+    StepRecord *rec_d = dmalloc<StepRecord>((size_t)n);
+    ConfRecord *conf_d = dmalloc<ConfRecord>((size_t)n);
+    // as debug_decide: the logits enter as ONE partial plane with a zero bias, so the kernel sees them unchanged
+    std::vector<float> plane((size_t)n * L_.vocab_pad, -1000.0f);
+    for (int i = 0; i < n; ++i) memcpy(plane.data() + (size_t)i * L_.vocab_pad, logits + (size_t)i * d.vocab, (size_t)d.vocab * 4);
+    float *plane_d = dmalloc<float>(plane.size()), *zero_d = dmalloc<float>((size_t)L_.vocab_pad);
+    HIP_CHECK(hipMemcpy(slots_d, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(plane_d, plane.data(), plane.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemset(zero_d, 0, (size_t)L_.vocab_pad * 4));
+    HIP_CHECK(hipMemset(conf_d, 0, (size_t)n * sizeof(ConfRecord)));
+    HIP_CHECK(hipMemcpy(active_d, gen.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(now_d, zeros.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    DecideArgs a;
+    a.ws = plane_d; a.parts = 1; a.m_stride = n; a.N = L_.vocab_pad; a.M = n; a.n_valid = d.vocab;
+    a.bias = zero_d; a.blank = P_.blank_id; a.early_emit = 1.0f;
+    a.slot_idx = slots_d; a.now_ms = now_d; a.active = active_d; a.dirty = dirty_d; a.tok_class = cls_; a.state = gstate_;
+    a.rec = rec_d; a.round = 0; a.gen = 1; a.dec = dec_params(); a.de_out = nullptr;
+    a.conf = conf_d; a.conf_k_all = k;
+    launch_decide(a, stream_);
+    sync();
+    HIP_CHECK(hipMemcpy(out, conf_d, (size_t)n * sizeof(ConfRecord), hipMemcpyDeviceToHost));
+    for (void *p : {(void *)slots_d, (void *)now_d, (void *)active_d, (void *)dirty_d, (void *)rec_d, (void *)conf_d, (void *)plane_d, (void *)zero_d}) (void)hipFree(p);
     zero_slots(n);
 }
 

@@ -11,7 +11,8 @@
 //   dout   [slots][joiner]          projected decoder output of the current token context
 //   gstate [slots]                  greedy-search state (token context, last emission time, last token)
 // plus per-step work buffers sized for `max_batch` rows.  State never leaves HBM
-// between feed calls; per joiner round 16 bytes per session come back (StepRecord), once per flight.
+// between feed calls; per joiner round 16 bytes per session come back (StepRecord), once per flight, plus one side record
+// (ConfRecord, 80 bytes) per row of a session that asked for confidences (aprilx_session_set_confidence).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -144,6 +145,21 @@ public:
     // splitting over the three streams; a lone flight runs on one stream (the events between the streams cost it ~50 us)
     void set_overlap_hint(bool on) { overlap_hint_ = on; }
     const StepRecord *records(int step_index) const { return rec_h_ + rec_off_h_[step_index]; }   // [3][m], valid after end_flight()
+    // ---- per-token confidences.  Inline over plain members: the scheduler harness links session.cc
+    // against an engine of its own.  set_slot_confidence() only QUEUES the change (any thread, for an idle session's slot);
+    // begin_flight() applies it on the stepping thread: the first K > 0 of an engine allocates the per-slot bytes and the side
+    // ring (device + pinned host) and drops the captured graphs, whose decision launches were captured without them.
+    void set_slot_confidence(int slot, int k)
+    {
+        std::lock_guard<std::mutex> g(conf_mu_);
+        conf_pending_.push_back(std::make_pair(slot, k));
+        if (k > 0) conf_ever_.store(true, std::memory_order_relaxed);
+        conf_has_pending_.store(true, std::memory_order_release);
+    }
+    // side records of a step, indexed like records(); null while no session of the engine has opted in.  Valid after the
+    // flight's wait for rows of opted-in sessions whose StepRecord is valid.
+    const ConfRecord *conf_records(int step_index) const { return conf_h_ ? conf_h_ + rec_off_h_[step_index] : nullptr; }
+    uint64_t confidence_records() const { return conf_copied_.load(std::memory_order_relaxed); }     // side records copied to the host so far
     void sync();                               // stepping thread (or under capture_mu_): waits for the three streams and clears the cross-stream dependency flags
     void sync_streams();                       // any thread: waits for the three streams, nothing else
 
@@ -154,6 +170,8 @@ public:
     // parity tests of the device's copy of the search decision: one decide_kernel round (op 0) or the end-of-flush reset
     // (op 1) on slots 0..n-1 with GIVEN logits rows and search states; returns the records and the new states
     void debug_decide(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out);
+    // the side records of n GIVEN logits rows with k alternatives through decide_kernel's confidence code (aprilx_run_confidence)
+    void debug_confidence(int n, const float *logits, int k, ConfRecord *out);
     void debug_fbank(int n_frames, const int16_t *pcm_frames /*[n][padded]*/, float *out /*[n][nbins]*/);
     // one whole segment through resample_kernel (aprilx_resample); out holds resample_total(n) samples
     void debug_resample(const ResampleSpec *spec, const int16_t *pcm, size_t n, int16_t *out);
@@ -262,6 +280,16 @@ private:
     int flight_parity_ = 0, next_parity_ = 0; size_t ring_base_ = 0, rec_base_ = 0; int flight_steps_ = 0;
     uint64_t step_seq_ = 0;                    // steps enqueued since the engine started = the device's step counter (advance_kernel)
     hipEvent_t flight_done_[2] = {nullptr, nullptr};
+    // confidences: nothing below is allocated until a session opts in
+    std::mutex conf_mu_;
+    std::vector<std::pair<int, int>> conf_pending_;   // (slot, K) not yet applied (conf_mu_)
+    std::atomic<bool> conf_has_pending_{false}, conf_ever_{false};     // conf_ever_: some session of this engine has asked for K > 0
+    uint8_t *conf_k_d_ = nullptr, *conf_k_h_ = nullptr;      // [slots] K per slot: device, pinned host mirror (stepping thread)
+    ConfRecord *conf_d_ = nullptr, *conf_h_ = nullptr;       // [2 * rec_cap_] side ring, indexed like rec_d_ / rec_h_
+    std::vector<std::pair<size_t, size_t>> conf_spans_;      // (first record, count) of this flight's steps that hold an opted-in row
+    std::atomic<uint64_t> conf_copied_{0};
+    void apply_confidence_pending();
+    void note_conf_step(int k, const int *slots, int m, size_t records);
     bool flight_open_[2] = {false, false};     // flight_done_[p] has been recorded and not yet waited for by begin_flight (wait_flight leaves it set: waiting twice is free)
     // streams (engine.cc "streams"): front end / search beside the layer chain, the per-parity buffers that make it safe
     hipStream_t f_stream_ = nullptr, s_stream_ = nullptr, search_stream_ = nullptr;

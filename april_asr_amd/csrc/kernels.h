@@ -213,6 +213,13 @@ void launch_row_z(const RowArgs *host_args, int n, const RowArgs *dev_args, hipS
 // device keeps what the NEXT network call depends on, so a chunk needs no host decision.
 // One joiner round of one session.  flags: 1 = valid (the round ran), 2 = resolved to blank, 4 = context changed
 struct StepRecord { int32_t idx; float max_val; float blank_val; uint32_t flags; };
+// Side record of one joiner round of a session that asked for confidences (aprilx_session_set_confidence):
+// log-sum-exp of the round's logits, the blank's logit and the n_alt best non-blank ids with their logits (logit descending, lower
+// id first on ties; [0] is StepRecord.idx / max_val bit for bit).  Unused entries hold id -1 / logit 0, so a record is a fixed
+// function of (row, K).  Written by decide_kernel beside the StepRecord, in a ring of its own with the same indexing.
+constexpr int kConfMaxAlt = 8;
+struct ConfRecord { float lse; float blank_val; int32_t n_alt; uint32_t reserved; int32_t alt_id[kConfMaxAlt]; float alt_logit[kConfMaxAlt]; };
+static_assert(sizeof(ConfRecord) == 80, "ConfRecord is 20 x 32 bit");
 enum { REC_VALID = 1, REC_BLANK = 2, REC_CTX = 4 };
 enum TokClassBits { TKC_WORD_START = 1, TKC_SENT_END = 2, TKC_COMMA = 4, TKC_DOT = 8, TKC_DIGIT_START = 16 };
 
@@ -250,6 +257,11 @@ struct DecideArgs {
     // rerun[r] == gen: some row's context changed in round r.  A round nobody needs costs three empty launches.
     int *run_flags = nullptr;              // [3]
     int *rerun_flags = nullptr;            // [3]
+    // confidences (kernels_confidence.inc): null / 0 unless a session of the engine opted in.  conf_k: per-slot K (0 = off);
+    // the side record goes to conf_ring at the StepRecord's ring index, or to conf[row] with conf_k_all alternatives (tests)
+    const uint8_t *conf_k = nullptr;       // [slots]
+    ConfRecord *conf_ring = nullptr;
+    ConfRecord *conf = nullptr; int conf_k_all = 0;
 };
 void launch_decide(const DecideArgs &a, hipStream_t s);
 

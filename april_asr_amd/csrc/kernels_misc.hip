@@ -125,13 +125,18 @@ __device__ __forceinline__ void dec_embed_row(const DecEmbedParams &p, int tok0,
     }
 }
 
+#include "kernels_confidence.inc"
+
 // ---------------------------------------------------------------- joiner decision
 // logits = tree(ws) + bias; masked arg-max (reference src/april_session.c:311-320: first maximum wins, blank excluded);
 // then the part of aas_process_logits (:322-429) that the NEXT network call depends on: blank or not, context push,
 // the >= 2200 ms silence reset of the context, and the class of the last active token (digit-dot rule).  Everything the
 // callbacks need (token text, active list, de-duplication) stays on the host, which replays the same decisions from the
 // 16-byte record written here.
-__global__ __launch_bounds__(256) void decide_kernel(DecideArgs a)
+// CONF = false is the kernel as it was before confidences existed (engines where no session has opted in launch only that one);
+// CONF = true adds the side record of rows whose session asked for it (kernels_confidence.inc), after the decision.
+template <bool CONF>
+__device__ __forceinline__ void decide_body(const DecideArgs &a)
 {
     __shared__ float s_best[4], s_blank[4];
     __shared__ int s_idx[4];
@@ -216,11 +221,22 @@ __global__ __launch_bounds__(256) void decide_kernel(DecideArgs a)
     }
     __syncthreads();
     if (s_ctx[2] && a.de_out) dec_embed_row(a.dec, s_ctx[0], s_ctx[1], a.de_out + (size_t)m * a.ld_de);     // (no table: the decoder runs for this row)
+    if (CONF) {      // sessions that asked for confidences: the side record of this round, beside the StepRecord (uniform per workgroup)
+        if (a.conf) confidence_row(a, m, a.conf_k_all, a.conf + m);
+        else {
+            const int k = a.conf_k[a.slot_idx[m]];
+            if (k) confidence_row(a, m, k, a.conf_ring + (rec - a.rec_ring));
+        }
+    }
 }
+
+__global__ __launch_bounds__(256) void decide_kernel(DecideArgs a) { decide_body<false>(a); }
+__global__ __launch_bounds__(256) void decide_conf_kernel(DecideArgs a) { decide_body<true>(a); }
 
 void launch_decide(const DecideArgs &a, hipStream_t s)
 {
-    hipLaunchKernelGGL(decide_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a);
+    if (a.conf || a.conf_k) hipLaunchKernelGGL(decide_conf_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(decide_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a);
 }
 
 // decoder front end for listed slots with the context held on the device (first use of a session, end of a flush)

@@ -41,6 +41,7 @@ void Greedy::init(const ModelParams *p, const std::vector<uint8_t> *cls)
     memset(active_, 0, sizeof active_);
     for (int &i : active_id_) i = -1;
     head_ = last_call_head_ = 0;
+    conf_k_ = 0; side_ = nullptr; evals_ = 0;
     emitted_silence_ = true;                       // april_session.c:64
     last_emit_ms_ = 0;
     ctx[0] = ctx[1] = 0;
@@ -51,7 +52,32 @@ void Greedy::call(int type, size_t count, std::vector<Event> &out)
 {
     Event e; e.type = type;
     e.tokens.assign(active_, active_ + count);
+    if (conf_k_ && count) {
+        e.infos.assign(info_, info_ + count);
+        for (size_t i = 0; i < count; ++i) e.tokens[i].reserved = &e.infos[i];
+    }
     out.push_back(std::move(e));
+}
+
+// the round's side record (Engine::conf_records) as the public struct; without a side record (no device behind this search)
+// the values are NaN and n_alt is 0
+void Greedy::fill_info(uint64_t eval_index)
+{
+    AprilxTokenInfo &o = cur_info_;
+    memset(&o, 0, sizeof o);
+    o.size = (uint32_t)sizeof(AprilxTokenInfo);
+    o.eval_index = eval_index;
+    const float nan = __builtin_nanf("");
+    o.lse = o.token_logprob = o.blank_logprob = nan;
+    for (int i = 0; i < 8; ++i) o.alt_id[i] = -1;
+    if (!side_) return;
+    const ConfRecord &c = *side_;
+    o.n_alt = (uint32_t)std::max(0, std::min(c.n_alt, std::min(conf_k_, (int)kConfMaxAlt)));
+    o.lse = c.lse;
+    if (o.n_alt) o.token_logprob = c.alt_logit[0] - c.lse;
+    o.blank_logprob = c.blank_val - c.lse;
+    for (uint32_t i = 0; i < o.n_alt; ++i) { o.alt_id[i] = c.alt_id[i]; o.alt_logit[i] = c.alt_logit[i]; }
+    side_ = nullptr;
 }
 
 void Greedy::push_ctx(int tok) { ctx[0] = ctx[1]; ctx[1] = tok; ctx_dirty = true; }   // :181-196 (context_size == 2)
@@ -83,6 +109,7 @@ void Greedy::finalize_before_word(const AprilToken &incoming, std::vector<Event>
     call(APRIL_RESULT_RECOGNITION_FINAL, start, out);
     memmove(active_, active_ + start, sizeof(AprilToken) * (head_ - start));
     memmove(active_id_, active_id_ + start, sizeof(int) * (head_ - start));
+    if (conf_k_) memmove(info_, info_ + start, sizeof(AprilxTokenInfo) * (head_ - start));
     head_ -= start;
 }
 
@@ -100,6 +127,7 @@ bool Greedy::emit_partial(const AprilToken *tok, int tok_id, bool force, std::ve
         if (!force && last_call_head_ == head_ + 1 && active_id_[head_] == tok_id) return false;
         active_[head_] = *tok;
         active_id_[head_] = tok_id;
+        if (conf_k_) info_[head_] = cur_info_;
         ++head_;
     } else if (!force && last_call_head_ == head_) {
         return false;
@@ -129,6 +157,8 @@ bool Greedy::on_joint(const JointResult &r, float early_emit, size_t now_ms, std
     tok.flags = (AprilTokenFlagBits)0;
     tok.time_ms = now_ms;
     tok.reserved = nullptr;
+    const uint64_t eval_index = evals_++;
+    if (conf_k_) fill_info(eval_index);
     int flags = 0;
     if (tc & TK_WORD_START) flags |= APRIL_TOKEN_FLAG_WORD_BOUNDARY_BIT;
     bool eos = (tc & TK_SENT_END) != 0;
@@ -435,6 +465,17 @@ bool Scheduler::set_input_rate(Session *s, const ResampleSpec *spec)
     if (s->closing || s->busy || s->fed || s->flush_requested || !s->inbox.empty() || s->borrow_cnt || s->seg_open || s->flush_phase) return false;
     s->fb.set_rate(spec);
     s->ring_limit = spec ? (size_t)(48000ull * spec->in_rate / spec->out_rate) : 48000;
+    return true;
+}
+
+bool Scheduler::set_confidence(Session *s, int k)
+{
+    wait_idle(s);
+    std::lock_guard<std::mutex> g(mu_);
+    if (s->closing || s->busy || s->fed || s->flush_requested || !s->inbox.empty() || s->borrow_cnt || s->seg_open || s->flush_phase) return false;
+    if (k == s->greedy.confidence()) return true;
+    s->greedy.set_confidence(k);
+    eng_->set_slot_confidence(s->slot, k);          // (queued: the stepping thread applies it before the session's next flight)
     return true;
 }
 
@@ -1017,8 +1058,10 @@ void Scheduler::replay(Flight &f)
             const Session::Replay &it = s->replay[q];
             if (it.kind == 1) { s->greedy.finish_flush(s->events); s->greedy.ctx_dirty = false; continue; }
             const StepRecord *recs = eng_->records(it.step);
+            const ConfRecord *side = s->greedy.confidence() ? eng_->conf_records(it.step) : nullptr;
             for (int r = 0; r < 3; ++r) {                               // april_session.c:449-454
                 const StepRecord &rec = recs[((size_t)it.chunk * 3 + r) * it.rows + it.row];
+                if (side) s->greedy.set_side(&side[((size_t)it.chunk * 3 + r) * it.rows + it.row]);
                 if (!(rec.flags & REC_VALID)) { tick_.replay_mismatch++; LOGE("replay: device skipped a round the host expected (slot %d)", s->slot); break; }
                 const JointResult jr{rec.idx, rec.max_val, rec.blank_val};
                 const bool blank = s->greedy.on_joint(jr, r == 0 ? 1.0f : 0.0f, (size_t)it.now_ms, s->events);

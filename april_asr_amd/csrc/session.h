@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/april_api.h"
+#include "../../include/aprilx_engine.h"
 #include "engine.h"
 #include "model_loader.h"
 
@@ -44,6 +45,9 @@ struct JointResult { int32_t idx; float max_val; float blank_val; };     // what
 struct Event {
     int type;                         // AprilResultType
     std::vector<AprilToken> tokens;
+    // sessions with confidences on (aprilx_session_set_confidence): one entry per token, and tokens[i].reserved points to infos[i].
+    // Events are only ever MOVED between containers (the vector's storage, and with it the pointers, stay where they are).
+    std::vector<AprilxTokenInfo> infos;
 };
 
 class Greedy {
@@ -55,6 +59,11 @@ public:
     // end of flush: FINAL, clear context, SILENCE (reference src/april_session.c:561-563)
     void finish_flush(std::vector<Event> &out);
     void reset_context_to_blank();            // first use: context = [blank, blank]
+    // confidences: K alternatives per delivered token, 0 = off.  With K > 0 the caller hands the round's
+    // side record to set_side() before each on_joint(); the token's AprilxTokenInfo is kept beside active_[] and travels with it.
+    void set_confidence(int k) { conf_k_ = k; }
+    int confidence() const { return conf_k_; }
+    void set_side(const ConfRecord *side) { side_ = side; }
     int ctx[2] = {0, 0};
     bool ctx_dirty = false;                   // decoder must be re-run for this session
 
@@ -71,6 +80,12 @@ private:
     const std::vector<uint8_t> *cls_ = nullptr;
     AprilToken active_[kMaxActive];
     int active_id_[kMaxActive];
+    AprilxTokenInfo info_[kMaxActive];        // (conf_k_ > 0) beside active_[]: moved and dropped with it
+    AprilxTokenInfo cur_info_;                // the info of the round on_joint is working on
+    void fill_info(uint64_t eval_index);
+    int conf_k_ = 0;
+    const ConfRecord *side_ = nullptr;
+    uint64_t evals_ = 0;                      // joiner evaluations consumed so far = rows aprilx_session_trace_logits has written
     size_t head_ = 0, last_call_head_ = 0;
     bool emitted_silence_ = true;
     size_t last_emit_ms_ = 0;
@@ -184,6 +199,8 @@ public:
     void wait_idle(Session *s);                    // everything queued so far has been processed
     // aprilx_session_set_input_rate: false when audio is queued or the session has an open segment
     bool set_input_rate(Session *s, const ResampleSpec *spec);
+    // aprilx_session_set_confidence: the same rule
+    bool set_confidence(Session *s, int k);
     void wait_idle_many(Session *const *ss, int n);
     // until every listed session has at most `max_open` feeds that were submitted and not completed yet (pipelined group feeds)
     void wait_backlog(Session *const *ss, int n, uint64_t max_open);

@@ -4,12 +4,14 @@
 // before it).  The reference has no counterpart: its sessions are fed one by one (example.cpp) and each runs its own ONNX graphs.
 //
 //   g++ -O2 -std=c++17 examples/serve_many.cpp -I include -L april_asr_amd -laprilasr -Wl,-rpath,$PWD/april_asr_amd -o serve_many
-//   ./serve_many model.april audio.raw [sessions=64] [mode=pipelined|lockstep] [input_rate]
+//   ./serve_many model.april audio.raw [sessions=64] [mode=pipelined|lockstep] [input_rate] [--alternatives K]
 //
 // Every session gets the same PCM16 file, rotated by (session index x 0.37 s) so that the streams differ.  With `input_rate` the file
 // is PCM16 at that rate and every session is told so (aprilx_session_set_input_rate): the library converts it to the model's rate on
 // the GPU; the feeds stay 100 ms of audio (input_rate / 10 samples).  Prints one line per
 // session -- "<index> <callbacks> <final results> <tokens in final results> <text of the last final result>" -- and the wall time.
+// `--alternatives K` (anywhere on the line) asks every session for per-token confidences with K alternatives
+// (aprilx_session_set_confidence) and adds the mean confidence of the tokens in final results to the timing line.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -19,7 +21,9 @@
 #include "april_api.h"
 #include "aprilx_engine.h"
 
-struct Stream { size_t calls = 0, finals = 0, final_tokens = 0; std::string last_final; };
+#include <cmath>
+
+struct Stream { size_t calls = 0, finals = 0, final_tokens = 0; std::string last_final; double conf_sum = 0; size_t conf_n = 0; };
 
 static void on_result(void *ud, AprilResultType type, size_t count, const AprilToken *tokens)
 {
@@ -28,11 +32,22 @@ static void on_result(void *ud, AprilResultType type, size_t count, const AprilT
     if (type != APRIL_RESULT_RECOGNITION_FINAL) return;
     s->finals++; s->final_tokens += count;
     s->last_final.clear();
-    for (size_t i = 0; i < count; ++i) s->last_final += tokens[i].token;
+    for (size_t i = 0; i < count; ++i) {
+        s->last_final += tokens[i].token;
+        if (const AprilxTokenInfo *info = static_cast<const AprilxTokenInfo *>(tokens[i].reserved)) { s->conf_sum += std::exp((double)info->token_logprob); s->conf_n++; }
+    }
 }
 
 int main(int argc, char **argv)
 {
+    int alternatives = 0;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!strcmp(argv[i], "--alternatives")) {
+            alternatives = atoi(argv[i + 1]);
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
     if (argc < 3) { fprintf(stderr, "usage: %s <model.april> <audio.raw (PCM16 mono)> [sessions=64] [pipelined|lockstep] [input_rate]\n", argv[0]); return 2; }
     const int n = argc > 3 ? atoi(argv[3]) : 64;
     const bool pipelined = !(argc > 4 && !strcmp(argv[4], "lockstep"));
@@ -60,6 +75,7 @@ int main(int argc, char **argv)
         sessions[(size_t)i] = aas_create_session(model, cfg);
         if (!sessions[(size_t)i]) { fprintf(stderr, "failed to create session %d\n", i); return 1; }
         if (argc > 5 && aprilx_session_set_input_rate(sessions[(size_t)i], (uint32_t)rate) != 0) { fprintf(stderr, "input rate %zu refused\n", rate); return 1; }
+        if (alternatives && aprilx_session_set_confidence(sessions[(size_t)i], alternatives) != 0) { fprintf(stderr, "%d alternatives refused\n", alternatives); return 1; }
         const size_t rot = ((size_t)i * (size_t)(0.37 * rate)) % pcm.size();
         audio[(size_t)i].assign(pcm.begin() + (long)rot, pcm.end());
         audio[(size_t)i].insert(audio[(size_t)i].end(), pcm.begin(), pcm.begin() + (long)rot);
@@ -78,6 +94,11 @@ int main(int argc, char **argv)
     for (int i = 0; i < n; ++i) printf("%d %zu %zu %zu %s\n", i, streams[(size_t)i].calls, streams[(size_t)i].finals, streams[(size_t)i].final_tokens, streams[(size_t)i].last_final.c_str());
     fprintf(stderr, "%d streams x %.1f s of audio in %.1f ms (%s feed): %.0f audio-seconds per second\n", n, steps * 0.1, ms, pipelined ? "pipelined" : "lock-step",
             n * steps * 0.1 / (ms * 1e-3));
+    if (alternatives) {
+        double sum = 0; size_t cnt = 0;
+        for (const Stream &s : streams) { sum += s.conf_sum; cnt += s.conf_n; }
+        fprintf(stderr, "%d alternatives: %.3f ms per 100 ms step, mean confidence of %zu final tokens %.3f\n", alternatives, ms / (double)steps, cnt, cnt ? sum / (double)cnt : 0.0);
+    }
     if (argc > 5) fprintf(stderr, "input at %zu Hz: %.3f ms per 100 ms step\n", rate, ms / (double)steps);
     for (AprilASRSession s : sessions) aas_free(s);
     aam_free(model);

@@ -142,6 +142,35 @@ APRIL_EXPORT int aprilx_resampler_taps(uint32_t in_rate, uint32_t out_rate, int3
  * samples (-1 on refusal or cap too small).  Tests only (extends aprilx_run_fbank's parity role to the resampler). */
 APRIL_EXPORT int64_t aprilx_resample(AprilASRModel model, uint32_t in_rate, const int16_t *pcm, size_t n, int16_t *out, size_t cap);
 
+/* ---- per-token confidence and alternatives ------------------------------------------------
+ * AprilToken.logprob (reference april_api.h:118-137) is the raw joiner logit of the token -- the reference does no softmax -- which
+ * cannot be compared between tokens, sessions or models.  A session can ask for the log-softmax of every token it delivers, the
+ * blank's, and the K best non-blank candidates of the joiner evaluation that produced it; they are computed where the search
+ * already reads the logit row, on the GPU, and change no decision (DESIGN.md section 12 has the contract and its error bound).
+ * Extends AprilToken through the field the reference reserves: for such a session AprilToken.reserved of every delivered token
+ * (partial and final results, provisional tokens included) points to an AprilxTokenInfo that is valid for the duration of the
+ * handler call, like the token array itself.  For every other session it stays NULL; AprilToken.logprob is unchanged in both cases. */
+typedef struct AprilxTokenInfo {
+    uint32_t size;            /* sizeof(AprilxTokenInfo) as the library was built */
+    uint32_t n_alt;           /* valid entries below, <= K */
+    uint64_t eval_index;      /* ordinal of the session's joiner evaluation that produced the token: the row
+                                 aprilx_session_trace_logits would have written for it */
+    float lse;                /* log-sum-exp of the evaluation's logits */
+    float token_logprob;      /* log-softmax of the token = alt_logit[0] - lse */
+    float blank_logprob;      /* log-softmax of the blank */
+    float reserved0;
+    int32_t alt_id[8];        /* non-blank ids by descending logit; [0] is the token itself */
+    float alt_logit[8];       /* their raw logits; log-softmax = alt_logit[i] - lse */
+} AprilxTokenInfo;
+/* Extends aas_create_session (reference april_api.h:174): 0 = off (default), 1..8 = K.  0 on success; -1 on a bad K or when the session
+   has audio queued or fed since its creation / last completed aas_flush (the rule of aprilx_session_set_input_rate). */
+APRIL_EXPORT int aprilx_session_set_confidence(AprilASRSession session, int n_alternatives);
+/* The session's K (0 = off). */
+APRIL_EXPORT int aprilx_session_confidence(AprilASRSession session);
+/* Tests only, beside aprilx_run_decide: the side records of n GIVEN logits rows [n][vocab] with K alternatives,
+   through the device code the search uses; out = n AprilxTokenInfo (eval_index = row). */
+APRIL_EXPORT int aprilx_run_confidence(AprilASRModel model, int n, const float *logits, int k, AprilxTokenInfo *out);
+
 /* ---- tracing / statistics ---------------------------------------------------------------*/
 /* every joiner evaluation of this session appends `vocab` floats to buf (tests only; chunk steps of a traced session are
    issued eagerly and waited for one by one) */
@@ -181,6 +210,7 @@ typedef struct AprilxStats {
     double gates_clock_ms; uint64_t gates_clock_launches, gates_clock_rows;
     double gates_clock_ms_by_n[4]; uint64_t gates_clock_launches_by_n[4];   /* the same, split by the problems sharing the launch (1, 2, 3, >= 4) */
     double resample_ms; uint64_t resample_launches;   /* profiling: the resample launches of sessions with an input rate of their own (before the fbank) */
+    uint64_t confidence_records; /* side records (aprilx_session_set_confidence) copied to the host so far; 0 while no session has opted in */
 } AprilxStats;
 APRIL_EXPORT void aprilx_model_stats(AprilASRModel model, int device_index, AprilxStats *out);
 /* Hand-over -> delivery latency of the last (up to 8192) completed ticks of one GPU's stepping thread, in ms, oldest first: from the
