@@ -478,6 +478,19 @@ void Engine::sync()
 // aprilx_session_read_frames / aprilx_session_context on an idle session while other sessions stream (found in round 5 by running
 // tests/sched_harness/driver.cc against the real engine: the reader's hipMemcpy aborted the process).  The stepping thread itself
 // issues nothing but kernel launches, async copies and event records inside a capture.
+template <typename Chain> static hipGraphExec_t capture_graph(hipStream_t st, Chain &&chain)
+{
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    HipLegacyLock capture_guard;      // (no legacy-stream call of any thread during the capture: see engine.h)
+    HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+    chain();
+    HIP_CHECK(hipStreamEndCapture(st, &graph));
+    HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    HIP_CHECK(hipGraphDestroy(graph));
+    return exec;
+}
+
 // ---------------------------------------------------------------- streams
 // Three in-order streams.  stream_ (M) carries the layer chain and every launch of the general paths; f_stream_ (F) the PCM
 // upload and the fbank kernel of every flight and, for a feed that runs as a split wavefront (lm_step mode 1), its index fetch
@@ -705,111 +718,181 @@ const float *Engine::resample_table(const ResampleSpec *spec)
 }
 
 // ---------------------------------------------------------------- encoder
-// Launch count per chunk at batch sizes where the full-K schedule applies: 2 (conv) + 1 (embed) + 4 per layer + 1.
+// Every GEMM of the encoder is stated ONCE, as the argument block of its fused form over rows [r0, r0 + rows) of the work buffers
+// (row r of y / ssq / xb / u / ff / p_lm / a3 / xin belongs to row r of the step: a chunk step works on rows 0 .. n - 1, the
+// layer-major stages and the wavefronts on the rows of their time steps; the sessions' slots are step_d_[0 .. m - 1]).  The chains
+// differ only in how they LAUNCH the blocks: one by one (run_encoder_rows, lm_stage_layer; the row-epilogue GEMMs through
+// launch_rowepi, which asks the planner) or z-batched over the active layers (sw_plan, run_lm_wavefront: force_fullk as built).
 // BasicNorm never runs as a kernel: EPI_RESID_SSQ leaves y and its per-32-column sums of squares, and every consumer
 // of the normalised row (the next layer's gate GEMM, its residual, encoder_proj) folds the row scale in (kernels.h).
-void Engine::run_encoder_rows(int n, const int *d_slots, const int *d_tails, const float *x_direct)
+
+// scale of the rows that enter layer l (l == n_layers: encoder_proj): epsilon of the BasicNorm that produced them
+RowScale Engine::in_scale(int l, size_t r0) const
+{
+    const NetDims &d = L_.dims;
+    const int G = d.d_model / SSQ_COLS;
+    RowScale r; r.ssq = ssq_ + r0 * G; r.groups = G; r.inv_n = 1.0f / (float)(d.d_norm ? d.d_norm : d.d_model); r.eps = l == 0 ? L_.embed_eps : L_.norm_eps[(size_t)l - 1];
+    return r;
+}
+
+// The gates GEMM [norm(y) | h_prev] x Wg in its two forms.  GATES_ALL: one launch per chunk with the fused LSTM cell (chunk steps,
+// feed wavefront).  Layer-major: two launches with the SAME chains -- GATES_X, the input half for a block's rows at once,
+// P = (p0 + p1) * scale (waves 0,1; the recurrent half sits the launch out), and per time step GATES_H, the recurrent half + cell,
+// ((P + p2) + p3) + bias.  `waves` is the form's wave mask.
+GemmArgs Engine::args_gates(int l, size_t r0, int rows, int waves) const
 {
     const NetDims &d = L_.dims;
     const size_t S = (size_t)cfg_.max_slots;
-    const int G = d.d_model / SSQ_COLS;
-    auto scale_of = [&](float eps) { RowScale r; r.ssq = ssq_; r.groups = G; r.inv_n = 1.0f / (float)(d.d_norm ? d.d_norm : d.d_model); r.eps = eps; return r; };
-    // conv front end
+    const PackedLayout::Layer &o = L_.layers[(size_t)l];
+    GemmArgs g; g.a0 = y_ + r0 * d.d_model; g.lda0 = d.d_model; g.K0 = d.d_model; g.lda1 = d.d_model; g.K1 = d.d_model;
+    lin(g, o.wg); g.M = rows; g.N = 4 * d.hidden; g.K = 2 * d.d_model; g.kz = 1; g.wave_mask = waves;
+    if (f16_tile_) { g.a0 = reinterpret_cast<const float *>(y16_ + r0 * d.d_model); lin16(g, o.wg); }      // binary16 operands
+    if (waves != GATES_H) g.x_scale = in_scale(l, r0);
+    if (waves == GATES_X) {           // (a1 is never read; P stays fp32 on fp16 engines too)
+        g.a1 = g.a0; g.epi = EPI_XPART; g.out = p_lm_ + r0 * 4 * d.hidden; g.ldo = 4 * d.hidden;
+        return g;
+    }
+    g.a1 = h_ + (size_t)l * S * d.d_model; g.aidx1 = step_d_; g.epi = EPI_LSTM;
+    g.out = u_ + r0 * d.hidden; g.ldo = d.hidden; g.bias = w_ + o.bg; g.c_state = c_ + (size_t)l * S * d.hidden; g.slot_idx = step_d_; g.hidden = d.hidden;
+    if (waves == GATES_H) { g.p_add = p_lm_ + r0 * 4 * d.hidden; g.ldp = 4 * d.hidden; }      // (a0 is never read)
+    else if (cfg_.precision == 0 && gates_tile_rows(rows)) g.tile_ok = 2;      // (one problem per launch; sw_plan decides again for z-batched launches)
+    if (f16_tile_) {                  // [y16 | h16(slot)], u leaves as binary16 only (its one reader is the projection)
+        g.a1 = reinterpret_cast<const float *>(h16_ + (size_t)l * S * d.d_model); g.out = nullptr; g.out16 = u16_ + r0 * d.hidden;
+    }
+    return g;
+}
+
+// fp32 gates GEMM on the GM_TILE schedule (same chains, same bits as the hand-scheduled K-split tiles -- tests/test_gpu_gates_tile.py):
+// measured 2..5 % per feed faster from ~2000 rows per launch (1024 sessions: RTF 0.0533 vs 0.055..0.058, 2048: 0.096..0.097 vs
+// 0.099..0.104), slower at 256 sessions (53.5 vs 46.5 us per launch) and at one session.  APRIL_GATES_TILE: 0 never, 1 always,
+// 2 (default) from GATES_TILE_MIN_ROWS rows per launch.
+constexpr long GATES_TILE_MIN_ROWS = 2048;
+bool Engine::gates_tile_rows(long rows) const
+{
+    static const int mode = env_int("APRIL_GATES_TILE", 2);
+    return mode == 1 || (mode == 2 && rows >= GATES_TILE_MIN_ROWS);
+}
+
+GemmArgs Engine::args_whr(int l, size_t r0, int rows) const
+{   // h' = u x Whr ; state write + residual: xb = norm(y) + h'
+    const NetDims &d = L_.dims;
+    const size_t S = (size_t)cfg_.max_slots;
+    const PackedLayout::Layer &o = L_.layers[(size_t)l];
+    GemmArgs g; g.a0 = u_ + r0 * d.hidden; g.lda0 = d.hidden; g.K0 = d.hidden; lin(g, o.whr);
+    g.M = rows; g.N = d.d_model; g.K = d.hidden; g.kz = kz_hr_; g.tile_ok = tile_ok(); g.force_fullk = 1;
+    g.epi = EPI_HR; g.state = h_ + (size_t)l * S * d.d_model; g.ld_state = d.d_model; g.slot_idx = step_d_; g.resid = y_ + r0 * d.d_model; g.ldr = d.d_model;
+    g.r_scale = in_scale(l, r0);
+    g.out = xb_ + r0 * d.d_model; g.ldo = d.d_model;
+    if (f16_tile_) {
+        g.a0 = reinterpret_cast<const float *>(u16_ + r0 * d.hidden); lin16(g, o.whr); g.kz = kzx_hr_;
+        g.state16 = h16_ + (size_t)l * S * d.d_model; g.out16 = xb16_ + r0 * d.d_model;
+    }
+    return g;
+}
+
+GemmArgs Engine::args_ff1(int l, size_t r0, int rows) const
+{   // FFN up + DoubleSwish
+    const NetDims &d = L_.dims;
+    const PackedLayout::Layer &o = L_.layers[(size_t)l];
+    GemmArgs g; g.a0 = xb_ + r0 * d.d_model; g.lda0 = d.d_model; g.K0 = d.d_model; lin(g, o.wff1);
+    g.M = rows; g.N = d.ffn; g.K = d.d_model; g.kz = 1; g.epi = EPI_BIAS_DSWISH; g.out = ff_ + r0 * d.ffn; g.ldo = d.ffn; g.bias = w_ + o.bff1;
+    if (f16_tile_) { g.a0 = reinterpret_cast<const float *>(xb16_ + r0 * d.d_model); lin16(g, o.wff1); g.out = nullptr; g.out16 = ff16_ + r0 * d.ffn; }
+    return g;
+}
+
+GemmArgs Engine::args_ff2(int l, size_t r0, int rows) const
+{   // FFN down + bias + residual -> y, ssq (the last reader of the previous y was the projection)
+    const NetDims &d = L_.dims;
+    const PackedLayout::Layer &o = L_.layers[(size_t)l];
+    GemmArgs g; g.a0 = ff_ + r0 * d.ffn; g.lda0 = d.ffn; g.K0 = d.ffn; lin(g, o.wff2);
+    g.M = rows; g.N = d.d_model; g.K = d.ffn; g.kz = kz_ff2_; g.tile_ok = tile_ok(); g.force_fullk = 1;
+    g.epi = EPI_RESID_SSQ; g.bias = w_ + o.bff2; g.resid = xb_ + r0 * d.d_model; g.ldr = d.d_model; g.out = y_ + r0 * d.d_model; g.ldo = d.d_model; g.ssq_out = ssq_ + r0 * (d.d_model / SSQ_COLS);
+    if (f16_tile_) { g.a0 = reinterpret_cast<const float *>(ff16_ + r0 * d.ffn); lin16(g, o.wff2); g.kz = kzx_ff2_; g.out16 = y16_ + r0 * d.d_model; }
+    return g;
+}
+
+GemmArgs Engine::args_encproj(size_t r0, int rows, const int *slot_idx, float *out) const
+{   // encoder_proj(norm(y)) -> out[slot] (out[row] without slot_idx); fp32 A on every engine
+    const NetDims &d = L_.dims;
+    GemmArgs g; g.a0 = y_ + r0 * d.d_model; g.lda0 = d.d_model; g.K0 = d.d_model; lin(g, L_.w_encproj);
+    g.M = rows; g.N = d.joiner; g.K = d.d_model; g.kz = kz_proj_; g.tile_ok = tile_ok();
+    g.epi = EPI_SLOT_STORE; g.bias = w_ + L_.b_encproj; g.out = out; g.ldo = d.joiner; g.slot_idx = slot_idx; g.x_scale = in_scale(d.n_layers, r0);
+    return g;
+}
+
+// A row-epilogue GEMM given in its fused form (EPI_HR / EPI_RESID_SSQ / EPI_SLOT_STORE): the partial-plane form of the same GEMM
+// over the workspace rows of its output, and the row problem that finishes it (same arithmetic as the fused epilogue)
+static GemmArgs partial_form(const GemmArgs &f, float *ws, int m_stride)
+{
+    GemmArgs g = f;
+    g.epi = EPI_PARTIAL; g.force_fullk = 0; g.out = ws; g.m_stride = m_stride;
+    g.bias = nullptr; g.resid = nullptr; g.state = nullptr; g.slot_idx = nullptr; g.ssq_out = nullptr; g.r_scale = RowScale(); g.out16 = nullptr; g.state16 = nullptr;
+    g.x_scale = RowScale(); g.row_mask = nullptr;
+    return g;
+}
+static RowArgs row_form(const GemmArgs &f, const float *ws, int m_stride, int parts)
+{
+    RowArgs r; r.ws = ws; r.parts = parts; r.m_stride = m_stride; r.N = f.N; r.M = f.M;
+    r.resid = f.resid; r.ldr = f.ldr; r.out = f.out; r.ldo = f.ldo; r.out16 = f.out16; r.run_flag = f.run_flag; r.run_gen = f.run_gen;
+    if (f.epi == EPI_HR) { r.mode = ROW_HR; r.r_scale = f.r_scale; r.slot_idx = f.slot_idx; r.state = f.state; r.ld_state = f.ld_state; r.state16 = f.state16; }
+    else if (f.epi == EPI_RESID_SSQ) { r.mode = ROW_RESID_SSQ; r.bias = f.bias; r.ssq_out = f.ssq_out; }
+    else { r.mode = ROW_SLOT_STORE; r.bias = f.bias; r.slot_idx = f.slot_idx; r.r_scale = f.x_scale; r.row_mask = f.row_mask; }
+    return r;
+}
+
+// One row-epilogue GEMM outside the z-batched chains: its fused form when the plan (asked with `force`: take the full-K plan even
+// when it yields few workgroups) keeps all of K in the workgroup, else partial planes into `ws` + the row kernel.
+// cls: the launches' timing class, T_GEMM_OTHER (its row kernel: T_ROW) or T_DEC (both).
+void Engine::launch_rowepi(GemmArgs f, float *ws, hipStream_t st, bool force, int cls)
+{
+    const int row_cls = cls == T_DEC ? T_DEC : T_ROW;
+    f.force_fullk = force ? 1 : 0;
+    if (gemm_fullk(f.M, f.N, f.kz, force, 1, f.tile_ok)) { timed_begin(cls); launch_gemm(f, st); timed_end(cls); return; }
+    timed_begin(cls); launch_gemm(partial_form(f, ws, ws_mstride_), st); timed_end(cls);
+    timed_begin(row_cls); launch_row(row_form(f, ws, ws_mstride_, gemm_partials(f.M, f.N, f.kz, 1, f.tile_ok)), st); timed_end(row_cls);
+}
+
+// conv front end + embed linear of rows [r0, r0 + rows) -> y, ssq (and y16: layer 0 of an fp16 tile engine reads binary16 rows).
+// row_slots: the slot of every row, from row 0; ring tails: index array [1]; split-K planes of the embed GEMM, if any, go to `ws`
+void Engine::encoder_front(size_t r0, int rows, const int *row_slots, const float *x_direct, hipStream_t st, float *ws)
+{
+    const NetDims &d = L_.dims;
     ConvEmbedArgs ca;
     ca.ring = ring_; ca.ring_frames = ring_frames_; ca.mel = d.mel; ca.seg = d.seg;
-    ca.slot_idx = d_slots; ca.ring_tail = d_tails; ca.x_direct = x_direct;
+    ca.slot_idx = row_slots + r0; ca.ring_tail = step_d_ + cfg_.max_batch + r0; ca.x_direct = x_direct;
     for (int i = 0; i < 3; ++i) { ca.w[i] = w_ + L_.conv_w[i]; ca.b[i] = w_ + L_.conv_b[i]; ca.ch[i] = d.conv_ch[i]; ca.stride[i] = d.conv_stride[i]; }
     ca.ch1_per_group = 1;                                 // largest divisor of the second conv's channel count that is <= 8
     for (int k = 8; k > 1; --k) if (d.conv_ch[1] % k == 0) { ca.ch1_per_group = k; break; }
-    ca.out = a3_; ca.ldo = L_.k3; ca.M = n;
+    ca.out = a3_ + r0 * d.f_out * L_.k3; ca.ldo = L_.k3; ca.M = rows;
     if (conv_wt_) { ca.w0t = conv_wt_; ca.w1t = conv_wt_ + (size_t)9 * d.conv_ch[0]; }
-    timed_begin(T_CONV); launch_conv_embed(ca, stream_); timed_end(T_CONV);
-    {   // third conv: [n*f_out, k3] x [k3, c2] + bias, DoubleSwish -> xin[n][f_out*c2]
-        GemmArgs g; g.a0 = a3_; g.lda0 = L_.k3; g.K0 = L_.k3; g.wp = w_ + L_.conv_w[2];
-        g.M = n * d.f_out; g.N = d.conv_ch[2]; g.K = L_.k3; g.kz = 1; g.epi = EPI_BIAS_DSWISH; g.out = xin_; g.ldo = d.conv_ch[2]; g.bias = w_ + L_.conv_b[2];
-        timed_begin(T_CONV); launch_gemm(g, stream_); timed_end(T_CONV);
+    timed_begin(T_CONV); launch_conv_embed(ca, st); timed_end(T_CONV);
+    {   // third conv: [rows * f_out, k3] x [k3, c2] + bias, DoubleSwish -> xin[rows][f_out * c2]
+        GemmArgs g; g.a0 = ca.out; g.lda0 = L_.k3; g.K0 = L_.k3; g.wp = w_ + L_.conv_w[2];
+        g.M = rows * d.f_out; g.N = d.conv_ch[2]; g.K = L_.k3; g.kz = 1; g.epi = EPI_BIAS_DSWISH; g.out = xin_ + r0 * d.embed_in; g.ldo = d.conv_ch[2]; g.bias = w_ + L_.conv_b[2];
+        timed_begin(T_CONV); launch_gemm(g, st); timed_end(T_CONV);
     }
-    // y = A x W + bias (+ residual) with sums of squares: fused into the GEMM where its tiles own all of K, else split-K + row kernel
-    auto resid_ssq = [&](const float *a, int K, size_t w_off, int kz, const float *bias, const float *resid) {
-        GemmArgs g; g.a0 = a; g.lda0 = K; g.K0 = K; lin(g, w_off);
-        g.M = n; g.N = d.d_model; g.K = K; g.kz = kz; g.tile_ok = tile_ok();
-        if (gemm_fullk(n, d.d_model, kz, false, 1, tile_ok())) {
-            g.epi = EPI_RESID_SSQ; g.bias = bias; g.resid = resid; g.ldr = d.d_model; g.out = y_; g.ldo = d.d_model; g.ssq_out = ssq_;
-            timed_begin(T_GEMM_OTHER); launch_gemm(g, stream_); timed_end(T_GEMM_OTHER);
-            return;
-        }
-        g.epi = EPI_PARTIAL; g.out = ws_; g.m_stride = ws_mstride_;
-        timed_begin(T_GEMM_OTHER); launch_gemm(g, stream_); timed_end(T_GEMM_OTHER);
-        RowArgs r; r.mode = ROW_RESID_SSQ; r.ws = ws_; r.parts = gemm_partials(n, d.d_model, kz, 1, tile_ok()); r.m_stride = ws_mstride_; r.N = d.d_model; r.M = n;
-        r.bias = bias; r.resid = resid; r.ldr = d.d_model; r.out = y_; r.ldo = d.d_model; r.ssq_out = ssq_;
-        timed_begin(T_ROW); launch_row(r, stream_); timed_end(T_ROW);
-    };
-    // embed linear + bias (BasicNorm deferred)
-    resid_ssq(xin_, d.embed_in, L_.w_embed, kz_embed_, w_ + L_.b_embed, nullptr);
-    float eps_in = L_.embed_eps;                          // epsilon of the BasicNorm that produced this layer's input
-    if (f16_tile_) {
-        // fp16 tile path: the four GEMMs of every layer read binary16 activations (row block 0 of the work buffers, d_slots ==
-        // step_d_) -- the same argument blocks as the feed wavefront at chunk 0; embed and encoder_proj stay on the fp32-A kernels
-        launch_cvt_f16(y_, y16_, (size_t)n * d.d_model, stream_);
-        for (int l = 0; l < d.n_layers; ++l) {
-            timed_begin(T_GATES); launch_gemm(sw_args_gates(l, n, 0), stream_); timed_end(T_GATES);
-            launch_rowepi(lm_args_whr(l, n, 0), 0, stream_);
-            timed_begin(T_GEMM_OTHER); launch_gemm(lm_args_ff1(l, n, 0, 1), stream_); timed_end(T_GEMM_OTHER);
-            launch_rowepi(lm_args_ff2(l, n, 0, 1), 0, stream_);
-        }
-        eps_in = L_.norm_eps[(size_t)d.n_layers - 1];
+    {   // embed linear + bias -> y, ssq (BasicNorm deferred); fp32 A on every engine
+        GemmArgs g; g.a0 = xin_ + r0 * d.embed_in; g.lda0 = d.embed_in; g.K0 = d.embed_in; lin(g, L_.w_embed);
+        g.M = rows; g.N = d.d_model; g.K = d.embed_in; g.kz = kz_embed_; g.tile_ok = tile_ok();
+        g.epi = EPI_RESID_SSQ; g.bias = w_ + L_.b_embed; g.ldr = d.d_model; g.out = y_ + r0 * d.d_model; g.ldo = d.d_model; g.ssq_out = ssq_ + r0 * (d.d_model / SSQ_COLS);
+        launch_rowepi(g, ws + r0 * d.d_model, st);
     }
-    for (int l = 0; l < (f16_tile_ ? 0 : d.n_layers); ++l) {
-        const PackedLayout::Layer &o = L_.layers[(size_t)l];
-        float *h_l = h_ + (size_t)l * S * d.d_model;
-        float *c_l = c_ + (size_t)l * S * d.hidden;
-        const RowScale xs = scale_of(eps_in);
-        {   // gates = [norm(y) | h_prev] x Wg ; fused LSTM cell
-            GemmArgs g; g.a0 = y_; g.lda0 = d.d_model; g.K0 = d.d_model; g.x_scale = xs;
-            g.a1 = h_l; g.lda1 = d.d_model; g.aidx1 = d_slots; g.K1 = d.d_model;
-            lin(g, o.wg); g.M = n; g.N = 4 * d.hidden; g.K = 2 * d.d_model; g.kz = 1; g.epi = EPI_LSTM;
-            g.out = u_; g.ldo = d.hidden; g.bias = w_ + o.bg; g.c_state = c_l; g.slot_idx = d_slots; g.hidden = d.hidden;
-            if (cfg_.precision == 0 && gates_tile_rows(n)) g.tile_ok = 2;
-            timed_begin(T_GATES); launch_gemm(g, stream_); timed_end(T_GATES);
-        }
-        {   // h' = u x Whr ; state write + residual: xb = norm(y) + h'
-            GemmArgs g; g.a0 = u_; g.lda0 = d.hidden; g.K0 = d.hidden; lin(g, o.whr);
-            g.M = n; g.N = d.d_model; g.K = d.hidden; g.kz = kz_hr_; g.tile_ok = tile_ok();
-            if (gemm_fullk(n, d.d_model, kz_hr_, false, 1, tile_ok())) {
-                g.epi = EPI_HR; g.state = h_l; g.ld_state = d.d_model; g.slot_idx = d_slots; g.resid = y_; g.ldr = d.d_model; g.r_scale = xs; g.out = xb_; g.ldo = d.d_model;
-                timed_begin(T_GEMM_OTHER); launch_gemm(g, stream_); timed_end(T_GEMM_OTHER);
-            } else {
-                g.epi = EPI_PARTIAL; g.out = ws_; g.m_stride = ws_mstride_;
-                timed_begin(T_GEMM_OTHER); launch_gemm(g, stream_); timed_end(T_GEMM_OTHER);
-                RowArgs r; r.mode = ROW_HR; r.ws = ws_; r.parts = gemm_partials(n, d.d_model, kz_hr_, 1, tile_ok()); r.m_stride = ws_mstride_; r.N = d.d_model; r.M = n;
-                r.resid = y_; r.ldr = d.d_model; r.r_scale = xs; r.out = xb_; r.ldo = d.d_model; r.slot_idx = d_slots; r.state = h_l; r.ld_state = d.d_model;
-                timed_begin(T_ROW); launch_row(r, stream_); timed_end(T_ROW);
-            }
-        }
-        {   // FFN up + DoubleSwish
-            GemmArgs g; g.a0 = xb_; g.lda0 = d.d_model; g.K0 = d.d_model; lin(g, o.wff1);
-            g.M = n; g.N = d.ffn; g.K = d.d_model; g.kz = 1; g.epi = EPI_BIAS_DSWISH; g.out = ff_; g.ldo = d.ffn; g.bias = w_ + o.bff1;
-            timed_begin(T_GEMM_OTHER); launch_gemm(g, stream_); timed_end(T_GEMM_OTHER);
-        }
-        // FFN down + bias + residual -> y (the last reader of the previous y was the projection above)
-        resid_ssq(ff_, d.ffn, o.wff2, kz_ff2_, w_ + o.bff2, xb_);
-        eps_in = L_.norm_eps[(size_t)l];
+    if (f16_tile_) launch_cvt_f16(y_ + r0 * d.d_model, y16_ + r0 * d.d_model, (size_t)rows * d.d_model, st);
+}
+
+// One chunk for n sessions on rows 0 .. n - 1 (slots step_d_[0 .. n - 1]).  Launch count per chunk at batch sizes where the
+// full-K schedule applies: 2 (conv) + 1 (embed) + 4 per layer + 1.
+void Engine::run_encoder_rows(int n, const float *x_direct)
+{
+    const NetDims &d = L_.dims;
+    encoder_front(0, n, step_d_, x_direct, stream_, ws_);
+    for (int l = 0; l < d.n_layers; ++l) {
+        timed_begin(T_GATES); launch_gemm(args_gates(l, 0, n, GATES_ALL), stream_); timed_end(T_GATES);
+        launch_rowepi(args_whr(l, 0, n), ws_, stream_);
+        timed_begin(T_GEMM_OTHER); launch_gemm(args_ff1(l, 0, n), stream_); timed_end(T_GEMM_OTHER);
+        launch_rowepi(args_ff2(l, 0, n), ws_, stream_);
     }
-    {   // encoder_proj(norm(y)) -> eout[slot]
-        const RowScale ys = scale_of(eps_in);
-        GemmArgs g; g.a0 = y_; g.lda0 = d.d_model; g.K0 = d.d_model; lin(g, L_.w_encproj);
-        g.M = n; g.N = d.joiner; g.K = d.d_model; g.kz = kz_proj_; g.tile_ok = tile_ok();
-        if (gemm_fullk(n, d.joiner, kz_proj_, false, 1, tile_ok())) {
-            g.epi = EPI_SLOT_STORE; g.bias = w_ + L_.b_encproj; g.out = eout_; g.ldo = d.joiner; g.slot_idx = d_slots; g.x_scale = ys;
-            timed_begin(T_GEMM_OTHER); launch_gemm(g, stream_); timed_end(T_GEMM_OTHER);
-        } else {
-            g.epi = EPI_PARTIAL; g.out = ws_; g.m_stride = ws_mstride_;
-            timed_begin(T_GEMM_OTHER); launch_gemm(g, stream_); timed_end(T_GEMM_OTHER);
-            RowArgs r; r.mode = ROW_SLOT_STORE; r.ws = ws_; r.parts = gemm_partials(n, d.joiner, kz_proj_, 1, tile_ok()); r.m_stride = ws_mstride_; r.N = d.joiner; r.M = n;
-            r.bias = w_ + L_.b_encproj; r.out = eout_; r.ldo = d.joiner; r.slot_idx = d_slots; r.r_scale = ys;
-            timed_begin(T_ROW); launch_row(r, stream_); timed_end(T_ROW);
-        }
-    }
+    launch_rowepi(args_encproj(0, n, step_d_, eout_), ws_, stream_);
 }
 
 // ---------------------------------------------------------------- decoder / joiner rounds
@@ -821,23 +904,14 @@ DecEmbedParams Engine::dec_params() const
     return p;
 }
 
-// dout[slot] = de x Wp + b for rows with row_mask != 0 (all rows when null)
+// dout[slot] = de x Wp + b for rows with row_mask != 0 (all rows when null), on the search's stream and workspace
 void Engine::run_decproj(int n, const int *d_slots, const int *row_mask, const int *run_flag, int run_gen, float *out)
 {
     const NetDims &d = L_.dims;
-    if (!out) out = dout_;
     GemmArgs g; g.a0 = de_; g.lda0 = d.d_model; g.K0 = d.d_model; lin(g, L_.w_decproj);
     g.M = n; g.N = d.joiner; g.K = d.d_model; g.kz = kz_proj_; g.tile_ok = tile_ok(); g.run_flag = run_flag; g.run_gen = run_gen;
-    if (gemm_fullk(n, d.joiner, kz_proj_, false, 1, tile_ok())) {
-        g.epi = EPI_SLOT_STORE; g.bias = w_ + L_.b_decproj; g.out = out; g.ldo = d.joiner; g.slot_idx = d_slots; g.row_mask = row_mask;
-        timed_begin(T_DEC); launch_gemm(g, search_stream_); timed_end(T_DEC);
-        return;
-    }
-    g.epi = EPI_PARTIAL; g.out = ws_g_; g.m_stride = ws_mstride_;
-    timed_begin(T_DEC); launch_gemm(g, search_stream_); timed_end(T_DEC);
-    RowArgs r; r.mode = ROW_SLOT_STORE; r.ws = ws_g_; r.parts = gemm_partials(n, d.joiner, kz_proj_, 1, tile_ok()); r.m_stride = ws_mstride_; r.N = d.joiner; r.M = n;
-    r.bias = w_ + L_.b_decproj; r.out = out; r.ldo = d.joiner; r.slot_idx = d_slots; r.row_mask = row_mask; r.run_flag = run_flag; r.run_gen = run_gen;
-    timed_begin(T_DEC); launch_row(r, search_stream_); timed_end(T_DEC);
+    g.epi = EPI_SLOT_STORE; g.bias = w_ + L_.b_decproj; g.out = out ? out : dout_; g.ldo = d.joiner; g.slot_idx = d_slots; g.row_mask = row_mask;
+    launch_rowepi(g, ws_g_, search_stream_, false, T_DEC);
 }
 
 // The reference's loop "joiner -> process_logits, up to three times, early-emit 1,0,0" (src/april_session.c:449-454)
@@ -880,278 +954,58 @@ void Engine::run_greedy_rounds(int n, const GreedyIo &io)
     }
 }
 
-void Engine::run_chain(int m, bool dump_logits)
+// the index fetch of a step: T == 0: a chunk step, three arrays of m (slots, ring tails, session times); else the layer-major
+// arrays (below) of T chunks of m sessions
+AdvanceArgs Engine::advance_args(int m, int T) const
 {
-    const int MB = cfg_.max_batch;
     AdvanceArgs a;
     a.host_ring = ring_h_; a.host_step_off = step_off_h_; a.host_rec_off = rec_off_h_; a.counter = counter_d_; a.index_mask = 2 * step_cap_ - 1;
-    a.dst = step_d_; a.dst_stride = MB; a.n_arrays = 3; a.len[0] = a.len[1] = a.len[2] = m; a.rec_off = rec_off_d_;
-    a.flags = flags_d_; a.n_flags = 8;
-    launch_advance(a, stream_);
-    run_encoder_rows(m, step_d_, step_d_ + MB, nullptr);
+    a.dst = step_d_; a.dst_stride = cfg_.max_batch; a.n_arrays = T ? 4 : 3; a.len[0] = m;
+    for (int i = 1; i < a.n_arrays; ++i) a.len[i] = T ? m * T : m;
+    a.rec_off = rec_off_d_; a.flags = flags_d_; a.n_flags = 8;
+    return a;
+}
+
+void Engine::run_chain(int m, bool dump_logits)
+{
+    launch_advance(advance_args(m, 0), stream_);
+    run_encoder_rows(m, nullptr);
     run_greedy_rounds(m, dump_logits);
 }
 
 // ---------------------------------------------------------------- layer-major step
 // Index arrays on the device (stride max_batch): [0] slots (m), [1] ring tails (T x m), [2] session times (T x m),
 // [3] slot of every row (T x m).  Row r = t * m + i.  The work is cut into STAGES over a block of time steps [t0, t1):
-//   embed(block)      conv front end + embed linear                 -> y, ssq rows of the block
+//   front(block)      conv front end + embed linear (encoder_front)   -> y, ssq rows of the block
 //   layer(l, block)   input half of the gates for the block's rows at once; per time step recurrent half + cell and the
 //                     projection; feed-forward over the block's rows   -> y, ssq rows of the block
 //   proj(block)       encoder_proj                                   -> eout_lm rows of the block
 // layer(l, b) needs layer(l - 1, b) (its input rows) and layer(l, b - 1) (the recurrent state): stages of different layers
-// on different blocks are independent: their launches are z-batched into one (see run_lm_wavefront).  Work buffers are row-partitioned,
-// so concurrent stages never share a byte.
-void Engine::lm_stage_embed(int m, int t0, int t1, hipStream_t st, bool own_ws)
-{
-    const NetDims &d = L_.dims;
-    const int MB = cfg_.max_batch;
-    const size_t r0 = (size_t)t0 * m;
-    const int rows = (t1 - t0) * m;
-    const int *d_tails = step_d_ + MB, *d_rowslot = step_d_ + 3 * MB;
-    ConvEmbedArgs ca;
-    ca.ring = ring_; ca.ring_frames = ring_frames_; ca.mel = d.mel; ca.seg = d.seg;
-    ca.slot_idx = d_rowslot + r0; ca.ring_tail = d_tails + r0;
-    for (int i = 0; i < 3; ++i) { ca.w[i] = w_ + L_.conv_w[i]; ca.b[i] = w_ + L_.conv_b[i]; ca.ch[i] = d.conv_ch[i]; ca.stride[i] = d.conv_stride[i]; }
-    ca.ch1_per_group = 1;
-    for (int k = 8; k > 1; --k) if (d.conv_ch[1] % k == 0) { ca.ch1_per_group = k; break; }
-    ca.out = a3_ + r0 * d.f_out * L_.k3; ca.ldo = L_.k3; ca.M = rows;
-    if (conv_wt_) { ca.w0t = conv_wt_; ca.w1t = conv_wt_ + (size_t)9 * d.conv_ch[0]; }
-    timed_begin(T_CONV); launch_conv_embed(ca, st); timed_end(T_CONV);
-    {
-        GemmArgs g; g.a0 = a3_ + r0 * d.f_out * L_.k3; g.lda0 = L_.k3; g.K0 = L_.k3; g.wp = w_ + L_.conv_w[2];
-        g.M = rows * d.f_out; g.N = d.conv_ch[2]; g.K = L_.k3; g.kz = 1; g.epi = EPI_BIAS_DSWISH; g.out = xin_ + r0 * d.embed_in; g.ldo = d.conv_ch[2]; g.bias = w_ + L_.conv_b[2];
-        timed_begin(T_CONV); launch_gemm(g, st); timed_end(T_CONV);
-    }
-    lm_resid_ssq(xin_ + r0 * d.embed_in, d.embed_in, L_.w_embed, kz_embed_, w_ + L_.b_embed, nullptr, r0, rows, st, own_ws ? ws_fe_ : ws_);
-    if (f16_tile_) launch_cvt_f16(y_ + r0 * d.d_model, y16_ + r0 * d.d_model, (size_t)rows * d.d_model, st);      // layer 0 reads binary16 rows
-}
-
-// y[r0 .. r0 + rows) = A x W + bias (+ residual) with sums of squares; fused where the tiles own all of K
-void Engine::lm_resid_ssq(const float *a, int K, size_t w_off, int kz, const float *bias, const float *resid, size_t r0, int rows, hipStream_t st, float *ws)
-{
-    if (!ws) ws = ws_;
-    const NetDims &d = L_.dims;
-    const int G = d.d_model / SSQ_COLS;
-    GemmArgs g; g.a0 = a; g.lda0 = K; g.K0 = K; lin(g, w_off);
-    g.M = rows; g.N = d.d_model; g.K = K; g.kz = kz; g.tile_ok = tile_ok();
-    float *yo = y_ + r0 * d.d_model, *so = ssq_ + r0 * G;
-    if (gemm_fullk(rows, d.d_model, kz, false, 1, tile_ok())) {
-        g.epi = EPI_RESID_SSQ; g.bias = bias; g.resid = resid; g.ldr = d.d_model; g.out = yo; g.ldo = d.d_model; g.ssq_out = so;
-        timed_begin(T_GEMM_OTHER); launch_gemm(g, st); timed_end(T_GEMM_OTHER);
-        return;
-    }
-    g.epi = EPI_PARTIAL; g.out = ws + r0 * d.d_model; g.m_stride = ws_mstride_;
-    timed_begin(T_GEMM_OTHER); launch_gemm(g, st); timed_end(T_GEMM_OTHER);
-    RowArgs r; r.mode = ROW_RESID_SSQ; r.ws = ws + r0 * d.d_model; r.parts = gemm_partials(rows, d.d_model, kz, 1, tile_ok()); r.m_stride = ws_mstride_; r.N = d.d_model; r.M = rows;
-    r.bias = bias; r.resid = resid; r.ldr = d.d_model; r.out = yo; r.ldo = d.d_model; r.ssq_out = so;
-    timed_begin(T_ROW); launch_row(r, st); timed_end(T_ROW);
-}
-
-// The GEMMs of one layer stage as argument blocks: launched one by one (lm_stage_layer) or, for all layers of a wavefront, in
-// one launch each (run_lm_wavefront).
-GemmArgs Engine::lm_args_xpart(int l, int m, int t0, int t1) const
-{   // input half of the gates for the block's rows: P = (p0 + p1) * scale   (waves 0,1; the recurrent half sits this launch out)
-    const NetDims &d = L_.dims;
-    const int G = d.d_model / SSQ_COLS;
-    const PackedLayout::Layer &o = L_.layers[(size_t)l];
-    const size_t b0 = (size_t)t0 * m;
-    GemmArgs g; g.a0 = y_ + b0 * d.d_model; g.lda0 = d.d_model; g.K0 = d.d_model;
-    g.x_scale.ssq = ssq_ + b0 * G; g.x_scale.groups = G; g.x_scale.inv_n = 1.0f / (float)(d.d_norm ? d.d_norm : d.d_model); g.x_scale.eps = l == 0 ? L_.embed_eps : L_.norm_eps[(size_t)l - 1];
-    g.a1 = g.a0; g.lda1 = d.d_model; g.K1 = d.d_model;          // never read (wave_mask)
-    lin(g, o.wg); g.M = (t1 - t0) * m; g.N = 4 * d.hidden; g.K = 2 * d.d_model; g.kz = 1; g.epi = EPI_XPART; g.wave_mask = 0x3;
-    g.out = p_lm_ + b0 * 4 * d.hidden; g.ldo = 4 * d.hidden;
-    if (f16_tile_) {                  // binary16 operands (y16), P stays fp32
-        g.a0 = reinterpret_cast<const float *>(y16_ + b0 * d.d_model); g.a1 = g.a0;
-        lin16(g, o.wg);
-    }
-    return g;
-}
-
-GemmArgs Engine::lm_args_gates(int l, int m, int t) const
-{   // recurrent half + LSTM cell: ((P + p2) + p3) + bias
-    const NetDims &d = L_.dims;
-    const size_t S = (size_t)cfg_.max_slots;
-    const PackedLayout::Layer &o = L_.layers[(size_t)l];
-    const size_t r0 = (size_t)t * m;
-    GemmArgs g; g.a0 = y_ + r0 * d.d_model; g.lda0 = d.d_model; g.K0 = d.d_model;      // never read (wave_mask)
-    g.a1 = h_ + (size_t)l * S * d.d_model; g.lda1 = d.d_model; g.aidx1 = step_d_; g.K1 = d.d_model;
-    lin(g, o.wg); g.M = m; g.N = 4 * d.hidden; g.K = 2 * d.d_model; g.kz = 1; g.epi = EPI_LSTM; g.wave_mask = 0xC;
-    g.p_add = p_lm_ + r0 * 4 * d.hidden; g.ldp = 4 * d.hidden;
-    g.out = u_ + r0 * d.hidden; g.ldo = d.hidden; g.bias = w_ + o.bg; g.c_state = c_ + (size_t)l * S * d.hidden; g.slot_idx = step_d_; g.hidden = d.hidden;
-    if (f16_tile_) {                  // [never read | h16(slot)], u leaves as binary16 only
-        g.a0 = reinterpret_cast<const float *>(y16_ + r0 * d.d_model); g.a1 = reinterpret_cast<const float *>(h16_ + (size_t)l * S * d.d_model);
-        lin16(g, o.wg); g.out = nullptr; g.out16 = u16_ + r0 * d.hidden;
-    }
-    return g;
-}
-
-// fp32 gates GEMM on the GM_TILE schedule (same chains, same bits as the hand-scheduled K-split tiles -- tests/test_gpu_gates_tile.py):
-// measured 2..5 % per feed faster from ~2000 rows per launch (1024 sessions: RTF 0.0533 vs 0.055..0.058, 2048: 0.096..0.097 vs
-// 0.099..0.104), slower at 256 sessions (53.5 vs 46.5 us per launch) and at one session.  APRIL_GATES_TILE: 0 never, 1 always,
-// 2 (default) from GATES_TILE_MIN_ROWS rows per launch.
-constexpr long GATES_TILE_MIN_ROWS = 2048;
-bool Engine::gates_tile_rows(long rows) const
-{
-    static const int mode = env_int("APRIL_GATES_TILE", 2);
-    return mode == 1 || (mode == 2 && rows >= GATES_TILE_MIN_ROWS);
-}
-
-// (the same for the FFN-up GEMM: no row count from which it is on, 0 = never)
-constexpr long FF1_TILE_MIN_ROWS = 0;
-bool Engine::ff1_tile_rows(long rows) const { return FF1_TILE_MIN_ROWS > 0 && rows >= FF1_TILE_MIN_ROWS; }
-
-GemmArgs Engine::sw_args_gates(int l, int m, int t) const
-{   // the one-launch gates GEMM of a chunk step (run_encoder_rows) on the rows of chunk t: [norm(y) | h_prev] x Wg, fused LSTM cell
-    const NetDims &d = L_.dims;
-    const size_t S = (size_t)cfg_.max_slots;
-    const int G = d.d_model / SSQ_COLS;
-    const PackedLayout::Layer &o = L_.layers[(size_t)l];
-    const size_t r0 = (size_t)t * m;
-    GemmArgs g; g.a0 = y_ + r0 * d.d_model; g.lda0 = d.d_model; g.K0 = d.d_model;
-    g.x_scale.ssq = ssq_ + r0 * G; g.x_scale.groups = G; g.x_scale.inv_n = 1.0f / (float)(d.d_norm ? d.d_norm : d.d_model); g.x_scale.eps = l == 0 ? L_.embed_eps : L_.norm_eps[(size_t)l - 1];
-    g.a1 = h_ + (size_t)l * S * d.d_model; g.lda1 = d.d_model; g.aidx1 = step_d_; g.K1 = d.d_model;
-    lin(g, o.wg); g.M = m; g.N = 4 * d.hidden; g.K = 2 * d.d_model; g.kz = 1; g.epi = EPI_LSTM;
-    g.out = u_ + r0 * d.hidden; g.ldo = d.hidden; g.bias = w_ + o.bg; g.c_state = c_ + (size_t)l * S * d.hidden; g.slot_idx = step_d_; g.hidden = d.hidden;
-    if (gates_tile_rows(m) && cfg_.precision == 0) g.tile_ok = 2;      // (one problem per launch; sw_plan decides again for z-batched launches)
-    if (f16_tile_) {                  // binary16 operands: [y16 | h16(slot)], u leaves as binary16 only (its one reader is the projection)
-        g.a0 = reinterpret_cast<const float *>(y16_ + r0 * d.d_model); g.a1 = reinterpret_cast<const float *>(h16_ + (size_t)l * S * d.d_model);
-        lin16(g, o.wg); g.out = nullptr; g.out16 = u16_ + r0 * d.hidden;
-    }
-    return g;
-}
-
-GemmArgs Engine::lm_args_whr(int l, int m, int t) const
-{   // h' = u x Whr ; state write + residual, in one launch however few workgroups (sequential step)
-    const NetDims &d = L_.dims;
-    const size_t S = (size_t)cfg_.max_slots;
-    const int G = d.d_model / SSQ_COLS;
-    const PackedLayout::Layer &o = L_.layers[(size_t)l];
-    const size_t r0 = (size_t)t * m;
-    GemmArgs g; g.a0 = u_ + r0 * d.hidden; g.lda0 = d.hidden; g.K0 = d.hidden; lin(g, o.whr);
-    g.M = m; g.N = d.d_model; g.K = d.hidden; g.kz = kz_hr_; g.tile_ok = tile_ok(); g.force_fullk = 1;
-    g.epi = EPI_HR; g.state = h_ + (size_t)l * S * d.d_model; g.ld_state = d.d_model; g.slot_idx = step_d_; g.resid = y_ + r0 * d.d_model; g.ldr = d.d_model;
-    g.r_scale.ssq = ssq_ + r0 * G; g.r_scale.groups = G; g.r_scale.inv_n = 1.0f / (float)(d.d_norm ? d.d_norm : d.d_model); g.r_scale.eps = l == 0 ? L_.embed_eps : L_.norm_eps[(size_t)l - 1];
-    g.out = xb_ + r0 * d.d_model; g.ldo = d.d_model;
-    if (f16_tile_) {
-        g.a0 = reinterpret_cast<const float *>(u16_ + r0 * d.hidden); lin16(g, o.whr); g.kz = kzx_hr_;
-        g.state16 = h16_ + (size_t)l * S * d.d_model; g.out16 = xb16_ + r0 * d.d_model;
-    }
-    return g;
-}
-
-GemmArgs Engine::lm_args_ff1(int l, int m, int t0, int t1) const
-{   // FFN up + DoubleSwish, the block's rows
-    const NetDims &d = L_.dims;
-    const PackedLayout::Layer &o = L_.layers[(size_t)l];
-    const size_t b0 = (size_t)t0 * m;
-    GemmArgs g; g.a0 = xb_ + b0 * d.d_model; g.lda0 = d.d_model; g.K0 = d.d_model; lin(g, o.wff1);
-    g.M = (t1 - t0) * m; g.N = d.ffn; g.K = d.d_model; g.kz = 1; g.epi = EPI_BIAS_DSWISH; g.out = ff_ + b0 * d.ffn; g.ldo = d.ffn; g.bias = w_ + o.bff1;
-    if (f16_tile_) { g.a0 = reinterpret_cast<const float *>(xb16_ + b0 * d.d_model); lin16(g, o.wff1); g.out = nullptr; g.out16 = ff16_ + b0 * d.ffn; }
-    else if (cfg_.precision == 0 && ff1_tile_rows((long)(t1 - t0) * m)) g.tile_ok = 2;
-    return g;
-}
-
-GemmArgs Engine::lm_args_ff2(int l, int m, int t0, int t1) const
-{   // FFN down + bias + residual + sums of squares in one launch (the wavefront form; lm_resid_ssq picks by occupancy)
-    const NetDims &d = L_.dims;
-    const int G = d.d_model / SSQ_COLS;
-    const PackedLayout::Layer &o = L_.layers[(size_t)l];
-    const size_t b0 = (size_t)t0 * m;
-    GemmArgs g; g.a0 = ff_ + b0 * d.ffn; g.lda0 = d.ffn; g.K0 = d.ffn; lin(g, o.wff2);
-    g.M = (t1 - t0) * m; g.N = d.d_model; g.K = d.ffn; g.kz = kz_ff2_; g.tile_ok = tile_ok(); g.force_fullk = 1;
-    g.epi = EPI_RESID_SSQ; g.bias = w_ + o.bff2; g.resid = xb_ + b0 * d.d_model; g.ldr = d.d_model; g.out = y_ + b0 * d.d_model; g.ldo = d.d_model; g.ssq_out = ssq_ + b0 * G;
-    if (f16_tile_) { g.a0 = reinterpret_cast<const float *>(ff16_ + b0 * d.ffn); lin16(g, o.wff2); g.kz = kzx_ff2_; g.out16 = y16_ + b0 * d.d_model; }
-    return g;
-}
-
-// A row-epilogue GEMM given in its fused form (EPI_HR / EPI_RESID_SSQ): the partial-plane form of the same GEMM over the
-// workspace rows of its output, and the row problem that finishes it (same arithmetic as the fused epilogue)
-static GemmArgs partial_form(const GemmArgs &f, float *ws, int m_stride)
-{
-    GemmArgs g = f;
-    g.epi = EPI_PARTIAL; g.force_fullk = 0; g.out = ws; g.m_stride = m_stride;
-    g.bias = nullptr; g.resid = nullptr; g.state = nullptr; g.slot_idx = nullptr; g.ssq_out = nullptr; g.r_scale = RowScale(); g.out16 = nullptr; g.state16 = nullptr;
-    return g;
-}
-static RowArgs row_form(const GemmArgs &f, const float *ws, int m_stride, int parts)
-{
-    RowArgs r; r.ws = ws; r.parts = parts; r.m_stride = m_stride; r.N = f.N; r.M = f.M;
-    r.resid = f.resid; r.ldr = f.ldr; r.out = f.out; r.ldo = f.ldo; r.out16 = f.out16;
-    if (f.epi == EPI_HR) { r.mode = ROW_HR; r.r_scale = f.r_scale; r.slot_idx = f.slot_idx; r.state = f.state; r.ld_state = f.ld_state; r.state16 = f.state16; }
-    else { r.mode = ROW_RESID_SSQ; r.bias = f.bias; r.ssq_out = f.ssq_out; }
-    return r;
-}
-
-// one row-epilogue GEMM outside the z-batched chains: fused when the plan keeps all of K in the workgroup, else planes + row kernel
-void Engine::launch_rowepi(GemmArgs f, size_t ws_row0, hipStream_t st)
-{
-    f.force_fullk = 0;
-    if (gemm_fullk(f.M, f.N, f.kz, false, 1, f.tile_ok)) { timed_begin(T_GEMM_OTHER); launch_gemm(f, st); timed_end(T_GEMM_OTHER); return; }
-    float *ws = ws_ + ws_row0 * f.N;
-    timed_begin(T_GEMM_OTHER); launch_gemm(partial_form(f, ws, ws_mstride_), st); timed_end(T_GEMM_OTHER);
-    timed_begin(T_ROW); launch_row(row_form(f, ws, ws_mstride_, gemm_partials(f.M, f.N, f.kz, 1, f.tile_ok)), st); timed_end(T_ROW);
-}
-
+// on different blocks are independent: their launches are z-batched into one (see run_lm_wavefront).  Work buffers are row-partitioned
+// (the split-K planes too: a stage's planes lie at its first row's d_model-wide slice of the workspace), so concurrent stages never
+// share a byte.
 void Engine::lm_stage_layer(int l, int m, int t0, int t1, hipStream_t st)
 {
     const NetDims &d = L_.dims;
-    const size_t S = (size_t)cfg_.max_slots;
-    const PackedLayout::Layer &o = L_.layers[(size_t)l];
     const size_t b0 = (size_t)t0 * m;
     const int brows = (t1 - t0) * m;
-    timed_begin(T_GATES); launch_gemm(lm_args_xpart(l, m, t0, t1), st); timed_end(T_GATES);
-    if (f16_tile_) {                  // fp16 tile engines: the same stage on the tile kernels (row epilogues fused or planes + row kernel, the planner's choice)
-        for (int t = t0; t < t1; ++t) {
-            timed_begin(T_GATES); launch_gemm(lm_args_gates(l, m, t), st); timed_end(T_GATES);
-            launch_rowepi(lm_args_whr(l, m, t), (size_t)t * m, st);
-        }
-        timed_begin(T_GEMM_OTHER); launch_gemm(lm_args_ff1(l, m, t0, t1), st); timed_end(T_GEMM_OTHER);
-        launch_rowepi(lm_args_ff2(l, m, t0, t1), b0, st);
-        return;
-    }
+    timed_begin(T_GATES); launch_gemm(args_gates(l, b0, brows, GATES_X), st); timed_end(T_GATES);
     for (int t = t0; t < t1; ++t) {
         const size_t r0 = (size_t)t * m;
-        timed_begin(T_GATES); launch_gemm(lm_args_gates(l, m, t), st); timed_end(T_GATES);
-        if (gemm_fullk(m, d.d_model, kz_hr_, true, 1, tile_ok())) {
-            timed_begin(T_GEMM_OTHER); launch_gemm(lm_args_whr(l, m, t), st); timed_end(T_GEMM_OTHER);
-        } else {
-            const GemmArgs f = lm_args_whr(l, m, t);
-            GemmArgs g; g.a0 = f.a0; g.lda0 = f.lda0; g.K0 = f.K0; lin(g, o.whr); g.M = m; g.N = d.d_model; g.K = d.hidden; g.kz = kz_hr_; g.tile_ok = tile_ok();
-            g.epi = EPI_PARTIAL; g.out = ws_ + r0 * d.d_model; g.m_stride = ws_mstride_;
-            timed_begin(T_GEMM_OTHER); launch_gemm(g, st); timed_end(T_GEMM_OTHER);
-            RowArgs r; r.mode = ROW_HR; r.ws = ws_ + r0 * d.d_model; r.parts = gemm_partials(m, d.d_model, kz_hr_, 1, tile_ok()); r.m_stride = ws_mstride_; r.N = d.d_model; r.M = m;
-            r.resid = f.resid; r.ldr = d.d_model; r.r_scale = f.r_scale; r.out = f.out; r.ldo = d.d_model;
-            r.slot_idx = step_d_; r.state = h_ + (size_t)l * S * d.d_model; r.ld_state = d.d_model;
-            timed_begin(T_ROW); launch_row(r, st); timed_end(T_ROW);
-        }
+        timed_begin(T_GATES); launch_gemm(args_gates(l, r0, m, GATES_H), st); timed_end(T_GATES);
+        // (sequential step: on the K-split kernels one launch however few workgroups; the fp16 tile kernels by the planner's choice)
+        launch_rowepi(args_whr(l, r0, m), ws_ + r0 * d.d_model, st, !f16_tile_);
     }
-    timed_begin(T_GEMM_OTHER); launch_gemm(lm_args_ff1(l, m, t0, t1), st); timed_end(T_GEMM_OTHER);
-    lm_resid_ssq(ff_ + b0 * d.ffn, d.ffn, o.wff2, kz_ff2_, w_ + o.bff2, xb_ + b0 * d.d_model, b0, brows, st);
+    timed_begin(T_GEMM_OTHER); launch_gemm(args_ff1(l, b0, brows), st); timed_end(T_GEMM_OTHER);
+    launch_rowepi(args_ff2(l, b0, brows), ws_ + b0 * d.d_model, st);
 }
 
 void Engine::lm_stage_proj(int m, int t0, int t1, hipStream_t st, float *ws)
 {
-    if (!ws) ws = ws_;
     const NetDims &d = L_.dims;
-    const int G = d.d_model / SSQ_COLS;
     const size_t b0 = (size_t)t0 * m;
-    const int brows = (t1 - t0) * m;
-    RowScale ys; ys.ssq = ssq_ + b0 * G; ys.groups = G; ys.inv_n = 1.0f / (float)(d.d_norm ? d.d_norm : d.d_model); ys.eps = L_.norm_eps[(size_t)d.n_layers - 1];
-    GemmArgs g; g.a0 = y_ + b0 * d.d_model; g.lda0 = d.d_model; g.K0 = d.d_model; lin(g, L_.w_encproj);
-    g.M = brows; g.N = d.joiner; g.K = d.d_model; g.kz = kz_proj_; g.tile_ok = tile_ok();
-    float *eo = eout_lm_ + b0 * d.joiner;
-    if (gemm_fullk(brows, d.joiner, kz_proj_, true, 1, tile_ok())) {
-        g.force_fullk = 1;
-        g.epi = EPI_SLOT_STORE; g.bias = w_ + L_.b_encproj; g.out = eo; g.ldo = d.joiner; g.x_scale = ys;
-        timed_begin(T_GEMM_OTHER); launch_gemm(g, st); timed_end(T_GEMM_OTHER);
-    } else {
-        g.epi = EPI_PARTIAL; g.out = ws + b0 * d.d_model; g.m_stride = ws_mstride_;     // (joiner width == a d_model-wide slice or less: see the constructor's workspace size)
-        timed_begin(T_GEMM_OTHER); launch_gemm(g, st); timed_end(T_GEMM_OTHER);
-        RowArgs r; r.mode = ROW_SLOT_STORE; r.ws = ws + b0 * d.d_model; r.parts = gemm_partials(brows, d.joiner, kz_proj_, 1, tile_ok()); r.m_stride = ws_mstride_; r.N = d.joiner; r.M = brows;
-        r.bias = w_ + L_.b_encproj; r.out = eo; r.ldo = d.joiner; r.r_scale = ys;
-        timed_begin(T_ROW); launch_row(r, st); timed_end(T_ROW);
-    }
+    // (joiner width == a d_model-wide slice or less: see the constructor's workspace size)
+    launch_rowepi(args_encproj(b0, (t1 - t0) * m, nullptr, eout_lm_ + b0 * d.joiner), ws + b0 * d.d_model, st, true);
 }
 
 // Time steps per block of the long-feed wavefront (run_lm_wavefront).  A macro step costs its block's recurrent launches (2 per
@@ -1179,14 +1033,10 @@ void Engine::run_lm_chain(int m, int T, bool dump_logits)
     const NetDims &d = L_.dims;
     const int MB = cfg_.max_batch;
     const int L = d.n_layers;
-    AdvanceArgs a;
-    a.host_ring = ring_h_; a.host_step_off = step_off_h_; a.host_rec_off = rec_off_h_; a.counter = counter_d_; a.index_mask = 2 * step_cap_ - 1;
-    a.dst = step_d_; a.dst_stride = MB; a.n_arrays = 4; a.len[0] = m; a.len[1] = a.len[2] = a.len[3] = m * T; a.rec_off = rec_off_d_;
-    a.flags = flags_d_; a.n_flags = 8;
-    launch_advance(a, stream_);
-    lm_stage_embed(m, 0, T, stream_);
+    launch_advance(advance_args(m, T), stream_);
+    encoder_front(0, m * T, step_d_ + 3 * MB, nullptr, stream_, ws_);
     for (int l = 0; l < L; ++l) lm_stage_layer(l, m, 0, T, stream_);
-    lm_stage_proj(m, 0, T, stream_);
+    lm_stage_proj(m, 0, T, stream_, ws_);
     // the search stays sequential in time (the decoder input of chunk t + 1 depends on the tokens of chunk t)
     for (int t = 0; t < T; ++t) run_greedy_rounds(m, dump_logits, t, eout_lm_ + (size_t)t * m * d.joiner);
 }
@@ -1207,11 +1057,7 @@ void Engine::run_lm_wavefront(int m, int T, bool dump_logits)
     const int L = d.n_layers;
     const int blk = lm_block_steps(T);
     const int NB = (T + blk - 1) / blk;
-    AdvanceArgs a;
-    a.host_ring = ring_h_; a.host_step_off = step_off_h_; a.host_rec_off = rec_off_h_; a.counter = counter_d_; a.index_mask = 2 * step_cap_ - 1;
-    a.dst = step_d_; a.dst_stride = MB; a.n_arrays = 4; a.len[0] = m; a.len[1] = a.len[2] = a.len[3] = m * T; a.rec_off = rec_off_d_;
-    a.flags = flags_d_; a.n_flags = 8;
-    launch_advance(a, stream_);
+    launch_advance(advance_args(m, T), stream_);
     hipStream_t cs = lm_stream_;
     HIP_CHECK(hipEventRecord(lm_events_[0], stream_));                 // the index block is on the device
     HIP_CHECK(hipStreamWaitEvent(cs, lm_events_[0], 0));
@@ -1263,15 +1109,15 @@ void Engine::run_lm_wavefront(int m, int T, bool dump_logits)
                 flush();
             }
         };
-        by_len([&](const Act &x) { return lm_args_xpart(x.l, m, x.t0, x.t1); });
+        by_len([&](const Act &x) { return args_gates(x.l, (size_t)x.t0 * m, (x.t1 - x.t0) * m, GATES_X); });
         for (int i = 0; i < blk; ++i) {
-            for (const Act &x : act) if (x.t0 + i < x.t1) items.push_back(lm_args_gates(x.l, m, x.t0 + i));
+            for (const Act &x : act) if (x.t0 + i < x.t1) items.push_back(args_gates(x.l, (size_t)(x.t0 + i) * m, m, GATES_H));
             flush();
-            for (const Act &x : act) if (x.t0 + i < x.t1) items.push_back(lm_args_whr(x.l, m, x.t0 + i));
+            for (const Act &x : act) if (x.t0 + i < x.t1) items.push_back(args_whr(x.l, (size_t)(x.t0 + i) * m, m));
             flush();
         }
-        by_len([&](const Act &x) { return lm_args_ff1(x.l, m, x.t0, x.t1); });
-        by_len([&](const Act &x) { return lm_args_ff2(x.l, m, x.t0, x.t1); });
+        by_len([&](const Act &x) { return args_ff1(x.l, (size_t)x.t0 * m, (x.t1 - x.t0) * m); });
+        by_len([&](const Act &x) { return args_ff2(x.l, (size_t)x.t0 * m, (x.t1 - x.t0) * m); });
         plan_end[(size_t)W] = plan.size();
     }
     lap(0);
@@ -1279,14 +1125,14 @@ void Engine::run_lm_wavefront(int m, int T, bool dump_logits)
         HIP_CHECK(hipMemcpyAsync(zargs_d_ + first, zargs_h_ + first, (zargs_pos_ - first) * sizeof(GemmArgs), hipMemcpyHostToDevice, cs));
     lap(1);
     for (int W = 0; W <= NB + L; ++W) {
-        if (W < NB) lm_stage_embed(m, W * blk, std::min(T, (W + 1) * blk), cs);
+        if (W < NB) encoder_front((size_t)W * blk * m, (std::min(T, (W + 1) * blk) - W * blk) * m, step_d_ + 3 * MB, nullptr, cs, ws_);
         lap(2);
         for (size_t k = W ? plan_end[(size_t)W - 1] : 0; k < plan_end[(size_t)W]; ++k) launch_gemm_z(zargs_h_ + plan[k].off, plan[k].n, zargs_d_ + plan[k].off, cs);
         lap(3);
         const int bp = W - L - 1;
         if (bp >= 0) {
             const int t0 = bp * blk, t1 = std::min(T, t0 + blk), len = t1 - t0;
-            lm_stage_proj(m, t0, t1, cs);
+            lm_stage_proj(m, t0, t1, cs, ws_);
             hipEvent_t e = lm_events_[1 + (size_t)(bp % (int)(lm_events_.size() - 1))];
             HIP_CHECK(hipEventRecord(e, cs));
             HIP_CHECK(hipStreamWaitEvent(stream_, e, 0));
@@ -1310,15 +1156,7 @@ void Engine::run_lm_wavefront(int m, int T, bool dump_logits)
             auto it = lm_search_graphs_.find(key);
             if (it == lm_search_graphs_.end()) {
                 if (lm_search_graphs_.size() >= 64) { HIP_CHECK(hipStreamSynchronize(stream_)); /* execs launched earlier in this flight may still run */ for (auto &g : lm_search_graphs_) (void)hipGraphExecDestroy(g.second); lm_search_graphs_.clear(); }
-                hipGraph_t graph = nullptr;
-                hipGraphExec_t exec = nullptr;
-                HipLegacyLock capture_guard_1;      // (no legacy-stream call of any thread during the capture: see engine.h)
-                HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeRelaxed));
-                search();
-                HIP_CHECK(hipStreamEndCapture(stream_, &graph));
-                HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                HIP_CHECK(hipGraphDestroy(graph));
-                it = lm_search_graphs_.emplace(key, exec).first;
+                it = lm_search_graphs_.emplace(key, capture_graph(stream_, search)).first;
             }
             HIP_CHECK(hipGraphLaunch(it->second, stream_));
             lap(5);
@@ -1378,11 +1216,11 @@ Engine::SwPlan &Engine::sw_plan(int m, int T)
             for (int l = 0; l < L; ++l) {
                 const int t = W - 1 - l;
                 if (t < 0 || t >= T) continue;
-                GemmArgs g = kind == 0 ? sw_args_gates(l, m, t) : kind == 1 ? lm_args_whr(l, m, t) : kind == 2 ? lm_args_ff1(l, m, t, t + 1) : lm_args_ff2(l, m, t, t + 1);
+                const size_t r0 = (size_t)t * m;
+                GemmArgs g = kind == 0 ? args_gates(l, r0, m, GATES_ALL) : kind == 1 ? args_whr(l, r0, m) : kind == 2 ? args_ff1(l, r0, m) : args_ff2(l, r0, m);
                 if (kind == 0 && cfg_.precision == 0) g.tile_ok = gates_tile_rows((long)m * n_act) ? 2 : 0;
-                if (kind == 2 && cfg_.precision == 0) g.tile_ok = ff1_tile_rows((long)m * n_act) ? 2 : 0;
                 if (split) {
-                    float *ws = ws_ + (size_t)t * m * d.d_model;
+                    float *ws = ws_ + r0 * d.d_model;
                     rows.push_back(row_form(g, ws, ws_mstride_, gemm_partials(m, d.d_model, kz, n_act, tk)));
                     g = partial_form(g, ws, ws_mstride_);
                 } else if (tk == 2) g.force_fullk = 0;
@@ -1435,14 +1273,10 @@ void Engine::run_sw_chain(int m, int T, bool dump_logits, const SwPlan &p, int p
     const NetDims &d = L_.dims;
     const int MB = cfg_.max_batch;
     if (part < 0 || part == 0) {
-        AdvanceArgs a;
-        a.host_ring = ring_h_; a.host_step_off = step_off_h_; a.host_rec_off = rec_off_h_; a.counter = counter_d_; a.index_mask = 2 * step_cap_ - 1;
-        a.dst = step_d_; a.dst_stride = MB; a.n_arrays = 4; a.len[0] = m; a.len[1] = a.len[2] = a.len[3] = m * T; a.rec_off = rec_off_d_;
-        a.flags = flags_d_; a.n_flags = 8;
-        launch_advance(a, st);
+        launch_advance(advance_args(m, T), st);
         // Front end and encoder_proj do not take part in the wavefront: one launch chain each over all T x m rows (as in the
         // layer-major step), before the first and after the last macro step; the searches follow in time order.
-        lm_stage_embed(m, 0, T, st, part == 0);
+        encoder_front(0, m * T, step_d_ + 3 * MB, nullptr, st, part == 0 ? ws_fe_ : ws_);
     }
     if (part < 0 || part == 1) {
         static const int cls_of[4] = {T_GATES, T_GEMM_OTHER, T_GEMM_OTHER, T_GEMM_OTHER};
@@ -1451,7 +1285,7 @@ void Engine::run_sw_chain(int m, int T, bool dump_logits, const SwPlan &p, int p
             timed_begin(cls_of[b.kind]); launch_gemm_z(p.host.data() + b.off, b.n, p.dev + b.off, st); timed_end(cls_of[b.kind]);
             if (b.rn > 0) { timed_begin(T_ROW); launch_row_z(p.rhost.data() + b.roff, b.rn, p.rdev + b.roff, st); timed_end(T_ROW); }
         }
-        if (part < 0) lm_stage_proj(m, 0, T, st);
+        if (part < 0) lm_stage_proj(m, 0, T, st, ws_);
     }
     if (part < 0 || part == 2) {
         // (split feed: encoder_proj feeds only the search, so it leaves the layer stream with it; its split-K planes, if any, go to
@@ -1517,24 +1351,10 @@ int Engine::lm_step(int m, int T, const int *slots, const int *ring_tails, const
                 if (split) {
                     if (pl.g3[0]) continue;
                     hipStream_t on[3] = {fe, stream_, s_stream_};
-                    for (int part = 0; part < 3; ++part) {
-                        hipGraph_t graph = nullptr;
-                        HipLegacyLock capture_guard_2;      // (no legacy-stream call of any thread during the capture: see engine.h)
-                        HIP_CHECK(hipStreamBeginCapture(on[part], hipStreamCaptureModeRelaxed));
-                        run_sw_chain(m, T, false, pl, part, on[part]);
-                        HIP_CHECK(hipStreamEndCapture(on[part], &graph));
-                        HIP_CHECK(hipGraphInstantiate(&pl.g3[part], graph, nullptr, nullptr, 0));
-                        HIP_CHECK(hipGraphDestroy(graph));
-                    }
+                    for (int part = 0; part < 3; ++part) pl.g3[part] = capture_graph(on[part], [&]() { run_sw_chain(m, T, false, pl, part, on[part]); });
                 } else {
                     if (pl.graph) continue;
-                    hipGraph_t graph = nullptr;
-                    HipLegacyLock capture_guard_3;      // (no legacy-stream call of any thread during the capture: see engine.h)
-                    HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeRelaxed));
-                    run_sw_chain(m, T, false, pl, -1, stream_);
-                    HIP_CHECK(hipStreamEndCapture(stream_, &graph));
-                    HIP_CHECK(hipGraphInstantiate(&pl.graph, graph, nullptr, nullptr, 0));
-                    HIP_CHECK(hipGraphDestroy(graph));
+                    pl.graph = capture_graph(stream_, [&]() { run_sw_chain(m, T, false, pl, -1, stream_); });
                 }
             }
             pp = &sw_plans_.find(std::make_pair(gclk_ ? -m : m, T * 2 + par))->second;      // (a plan-cache eviction in between would have moved it)
@@ -1584,15 +1404,7 @@ int Engine::lm_step(int m, int T, const int *slots, const int *ring_tails, const
             auto it = lm_graphs_.find(key);
             if (it == lm_graphs_.end()) {
                 if (lm_graphs_.size() >= 32) { sync(); for (auto &g : lm_graphs_) (void)hipGraphExecDestroy(g.second); lm_graphs_.clear(); }
-                hipGraph_t graph = nullptr;
-                hipGraphExec_t exec = nullptr;
-                HipLegacyLock capture_guard_4;      // (no legacy-stream call of any thread during the capture: see engine.h)
-                HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeRelaxed));
-                run_lm_chain(m, T, false);
-                HIP_CHECK(hipStreamEndCapture(stream_, &graph));
-                HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                HIP_CHECK(hipGraphDestroy(graph));
-                it = lm_graphs_.emplace(key, exec).first;
+                it = lm_graphs_.emplace(key, capture_graph(stream_, [&]() { run_lm_chain(m, T, false); })).first;
             }
             HIP_CHECK(hipGraphLaunch(it->second, stream_));
             return k;
@@ -1718,15 +1530,7 @@ int Engine::step(int m, const int *slots, const int *ring_tails, const int *now_
                 const int q = k2 == 0 ? 1 - par : par;
                 if (step_graphs_.count(m * 2 + q)) continue;
                 select_parity(q);
-                hipGraph_t graph = nullptr;
-                hipGraphExec_t exec = nullptr;
-                HipLegacyLock capture_guard_5;      // (no legacy-stream call of any thread during the capture: see engine.h)
-                HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeRelaxed));
-                run_chain(m, false);
-                HIP_CHECK(hipStreamEndCapture(stream_, &graph));
-                HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                HIP_CHECK(hipGraphDestroy(graph));
-                step_graphs_.emplace(m * 2 + q, exec);
+                step_graphs_.emplace(m * 2 + q, capture_graph(stream_, [&]() { run_chain(m, false); }));
             }
             select_parity(par);
             it = step_graphs_.find(gkey);
@@ -1845,7 +1649,7 @@ void Engine::debug_encoder(int n, const float *x, const float *h, const float *c
     HIP_CHECK(hipMemcpy(step_d_, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     if (f16_tile_)                              // the binary16 copy of the uploaded h rows (slots 0..n-1 of every layer)
         for (int l = 0; l < d.n_layers; ++l) launch_cvt_f16(h_ + (size_t)l * S * d.d_model, h16_ + (size_t)l * S * d.d_model, (size_t)n * d.d_model, stream_);
-    run_encoder_rows(n, step_d_, step_d_, xd);
+    run_encoder_rows(n, xd);
     sync();
     for (int i = 0; i < n; ++i) {
         HIP_CHECK(hipMemcpy(eout + (size_t)i * d.joiner, eout_ + (size_t)i * d.joiner, (size_t)d.joiner * 4, hipMemcpyDeviceToHost));

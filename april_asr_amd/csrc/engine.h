@@ -195,17 +195,19 @@ public:
 private:
     void upload_tables(const FbankHostTables &ft);
     void zero_slots(int n);
-    void run_encoder_rows(int n, const int *d_slots, const int *d_tails, const float *x_direct);
-    void lm_stage_embed(int m, int t0, int t1, hipStream_t st, bool own_ws = false);
+    void run_encoder_rows(int n, const float *x_direct);
+    void encoder_front(size_t r0, int rows, const int *row_slots, const float *x_direct, hipStream_t st, float *ws);
     void lm_stage_layer(int l, int m, int t0, int t1, hipStream_t st);
-    void lm_stage_proj(int m, int t0, int t1, hipStream_t st, float *ws = nullptr);
-    void lm_resid_ssq(const float *a, int K, size_t w_off, int kz, const float *bias, const float *resid, size_t r0, int rows, hipStream_t st, float *ws = nullptr);
-    GemmArgs lm_args_xpart(int l, int m, int t0, int t1) const;
-    GemmArgs lm_args_gates(int l, int m, int t) const;
-    GemmArgs sw_args_gates(int l, int m, int t) const;
-    GemmArgs lm_args_whr(int l, int m, int t) const;
-    GemmArgs lm_args_ff1(int l, int m, int t0, int t1) const;
-    GemmArgs lm_args_ff2(int l, int m, int t0, int t1) const;
+    void lm_stage_proj(int m, int t0, int t1, hipStream_t st, float *ws);
+    // the encoder's GEMMs as argument blocks over rows [r0, r0 + rows) of the work buffers (engine.cc "encoder")
+    enum { GATES_ALL = 0xF, GATES_X = 0x3, GATES_H = 0xC };      // forms of the gates GEMM = their wave masks
+    RowScale in_scale(int l, size_t r0) const;
+    GemmArgs args_gates(int l, size_t r0, int rows, int waves) const;
+    GemmArgs args_whr(int l, size_t r0, int rows) const;
+    GemmArgs args_ff1(int l, size_t r0, int rows) const;
+    GemmArgs args_ff2(int l, size_t r0, int rows) const;
+    GemmArgs args_encproj(size_t r0, int rows, const int *slot_idx, float *out) const;
+    AdvanceArgs advance_args(int m, int T) const;
     // where one chunk's search reads its inputs and writes its records
     struct GreedyIo {
         int gen = 1;                          // generation of the chunk for the round flags / active marks (unique until they are cleared)
@@ -236,9 +238,8 @@ private:
     void join(hipStream_t waiter, hipStream_t src);
     void general_prologue();
     int next_step_index() { ++flight_steps_; return (int)(step_seq_++ & (uint64_t)(2 * step_cap_ - 1)); }
-    void launch_rowepi(GemmArgs fused_form, size_t ws_row0, hipStream_t st);
+    void launch_rowepi(GemmArgs fused_form, float *ws, hipStream_t st, bool force = false, int cls = T_GEMM_OTHER);
     bool gates_tile_rows(long rows) const;
-    bool ff1_tile_rows(long rows) const;
     void run_decproj(int n, const int *d_slots, const int *row_mask, const int *run_flag, int run_gen, float *out = nullptr);
     void build_dec_table();
     void run_chain(int m, bool dump_logits);     // advance + encoder + greedy rounds with arguments that depend on m only
