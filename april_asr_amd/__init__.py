@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _ffi
 
-__all__ = ["Result", "Token", "Model", "Session", "SessionGroup", "resampler_taps"]
+__all__ = ["Result", "Token", "Model", "Session", "SessionGroup", "Bias", "resampler_taps"]
 
 
 class Result(IntEnum):
@@ -251,6 +251,26 @@ class Model:
             raise ValueError("aprilx_run_confidence refused n=%d k=%d" % (a.shape[0], k))
         return out
 
+    def bias(self, phrases, boost: float = 2.0):
+        """A phrase-boosting set for this model (aprilx_bias_create; no GPU needed): `phrases` is a list of strings / bytes, all with
+        `boost` logit units, or of (phrase, boost) pairs.  Hand it to Session(..., bias=...) or Session.set_bias()."""
+        return Bias(self, phrases, boost)
+
+    def run_decide_biased(self, logits, early_emit, now_ms, rnd, state, bias, bias_state, op: int = 0):
+        """One decision round on GIVEN logits rows with `bias` on the rows whose bias_state is >= 0 (aprilx_run_decide_biased; tests):
+        returns (records [n] as (idx int32, max float32, blank float32, flags uint32), search states [n][4], bias states [n])."""
+        st = np.ascontiguousarray(state, np.int32).reshape(-1, 4).copy()
+        n = st.shape[0]
+        lg = np.ascontiguousarray(logits, np.float32).reshape(n, self.dims.vocab)
+        now = np.ascontiguousarray(now_ms, np.int32).reshape(n)
+        bs = np.ascontiguousarray(bias_state, np.int32).reshape(n).copy()
+        rec = np.zeros(n, np.dtype([("idx", np.int32), ("max", np.float32), ("blank", np.float32), ("flags", np.uint32)]))
+        rc = self._L.aprilx_run_decide_biased(self._handle, n, int(op), lg.ctypes.data, float(early_emit), now.ctypes.data, int(rnd),
+                                              st.ctypes.data, rec.ctypes.data, bias._handle, bs.ctypes.data)
+        if rc != 0:
+            raise ValueError("aprilx_run_decide_biased refused the call")
+        return rec, st, bs
+
     def stats(self, device_index: int = 0):
         s = _ffi.AprilxStats()
         self._L.aprilx_model_stats(self._handle, device_index, C.byref(s))
@@ -272,6 +292,53 @@ class Model:
         self._L.aprilx_model_profile(self._handle, int(enable))
 
 
+class Bias:
+    """A set of boosted phrases.  Sessions that use it keep it alive after close()."""
+
+    def __init__(self, model: Model, phrases, boost: float = 2.0):
+        self._L = model._L
+        items = [(p, boost) if isinstance(p, (str, bytes)) else (p[0], p[1]) for p in phrases]
+        raw = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p, _ in items]
+        arr = (C.c_char_p * max(len(raw), 1))(*raw)
+        boosts = (C.c_float * max(len(raw), 1))(*[float(b) for _, b in items])
+        err = C.create_string_buffer(256)
+        self._handle = self._L.aprilx_bias_create(model._handle, len(raw), arr, boosts, err, 256)
+        self.message = err.value.decode("utf-8", "replace")          # a note about left-out phrases when the call succeeded
+        if not self._handle:
+            raise ValueError("bias set refused: " + self.message)
+        st, ed = C.c_int32(0), C.c_int64(0)
+        self.dropped = int(self._L.aprilx_bias_info(self._handle, C.byref(st), C.byref(ed)))
+        self.states, self.n_edges = int(st.value), int(ed.value)
+
+    def edges(self, state: int):
+        """(token ids, next states, bonuses) of the effective edges of one trie state, token ids ascending"""
+        n = int(self._L.aprilx_bias_edges(self._handle, int(state), None, None, None, 0))
+        if n < 0:
+            raise ValueError("no state %d" % state)
+        tok = np.zeros(n, np.int32); nxt = np.zeros(n, np.int32); bonus = np.zeros(n, np.float32)
+        if n:
+            assert self._L.aprilx_bias_edges(self._handle, int(state), tok.ctypes.data, nxt.ctypes.data, bonus.ctypes.data, n) == n
+        return tok, nxt, bonus
+
+    def csr(self):
+        """(state_off [S + 1], edge_tok, edge_next, edge_bonus) as the device receives them"""
+        parts = [self.edges(s) for s in range(self.states)]
+        off = np.zeros(self.states + 1, np.int32)
+        off[1:] = np.cumsum([p[0].size for p in parts])
+        return (off,) + tuple(np.concatenate([p[i] for p in parts]) if parts else np.zeros(0) for i in range(3))
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            self._L.aprilx_bias_free(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _dispatch(userdata, result_type, count, tokens):
     sess = C.cast(userdata, C.py_object).value
     sess._on_result(result_type, count, tokens)
@@ -283,13 +350,14 @@ _HANDLER = _ffi.HANDLER(_dispatch)
 class Session:
     def __init__(self, model: Model, callback: Callable[[Result, List[Token]], None], asynchronous: bool = False,
                  no_rt: bool = False, speaker_name: str = "", raw_events: bool = False, counters=None, input_sample_rate=None,
-                 alternatives=None):
+                 alternatives=None, bias=None):
         """`counters`: a uint64 ndarray of 6 entries; when given, results are only counted by a C handler inside the
         library (calls, partial, final, cant_keep_up, silence, tokens) and `callback` is never invoked.
         `input_sample_rate`: the rate of the PCM this session will receive (converted to the model's rate on the GPU); None: the
         model's rate.
         `alternatives`: K in 1..8: every delivered Token carries its log-softmax, the blank's and the K best candidates
-        (set_confidence); None / 0: off."""
+        (set_confidence); None / 0: off.
+        `bias`: a Bias (Model.bias): the search boosts the tokens that continue one of its phrases (set_bias); None: off."""
         self._L = model._L
         self.info_log = None      # tests: a list that receives (type, [the token's AprilxTokenInfo as bytes, or None]) per result
         self.model = model
@@ -316,6 +384,8 @@ class Session:
             self.set_input_rate(input_sample_rate)
         if alternatives:
             self.set_confidence(alternatives)
+        if bias is not None:
+            self.set_bias(bias)
 
     def _on_result(self, result_type, count, tokens):
         if self.info_log is not None:
@@ -355,6 +425,18 @@ class Session:
         no recognition result."""
         if self._L.aprilx_session_set_confidence(self._handle, int(n_alternatives)) != 0:
             raise ValueError("confidence with %d alternatives refused (0..8, and no audio fed since the last flush)" % n_alternatives)
+
+    def set_bias(self, bias) -> None:
+        """The search of this session uses the phrase-boosting set `bias` (Model.bias) from now on, starting at the root; None switches
+        it off (aprilx_session_set_bias).  Allowed right after creation and after a completed flush."""
+        if self._L.aprilx_session_set_bias(self._handle, bias._handle if bias is not None else None) != 0:
+            raise ValueError("bias set refused (built for another token list, 64 sets in use on the engine already, or audio fed since the last flush)")
+
+    def bias_state(self):
+        """(host, device) trie state of the session's phrase boosting -- derived independently, must agree (tests)"""
+        h, d = C.c_int32(0), C.c_int32(0)
+        self._L.aprilx_session_bias_state(self._handle, C.byref(h), C.byref(d))
+        return int(h.value), int(d.value)
 
     @property
     def alternatives(self) -> int:

@@ -71,6 +71,8 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_greedy_create", "aprilx_greedy_step", "aprilx_greedy_finish", "aprilx_greedy_free", "aprilx_probe_file", "aprilx_model_load_host", "aprilx_model_fbank_tables", "aprilx_counting_handler",
     "aprilx_session_set_input_rate", "aprilx_session_input_rate", "aprilx_resampler_taps", "aprilx_resample",
     "aprilx_session_set_confidence", "aprilx_session_confidence", "aprilx_run_confidence",
+    "aprilx_bias_create", "aprilx_bias_free", "aprilx_bias_info", "aprilx_bias_edges", "aprilx_session_set_bias", "aprilx_session_bias_state",
+    "aprilx_run_decide_biased", "aprilx_greedy_set_bias", "aprilx_greedy_bias_state",
 ]
 
 _lib = None
@@ -143,6 +145,15 @@ def lib():
     L.aprilx_session_set_confidence.argtypes = [vp, C.c_int]; L.aprilx_session_set_confidence.restype = C.c_int
     L.aprilx_session_confidence.argtypes = [vp]; L.aprilx_session_confidence.restype = C.c_int
     L.aprilx_run_confidence.argtypes = [vp, C.c_int, vp, C.c_int, vp]; L.aprilx_run_confidence.restype = C.c_int
+    L.aprilx_bias_create.argtypes = [vp, sz, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_char_p, sz]; L.aprilx_bias_create.restype = vp
+    L.aprilx_bias_free.argtypes = [vp]; L.aprilx_bias_free.restype = None
+    L.aprilx_bias_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]; L.aprilx_bias_info.restype = C.c_int
+    L.aprilx_bias_edges.argtypes = [vp, C.c_int32, vp, vp, vp, sz]; L.aprilx_bias_edges.restype = C.c_int
+    L.aprilx_session_set_bias.argtypes = [vp, vp]; L.aprilx_session_set_bias.restype = C.c_int
+    L.aprilx_session_bias_state.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]; L.aprilx_session_bias_state.restype = C.c_int
+    L.aprilx_run_decide_biased.argtypes = [vp, C.c_int, C.c_int, vp, C.c_float, vp, C.c_int, vp, vp, vp, vp]; L.aprilx_run_decide_biased.restype = C.c_int
+    L.aprilx_greedy_set_bias.argtypes = [vp, vp]; L.aprilx_greedy_set_bias.restype = C.c_int
+    L.aprilx_greedy_bias_state.argtypes = [vp]; L.aprilx_greedy_bias_state.restype = C.c_int
     _lib = L
     return L
 

@@ -363,6 +363,9 @@ Engine::~Engine()
     if (conf_d_) (void)hipFree(conf_d_);
     if (conf_k_h_) (void)hipHostFree(conf_k_h_);
     if (conf_h_) (void)hipHostFree(conf_h_);
+    for (auto &b : bias_sets_) if (b.dev) (void)hipFree(b.dev);
+    for (void *p : {(void *)bias_set_d_, (void *)bias_state_d_, (void *)bias_desc_d_}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)bias_set_h_, (void *)bias_desc_h_}) if (p) (void)hipHostFree(p);
     if (ws_g_) (void)hipFree(ws_g_);
     if (conv_wt_) (void)hipFree(conv_wt_);
     if (dec_table_) (void)hipFree(dec_table_);
@@ -447,6 +450,7 @@ void Engine::free_slot(int slot)
     // and a [blank, blank] context -- in a batch: when 256 freed slots have gathered, when the free list runs dry, or before
     // the next flight is launched (begin_flight), stream-ordered ahead of any later use of the slot
     if (conf_ever_.load(std::memory_order_relaxed)) set_slot_confidence(slot, 0);     // the next owner starts with confidences off
+    if (bias_ever_.load(std::memory_order_relaxed)) set_slot_bias(slot, nullptr);      // ... without a bias set, at the root
     std::lock_guard<std::mutex> g(slot_mu_);
     zero_pending_.push_back(slot);
     --live_;
@@ -949,6 +953,7 @@ void Engine::run_greedy_rounds(int n, const GreedyIo &io)
         a.dec = dec_params(); a.de_out = dec_table_ ? nullptr : de_; a.ld_de = d.d_model;
         a.run_flags = flags_d_; a.rerun_flags = flags_d_ + 4;
         a.conf_k = conf_k_d_; a.conf_ring = conf_d_;          // (null until a session of this engine asks for confidences)
+        a.bias_set = bias_set_d_; a.bias_state = bias_state_d_; a.bias_desc = bias_desc_d_;      // (null until a session of this engine has a bias set)
         timed_begin(T_DEC); launch_decide(a, search_stream_); timed_end(T_DEC);
         if (!dec_table_) run_decproj(n, d_slots, dirty_d_, flags_d_ + 4 + round, gen);
     }
@@ -1439,16 +1444,7 @@ void Engine::apply_confidence_pending()
         std::lock_guard<std::mutex> cg(capture_mu_);
         HipLegacyLock legacy;
         sync();
-        for (auto &g : step_graphs_) (void)hipGraphExecDestroy(g.second);
-        step_graphs_.clear(); step_seen_.clear();
-        for (auto &g : lm_graphs_) (void)hipGraphExecDestroy(g.second);
-        lm_graphs_.clear();
-        for (auto &g : lm_search_graphs_) (void)hipGraphExecDestroy(g.second);
-        lm_search_graphs_.clear();
-        for (auto &p : sw_plans_) {
-            if (p.second.graph) { (void)hipGraphExecDestroy(p.second.graph); p.second.graph = nullptr; }
-            for (hipGraphExec_t &x : p.second.g3) if (x) { (void)hipGraphExecDestroy(x); x = nullptr; }
-        }
+        drop_graphs();
         const size_t S = (size_t)cfg_.max_slots;
         conf_k_d_ = dmalloc<uint8_t>(S); conf_k_h_ = hmalloc<uint8_t>(S);
         memset(conf_k_h_, 0, S);
@@ -1460,6 +1456,103 @@ void Engine::apply_confidence_pending()
     // the air reads the same bytes before and after); the slots that change belong to idle sessions.
     std::lock_guard<std::mutex> cg(capture_mu_);
     HIP_CHECK(hipMemcpyAsync(conf_k_d_, conf_k_h_, (size_t)cfg_.max_slots, hipMemcpyHostToDevice, stream_));
+}
+
+void Engine::drop_graphs()
+{
+    for (auto &g : step_graphs_) (void)hipGraphExecDestroy(g.second);
+    step_graphs_.clear(); step_seen_.clear();
+    for (auto &g : lm_graphs_) (void)hipGraphExecDestroy(g.second);
+    lm_graphs_.clear();
+    for (auto &g : lm_search_graphs_) (void)hipGraphExecDestroy(g.second);
+    lm_search_graphs_.clear();
+    for (auto &p : sw_plans_) {
+        if (p.second.graph) { (void)hipGraphExecDestroy(p.second.graph); p.second.graph = nullptr; }
+        for (hipGraphExec_t &x : p.second.g3) if (x) { (void)hipGraphExecDestroy(x); x = nullptr; }
+    }
+}
+
+// ---------------------------------------------------------------- phrase boosting
+// The four CSR arrays of a set in ONE device allocation (16-byte aligned parts); the copies are queued on `st`
+BiasDesc Engine::upload_bias(const BiasSet &set, void **dev, hipStream_t st)
+{
+    auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t ns = set.state_off.size() * 4, ne = std::max<size_t>(set.edge_tok.size(), 1) * 4;
+    char *p = nullptr;
+    HIP_CHECK(hipMalloc((void **)&p, pad(ns) + 3 * pad(ne)));
+    BiasDesc d;
+    d.state_off = (const int32_t *)p; d.edge_tok = (const int32_t *)(p + pad(ns)); d.edge_next = (const int32_t *)(p + pad(ns) + pad(ne));
+    d.edge_bonus = (const float *)(p + pad(ns) + 2 * pad(ne)); d.n_states = set.states();
+    HIP_CHECK(hipMemcpyAsync((void *)d.state_off, set.state_off.data(), ns, hipMemcpyHostToDevice, st));
+    if (!set.edge_tok.empty()) {
+        const size_t b = set.edge_tok.size() * 4;
+        HIP_CHECK(hipMemcpyAsync((void *)d.edge_tok, set.edge_tok.data(), b, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync((void *)d.edge_next, set.edge_next.data(), b, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync((void *)d.edge_bonus, set.edge_bonus.data(), b, hipMemcpyHostToDevice, st));
+    }
+    *dev = p;
+    return d;
+}
+
+// Stepping thread, between two flights' enqueues (as apply_confidence_pending).  The slots that change belong to idle sessions, so
+// no flight in the air reads their entries; a set nobody uses any more is read by no flight either.
+void Engine::apply_bias_pending()
+{
+    std::lock_guard<std::mutex> bg(bias_mu_);
+    std::vector<std::pair<int, int>> todo;
+    todo.swap(bias_pending_);
+    bias_has_pending_.store(false, std::memory_order_release);
+    std::lock_guard<std::mutex> cg(capture_mu_);
+    if (!bias_set_h_) {
+        bool any = false;
+        for (const auto &t : todo) any = any || t.second >= 0;
+        if (!any) return;
+        HipLegacyLock legacy;
+        sync();
+        drop_graphs();
+        const size_t S = (size_t)cfg_.max_slots;
+        bias_set_d_ = dmalloc<int32_t>(S); bias_set_h_ = hmalloc<int32_t>(S); bias_state_d_ = dmalloc<int32_t>(S);
+        bias_desc_d_ = dmalloc<BiasDesc>(kBiasSets); bias_desc_h_ = hmalloc<BiasDesc>(kBiasSets);
+        for (size_t i = 0; i < S; ++i) bias_set_h_[i] = -1;
+        for (int i = 0; i < kBiasSets; ++i) bias_desc_h_[i] = BiasDesc();
+        HIP_CHECK(hipMemsetAsync(bias_state_d_, 0, S * 4, stream_));
+        LOGI("engine: phrase boosting on");
+    }
+    bool tables = false;
+    for (int i = 0; i < kBiasSets; ++i) {
+        BiasEntry &b = bias_sets_[(size_t)i];
+        if (b.set && b.users > 0 && !b.dev) {                     // first use on this engine
+            HipLegacyLock legacy;
+            bias_desc_h_[i] = upload_bias(*b.set, &b.dev, stream_);
+            HIP_CHECK(hipStreamSynchronize(stream_));             // (the source is pageable memory; rare)
+            tables = true;
+        } else if (b.set && b.users == 0) {                       // the last slot has let go of it
+            if (b.dev) { HipLegacyLock legacy; sync_streams(); (void)hipFree(b.dev); b.dev = nullptr; }
+            bias_desc_h_[i] = BiasDesc();
+            b.set.reset();
+            tables = true;
+        }
+    }
+    for (const auto &t : todo) {
+        bias_set_h_[t.first] = t.second;
+        HIP_CHECK(hipMemsetAsync(bias_state_d_ + t.first, 0, 4, stream_));      // every change starts at the root
+    }
+    // whole tables, stream-ordered ahead of this flight's steps; entries of other sessions keep their values
+    if (tables) HIP_CHECK(hipMemcpyAsync(bias_desc_d_, bias_desc_h_, sizeof(BiasDesc) * kBiasSets, hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(bias_set_d_, bias_set_h_, (size_t)cfg_.max_slots * 4, hipMemcpyHostToDevice, stream_));
+}
+
+int Engine::read_bias_state(int slot)
+{
+    if (!bias_ever_.load(std::memory_order_relaxed)) return 0;
+    std::lock_guard<std::mutex> bg(bias_mu_);             // (apply_bias_pending allocates the table under it)
+    for (const auto &t : bias_pending_) if (t.first == slot) return 0;
+    HipLegacyLock legacy;
+    HIP_CHECK(hipSetDevice(cfg_.device));
+    sync_streams();
+    int v = 0;
+    if (bias_state_d_) HIP_CHECK(hipMemcpy(&v, bias_state_d_ + slot, 4, hipMemcpyDeviceToHost));
+    return v;
 }
 
 void Engine::note_conf_step(int k, const int *slots, int m, size_t records)
@@ -1491,6 +1584,7 @@ void Engine::begin_flight()
     // is done long ago and this costs nothing; any other caller would silently overwrite an in-flight search
     if (flight_open_[p]) { HIP_CHECK(hipEventSynchronize(flight_done_[p])); flight_open_[p] = false; }
     if (conf_has_pending_.load(std::memory_order_acquire)) apply_confidence_pending();
+    if (bias_has_pending_.load(std::memory_order_acquire)) apply_bias_pending();
     conf_spans_.clear();
     ring_base_ = (size_t)p * ring_cap_; rec_base_ = (size_t)p * rec_cap_;
     ring_pos_ = ring_base_; rec_pos_ = rec_base_; flight_steps_ = 0;
@@ -1568,6 +1662,7 @@ void Engine::decode_rows(int n, const int *slots, int op)
         ring_pos_ += (size_t)m;
         HIP_CHECK(hipMemcpyAsync(dec_slots_d_, blk, (size_t)m * 4, hipMemcpyHostToDevice, stream_));
         DecRowsArgs a; a.slot_idx = dec_slots_d_; a.M = m; a.op = op; a.blank = P_.blank_id; a.state = gstate_; a.dec = dec_params(); a.de_out = dec_table_ ? nullptr : de_; a.ld_de = d.d_model;
+        a.bias_state = bias_state_d_;
         timed_begin(T_DEC); launch_dec_rows(a, stream_); timed_end(T_DEC);
         if (!dec_table_) run_decproj(m, dec_slots_d_, nullptr, nullptr, 1);
     }
@@ -1630,7 +1725,7 @@ void Engine::zero_slots(int n)
 
 void Engine::debug_encoder(int n, const float *x, const float *h, const float *c, float *eout, float *h2, float *c2)
 {
-    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order everywhere: capture_mu_, then the process-wide legacy-stream lock -- step() takes them in that order)
+    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order everywhere: bias_mu_ first where it is needed -- apply_bias_pending, read_bias_state --, then capture_mu_, then the process-wide legacy-stream lock; step() takes the last two in that order)
     HipLegacyLock legacy;
     HIP_CHECK(hipSetDevice(cfg_.device));
     const NetDims &d = L_.dims;
@@ -1664,7 +1759,7 @@ void Engine::debug_encoder(int n, const float *x, const float *h, const float *c
 
 void Engine::debug_decoder(int n, const int64_t *ctx, float *dout)
 {
-    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order everywhere: capture_mu_, then the process-wide legacy-stream lock -- step() takes them in that order)
+    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order everywhere: bias_mu_ first where it is needed -- apply_bias_pending, read_bias_state --, then capture_mu_, then the process-wide legacy-stream lock; step() takes the last two in that order)
     HipLegacyLock legacy;
     HIP_CHECK(hipSetDevice(cfg_.device));
     const NetDims &d = L_.dims;
@@ -1695,7 +1790,7 @@ void Engine::debug_decoder(int n, const int64_t *ctx, float *dout)
 
 void Engine::debug_joiner(int n, const float *eout, const float *dout, float *logits)
 {
-    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order everywhere: capture_mu_, then the process-wide legacy-stream lock -- step() takes them in that order)
+    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order everywhere: bias_mu_ first where it is needed -- apply_bias_pending, read_bias_state --, then capture_mu_, then the process-wide legacy-stream lock; step() takes the last two in that order)
     HipLegacyLock legacy;
     const NetDims &d = L_.dims;
     HIP_CHECK(hipSetDevice(cfg_.device));
@@ -1723,7 +1818,20 @@ void Engine::debug_joiner(int n, const float *eout, const float *dout, float *lo
 
 void Engine::debug_decide(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out)
 {
-    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order everywhere: capture_mu_, then the process-wide legacy-stream lock -- step() takes them in that order)
+    debug_decide_impl(n, op, logits, early_emit, now_ms, round, state_io, rec_out, nullptr, nullptr);
+}
+
+void Engine::debug_decide_biased(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
+                                 const BiasSet &set, int32_t *bias_state_io)
+{
+    debug_decide_impl(n, op, logits, early_emit, now_ms, round, state_io, rec_out, &set, bias_state_io);
+}
+
+// `set` non-null: tables of its own for the call -- row i uses the set from state bias_state_io[i], or none when that is -1
+void Engine::debug_decide_impl(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
+                               const BiasSet *set, int32_t *bias_state_io)
+{
+    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order everywhere: bias_mu_ first where it is needed -- apply_bias_pending, read_bias_state --, then capture_mu_, then the process-wide legacy-stream lock; step() takes the last two in that order)
     HipLegacyLock legacy;
     const NetDims &d = L_.dims;
     HIP_CHECK(hipSetDevice(cfg_.device));
@@ -1735,8 +1843,20 @@ void Engine::debug_decide(int n, int op, const float *logits, float early_emit, 
     StepRecord *rec_d = dmalloc<StepRecord>((size_t)n);
     HIP_CHECK(hipMemcpy(slots_d, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(gstate_, state_io, (size_t)n * sizeof(GreedyState), hipMemcpyHostToDevice));
+    int32_t *bset_d = nullptr, *bstate_d = nullptr; BiasDesc *bdesc_d = nullptr; void *barrays_d = nullptr;
+    if (set) {
+        std::vector<int32_t> bset((size_t)n), bstate((size_t)n);
+        for (int i = 0; i < n; ++i) { bset[(size_t)i] = bias_state_io[i] < 0 ? -1 : 0; bstate[(size_t)i] = std::max(0, bias_state_io[i]); }
+        bset_d = dmalloc<int32_t>((size_t)n); bstate_d = dmalloc<int32_t>((size_t)n); bdesc_d = dmalloc<BiasDesc>(1);
+        const BiasDesc desc = upload_bias(*set, &barrays_d, stream_);
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        HIP_CHECK(hipMemcpy(bset_d, bset.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(bstate_d, bstate.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(bdesc_d, &desc, sizeof desc, hipMemcpyHostToDevice));
+    }
     if (op == 1) {
         DecRowsArgs a; a.slot_idx = slots_d; a.M = n; a.op = 1; a.blank = P_.blank_id; a.state = gstate_; a.dec = dec_params(); a.de_out = nullptr;
+        a.bias_state = bstate_d;
         launch_dec_rows(a, stream_);
     } else {
         // the logits enter as ONE partial plane with a zero bias: decide_kernel's tree sum + bias returns them unchanged
@@ -1753,6 +1873,7 @@ void Engine::debug_decide(int n, int op, const float *logits, float early_emit, 
         a.bias = zero_d; a.blank = P_.blank_id; a.early_emit = early_emit;
         a.slot_idx = slots_d; a.now_ms = now_d; a.active = active_d; a.dirty = dirty_d; a.tok_class = cls_; a.state = gstate_;
         a.rec = rec_d; a.round = round; a.gen = 1; a.dec = dec_params(); a.de_out = nullptr;
+        a.bias_set = bset_d; a.bias_state = bstate_d; a.bias_desc = bdesc_d;
         launch_decide(a, stream_);
         sync();
         HIP_CHECK(hipMemcpy(rec_out, rec_d, (size_t)n * sizeof(StepRecord), hipMemcpyDeviceToHost));
@@ -1760,6 +1881,12 @@ void Engine::debug_decide(int n, int op, const float *logits, float early_emit, 
     }
     sync();
     HIP_CHECK(hipMemcpy(state_io, gstate_, (size_t)n * sizeof(GreedyState), hipMemcpyDeviceToHost));
+    if (set) {
+        std::vector<int32_t> bstate((size_t)n);
+        HIP_CHECK(hipMemcpy(bstate.data(), bstate_d, (size_t)n * 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) if (bias_state_io[i] >= 0) bias_state_io[i] = bstate[(size_t)i];
+        for (void *p : {(void *)bset_d, (void *)bstate_d, (void *)bdesc_d, barrays_d}) (void)hipFree(p);
+    }
     (void)hipFree(slots_d); (void)hipFree(now_d); (void)hipFree(active_d); (void)hipFree(dirty_d); (void)hipFree(rec_d);
     zero_slots(n);
 }

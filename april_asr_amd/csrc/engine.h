@@ -21,10 +21,12 @@
 #include <array>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
+#include "bias.h"
 #include "fbank_tables.h"
 #include "resample.h"
 #include "kernels.h"
@@ -160,6 +162,46 @@ public:
     // flight's wait for rows of opted-in sessions whose StepRecord is valid.
     const ConfRecord *conf_records(int step_index) const { return conf_h_ ? conf_h_ + rec_off_h_[step_index] : nullptr; }
     uint64_t confidence_records() const { return conf_copied_.load(std::memory_order_relaxed); }     // side records copied to the host so far
+    // ---- phrase boosting, the life cycle of the confidences above: set_slot_bias() only QUEUES the change (any
+    // thread, for an idle session's slot; null = off) and keeps the books -- which of the engine's kBiasSets table entries holds the
+    // set, how many slots use it --; begin_flight() applies it on the stepping thread: the first set of an engine allocates the
+    // per-slot tables and the descriptor table (fixed capacity: captured pointers never change afterwards) and drops the captured
+    // graphs; a set is uploaded the first time a slot of this engine uses it and freed when no slot uses it any more.  The slot's
+    // trie state returns to the root with every change.  False: the table is full or the vocabulary is too large for the kernel.
+    static constexpr int kBiasSets = 64;
+    bool set_slot_bias(int slot, const std::shared_ptr<const BiasSet> &set)
+    {
+        std::lock_guard<std::mutex> g(bias_mu_);
+        if (slot < 0 || slot >= cfg_.max_slots) return false;
+        if (bias_slot_set_.empty()) {
+            if (!set) return true;                               // nothing was ever on
+            bias_slot_set_.assign((size_t)cfg_.max_slots, -1); bias_sets_.resize(kBiasSets);
+        }
+        int idx = -1;
+        if (set) {
+            if (set->vocab != L_.dims.vocab || set->vocab > kBiasMaxVocab) return false;
+            for (int i = 0; i < kBiasSets && idx < 0; ++i) if (bias_sets_[(size_t)i].set == set) idx = i;
+            for (int i = 0; i < kBiasSets && idx < 0; ++i) if (!bias_sets_[(size_t)i].set) idx = i;
+            // (an entry nobody uses any more becomes free when begin_flight has released its device copy)
+            if (idx < 0) return false;
+            bias_sets_[(size_t)idx].set = set;
+            ++bias_sets_[(size_t)idx].users;
+        }
+        const int old = bias_slot_set_[(size_t)slot];
+        if (old < 0 && idx < 0) return true;                     // no set before, none now (every aas_free comes through here): nothing to apply
+        if (old >= 0) --bias_sets_[(size_t)old].users;
+        bias_slot_set_[(size_t)slot] = idx;
+        bias_pending_.push_back(std::make_pair(slot, idx));
+        if (set) bias_ever_.store(true, std::memory_order_relaxed);
+        bias_has_pending_.store(true, std::memory_order_release);
+        return true;
+    }
+    // the device's trie state of a slot; waits for the streams.  0 while no session of the engine has a set, and for a slot with a queued
+    // change (begin_flight returns it to the root before the slot's next step)
+    int read_bias_state(int slot);
+    // aprilx_run_decide_biased: debug_decide with `set` on the rows whose bias_state_io is >= 0 (-1: a row without a set)
+    void debug_decide_biased(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
+                             const BiasSet &set, int32_t *bias_state_io);
     void sync();                               // stepping thread (or under capture_mu_): waits for the three streams and clears the cross-stream dependency flags
     void sync_streams();                       // any thread: waits for the three streams, nothing else
 
@@ -290,6 +332,20 @@ private:
     std::vector<std::pair<size_t, size_t>> conf_spans_;      // (first record, count) of this flight's steps that hold an opted-in row
     std::atomic<uint64_t> conf_copied_{0};
     void apply_confidence_pending();
+    void drop_graphs();                        // (capture_mu_ held, streams drained) every captured graph; they are captured again at their next use
+    // phrase boosting: nothing below is allocated until a session opts in
+    struct BiasEntry { std::shared_ptr<const BiasSet> set; int users = 0; void *dev = nullptr; };      // dev: one allocation holding the four arrays
+    std::mutex bias_mu_;
+    std::vector<BiasEntry> bias_sets_;                // [kBiasSets] (bias_mu_)
+    std::vector<int> bias_slot_set_;                  // [slots] the queued set of every slot (bias_mu_)
+    std::vector<std::pair<int, int>> bias_pending_;   // (slot, table entry or -1) not yet applied (bias_mu_)
+    std::atomic<bool> bias_has_pending_{false}, bias_ever_{false};
+    int32_t *bias_set_d_ = nullptr, *bias_set_h_ = nullptr, *bias_state_d_ = nullptr;     // [slots] device, pinned host mirror; [slots] device
+    BiasDesc *bias_desc_d_ = nullptr, *bias_desc_h_ = nullptr;                           // [kBiasSets]
+    void apply_bias_pending();
+    BiasDesc upload_bias(const BiasSet &set, void **dev, hipStream_t st);
+    void debug_decide_impl(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
+                           const BiasSet *set, int32_t *bias_state_io);
     void note_conf_step(int k, const int *slots, int m, size_t records);
     bool flight_open_[2] = {false, false};     // flight_done_[p] has been recorded and not yet waited for by begin_flight (wait_flight leaves it set: waiting twice is free)
     // streams (engine.cc "streams"): front end / search beside the layer chain, the per-parity buffers that make it safe

@@ -223,6 +223,9 @@ static_assert(sizeof(ConfRecord) == 80, "ConfRecord is 20 x 32 bit");
 enum { REC_VALID = 1, REC_BLANK = 2, REC_CTX = 4 };
 enum TokClassBits { TKC_WORD_START = 1, TKC_SENT_END = 2, TKC_COMMA = 4, TKC_DOT = 8, TKC_DIGIT_START = 16 };
 
+// Phrase boosting (bias.h): one bias set on the device -- the effective token edges of every trie state, CSR
+struct BiasDesc { const int32_t *state_off = nullptr, *edge_tok = nullptr, *edge_next = nullptr; const float *edge_bonus = nullptr; int32_t n_states = 0, reserved = 0; };
+
 struct DecEmbedParams {
     const float *emb = nullptr;            // [vocab][d]
     const float *conv_w = nullptr;         // [d][d/groups][context]
@@ -262,6 +265,11 @@ struct DecideArgs {
     const uint8_t *conf_k = nullptr;       // [slots]
     ConfRecord *conf_ring = nullptr;
     ConfRecord *conf = nullptr; int conf_k_all = 0;
+    // phrase boosting (kernels_bias.inc): null unless a session of the engine opted in.  bias_set: per-slot index into bias_desc
+    // (-1 = none); bias_state: per-slot trie state (0 = root), read and written by the decision beside `state`
+    const int32_t *bias_set = nullptr;     // [slots]
+    int32_t *bias_state = nullptr;         // [slots]
+    const BiasDesc *bias_desc = nullptr;
 };
 void launch_decide(const DecideArgs &a, hipStream_t s);
 
@@ -274,6 +282,7 @@ struct DecRowsArgs {
     GreedyState *state = nullptr;
     DecEmbedParams dec;
     float *de_out = nullptr; int ld_de = 0;
+    int32_t *bias_state = nullptr;         // [slots] or null: op 1 also returns the slot's phrase-boosting state to the root
 };
 void launch_dec_rows(const DecRowsArgs &a, hipStream_t s);
 

@@ -13,9 +13,12 @@
 
 constexpr int kConfRegs = 4;                       // logits each lane keeps in registers (V <= 1024); the rest is re-evaluated per pass
 
-__device__ __forceinline__ float conf_logit(const DecideArgs &a, int m, int n)
+// `bonus`: the row's phrase-boosting table in LDS (kernels_bias.inc; DESIGN.md section 13) or null -- the search of a biased session
+// compares v' = v + bonus, and so do the confidences
+__device__ __forceinline__ float conf_logit(const DecideArgs &a, int m, int n, const float *bonus)
 {
-    return tree_sum(a.ws, a.parts, a.m_stride, a.N, m, n) + a.bias[n];
+    const float v = tree_sum(a.ws, a.parts, a.m_stride, a.N, m, n) + a.bias[n];
+    return bonus ? bias_apply(v, bonus[n]) : v;
 }
 
 // (value, id) arg-max over the workgroup with the search's order: higher value first, lower id on ties; id < 0 = nothing.
@@ -38,7 +41,7 @@ __device__ __forceinline__ void conf_block_best(float &v, int &i, float (*s_v)[4
     }
 }
 
-__device__ __forceinline__ void confidence_row(const DecideArgs &a, int m, int K, ConfRecord *out)
+__device__ __forceinline__ void confidence_row(const DecideArgs &a, int m, int K, ConfRecord *out, const float *bonus = nullptr)
 {
     __shared__ float s_v[2][4], s_f[2][4];
     __shared__ int s_i[2][4];
@@ -55,13 +58,13 @@ __device__ __forceinline__ void confidence_row(const DecideArgs &a, int m, int K
         const int n = tid + 256 * j;
         c[j] = 0.0f;
         if (n < V) {
-            const float v = c[j] = conf_logit(a, m, n);
+            const float v = c[j] = conf_logit(a, m, n, bonus);
             mx = fmaxf(mx, v);
             if (n != a.blank && v > best) { best = v; best_i = n; }
         }
     }
     for (int n = tid + 256 * kConfRegs; n < V; n += 256) {
-        const float v = conf_logit(a, m, n);
+        const float v = conf_logit(a, m, n, bonus);
         mx = fmaxf(mx, v);
         if (n != a.blank && v > best) { best = v; best_i = n; }
     }
@@ -73,7 +76,7 @@ __device__ __forceinline__ void confidence_row(const DecideArgs &a, int m, int K
 
     if (best_i < 0) {                                            // no logit beat the initial value (NaNs): StepRecord.idx == -1
         if (tid == 0) {
-            out->lse = __builtin_nanf(""); out->blank_val = conf_logit(a, m, a.blank); out->n_alt = 0; out->reserved = 0;
+            out->lse = __builtin_nanf(""); out->blank_val = conf_logit(a, m, a.blank, bonus); out->n_alt = 0; out->reserved = 0;
             for (int k = 0; k < kConfMaxAlt; ++k) { out->alt_id[k] = -1; out->alt_logit[k] = 0.0f; }
         }
         return;
@@ -84,7 +87,7 @@ __device__ __forceinline__ void confidence_row(const DecideArgs &a, int m, int K
 #pragma unroll
     for (int j = 0; j < kConfRegs; ++j)
         if (tid + 256 * j < V) sum += expf(c[j] - mx);
-    for (int n = tid + 256 * kConfRegs; n < V; n += 256) sum += expf(conf_logit(a, m, n) - mx);
+    for (int n = tid + 256 * kConfRegs; n < V; n += 256) sum += expf(conf_logit(a, m, n, bonus) - mx);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
     if ((tid & 63) == 0) s_f[1][tid >> 6] = sum;
@@ -92,7 +95,7 @@ __device__ __forceinline__ void confidence_row(const DecideArgs &a, int m, int K
     if (tid == 0) {
         const float S = ((s_f[1][0] + s_f[1][1]) + s_f[1][2]) + s_f[1][3];
         out->lse = mx + logf(S);
-        out->blank_val = conf_logit(a, m, a.blank);
+        out->blank_val = conf_logit(a, m, a.blank, bonus);
         out->reserved = 0;
         out->alt_id[0] = best_i; out->alt_logit[0] = best;
     }
@@ -111,7 +114,7 @@ __device__ __forceinline__ void confidence_row(const DecideArgs &a, int m, int K
 #pragma unroll
         for (int j = 0; j < kConfRegs; ++j)
             if (tid + 256 * j < V) offer(c[j], tid + 256 * j);
-        for (int n = tid + 256 * kConfRegs; n < V; n += 256) offer(conf_logit(a, m, n), n);
+        for (int n = tid + 256 * kConfRegs; n < V; n += 256) offer(conf_logit(a, m, n, bonus), n);
         conf_block_best(bv, bi, s_v, s_i, k & 1);
         if (bi < 0) break;                                       // fewer than K candidates (uniform: every thread holds the same result)
         if (tid == 0) { out->alt_id[k] = bi; out->alt_logit[k] = bv; }

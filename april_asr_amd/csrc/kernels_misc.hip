@@ -125,6 +125,7 @@ __device__ __forceinline__ void dec_embed_row(const DecEmbedParams &p, int tok0,
     }
 }
 
+#include "kernels_bias.inc"
 #include "kernels_confidence.inc"
 
 // ---------------------------------------------------------------- joiner decision
@@ -135,9 +136,12 @@ __device__ __forceinline__ void dec_embed_row(const DecEmbedParams &p, int tok0,
 // 16-byte record written here.
 // CONF = false is the kernel as it was before confidences existed (engines where no session has opted in launch only that one);
 // CONF = true adds the side record of rows whose session asked for it (kernels_confidence.inc), after the decision.
-template <bool CONF>
+// BIAS = true (engines where a session has a phrase-boosting set; kernels_bias.inc): rows whose slot has a set
+// take the arg-max on v' = v + bonus(state, n) and move the slot's trie state with the decision; the other rows run the lines below.
+template <bool CONF, bool BIAS>
 __device__ __forceinline__ void decide_body(const DecideArgs &a)
 {
+    extern __shared__ __attribute__((aligned(16))) unsigned char bias_lds[];      // BIAS: bonus[V] | next[V] (bias_lds_bytes)
     __shared__ float s_best[4], s_blank[4];
     __shared__ int s_idx[4];
     __shared__ int s_ctx[3];                        // [0..1] context for the decoder front end, [2] re-run flag
@@ -152,6 +156,12 @@ __device__ __forceinline__ void decide_body(const DecideArgs &a)
     float best = -9999999999.0f;
     int best_i = -1;
     float blank_v = 0.0f;
+    BiasRow br;
+    if (BIAS) bias_row_begin(a, m, bias_lds, br);
+    // (bias_scan in kernels_bias.inc is a COPY of the loop below with the bonus added: a change to the loop -- the dump, the blank test,
+    // the comparison -- has to be made in both; tests/mutate_device_decide.py edits only this one)
+    if (BIAS && br.bonus) bias_scan(a, m, br, best, best_i, blank_v);
+    else
     for (int n = tid; n < a.n_valid; n += 256) {
         const float v = tree_sum(a.ws, a.parts, a.m_stride, a.N, m, n) + a.bias[n];
         if (a.logits_dump) a.logits_dump[(size_t)m * a.n_valid + n] = v;
@@ -212,6 +222,7 @@ __device__ __forceinline__ void decide_body(const DecideArgs &a)
         if (rerun) flags |= REC_CTX;
         rec->flags = flags;
         a.state[slot] = st;
+        if (BIAS && br.bonus) bias_row_end(a, br, slot, is_blank, tok, is_blank && now - st.last_emit_ms >= 2200u);
         a.dirty[m] = rerun ? 1 : 0;
         if (a.run_flags) {
             if (!is_blank && a.round < 2) a.run_flags[a.round + 1] = a.gen;   // plain stores of the same value: no atomics needed
@@ -222,20 +233,29 @@ __device__ __forceinline__ void decide_body(const DecideArgs &a)
     __syncthreads();
     if (s_ctx[2] && a.de_out) dec_embed_row(a.dec, s_ctx[0], s_ctx[1], a.de_out + (size_t)m * a.ld_de);     // (no table: the decoder runs for this row)
     if (CONF) {      // sessions that asked for confidences: the side record of this round, beside the StepRecord (uniform per workgroup)
-        if (a.conf) confidence_row(a, m, a.conf_k_all, a.conf + m);
+        if (a.conf) confidence_row(a, m, a.conf_k_all, a.conf + m, BIAS ? br.bonus : nullptr);
         else {
             const int k = a.conf_k[a.slot_idx[m]];
-            if (k) confidence_row(a, m, k, a.conf_ring + (rec - a.rec_ring));
+            if (k) confidence_row(a, m, k, a.conf_ring + (rec - a.rec_ring), BIAS ? br.bonus : nullptr);
         }
     }
 }
 
-__global__ __launch_bounds__(256) void decide_kernel(DecideArgs a) { decide_body<false>(a); }
-__global__ __launch_bounds__(256) void decide_conf_kernel(DecideArgs a) { decide_body<true>(a); }
+__global__ __launch_bounds__(256) void decide_kernel(DecideArgs a) { decide_body<false, false>(a); }
+__global__ __launch_bounds__(256) void decide_conf_kernel(DecideArgs a) { decide_body<true, false>(a); }
+__global__ __launch_bounds__(256) void decide_bias_kernel(DecideArgs a) { decide_body<false, true>(a); }
+__global__ __launch_bounds__(256) void decide_conf_bias_kernel(DecideArgs a) { decide_body<true, true>(a); }
 
 void launch_decide(const DecideArgs &a, hipStream_t s)
 {
-    if (a.conf || a.conf_k) hipLaunchKernelGGL(decide_conf_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a);
+    const bool conf = a.conf || a.conf_k;
+    if (a.bias_set) {
+        if (a.n_valid > 8192 || !a.bias_state || !a.bias_desc) { fprintf(stderr, "libapril(mi355x): launch_decide: phrase boosting needs a vocabulary of at most 8192 tokens and all three tables\n"); abort(); }
+        const size_t lds = bias_lds_bytes(a.n_valid);
+        if (conf) hipLaunchKernelGGL(decide_conf_bias_kernel, dim3((unsigned)a.M), dim3(256), lds, s, a);
+        else hipLaunchKernelGGL(decide_bias_kernel, dim3((unsigned)a.M), dim3(256), lds, s, a);
+    }
+    else if (conf) hipLaunchKernelGGL(decide_conf_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(decide_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a);
 }
 
@@ -251,6 +271,7 @@ __global__ __launch_bounds__(256) void dec_rows_kernel(DecRowsArgs a)
             st.last_tok = -1;
             if (st.ctx0 != a.blank) { st.ctx0 = a.blank; st.ctx1 = a.blank; }
             a.state[slot] = st;
+            if (a.bias_state) a.bias_state[slot] = 0;
         }
         s_ctx[0] = st.ctx0; s_ctx[1] = st.ctx1;
     }

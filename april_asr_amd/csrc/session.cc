@@ -42,6 +42,7 @@ void Greedy::init(const ModelParams *p, const std::vector<uint8_t> *cls)
     for (int &i : active_id_) i = -1;
     head_ = last_call_head_ = 0;
     conf_k_ = 0; side_ = nullptr; evals_ = 0;
+    bias_.reset(); bias_state_ = 0;
     emitted_silence_ = true;                       // april_session.c:64
     last_emit_ms_ = 0;
     ctx[0] = ctx[1] = 0;
@@ -174,6 +175,7 @@ bool Greedy::on_joint(const JointResult &r, float early_emit, size_t now_ms, std
     if (!is_blank) {                                // :361-400
         last_emit_ms_ = now_ms;
         push_ctx(best);
+        if (bias_) bias_state_ = bias_->next(bias_state_, best);
         bool fin = head_ >= (size_t)(kMaxActive - 1);
         if (head_ > 0 && (flags & APRIL_TOKEN_FLAG_WORD_BOUNDARY_BIT)) {
             AprilToken &prev = active_[head_ - 1];
@@ -193,6 +195,7 @@ bool Greedy::on_joint(const JointResult &r, float early_emit, size_t now_ms, std
         if (gap >= 2200) {
             finalize_all(out);
             clear_context();
+            bias_state_ = 0;
             emit_silence(out);
         } else if (confident) {
             tok.logprob -= 8.0f;
@@ -206,6 +209,7 @@ bool Greedy::on_joint(const JointResult &r, float early_emit, size_t now_ms, std
 
 void Greedy::finish_flush(std::vector<Event> &out)
 {
+    bias_state_ = 0;
     finalize_all(out);
     clear_context();
     emit_silence(out);
@@ -476,6 +480,17 @@ bool Scheduler::set_confidence(Session *s, int k)
     if (k == s->greedy.confidence()) return true;
     s->greedy.set_confidence(k);
     eng_->set_slot_confidence(s->slot, k);          // (queued: the stepping thread applies it before the session's next flight)
+    return true;
+}
+
+bool Scheduler::set_bias(Session *s, std::shared_ptr<const BiasSet> set)
+{
+    wait_idle(s);
+    std::lock_guard<std::mutex> g(mu_);
+    if (s->closing || s->busy || s->fed || s->flush_requested || !s->inbox.empty() || s->borrow_cnt || s->seg_open || s->flush_phase) return false;
+    if (set.get() == s->greedy.bias() && s->greedy.bias_state() == 0) return true;
+    if (!eng_->set_slot_bias(s->slot, set)) return false;      // (queued: the stepping thread applies it before the session's next flight)
+    s->greedy.set_bias(std::move(set));
     return true;
 }
 

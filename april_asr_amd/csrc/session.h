@@ -21,11 +21,13 @@
 #include <condition_variable>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
 #include "../../include/april_api.h"
 #include "../../include/aprilx_engine.h"
+#include "bias.h"
 #include "engine.h"
 #include "model_loader.h"
 
@@ -64,6 +66,12 @@ public:
     void set_confidence(int k) { conf_k_ = k; }
     int confidence() const { return conf_k_; }
     void set_side(const ConfRecord *side) { side_ = side; }
+    // phrase boosting: the session's bias set and the host's own copy of the trie state, advanced where the
+    // context is pushed / cleared.  The replay does not need it (the records carry the biased arg-max); it is the independent
+    // derivation the device's state is checked against (aprilx_session_bias_state).
+    void set_bias(std::shared_ptr<const BiasSet> set) { bias_ = std::move(set); bias_state_ = 0; }
+    const BiasSet *bias() const { return bias_.get(); }
+    int bias_state() const { return bias_state_; }
     int ctx[2] = {0, 0};
     bool ctx_dirty = false;                   // decoder must be re-run for this session
 
@@ -85,6 +93,8 @@ private:
     void fill_info(uint64_t eval_index);
     int conf_k_ = 0;
     const ConfRecord *side_ = nullptr;
+    std::shared_ptr<const BiasSet> bias_;
+    int bias_state_ = 0;
     uint64_t evals_ = 0;                      // joiner evaluations consumed so far = rows aprilx_session_trace_logits has written
     size_t head_ = 0, last_call_head_ = 0;
     bool emitted_silence_ = true;
@@ -201,6 +211,8 @@ public:
     bool set_input_rate(Session *s, const ResampleSpec *spec);
     // aprilx_session_set_confidence: the same rule
     bool set_confidence(Session *s, int k);
+    // aprilx_session_set_bias: the same rule; null = off.  False also when the engine has no room for another set
+    bool set_bias(Session *s, std::shared_ptr<const BiasSet> set);
     void wait_idle_many(Session *const *ss, int n);
     // until every listed session has at most `max_open` feeds that were submitted and not completed yet (pipelined group feeds)
     void wait_backlog(Session *const *ss, int n, uint64_t max_open);

@@ -4,7 +4,7 @@
 // before it).  The reference has no counterpart: its sessions are fed one by one (example.cpp) and each runs its own ONNX graphs.
 //
 //   g++ -O2 -std=c++17 examples/serve_many.cpp -I include -L april_asr_amd -laprilasr -Wl,-rpath,$PWD/april_asr_amd -o serve_many
-//   ./serve_many model.april audio.raw [sessions=64] [mode=pipelined|lockstep] [input_rate] [--alternatives K]
+//   ./serve_many model.april audio.raw [sessions=64] [mode=pipelined|lockstep] [input_rate] [--alternatives K] [--bias FILE]
 //
 // Every session gets the same PCM16 file, rotated by (session index x 0.37 s) so that the streams differ.  With `input_rate` the file
 // is PCM16 at that rate and every session is told so (aprilx_session_set_input_rate): the library converts it to the model's rate on
@@ -12,6 +12,9 @@
 // session -- "<index> <callbacks> <final results> <tokens in final results> <text of the last final result>" -- and the wall time.
 // `--alternatives K` (anywhere on the line) asks every session for per-token confidences with K alternatives
 // (aprilx_session_set_confidence) and adds the mean confidence of the tokens in final results to the timing line.
+// `--bias FILE` (anywhere on the line): one "boost<TAB>phrase" per line; every session's search boosts these phrases
+// (aprilx_bias_create / aprilx_session_set_bias, one set shared by all sessions); `--bias-sessions N` gives the set to the first N
+// sessions only (the others are unbiased neighbours on an engine that has opted in).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -41,6 +44,22 @@ static void on_result(void *ud, AprilResultType type, size_t count, const AprilT
 int main(int argc, char **argv)
 {
     int alternatives = 0;
+    const char *bias_file = nullptr;
+    int bias_sessions = -1;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!strcmp(argv[i], "--bias-sessions")) {
+            bias_sessions = atoi(argv[i + 1]);
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!strcmp(argv[i], "--bias")) {
+            bias_file = argv[i + 1];
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
     for (int i = 1; i + 1 < argc; ++i)
         if (!strcmp(argv[i], "--alternatives")) {
             alternatives = atoi(argv[i + 1]);
@@ -64,6 +83,30 @@ int main(int argc, char **argv)
     const size_t steps = pcm.size() / step;
     if (!steps) { fprintf(stderr, "audio shorter than one feed\n"); return 1; }
 
+    AprilxBias bias = nullptr;
+    if (bias_file) {
+        FILE *bf = fopen(bias_file, "r");
+        if (!bf) { fprintf(stderr, "cannot open %s\n", bias_file); return 1; }
+        std::vector<std::string> phrases; std::vector<float> boosts;
+        char line[1024];
+        for (int ln = 1; fgets(line, sizeof line, bf); ++ln) {
+            char *tab = strchr(line, '\t'), *end = nullptr;
+            const float boost = strtof(line, &end);
+            std::string p(tab ? tab + 1 : "");
+            while (!p.empty() && (p.back() == '\n' || p.back() == '\r')) p.pop_back();
+            if (!tab || end != tab || end == line || p.empty()) { fprintf(stderr, "%s:%d: expected boost<TAB>phrase\n", bias_file, ln); return 1; }
+            boosts.push_back(boost); phrases.push_back(p);
+        }
+        fclose(bf);
+        std::vector<const char *> ptrs;
+        for (const std::string &p : phrases) ptrs.push_back(p.c_str());
+        char err[256];
+        bias = aprilx_bias_create(model, ptrs.size(), ptrs.data(), boosts.data(), err, sizeof err);
+        if (!bias) { fprintf(stderr, "bias set refused: %s\n", err); return 1; }
+        int32_t states = 0; int64_t edges = 0;
+        const int dropped = aprilx_bias_info(bias, &states, &edges);
+        fprintf(stderr, "bias set: %zu phrases (%d left out as unspellable), %d states, %lld token edges\n", phrases.size(), dropped, states, (long long)edges);
+    }
     std::vector<Stream> streams((size_t)n);
     std::vector<AprilASRSession> sessions((size_t)n);
     std::vector<std::vector<short>> audio((size_t)n);
@@ -76,6 +119,7 @@ int main(int argc, char **argv)
         if (!sessions[(size_t)i]) { fprintf(stderr, "failed to create session %d\n", i); return 1; }
         if (argc > 5 && aprilx_session_set_input_rate(sessions[(size_t)i], (uint32_t)rate) != 0) { fprintf(stderr, "input rate %zu refused\n", rate); return 1; }
         if (alternatives && aprilx_session_set_confidence(sessions[(size_t)i], alternatives) != 0) { fprintf(stderr, "%d alternatives refused\n", alternatives); return 1; }
+        if (bias && (bias_sessions < 0 || i < bias_sessions) && aprilx_session_set_bias(sessions[(size_t)i], bias) != 0) { fprintf(stderr, "bias set refused by session %d\n", i); return 1; }
         const size_t rot = ((size_t)i * (size_t)(0.37 * rate)) % pcm.size();
         audio[(size_t)i].assign(pcm.begin() + (long)rot, pcm.end());
         audio[(size_t)i].insert(audio[(size_t)i].end(), pcm.begin(), pcm.begin() + (long)rot);
@@ -99,8 +143,10 @@ int main(int argc, char **argv)
         for (const Stream &s : streams) { sum += s.conf_sum; cnt += s.conf_n; }
         fprintf(stderr, "%d alternatives: %.3f ms per 100 ms step, mean confidence of %zu final tokens %.3f\n", alternatives, ms / (double)steps, cnt, cnt ? sum / (double)cnt : 0.0);
     }
+    if (bias) fprintf(stderr, "phrase boosting: %.3f ms per 100 ms step\n", ms / (double)steps);
     if (argc > 5) fprintf(stderr, "input at %zu Hz: %.3f ms per 100 ms step\n", rate, ms / (double)steps);
     for (AprilASRSession s : sessions) aas_free(s);
+    if (bias) aprilx_bias_free(bias);
     aam_free(model);
     return 0;
 }

@@ -171,6 +171,38 @@ APRIL_EXPORT int aprilx_session_confidence(AprilASRSession session);
    through the device code the search uses; out = n AprilxTokenInfo (eval_index = row). */
 APRIL_EXPORT int aprilx_run_confidence(AprilASRModel model, int n, const float *logits, int k, AprilxTokenInfo *out);
 
+/* ---- phrase boosting ("hot words", contextual biasing) ------------------------------------
+ * Vocabulary the model was not tuned for: the caller hands over phrases, each with a boost in logit units, and the search adds the
+ * boost to the tokens that continue one of them -- on the GPU, where the arg-max reads the logit row (DESIGN.md section 13 has the
+ * contract).  A phrase is a byte string written the way the model's tokens are written (UTF-8, no case folding); one that does not
+ * begin with ' ' gets one prepended (phrases start at word boundaries).  No tokeniser is needed: every segmentation of a phrase into
+ * the model's tokens is matched.  Negative boosts suppress.  AprilToken.logprob of a session with a set is the value the search
+ * compared, bonus included.  Sessions without a set are not affected. */
+typedef struct AprilxBias_i *AprilxBias;
+/* Builds a set for this model (no GPU needed; works on aprilx_model_load_host models).  NULL and a message in err when refused: no
+ * phrases, an empty phrase, one over 256 bytes, a boost that is not finite or beyond +-100, more than 65535 trie states or 4 M token
+ * edges, a vocabulary over 8192 tokens.  Phrases that no sequence of the model's tokens can spell are left out and counted
+ * (aprilx_bias_info; err then holds a note although the call succeeds). */
+APRIL_EXPORT AprilxBias aprilx_bias_create(AprilASRModel model, size_t n, const char *const *phrases, const float *boosts, char *err, size_t err_cap);
+/* Sessions still using the set keep it alive. */
+APRIL_EXPORT void aprilx_bias_free(AprilxBias bias);
+/* Trie states and effective token edges of the set; returns the number of phrases left out as unspellable (-1: no set). */
+APRIL_EXPORT int aprilx_bias_info(AprilxBias bias, int32_t *states, int64_t *edges);
+/* The effective edges of one state, token ids ascending (no GPU): returns their number, -1 on a bad state or when cap is too small
+ * (with all three arrays NULL: only the count). */
+APRIL_EXPORT int aprilx_bias_edges(AprilxBias bias, int32_t state, int32_t *tok, int32_t *next, float *bonus, size_t cap);
+/* Extends aas_create_session: the session's search uses the set from now on, starting at the root; NULL = off.  0 on success; -1 when
+ * the set was built for another token list, the engine already holds 64 different sets in use, or the session has audio queued or fed since its
+ * creation / last completed aas_flush (the rule of aprilx_session_set_input_rate). */
+APRIL_EXPORT int aprilx_session_set_bias(AprilASRSession session, AprilxBias bias);
+/* The trie state as the host's state machine holds it and as the device keeps it for the session's slot: derived independently,
+ * must agree; tests only.  Returns 1 when the session has a set, 0 when not. */
+APRIL_EXPORT int aprilx_session_bias_state(AprilASRSession session, int32_t *host_state, int32_t *device_state);
+/* Tests only: aprilx_run_decide with the set on the rows whose bias_state_io[i] >= 0 (the row's trie state, in and out); -1 = a row
+ * without a set.  op 1 returns the states to the root. */
+APRIL_EXPORT int aprilx_run_decide_biased(AprilASRModel model, int n, int op, const float *logits, float early_emit, const int32_t *now_ms, int round,
+                                          int32_t *state_io, void *records_out, AprilxBias bias, int32_t *bias_state_io);
+
 /* ---- tracing / statistics ---------------------------------------------------------------*/
 /* every joiner evaluation of this session appends `vocab` floats to buf (tests only; chunk steps of a traced session are
    issued eagerly and waited for one by one) */
@@ -234,6 +266,9 @@ APRIL_EXPORT int aprilx_greedy_step(AprilxGreedy g, int32_t idx, float max_val, 
                                     size_t now_ms, int32_t *ctx_out);
 APRIL_EXPORT void aprilx_greedy_finish(AprilxGreedy g);
 APRIL_EXPORT void aprilx_greedy_free(AprilxGreedy g);
+/* the state machine's own copy of the phrase-boosting state: attach a set (NULL = off; the state returns to the root), read the state */
+APRIL_EXPORT int aprilx_greedy_set_bias(AprilxGreedy g, AprilxBias bias);
+APRIL_EXPORT int aprilx_greedy_bias_state(AprilxGreedy g);
 
 /* A result handler implemented in C, for load generators and benchmarks (a Python or JNI callback costs more than
    the GPU step at thousands of sessions).  userdata -> uint64_t[6]: calls, partial, final, cant_keep_up, silence, tokens */
