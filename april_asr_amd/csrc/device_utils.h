@@ -1,16 +1,18 @@
 // Device helpers shared by the GEMM and row kernels.  Anything that takes part in a floating-point reduction lives
-// here exactly once: the fused (small-batch) and unfused paths must produce the same bits.
+// here exactly once, and so does the arithmetic that follows it (epilogue.h): the fused (small-batch) and unfused paths
+// must produce the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 
 #include <hip/hip_ext.h>
+#include <atomic>
 
 namespace aprilx {
 
-// host side: the GEMM kernels of kernels_gemm.hip, kernels_gemm_tile.hip, kernels_gemm_pp.hip and kernels_gemm_pw.hip go out through
-// APRIL_LAUNCH so that a pending pair of profiling events (gemm_profile_next_launch, kernels.h) rides in the kernel's own dispatch
-// packet; the stream kernels (kernels_recur.hip) and GM_KW (kernels_gemm_kw.hip) use plain hipLaunchKernelGGL and take no events
+// host side: every GEMM kernel (kernels_gemm*.hip, kernels_recur.hip) goes out through APRIL_LAUNCH so that a pending pair of
+// profiling events (gemm_profile_next_launch, kernels.h) rides in the kernel's own dispatch packet; with no pair pending (the
+// product's case) it is the plain hipLaunchKernelGGL call
 struct ProfileEvents { hipEvent_t a = nullptr, b = nullptr; };
 ProfileEvents &tl_profile_events();
 #define APRIL_LAUNCH(kernel, grid, block, lds, stream, ...)                                                                         \
@@ -19,6 +21,36 @@ ProfileEvents &tl_profile_events();
         if (pe_.a) { hipExtLaunchKernelGGL(kernel, grid, block, (std::uint32_t)(lds), stream, pe_.a, pe_.b, 0, __VA_ARGS__); pe_.a = pe_.b = nullptr; } \
         else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                                    \
     } while (0)
+
+// The launch of a schedule's kernel pair: Kernel takes g by value, ZKernel the device array of n same-shape problems (dev_args != null)
+// and whatever else the schedule passes (ztail).  announce_lds: dynamic LDS beyond 64 KB has to be announced, per instantiation AND
+// per device (one engine per GPU, each with its own stepping thread: a bit per device id, set after the attribute calls).
+template <auto Kernel, auto ZKernel, class... ZTail>
+void launch_gemm_pair(dim3 grid, dim3 block, size_t lds, bool announce_lds, hipStream_t s, const GemmArgs &g, const GemmArgs *dev_args, ZTail... ztail)
+{
+    if (announce_lds) {
+        static std::atomic<uint64_t> attr_devs{0};
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        const uint64_t bit = 1ull << (dev & 63);
+        if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ZKernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            attr_devs.fetch_or(bit, std::memory_order_release);
+        }
+    }
+    if (dev_args) APRIL_LAUNCH(ZKernel, grid, block, lds, s, dev_args, ztail...);
+    else APRIL_LAUNCH(Kernel, grid, block, lds, s, g);
+}
+
+// LDS floats behind a tile's planes for the BasicNorm scales of its bm rows (rows_scale_park, epilogue.h): the scales, then the rows'
+// partials padded to groups + 1 -- for the epilogues that take a row scale, when the GEMM has one
+inline size_t scale_lds_floats(const GemmArgs &g, int bm)
+{
+    const RowScale &rsc = g.epi == EPI_HR ? g.r_scale : g.x_scale;
+    const int sg = ((g.epi == EPI_HR || g.epi == EPI_LSTM || g.epi == EPI_SLOT_STORE || g.epi == EPI_XPART) && rsc.ssq) ? rsc.groups : 0;
+    return (size_t)bm + (sg ? (size_t)bm * (sg + 1) : 0);
+}
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
@@ -133,6 +165,9 @@ __device__ __forceinline__ void stamp_end(unsigned long long *slot, unsigned tot
         }
     }
 }
+// the same for a launch whose workgroups are the grid's: the first one starts the clock, linear id = x + gx (y + gy z)
+__device__ __forceinline__ void stamp_begin(unsigned long long *slot) { stamp_begin(slot, (blockIdx.x | blockIdx.y | blockIdx.z) == 0); }
+__device__ __forceinline__ void stamp_end(unsigned long long *slot) { stamp_end(slot, gridDim.x * gridDim.y * gridDim.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)); }
 
 // sigma and tanh on the hardware exp2 / rcp units (v_exp_f32, v_rcp_f32: ~1 ulp each); absolute error ~1e-7, far inside
 // the 1e-4 per-call parity tolerance, and ~10x fewer VALU instructions than libm's expf/tanhf
@@ -140,3 +175,5 @@ __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn
 __device__ __forceinline__ float fast_tanh(float x) { return 2.0f * fast_sigmoid(2.0f * x) - 1.0f; }
 
 }  // namespace aprilx
+
+#include "epilogue.h"

@@ -606,7 +606,7 @@ void Engine::timed_end(int cls)
 {
     if (!profiling_) return;
     if (cls == T_GATES) {
-        // (a launch path that does not go through APRIL_LAUNCH left the pair untouched: drop the sample instead of reading unrecorded events)
+        // (every GEMM launcher goes through APRIL_LAUNCH, which consumes the pair; a guard for a launch path that does not: drop the sample instead of reading unrecorded events)
         if (gemm_profile_pending()) { gemm_profile_next_launch(nullptr, nullptr); return; }
     } else HIP_CHECK(hipEventRecord(ev_pool_[ev_used_].b, stream_));
     ++ev_used_;

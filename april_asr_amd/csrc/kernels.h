@@ -133,7 +133,7 @@ struct GemmArgs {
     // of a z-batched launch point at the same one).  Every workgroup stamps real time (s_memrealtime, 10 ns) when it starts and when it has
     // finished; the last one to finish adds (latest end - earliest start) to the slot's sum and re-arms it -- the launch's duration under
     // whatever launch path is in use (graph replay), with no event packet near the kernel.  null (the product's case): two scalar branches.
-    unsigned long long *stamp = nullptr;   // slot of 128 words (device_utils.h stamp_begin / stamp_end): [0] start, [1] arrivals, [2] sum of durations (ticks), [3] launches, [8..71] end stamps
+    unsigned long long *stamp = nullptr;   // slot of STAMP_WORDS = 144 words (device_utils.h stamp_begin / stamp_end): [0] start, [1] classes done, [2] sum of durations (ticks), [3] launches, [8..71] end stamps, [72..135] arrival counters
     int debug = 0;                         // measurement only: 1 = skip the MFMA main loop, 2 = skip the epilogue math, 3 = all k blocks read block 0
 };
 void launch_gemm(const GemmArgs &g, hipStream_t s);

@@ -46,7 +46,6 @@ struct TileCfg {
     static constexpr int LDS_FLOATS = 4 * BM * LDR;       // one partial plane per wave; BM row scales follow (LDS_FLOATS + BM floats are requested)
 };
 
-using h4 = __attribute__((ext_vector_type(4))) _Float16;
 template <int WT> struct WQuad { using type = f32x4; };
 template <> struct WQuad<1> { using type = h4; };
 
@@ -537,24 +536,10 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int zg, const
     if (NEED_SCL) {
         // the rows' scales: partials (in registers since the first instruction of the kernel) -> LDS, 64 threads add them in
         // column order (the order of row_scale()); rows are padded to G + 1 floats (conflict-free column walks)
-        const int G = rsc.groups;
         float *part = scl + Cfg::BM;
-        if (staged) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) if (k < ppt && sj0 + k < G) part[srow * (G + 1) + sj0 + k] = stg[k];
-        } else {
-            for (int i = threadIdx.x; i < Cfg::BM * G; i += NTH) {
-                int r = m0 + i / G;
-                if (r >= g.M) r = g.M - 1;
-                part[(i / G) * (G + 1) + i % G] = rsc.ssq[(size_t)r * G + i % G];
-            }
-        }
+        rows_scale_park<Cfg::BM, NTH>(part, rsc, staged, stg, ppt, srow, sj0, m0, g.M, [](const float *p) { return *p; });
         __syncthreads();
-        if (threadIdx.x < Cfg::BM) {
-            float t = 0.0f;
-            for (int j = 0; j < G; ++j) t += part[threadIdx.x * (G + 1) + j];
-            scl[threadIdx.x] = __builtin_amdgcn_rsqf(t * rsc.inv_n + rsc.eps);
-        }
+        if (threadIdx.x < Cfg::BM) scl[threadIdx.x] = rows_scale_sum(part + threadIdx.x * (rsc.groups + 1), rsc);
         __syncthreads();
     }
     if constexpr (!ASM) stamp(3);
@@ -574,9 +559,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int zg, const
             const int q = threadIdx.x + i * NTH;
             const int m = m0 + q / QROW, n = nt0 * 16 + (q % QROW) * 4;
             if (e_ok[i]) {
-                const float rs = scl[q / QROW];
-                *reinterpret_cast<f32x4 *>(g.state + (size_t)e_slot[i] * g.ld_state + n) = v[i];
-                *reinterpret_cast<f32x4 *>(g.out + (size_t)m * g.ldo + n) = e_res[i] * rs + v[i];
+                const HrTail t = hr_tail(v[i], e_res[i], scl[q / QROW]);
+                *reinterpret_cast<f32x4 *>(g.state + (size_t)e_slot[i] * g.ld_state + n) = t.state;
+                *reinterpret_cast<f32x4 *>(g.out + (size_t)m * g.ldo + n) = t.out;
             }
         }
     } else if (EPI == EPI_RESID_SSQ) {
@@ -587,12 +572,11 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int zg, const
             const bool ok = e_ok[i];
             f32x4 y = f32x4{0.f, 0.f, 0.f, 0.f};
             if (ok) {
-                y = v[i] + e_bias[i];
-                if (g.resid) y = e_res[i] + y;
+                y = resid_tail(v[i], e_bias[i], e_res[i], g.resid != nullptr);
                 *reinterpret_cast<f32x4 *>(g.out + (size_t)m * g.ldo + n) = y;
             }
-            const float ss = granule_ssq(y);           // all lanes take part in the shuffles
-            if (ok && (q & 7) == 0) g.ssq_out[(size_t)m * (g.N / SSQ_COLS) + n / SSQ_COLS] = ss;
+            float ss;                                  // (all lanes take part in the shuffles)
+            if (granule_ssq_store(y, ok, q, ss)) g.ssq_out[(size_t)m * (g.N / SSQ_COLS) + n / SSQ_COLS] = ss;
         }
     } else if (EPI == EPI_SLOT_STORE) {
 #pragma unroll
@@ -600,7 +584,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int zg, const
             const int q = threadIdx.x + i * NTH;
             const int n = nt0 * 16 + (q % QROW) * 4;
             if (e_ok[i])
-                *reinterpret_cast<f32x4 *>(g.out + (size_t)e_slot[i] * g.ldo + n) = NEED_SCL ? v[i] * scl[q / QROW] + e_bias[i] : v[i] + e_bias[i];
+                *reinterpret_cast<f32x4 *>(g.out + (size_t)e_slot[i] * g.ldo + n) = NEED_SCL ? slot_value(v[i], scl[q / QROW], e_bias[i]) : slot_value(v[i], e_bias[i]);
         }
     } else if (EPI == EPI_XPART) {
 #pragma unroll
@@ -611,7 +595,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int zg, const
             if (q < NQ && m < g.M) {
                 const int o = row * Cfg::LDR + col;
                 const f32x4 p0 = *reinterpret_cast<const f32x4 *>(red + o), p1 = *reinterpret_cast<const f32x4 *>(red + PLANE + o);
-                *reinterpret_cast<f32x4 *>(g.out + (size_t)m * g.ldo + n) = NEED_SCL ? (p0 + p1) * scl[row] : (p0 + p1);
+                *reinterpret_cast<f32x4 *>(g.out + (size_t)m * g.ldo + n) = NEED_SCL ? gate_xin(p0, p1, scl[row]) : (p0 + p1);
             }
         }
     } else if (EPI == EPI_BIAS_DSWISH) {
@@ -630,11 +614,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int zg, const
             const int row = q / QROW, col = (q % QROW) * 4;
             const int m = m0 + row, n = nt0 * 16 + col;
             if (q < NQ && m < g.M) {
-                const f32x4 y = summed4(row * Cfg::LDR + col) + bq[i];
-                f32x4 o;
-                o.x = y.x * fast_sigmoid(y.x - 1.0f); o.y = y.y * fast_sigmoid(y.y - 1.0f);
-                o.z = y.z * fast_sigmoid(y.z - 1.0f); o.w = y.w * fast_sigmoid(y.w - 1.0f);
-                *reinterpret_cast<f32x4 *>(g.out + (size_t)m * g.ldo + n) = o;
+                *reinterpret_cast<f32x4 *>(g.out + (size_t)m * g.ldo + n) = dswish4(summed4(row * Cfg::LDR + col) + bq[i]);
             }
         }
     } else {   // EPI_LSTM: each 4-column group = gates i,f,g,o of one hidden unit
@@ -665,15 +645,15 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int zg, const
                     xin = pq[i];
                 } else {
                     const f32x4 p0 = *reinterpret_cast<const f32x4 *>(red + o), p1 = *reinterpret_cast<const f32x4 *>(red + PLANE + o);
-                    xin = (p0 + p1) * scl[(threadIdx.x + i * NTH) / QROW];
+                    xin = gate_xin(p0, p1, scl[(threadIdx.x + i * NTH) / QROW]);
                 }
-                gt = ((xin + p2) + p3) + qb[i];
+                gt = gate_combine(xin, p2, p3, qb[i]);
             } else {
                 gt = summed4(qo[i]) + qb[i];
             }
-            const float c_new = fast_sigmoid(gt.y) * cprev[i] + fast_sigmoid(gt.x) * fast_tanh(gt.z);
-            const float u = g.debug == 2 ? gt.x + gt.y + gt.z + gt.w : fast_sigmoid(gt.w) * fast_tanh(c_new);
-            if (qok[i]) { *cptr[i] = c_new; g.out[(size_t)qm[i] * g.ldo + qunit[i]] = u; }
+            const LstmCell cell = lstm_cell(gt, cprev[i]);
+            const float u = g.debug == 2 ? gt.x + gt.y + gt.z + gt.w : cell.u;      // (measurement only)
+            if (qok[i]) { *cptr[i] = cell.c_new; g.out[(size_t)qm[i] * g.ldo + qunit[i]] = u; }
         }
     }
     stamp(4);
@@ -682,9 +662,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int zg, const
 template <int MT, int NT, int EPI, int AOP, int WT, int MODE, int ASM>
 __global__ __launch_bounds__(256, (MT == 4 && !ASM) ? 2 : 1) void gemm_f32_kernel(GemmArgs g)
 {
-    if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp, (blockIdx.x | blockIdx.y | blockIdx.z) == 0);
+    if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp);
     gemm_body<MT, NT, EPI, AOP, WT, MODE, ASM>(g, (int)blockIdx.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), (int)blockIdx.x, (int)blockIdx.y, gridDim.y == 1);
-    if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp, gridDim.x * gridDim.y * gridDim.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+    if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp);
 }
 
 // The same GEMM for `gridDim.z / zdiv` INDEPENDENT problems of one shape in one launch: blockIdx.z / zdiv selects the argument
@@ -699,9 +679,9 @@ __global__ __launch_bounds__(256, (MT == 4 && !ASM) ? 2 : 1) void gemm_f32_zkern
     // are generic to the compiler -- flat_load / flat_store instead of global_load with an SGPR base -- and neither assumptions
     // nor address-space round trips change that; measured against the by-value kernel at one problem per launch: no difference.)
     const GemmArgs g = zargs[zl];
-    if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp, (blockIdx.x | blockIdx.y | blockIdx.z) == 0);
+    if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp);
     gemm_body<MT, NT, EPI, AOP, WT, MODE, ASM>(g, (int)blockIdx.z - zl * zdiv, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), (int)blockIdx.x, (int)blockIdx.y, gridDim.y == 1);
-    if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp, gridDim.x * gridDim.y * gridDim.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+    if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp);
 }
 
 // Balanced form of the z-batched launch for tile counts that are not a whole number of rounds (three 256-row gate problems =
@@ -927,8 +907,7 @@ static void launch_one(const GemmArgs &g, hipStream_t s)
     constexpr bool HAS_ASM = MODE == GM_SLAB && MT == 4 && (NT == 4 || NT == 2) && AOP == AOP_NONE && (EPI == EPI_LSTM || EPI == EPI_BIAS_DSWISH);
     using Cfg = TileCfg<MT, NT>;
     dim3 grid((unsigned)(g.N / Cfg::BN), (unsigned)((g.M + Cfg::BM - 1) / Cfg::BM), (unsigned)(MODE == GM_FULLK ? 1 : g.kz / g.zs));
-    const int sg = EPI == EPI_HR ? g.r_scale.groups : ((EPI == EPI_LSTM || EPI == EPI_SLOT_STORE || EPI == EPI_XPART) && g.x_scale.ssq ? g.x_scale.groups : 0);
-    const size_t lds = (size_t)(Cfg::LDS_FLOATS + Cfg::BM + (sg ? Cfg::BM * (sg + 1) : 0)) * sizeof(float);
+    const size_t lds = (Cfg::LDS_FLOATS + scale_lds_floats(g, Cfg::BM)) * sizeof(float);
     if (g.wt == 1) { APRIL_LAUNCH((gemm_f32_kernel<MT, NT, EPI, AOP, 1, MODE, 0>), grid, dim3(256), lds, s, g); return; }
     if constexpr (HAS_ASM) {
         if (g.asm_loop && g.debug != 1) { APRIL_LAUNCH((gemm_f32_kernel<MT, NT, EPI, AOP, 0, MODE, 1>), grid, dim3(256), lds, s, g); return; }
@@ -1056,8 +1035,7 @@ static void launch_one_z(const GemmArgs &g, const GemmArgs *dev_args, int n, hip
     using Cfg = TileCfg<MT, NT>;
     const int zdiv = MODE == GM_FULLK ? 1 : g.kz / g.zs;
     dim3 grid((unsigned)(g.N / Cfg::BN), (unsigned)((g.M + Cfg::BM - 1) / Cfg::BM), (unsigned)(zdiv * n));
-    const int sg = EPI == EPI_HR ? g.r_scale.groups : ((EPI == EPI_LSTM || EPI == EPI_SLOT_STORE || EPI == EPI_XPART) && g.x_scale.ssq ? g.x_scale.groups : 0);
-    const size_t lds = (size_t)(Cfg::LDS_FLOATS + Cfg::BM + (sg ? Cfg::BM * (sg + 1) : 0)) * sizeof(float);
+    const size_t lds = (Cfg::LDS_FLOATS + scale_lds_floats(g, Cfg::BM)) * sizeof(float);
     constexpr bool HAS_ASM = MODE == GM_SLAB && MT == 4 && (NT == 4 || NT == 2) && AOP == AOP_NONE && (EPI == EPI_LSTM || EPI == EPI_BIAS_DSWISH);
     if (g.wt == 1) { APRIL_LAUNCH((gemm_f32_zkernel<MT, NT, EPI, AOP, 1, MODE, 0>), grid, dim3(256), lds, s, dev_args, zdiv); return; }
     if constexpr (HAS_ASM) {

@@ -386,30 +386,13 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
                 }
     }
     if (NEED_SCL) {
-        // the rows' scales: partials (in registers since the first instruction of the kernel) -> LDS, BM threads add them in column
-        // order (the order of row_scale()); rows are padded to G + 1 floats
-        const int Gn = rsc.groups;
-        float *part = scl + BM;
-        if (staged) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) if (k < ppt && sj0 + k < Gn) part[srow * (Gn + 1) + sj0 + k] = stg[k];
-        } else {
-            for (int i = threadIdx.x; i < BM * Gn; i += NTH) {
-                int r = m0 + i / Gn;
-                if (r >= g.M) r = g.M - 1;
-                part[(i / Gn) * (Gn + 1) + i % Gn] = gload<float>(rsc.ssq + (size_t)r * Gn + i % Gn);
-            }
-        }
+        // the rows' scales: partials (in registers since the first instruction of the kernel, or fetched now) -> LDS, behind the barrier
+        // of the meet BM threads add them in column order (rows_scale_park / rows_scale_sum, epilogue.h)
+        rows_scale_park<BM, NTH>(scl + BM, rsc, staged, stg, ppt, srow, sj0, m0, g.M, [](const float *p) { return gload<float>(p); });
     }
     __syncthreads();
     if (NEED_SCL) {
-        if (threadIdx.x < BM) {
-            const int Gn = rsc.groups;
-            const float *part = scl + BM;
-            float t = 0.0f;
-            for (int j = 0; j < Gn; ++j) t += part[threadIdx.x * (Gn + 1) + j];
-            scl[threadIdx.x] = __builtin_amdgcn_rsqf(t * rsc.inv_n + rsc.eps);
-        }
+        if (threadIdx.x < BM) scl[threadIdx.x] = rows_scale_sum(scl + BM + threadIdx.x * (rsc.groups + 1), rsc);
         __syncthreads();
     }
     stamp(3);
@@ -429,20 +412,19 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
         const f32x4 v = q < NQ ? summed4(row * LDR + col) : f32x4{0.f, 0.f, 0.f, 0.f};
         if (EPI == EPI_HR) {
             if (e_ok[i]) {
-                const float rs = scl[row];
-                gstore<f32x4>(g.state + (size_t)e_slot[i] * g.ld_state + n, v);
-                gstore<f32x4>(g.out + (size_t)m * g.ldo + n, e_res[i] * rs + v);
+                const HrTail t = hr_tail(v, e_res[i], scl[row]);
+                gstore<f32x4>(g.state + (size_t)e_slot[i] * g.ld_state + n, t.state);
+                gstore<f32x4>(g.out + (size_t)m * g.ldo + n, t.out);
             }
         } else {   // EPI_RESID_SSQ
             const bool ok = e_ok[i];
             f32x4 y = f32x4{0.f, 0.f, 0.f, 0.f};
             if (ok) {
-                y = v + e_bias[i];
-                if (g.resid) y = e_res[i] + y;
+                y = resid_tail(v, e_bias[i], e_res[i], g.resid != nullptr);
                 gstore<f32x4>(g.out + (size_t)m * g.ldo + n, y);
             }
-            const float ss = granule_ssq(y);               // all lanes take part in the shuffles
-            if (ok && (q & 7) == 0) gstore<float>(g.ssq_out + (size_t)m * (g.N / SSQ_COLS) + n / SSQ_COLS, ss);
+            float ss;                                      // (all lanes take part in the shuffles)
+            if (granule_ssq_store(y, ok, q, ss)) gstore<float>(g.ssq_out + (size_t)m * (g.N / SSQ_COLS) + n / SSQ_COLS, ss);
         }
     }
     stamp(4);
@@ -468,20 +450,8 @@ void launch_kw_one(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream
 {
     using G = KwGeom<MT, NT>;
     dim3 grid((unsigned)(g.N / G::BN), (unsigned)((g.M + G::BM - 1) / G::BM), (unsigned)std::max(1, n));
-    const int sg = (EPI == EPI_HR && g.r_scale.ssq) ? g.r_scale.groups : 0;
-    const size_t lds = (size_t)G::LDS_MAIN + (size_t)(G::BM + (sg ? G::BM * (sg + 1) : 0)) * sizeof(float);
-    // dynamic LDS beyond 64 KB has to be announced, per instantiation AND per device (see kernels_gemm_tile.hip)
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_kw_kernel<MT, NT, EPI, CPW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_kw_zkernel<MT, NT, EPI, CPW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_devs.fetch_or(bit, std::memory_order_release);
-    }
-    if (dev_args) hipLaunchKernelGGL((gemm_kw_zkernel<MT, NT, EPI, CPW>), grid, dim3(G::NTH), lds, s, dev_args);
-    else hipLaunchKernelGGL((gemm_kw_kernel<MT, NT, EPI, CPW>), grid, dim3(G::NTH), lds, s, g);
+    const size_t lds = (size_t)G::LDS_MAIN + scale_lds_floats(g, G::BM) * sizeof(float);
+    launch_gemm_pair<&gemm_kw_kernel<MT, NT, EPI, CPW>, &gemm_kw_zkernel<MT, NT, EPI, CPW>>(grid, dim3(G::NTH), lds, true, s, g, dev_args);
 }
 
 template <int MT, int NT>

@@ -57,9 +57,7 @@ namespace aprilx {
 
 namespace {
 
-using h4 = __attribute__((ext_vector_type(4))) _Float16;
 using h8 = __attribute__((ext_vector_type(8))) _Float16;
-__device__ __forceinline__ h4 to_h4(const f32x4 &v) { return h4{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w}; }
 
 template <int MT> struct PPGeom {
     static constexpr int NT = 8, NS = 3, NW = 8, NTH = 64 * NW;
@@ -286,28 +284,14 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs &g)
     {
         // ---- prologue (stages 0 and 1 are in flight): the rows' scales through the third buffer
         if (fold_scale) {
-            // partials (in registers since the first instruction of the kernel) -> LDS, BM threads add them in column order (the
-            // order of row_scale()); rows are padded to Gn + 1 floats (conflict-free column walks).  Staged in stage buffer 2,
-            // which takes its first DMA piece behind the barriers below.
-            const int Gn = rsc.groups;
+            // partials (in registers since the first instruction of the kernel) -> LDS, BM threads add them in column order
+            // (rows_scale_park / rows_scale_sum, epilogue.h).  Staged in stage buffer 2, which takes its first DMA piece behind the
+            // barriers below.
             float *part = reinterpret_cast<float *>(lds + 2 * G::STAGE_BYTES);
-            if (ppt <= STG) {
-#pragma unroll
-                for (int k = 0; k < STG; ++k) if (k < ppt && sj0 + k < Gn) part[srow * (Gn + 1) + sj0 + k] = stg[k];
-            } else {
-                for (int i = threadIdx.x; i < BM * Gn; i += NTH) {
-                    int r = m0 + i / Gn;
-                    if (r >= g.M) r = g.M - 1;
-                    part[(i / Gn) * (Gn + 1) + i % Gn] = gp(rsc.ssq)[(size_t)r * Gn + i % Gn];
-                }
-            }
+            rows_scale_park<BM, NTH>(part, rsc, ppt <= STG, stg, ppt, srow, sj0, m0, g.M, [](const float *p) { return *gp(p); });
             // (raw barriers: __syncthreads() would drain every DMA stage and the cell prefetch in flight)
             wait_lgkm0(); __builtin_amdgcn_s_barrier();
-            if (threadIdx.x < BM) {
-                float t = 0.0f;
-                for (int j = 0; j < Gn; ++j) t += part[threadIdx.x * (Gn + 1) + j];
-                scl[threadIdx.x] = __builtin_amdgcn_rsqf(t * rsc.inv_n + rsc.eps);
-            }
+            if (threadIdx.x < BM) scl[threadIdx.x] = rows_scale_sum(part + threadIdx.x * (rsc.groups + 1), rsc);
             wait_lgkm0(); __builtin_amdgcn_s_barrier();
 #pragma unroll
             for (int mt = 0; mt < MTW; ++mt)
@@ -447,10 +431,7 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs &g)
         for (int i = 0; i < QPT; ++i) {
             const int m = m0 + qrow0 + QRS * i;
             if (m < g.M) {
-                const f32x4 y = v[i] + l_bias;
-                f32x4 o;
-                o.x = y.x * fast_sigmoid(y.x - 1.0f); o.y = y.y * fast_sigmoid(y.y - 1.0f);
-                o.z = y.z * fast_sigmoid(y.z - 1.0f); o.w = y.w * fast_sigmoid(y.w - 1.0f);
+                const f32x4 o = dswish4(v[i] + l_bias);
                 if (g.out) *reinterpret_cast<__attribute__((address_space(1))) f32x4 *>(gp(g.out) + (size_t)m * g.ldo + ncol) = o;
                 if (g.out16) *reinterpret_cast<__attribute__((address_space(1))) h4 *>(gp(reinterpret_cast<_Float16 *>(g.out16)) + (size_t)m * g.ldo + ncol) = to_h4(o);
             }
@@ -459,13 +440,11 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs &g)
 #pragma unroll
         for (int i = 0; i < QPT; ++i) {
             const int m = m0 + qrow0 + QRS * i;
-            const f32x4 gt = v[i] + l_bias;
-            const float c_new = fast_sigmoid(gt.y) * l_cprev[i] + fast_sigmoid(gt.x) * fast_tanh(gt.z);
-            const float u = fast_sigmoid(gt.w) * fast_tanh(c_new);
+            const LstmCell cell = lstm_cell(v[i] + l_bias, l_cprev[i]);
             if (m < g.M) {
-                gp(g.c_state)[(size_t)l_slot[i] * g.hidden + l_unit] = c_new;
-                if (g.out) gp(g.out)[(size_t)m * g.ldo + l_unit] = u;
-                if (g.out16) gp(reinterpret_cast<_Float16 *>(g.out16))[(size_t)m * g.ldo + l_unit] = (_Float16)u;
+                gp(g.c_state)[(size_t)l_slot[i] * g.hidden + l_unit] = cell.c_new;
+                if (g.out) gp(g.out)[(size_t)m * g.ldo + l_unit] = cell.u;
+                if (g.out16) gp(reinterpret_cast<_Float16 *>(g.out16))[(size_t)m * g.ldo + l_unit] = (_Float16)cell.u;
             }
         }
     }
@@ -481,9 +460,9 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs &g)
 template <int MT, int EPI>
 __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs g)
 {
-    if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp, (blockIdx.x | blockIdx.y | blockIdx.z) == 0);
+    if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp);
     gemm_pp_body<MT, EPI>(g);
-    if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp, gridDim.x * gridDim.y * gridDim.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+    if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp);
 }
 
 // n independent same-shape problems in one launch (see gemm_f32_zkernel): blockIdx.z picks the argument block
@@ -491,9 +470,9 @@ template <int MT, int EPI>
 __global__ __launch_bounds__(512, 1) void gemm_pp_zkernel(const GemmArgs *__restrict__ zargs)
 {
     const GemmArgs g = zargs[blockIdx.z];
-    if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp, (blockIdx.x | blockIdx.y | blockIdx.z) == 0);
+    if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp);
     gemm_pp_body<MT, EPI>(g);
-    if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp, gridDim.x * gridDim.y * gridDim.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+    if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp);
 }
 
 template <int MT, int EPI>
@@ -501,18 +480,7 @@ void launch_pp_one(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream
 {
     using G = PPGeom<MT>;
     dim3 grid((unsigned)(g.N / G::BN), (unsigned)((g.M + G::BM - 1) / G::BM), (unsigned)(dev_args ? n : 1));
-    // dynamic LDS beyond 64 KB has to be announced, per instantiation AND per device (one engine per GPU)
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_pp_kernel<MT, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_pp_zkernel<MT, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_devs.fetch_or(bit, std::memory_order_release);
-    }
-    if (dev_args) APRIL_LAUNCH((gemm_pp_zkernel<MT, EPI>), grid, dim3(G::NTH), (size_t)G::LDS_BYTES, s, dev_args);
-    else APRIL_LAUNCH((gemm_pp_kernel<MT, EPI>), grid, dim3(G::NTH), (size_t)G::LDS_BYTES, s, g);
+    launch_gemm_pair<&gemm_pp_kernel<MT, EPI>, &gemm_pp_zkernel<MT, EPI>>(grid, dim3(G::NTH), (size_t)G::LDS_BYTES, true, s, g, dev_args);
 }
 
 }  // namespace

@@ -70,9 +70,7 @@ template <int N> __device__ __forceinline__ void wait_vm()
     __builtin_amdgcn_s_waitcnt(0x0F70 | (N & 15) | ((N >> 4) << 14));
 }
 
-using h4 = __attribute__((ext_vector_type(4))) _Float16;
 using h8 = __attribute__((ext_vector_type(8))) _Float16;
-__device__ __forceinline__ h4 to_h4(const f32x4 &v) { return h4{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w}; }
 
 template <int MT, int EPI, int WT, int NT = 4, int NWM = 2, int NWN = 2, int NSB = TILE_STAGES>
 __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int zg)
@@ -345,26 +343,12 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int zg)
     };
 
     // the rows' BasicNorm scales: partials (in registers since the first instruction of the kernel) -> LDS, BM threads add them in
-    // column order (the order of row_scale()); rows are padded to G + 1 floats (conflict-free column walks)
+    // column order (rows_scale_park / rows_scale_sum, epilogue.h)
     auto compute_scl = [&]() {
-        const int Gn = rsc.groups;
         float *part = scl + BM;
-        if (staged) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) if (k < ppt && sj0 + k < Gn) part[srow * (Gn + 1) + sj0 + k] = stg[k];
-        } else {
-            for (int i = threadIdx.x; i < BM * Gn; i += NTH) {
-                int r = m0 + i / Gn;
-                if (r >= g.M) r = g.M - 1;
-                part[(i / Gn) * (Gn + 1) + i % Gn] = rsc.ssq[(size_t)r * Gn + i % Gn];
-            }
-        }
+        rows_scale_park<BM, NTH>(part, rsc, staged, stg, ppt, srow, sj0, m0, g.M, [](const float *p) { return *p; });
         __syncthreads();
-        if (threadIdx.x < BM) {
-            float t = 0.0f;
-            for (int j = 0; j < Gn; ++j) t += part[threadIdx.x * (Gn + 1) + j];
-            scl[threadIdx.x] = __builtin_amdgcn_rsqf(t * rsc.inv_n + rsc.eps);
-        }
+        if (threadIdx.x < BM) scl[threadIdx.x] = rows_scale_sum(part + threadIdx.x * (rsc.groups + 1), rsc);
         __syncthreads();
     };
 
@@ -567,12 +551,11 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int zg)
             const int q = threadIdx.x + i * NTH;
             const int m = m0 + q / QROW, n = n0 + (q % QROW) * 4;
             if (e_ok[i]) {
-                const float rs = scl[q / QROW];
-                const f32x4 o = e_res[i] * rs + v[i];
-                *reinterpret_cast<f32x4 *>(g.state + (size_t)e_slot[i] * g.ld_state + n) = v[i];
-                *reinterpret_cast<f32x4 *>(g.out + (size_t)m * g.ldo + n) = o;
-                if (g.state16) *reinterpret_cast<h4 *>(reinterpret_cast<_Float16 *>(g.state16) + (size_t)e_slot[i] * g.ld_state + n) = to_h4(v[i]);
-                if (g.out16) *reinterpret_cast<h4 *>(reinterpret_cast<_Float16 *>(g.out16) + (size_t)m * g.ldo + n) = to_h4(o);
+                const HrTail t = hr_tail(v[i], e_res[i], scl[q / QROW]);
+                *reinterpret_cast<f32x4 *>(g.state + (size_t)e_slot[i] * g.ld_state + n) = t.state;
+                *reinterpret_cast<f32x4 *>(g.out + (size_t)m * g.ldo + n) = t.out;
+                if (g.state16) *reinterpret_cast<h4 *>(reinterpret_cast<_Float16 *>(g.state16) + (size_t)e_slot[i] * g.ld_state + n) = to_h4(t.state);
+                if (g.out16) *reinterpret_cast<h4 *>(reinterpret_cast<_Float16 *>(g.out16) + (size_t)m * g.ldo + n) = to_h4(t.out);
             }
         }
     } else if (EPI == EPI_RESID_SSQ) {
@@ -583,13 +566,12 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int zg)
             const bool ok = e_ok[i];
             f32x4 y = f32x4{0.f, 0.f, 0.f, 0.f};
             if (ok) {
-                y = v[i] + e_bias[i];
-                if (g.resid) y = e_res[i] + y;
+                y = resid_tail(v[i], e_bias[i], e_res[i], g.resid != nullptr);
                 *reinterpret_cast<f32x4 *>(g.out + (size_t)m * g.ldo + n) = y;
                 if (g.out16) *reinterpret_cast<h4 *>(reinterpret_cast<_Float16 *>(g.out16) + (size_t)m * g.ldo + n) = to_h4(y);
             }
-            const float ss = granule_ssq(y);               // all lanes take part in the shuffles
-            if (ok && (q & 7) == 0) g.ssq_out[(size_t)m * (g.N / SSQ_COLS) + n / SSQ_COLS] = ss;
+            float ss;                                      // (all lanes take part in the shuffles)
+            if (granule_ssq_store(y, ok, q, ss)) g.ssq_out[(size_t)m * (g.N / SSQ_COLS) + n / SSQ_COLS] = ss;
         }
     } else if (EPI == EPI_SLOT_STORE) {
 #pragma unroll
@@ -597,7 +579,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int zg)
             const int q = threadIdx.x + i * NTH;
             const int n = n0 + (q % QROW) * 4;
             if (e_ok[i])
-                *reinterpret_cast<f32x4 *>(g.out + (size_t)e_slot[i] * g.ldo + n) = NEED_SCL ? v[i] * scl[q / QROW] + e_bias[i] : v[i] + e_bias[i];
+                *reinterpret_cast<f32x4 *>(g.out + (size_t)e_slot[i] * g.ldo + n) = NEED_SCL ? slot_value(v[i], scl[q / QROW], e_bias[i]) : slot_value(v[i], e_bias[i]);
         }
     } else if (EPI == EPI_BIAS_DSWISH) {
 #pragma unroll
@@ -605,10 +587,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int zg)
             const int q = threadIdx.x + i * NTH;
             const int m = m0 + q / QROW, n = n0 + (q % QROW) * 4;
             if (q < NQ && m < g.M) {
-                const f32x4 y = v[i] + l_bias[i];
-                f32x4 o;
-                o.x = y.x * fast_sigmoid(y.x - 1.0f); o.y = y.y * fast_sigmoid(y.y - 1.0f);
-                o.z = y.z * fast_sigmoid(y.z - 1.0f); o.w = y.w * fast_sigmoid(y.w - 1.0f);
+                const f32x4 o = dswish4(v[i] + l_bias[i]);
                 if (g.out) *reinterpret_cast<f32x4 *>(g.out + (size_t)m * g.ldo + n) = o;
                 if (g.out16) *reinterpret_cast<h4 *>(reinterpret_cast<_Float16 *>(g.out16) + (size_t)m * g.ldo + n) = to_h4(o);
             }
@@ -617,13 +596,11 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int zg)
         // (every load this epilogue depends on was issued before the K loop: nothing below waits on memory while stores are in flight)
 #pragma unroll
         for (int i = 0; i < QPT; ++i) {
-            const f32x4 gt = v[i] + l_bias[i];
-            const float c_new = fast_sigmoid(gt.y) * l_cprev[i] + fast_sigmoid(gt.x) * fast_tanh(gt.z);
-            const float u = fast_sigmoid(gt.w) * fast_tanh(c_new);
+            const LstmCell cell = lstm_cell(v[i] + l_bias[i], l_cprev[i]);
             if (l_ok[i]) {
-                *l_cptr[i] = c_new;
-                if (g.out) g.out[(size_t)l_m[i] * g.ldo + l_unit[i]] = u;
-                if (g.out16) reinterpret_cast<_Float16 *>(g.out16)[(size_t)l_m[i] * g.ldo + l_unit[i]] = (_Float16)u;
+                *l_cptr[i] = cell.c_new;
+                if (g.out) g.out[(size_t)l_m[i] * g.ldo + l_unit[i]] = cell.u;
+                if (g.out16) reinterpret_cast<_Float16 *>(g.out16)[(size_t)l_m[i] * g.ldo + l_unit[i]] = (_Float16)cell.u;
             }
         }
     }
@@ -640,9 +617,9 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int zg)
 template <int MT, int EPI, int WT, int NT = 4, int NWM = 2, int NWN = 2, int NSB = TILE_STAGES>
 __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void gemm_tile_kernel(GemmArgs g)
 {
-    if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp, (blockIdx.x | blockIdx.y | blockIdx.z) == 0);
+    if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp);
     gemm_tile_body<MT, EPI, WT, NT, NWM, NWN, NSB>(g, (int)blockIdx.z);
-    if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp, gridDim.x * gridDim.y * gridDim.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+    if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp);
 }
 
 // n independent same-shape problems in one launch (see gemm_f32_zkernel): blockIdx.z / zdiv picks the argument block
@@ -651,15 +628,9 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void gemm_t
 {
     const int zl = (int)blockIdx.z / zdiv;
     const GemmArgs g = zargs[zl];
-    if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp, (blockIdx.x | blockIdx.y | blockIdx.z) == 0);
+    if constexpr (EPI == EPI_LSTM) stamp_begin(g.stamp);
     gemm_tile_body<MT, EPI, WT, NT, NWM, NWN, NSB>(g, (int)blockIdx.z - zl * zdiv);
-    if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp, gridDim.x * gridDim.y * gridDim.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-}
-
-template <class G> size_t tile_lds_bytes(const GemmArgs &g)
-{
-    const int sg = g.epi == EPI_HR ? g.r_scale.groups : ((g.epi == EPI_SLOT_STORE || g.epi == EPI_LSTM || g.epi == EPI_XPART) && g.x_scale.ssq ? g.x_scale.groups : 0);
-    return (size_t)G::LDS_MAIN + (size_t)(G::BM + (sg ? G::BM * (sg + 1) : 0)) * sizeof(float);
+    if constexpr (EPI == EPI_LSTM) stamp_end(g.stamp);
 }
 
 // fp16 operands: a stage is a few dozen SIMD cycles of MFMA against 12 .. 32 KB of DMA, so the depth of the DMA pipeline decides:
@@ -678,20 +649,8 @@ void launch_tile_one(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStre
     using G = TileGeom<MT, NT, NWM, NWN, NSB>;
     const int zdiv = g.kz / g.zs;
     dim3 grid((unsigned)(g.N / G::BN), (unsigned)((g.M + G::BM - 1) / G::BM), (unsigned)(zdiv * std::max(1, n)));
-    const size_t lds = tile_lds_bytes<G>(g);
-    // dynamic LDS beyond 64 KB has to be announced, per instantiation AND per device (one engine per GPU, each with its own
-    // stepping thread: a bit per device id, set after the attribute calls)
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tile_kernel<MT, EPI, WT, NT, NWM, NWN, NSB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tile_zkernel<MT, EPI, WT, NT, NWM, NWN, NSB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_devs.fetch_or(bit, std::memory_order_release);
-    }
-    if (dev_args) APRIL_LAUNCH((gemm_tile_zkernel<MT, EPI, WT, NT, NWM, NWN, NSB>), grid, dim3(G::NTH), lds, s, dev_args, zdiv);
-    else APRIL_LAUNCH((gemm_tile_kernel<MT, EPI, WT, NT, NWM, NWN, NSB>), grid, dim3(G::NTH), lds, s, g);
+    const size_t lds = (size_t)G::LDS_MAIN + scale_lds_floats(g, G::BM) * sizeof(float);
+    launch_gemm_pair<&gemm_tile_kernel<MT, EPI, WT, NT, NWM, NWN, NSB>, &gemm_tile_zkernel<MT, EPI, WT, NT, NWM, NWN, NSB>>(grid, dim3(G::NTH), lds, true, s, g, dev_args, zdiv);
 }
 
 template <int MT, int WT>

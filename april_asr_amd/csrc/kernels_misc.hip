@@ -12,10 +12,6 @@
 
 namespace aprilx {
 
-using h4 = __attribute__((ext_vector_type(4))) _Float16;
-__device__ __forceinline__ float sigmoid_dev(float x) { return fast_sigmoid(x); }
-__device__ __forceinline__ float dswish_dev(float y) { return y * sigmoid_dev(y - 1.0f); }
-
 // ---------------------------------------------------------------- row kernels
 // Small-batch path: finish the split-K GEMMs.  s[n] = balanced tree over the partial planes, then the mode-specific
 // tail -- the same arithmetic, in the same order, as the GEMM's fused row epilogues (EPI_HR / EPI_RESID_SSQ /
@@ -41,27 +37,26 @@ __device__ __forceinline__ void row_body(const RowArgs &r)
         if (ok) s = tree_sum4(r.ws, r.parts, r.m_stride, r.N, m, n);
         if (MODE == ROW_HR) {
             if (ok) {
-                const f32x4 y = *reinterpret_cast<const f32x4 *>(r.resid + (size_t)m * r.ldr + n);
-                const f32x4 o = y * rs + s;
-                *reinterpret_cast<f32x4 *>(r.state + (size_t)slot * r.ld_state + n) = s;
-                *reinterpret_cast<f32x4 *>(r.out + (size_t)m * r.ldo + n) = o;
-                if (r.state16) *reinterpret_cast<h4 *>(reinterpret_cast<_Float16 *>(r.state16) + (size_t)slot * r.ld_state + n) = h4{(_Float16)s.x, (_Float16)s.y, (_Float16)s.z, (_Float16)s.w};
-                if (r.out16) *reinterpret_cast<h4 *>(reinterpret_cast<_Float16 *>(r.out16) + (size_t)m * r.ldo + n) = h4{(_Float16)o.x, (_Float16)o.y, (_Float16)o.z, (_Float16)o.w};
+                const HrTail t = hr_tail(s, *reinterpret_cast<const f32x4 *>(r.resid + (size_t)m * r.ldr + n), rs);
+                *reinterpret_cast<f32x4 *>(r.state + (size_t)slot * r.ld_state + n) = t.state;
+                *reinterpret_cast<f32x4 *>(r.out + (size_t)m * r.ldo + n) = t.out;
+                if (r.state16) *reinterpret_cast<h4 *>(reinterpret_cast<_Float16 *>(r.state16) + (size_t)slot * r.ld_state + n) = to_h4(t.state);
+                if (r.out16) *reinterpret_cast<h4 *>(reinterpret_cast<_Float16 *>(r.out16) + (size_t)m * r.ldo + n) = to_h4(t.out);
             }
         } else if (MODE == ROW_RESID_SSQ) {
             f32x4 y = f32x4{0.f, 0.f, 0.f, 0.f};
             if (ok) {
-                y = s + *reinterpret_cast<const f32x4 *>(r.bias + n);
-                if (r.resid) y = *reinterpret_cast<const f32x4 *>(r.resid + (size_t)m * r.ldr + n) + y;
+                const f32x4 res = r.resid ? *reinterpret_cast<const f32x4 *>(r.resid + (size_t)m * r.ldr + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+                y = resid_tail(s, *reinterpret_cast<const f32x4 *>(r.bias + n), res, r.resid != nullptr);
                 *reinterpret_cast<f32x4 *>(r.out + (size_t)m * r.ldo + n) = y;
-                if (r.out16) *reinterpret_cast<h4 *>(reinterpret_cast<_Float16 *>(r.out16) + (size_t)m * r.ldo + n) = h4{(_Float16)y.x, (_Float16)y.y, (_Float16)y.z, (_Float16)y.w};
+                if (r.out16) *reinterpret_cast<h4 *>(reinterpret_cast<_Float16 *>(r.out16) + (size_t)m * r.ldo + n) = to_h4(y);
             }
-            const float ss = granule_ssq(y);           // every lane takes part in the shuffles
-            if (ok && (q & 7) == 0) r.ssq_out[(size_t)m * (r.N / SSQ_COLS) + n / SSQ_COLS] = ss;
+            float ss;                                  // (every lane takes part in the shuffles)
+            if (granule_ssq_store(y, ok, q, ss)) r.ssq_out[(size_t)m * (r.N / SSQ_COLS) + n / SSQ_COLS] = ss;
         } else {   // ROW_SLOT_STORE
             if (ok) {
                 const f32x4 b = *reinterpret_cast<const f32x4 *>(r.bias + n);
-                *reinterpret_cast<f32x4 *>(r.out + (size_t)slot * r.ldo + n) = scaled ? s * rs + b : s + b;
+                *reinterpret_cast<f32x4 *>(r.out + (size_t)slot * r.ldo + n) = scaled ? slot_value(s, rs, b) : slot_value(s, b);
             }
         }
     }
@@ -402,7 +397,7 @@ __global__ __launch_bounds__(256) void conv12_kernel(ConvEmbedArgs a)
 #pragma unroll
             for (int k = 0; k < 9; ++k) acc += patch[k] * w[k];
             acc += a.b[0][c];
-            a1[c * H1 * W1 + p] = dswish_dev(acc);
+            a1[c * H1 * W1 + p] = dswish(acc);
         }
     }
     __syncthreads();
@@ -440,7 +435,7 @@ __global__ __launch_bounds__(256) void conv12_kernel(ConvEmbedArgs a)
                 for (int cc = 0; cc < 8; ++cc)
                     if (cc < cps) {
                         const int cl = sub * cps + cc;
-                        a2[cl * NP + p] = dswish_dev(acc[cc] + a.b[1][grp * cg + cl]);
+                        a2[cl * NP + p] = dswish(acc[cc] + a.b[1][grp * cg + cl]);
                     }
             }
         }
@@ -517,10 +512,10 @@ __global__ __launch_bounds__(256) void conv12_wide_kernel(ConvEmbedArgs a)
                 lo = lo + pk * f32x2{w.x, w.y};
                 hi = hi + pk * f32x2{w.z, w.w};
             }
-            a1[(cq + 0) * H1 * W1 + p] = dswish_dev(lo.x + a.b[0][cq + 0]);
-            a1[(cq + 1) * H1 * W1 + p] = dswish_dev(lo.y + a.b[0][cq + 1]);
-            a1[(cq + 2) * H1 * W1 + p] = dswish_dev(hi.x + a.b[0][cq + 2]);
-            a1[(cq + 3) * H1 * W1 + p] = dswish_dev(hi.y + a.b[0][cq + 3]);
+            a1[(cq + 0) * H1 * W1 + p] = dswish(lo.x + a.b[0][cq + 0]);
+            a1[(cq + 1) * H1 * W1 + p] = dswish(lo.y + a.b[0][cq + 1]);
+            a1[(cq + 2) * H1 * W1 + p] = dswish(hi.x + a.b[0][cq + 2]);
+            a1[(cq + 3) * H1 * W1 + p] = dswish(hi.y + a.b[0][cq + 3]);
         }
     }
     __syncthreads();
@@ -558,8 +553,8 @@ __global__ __launch_bounds__(256) void conv12_wide_kernel(ConvEmbedArgs a)
 #pragma unroll
             for (int q = 0; q < CPS / 2; ++q) {
                 const int cl = cbase + 2 * q;
-                a2[cl * NP + pq] = dswish_dev(acc[q].x + a.b[1][cl]);
-                a2[(cl + 1) * NP + pq] = dswish_dev(acc[q].y + a.b[1][cl + 1]);
+                a2[cl * NP + pq] = dswish(acc[q].x + a.b[1][cl]);
+                a2[(cl + 1) * NP + pq] = dswish(acc[q].y + a.b[1][cl + 1]);
             }
         }
     }

@@ -75,7 +75,8 @@ __device__ __forceinline__ void plane_store(float *plane, int lane, const f32x4 
 }
 
 // the rows' BasicNorm scales (RowScale): threads 0..63 (row = t / 4) fetch eight sum-of-squares partials each before the weight
-// stream, park them in LDS after it; row_scale_sum adds a row's partials in column order (the order of row_scale())
+// stream, park them in LDS after it (<= 16 rows from one wave, a fixed row pitch: a form of its own, not rows_scale_park); a row's
+// partials are added in the shared column order, by the shared function (rows_scale_sum, epilogue.h)
 constexpr int MAX_GROUPS = 32;
 struct ScalePart { float v[MAX_GROUPS / 4]; };
 __device__ __forceinline__ void scale_fetch(const RowScale &rs, int M, ScalePart &sp)
@@ -91,12 +92,7 @@ __device__ __forceinline__ void scale_park(float *part, const ScalePart &sp)
 #pragma unroll
     for (int k = 0; k < MAX_GROUPS / 4; ++k) part[row * (MAX_GROUPS + 1) + q * (MAX_GROUPS / 4) + k] = sp.v[k];
 }
-__device__ __forceinline__ float row_scale_sum(const float *part, int row, const RowScale &rs)
-{
-    float t = 0.0f;
-    for (int j = 0; j < rs.groups; ++j) t += part[row * (MAX_GROUPS + 1) + j];
-    return __builtin_amdgcn_rsqf(t * rs.inv_n + rs.eps);
-}
+__device__ __forceinline__ float row_scale_sum(const float *part, int row, const RowScale &rs) { return rows_scale_sum(part + row * (MAX_GROUPS + 1), rs); }
 
 // ---- the fused-epilogue GEMMs whose K is one slab (kz = 1, four chunks), four waves per workgroup:
 //   CF_GATES_H  gates, recurrent half (wave_mask 0b1100, p_add): 2 tiles x chunks 2, 3;  ((P + c2) + c3) + bias, LSTM cell
@@ -159,25 +155,22 @@ __device__ __forceinline__ void recur_cell_body(const GemmArgs &g)
         const float *pl = red + (HALF ? 2 * et : 0) * RPLANE + o;           // the tile's planes, in chunk order
         const f32x4 pa = *reinterpret_cast<const f32x4 *>(pl), pb = *reinterpret_cast<const f32x4 *>(pl + RPLANE);
         if (FORM == CF_XPART) {
-            const f32x4 x = scaled ? (pa + pb) * row_scale_sum(part, erow, g.x_scale) : (pa + pb);
+            const f32x4 x = scaled ? gate_xin(pa, pb, row_scale_sum(part, erow, g.x_scale)) : (pa + pb);
             if (e_ok) gstore<f32x4>(g.out + (size_t)erow * g.ldo + en, x);
         } else if (FORM == CF_DSWISH) {
             const f32x4 y = (((pa + pb) + *reinterpret_cast<const f32x4 *>(pl + 2 * RPLANE)) + *reinterpret_cast<const f32x4 *>(pl + 3 * RPLANE)) + ebias;
-            f32x4 v;
-            v.x = y.x * fast_sigmoid(y.x - 1.0f); v.y = y.y * fast_sigmoid(y.y - 1.0f);
-            v.z = y.z * fast_sigmoid(y.z - 1.0f); v.w = y.w * fast_sigmoid(y.w - 1.0f);
+            const f32x4 v = dswish4(y);
             if (e_ok) gstore<f32x4>(g.out + (size_t)erow * g.ldo + en, v);
         } else {
             f32x4 gt;
-            if (FORM == CF_GATES_H) gt = ((xin + pa) + pb) + ebias;
+            if (FORM == CF_GATES_H) gt = gate_combine(xin, pa, pb, ebias);      // (the tile's planes are chunks 2 and 3)
             else {
                 const f32x4 p2 = *reinterpret_cast<const f32x4 *>(pl + 2 * RPLANE), p3 = *reinterpret_cast<const f32x4 *>(pl + 3 * RPLANE);
-                if (scaled) gt = (((pa + pb) * row_scale_sum(part, erow, g.x_scale) + p2) + p3) + ebias;
-                else gt = (((pa + pb) + p2) + p3) + ebias;
+                if (scaled) gt = gate_combine(gate_xin(pa, pb, row_scale_sum(part, erow, g.x_scale)), p2, p3, ebias);
+                else gt = gate_combine(pa + pb, p2, p3, ebias);
             }
-            const float c_new = fast_sigmoid(gt.y) * cprev + fast_sigmoid(gt.x) * fast_tanh(gt.z);
-            const float u = fast_sigmoid(gt.w) * fast_tanh(c_new);
-            if (e_ok) { gstore<float>(cptr, c_new); gstore<float>(g.out + (size_t)erow * g.ldo + eunit, u); }
+            const LstmCell cell = lstm_cell(gt, cprev);
+            if (e_ok) { gstore<float>(cptr, cell.c_new); gstore<float>(g.out + (size_t)erow * g.ldo + eunit, cell.u); }
         }
     }
 }
@@ -241,20 +234,19 @@ __device__ __forceinline__ void recur_row_body(const GemmArgs &g)
         else if (g.kz == 2) v = slab(0) + slab(1);
         else v = slab(0);
         if (FORM == RF_HR) {
-            const float rs = row_scale_sum(part, erow, g.r_scale);
+            const HrTail t = hr_tail(v, eres, row_scale_sum(part, erow, g.r_scale));
             if (e_ok) {
-                gstore<f32x4>(g.state + (size_t)eslot * g.ld_state + en, v);
-                gstore<f32x4>(g.out + (size_t)erow * g.ldo + en, eres * rs + v);
+                gstore<f32x4>(g.state + (size_t)eslot * g.ld_state + en, t.state);
+                gstore<f32x4>(g.out + (size_t)erow * g.ldo + en, t.out);
             }
         } else {
             f32x4 y = f32x4{0.f, 0.f, 0.f, 0.f};
             if (e_ok) {
-                y = v + ebias;
-                if (g.resid) y = eres + y;
+                y = resid_tail(v, ebias, eres, g.resid != nullptr);
                 gstore<f32x4>(g.out + (size_t)erow * g.ldo + en, y);
             }
-            const float ss = granule_ssq(y);                             // all lanes of waves 0 and 1 take part in the shuffles
-            if (e_ok && eq == 0) gstore<float>(g.ssq_out + (size_t)erow * (g.N / SSQ_COLS) + en / SSQ_COLS, ss);
+            float ss;                                                    // (all lanes of waves 0 and 1 take part in the shuffles)
+            if (granule_ssq_store(y, e_ok, eq, ss)) gstore<float>(g.ssq_out + (size_t)erow * (g.N / SSQ_COLS) + en / SSQ_COLS, ss);
         }
     }
 }
@@ -293,7 +285,7 @@ void launch_cell(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t
     constexpr int TPW = (FORM == CF_GATES_H || FORM == CF_XPART) ? 2 : 1;
     const dim3 grid((unsigned)(g.N / (16 * TPW)), (unsigned)(dev_args ? n : 1), 1);
     switch (g.K / 64) {
-#define X(tb) case tb: if (dev_args) hipLaunchKernelGGL((recur_cell_zkernel<tb, FORM>), grid, dim3(256), 0, s, dev_args); else hipLaunchKernelGGL((recur_cell_kernel<tb, FORM>), grid, dim3(256), 0, s, g); return;
+#define X(tb) case tb: launch_gemm_pair<&recur_cell_kernel<tb, FORM>, &recur_cell_zkernel<tb, FORM>>(grid, dim3(256), 0, false, s, g, dev_args); return;
     APRIL_RECUR_CELL_TB(X)
 #undef X
     }
@@ -309,20 +301,7 @@ void launch_row(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t 
     const dim3 grid((unsigned)(g.N / (16 * NTILE)), (unsigned)(dev_args ? n : 1), 1);
     const size_t lds = ((size_t)chains * RPLANE + 16 * (MAX_GROUPS + 1)) * sizeof(float);
     switch (g.K / 16 / (4 * g.kz) * (chains / nw)) {
-#define X(tb) case tb: { \
-        if (lds > 64 * 1024) {      /* dynamic LDS beyond 64 KB has to be announced, per instantiation and device */ \
-            static std::atomic<uint64_t> attr_devs{0}; \
-            int dev = 0; (void)hipGetDevice(&dev); \
-            const uint64_t bit = 1ull << (dev & 63); \
-            if (!(attr_devs.load(std::memory_order_acquire) & bit)) { \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&recur_row_kernel<tb, FORM>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&recur_row_zkernel<tb, FORM>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                attr_devs.fetch_or(bit, std::memory_order_release); \
-            } \
-        } \
-        if (dev_args) hipLaunchKernelGGL((recur_row_zkernel<tb, FORM>), grid, dim3(64 * nw), lds, s, dev_args); \
-        else hipLaunchKernelGGL((recur_row_kernel<tb, FORM>), grid, dim3(64 * nw), lds, s, g); \
-        return; }
+#define X(tb) case tb: launch_gemm_pair<&recur_row_kernel<tb, FORM>, &recur_row_zkernel<tb, FORM>>(grid, dim3(64 * nw), lds, lds > 64 * 1024, s, g, dev_args); return;
     APRIL_RECUR_ROW_TB(X)
 #undef X
     }

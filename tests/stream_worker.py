@@ -28,9 +28,12 @@ def main():
     grp = A.SessionGroup(sess)
     pcm = [SM.lcg_pcm16(feed * steps, seed=4242 + i) for i in range(nsess)]
     grp.plan(pcm, feed)
-    prof = int(os.environ.get("APRIL_TEST_PROFILE", "0"))      # 2: the gates clock from the 5th feed on (aprilx_model_profile(model, 2))
+    # 2: the gates clock (aprilx_model_profile(model, 2)), 1: launches one by one with their times per class; from the 5th feed on, or
+    # from feed APRIL_TEST_PROFILE_FROM
+    prof = int(os.environ.get("APRIL_TEST_PROFILE", "0"))
+    prof_from = int(os.environ.get("APRIL_TEST_PROFILE_FROM", "4"))
     for k in range(steps):
-        if prof and k == 4:
+        if prof and k == prof_from:
             grp.drain()
             m.profile(prof)
         if mode == "sync":
@@ -42,6 +45,7 @@ def main():
         m.profile(0)
         sg = m.stats()
         print("GCLOCK", int(sg.gates_clock_launches), "%.4f" % float(sg.gates_clock_ms), int(sg.gates_clock_rows), flush=True)
+        print("KSTATS", " ".join("%d %.6f" % (int(sg.kernel_launches[i]), float(sg.kernel_ms[i])) for i in range(6)), flush=True)
     lat = m.feed_latencies(reset=True)          # hand-over -> delivery per tick (aprilx_model_feed_latency), before the flush
     if flush:
         grp.flush()

@@ -124,3 +124,33 @@ def test_gates_clock_times_replayed_launches_and_changes_nothing(built, v0_model
     assert launches >= 8 * 13, clk
     assert rows % 64 == 0 and rows // 64 >= 8 * 2 * 12, clk
     assert 1e-3 * launches < ms < 1.0 * launches, clk                                        # 1 us .. 1 ms per launch
+
+
+def test_profile_1_times_the_gates_of_one_session(built, tiny_model):
+    """aprilx_model_profile(model, 1) at one session, one second of audio: the gates GEMMs are the stream kernels of
+    csrc/kernels_recur.hip (<= 16 rows), and like every GEMM they take the parked event pair into their dispatch packet, so class 0
+    (gates) of stats().kernel_ms / kernel_launches is filled -- with as many launches as the same feed counts on the general kernels
+    (APRIL_RECUR_KERNELS=0) -- and the callbacks are those of the unprofiled run."""
+    path = tiny_model["path"]
+
+    def worker(**env):
+        e = dict(os.environ, APRIL_MAX_SESSIONS="512", APRIL_MAX_BATCH="2048")
+        e.update({k: str(v) for k, v in env.items()})
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "stream_worker.py"), path, "1", "10", "sync", "1600", "1"],
+                           env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        out = r.stdout.decode().splitlines()
+        dig = [ln for ln in out if ln.startswith("DIGEST")][-1].split()
+        ks = [ln for ln in out if ln.startswith("KSTATS")]
+        return dig, (ks[-1].split() if ks else None)
+
+    off, _ = worker()
+    on, ks = worker(APRIL_TEST_PROFILE=1, APRIL_TEST_PROFILE_FROM=0)
+    gen, ks_gen = worker(APRIL_TEST_PROFILE=1, APRIL_TEST_PROFILE_FROM=0, APRIL_RECUR_KERNELS=0)
+    launches, ms = int(ks[1]), float(ks[2])
+    print("gates under profile(1): %d launches, %.4f ms; general kernels: %s launches" % (launches, ms, ks_gen[1]))
+    assert int(off[2]) > 0 and int(off[3]) == 0 and int(on[3]) == 0
+    assert launches > 0 and ms > 0.0, ks
+    assert launches == int(ks_gen[1]), (ks, ks_gen)
+    assert on[1] == off[1] and on[2] == off[2], "callbacks differ with profiling on"
+    assert gen[1] == off[1], "callbacks differ between the stream kernels and the general kernels"
