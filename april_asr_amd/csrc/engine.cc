@@ -269,6 +269,8 @@ Engine::Engine(const EngineConfig &cfg, const PackedLayout &layout, const float 
 
     upload_tables(ft);
     use_graphs_ = env_int("APRIL_NO_GRAPHS", 0) == 0;
+    if (const int n = env_int("APRIL_GRAPH_CACHE_CAP", 0))        // tests: every family of captured chains is emptied early (a both-parity capture inserts two entries)
+        step_graphs_.cap = lm_graphs_.cap = lm_search_graphs_.cap = sw_plan_cap_ = (size_t)std::max(n, 2), sw_graphs_.cap = 4 * sw_plan_cap_;
     free_.reserve(S);
     for (int i = cfg_.max_slots - 1; i >= 0; --i) free_.push_back(i);
     LOGI("engine: device %d, %d slots, max batch %d, weights %.1f MB, kz(embed,hr,ff2,proj,out)=%d,%d,%d,%d,%d",
@@ -350,10 +352,7 @@ Engine::~Engine()
     if (trace_base_) (void)hipEventDestroy(trace_base_);
     for (hipEvent_t e : join_ev_) (void)hipEventDestroy(e);
     for (auto &e : ev_pool_) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    for (auto &g : step_graphs_) (void)hipGraphExecDestroy(g.second);
-    for (auto &g : lm_graphs_) (void)hipGraphExecDestroy(g.second);
-    for (auto &g : lm_search_graphs_) (void)hipGraphExecDestroy(g.second);
-    for (auto &p : sw_plans_) { if (p.second.graph) (void)hipGraphExecDestroy(p.second.graph); for (hipGraphExec_t x : p.second.g3) if (x) (void)hipGraphExecDestroy(x); if (p.second.dev) (void)hipFree(p.second.dev); if (p.second.rdev) (void)hipFree(p.second.rdev); }
+    drop_graphs(); free_sw_plans(); if (gclk_slots_) (void)hipFree(gclk_slots_);
     if (lm_stream_) { (void)hipStreamSynchronize(lm_stream_); (void)hipStreamDestroy(lm_stream_); }
     for (hipEvent_t e : lm_events_) (void)hipEventDestroy(e);
     if (zargs_h_) { (void)hipHostFree(zargs_h_); (void)hipFree(zargs_d_); }
@@ -495,6 +494,29 @@ template <typename Chain> static hipGraphExec_t capture_graph(hipStream_t st, Ch
     return exec;
 }
 
+void GraphCache::clear()
+{
+    if (!map_.empty()) LOGI("engine: %s graphs emptied (%zu entries)", name, map_.size());
+    for (auto &g : map_) (void)hipGraphExecDestroy(g.second);
+    map_.clear(); uses_.clear();
+}
+
+// the family's graph for `key`, captured now when it is missing (the caller has made room)
+template <typename Chain> hipGraphExec_t Engine::cached_graph(GraphCache &cache, const GraphCache::Key &key, hipStream_t st, Chain &&chain)
+{
+    if (!cache.find(key)) cache.insert(key, capture_graph(st, chain));
+    return cache.find(key);
+}
+
+// A chain that is captured at its second use is captured for BOTH flight parities (the parity selects buffers): which parity a shape meets depends
+// on the history of flights (feeds alternate between 2 and 3 chunks, parities alternate too, one merged or empty flight flips the pairing), and a capture in
+// mid-stream is a 3 ms hiccup.  `capture` runs once per parity and fills the cache (cached_graph): the other parity first, this one last, so the member pointers end where they were.
+template <typename Capture> void Engine::capture_both_parities(Capture &&capture)
+{
+    const int par = flight_parity_;
+    for (int q : {1 - par, par}) { select_parity(q); capture(); }
+}
+
 // ---------------------------------------------------------------- streams
 // Three in-order streams.  stream_ (M) carries the layer chain and every launch of the general paths; f_stream_ (F) the PCM
 // upload and the fbank kernel of every flight and, for a feed that runs as a split wavefront (lm_step mode 1), its index fetch
@@ -575,21 +597,22 @@ void Engine::set_gates_clock(bool on)
         gclk_ = true;
         return;
     }
-    if (gclk_ && gclk_slots_) {
-        // every plan built while the clock was on: its slots' sums (10 ns ticks of s_memrealtime) and launch counts
-        std::vector<unsigned long long> h((size_t)GCLK_SLOTS * STAMP_WORDS);
-        HIP_CHECK(hipMemcpyAsync(h.data(), gclk_slots_, h.size() * 8, hipMemcpyDeviceToHost, stream_));
-        HIP_CHECK(hipStreamSynchronize(stream_));
-        for (auto &kv : sw_plans_)
-            for (size_t i = 0; i < kv.second.stamp_slots.size(); ++i) {
-                const auto &sl = kv.second.stamp_slots[i];
-                const unsigned long long ticks = h[(size_t)sl.first * STAMP_WORDS + 2], n = h[(size_t)sl.first * STAMP_WORDS + 3];
-                gclk_ms_ += (double)ticks * 1e-5; gclk_launches_ += (long)n; gclk_rows_ += (long)n * sl.second;
-                const int bn = std::min(std::max(kv.second.stamp_n[i], 1), 4) - 1;
-                gclk_ms_n_[bn] += (double)ticks * 1e-5; gclk_launches_n_[bn] += (long)n;
-            }
-    }
-    gclk_ = false;
+    collect_gates_clock(); gclk_ = false;
+}
+// every plan built while the clock was on: its slots' sums (10 ns ticks of s_memrealtime) and launch counts (clock switched off; plans about to be discarded)
+void Engine::collect_gates_clock()
+{
+    if (!gclk_ || !gclk_slots_) return;
+    std::vector<unsigned long long> h((size_t)GCLK_SLOTS * STAMP_WORDS);
+    HIP_CHECK(hipMemcpyAsync(h.data(), gclk_slots_, h.size() * 8, hipMemcpyDeviceToHost, stream_)); HIP_CHECK(hipStreamSynchronize(stream_));
+    for (auto &kv : sw_plans_)
+        for (size_t i = 0; i < kv.second.stamp_slots.size(); ++i) {
+            const auto &sl = kv.second.stamp_slots[i];
+            const unsigned long long ticks = h[(size_t)sl.first * STAMP_WORDS + 2], n = h[(size_t)sl.first * STAMP_WORDS + 3];
+            gclk_ms_ += (double)ticks * 1e-5; gclk_launches_ += (long)n; gclk_rows_ += (long)n * sl.second;
+            const int bn = std::min(std::max(kv.second.stamp_n[i], 1), 4) - 1;
+            gclk_ms_n_[bn] += (double)ticks * 1e-5; gclk_launches_n_[bn] += (long)n;
+        }
 }
 void Engine::timed_begin(int cls)
 {
@@ -1157,13 +1180,9 @@ void Engine::run_lm_wavefront(int m, int T, bool dump_logits)
                 }
             };
             if (!use_graphs_ || dump_logits) { search(); continue; }
-            const std::pair<int, int> key(m * 2 + flight_parity_, len);      // (round flags and encoder outputs are per flight parity)
-            auto it = lm_search_graphs_.find(key);
-            if (it == lm_search_graphs_.end()) {
-                if (lm_search_graphs_.size() >= 64) { HIP_CHECK(hipStreamSynchronize(stream_)); /* execs launched earlier in this flight may still run */ for (auto &g : lm_search_graphs_) (void)hipGraphExecDestroy(g.second); lm_search_graphs_.clear(); }
-                it = lm_search_graphs_.emplace(key, capture_graph(stream_, search)).first;
-            }
-            HIP_CHECK(hipGraphLaunch(it->second, stream_));
+            const GraphCache::Key key = graph_key(m, len);       // (round flags and encoder outputs are per flight parity)
+            if (!lm_search_graphs_.find(key) && lm_search_graphs_.full()) { HIP_CHECK(hipStreamSynchronize(stream_)); /* execs launched earlier in this flight may still run */ lm_search_graphs_.clear(); }
+            HIP_CHECK(hipGraphLaunch(cached_graph(lm_search_graphs_, key, stream_, search), stream_));
             lap(5);
         }
     }
@@ -1190,16 +1209,15 @@ static bool lm_gates_split_on()
 
 Engine::SwPlan &Engine::sw_plan(int m, int T)
 {
-    // (the argument blocks point into the parity's buffers; plans built under the gates clock carry stamp slots and are kept apart:
-    // negative m)
-    const std::pair<int, int> key(gclk_ ? -m : m, T * 2 + flight_parity_);
+    const GraphCache::Key key = sw_key(m, T);         // (the argument blocks point into the parity's buffers)
     auto it = sw_plans_.find(key);
     if (it != sw_plans_.end()) return it->second;
-    if (sw_plans_.size() >= 64) {
+    if (sw_plans_.size() >= sw_plan_cap_) {
         sync();
         HipLegacyLock evict_guard;                    // (see fbank())
-        for (auto &p : sw_plans_) { if (p.second.graph) (void)hipGraphExecDestroy(p.second.graph); for (hipGraphExec_t x : p.second.g3) if (x) (void)hipGraphExecDestroy(x); if (p.second.dev) (void)hipFree(p.second.dev); if (p.second.rdev) (void)hipFree(p.second.rdev); }
-        sw_plans_.clear();
+        collect_gates_clock(); free_sw_plans();       // the stamp slots of the clocked plans go with them: their sums first, ...
+        if (gclk_slots_) { HIP_CHECK(hipMemsetAsync(gclk_slots_, 0, (size_t)GCLK_SLOTS * STAMP_WORDS * 8, stream_)); HIP_CHECK(hipStreamSynchronize(stream_)); }
+        gclk_used_ = 0;                               // ... then every slot is free again
     }
     SwPlan &p = sw_plans_[key];
     const NetDims &d = L_.dims;
@@ -1250,6 +1268,8 @@ Engine::SwPlan &Engine::sw_plan(int m, int T)
                     p.stamp_slots.push_back(std::make_pair(gclk_used_, (long)m * gn)); p.stamp_n.push_back(gn);
                     for (int i = 0; i < gn; ++i) items[first + (size_t)i].stamp = gclk_slots_ + (size_t)gclk_used_ * STAMP_WORDS;
                     ++gclk_used_;
+                } else if (kind == 0 && gclk_ && gclk_slots_ && !gclk_warned_) {
+                    gclk_warned_ = true; LOGW("engine: the gates clock is out of stamp slots (%d): the gates launches of further plans are not timed", GCLK_SLOTS);
                 }
                 SwPlan::Batch b; b.off = p.host.size(); b.n = gn; b.macro = W; b.kind = kind; b.roff = p.rhost.size(); b.rn = gi == 0 ? (int)rows.size() : 0;
                 p.host.resize(p.host.size() + (size_t)gn);
@@ -1269,6 +1289,13 @@ Engine::SwPlan &Engine::sw_plan(int m, int T)
         HIP_CHECK(hipMemcpyAsync(p.rdev, p.rhost.data(), p.rhost.size() * sizeof(RowArgs), hipMemcpyHostToDevice, stream_));
     }
     return p;
+}
+
+void Engine::free_sw_plans()
+{
+    if (!sw_plans_.empty()) LOGI("engine: feed wavefront plans emptied (%zu plans)", sw_plans_.size());
+    for (auto &p : sw_plans_) { if (p.second.dev) (void)hipFree(p.second.dev); if (p.second.rdev) (void)hipFree(p.second.rdev); }
+    sw_graphs_.clear(); sw_plans_.clear();
 }
 
 // part 0: index fetch + front end (stream fe), 1: the layer wavefront + encoder_proj (stream ly), 2: the searches (stream sr);
@@ -1320,114 +1347,96 @@ int Engine::lm_step(int m, int T, const int *slots, const int *ring_tails, const
         for (int i = 0; i < 3; ++i) HIP_CHECK(hipEventCreateWithFlags(&zargs_done_[i], hipEventDisableTiming));
         lm_now_d_ = dmalloc<int>((size_t)cfg_.max_batch); lm_rows_d_ = dmalloc<int>((size_t)cfg_.max_batch); lm_rec_off_d_ = dmalloc<int>(1);
     }
-    const int k = next_step_index();
-    int *blk = ring_h_ + ring_pos_;
-    memcpy(blk, slots, (size_t)m * 4);
-    memcpy(blk + m, ring_tails, (size_t)rows * 4);
-    memcpy(blk + m + rows, now_ms, (size_t)rows * 4);
-    for (int t = 0; t < T; ++t) memcpy(blk + m + 2 * rows + (size_t)t * m, slots, (size_t)m * 4);
-    step_off_h_[k] = (int)ring_pos_; rec_off_h_[k] = (int)rec_pos_;
-    ring_pos_ += (size_t)m + 3 * (size_t)rows; rec_pos_ += (size_t)3 * rows;
-    if (conf_k_h_) note_conf_step(k, slots, m, (size_t)3 * rows);
+    const int k = stage_step(m, T, slots, ring_tails, now_ms);
     std::lock_guard<std::mutex> cg(capture_mu_);
-    if (mode == 1) {                 // the chunk steps of one feed as a wavefront over the layers (run_sw_chain)
-        // a shape is captured into graphs the SECOND time it is seen (by either flight parity): capturing costs a few
-        // milliseconds, which a batch shape that occurs once (sessions joining and leaving) never earns back; its launches go
-        // out one by one (~0.25 ms of host time).  When it is captured, it is captured for BOTH parities: which parity a shape
-        // meets depends on the history of flights (feeds alternate between 2 and 3 chunks, parities alternate too, and one merged
-        // or empty flight flips the pairing), and a capture in the middle of a stream is a 3 ms hiccup.
-        const int par = flight_parity_;
-        sw_plan(m, T);
-        SwPlan *pp = &sw_plans_.find(std::make_pair(gclk_ ? -m : m, T * 2 + par))->second;
-        int &uses = sw_uses_[std::make_pair(m, T)];
-        const bool graphs = use_graphs_ && !profiling_ && !logits_out && (pp->graph || pp->g3[0] || ++uses >= 2);
-        // (split: only the FIRST step of a flight: the per-parity buffers keep neighbouring FLIGHTS apart, a second step of the same
-        // flight -- a flush runs several -- would have its index fetch and front end overwrite what the first step's layers and
-        // search still read; it takes the one-stream path, behind everything the first step put on F and S)
-        // (gates clock on: one stream for everything, so that no other stream's kernel shares the CUs with a gates launch while it times itself;
-        // the feeds still arrive pipelined, the GPU stays busy and at speed)
-        const bool split = graphs && split_streams_ > 0 && overlap_hint_ && flight_steps_ == 1 && !gclk_;
-        hipStream_t fe = split_streams_ >= 2 ? f_stream_ : stream_;
-        if (graphs && (split ? !pp->g3[0] : !pp->graph)) {
-            for (int k2 = 0; k2 < 2; ++k2) {
-                const int q = k2 == 0 ? 1 - par : par;          // the other parity first, this one last (the member pointers end where they were)
-                select_parity(q);
-                SwPlan &pl = sw_plan(m, T);
-                if (split) {
-                    if (pl.g3[0]) continue;
-                    hipStream_t on[3] = {fe, stream_, s_stream_};
-                    for (int part = 0; part < 3; ++part) pl.g3[part] = capture_graph(on[part], [&]() { run_sw_chain(m, T, false, pl, part, on[part]); });
-                } else {
-                    if (pl.graph) continue;
-                    pl.graph = capture_graph(stream_, [&]() { run_sw_chain(m, T, false, pl, -1, stream_); });
-                }
-            }
-            pp = &sw_plans_.find(std::make_pair(gclk_ ? -m : m, T * 2 + par))->second;      // (a plan-cache eviction in between would have moved it)
-        }
-        SwPlan &p = *pp;
-        if (split) {
-            // split feed: front end on F, layers on M, search on S, chained by events inside the feed; across feeds the three
-            // parts of neighbouring flights overlap (see "streams" above).  split_streams_ == 1 keeps the front end on M.
-            if (fe == f_stream_) {
-                if (m_unseen_by_f_) { join(f_stream_, stream_); m_unseen_by_f_ = false; }
-            } else if (f_unseen_by_m_) { join(stream_, f_stream_); f_unseen_by_m_ = false; }       // (the fbank launch of this flight)
-            if (m_unseen_by_s_) { join(s_stream_, stream_); m_unseen_by_s_ = false; }
-            StreamTrace *tr = trace_slot();
-            if (tr) HIP_CHECK(hipEventRecord(tr->ev[0], fe));
-            HIP_CHECK(hipGraphLaunch(p.g3[0], fe));
-            if (tr) HIP_CHECK(hipEventRecord(tr->ev[1], fe));
-            if (fe == f_stream_) { join(stream_, f_stream_); f_unseen_by_m_ = false; }
-            if (tr) HIP_CHECK(hipEventRecord(tr->ev[2], stream_));
-            HIP_CHECK(hipGraphLaunch(p.g3[1], stream_));
-            if (tr) HIP_CHECK(hipEventRecord(tr->ev[3], stream_));
-            join(s_stream_, stream_);
-            if (tr) HIP_CHECK(hipEventRecord(tr->ev[4], s_stream_));
-            HIP_CHECK(hipGraphLaunch(p.g3[2], s_stream_));
-            if (tr) { HIP_CHECK(hipEventRecord(tr->ev[5], s_stream_)); tr->m = m; tr->T = T; tr->used = true; }
-            s_unseen_by_m_ = true; flight_tail_s_ = true;
-            if (fe != f_stream_) m_unseen_by_f_ = true;          // (front-end kernels on M read ring rows: the next fbank waits for them)
-            return k;
-        }
-        general_prologue();
-        if (graphs) {
-            HIP_CHECK(hipGraphLaunch(p.graph, stream_));
-            return k;
-        }
-        launch_count_ = 0;
-        run_sw_chain(m, T, logits_out != nullptr, p, -1, stream_);
-        kernels_per_step_ = (launch_count_ + 1 + T - 1) / T;          // per chunk
-    } else {
-        general_prologue();
-        const int tk = f16_tile_ ? 2 : tile_ok();
-        const bool wavefront = lm_wavefront_on() && !profiling_ && T > LM_WAVEFRONT_MIN_CHUNKS &&
-                               gemm_fullk(m, d.d_model, kz_hr(), true, 1, tk) && gemm_fullk(m, d.d_model, kz_ff2(), true, 1, tk);
-        if (wavefront) {                 // long feed: all layers of a wavefront per launch (run_lm_wavefront)
-            run_lm_wavefront(m, T, logits_out != nullptr);
-            if (!logits_out) return k;
-        } else if (use_graphs_ && !profiling_ && !logits_out) {
-            const std::pair<int, int> key(m * 2 + flight_parity_, T);
-            auto it = lm_graphs_.find(key);
-            if (it == lm_graphs_.end()) {
-                if (lm_graphs_.size() >= 32) { sync(); for (auto &g : lm_graphs_) (void)hipGraphExecDestroy(g.second); lm_graphs_.clear(); }
-                it = lm_graphs_.emplace(key, capture_graph(stream_, [&]() { run_lm_chain(m, T, false); })).first;
-            }
-            HIP_CHECK(hipGraphLaunch(it->second, stream_));
-            return k;
-        } else {
-            launch_count_ = 0;
-            run_lm_chain(m, T, logits_out != nullptr);
-            kernels_per_step_ = launch_count_ + 1;
-        }
-    }
-    if (logits_out) {
-        HIP_CHECK(hipMemcpyAsync(logits_h_, logits_, (size_t)3 * rows * d.vocab * 4, hipMemcpyDeviceToHost, stream_));
-        HIP_CHECK(hipMemcpyAsync(rec_h_ + rec_off_h_[k], rec_d_ + rec_off_h_[k], (size_t)3 * rows * sizeof(StepRecord), hipMemcpyDeviceToHost, stream_));
-        sync();
-        memcpy(logits_out, logits_h_, (size_t)3 * rows * d.vocab * 4);
-    }
+    mode == 1 ? run_feed_wavefront(m, T, logits_out != nullptr) : run_layer_major(m, T, logits_out != nullptr);
+    if (logits_out) read_back_logits(k, rows, logits_out);
     return k;
 }
 
+// mode 1: the chunk steps of one feed as a wavefront over the layers (run_sw_chain)
+void Engine::run_feed_wavefront(int m, int T, bool dump_logits)
+{
+    sw_plan(m, T);
+    // captured at the SECOND time the shape is seen (by either flight parity), for both parities; until then its launches go out one by one (~0.25 ms of host time)
+    const bool graphs = use_graphs_ && !profiling_ && !dump_logits && (sw_graphs_.find(sw_key(m, T)) || sw_graphs_.find(sw_key(m, T, 1)) || sw_graphs_.use(m, T) >= 2);
+    // (split: only the FIRST step of a flight: the per-parity buffers keep neighbouring FLIGHTS apart, a second step of the same
+    // flight -- a flush runs several -- would have its index fetch and front end overwrite what the first step's layers and
+    // search still read; it takes the one-stream path, behind everything the first step put on F and S)
+    // (gates clock on: one stream for everything, so that no other stream's kernel shares the CUs with a gates launch while it times itself;
+    // the feeds still arrive pipelined, the GPU stays busy and at speed)
+    const bool split = graphs && split_streams_ > 0 && overlap_hint_ && flight_steps_ == 1 && !gclk_;
+    const hipStream_t on[3] = {split_streams_ >= 2 ? f_stream_ : stream_, stream_, s_stream_};
+    if (graphs && !sw_graphs_.find(sw_key(m, T, split ? 1 : 0)))
+        capture_both_parities([&]() {
+            const SwPlan &pl = sw_plan(m, T);
+            if (split) for (int part = 0; part < 3; ++part) cached_graph(sw_graphs_, sw_key(m, T, 1 + part), on[part], [&]() { run_sw_chain(m, T, false, pl, part, on[part]); });
+            else cached_graph(sw_graphs_, sw_key(m, T), stream_, [&]() { run_sw_chain(m, T, false, pl, -1, stream_); });
+        });
+    if (split) { launch_split_feed(m, T, on[0]); return; }
+    general_prologue();
+    if (graphs) { HIP_CHECK(hipGraphLaunch(sw_graphs_.find(sw_key(m, T)), stream_)); return; }
+    launch_count_ = 0; run_sw_chain(m, T, dump_logits, sw_plan(m, T), -1, stream_); kernels_per_step_ = (launch_count_ + 1 + T - 1) / T;          // per chunk
+}
+
+// split feed: front end on F (`fe`; split_streams_ == 1 keeps it on M), layers on M, search on S, chained by events inside the feed (see "streams" above)
+void Engine::launch_split_feed(int m, int T, hipStream_t fe)
+{
+    if (fe == f_stream_) {
+        if (m_unseen_by_f_) { join(f_stream_, stream_); m_unseen_by_f_ = false; }
+    } else if (f_unseen_by_m_) { join(stream_, f_stream_); f_unseen_by_m_ = false; }       // (the fbank launch of this flight)
+    if (m_unseen_by_s_) { join(s_stream_, stream_); m_unseen_by_s_ = false; }
+    StreamTrace *tr = trace_slot();
+    auto part = [&](int i, hipStream_t st) {          // one of the feed's three graphs between its two trace events
+        if (tr) HIP_CHECK(hipEventRecord(tr->ev[2 * i], st));
+        HIP_CHECK(hipGraphLaunch(sw_graphs_.find(sw_key(m, T, 1 + i)), st));
+        if (tr) HIP_CHECK(hipEventRecord(tr->ev[2 * i + 1], st));
+    };
+    part(0, fe);
+    if (fe == f_stream_) { join(stream_, f_stream_); f_unseen_by_m_ = false; }
+    part(1, stream_); join(s_stream_, stream_); part(2, s_stream_);
+    if (tr) { tr->m = m; tr->T = T; tr->used = true; }
+    s_unseen_by_m_ = true; flight_tail_s_ = true;
+    if (fe != f_stream_) m_unseen_by_f_ = true;          // (front-end kernels on M read ring rows: the next fbank waits for them)
+}
+
+// mode 0: layer-major; a long feed as a wavefront over blocks of time steps
+void Engine::run_layer_major(int m, int T, bool dump_logits)
+{
+    general_prologue();
+    const NetDims &d = L_.dims; const int tk = f16_tile_ ? 2 : tile_ok();
+    const bool wavefront = lm_wavefront_on() && !profiling_ && T > LM_WAVEFRONT_MIN_CHUNKS &&
+                           gemm_fullk(m, d.d_model, kz_hr(), true, 1, tk) && gemm_fullk(m, d.d_model, kz_ff2(), true, 1, tk);
+    if (wavefront) { run_lm_wavefront(m, T, dump_logits); return; }       // long feed: all layers of a wavefront per launch
+    if (!use_graphs_ || profiling_ || dump_logits) { launch_count_ = 0; run_lm_chain(m, T, dump_logits); kernels_per_step_ = launch_count_ + 1; return; }
+    const GraphCache::Key key = graph_key(m, T);
+    if (!lm_graphs_.find(key) && lm_graphs_.full()) { sync(); lm_graphs_.clear(); }
+    HIP_CHECK(hipGraphLaunch(cached_graph(lm_graphs_, key, stream_, [&]() { run_lm_chain(m, T, false); }), stream_));
+}
+
+// Stages a step's index block in the flight's pinned ring (read by the advance kernel) and books its records; returns its index inside the flight.
+// T == 0: a chunk step, [slots | ring tails | times] of m rows; else the layer-major form: [slots], then ring tails, times and row slots, each [T][m].
+int Engine::stage_step(int m, int T, const int *slots, const int *ring_tails, const int *now_ms)
+{
+    const size_t rows = (size_t)m * (size_t)std::max(T, 1);
+    const int k = next_step_index(); int *blk = ring_h_ + ring_pos_;
+    memcpy(blk, slots, (size_t)m * 4); memcpy(blk + m, ring_tails, rows * 4); memcpy(blk + m + rows, now_ms, rows * 4);
+    for (int t = 0; t < T; ++t) memcpy(blk + m + 2 * rows + (size_t)t * m, slots, (size_t)m * 4);
+    step_off_h_[k] = (int)ring_pos_; rec_off_h_[k] = (int)rec_pos_;
+    ring_pos_ += (size_t)m + (T ? 3 : 2) * rows; rec_pos_ += 3 * rows;
+    if (conf_k_h_) note_conf_step(k, slots, m, 3 * rows);
+    return k;
+}
+
+// traced steps (tests): the logits of step k's rounds [3 * rows][vocab] and its records, after everything enqueued has run
+void Engine::read_back_logits(int k, int rows, float *out)
+{
+    const size_t n = (size_t)3 * rows * L_.dims.vocab;
+    HIP_CHECK(hipMemcpyAsync(logits_h_, logits_, n * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(rec_h_ + rec_off_h_[k], rec_d_ + rec_off_h_[k], (size_t)3 * rows * sizeof(StepRecord), hipMemcpyDeviceToHost, stream_));
+    sync();
+    memcpy(out, logits_h_, n * 4);
+}
 
 // ---------------------------------------------------------------- confidences
 // Stepping thread, between two flights' enqueues.  The decision launches carry the per-slot K bytes and the side ring as kernel
@@ -1460,16 +1469,7 @@ void Engine::apply_confidence_pending()
 
 void Engine::drop_graphs()
 {
-    for (auto &g : step_graphs_) (void)hipGraphExecDestroy(g.second);
-    step_graphs_.clear(); step_seen_.clear();
-    for (auto &g : lm_graphs_) (void)hipGraphExecDestroy(g.second);
-    lm_graphs_.clear();
-    for (auto &g : lm_search_graphs_) (void)hipGraphExecDestroy(g.second);
-    lm_search_graphs_.clear();
-    for (auto &p : sw_plans_) {
-        if (p.second.graph) { (void)hipGraphExecDestroy(p.second.graph); p.second.graph = nullptr; }
-        for (hipGraphExec_t &x : p.second.g3) if (x) { (void)hipGraphExecDestroy(x); x = nullptr; }
-    }
+    for (GraphCache *c : {&step_graphs_, &lm_graphs_, &lm_search_graphs_, &sw_graphs_}) c->clear();      // (the feed wavefront plans hold no such pointer: they stay)
 }
 
 // ---------------------------------------------------------------- phrase boosting
@@ -1602,46 +1602,24 @@ bool Engine::flight_has_room(int rows, int nsteps) const
 int Engine::step(int m, const int *slots, const int *ring_tails, const int *now_ms, float *logits_out)
 {
     if (m <= 0 || m > cfg_.max_batch || !flight_has_room(m, 1)) { LOGE("engine: step of %d rows does not fit (max batch %d)", m, cfg_.max_batch); abort(); }
-    const int k = next_step_index();
-    int *blk = ring_h_ + ring_pos_;
-    memcpy(blk, slots, (size_t)m * 4); memcpy(blk + m, ring_tails, (size_t)m * 4); memcpy(blk + 2 * m, now_ms, (size_t)m * 4);
-    step_off_h_[k] = (int)ring_pos_; rec_off_h_[k] = (int)rec_pos_;
-    ring_pos_ += (size_t)3 * m; rec_pos_ += (size_t)3 * m;
-    if (conf_k_h_) note_conf_step(k, slots, m, (size_t)3 * m);
+    const int k = stage_step(m, 0, slots, ring_tails, now_ms);
     // The whole per-chunk chain (index fetch + 58 kernels) is replayed from a hipGraph captured once per batch size (and flight
     // parity: the parity selects buffers): at small batches the chain is launch-bound on the host (~3.5 us per launch), the
     // replay is not.  Kernel arguments depend only on m; the step's indices and its record offset reach the kernels through
     // the device step counter.
     std::lock_guard<std::mutex> cg(capture_mu_);               // aas_free on another thread resets slots through this stream
     general_prologue();
-    const int gkey = m * 2 + flight_parity_;
-    if (use_graphs_ && !profiling_ && !logits_out && (step_graphs_.count(gkey) || ++step_seen_[m] >= 2)) {      // (captured at the second use, see lm_step)
-        auto it = step_graphs_.find(gkey);
-        if (it == step_graphs_.end()) {
-            if (step_graphs_.size() >= 256) { sync(); for (auto &g : step_graphs_) (void)hipGraphExecDestroy(g.second); step_graphs_.clear(); step_seen_.clear(); }
-            const int par = flight_parity_;
-            for (int k2 = 0; k2 < 2; ++k2) {               // both parities at once (see lm_step), this flight's last
-                const int q = k2 == 0 ? 1 - par : par;
-                if (step_graphs_.count(m * 2 + q)) continue;
-                select_parity(q);
-                step_graphs_.emplace(m * 2 + q, capture_graph(stream_, [&]() { run_chain(m, false); }));
-            }
-            select_parity(par);
-            it = step_graphs_.find(gkey);
+    const GraphCache::Key key = graph_key(m);
+    if (use_graphs_ && !profiling_ && !logits_out && (step_graphs_.find(key) || step_graphs_.use(m) >= 2)) {      // (captured at the second use, for both parities)
+        if (!step_graphs_.find(key)) {
+            if (step_graphs_.full()) { sync(); step_graphs_.clear(); }
+            capture_both_parities([&]() { cached_graph(step_graphs_, graph_key(m), stream_, [&]() { run_chain(m, false); }); });
         }
-        HIP_CHECK(hipGraphLaunch(it->second, stream_));
+        HIP_CHECK(hipGraphLaunch(step_graphs_.find(key), stream_));
         return k;
     }
-    launch_count_ = 0;
-    run_chain(m, logits_out != nullptr);
-    kernels_per_step_ = launch_count_ + 1;        // + the index fetch
-    if (logits_out) {
-        const NetDims &d = L_.dims;
-        HIP_CHECK(hipMemcpyAsync(logits_h_, logits_, (size_t)3 * m * d.vocab * 4, hipMemcpyDeviceToHost, stream_));
-        HIP_CHECK(hipMemcpyAsync(rec_h_ + rec_off_h_[k], rec_d_ + rec_off_h_[k], (size_t)3 * m * sizeof(StepRecord), hipMemcpyDeviceToHost, stream_));
-        sync();
-        memcpy(logits_out, logits_h_, (size_t)3 * m * d.vocab * 4);
-    }
+    launch_count_ = 0; run_chain(m, logits_out != nullptr); kernels_per_step_ = launch_count_ + 1;        // + the index fetch
+    if (logits_out) read_back_logits(k, m, logits_out);
     return k;
 }
 

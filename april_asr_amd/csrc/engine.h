@@ -76,6 +76,19 @@ struct EngineConfig {
 
 struct KernelTiming { double ms = 0; long launches = 0; };
 
+// One family of captured launch chains: key -> instantiated graph, with a capacity.  A full family is emptied as a whole (its owner first drains the streams that may
+// still run one of its execs).  use() counts how often a batch shape has come by, for the families that capture at the SECOND use: a capture costs milliseconds.
+struct GraphCache {
+    using Key = std::array<int, 3>;          // {rows m (negated: built under the gates clock), chunks T / block length, flight parity * 4 + part}
+    const char *name; size_t cap;
+    bool full() const { return map_.size() >= cap; }
+    hipGraphExec_t find(const Key &k) const { auto it = map_.find(k); return it == map_.end() ? nullptr : it->second; }
+    void insert(const Key &k, hipGraphExec_t g) { map_[k] = g; }
+    int use(int m, int T = 0) { return ++uses_[std::make_pair(m, T)]; }
+    void clear();                            // destroys every exec and forgets the use counts (engine.cc); one INFO line
+    std::map<Key, hipGraphExec_t> map_; std::map<std::pair<int, int>, int> uses_;
+};
+
 class Engine {
 public:
     Engine(const EngineConfig &cfg, const PackedLayout &layout, const float *blob_host, const float *blob_device,
@@ -263,15 +276,22 @@ private:
     void run_greedy_rounds(int n, const GreedyIo &io);
     void run_lm_chain(int m, int T, bool dump_logits);
     void run_lm_wavefront(int m, int T, bool dump_logits);
-    struct SwPlan {                          // argument blocks + launch list of run_sw_chain for one (m, T), and its captured graph
+    struct SwPlan {                          // argument blocks + launch list of run_sw_chain for one (m, T, parity); its captured graphs live in sw_graphs_
         struct Batch { size_t off; int n, macro, kind; size_t roff; int rn; };      // rn > 0: the GEMMs write partial planes, rn row problems finish them
-        std::vector<GemmArgs> host; GemmArgs *dev = nullptr; std::vector<Batch> batches; hipGraphExec_t graph = nullptr; int uses = 0;
-        hipGraphExec_t g3[3] = {nullptr, nullptr, nullptr};                      // split feed: front end / layers / search, one graph per stream
+        std::vector<GemmArgs> host; GemmArgs *dev = nullptr; std::vector<Batch> batches;
         std::vector<RowArgs> rhost; RowArgs *rdev = nullptr;
         std::vector<std::pair<int, long>> stamp_slots; std::vector<int> stamp_n;  // gates clock: (slot, rows) and problem count of every gates launch of a plan built while it was on
     };
+    // keys of the current flight parity (it selects buffers); plans built under the gates clock carry stamp slots: -m; part 0: the one-stream graph, 1..3: a split feed's
+    GraphCache::Key graph_key(int m, int T = 0, int part = 0) const { return {m, T, flight_parity_ * 4 + part}; }
+    GraphCache::Key sw_key(int m, int T, int part = 0) const { return graph_key(gclk_ ? -m : m, T, part); }
     SwPlan &sw_plan(int m, int T);
+    void free_sw_plans();                    // every plan's device blocks and graphs (streams drained, legacy lock held)
     void run_sw_chain(int m, int T, bool dump_logits, const SwPlan &p, int part, hipStream_t st);
+    int stage_step(int m, int T, const int *slots, const int *ring_tails, const int *now_ms); void read_back_logits(int k, int rows, float *out);
+    template <typename Chain> hipGraphExec_t cached_graph(GraphCache &cache, const GraphCache::Key &key, hipStream_t st, Chain &&chain);
+    template <typename Capture> void capture_both_parities(Capture &&capture);
+    void run_feed_wavefront(int m, int T, bool dump_logits); void run_layer_major(int m, int T, bool dump_logits); void launch_split_feed(int m, int T, hipStream_t fe);   // lm_step's paths
     struct StreamTrace { hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; int m = 0, T = 0; bool used = false; };
     std::deque<StreamTrace> trace_; hipEvent_t trace_base_ = nullptr;
     StreamTrace *trace_slot();
@@ -285,6 +305,7 @@ private:
     void run_decproj(int n, const int *d_slots, const int *row_mask, const int *run_flag, int run_gen, float *out = nullptr);
     void build_dec_table();
     void run_chain(int m, bool dump_logits);     // advance + encoder + greedy rounds with arguments that depend on m only
+    void collect_gates_clock();                  // adds the stamp slots of every clocked plan to the sums
     void timed_begin(int cls);
     void timed_end(int cls);
     void collect_timing();
@@ -357,7 +378,6 @@ private:
     float *y_buf_[2] = {nullptr, nullptr}, *ssq_buf_[2] = {nullptr, nullptr}, *eout_lm_buf_[2] = {nullptr, nullptr}, *ws_fe_ = nullptr, *ws_sr_ = nullptr;
     uint16_t *y16_buf_[2] = {nullptr, nullptr};
     int *step_buf_[2] = {nullptr, nullptr}, *flags_buf_[2] = {nullptr, nullptr}, *rec_off_buf_[2] = {nullptr, nullptr};
-    std::map<std::pair<int, int>, int> sw_uses_;
     int *counter_d_ = nullptr, *step_d_ = nullptr, *active_d_ = nullptr, *dirty_d_ = nullptr, *rec_off_d_ = nullptr, *flags_d_ = nullptr;
     int *dec_slots_d_ = nullptr;
     float *logits_h_ = nullptr;
@@ -390,15 +410,15 @@ private:
     int kz_embed_ = 1, kz_hr_ = 1, kz_ff2_ = 1, kz_proj_ = 1, kz_out_ = 1;
     int ws_mstride_ = 0;
     float *conv_wt_ = nullptr;      // transposed weights of the first two convolutions: [9][ch0] then [ch0 * 9][ch1] (finish_weights)
-    // chunk-step launch chains captured per batch size
+    // captured launch chains: four families; APRIL_GRAPH_CACHE_CAP replaces all four capacities
     bool use_graphs_ = true;
-    std::map<int, hipGraphExec_t> step_graphs_;
-    std::map<int, int> step_seen_;             // batch size -> times seen (a chain is captured at its second use)
-    std::map<std::pair<int, int>, hipGraphExec_t> lm_graphs_;      // (m, T)
-    // wavefront form of the layer-major step: its stream, events, per-launch argument blocks (pinned + device), the
-    // block-independent search graphs (m, block length) and their bookkeeping words
-    std::map<std::pair<int, int>, hipGraphExec_t> lm_search_graphs_;
-    std::map<std::pair<int, int>, SwPlan> sw_plans_;
+    GraphCache step_graphs_{"chunk step", 256};          // {m, 0, parity}: second use, both parities
+    GraphCache lm_graphs_{"layer-major chain", 32};      // {m, T, parity}: first use, this parity
+    GraphCache lm_search_graphs_{"long-feed search", 64};  // {m, block length, parity}: first use, this parity
+    GraphCache sw_graphs_{"feed wavefront", 4 * 64};     // sw_key(): second use, both parities; at most four graphs per plan, so sw_plans_ is full first: emptied with it
+    size_t sw_plan_cap_ = 64;
+    std::map<GraphCache::Key, SwPlan> sw_plans_;         // sw_key(m, T)
+    // wavefront form of the layer-major step: its stream, events, per-launch argument blocks (pinned + device), the bookkeeping words of its search graphs
     hipStream_t lm_stream_ = nullptr;
     std::vector<hipEvent_t> lm_events_;
     GemmArgs *zargs_h_ = nullptr, *zargs_d_ = nullptr; size_t zargs_region_ = 0, zargs_pos_ = 0;     // three regions, round robin
@@ -408,7 +428,7 @@ private:
     long launch_count_ = 0;
     // profiling
     bool profiling_ = false;
-    bool gclk_ = false; unsigned long long *gclk_slots_ = nullptr; int gclk_used_ = 0;      // gates clock (set_gates_clock): device slots of STAMP_WORDS (144) words
+    bool gclk_ = false, gclk_warned_ = false; unsigned long long *gclk_slots_ = nullptr; int gclk_used_ = 0;      // gates clock (set_gates_clock): device slots of STAMP_WORDS (144) words
     static constexpr int GCLK_SLOTS = 2048;       // launch sites x 1152 B (STAMP_WORDS, kernels.h; layout: device_utils.h)
     double gclk_ms_ = 0; long gclk_launches_ = 0, gclk_rows_ = 0; double gclk_ms_n_[4] = {0, 0, 0, 0}; long gclk_launches_n_[4] = {0, 0, 0, 0};
     struct Ev { hipEvent_t a, b; int cls; };

@@ -518,6 +518,88 @@ def test_many_batch_shapes(gpu_tiny):
         s_.close()
 
 
+def _eviction_script(model, traced):
+    """Two shapes per family of captured chains, each several times: 100 ms feeds at one session then two (feed wavefront plans, or
+    chunk-step graphs when the model steps chunk by chunk), 0.9 s feeds at two sessions then one (layer-major chain graphs), 3 s feeds
+    at two sessions then one (long-feed wavefront, per-block search graphs), flush.  Returns per session (traced logits, events)."""
+    import april_asr_amd as A
+    pcms = [speech_like_pcm(10.5, seed=700 + i) for i in range(3)]
+    evs, sess, pos, out = [[] for _ in pcms], {}, [0] * 3, {}
+
+    def join(i):
+        sess[i] = A.Session(model, lambda t, toks: evs[i].append((t, toks)), raw_events=True)
+        if traced:
+            sess[i].trace_logits(4000)
+
+    def leave(i):
+        out[i] = (sess[i].traced_logits().copy() if traced else None, evs[i])
+        sess.pop(i).close()
+
+    def feed(n):
+        ids = sorted(sess)
+        A.SessionGroup([sess[i] for i in ids]).feed([pcms[i][pos[i]:pos[i] + n] for i in ids])
+        for i in ids:
+            pos[i] += n
+
+    join(0)
+    for _ in range(4):
+        feed(1600)
+    join(1)
+    for _ in range(4):
+        feed(1600)
+    feed(14400); feed(14400)
+    leave(1)
+    feed(14400); feed(14400)
+    join(2)
+    feed(48000)
+    A.SessionGroup([sess[0], sess[2]]).flush()
+    leave(2)
+    feed(48000)
+    sess[0].flush()
+    leave(0)
+    return out
+
+
+def test_captured_chains_survive_cache_eviction(tiny_model, gpu_tiny):
+    """Every family of captured launch chains (chunk-step graphs, layer-major chain graphs, long-feed search graphs, feed wavefront
+    plans and their graphs) is emptied when it is full and captured again at the next use.  Two models loaded with
+    APRIL_GRAPH_CACHE_CAP=2 (the smallest capacity: a both-parity capture inserts two entries) -- one of them stepping chunk by chunk,
+    APRIL_WAVE_MIN_CHUNKS=0 -- run a script that shows every family two shapes several times each, so each is emptied, refilled and
+    replayed; the reference is the same script on the model with the default capacities.  The script runs twice per model: with
+    traced sessions (a traced step is launched eagerly: logits and events, BIT FOR BIT) and with untraced ones (the steps that replay
+    the captured graphs: events, which carry every token's log-probability)."""
+    import os
+    import april_asr_amd as A
+
+    def load(**env):
+        old = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        try:
+            return A.Model(tiny_model["path"])
+        finally:
+            for k, v in old.items():
+                if v is None:
+                    del os.environ[k]
+                else:
+                    os.environ[k] = v
+
+    small = load(APRIL_GRAPH_CACHE_CAP="2")
+    plain = load(APRIL_GRAPH_CACHE_CAP="2", APRIL_WAVE_MIN_CHUNKS="0")
+    try:
+        for traced in (True, False):
+            want = _eviction_script(gpu_tiny, traced)
+            for name, m in (("small", small), ("plain", plain)):
+                got = _eviction_script(m, traced)
+                for i in sorted(want):
+                    if traced:
+                        assert want[i][0].size > 0 and np.array_equal(got[i][0], want[i][0]), (name, i)
+                    assert len(want[i][1]) > 0 and got[i][1] == want[i][1], (name, traced, i)
+        assert gpu_tiny.stats().replay_mismatch == 0 and small.stats().replay_mismatch == 0 and plain.stats().replay_mismatch == 0
+        assert plain.stats().wave_chunks == 0 and small.stats().wave_chunks > 0
+    finally:
+        small.close(); plain.close()
+
+
 def test_decoder_table_equals_decoder_network(tiny_model, gpu_tiny):
     """The decoder output of EVERY 2-token context is computed once at load (Engine::build_dec_table) and the joiner reads the
     row of a session's context.  A model loaded with the table disabled runs the decoder network per context change as in
