@@ -40,6 +40,39 @@ std::vector<int> g_devices;
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 double aprilx_now_ms() { return now_ms(); }
 
+// how `floats` packed weights reached the model's engines
+void set_load_info(Model &m, double broadcast_ms, double comm_init_ms, size_t floats, int ranks, int used_rccl)
+{
+    m.load = LoadInfo{broadcast_ms, comm_init_ms, floats * 4, ranks, used_rccl};
+}
+
+// APRIL_PRECISION: 0 = fp32 (unset, f32, fp32), 1 = fp16 operands (f16, fp16, half), -1 = anything else
+int env_precision()
+{
+    const char *pv = env_str("APRIL_PRECISION");
+    const std::string v(pv ? pv : "");
+    if (v == "f16" || v == "fp16" || v == "half") return 1;
+    return (v.empty() || v == "f32" || v == "fp32") ? 0 : -1;
+}
+
+// "load file, pad, plan layout" of aam_create_model / aprilx_model_load_host
+bool load_model_file(const char *model_path, Model &m)
+{
+    std::string err;
+    if (!load_april_file(model_path, m.host, err) || !pad_host_model(m.host, err)) { LOGE("aam: failed to load %s: %s", model_path ? model_path : "(null)", err.c_str()); return false; }
+    plan_layout(m.host.dims, !m.host.dec_conv_b.empty(), m.layout);
+    return true;
+}
+
+// what every model has beside its weights, with or without engines: the fbank tables and the token classes
+bool build_host_tables(Model &m)
+{
+    const ModelParams &P = m.host.params;
+    if (!build_fbank_tables(P.sample_rate, P.frame_shift_ms, P.frame_length_ms, P.mel_features, P.round_pow2 != 0, P.mel_low, P.mel_high, m.ftab)) return false;
+    m.tok_class = classify_tokens(P);
+    return true;
+}
+
 // One process, several GPUs (APRIL_GPU_DEVICES=0,1,...): the packed weights are uploaded ONCE, to the first device, and
 // broadcast from there to the other devices' engines with RCCL over xGMI (grouped ncclBroadcast on a communicator made by
 // ncclCommInitAll) -- the one collective of this system, at model load (reference load site src/april_model.c:57-61).
@@ -89,10 +122,8 @@ bool broadcast_local(Model &m)
         auto rccl_path = [&]() -> bool { return rccl_group_broadcast(api, devs, comms, &t1); };
         const bool used = rccl_path();
         for (ncclComm_t c : comms) if (c) (void)ncclCommDestroy(c);
-        if (used) {
-            m.load.broadcast_ms = now_ms() - t1; m.load.comm_init_ms = t1 - t0;
-            m.load.broadcast_bytes = count * 4; m.load.ranks = (int)devs.size(); m.load.used_rccl = 1;
-        } else {
+        if (used) set_load_info(m, now_ms() - t1, t1 - t0, count, (int)devs.size(), 1);
+        else {
             if (env_int("APRIL_STRICT_RCCL", 0)) { LOGE("aam: RCCL weight broadcast failed and APRIL_STRICT_RCCL=1: giving up"); return false; }
             LOGE("aam: RCCL weight broadcast failed: falling back to peer copies from device %d (used_rccl = 0)", devs[0]);
             const double t2 = now_ms();
@@ -102,8 +133,7 @@ bool broadcast_local(Model &m)
                 if (devs[i] == devs[0]) HIP_CHECK(hipMemcpy(peers[i]->weights_mut(), peers[0]->weights_device(), count * 4, hipMemcpyDeviceToDevice));
                 else HIP_CHECK(hipMemcpyPeer(peers[i]->weights_mut(), devs[i], peers[0]->weights_device(), devs[0], count * 4));
             }
-            m.load.broadcast_ms = now_ms() - t2; m.load.comm_init_ms = 0;
-            m.load.broadcast_bytes = count * 4; m.load.ranks = (int)devs.size(); m.load.used_rccl = 0;
+            set_load_info(m, now_ms() - t2, 0, count, (int)devs.size(), 0);
         }
     }
     // further engines on a device that already holds the weights ("lanes"): a device-to-device copy
@@ -121,8 +151,7 @@ bool broadcast_local(Model &m)
 // calls distribute_weights() itself
 bool create_engines(Model &m, const float *blob_host, const float *blob_device)
 {
-    const ModelParams &P = m.host.params;
-    if (!build_fbank_tables(P.sample_rate, P.frame_shift_ms, P.frame_length_ms, P.mel_features, P.round_pow2 != 0, P.mel_low, P.mel_high, m.ftab)) {
+    if (!build_host_tables(m)) {
         LOGE("aam: unsupported frame length (an FFT size of 8 .. 8192 that pocketfft runs through its radix passes; a large prime factor means Bluestein, which is not built)");
         return false;
     }
@@ -131,19 +160,15 @@ bool create_engines(Model &m, const float *blob_host, const float *blob_device)
         return false;
     }
     if (m.layout.dims.d_model > 2048) { LOGE("aam: d_model > 2048 unsupported (row scales are staged for at most 64 column groups)"); return false; }
-    m.tok_class = classify_tokens(P);
     EngineConfig cfg;
     cfg.max_slots = env_int("APRIL_MAX_SESSIONS", 4096);
     // rows of the work buffers = sessions x chunks stepped together (a 100 ms feed of 2048 sessions is 3 x 2048 rows); < 1 GB at 8192
     cfg.max_batch = std::max(1, env_int("APRIL_MAX_BATCH", 8192));
-    if (const char *pv = env_str("APRIL_PRECISION")) {
-        const std::string v(pv);
-        if (v == "f16" || v == "fp16" || v == "half") cfg.precision = 1;
-        else if (!(v.empty() || v == "f32" || v == "fp32")) { LOGE("aam: APRIL_PRECISION must be f32 or f16 (got '%s')", pv); return false; }
-    }
+    cfg.precision = env_precision();
+    if (cfg.precision < 0) { LOGE("aam: APRIL_PRECISION must be f32 or f16 (got '%s')", env_str("APRIL_PRECISION")); return false; }
     for (size_t i = 0; i < g_devices.size(); ++i) {
         cfg.device = g_devices[i];
-        Engine *e = new Engine(cfg, m.layout, i == 0 ? blob_host : nullptr, i == 0 ? blob_device : nullptr, P, m.ftab, m.tok_class);
+        Engine *e = new Engine(cfg, m.layout, i == 0 ? blob_host : nullptr, i == 0 ? blob_device : nullptr, m.host.params, m.ftab, m.tok_class);
         m.engines.push_back(e);
     }
     return true;
@@ -163,6 +188,46 @@ bool build_runtime(Model &m, const float *blob_host, const float *blob_device)
 
 // ---- blob (de)serialisation: [magic][meta_bytes][weight_floats][meta][pad to 256][weights]
 struct BlobHeader { char magic[8]; uint64_t meta_bytes, weight_floats, weights_offset; };
+size_t blob_weights_offset(size_t meta_bytes) { return (sizeof(BlobHeader) + meta_bytes + 255) & ~(size_t)255; }
+// header and metadata lie inside a blob of `size` bytes, in front of the weights (each caller bounds weight_floats in its own way)
+bool blob_header_ok(const BlobHeader &hd, size_t size)
+{
+    return hd.weights_offset <= size && hd.meta_bytes <= size && sizeof hd + hd.meta_bytes <= hd.weights_offset;
+}
+
+// the payload of the fp16 cache file (aprilx_model_save_blob_f16) in order: span(first, count, half) per span; false from it ends the walk
+template <class Span> bool walk_f16_payload(const PackedLayout &layout, size_t total, Span span)
+{
+    size_t pos = 0;
+    for (const auto &sec : gemm_sections(layout)) {
+        if (sec.first > pos && !span(pos, sec.first - pos, false)) return false;
+        if (!span(sec.first, sec.second, true)) return false;
+        pos = sec.first + sec.second;
+    }
+    return total <= pos || span(pos, total - pos, false);
+}
+
+// the whole file: 0 = read (an empty file gives an empty buffer), -1 = cannot open, -2 = short read
+template <class Byte> int read_file(const char *path, std::vector<Byte> &buf)
+{
+    buf.clear();
+    FILE *f = path ? fopen(path, "rb") : nullptr;
+    if (!f) return -1;
+    const long n = fseek(f, 0, SEEK_END) == 0 ? ftell(f) : 0;
+    rewind(f);
+    buf.resize(n > 0 ? (size_t)n : 0);
+    const size_t got = buf.empty() ? 0 : fread(buf.data(), 1, buf.size(), f);
+    fclose(f);
+    return got == buf.size() ? 0 : -2;
+}
+
+int write_file(const char *path, const void *data, size_t n)
+{
+    FILE *f = fopen(path, "wb");
+    if (!f) { LOGE("aprilx: cannot write '%s'", path); return -1; }
+    const bool ok = fwrite(data, 1, n, f) == n;
+    return (fclose(f) == 0 && ok) ? 0 : -1;
+}
 
 void put(std::string &b, const void *p, size_t n) { b.append((const char *)p, n); }
 template <typename T> void putv(std::string &b, const T &v) { put(b, &v, sizeof v); }
@@ -237,6 +302,37 @@ void free_host_weights(HostModel &h)
     std::vector<float>().swap(h.w_encproj); std::vector<float>().swap(h.emb); std::vector<float>().swap(h.dec_conv);
     std::vector<float>().swap(h.w_decproj); std::vector<float>().swap(h.w_out);
 }
+
+// ---- group calls: the listed sessions by scheduler (GPU), in the order of the list, with their PCM when the call carries some
+struct SchedGroup { Scheduler *sched; std::vector<Session *> ss; std::vector<const short *> pcm; std::vector<size_t> counts; };
+
+std::vector<SchedGroup> group_by_scheduler(size_t n, AprilASRSession *sessions, const short *const *pcm16, const size_t *short_counts)
+{
+    std::vector<SchedGroup> groups;
+    for (size_t i = 0; i < n; ++i) {
+        Session *s = &sessions[i]->s;
+        auto g = std::find_if(groups.begin(), groups.end(), [&](const SchedGroup &x) { return x.sched == s->sched; });
+        if (g == groups.end()) { groups.emplace_back(); g = groups.end() - 1; g->sched = s->sched; }
+        g->ss.push_back(s);
+        if (pcm16) { g->pcm.push_back(pcm16[i]); g->counts.push_back(short_counts[i]); }
+    }
+    return groups;
+}
+
+void deliver_sync_events_all(size_t n, AprilASRSession *sessions)
+{
+    for (size_t i = 0; i < n; ++i) if (sessions[i]->s.sync_mode) sessions[i]->s.sched->deliver_sync_events(&sessions[i]->s);
+}
+
+// a group feed: each scheduler's sessions are submitted at once so that they step together; every GPU is queued first (no wait),
+// then `wait` runs per group, so the GPUs work concurrently
+template <class Wait> void feed_groups(size_t n, AprilASRSession *sessions, const short *const *pcm16, const size_t *short_counts, bool borrow, Wait wait)
+{
+    std::vector<SchedGroup> groups = group_by_scheduler(n, sessions, pcm16, short_counts);
+    for (SchedGroup &g : groups) g.sched->submit((int)g.ss.size(), g.ss.data(), g.pcm.data(), g.counts.data(), false, false, borrow);
+    for (SchedGroup &g : groups) wait(g);
+    deliver_sync_events_all(n, sessions);
+}
 }  // namespace
 
 namespace {
@@ -282,9 +378,7 @@ AprilASRModel aam_create_model(const char *model_path)
 {
     if (!g_inited) { LOGE("aam: not initialised (call aam_api_init; a HIP device is required)"); return nullptr; }
     AprilASRModel_i *h = new AprilASRModel_i();
-    std::string err;
-    if (!load_april_file(model_path, h->m.host, err) || !pad_host_model(h->m.host, err)) { LOGE("aam: failed to load %s: %s", model_path ? model_path : "(null)", err.c_str()); delete h; return nullptr; }
-    plan_layout(h->m.host.dims, !h->m.host.dec_conv_b.empty(), h->m.layout);
+    if (!load_model_file(model_path, h->m)) { delete h; return nullptr; }
     std::vector<float> blob;
     pack_weights(h->m.host, h->m.layout, blob);
     if (!build_runtime(h->m, blob.data(), nullptr)) { delete h; return nullptr; }
@@ -298,13 +392,9 @@ AprilASRModel aam_create_model(const char *model_path)
 AprilASRModel aprilx_model_load_host(const char *model_path)
 {
     AprilASRModel_i *h = new AprilASRModel_i();
-    std::string err;
-    if (!load_april_file(model_path, h->m.host, err) || !pad_host_model(h->m.host, err)) { LOGE("aam: failed to load %s: %s", model_path ? model_path : "(null)", err.c_str()); delete h; return nullptr; }
-    plan_layout(h->m.host.dims, !h->m.host.dec_conv_b.empty(), h->m.layout);
+    if (!load_model_file(model_path, h->m)) { delete h; return nullptr; }
     pack_weights(h->m.host, h->m.layout, h->m.host_blob);
-    const ModelParams &P = h->m.host.params;
-    if (!build_fbank_tables(P.sample_rate, P.frame_shift_ms, P.frame_length_ms, P.mel_features, P.round_pow2 != 0, P.mel_low, P.mel_high, h->m.ftab)) { delete h; return nullptr; }
-    h->m.tok_class = classify_tokens(P);
+    if (!build_host_tables(h->m)) { delete h; return nullptr; }
     free_host_weights(h->m.host);
     return h;
 }
@@ -410,9 +500,7 @@ const char *aprilx_model_token(AprilASRModel model, int32_t id)
 
 size_t aprilx_model_blob_size(AprilASRModel model)
 {
-    const std::string meta = make_meta(model->m);
-    const size_t woff = (sizeof(BlobHeader) + meta.size() + 255) & ~(size_t)255;
-    return woff + model->m.layout.total * 4;
+    return blob_weights_offset(make_meta(model->m).size()) + model->m.layout.total * 4;
 }
 
 int aprilx_model_export_blob(AprilASRModel model, void *dst, size_t dst_size)
@@ -422,7 +510,7 @@ int aprilx_model_export_blob(AprilASRModel model, void *dst, size_t dst_size)
     BlobHeader hd;
     memcpy(hd.magic, "APXBLOB2", 8);
     hd.meta_bytes = meta.size(); hd.weight_floats = model->m.layout.total;
-    hd.weights_offset = (sizeof(BlobHeader) + meta.size() + 255) & ~(size_t)255;
+    hd.weights_offset = blob_weights_offset(meta.size());
     if (dst_size < hd.weights_offset + hd.weight_floats * 4) return -1;
     memset(dst, 0, (size_t)hd.weights_offset);
     memcpy(dst, &hd, sizeof hd);
@@ -439,10 +527,7 @@ int aprilx_model_save_blob(AprilASRModel model, const char *path)
     if (!model || !path) return -1;
     std::vector<char> buf(aprilx_model_blob_size(model));
     if (aprilx_model_export_blob(model, buf.data(), buf.size()) != 0) return -1;
-    FILE *f = fopen(path, "wb");
-    if (!f) { LOGE("aprilx: cannot write '%s'", path); return -1; }
-    const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
-    return (fclose(f) == 0 && ok) ? 0 : -1;
+    return write_file(path, buf.data(), buf.size());
 }
 
 // The fp16 cache file (BASELINE configs[4]): same header and metadata, magic "APXBL16B"; the payload walks the blob's float
@@ -458,37 +543,26 @@ int aprilx_model_save_blob_f16(AprilASRModel model, const char *path)
     const float *w = (const float *)(full.data() + hd.weights_offset);
     std::string out(full.data(), (size_t)hd.weights_offset);
     memcpy(&out[0], "APXBL16B", 8);
-    size_t pos = 0;
-    auto raw = [&](size_t upto) { if (upto > pos) out.append((const char *)(w + pos), (upto - pos) * 4); pos = upto; };
-    for (const auto &sec : gemm_sections(model->m.layout)) {
-        raw(sec.first);
-        std::vector<_Float16> h(sec.second);
-        for (size_t i = 0; i < sec.second; ++i) h[i] = (_Float16)w[sec.first + i];
-        out.append((const char *)h.data(), h.size() * 2);
-        pos = sec.first + sec.second;
-    }
-    raw((size_t)hd.weight_floats);
-    FILE *f = fopen(path, "wb");
-    if (!f) { LOGE("aprilx: cannot write '%s'", path); return -1; }
-    const bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
-    return (fclose(f) == 0 && ok) ? 0 : -1;
+    walk_f16_payload(model->m.layout, (size_t)hd.weight_floats, [&](size_t first, size_t n, bool half) {
+        std::vector<_Float16> h(half ? n : 0);
+        for (size_t i = 0; i < h.size(); ++i) h[i] = (_Float16)w[first + i];
+        if (half) out.append((const char *)h.data(), n * 2); else out.append((const char *)(w + first), n * 4);
+        return true;
+    });
+    return write_file(path, out.data(), out.size());
 }
 
 AprilASRModel aprilx_model_load_blob(const char *path)
 {
-    FILE *f = path ? fopen(path, "rb") : nullptr;
-    if (!f) { LOGE("aprilx: cannot read '%s'", path ? path : "(null)"); return nullptr; }
     std::vector<char> buf;
-    if (fseek(f, 0, SEEK_END) == 0) { const long n = ftell(f); if (n > 0) { buf.resize((size_t)n); rewind(f); if (fread(buf.data(), 1, buf.size(), f) != buf.size()) buf.clear(); } }
-    fclose(f);
+    const int rc = read_file(path, buf);
+    if (rc == -1) { LOGE("aprilx: cannot read '%s'", path ? path : "(null)"); return nullptr; }
+    if (rc != 0 || buf.empty()) return nullptr;
     if (buf.size() >= sizeof(BlobHeader) && memcmp(buf.data(), "APXBL16B", 8) == 0) {
         // expand to the fp32 blob; only the fp16-operand engine may use the rounded matrices
-        if (g_inited) {
-            const char *pv = env_str("APRIL_PRECISION");
-            if (!pv || !(std::string(pv) == "f16" || std::string(pv) == "fp16" || std::string(pv) == "half")) { LOGE("aprilx: '%s' is an fp16 cache file: set APRIL_PRECISION=f16 (the fp32 engine needs the fp32 file)", path); return nullptr; }
-        }
+        if (g_inited && env_precision() != 1) { LOGE("aprilx: '%s' is an fp16 cache file: set APRIL_PRECISION=f16 (the fp32 engine needs the fp32 file)", path); return nullptr; }
         BlobHeader hd; memcpy(&hd, buf.data(), sizeof hd);
-        if (hd.weights_offset > buf.size() || hd.meta_bytes > buf.size() || sizeof hd + hd.meta_bytes > hd.weights_offset || hd.weight_floats > ((uint64_t)1 << 34)) { LOGE("aprilx: bad blob"); return nullptr; }
+        if (!blob_header_ok(hd, buf.size()) || hd.weight_floats > ((uint64_t)1 << 34)) { LOGE("aprilx: bad blob"); return nullptr; }
         AprilASRModel_i probe;
         if (!parse_meta(buf.data() + sizeof hd, (size_t)hd.meta_bytes, probe.m) || probe.m.layout.total != hd.weight_floats) { LOGE("aprilx: blob metadata invalid"); return nullptr; }
         std::vector<char> full((size_t)hd.weights_offset + (size_t)hd.weight_floats * 4);
@@ -496,21 +570,18 @@ AprilASRModel aprilx_model_load_blob(const char *path)
         memcpy(full.data(), "APXBLOB2", 8);
         float *w = (float *)(full.data() + hd.weights_offset);
         const char *src = buf.data() + hd.weights_offset, *end = buf.data() + buf.size();
-        size_t pos = 0;
-        bool ok = true;
-        auto raw = [&](size_t upto) { if (upto > pos) { const size_t n = (upto - pos) * 4; if ((size_t)(end - src) < n) { ok = false; return; } memcpy(w + pos, src, n); src += n; } pos = upto; };
-        for (const auto &sec : gemm_sections(probe.m.layout)) {
-            raw(sec.first);
-            if (!ok || (size_t)(end - src) < sec.second * 2) { ok = false; break; }
-            const _Float16 *h = (const _Float16 *)src;
-            for (size_t i = 0; i < sec.second; ++i) w[sec.first + i] = (float)h[i];
-            src += sec.second * 2; pos = sec.first + sec.second;
-        }
-        if (ok) raw((size_t)hd.weight_floats);
+        const bool ok = walk_f16_payload(probe.m.layout, (size_t)hd.weight_floats, [&](size_t first, size_t n, bool half) {
+            const size_t bytes = n * (half ? 2 : 4);
+            if ((size_t)(end - src) < bytes) return false;
+            if (!half) memcpy(w + first, src, bytes);
+            else for (size_t i = 0; i < n; ++i) w[first + i] = (float)((const _Float16 *)src)[i];
+            src += bytes;
+            return true;
+        });
         if (!ok || src != end) { LOGE("aprilx: fp16 blob payload size mismatch"); return nullptr; }
         return aprilx_model_from_blob(full.data(), full.size(), 0);
     }
-    return buf.empty() ? nullptr : aprilx_model_from_blob(buf.data(), buf.size(), 0);
+    return aprilx_model_from_blob(buf.data(), buf.size(), 0);
 }
 
 AprilASRModel aprilx_model_from_blob(const void *blob, size_t size, int blob_is_device_ptr)
@@ -527,8 +598,7 @@ AprilASRModel aprilx_model_from_blob(const void *blob, size_t size, int blob_is_
     if (!host_only && g_devices.empty()) { LOGE("aprilx: no device selected"); return nullptr; }
     if (blob_is_device_ptr) { HipLegacyLock legacy; HIP_CHECK(hipSetDevice(g_devices[0])); HIP_CHECK(hipMemcpy(&hd, blob, sizeof hd, hipMemcpyDeviceToHost)); }
     else memcpy(&hd, blob, sizeof hd);
-    if (memcmp(hd.magic, "APXBLOB2", 8) != 0 || hd.weights_offset > size || hd.weight_floats > (size - hd.weights_offset) / 4 ||
-        hd.meta_bytes > size || sizeof hd + hd.meta_bytes > hd.weights_offset) { LOGE("aprilx: bad blob"); return nullptr; }
+    if (memcmp(hd.magic, "APXBLOB2", 8) != 0 || !blob_header_ok(hd, size) || hd.weight_floats > (size - hd.weights_offset) / 4) { LOGE("aprilx: bad blob"); return nullptr; }
     std::string meta((size_t)hd.meta_bytes, '\0');
     if (blob_is_device_ptr) { HipLegacyLock legacy; HIP_CHECK(hipMemcpy(&meta[0], (const char *)blob + sizeof hd, meta.size(), hipMemcpyDeviceToHost)); }
     else memcpy(&meta[0], (const char *)blob + sizeof hd, meta.size());
@@ -536,10 +606,8 @@ AprilASRModel aprilx_model_from_blob(const void *blob, size_t size, int blob_is_
     if (!parse_meta(meta.data(), meta.size(), h->m) || h->m.layout.total != hd.weight_floats) { LOGE("aprilx: blob metadata invalid"); delete h; return nullptr; }
     const float *w = (const float *)((const char *)blob + hd.weights_offset);
     if (host_only) {
-        const ModelParams &P = h->m.host.params;
         h->m.host_blob.assign(w, w + hd.weight_floats);
-        if (!build_fbank_tables(P.sample_rate, P.frame_shift_ms, P.frame_length_ms, P.mel_features, P.round_pow2 != 0, P.mel_low, P.mel_high, h->m.ftab)) { delete h; return nullptr; }
-        h->m.tok_class = classify_tokens(P);
+        if (!build_host_tables(h->m)) { delete h; return nullptr; }
         return h;
     }
     // a device blob lives on g_devices[0]: engine 0 copies it device-to-device, further devices receive it over RCCL
@@ -630,7 +698,7 @@ AprilASRModel aprilx_model_broadcast(AprilASRModel root_model, int rank, int wor
     if (r != ncclSuccess) { if (rank != 0 && h) delete h; return fail("ncclBroadcast(weights)", r); }
     if (!h) return nullptr;
     if (rank != 0 && !distribute_weights(h->m)) { delete h; return nullptr; }
-    h->m.load.broadcast_ms = t3 - t2; h->m.load.comm_init_ms = t1 - t0; h->m.load.broadcast_bytes = (size_t)hdr[1] * 4; h->m.load.ranks = world; h->m.load.used_rccl = 1;
+    set_load_info(h->m, t3 - t2, t1 - t0, (size_t)hdr[1], world, 1);
     return h;
 }
 
@@ -644,60 +712,28 @@ int aprilx_model_load_info(AprilASRModel model, AprilxLoadInfo *out)
 
 void aprilx_feed_many(size_t n, AprilASRSession *sessions, const short *const *pcm16, const size_t *short_counts)
 {
-    if (n == 0) return;
-    // group by scheduler (GPU); each group is submitted at once so the sessions step together
-    std::vector<Scheduler *> scheds;
-    for (size_t i = 0; i < n; ++i) { Scheduler *sc = sessions[i]->s.sched; if (std::find(scheds.begin(), scheds.end(), sc) == scheds.end()) scheds.push_back(sc); }
-    std::vector<std::vector<Session *>> groups(scheds.size());
-    std::vector<std::vector<const short *>> gp(scheds.size());
-    std::vector<std::vector<size_t>> gc(scheds.size());
-    for (size_t i = 0; i < n; ++i) {
-        size_t k = (size_t)(std::find(scheds.begin(), scheds.end(), sessions[i]->s.sched) - scheds.begin());
-        groups[k].push_back(&sessions[i]->s); gp[k].push_back(pcm16[i]); gc[k].push_back(short_counts[i]);
-    }
-    // queue on every GPU first (no wait), then wait, so GPUs run concurrently
-    for (size_t k = 0; k < scheds.size(); ++k) scheds[k]->submit((int)groups[k].size(), groups[k].data(), gp[k].data(), gc[k].data(), false, false, /*borrow=*/true);
-    for (size_t k = 0; k < scheds.size(); ++k) scheds[k]->wait_idle_many(groups[k].data(), (int)groups[k].size());
-    for (size_t i = 0; i < n; ++i) if (sessions[i]->s.sync_mode) sessions[i]->s.sched->deliver_sync_events(&sessions[i]->s);
+    // the sessions' buffers are lent until every session is idle again
+    feed_groups(n, sessions, pcm16, short_counts, /*borrow=*/true, [](SchedGroup &g) { g.sched->wait_idle_many(g.ss.data(), (int)g.ss.size()); });
 }
 
 void aprilx_feed_many_pipelined(size_t n, AprilASRSession *sessions, const short *const *pcm16, const size_t *short_counts, int depth)
 {
-    if (n == 0) return;
-    if (depth < 1) depth = 1;
-    std::vector<Scheduler *> scheds;
-    for (size_t i = 0; i < n; ++i) { Scheduler *sc = sessions[i]->s.sched; if (std::find(scheds.begin(), scheds.end(), sc) == scheds.end()) scheds.push_back(sc); }
-    std::vector<std::vector<Session *>> groups(scheds.size());
-    std::vector<std::vector<const short *>> gp(scheds.size());
-    std::vector<std::vector<size_t>> gc(scheds.size());
-    for (size_t i = 0; i < n; ++i) {
-        size_t k = (size_t)(std::find(scheds.begin(), scheds.end(), sessions[i]->s.sched) - scheds.begin());
-        groups[k].push_back(&sessions[i]->s); gp[k].push_back(pcm16[i]); gc[k].push_back(short_counts[i]);
-    }
-    // the samples are copied into the sessions' queues (the caller may reuse its buffers at once), every GPU first, then the wait
-    for (size_t k = 0; k < scheds.size(); ++k) scheds[k]->submit((int)groups[k].size(), groups[k].data(), gp[k].data(), gc[k].data(), false, false, /*borrow=*/false);
-    for (size_t k = 0; k < scheds.size(); ++k) scheds[k]->wait_backlog(groups[k].data(), (int)groups[k].size(), (uint64_t)(depth - 1));
-    for (size_t i = 0; i < n; ++i) if (sessions[i]->s.sync_mode) sessions[i]->s.sched->deliver_sync_events(&sessions[i]->s);
+    // the samples are copied into the sessions' queues (the caller may reuse its buffers at once)
+    const uint64_t max_open = (uint64_t)(std::max(depth, 1) - 1);
+    feed_groups(n, sessions, pcm16, short_counts, /*borrow=*/false, [&](SchedGroup &g) { g.sched->wait_backlog(g.ss.data(), (int)g.ss.size(), max_open); });
 }
 
 void aprilx_drain_many(size_t n, AprilASRSession *sessions)
 {
-    if (n == 0) return;
-    std::vector<Scheduler *> scheds;
-    for (size_t i = 0; i < n; ++i) { Scheduler *sc = sessions[i]->s.sched; if (std::find(scheds.begin(), scheds.end(), sc) == scheds.end()) scheds.push_back(sc); }
-    for (Scheduler *sc : scheds) {
-        std::vector<Session *> g;
-        for (size_t i = 0; i < n; ++i) if (sessions[i]->s.sched == sc) g.push_back(&sessions[i]->s);
-        sc->wait_backlog(g.data(), (int)g.size(), 0);
-    }
-    for (size_t i = 0; i < n; ++i) if (sessions[i]->s.sync_mode) sessions[i]->s.sched->deliver_sync_events(&sessions[i]->s);
+    for (SchedGroup &g : group_by_scheduler(n, sessions, nullptr, nullptr)) g.sched->wait_backlog(g.ss.data(), (int)g.ss.size(), 0);
+    deliver_sync_events_all(n, sessions);
 }
 
 void aprilx_flush_many(size_t n, AprilASRSession *sessions)
 {
     for (size_t i = 0; i < n; ++i) { Session *s = &sessions[i]->s; s->sched->submit(1, &s, nullptr, nullptr, true, false); }
     for (size_t i = 0; i < n; ++i) aprilx_session_drain(sessions[i]);
-    for (size_t i = 0; i < n; ++i) if (sessions[i]->s.sync_mode) sessions[i]->s.sched->deliver_sync_events(&sessions[i]->s);
+    deliver_sync_events_all(n, sessions);
 }
 
 void aprilx_session_drain(AprilASRSession session)
@@ -843,7 +879,7 @@ void aprilx_model_profile(AprilASRModel model, int enable)
 
 struct AprilxGreedy_i {
     Greedy g; AprilRecognitionResultHandler handler; void *ud; std::vector<Event> ev;
-    void flush_events() { for (auto &e : ev) handler(ud, (AprilResultType)e.type, e.tokens.size(), e.tokens.empty() ? nullptr : e.tokens.data()); ev.clear(); }
+    void flush_events() { deliver_events(ev, handler, ud); }
 };
 
 AprilxGreedy aprilx_greedy_create(AprilASRModel model, AprilRecognitionResultHandler handler, void *userdata)
@@ -888,18 +924,12 @@ int aprilx_model_fbank_tables(AprilASRModel model, float *window, float *mel)
 
 int aprilx_probe_file(const char *path, char *err, size_t err_cap)
 {
-    FILE *fd = fopen(path, "rb");
+    std::vector<uint8_t> blob;
     std::string e;
-    if (!fd) e = "cannot open file";
-    else {
-        fseek(fd, 0, SEEK_END); long sz = ftell(fd); fseek(fd, 0, SEEK_SET);
-        std::vector<uint8_t> blob(sz > 0 ? (size_t)sz : 0);
-        size_t got = blob.empty() ? 0 : fread(blob.data(), 1, blob.size(), fd);
-        fclose(fd);
-        ContainerInfo info;
-        if (got != blob.size()) e = "short read";
-        else if (parse_container(blob, info, e)) { if (err && err_cap) err[0] = 0; return 0; }
-    }
+    ContainerInfo info;
+    const int rc = read_file(path, blob);
+    if (rc != 0) e = rc == -1 ? "cannot open file" : "short read";
+    else if (parse_container(blob, info, e)) { if (err && err_cap) err[0] = 0; return 0; }
     if (err && err_cap) { strncpy(err, e.c_str(), err_cap - 1); err[err_cap - 1] = 0; }
     return -1;
 }

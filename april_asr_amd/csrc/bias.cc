@@ -20,7 +20,7 @@ struct AprilASRModel_i { Model m; };          // (the same definitions as april_
 struct AprilASRSession_i { Session s; };
 struct AprilxGreedy_i {
     Greedy g; AprilRecognitionResultHandler handler; void *ud; std::vector<Event> ev;
-    void flush_events() { for (auto &e : ev) handler(ud, (AprilResultType)e.type, e.tokens.size(), e.tokens.empty() ? nullptr : e.tokens.data()); ev.clear(); }
+    void flush_events() { deliver_events(ev, handler, ud); }
 };
 struct AprilxBias_i { std::shared_ptr<const BiasSet> set; };
 

@@ -1,9 +1,7 @@
 // See session.h.
 #include "session.h"
 #include <algorithm>
-#include <tuple>
 #include <cstring>
-#include <chrono>
 #include "common.h"
 #include "env.h"
 
@@ -215,6 +213,22 @@ void Greedy::finish_flush(std::vector<Event> &out)
     emit_silence(out);
 }
 
+void FrameBook::append_span(size_t l0, size_t l1, Parts &parts) const
+{
+    const size_t fsz = fifo.size();
+    if (l0 < fsz) parts.emplace_back(fifo.data() + l0, std::min(l1, fsz) - l0);
+    if (l1 > fsz) parts.emplace_back(ext + (std::max(l0, fsz) - fsz), l1 - std::max(l0, fsz));
+}
+
+FbankFrameDesc FrameBook::write_row(int slot, int pcm_off)
+{
+    FbankFrameDesc d; d.slot = slot; d.ring_row = head; d.pcm_off = pcm_off;
+    head = (head + 1) % ring_frames;
+    rows_written += 1;
+    avail += 1;
+    return d;
+}
+
 void FrameBook::compact()
 {
     if (ext) return;                                   // positions may point into the lent buffer: settle() does it
@@ -349,7 +363,7 @@ static int host_helpers()
 
 static int env_0_1M(const char *name, int def) { return std::max(0, std::min(1000000, env_int(name, def))); }
 
-Scheduler::Scheduler(Model *m, Engine *e) : model_(m), eng_(e), pool_(host_helpers())
+Scheduler::Scheduler(Model *m, Engine *e) : eng_(e), stride_ms_(m->host.params.segment_step * m->host.params.frame_shift_ms), pool_(host_helpers())
 {
     spin_step_us_ = env_0_1M("APRIL_SPIN_STEP_US", 1000);     // (1 ms: a client that pauses for a barrier or a sync between two feeds finds the thread awake; 100 us until round 3)
     spin_wait_us_ = env_0_1M("APRIL_SPIN_WAIT_US", 3000);
@@ -361,14 +375,15 @@ Scheduler::Scheduler(Model *m, Engine *e) : model_(m), eng_(e), pool_(host_helpe
 
 static inline void cpu_relax() { __builtin_ia32_pause(); }
 
-// caller side: poll the tick counter for a bounded time before sleeping on the condition variable
-void Scheduler::spin_for_done(uint64_t seen)
+// both sides of the hand-over: poll a sequence counter (callers the tick counter done_seq_, the stepping thread work_seq_) until it
+// moves away from `seen`, for at most `budget_us`, before sleeping on the condition variable
+static void spin_while_unchanged(const std::atomic<uint64_t> &seq, uint64_t seen, int budget_us)
 {
-    if (spin_wait_us_ <= 0) return;
+    if (budget_us <= 0) return;
     const auto t0 = std::chrono::steady_clock::now();
-    while (done_seq_.load(std::memory_order_acquire) == seen) {
+    while (seq.load(std::memory_order_acquire) == seen) {
         for (int i = 0; i < 64; ++i) cpu_relax();
-        if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > spin_wait_us_) break;
+        if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > budget_us) break;
     }
 }
 
@@ -448,7 +463,7 @@ void Scheduler::submit(int n, Session *const *ss, const short *const *pcm, const
     cv_work_.notify_one();
     for (Session *s : overflowed) s->handler(s->userdata, APRIL_RESULT_ERROR_CANT_KEEP_UP, 0, nullptr);
     if (!wait) return;
-    spin_for_done(done_seen);
+    spin_while_unchanged(done_seq_, done_seen, spin_wait_us_);
     std::unique_lock<std::mutex> lk(mu_);
     cv_done_.wait(lk, [&] {
         for (int i = 0; i < n; ++i) if (tickets[(size_t)i] && ss[i]->completed < tickets[(size_t)i] && !ss[i]->closing) return false;
@@ -459,62 +474,59 @@ void Scheduler::submit(int n, Session *const *ss, const short *const *pcm, const
 void Scheduler::wait_idle(Session *s)
 {
     std::unique_lock<std::mutex> lk(mu_);
-    cv_done_.wait(lk, [&] { return s->closing || (s->completed >= s->submitted && !s->busy && !s->fed && !s->flush_requested); });
+    cv_done_.wait(lk, [&] { return s->idle(); });
+}
+
+template <class Apply> bool Scheduler::configure(Session *s, Apply apply)
+{
+    wait_idle(s);
+    std::lock_guard<std::mutex> g(mu_);
+    return s->settable() && apply();
 }
 
 bool Scheduler::set_input_rate(Session *s, const ResampleSpec *spec)
 {
-    wait_idle(s);
-    std::lock_guard<std::mutex> g(mu_);
-    if (s->closing || s->busy || s->fed || s->flush_requested || !s->inbox.empty() || s->borrow_cnt || s->seg_open || s->flush_phase) return false;
-    s->fb.set_rate(spec);
-    s->ring_limit = spec ? (size_t)(48000ull * spec->in_rate / spec->out_rate) : 48000;
-    return true;
+    return configure(s, [&] {
+        s->fb.set_rate(spec);
+        s->ring_limit = spec ? (size_t)(48000ull * spec->in_rate / spec->out_rate) : 48000;
+        return true;
+    });
 }
 
 bool Scheduler::set_confidence(Session *s, int k)
 {
-    wait_idle(s);
-    std::lock_guard<std::mutex> g(mu_);
-    if (s->closing || s->busy || s->fed || s->flush_requested || !s->inbox.empty() || s->borrow_cnt || s->seg_open || s->flush_phase) return false;
-    if (k == s->greedy.confidence()) return true;
-    s->greedy.set_confidence(k);
-    eng_->set_slot_confidence(s->slot, k);          // (queued: the stepping thread applies it before the session's next flight)
-    return true;
+    return configure(s, [&] {
+        if (k == s->greedy.confidence()) return true;
+        s->greedy.set_confidence(k);
+        eng_->set_slot_confidence(s->slot, k);          // (queued: the stepping thread applies it before the session's next flight)
+        return true;
+    });
 }
 
 bool Scheduler::set_bias(Session *s, std::shared_ptr<const BiasSet> set)
 {
-    wait_idle(s);
-    std::lock_guard<std::mutex> g(mu_);
-    if (s->closing || s->busy || s->fed || s->flush_requested || !s->inbox.empty() || s->borrow_cnt || s->seg_open || s->flush_phase) return false;
-    if (set.get() == s->greedy.bias() && s->greedy.bias_state() == 0) return true;
-    if (!eng_->set_slot_bias(s->slot, set)) return false;      // (queued: the stepping thread applies it before the session's next flight)
-    s->greedy.set_bias(std::move(set));
-    return true;
+    return configure(s, [&] {
+        if (set.get() == s->greedy.bias() && s->greedy.bias_state() == 0) return true;
+        if (!eng_->set_slot_bias(s->slot, set)) return false;      // (queued: the stepping thread applies it before the session's next flight)
+        s->greedy.set_bias(std::move(set));
+        return true;
+    });
 }
 
 void Scheduler::wait_idle_many(Session *const *ss, int n)
 {
-    {   // called right after a submit: poll for the end of the tick that took the work before sleeping
-        uint64_t seen;
-        bool idle;
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            seen = done_seq_.load(std::memory_order_acquire);      // under the lock, as in submit()
-            idle = true;
-            for (int i = 0; i < n && idle; ++i) { const Session *s = ss[i]; idle = s->closing || (s->completed >= s->submitted && !s->busy && !s->fed && !s->flush_requested); }
-        }
-        if (!idle) spin_for_done(seen);
-    }
-    std::unique_lock<std::mutex> lk(mu_);
-    cv_done_.wait(lk, [&] {
-        for (int i = 0; i < n; ++i) {
-            const Session *s = ss[i];
-            if (!(s->closing || (s->completed >= s->submitted && !s->busy && !s->fed && !s->flush_requested))) return false;
-        }
+    auto all_idle = [&] {
+        for (int i = 0; i < n; ++i) if (!ss[i]->idle()) return false;
         return true;
-    });
+    };
+    std::unique_lock<std::mutex> lk(mu_);
+    if (!all_idle()) {   // called right after a submit: poll for the end of the tick that took the work before sleeping
+        const uint64_t seen = done_seq_.load(std::memory_order_acquire);      // under the lock, as in submit()
+        lk.unlock();
+        spin_while_unchanged(done_seq_, seen, spin_wait_us_);
+        lk.lock();
+    }
+    cv_done_.wait(lk, all_idle);
 }
 
 void Scheduler::wait_backlog(Session *const *ss, int n, uint64_t max_open)
@@ -530,18 +542,24 @@ void Scheduler::wait_backlog(Session *const *ss, int n, uint64_t max_open)
             if (ok()) return;
             seen = done_seq_.load(std::memory_order_acquire);      // under the lock, as in submit()
         }
-        spin_for_done(seen);
+        spin_while_unchanged(done_seq_, seen, spin_wait_us_);
         if (done_seq_.load(std::memory_order_acquire) != seen) continue;
         std::unique_lock<std::mutex> lk(mu_);
         cv_done_.wait(lk, [&] { return ok() || done_seq_.load(std::memory_order_acquire) != seen; });
     }
 }
 
+void deliver_events(std::vector<Event> &ev, AprilRecognitionResultHandler handler, void *userdata)
+{
+    for (auto &e : ev) handler(userdata, (AprilResultType)e.type, e.tokens.size(), e.tokens.empty() ? nullptr : e.tokens.data());
+    ev.clear();
+}
+
 void Scheduler::deliver_sync_events(Session *s)
 {
     std::vector<Event> ev;
     { std::lock_guard<std::mutex> g(mu_); ev.swap(s->done_events); }
-    for (auto &e : ev) s->handler(s->userdata, (AprilResultType)e.type, e.tokens.size(), e.tokens.empty() ? nullptr : e.tokens.data());
+    deliver_events(ev, s->handler, s->userdata);
 }
 
 // One stepping thread, TWO flights in the air.  A flight is launched (frames cut, chunk steps enqueued, record copy + event
@@ -555,13 +573,7 @@ void Scheduler::deliver_sync_events(Session *s)
 bool Scheduler::collect(std::vector<Session *> &work, std::vector<uint64_t> &taken, bool block, uint64_t &work_seen)
 {
     work.clear(); taken.clear();
-    if (block && spin_step_us_ > 0) {           // a feed usually follows the previous one within microseconds: poll before sleeping
-        const auto t0 = std::chrono::steady_clock::now();
-        while (work_seq_.load(std::memory_order_acquire) == work_seen) {
-            for (int i = 0; i < 64; ++i) cpu_relax();
-            if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > spin_step_us_) break;
-        }
-    }
+    if (block) spin_while_unchanged(work_seq_, work_seen, spin_step_us_);      // a feed usually follows the previous one within microseconds
     Lap lap;
     std::unique_lock<std::mutex> lk(mu_);
     auto have = [&] {
@@ -663,7 +675,7 @@ void Scheduler::complete_flight(Flight &f)
         const auto from = (have_prev_done_ && prev_done_ > f.t0) ? prev_done_ : f.t0;
         const double tick_ms = std::chrono::duration<double, std::milli>(now - from).count();
         prev_done_ = now; have_prev_done_ = true;
-        const double stride_ms = (double)(model_->host.params.segment_step * model_->host.params.frame_shift_ms);
+        const double stride_ms = (double)stride_ms_;
         for (size_t i = 0; i < work.size(); ++i) {
             Session *s = work[i];
             const uint64_t n = f.chunks1[i] - f.chunks0[i];
@@ -674,10 +686,7 @@ void Scheduler::complete_flight(Flight &f)
         }
     }
     // async sessions: deliver on this (library) thread, outside the lock
-    for (Session *s : work) if (!s->sync_mode) {
-        for (auto &e : s->events) s->handler(s->userdata, (AprilResultType)e.type, e.tokens.size(), e.tokens.empty() ? nullptr : e.tokens.data());
-        s->events.clear();
-    }
+    for (Session *s : work) if (!s->sync_mode) deliver_events(s->events, s->handler, s->userdata);
     {
         std::lock_guard<std::mutex> g(mu_);
         for (size_t i = 0; i < work.size(); ++i) {
@@ -763,7 +772,6 @@ void Scheduler::stage_resampled(const FrameBook &fb, int64_t first, int64_t last
 {
     const ResampleSpec &r = *fb.rs;
     pcm_parts_.emplace_back(nullptr, (size_t)(last_end - first));
-    const size_t fsz = fb.fifo.size();
     for (size_t si = 0; si < fb.segs.size(); ++si) {
         const FrameBook::RsSeg &g = fb.segs[si];
         const int64_t lo = std::max(first, g.pos);
@@ -781,9 +789,8 @@ void Scheduler::stage_resampled(const FrameBook &fb, int64_t first, int64_t last
         }
         d.in_base = k_lo; d.in_n = (int32_t)std::max<int64_t>(0, k_hi - k_lo); d.in_off = (int32_t)staged_in;
         if (d.in_n > 0) {
-            const size_t l0 = (size_t)(g.in_start + k_lo - fb.in_drop), l1 = l0 + (size_t)d.in_n;      // fifo ++ ext
-            if (l0 < fsz) in_parts_.emplace_back(fb.fifo.data() + l0, std::min(l1, fsz) - l0);
-            if (l1 > fsz) in_parts_.emplace_back(fb.ext + (std::max(l0, fsz) - fsz), l1 - std::max(l0, fsz));
+            const size_t l0 = (size_t)(g.in_start + k_lo - fb.in_drop);
+            fb.append_span(l0, l0 + (size_t)d.in_n, in_parts_);
             staged_in += (size_t)d.in_n;
         }
         rdesc_.push_back(d);
@@ -820,23 +827,14 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
             int cut = 0;
             // (up to a ring's worth per pass: a long feed then yields ~70 chunks per session at once for the layer-major step)
             while (fb.can_cut() && cut < fb.ring_frames && staged + staged_in + need(cut + 1) <= stage_limit) {
-                FbankFrameDesc d; d.slot = s->slot; d.ring_row = fb.head; d.pcm_off = (int)(base + (size_t)cut * fb.shift);
-                desc_.push_back(d);
-                fb.head = (fb.head + 1) % fb.ring_frames;
-                fb.rows_written += 1;
-                fb.avail += 1;
+                desc_.push_back(fb.write_row(s->slot, (int)(base + (size_t)cut * fb.shift)));
                 fb.avail_shadow = fb.avail;                       // fbank.c:300
                 fb.fifo_pos += (size_t)fb.shift;
                 ++cut;
             }
             const size_t last_end = first + (size_t)(cut - 1) * fb.shift + (size_t)fb.padded;
-            if (fb.rs) {
-                stage_resampled(fb, (int64_t)first, (int64_t)last_end, base, staged_in);
-            } else {
-                const size_t fsz = fb.fifo.size();
-                if (first < fsz) pcm_parts_.emplace_back(fb.fifo.data() + first, std::min(last_end, fsz) - first);          // (contiguous in staging)
-                if (last_end > fsz) pcm_parts_.emplace_back(fb.ext + (std::max(first, fsz) - fsz), last_end - std::max(first, fsz));
-            }
+            if (fb.rs) stage_resampled(fb, (int64_t)first, (int64_t)last_end, base, staged_in);
+            else fb.append_span(first, last_end, pcm_parts_);                 // (contiguous in staging)
             staged += last_end - first;
             s->compact_pending = true;                 // the fifo must not move until the window has been staged
             progressed = true;
@@ -863,13 +861,7 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
                     pad += need; av += need;
                     av -= fb.seg_step; sh -= fb.seg_step;
                 }
-                for (long i = 0; i < pad; ++i) {
-                    FbankFrameDesc d; d.slot = s->slot; d.ring_row = fb.head; d.pcm_off = -1;
-                    desc_.push_back(d);
-                    fb.head = (fb.head + 1) % fb.ring_frames;
-                    fb.rows_written += 1;
-                    fb.avail += 1;                                // padding does not touch the shadow counter
-                }
+                for (long i = 0; i < pad; ++i) desc_.push_back(fb.write_row(s->slot, -1));     // padding does not touch the shadow counter
             } else {
                 s->flush_phase += 1;
             }
@@ -908,25 +900,26 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
     }
 }
 
-// Layer-major step for a group of sessions that all have at least T chunks waiting (a long feed: "whole file at once",
-// reference use case example.cpp:157-216 -> src/april_session.c:431-476).  The encoder does not depend on emitted tokens, so
-// the T chunks of a session go through each layer together; see Engine::lm_step.
-bool Scheduler::step_layer_major(std::vector<Session *> &group, int T, int mode)
+// T consecutive chunks of each of the m sessions of `group` (all have them waiting) as ONE engine step.  STEP_CHUNK: the chunk step
+// (T == 1; reference src/april_session.c:431-476, batched).  STEP_LAYER_MAJOR: a long feed ("whole file at once", reference use case
+// example.cpp:157-216): the encoder does not depend on emitted tokens, so the T chunks of a session go through each layer together, see
+// Engine::lm_step.  STEP_WAVE: the 2..3 chunks of a feed as one wavefront over the layers (Engine::lm_step mode 1).  Row t * m + i of
+// the step is chunk t of session i; its three rounds of records (and traced logits) are at (t * 3 + r) * m + i.
+bool Scheduler::advance(Session *const *group, int m, int T, StepPath path)
 {
-    const int m = (int)group.size();
     const int rows = m * T;
     const NetDims &d = eng_->dims();
-    if (!eng_->flight_has_room(rows + m, 1)) return false;
-    const int stride_ms = model_->host.params.segment_step * model_->host.params.frame_shift_ms;
+    // (the chunk path's caller has asked for the room of all its sub-batches at once)
+    if (path != STEP_CHUNK && !eng_->flight_has_room(rows + m, 1)) return false;
     slots_.clear(); tails_.assign((size_t)rows, 0); now_.assign((size_t)rows, 0);
     bool traced = false;
     for (int i = 0; i < m; ++i) {
-        Session *s = group[(size_t)i];
+        Session *s = group[i];
         FrameBook &fb = s->fb;
         slots_.push_back(s->slot);
         for (int t = 0; t < T; ++t) {
             tails_[(size_t)t * m + i] = (fb.tail + t * fb.seg_step) % fb.ring_frames;          // fbank.c:327-349, T pulls
-            now_[(size_t)t * m + i] = (int)(s->now_ms + (size_t)(t + 1) * stride_ms);         // april_session.c:442-443
+            now_[(size_t)t * m + i] = (int)(s->now_ms + (size_t)(t + 1) * stride_ms_);        // april_session.c:442-443
         }
         fb.tail = (fb.tail + T * fb.seg_step) % fb.ring_frames;
         fb.avail -= (long)T * fb.seg_step;
@@ -934,14 +927,16 @@ bool Scheduler::step_layer_major(std::vector<Session *> &group, int T, int mode)
         if (s->trace_buf) traced = true;
     }
     if (traced) logit_stage_.resize((size_t)3 * rows * d.vocab);
-    const int k = eng_->lm_step(m, T, slots_.data(), tails_.data(), now_.data(), traced ? logit_stage_.data() : nullptr, mode);
+    float *logits = traced ? logit_stage_.data() : nullptr;
+    const int k = path == STEP_CHUNK ? eng_->step(m, slots_.data(), tails_.data(), now_.data(), logits)
+                                     : eng_->lm_step(m, T, slots_.data(), tails_.data(), now_.data(), logits, path == STEP_WAVE ? 1 : 0);
     for (int i = 0; i < m; ++i) {
-        Session *s = group[(size_t)i];
+        Session *s = group[i];
         for (int t = 0; t < T; ++t) {
-            s->now_ms += (size_t)stride_ms;
+            s->now_ms += (size_t)stride_ms_;
             s->chunks++;
             s->replay.push_back(Session::Replay{k, i, m, (uint32_t)s->now_ms, 0, t});
-            if (traced && s->trace_buf) {
+            if (traced && s->trace_buf) {                               // tests: the logits of every round that ran, in order
                 const StepRecord *recs = eng_->records(k);
                 for (int r = 0; r < 3; ++r) {
                     const size_t at = ((size_t)t * 3 + r) * m + i;
@@ -957,16 +952,16 @@ bool Scheduler::step_layer_major(std::vector<Session *> &group, int T, int mode)
         }
     }
     tick_.steps++; tick_.chunks += (uint64_t)rows;
-    if (mode == 1) { tick_.wave_steps++; tick_.wave_chunks += (uint64_t)rows; }
-    else { tick_.lm_steps++; tick_.lm_chunks += (uint64_t)rows; }
+    if (path == STEP_WAVE) { tick_.wave_steps++; tick_.wave_chunks += (uint64_t)rows; }
+    if (path == STEP_LAYER_MAJOR) { tick_.lm_steps++; tick_.lm_chunks += (uint64_t)rows; }
     if ((uint64_t)m > tick_.max_batch_seen) tick_.max_batch_seen = (uint64_t)m;
     return true;
 }
 
+// Who goes where: every ready session advances by at least one chunk, on the path that suits its backlog.
 bool Scheduler::step_chunks(std::vector<Session *> &ready)
 {
     Lap lap;
-    const NetDims &d = eng_->dims();
     const int MB = eng_->max_batch();
     // first use of a session: context = [blank, blank] (already in the slot's device state), run the decoder (april_session.c:432-438)
     slots_.clear();
@@ -977,10 +972,13 @@ bool Scheduler::step_chunks(std::vector<Session *> &ready)
         slots_.push_back(s->slot);
     }
     if (!slots_.empty()) { eng_->decode_rows((int)slots_.size(), slots_.data(), 0); tick_.host_ms[6] += lap(); }
+    struct Enqueued { Lap &lap; double &ms; ~Enqueued() { ms += lap(); } } enqueued{lap, tick_.host_ms[3]};      // on every way out
 
     // sessions with a long backlog (a whole file fed at once) go layer-major, in groups that fit the work buffers
     std::vector<Session *> one, lm;
     auto waiting = [](const Session *s) { return (int)((s->fb.avail - s->fb.seg_count) / s->fb.seg_step + 1); };
+    // the chunks m sessions can advance together: what the work buffers hold, and what every one of them has waiting
+    auto depth = [&](Session *const *g, int m) { int T = MB / m; for (int i = 0; i < m; ++i) T = std::min(T, waiting(g[i])); return T; };
     // (fp16 tile engines: layer-major since round 4 -- the tile kernels have the two halves of the gate GEMM; APRIL_F16_LM=0 falls back
     // to successive feed wavefronts of up to wave_max_chunks_ chunks)
     static const bool f16_lm = env_int("APRIL_F16_LM", 1) != 0;
@@ -992,72 +990,24 @@ bool Scheduler::step_chunks(std::vector<Session *> &ready)
     // 0.13 vs 0.33, 32: 0.33 vs 0.49, 64: 0.73 vs 0.60, 256: 1.74 vs 1.31 -- round 6; an asynchronous client that runs ahead of the GPU
     // is the case: bench.py `reference_api_async` 1.93 -> 1.45 ms per step)
     constexpr size_t lm_max_sessions = 48;
+    // (ADVICE.md finding 1, the wavefront depth cliff: the backlog sessions merged here share the depth of the shortest session of `one`)
     if (lm.size() > lm_max_sessions && wave_min_chunks_ > 0) { one.insert(one.end(), lm.begin(), lm.end()); lm.clear(); }
-    if (!lm.empty()) {
-        const int per = std::max(1, MB / lm_min_chunks_);
-        std::vector<Session *> group;
-        for (size_t o = 0; o < lm.size(); o += (size_t)per) {
-            group.assign(lm.begin() + (long)o, lm.begin() + (long)std::min(lm.size(), o + (size_t)per));
-            int T = MB / (int)group.size();
-            for (Session *s : group) T = std::min(T, waiting(s));
-            if (!step_layer_major(group, T)) { tick_.host_ms[3] += lap(); return false; }
-        }
+    const int per = lm_ok ? std::max(1, MB / lm_min_chunks_) : 1;
+    for (size_t o = 0; o < lm.size(); o += (size_t)per) {
+        const int m = (int)std::min(lm.size() - o, (size_t)per);
+        if (!advance(lm.data() + o, m, depth(lm.data() + o, m), STEP_LAYER_MAJOR)) return false;
     }
 
     const int n = (int)one.size();
+    if (n == 0) return true;
     // A feed usually carries 2..3 chunks for every session (100 ms = 2.5 chunks): those chunk steps run as ONE wavefront over
-    // the layers (Engine::lm_step mode 1) when the rows fit the work buffers; what is left over goes chunk by chunk.
-    if (n > 0 && wave_min_chunks_ > 0) {
-        int T = MB / n;
-        for (Session *s : one) T = std::min(T, waiting(s));
-        T = std::min(T, wave_max_chunks_);
-        if (T >= wave_min_chunks_) {
-            const bool ok = step_layer_major(one, T, 1);
-            tick_.host_ms[3] += lap();
-            return ok;
-        }
+    // the layers when the rows fit the work buffers; what is left over goes chunk by chunk, in sub-batches of at most MB sessions.
+    if (wave_min_chunks_ > 0) {
+        const int T = std::min(depth(one.data(), n), wave_max_chunks_);
+        if (T >= wave_min_chunks_) return advance(one.data(), n, T, STEP_WAVE);
     }
-    if (n > 0 && !eng_->flight_has_room(n, (n + MB - 1) / MB)) { tick_.host_ms[3] += lap(); return false; }
-    const int stride_ms = model_->host.params.segment_step * model_->host.params.frame_shift_ms;
-    for (int o = 0; o < n; o += MB) {
-        const int m = std::min(MB, n - o);
-        slots_.clear(); tails_.clear(); now_.clear();
-        bool traced = false;
-        for (int i = 0; i < m; ++i) {
-            Session *s = one[(size_t)(o + i)];
-            FrameBook &fb = s->fb;
-            slots_.push_back(s->slot);
-            tails_.push_back(fb.tail);                                  // fbank.c:327-349
-            fb.tail = (fb.tail + fb.seg_step) % fb.ring_frames;
-            fb.avail -= fb.seg_step;
-            fb.avail_shadow -= fb.seg_step;
-            s->now_ms += (size_t)stride_ms;                             // april_session.c:442-443
-            s->chunks++;
-            now_.push_back((int)s->now_ms);
-            if (s->trace_buf) traced = true;
-        }
-        if (traced) logit_stage_.resize((size_t)3 * m * d.vocab);
-        const int k = eng_->step(m, slots_.data(), tails_.data(), now_.data(), traced ? logit_stage_.data() : nullptr);
-        for (int i = 0; i < m; ++i) {
-            Session *s = one[(size_t)(o + i)];
-            s->replay.push_back(Session::Replay{k, i, m, (uint32_t)s->now_ms, 0, 0});
-            if (traced && s->trace_buf) {                               // tests: the logits of every round that ran, in order
-                const StepRecord *recs = eng_->records(k);
-                for (int r = 0; r < 3; ++r) {
-                    const StepRecord &rec = recs[(size_t)r * m + i];
-                    if (!(rec.flags & REC_VALID)) break;
-                    if (*s->trace_used + (size_t)d.vocab <= s->trace_cap) {
-                        memcpy(s->trace_buf + *s->trace_used, logit_stage_.data() + ((size_t)r * m + i) * d.vocab, (size_t)d.vocab * 4);
-                        *s->trace_used += (size_t)d.vocab;
-                    }
-                    if (rec.flags & REC_BLANK) break;
-                }
-            }
-        }
-        tick_.steps++; tick_.chunks += (uint64_t)m;
-        if ((uint64_t)m > tick_.max_batch_seen) tick_.max_batch_seen = (uint64_t)m;
-    }
-    tick_.host_ms[3] += lap();
+    if (!eng_->flight_has_room(n, (n + MB - 1) / MB)) return false;
+    for (int o = 0; o < n; o += MB) advance(one.data() + o, std::min(MB, n - o), 1, STEP_CHUNK);
     return true;
 }
 

@@ -51,6 +51,8 @@ struct Event {
     // Events are only ever MOVED between containers (the vector's storage, and with it the pointers, stay where they are).
     std::vector<AprilxTokenInfo> infos;
 };
+// the handler once per event, in order (null token pointer when an event has no tokens); `ev` is empty afterwards
+void deliver_events(std::vector<Event> &ev, AprilRecognitionResultHandler handler, void *userdata);
 
 class Greedy {
 public:
@@ -132,6 +134,9 @@ struct FrameBook {
     bool can_cut() const { return stream_end() - fifo_pos >= (size_t)padded && avail + 1 <= ring_frames; }
     void absorb_ext();              // ext -> fifo (keeps stream positions valid)
     void settle();                  // end of tick: drop consumed samples, keep the tail, forget the lent buffer
+    typedef std::vector<std::pair<const int16_t *, size_t>> Parts;
+    void append_span(size_t l0, size_t l1, Parts &parts) const;     // samples [l0, l1) of fifo ++ ext (l0 < l1) as at most two parts
+    FbankFrameDesc write_row(int slot, int pcm_off);     // one more ring row (pcm_off -1: flush padding); a real frame's caller moves avail_shadow and fifo_pos
     bool flush_allowed() const { return avail_shadow >= -(long)(seg_count * 3); }
     void compact();
 };
@@ -161,6 +166,10 @@ struct Session {
     std::chrono::steady_clock::time_point oldest_submit;   // when the oldest work not yet collected by the stepping thread was handed over
     bool has_oldest = false;
     std::vector<Event> done_events;           // sync sessions: events waiting for the caller thread
+    // (both read under Scheduler::mu_) everything queued so far has been processed ...
+    bool idle() const { return closing || (completed >= submitted && !busy && !fed && !flush_requested); }
+    // ... and nothing is queued, no segment is open, no flush is under way: the session's options may change
+    bool settable() const { return !(closing || busy || fed || flush_requested || !inbox.empty() || borrow_cnt || seg_open || flush_phase); }
 
     // ---- owned by the stepping thread while busy
     FrameBook fb;
@@ -243,13 +252,16 @@ private:
     void cut_frames(std::vector<Session *> &work, bool &progressed);
     void stage_resampled(const FrameBook &fb, int64_t first, int64_t last_end, size_t base, size_t &staged_in);
     bool step_chunks(std::vector<Session *> &ready);     // false: the flight's rings are full, (some) work is left for the next flight
-    bool step_layer_major(std::vector<Session *> &group, int T, int mode = 0);
+    // how advance() runs its T chunks: one chunk step (T == 1, Engine::step), or Engine::lm_step as a feed wavefront / layer-major
+    enum StepPath { STEP_CHUNK, STEP_WAVE, STEP_LAYER_MAJOR };
+    bool advance(Session *const *group, int m, int T, StepPath path);
+    template <class Apply> bool configure(Session *s, Apply apply);     // the three set_* calls: wait_idle, lock, refuse unless settable, apply
     void replay(Flight &f);
     int split_sticky_ = 0;
     int pipeline_depth_ = 2;                             // APRIL_PIPELINE: 2 = launch the next flight before completing the current one, 1 = one flight at a time
 
-    Model *model_;
     Engine *eng_;
+    const int stride_ms_;                          // audio time of one chunk step (segment_step frames)
     HostPool pool_;                                // helpers for the per-session host copies (APRIL_HOST_THREADS, default 3)
     std::mutex mu_;
     std::condition_variable cv_work_, cv_done_;
@@ -262,7 +274,6 @@ private:
     int wave_min_chunks_ = 2;                        // APRIL_WAVE_MIN_CHUNKS (0 = chunk steps one by one): chunk steps of one feed as a wavefront ...
     static constexpr int wave_max_chunks_ = 7;       // ... of at most this many chunks
     int lm_min_chunks_ = 8;                          // APRIL_LM_MIN_CHUNKS: sessions with at least this many chunks waiting take the layer-major path (0 = never)
-    void spin_for_done(uint64_t seen);
     std::vector<Session *> sessions_;
     bool stop_ = false;
     std::thread thread_;
@@ -275,8 +286,8 @@ private:
     std::thread::id loop_tid_;
     // scratch reused across ticks
     std::vector<FbankFrameDesc> desc_;
-    std::vector<std::pair<const int16_t *, size_t>> pcm_parts_;   // windows to stage, in order
-    std::vector<std::pair<const int16_t *, size_t>> in_parts_;    // input-rate spans of resampled sessions' windows, in order
+    FrameBook::Parts pcm_parts_;                   // windows to stage, in order
+    FrameBook::Parts in_parts_;                    // input-rate spans of resampled sessions' windows, in order
     std::vector<ResampleDesc> rdesc_;
     std::vector<const ResampleSpec *> rspec_;
     std::vector<int> slots_, tails_, now_;

@@ -240,8 +240,11 @@ int main(int argc, char **argv)
     CHECK(st.chunks > 0 && st.flights > 0, "nothing ran");
     double lat[64]; const int nl = aprilx_model_feed_latency(m, 0, lat, 64, 0);
     CHECK(nl > 0 && lat[0] > 0.0, "no feed latencies recorded");
-    printf("HARNESS %s: %llu chunks, %llu flights, %llu steps (%llu layer-major / %llu wavefront), %d callbacks in the reference pass\n", g_fail ? "FAILED" : "ok",
-           (unsigned long long)st.chunks, (unsigned long long)st.flights, (unsigned long long)st.steps, (unsigned long long)st.lm_steps, (unsigned long long)st.wave_steps, calls);
+    Sess all;                                                 // one FNV digest over the reference pass: every callback of its sessions, in session order
+    all.mix(ref.data(), ref.size() * sizeof(uint64_t));
+    printf("HARNESS %s: %llu chunks, %llu flights, %llu steps (%llu layer-major / %llu wavefront), %d callbacks in the reference pass, ref digest %016llx\n", g_fail ? "FAILED" : "ok",
+           (unsigned long long)st.chunks, (unsigned long long)st.flights, (unsigned long long)st.steps, (unsigned long long)st.lm_steps, (unsigned long long)st.wave_steps, calls,
+           (unsigned long long)all.digest);
     aam_free(m);
     return g_fail ? 1 : 0;
 }

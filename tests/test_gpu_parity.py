@@ -695,6 +695,48 @@ def test_sessions_above_max_batch(tiny_model):
     assert outs[0] == outs[1] and any(len(e) for e in outs[0])
 
 
+def test_traced_sub_batches_equal_one_batch(tiny_model):
+    """Six traced sessions with APRIL_MAX_BATCH=4: every chunk step is split into sub-batches of 4 + 2 rows, so a session of the
+    second sub-batch has its records and traced logits at the row inside its OWN sub-batch.  Traced logits and raw events are equal
+    BIT FOR BIT to the unsplit run (APRIL_MAX_BATCH=2048), on the feed wavefront path (APRIL_WAVE_MIN_CHUNKS unset; at 4 rows
+    the six sessions do not fit a wavefront and go chunk by chunk) and on the chunk-by-chunk path (APRIL_WAVE_MIN_CHUNKS=0)."""
+    import os
+    import pickle
+    import subprocess
+    import sys
+    code = (
+        "import sys, numpy as np; sys.path.insert(0, %r)\n"
+        "import april_asr_amd as A\n"
+        "from april_asr_amd import synth_model as SM\n"
+        "m = A.Model(%r)\n"
+        "n = 6; pcms = [SM.lcg_pcm16(16000, seed=900 + i) for i in range(n)]\n"
+        "evs = [[] for _ in range(n)]\n"
+        "ss = [A.Session(m, (lambda k: (lambda t, toks: evs[k].append((t, toks))))(i), raw_events=True) for i in range(n)]\n"
+        "for s in ss: s.trace_logits(1000)\n"
+        "g = A.SessionGroup(ss)\n"
+        "for o in range(0, 16000, 1600): g.feed([p[o:o + 1600] for p in pcms])\n"
+        "g.flush()\n"
+        "import pickle; pickle.dump((evs, [s.traced_logits().copy() for s in ss], int(m.stats().replay_mismatch)), open(sys.argv[1], 'wb'))\n"
+        "for s in ss: s.close()\n"
+        "m.close()\n" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), tiny_model["path"]))
+    outs = []
+    for mb in ("4", "2048"):
+        for wave in (None, "0"):
+            out = os.path.join(os.path.dirname(tiny_model["path"]), "traced_%s_%s.pkl" % (mb, wave))
+            env = dict(os.environ, APRIL_MAX_BATCH=mb)
+            env.pop("APRIL_WAVE_MIN_CHUNKS", None)
+            if wave is not None:
+                env["APRIL_WAVE_MIN_CHUNKS"] = wave
+            subprocess.check_call([sys.executable, "-c", code, out], env=env)
+            outs.append(pickle.load(open(out, "rb")))
+    evs0, lg0, _ = outs[0]
+    assert any(len(e) for e in evs0) and all(l.size > 0 for l in lg0)
+    for evs, lg, mismatch in outs:
+        assert mismatch == 0
+        assert evs == evs0
+        assert len(lg) == len(lg0) and all(np.array_equal(a, b) for a, b in zip(lg, lg0))
+
+
 def test_config3_256_sessions_aprilv0(gpu_v0, orc_v0):
     """BASELINE configs[2]: 256 concurrent streaming sessions at aprilv0 dimensions in 100 ms feeds on one GPU (the workload
     bench.py times).  The batch runs untraced, i.e. on the captured launch chains with the full-K GEMM schedule; session 0

@@ -9,6 +9,7 @@ threads with their own sessions, session churn beside streaming sessions, frees 
 long feeds.  Once with -fsanitize=thread, once with -fsanitize=address,undefined; any report, inconsistency, replay mismatch or
 hang fails.  Reference threading contract: src/april_session.c:479-493,567-585, src/audio_provider.c:25-40."""
 import os
+import re
 import subprocess
 
 import pytest
@@ -32,8 +33,30 @@ def _run(exe, model, **env):
     r = subprocess.run([exe, model], env=e, capture_output=True, timeout=600)
     out = r.stdout.decode() + r.stderr.decode()
     assert "ThreadSanitizer" not in out and "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
-    assert r.returncode == 0 and "HARNESS ok" in out, out[-4000:]
-    return out
+    assert r.returncode == 0 and "HARNESS ok" in out, out[-4000:]          # (the driver itself checks replay_mismatch == 0)
+    m = re.search(r"HARNESS ok: .* (\d+) steps \((\d+) layer-major / (\d+) wavefront\), .* ref digest ([0-9a-f]{16})$", out, re.M)
+    assert m, out[-4000:]
+    return dict(steps=int(m.group(1)), lm_steps=int(m.group(2)), wave_steps=int(m.group(3)), digest=m.group(4))
+
+
+def _run_stepping_paths(exe, model, **env):
+    """The knobs that route chunk steps: without the feed wavefront, without the layer-major path, and without both -- every step
+    is then a chunk step of one chunk per session (sub-batches included) -- also with flights that fill up after one step."""
+    runs = [_run(exe, model, APRIL_WAVE_MIN_CHUNKS=0, **env), _run(exe, model, APRIL_LM_MIN_CHUNKS=0, **env)]
+    assert runs[0]["wave_steps"] == 0 and runs[1]["lm_steps"] == 0
+    for extra in ({}, dict(FAKE_STEP_CAP=1)):
+        r = _run(exe, model, APRIL_WAVE_MIN_CHUNKS=0, APRIL_LM_MIN_CHUNKS=0, **dict(env, **extra))
+        assert r["lm_steps"] == 0 and r["wave_steps"] == 0 and r["steps"] > 0, r      # "0 layer-major / 0 wavefront", and it stepped
+        runs.append(r)
+    return runs
+
+
+def _assert_one_digest(runs):
+    """Every single-engine run of one build delivers the same callbacks in the driver's reference pass (one FNV digest over all of
+    them): the fake engine decides from the samples alone, so neither the stepping path that served a chunk, nor the flight it
+    went into, nor the pipelining or spinning around it may show.  (The three-engine run spreads the sessions over three fake
+    engines; it is checked by the driver's own comparisons and left out of this one.)"""
+    assert len({r["digest"] for r in runs}) == 1, runs
 
 
 @pytest.fixture(scope="module")
@@ -43,16 +66,19 @@ def harness_dir(tmp_path_factory):
 
 def test_scheduler_under_thread_sanitizer(harness_dir, tiny_model):
     exe = _build(harness_dir, "harness_tsan", "-fsanitize=thread")
-    _run(exe, tiny_model["path"])
-    _run(exe, tiny_model["path"], FAKE_STEP_CAP=1)                      # every flight fills up: follow-up flights of one tick
-    _run(exe, tiny_model["path"], APRIL_PIPELINE=1)                     # one flight at a time
-    _run(exe, tiny_model["path"], FAKE_DELAY_US=0, FAKE_DELAY_US_MAX=5, FAKE_STEP_CAP=2)      # flights complete at once
-    _run(exe, tiny_model["path"], APRIL_SPIN_STEP_US=0, APRIL_SPIN_WAIT_US=0)                 # no spinning: every hand-over through the condition variables
+    runs = [_run(exe, tiny_model["path"])]
+    runs.append(_run(exe, tiny_model["path"], FAKE_STEP_CAP=1))                      # every flight fills up: follow-up flights of one tick
+    runs.append(_run(exe, tiny_model["path"], APRIL_PIPELINE=1))                     # one flight at a time
+    runs.append(_run(exe, tiny_model["path"], FAKE_DELAY_US=0, FAKE_DELAY_US_MAX=5, FAKE_STEP_CAP=2))      # flights complete at once
+    runs.append(_run(exe, tiny_model["path"], APRIL_SPIN_STEP_US=0, APRIL_SPIN_WAIT_US=0))                 # no spinning: every hand-over through the condition variables
     _run(exe, tiny_model["path"], APRIL_GPU_DEVICES="0,0,0")          # three engines = three stepping threads behind one model; least-loaded placement from client threads
                                                                          # (found in round 5: Engine::live_slots() read the slot count without the lock -> now atomic)
+    runs += _run_stepping_paths(exe, tiny_model["path"])
+    _assert_one_digest(runs)
 
 
 def test_scheduler_under_address_and_ub_sanitizers(harness_dir, tiny_model):
     exe = _build(harness_dir, "harness_asan", "-fsanitize=address,undefined -fno-sanitize-recover=undefined")
-    _run(exe, tiny_model["path"])
-    _run(exe, tiny_model["path"], FAKE_STEP_CAP=1, APRIL_HOST_THREADS=8)
+    runs = [_run(exe, tiny_model["path"]), _run(exe, tiny_model["path"], FAKE_STEP_CAP=1, APRIL_HOST_THREADS=8)]
+    runs += _run_stepping_paths(exe, tiny_model["path"])
+    _assert_one_digest(runs)
