@@ -251,10 +251,20 @@ class Model:
             raise ValueError("aprilx_run_confidence refused n=%d k=%d" % (a.shape[0], k))
         return out
 
-    def bias(self, phrases, boost: float = 2.0):
-        """A phrase-boosting set for this model (aprilx_bias_create; no GPU needed): `phrases` is a list of strings / bytes, all with
-        `boost` logit units, or of (phrase, boost) pairs.  Hand it to Session(..., bias=...) or Session.set_bias()."""
-        return Bias(self, phrases, boost)
+    def bias(self, phrases, boost: float = 2.0, strict: bool = False):
+        """A phrase-boosting set for this model (aprilx_bias_create_ex; no GPU needed): `phrases` is a list of strings / bytes, all with
+        `boost` logit units, or of (phrase, boost) pairs.  Hand it to Session(..., bias=...) or Session.set_bias().
+        `strict`: a closed phrase list -- the session emits only sequences of these phrases (APRILX_BIAS_STRICT)."""
+        return Bias(self, phrases, boost, flags=BIAS_STRICT if strict else 0)
+
+    def run_confidence_biased(self, logits, k: int, bias, bias_state):
+        """run_confidence with `bias` on the rows whose bias_state is >= 0 (aprilx_run_confidence_biased; tests)."""
+        a = np.ascontiguousarray(logits, np.float32).reshape(-1, self.dims.vocab)
+        bs = np.ascontiguousarray(bias_state, np.int32).reshape(a.shape[0])
+        out = (_ffi.AprilxTokenInfo * a.shape[0])()
+        if self._L.aprilx_run_confidence_biased(self._handle, a.shape[0], a.ctypes.data, int(k), bias._handle, bs.ctypes.data, out) != 0:
+            raise ValueError("aprilx_run_confidence_biased refused n=%d k=%d" % (a.shape[0], k))
+        return out
 
     def run_decide_biased(self, logits, early_emit, now_ms, rnd, state, bias, bias_state, op: int = 0):
         """One decision round on GIVEN logits rows with `bias` on the rows whose bias_state is >= 0 (aprilx_run_decide_biased; tests):
@@ -292,23 +302,29 @@ class Model:
         self._L.aprilx_model_profile(self._handle, int(enable))
 
 
-class Bias:
-    """A set of boosted phrases.  Sessions that use it keep it alive after close()."""
+BIAS_STRICT = 1                                   # APRILX_BIAS_STRICT
 
-    def __init__(self, model: Model, phrases, boost: float = 2.0):
+
+class Bias:
+    """A set of boosted phrases.  Sessions that use it keep it alive after close().
+    `flags`: BIAS_STRICT for a closed phrase list; `edges()` of such a set are the tokens permitted at a state."""
+
+    def __init__(self, model: Model, phrases, boost: float = 2.0, flags: int = 0):
         self._L = model._L
         items = [(p, boost) if isinstance(p, (str, bytes)) else (p[0], p[1]) for p in phrases]
         raw = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p, _ in items]
         arr = (C.c_char_p * max(len(raw), 1))(*raw)
         boosts = (C.c_float * max(len(raw), 1))(*[float(b) for _, b in items])
         err = C.create_string_buffer(256)
-        self._handle = self._L.aprilx_bias_create(model._handle, len(raw), arr, boosts, err, 256)
+        self._handle = self._L.aprilx_bias_create_ex(model._handle, len(raw), arr, boosts, int(flags), err, 256)
         self.message = err.value.decode("utf-8", "replace")          # a note about left-out phrases when the call succeeded
         if not self._handle:
             raise ValueError("bias set refused: " + self.message)
         st, ed = C.c_int32(0), C.c_int64(0)
         self.dropped = int(self._L.aprilx_bias_info(self._handle, C.byref(st), C.byref(ed)))
         self.states, self.n_edges = int(st.value), int(ed.value)
+        self.flags = int(self._L.aprilx_bias_flags(self._handle))
+        self.strict = bool(self.flags & BIAS_STRICT)
 
     def edges(self, state: int):
         """(token ids, next states, bonuses) of the effective edges of one trie state, token ids ascending"""

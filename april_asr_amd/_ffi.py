@@ -73,6 +73,7 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_session_set_confidence", "aprilx_session_confidence", "aprilx_run_confidence",
     "aprilx_bias_create", "aprilx_bias_free", "aprilx_bias_info", "aprilx_bias_edges", "aprilx_session_set_bias", "aprilx_session_bias_state",
     "aprilx_run_decide_biased", "aprilx_greedy_set_bias", "aprilx_greedy_bias_state",
+    "aprilx_bias_create_ex", "aprilx_bias_flags", "aprilx_run_confidence_biased",
 ]
 
 _lib = None
@@ -146,6 +147,9 @@ def lib():
     L.aprilx_session_confidence.argtypes = [vp]; L.aprilx_session_confidence.restype = C.c_int
     L.aprilx_run_confidence.argtypes = [vp, C.c_int, vp, C.c_int, vp]; L.aprilx_run_confidence.restype = C.c_int
     L.aprilx_bias_create.argtypes = [vp, sz, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_char_p, sz]; L.aprilx_bias_create.restype = vp
+    L.aprilx_bias_create_ex.argtypes = [vp, sz, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_uint32, C.c_char_p, sz]; L.aprilx_bias_create_ex.restype = vp
+    L.aprilx_bias_flags.argtypes = [vp]; L.aprilx_bias_flags.restype = C.c_int
+    L.aprilx_run_confidence_biased.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp]; L.aprilx_run_confidence_biased.restype = C.c_int
     L.aprilx_bias_free.argtypes = [vp]; L.aprilx_bias_free.restype = None
     L.aprilx_bias_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]; L.aprilx_bias_info.restype = C.c_int
     L.aprilx_bias_edges.argtypes = [vp, C.c_int32, vp, vp, vp, sz]; L.aprilx_bias_edges.restype = C.c_int

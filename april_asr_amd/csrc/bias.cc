@@ -59,8 +59,11 @@ bool spellable(const Vocab &v, const std::string &s)
 
 struct Edge { int tok, next; float bonus; };
 
-std::shared_ptr<BiasSet> build_set(const ModelParams &P, size_t n, const char *const *phrases, const float *boosts, std::string &err)
+// strict (kBiasStrict): the emitted edges are the tokens PERMITTED at every state -- own edges whose target can still reach the end of
+// a phrase, and the root's such edges at the root and where a phrase ends; without the flag the code takes the path it took before
+std::shared_ptr<BiasSet> build_set(const ModelParams &P, size_t n, const char *const *phrases, const float *boosts, uint32_t flags, std::string &err)
 {
+    const bool strict = (flags & kBiasStrict) != 0;
     if (n == 0 || !phrases || !boosts) { err = "a bias set needs at least one phrase"; return nullptr; }
     if (P.token_count > kBiasMaxVocab) { err = "phrase boosting supports vocabularies of at most " + std::to_string(kBiasMaxVocab) + " tokens"; return nullptr; }
     const Vocab voc(P);
@@ -68,6 +71,8 @@ std::shared_ptr<BiasSet> build_set(const ModelParams &P, size_t n, const char *c
     auto set = std::make_shared<BiasSet>();
     set->vocab = P.token_count;
     set->vocab_hash = bias_vocab_hash(P);
+    set->flags = flags;
+    std::vector<int> ends;                                          // the node where every kept phrase ends
     for (size_t i = 0; i < n; ++i) {
         const std::string where = "phrase " + std::to_string(i);
         if (!phrases[i] || !phrases[i][0]) { err = where + " is empty"; return nullptr; }
@@ -91,8 +96,11 @@ std::shared_ptr<BiasSet> build_set(const ModelParams &P, size_t n, const char *c
             }
             node = trie[(size_t)node].child[c];
         }
+        ends.push_back(node);
     }
     const int S = (int)trie.size();
+    std::vector<char> terminal((size_t)S, 0);
+    for (int e : ends) terminal[(size_t)e] = 1;
     // own edges of state s: every non-blank token whose whole text can be walked from s, ids ascending
     auto own_edges = [&](int s, std::vector<Edge> &out) {
         out.clear();
@@ -107,17 +115,34 @@ std::shared_ptr<BiasSet> build_set(const ModelParams &P, size_t n, const char *c
         std::sort(out.begin(), out.end(), [](const Edge &a, const Edge &b) { return a.tok < b.tok; });
     };
     std::vector<Edge> root, own;
+    // strict: live(s) = a phrase ends at s, or an own edge of s leads to a live state.  An own edge leads to a descendant, and a node's
+    // number is larger than its parent's, so one pass from the last node down IS the fixed point.  Only edges to live states are kept.
+    std::vector<char> live;
+    if (strict) {
+        live = terminal;
+        for (int s = S - 1; s >= 0; --s) {
+            if (live[(size_t)s]) continue;
+            own_edges(s, own);
+            for (const Edge &e : own) if (live[(size_t)e.next]) { live[(size_t)s] = 1; break; }
+        }
+    }
+    auto prune = [&](std::vector<Edge> &v) {
+        if (strict) v.erase(std::remove_if(v.begin(), v.end(), [&](const Edge &e) { return !live[(size_t)e.next]; }), v.end());
+    };
     own_edges(0, root);
+    prune(root);
     set->state_off.assign((size_t)S + 1, 0);
     for (int s = 0; s < S; ++s) {
-        // effective edges: the state's own, plus the root's for every token it has none for (a new match may start where this one breaks)
-        if (s == 0) own = root; else own_edges(s, own);
+        // effective edges: the state's own, plus the root's for every token it has none for (a new match may start where this one breaks;
+        // in a strict set only where a phrase has ended: inside a phrase nothing but its continuations is permitted)
+        if (s == 0) own = root; else { own_edges(s, own); prune(own); }
+        const bool with_root = s != 0 && (!strict || terminal[(size_t)s]);
         size_t i = 0, j = 0;
-        while (i < own.size() || (s != 0 && j < root.size())) {
+        while (i < own.size() || (with_root && j < root.size())) {
             Edge e;
-            if (s == 0 || j >= root.size() || (i < own.size() && own[i].tok <= root[j].tok)) {
+            if (!with_root || j >= root.size() || (i < own.size() && own[i].tok <= root[j].tok)) {
                 e = own[i];
-                if (s != 0 && j < root.size() && root[j].tok == e.tok) ++j;
+                if (with_root && j < root.size() && root[j].tok == e.tok) ++j;
                 ++i;
             } else e = root[j++];
             set->edge_tok.push_back(e.tok); set->edge_next.push_back(e.next); set->edge_bonus.push_back(e.bonus);
@@ -125,6 +150,9 @@ std::shared_ptr<BiasSet> build_set(const ModelParams &P, size_t n, const char *c
         if ((int64_t)set->edge_tok.size() > kBiasMaxEdges) { err = "the phrases need more than " + std::to_string(kBiasMaxEdges) + " token edges"; return nullptr; }
         set->state_off[(size_t)s + 1] = (int32_t)set->edge_tok.size();
     }
+    // a phrase that can be spelled keeps the edges of its spelling (each leads to a live state), so pruning loses none: the phrases left
+    // out of a strict set are section 13's unspellable ones, and a set with none left would permit nothing
+    if (strict && ends.empty()) { err = "no phrase of the strict set can be spelled with the model's tokens: the session could emit nothing"; return nullptr; }
     if (set->dropped) err = std::to_string(set->dropped) + " phrase(s) cannot be spelled with the model's tokens and were left out";
     return set;
 }
@@ -142,10 +170,17 @@ extern "C" {
 
 AprilxBias aprilx_bias_create(AprilASRModel model, size_t n, const char *const *phrases, const float *boosts, char *err, size_t err_cap)
 {
+    return aprilx_bias_create_ex(model, n, phrases, boosts, 0, err, err_cap);
+}
+
+AprilxBias aprilx_bias_create_ex(AprilASRModel model, size_t n, const char *const *phrases, const float *boosts, uint32_t flags, char *err, size_t err_cap)
+{
     put_err(err, err_cap, "");
     if (!model) { put_err(err, err_cap, "no model"); return nullptr; }
+    if (flags & ~(uint32_t)APRILX_BIAS_STRICT) { put_err(err, err_cap, "unknown flag bits"); return nullptr; }
+    static_assert(APRILX_BIAS_STRICT == kBiasStrict, "the ABI's flag is BiasSet's");
     std::string e;
-    std::shared_ptr<BiasSet> set = build_set(model->m.host.params, n, phrases, boosts, e);
+    std::shared_ptr<BiasSet> set = build_set(model->m.host.params, n, phrases, boosts, flags, e);
     put_err(err, err_cap, e);
     if (!set) return nullptr;
     AprilxBias_i *h = new AprilxBias_i();
@@ -162,6 +197,8 @@ int aprilx_bias_info(AprilxBias bias, int32_t *states, int64_t *edges)
     if (edges) *edges = bias->set->edges();
     return bias->set->dropped;
 }
+
+int aprilx_bias_flags(AprilxBias bias) { return bias ? (int)bias->set->flags : -1; }
 
 int aprilx_bias_edges(AprilxBias bias, int32_t state, int32_t *tok, int32_t *next, float *bonus, size_t cap)
 {

@@ -14,6 +14,7 @@ constexpr int64_t kBiasMaxEdges = 4 << 20;         // effective edges of one set
 constexpr int kBiasMaxPhraseBytes = 256;
 constexpr float kBiasMaxBoost = 100.0f;
 constexpr int kBiasMaxVocab = 8192;                // 6 bytes of LDS per token in the biased decision kernel (48 KB)
+constexpr uint32_t kBiasStrict = 1;                // BiasSet::flags (APRILX_BIAS_STRICT): a token without an edge is forbidden, not "no bonus"
 
 // FNV-1a over the token texts (each with its NUL) and the blank id: a set only fits the token list it was built for
 inline uint64_t bias_vocab_hash(const ModelParams &p)
@@ -28,13 +29,15 @@ inline uint64_t bias_vocab_hash(const ModelParams &p)
 struct BiasSet {
     int vocab = 0;                                 // of the model it was built for
     uint64_t vocab_hash = 0;                       // bias_vocab_hash of that model's token list
+    uint32_t flags = 0;                            // kBiasStrict: the edges below are the PERMITTED tokens of every state (a closed phrase list)
     int dropped = 0;                               // phrases no token sequence can spell (left out of the trie)
     std::vector<int32_t> state_off;                // [states + 1]
     std::vector<int32_t> edge_tok, edge_next;      // [edges] effective edges of state s: [state_off[s], state_off[s + 1]), token ids ascending
     std::vector<float> edge_bonus;
     int states() const { return (int)state_off.size() - 1; }
     int64_t edges() const { return (int64_t)edge_tok.size(); }
-    // effective edge (s, tok), or -1: the token leads to the root with bonus 0
+    // effective edge (s, tok), or -1: the token leads to the root with bonus 0 (a strict set: the search never decides for such a token
+    // unless nothing permitted beat the initial value and the blank lost as well -- the NaN row of decide_body --, then to the root too)
     int find(int s, int tok) const
     {
         int lo = state_off[(size_t)s], hi = state_off[(size_t)s + 1];

@@ -1482,7 +1482,7 @@ BiasDesc Engine::upload_bias(const BiasSet &set, void **dev, hipStream_t st)
     HIP_CHECK(hipMalloc((void **)&p, pad(ns) + 3 * pad(ne)));
     BiasDesc d;
     d.state_off = (const int32_t *)p; d.edge_tok = (const int32_t *)(p + pad(ns)); d.edge_next = (const int32_t *)(p + pad(ns) + pad(ne));
-    d.edge_bonus = (const float *)(p + pad(ns) + 2 * pad(ne)); d.n_states = set.states();
+    d.edge_bonus = (const float *)(p + pad(ns) + 2 * pad(ne)); d.n_states = set.states(); d.flags = (int32_t)set.flags;
     HIP_CHECK(hipMemcpyAsync((void *)d.state_off, set.state_off.data(), ns, hipMemcpyHostToDevice, st));
     if (!set.edge_tok.empty()) {
         const size_t b = set.edge_tok.size() * 4;
@@ -1869,7 +1869,7 @@ void Engine::debug_decide_impl(int n, int op, const float *logits, float early_e
     zero_slots(n);
 }
 
-void Engine::debug_confidence(int n, const float *logits, int k, ConfRecord *out)
+void Engine::debug_confidence(int n, const float *logits, int k, ConfRecord *out, const BiasSet *set, const int32_t *bias_state)
 {
     std::lock_guard<std::mutex> cg(capture_mu_);
     HipLegacyLock legacy;
@@ -1897,9 +1897,22 @@ void Engine::debug_confidence(int n, const float *logits, int k, ConfRecord *out
     a.slot_idx = slots_d; a.now_ms = now_d; a.active = active_d; a.dirty = dirty_d; a.tok_class = cls_; a.state = gstate_;
     a.rec = rec_d; a.round = 0; a.gen = 1; a.dec = dec_params(); a.de_out = nullptr;
     a.conf = conf_d; a.conf_k_all = k;
+    int32_t *bset_d = nullptr, *bstate_d = nullptr; BiasDesc *bdesc_d = nullptr; void *barrays_d = nullptr;
+    if (set) {                                             // tables of its own for the call, as debug_decide_impl
+        std::vector<int32_t> bset((size_t)n), bstate((size_t)n);
+        for (int i = 0; i < n; ++i) { bset[(size_t)i] = bias_state[i] < 0 ? -1 : 0; bstate[(size_t)i] = std::max(0, bias_state[i]); }
+        bset_d = dmalloc<int32_t>((size_t)n); bstate_d = dmalloc<int32_t>((size_t)n); bdesc_d = dmalloc<BiasDesc>(1);
+        const BiasDesc desc = upload_bias(*set, &barrays_d, stream_);
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        HIP_CHECK(hipMemcpy(bset_d, bset.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(bstate_d, bstate.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(bdesc_d, &desc, sizeof desc, hipMemcpyHostToDevice));
+        a.bias_set = bset_d; a.bias_state = bstate_d; a.bias_desc = bdesc_d;
+    }
     launch_decide(a, stream_);
     sync();
     HIP_CHECK(hipMemcpy(out, conf_d, (size_t)n * sizeof(ConfRecord), hipMemcpyDeviceToHost));
+    if (set) for (void *p : {(void *)bset_d, (void *)bstate_d, (void *)bdesc_d, barrays_d}) (void)hipFree(p);
     for (void *p : {(void *)slots_d, (void *)now_d, (void *)active_d, (void *)dirty_d, (void *)rec_d, (void *)conf_d, (void *)plane_d, (void *)zero_d}) (void)hipFree(p);
     zero_slots(n);
 }

@@ -226,7 +226,8 @@ public:
     // (op 1) on slots 0..n-1 with GIVEN logits rows and search states; returns the records and the new states
     void debug_decide(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out);
     // the side records of n GIVEN logits rows with k alternatives through decide_kernel's confidence code (aprilx_run_confidence)
-    void debug_confidence(int n, const float *logits, int k, ConfRecord *out);
+    // (`set` non-null: on the rows whose bias_state[i] >= 0, from that trie state -- aprilx_run_confidence_biased)
+    void debug_confidence(int n, const float *logits, int k, ConfRecord *out, const BiasSet *set = nullptr, const int32_t *bias_state = nullptr);
     void debug_fbank(int n_frames, const int16_t *pcm_frames /*[n][padded]*/, float *out /*[n][nbins]*/);
     // one whole segment through resample_kernel (aprilx_resample); out holds resample_total(n) samples
     void debug_resample(const ResampleSpec *spec, const int16_t *pcm, size_t n, int16_t *out);

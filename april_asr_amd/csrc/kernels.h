@@ -224,7 +224,7 @@ enum { REC_VALID = 1, REC_BLANK = 2, REC_CTX = 4 };
 enum TokClassBits { TKC_WORD_START = 1, TKC_SENT_END = 2, TKC_COMMA = 4, TKC_DOT = 8, TKC_DIGIT_START = 16 };
 
 // Phrase boosting (bias.h): one bias set on the device -- the effective token edges of every trie state, CSR
-struct BiasDesc { const int32_t *state_off = nullptr, *edge_tok = nullptr, *edge_next = nullptr; const float *edge_bonus = nullptr; int32_t n_states = 0, reserved = 0; };
+struct BiasDesc { const int32_t *state_off = nullptr, *edge_tok = nullptr, *edge_next = nullptr; const float *edge_bonus = nullptr; int32_t n_states = 0, flags = 0; };      // flags: BiasSet::flags (kBiasStrict)
 
 struct DecEmbedParams {
     const float *emb = nullptr;            // [vocab][d]

@@ -10,12 +10,23 @@
 // edges / 256 load-store pairs per lane once, and 6 bytes of LDS per token (V <= 8192, checked on the host).
 // A token without an edge gets NO addition (not "+ 0"), so the row's other logits keep their bits.
 // Vector stores only, no atomics; thread 0 writes the new state beside the GreedyState.
+//
+// Strict sets (BiasDesc::flags & 1: a closed phrase list): the edges of a state are the tokens PERMITTED there, and the table is
+// filled with a third cell value, "forbidden", in place of "no edge" -- the scatter is the same.  A forbidden non-blank token takes no
+// part in the arg-max (bias_scan) nor in any pass of confidence_row, exactly as the blank takes none in the arg-max; the blank's own
+// cell is never scattered to and is not consulted (the blank is always permitted, never biased).  A row with nothing permitted above
+// the initial value leaves best_i == -1, which decide_body's unchanged lines resolve (to blank, unless the blank logit is a NaN).
+// bias_row_end needs no case of its own: next[] of a forbidden token is the root's 0.
 
 constexpr unsigned kBiasNoEdge = 0x7fc0b1a5u;      // a NaN pattern: boosts are finite, so no edge's bonus has these bits
+constexpr unsigned kBiasForbidden = 0x7fc0f0bdu;   // another one: the fill value of a strict set's table
 
+__device__ __forceinline__ bool bias_forbidden(float cell) { return __float_as_uint(cell) == kBiasForbidden; }
+
+// (not called for a forbidden cell, except for the blank's, which never holds a bonus)
 __device__ __forceinline__ float bias_apply(float v, float cell)
 {
-    return __float_as_uint(cell) == kBiasNoEdge ? v : v + cell;
+    return __float_as_uint(cell) == kBiasNoEdge || bias_forbidden(cell) ? v : v + cell;
 }
 
 struct BiasRow {
@@ -39,7 +50,8 @@ __device__ __forceinline__ void bias_row_begin(const DecideArgs &a, int m, unsig
     const int V = a.n_valid;
     float *bonus = reinterpret_cast<float *>(lds);
     unsigned short *next = reinterpret_cast<unsigned short *>(lds + (size_t)V * 4);
-    for (int n = threadIdx.x; n < V; n += 256) { bonus[n] = __uint_as_float(kBiasNoEdge); next[n] = 0; }
+    const float fill = __uint_as_float((d.flags & 1) ? kBiasForbidden : kBiasNoEdge);
+    for (int n = threadIdx.x; n < V; n += 256) { bonus[n] = fill; next[n] = 0; }
     __syncthreads();
     for (int e = e0 + (int)threadIdx.x; e < e1; e += 256) {
         const int t = d.edge_tok[e];
@@ -57,8 +69,10 @@ __device__ __forceinline__ void bias_scan(const DecideArgs &a, int m, const Bias
     for (int n = threadIdx.x; n < a.n_valid; n += 256) {
         const float raw = tree_sum(a.ws, a.parts, a.m_stride, a.N, m, n) + a.bias[n];
         if (a.logits_dump) a.logits_dump[(size_t)m * a.n_valid + n] = raw;
-        const float v = bias_apply(raw, br.bonus[n]);
+        const float cell = br.bonus[n];
+        const float v = bias_apply(raw, cell);
         if (n == a.blank) blank_v = v;
+        else if (bias_forbidden(cell)) continue;                 // strict set: not permitted from this state
         else if (v > best) { best = v; best_i = n; }
     }
 }

@@ -21,6 +21,13 @@ __device__ __forceinline__ float conf_logit(const DecideArgs &a, int m, int n, c
     return bonus ? bias_apply(v, bonus[n]) : v;
 }
 
+// a strict set's forbidden token: the search did not compare it, so it is in no pass below -- not in the maximum, not a term of the
+// sum (skipped, not added as zero), never an alternative.  The blank is always permitted.
+__device__ __forceinline__ bool conf_skip(const DecideArgs &a, int n, const float *bonus)
+{
+    return bonus && n != a.blank && bias_forbidden(bonus[n]);
+}
+
 // (value, id) arg-max over the workgroup with the search's order: higher value first, lower id on ties; id < 0 = nothing.
 // One barrier per call: the LDS cells alternate with `phase`, so a call never overwrites cells another wave may still read.
 __device__ __forceinline__ void conf_block_best(float &v, int &i, float (*s_v)[4], int (*s_i)[4], int phase)
@@ -48,6 +55,7 @@ __device__ __forceinline__ void confidence_row(const DecideArgs &a, int m, int K
     const int tid = threadIdx.x;
     const int V = a.n_valid;
     float c[kConfRegs];
+    unsigned skip = 0;                                           // bit j: c[j] belongs to a forbidden token (conf_skip)
 
     // pass 1: the row maximum (blank included) and the arg-max the StepRecord holds (same comparison, same initial value)
     float mx = -INFINITY;
@@ -57,13 +65,15 @@ __device__ __forceinline__ void confidence_row(const DecideArgs &a, int m, int K
     for (int j = 0; j < kConfRegs; ++j) {
         const int n = tid + 256 * j;
         c[j] = 0.0f;
-        if (n < V) {
+        if (n < V && conf_skip(a, n, bonus)) skip |= 1u << j;
+        else if (n < V) {
             const float v = c[j] = conf_logit(a, m, n, bonus);
             mx = fmaxf(mx, v);
             if (n != a.blank && v > best) { best = v; best_i = n; }
         }
     }
     for (int n = tid + 256 * kConfRegs; n < V; n += 256) {
+        if (conf_skip(a, n, bonus)) continue;
         const float v = conf_logit(a, m, n, bonus);
         mx = fmaxf(mx, v);
         if (n != a.blank && v > best) { best = v; best_i = n; }
@@ -86,8 +96,9 @@ __device__ __forceinline__ void confidence_row(const DecideArgs &a, int m, int K
     float sum = 0.0f;
 #pragma unroll
     for (int j = 0; j < kConfRegs; ++j)
-        if (tid + 256 * j < V) sum += expf(c[j] - mx);
-    for (int n = tid + 256 * kConfRegs; n < V; n += 256) sum += expf(conf_logit(a, m, n, bonus) - mx);
+        if (tid + 256 * j < V && !(skip >> j & 1)) sum += expf(c[j] - mx);
+    for (int n = tid + 256 * kConfRegs; n < V; n += 256)
+        if (!conf_skip(a, n, bonus)) sum += expf(conf_logit(a, m, n, bonus) - mx);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
     if ((tid & 63) == 0) s_f[1][tid >> 6] = sum;
@@ -113,8 +124,9 @@ __device__ __forceinline__ void confidence_row(const DecideArgs &a, int m, int K
         };
 #pragma unroll
         for (int j = 0; j < kConfRegs; ++j)
-            if (tid + 256 * j < V) offer(c[j], tid + 256 * j);
-        for (int n = tid + 256 * kConfRegs; n < V; n += 256) offer(conf_logit(a, m, n, bonus), n);
+            if (tid + 256 * j < V && !(skip >> j & 1)) offer(c[j], tid + 256 * j);
+        for (int n = tid + 256 * kConfRegs; n < V; n += 256)
+            if (!conf_skip(a, n, bonus)) offer(conf_logit(a, m, n, bonus), n);
         conf_block_best(bv, bi, s_v, s_i, k & 1);
         if (bi < 0) break;                                       // fewer than K candidates (uniform: every thread holds the same result)
         if (tid == 0) { out->alt_id[k] = bi; out->alt_logit[k] = bv; }

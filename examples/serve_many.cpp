@@ -4,7 +4,7 @@
 // before it).  The reference has no counterpart: its sessions are fed one by one (example.cpp) and each runs its own ONNX graphs.
 //
 //   g++ -O2 -std=c++17 examples/serve_many.cpp -I include -L april_asr_amd -laprilasr -Wl,-rpath,$PWD/april_asr_amd -o serve_many
-//   ./serve_many model.april audio.raw [sessions=64] [mode=pipelined|lockstep] [input_rate] [--alternatives K] [--bias FILE]
+//   ./serve_many model.april audio.raw [sessions=64] [mode=pipelined|lockstep] [input_rate] [--alternatives K] [--bias FILE [--bias-strict]]
 //
 // Every session gets the same PCM16 file, rotated by (session index x 0.37 s) so that the streams differ.  With `input_rate` the file
 // is PCM16 at that rate and every session is told so (aprilx_session_set_input_rate): the library converts it to the model's rate on
@@ -14,7 +14,8 @@
 // (aprilx_session_set_confidence) and adds the mean confidence of the tokens in final results to the timing line.
 // `--bias FILE` (anywhere on the line): one "boost<TAB>phrase" per line; every session's search boosts these phrases
 // (aprilx_bias_create / aprilx_session_set_bias, one set shared by all sessions); `--bias-sessions N` gives the set to the first N
-// sessions only (the others are unbiased neighbours on an engine that has opted in).
+// sessions only (the others are unbiased neighbours on an engine that has opted in).  `--bias-strict` builds the set as a closed
+// phrase list (APRILX_BIAS_STRICT): the sessions that have it emit only sequences of the file's phrases.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -46,6 +47,14 @@ int main(int argc, char **argv)
     int alternatives = 0;
     const char *bias_file = nullptr;
     int bias_sessions = -1;
+    bool bias_strict = false;
+    for (int i = 1; i < argc; ++i)
+        if (!strcmp(argv[i], "--bias-strict")) {
+            bias_strict = true;
+            for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+            argc -= 1;
+            break;
+        }
     for (int i = 1; i + 1 < argc; ++i)
         if (!strcmp(argv[i], "--bias-sessions")) {
             bias_sessions = atoi(argv[i + 1]);
@@ -101,11 +110,11 @@ int main(int argc, char **argv)
         std::vector<const char *> ptrs;
         for (const std::string &p : phrases) ptrs.push_back(p.c_str());
         char err[256];
-        bias = aprilx_bias_create(model, ptrs.size(), ptrs.data(), boosts.data(), err, sizeof err);
+        bias = aprilx_bias_create_ex(model, ptrs.size(), ptrs.data(), boosts.data(), bias_strict ? APRILX_BIAS_STRICT : 0u, err, sizeof err);
         if (!bias) { fprintf(stderr, "bias set refused: %s\n", err); return 1; }
         int32_t states = 0; int64_t edges = 0;
         const int dropped = aprilx_bias_info(bias, &states, &edges);
-        fprintf(stderr, "bias set: %zu phrases (%d left out as unspellable), %d states, %lld token edges\n", phrases.size(), dropped, states, (long long)edges);
+        fprintf(stderr, "bias set%s: %zu phrases (%d left out as unspellable), %d states, %lld token edges\n", bias_strict ? " (strict)" : "", phrases.size(), dropped, states, (long long)edges);
     }
     std::vector<Stream> streams((size_t)n);
     std::vector<AprilASRSession> sessions((size_t)n);

@@ -184,12 +184,24 @@ typedef struct AprilxBias_i *AprilxBias;
  * edges, a vocabulary over 8192 tokens.  Phrases that no sequence of the model's tokens can spell are left out and counted
  * (aprilx_bias_info; err then holds a note although the call succeeds). */
 APRIL_EXPORT AprilxBias aprilx_bias_create(AprilASRModel model, size_t n, const char *const *phrases, const float *boosts, char *err, size_t err_cap);
+/* Strict sets: a CLOSED phrase list (an IVR menu, digit strings, a spelling alphabet, command-and-control).  A session with such a set
+ * emits only sequences of its phrases: at every point the search may pick only the tokens that continue a phrase towards its end -- and,
+ * at the start and where a phrase has ended, the tokens that begin one --; every other non-blank token takes no part in the arg-max.  The
+ * blank stays free, so the session can still say nothing.  Boosts work as in any set (0 is usual here).  A round in which no permitted
+ * token has a usable logit resolves to blank.  Confidences of such a session are taken over the blank and the permitted tokens.
+ * aprilx_bias_create_ex with flags = 0 is aprilx_bias_create; unknown flag bits are refused; a strict set of which no phrase can be
+ * spelled is refused (it would permit nothing). */
+#define APRILX_BIAS_STRICT 1u
+APRIL_EXPORT AprilxBias aprilx_bias_create_ex(AprilASRModel model, size_t n, const char *const *phrases, const float *boosts, uint32_t flags, char *err,
+                                              size_t err_cap);
+/* The flags the set was built with (-1: no set). */
+APRIL_EXPORT int aprilx_bias_flags(AprilxBias bias);
 /* Sessions still using the set keep it alive. */
 APRIL_EXPORT void aprilx_bias_free(AprilxBias bias);
 /* Trie states and effective token edges of the set; returns the number of phrases left out as unspellable (-1: no set). */
 APRIL_EXPORT int aprilx_bias_info(AprilxBias bias, int32_t *states, int64_t *edges);
 /* The effective edges of one state, token ids ascending (no GPU): returns their number, -1 on a bad state or when cap is too small
- * (with all three arrays NULL: only the count). */
+ * (with all three arrays NULL: only the count).  For a strict set these are the permitted tokens of the state. */
 APRIL_EXPORT int aprilx_bias_edges(AprilxBias bias, int32_t state, int32_t *tok, int32_t *next, float *bonus, size_t cap);
 /* Extends aas_create_session: the session's search uses the set from now on, starting at the root; NULL = off.  0 on success; -1 when
  * the set was built for another token list, the engine already holds 64 different sets in use, or the session has audio queued or fed since its
@@ -202,6 +214,9 @@ APRIL_EXPORT int aprilx_session_bias_state(AprilASRSession session, int32_t *hos
  * without a set.  op 1 returns the states to the root. */
 APRIL_EXPORT int aprilx_run_decide_biased(AprilASRModel model, int n, int op, const float *logits, float early_emit, const int32_t *now_ms, int round,
                                           int32_t *state_io, void *records_out, AprilxBias bias, int32_t *bias_state_io);
+/* Tests only: aprilx_run_confidence with the set on the rows whose bias_state[i] >= 0 (the row's trie state); -1 = a row without a set. */
+APRIL_EXPORT int aprilx_run_confidence_biased(AprilASRModel model, int n, const float *logits, int k, AprilxBias bias, const int32_t *bias_state,
+                                              AprilxTokenInfo *out);
 
 /* ---- tracing / statistics ---------------------------------------------------------------*/
 /* every joiner evaluation of this session appends `vocab` floats to buf (tests only; chunk steps of a traced session are
