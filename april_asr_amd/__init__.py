@@ -281,6 +281,26 @@ class Model:
             raise ValueError("aprilx_run_decide_biased refused the call")
         return rec, st, bs
 
+    def run_decide_opts(self, logits, early_emit, now_ms, rnd, state, opts, bias=None, bias_state=None, op: int = 0):
+        """One decision round on GIVEN logits rows with per-row search options (aprilx_run_decide_opts; tests): `opts` has one entry per
+        row, None (a row without options) or (endpoint_silence_ms, blank_penalty).  With `bias`, the set acts on the rows whose bias_state
+        is >= 0.  Returns (records, search states [n][4], bias states [n] or None) as run_decide_biased."""
+        st = np.ascontiguousarray(state, np.int32).reshape(-1, 4).copy()
+        n = st.shape[0]
+        lg = np.ascontiguousarray(logits, np.float32).reshape(n, self.dims.vocab)
+        now = np.ascontiguousarray(now_ms, np.int32).reshape(n)
+        bs = np.ascontiguousarray(bias_state, np.int32).reshape(n).copy() if bias is not None else None
+        arr = (_ffi.AprilxSearchOptions * n)()
+        for i, o in enumerate(opts):
+            if o is not None:
+                arr[i].size = C.sizeof(_ffi.AprilxSearchOptions); arr[i].endpoint_silence_ms = int(o[0]); arr[i].blank_penalty = float(o[1])
+        rec = np.zeros(n, np.dtype([("idx", np.int32), ("max", np.float32), ("blank", np.float32), ("flags", np.uint32)]))
+        rc = self._L.aprilx_run_decide_opts(self._handle, n, int(op), lg.ctypes.data, float(early_emit), now.ctypes.data, int(rnd), st.ctypes.data,
+                                            rec.ctypes.data, bias._handle if bias is not None else None, bs.ctypes.data if bs is not None else None, arr)
+        if rc != 0:
+            raise ValueError("aprilx_run_decide_opts refused the call")
+        return rec, st, bs
+
     def stats(self, device_index: int = 0):
         s = _ffi.AprilxStats()
         self._L.aprilx_model_stats(self._handle, device_index, C.byref(s))
@@ -366,14 +386,15 @@ _HANDLER = _ffi.HANDLER(_dispatch)
 class Session:
     def __init__(self, model: Model, callback: Callable[[Result, List[Token]], None], asynchronous: bool = False,
                  no_rt: bool = False, speaker_name: str = "", raw_events: bool = False, counters=None, input_sample_rate=None,
-                 alternatives=None, bias=None):
+                 alternatives=None, bias=None, endpoint_silence_ms=None, blank_penalty=None, max_utterance_ms=None):
         """`counters`: a uint64 ndarray of 6 entries; when given, results are only counted by a C handler inside the
         library (calls, partial, final, cant_keep_up, silence, tokens) and `callback` is never invoked.
         `input_sample_rate`: the rate of the PCM this session will receive (converted to the model's rate on the GPU); None: the
         model's rate.
         `alternatives`: K in 1..8: every delivered Token carries its log-softmax, the blank's and the K best candidates
         (set_confidence); None / 0: off.
-        `bias`: a Bias (Model.bias): the search boosts the tokens that continue one of its phrases (set_bias); None: off."""
+        `bias`: a Bias (Model.bias): the search boosts the tokens that continue one of its phrases (set_bias); None: off.
+        `endpoint_silence_ms`, `blank_penalty`, `max_utterance_ms`: the session's search options (set_search_options); all None: none."""
         self._L = model._L
         self.info_log = None      # tests: a list that receives (type, [the token's AprilxTokenInfo as bytes, or None]) per result
         self.model = model
@@ -402,6 +423,8 @@ class Session:
             self.set_confidence(alternatives)
         if bias is not None:
             self.set_bias(bias)
+        if endpoint_silence_ms is not None or blank_penalty is not None or max_utterance_ms is not None:
+            self.set_search_options(endpoint_silence_ms, blank_penalty, max_utterance_ms)
 
     def _on_result(self, result_type, count, tokens):
         if self.info_log is not None:
@@ -447,6 +470,28 @@ class Session:
         it off (aprilx_session_set_bias).  Allowed right after creation and after a completed flush."""
         if self._L.aprilx_session_set_bias(self._handle, bias._handle if bias is not None else None) != 0:
             raise ValueError("bias set refused (built for another token list, 64 sets in use on the engine already, or audio fed since the last flush)")
+
+    def set_search_options(self, endpoint_silence_ms=None, blank_penalty=None, max_utterance_ms=None) -> None:
+        """The session's search options (aprilx_session_set_search_options): the silence after the last token that
+        ends an utterance (200..60000 ms, default 2200), the constant subtracted from the blank logit in the decision (|p| <= 100, default
+        0) and the cap on an utterance's length (0 = off, or 1000..600000 ms).  An argument left None takes its default; all three None
+        returns the session to no options.  Allowed right after creation and after a completed flush; the options persist across flushes."""
+        if endpoint_silence_ms is None and blank_penalty is None and max_utterance_ms is None:
+            rc = self._L.aprilx_session_set_search_options(self._handle, None)
+        else:
+            o = _ffi.AprilxSearchOptions(C.sizeof(_ffi.AprilxSearchOptions), 2200 if endpoint_silence_ms is None else int(endpoint_silence_ms),
+                                         0 if max_utterance_ms is None else int(max_utterance_ms), 0.0 if blank_penalty is None else float(blank_penalty))
+            rc = self._L.aprilx_session_set_search_options(self._handle, C.byref(o))
+        if rc != 0:
+            raise ValueError("search options refused (a value out of range, or audio fed since the last flush)")
+
+    @property
+    def search_options(self):
+        """(endpoint_silence_ms, blank_penalty, max_utterance_ms) of the session, or None when it has no options"""
+        o = _ffi.AprilxSearchOptions()
+        if self._L.aprilx_session_search_options(self._handle, C.byref(o)) != 1:
+            return None
+        return int(o.endpoint_silence_ms), float(o.blank_penalty), int(o.max_utterance_ms)
 
     def bias_state(self):
         """(host, device) trie state of the session's phrase boosting -- derived independently, must agree (tests)"""

@@ -52,6 +52,10 @@ class AprilxTokenInfo(C.Structure):
                 ("alt_id", C.c_int32 * 8), ("alt_logit", C.c_float * 8)]
 
 
+class AprilxSearchOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("endpoint_silence_ms", C.c_uint32), ("max_utterance_ms", C.c_uint32), ("blank_penalty", C.c_float)]
+
+
 class AprilxLoadInfo(C.Structure):
     _fields_ = [("broadcast_ms", C.c_double), ("comm_init_ms", C.c_double), ("broadcast_bytes", C.c_uint64),
                 ("ranks", C.c_int32), ("used_rccl", C.c_int32)]
@@ -74,6 +78,7 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_bias_create", "aprilx_bias_free", "aprilx_bias_info", "aprilx_bias_edges", "aprilx_session_set_bias", "aprilx_session_bias_state",
     "aprilx_run_decide_biased", "aprilx_greedy_set_bias", "aprilx_greedy_bias_state",
     "aprilx_bias_create_ex", "aprilx_bias_flags", "aprilx_run_confidence_biased",
+    "aprilx_session_set_search_options", "aprilx_session_search_options", "aprilx_run_decide_opts", "aprilx_greedy_set_search_options",
 ]
 
 _lib = None
@@ -158,6 +163,10 @@ def lib():
     L.aprilx_run_decide_biased.argtypes = [vp, C.c_int, C.c_int, vp, C.c_float, vp, C.c_int, vp, vp, vp, vp]; L.aprilx_run_decide_biased.restype = C.c_int
     L.aprilx_greedy_set_bias.argtypes = [vp, vp]; L.aprilx_greedy_set_bias.restype = C.c_int
     L.aprilx_greedy_bias_state.argtypes = [vp]; L.aprilx_greedy_bias_state.restype = C.c_int
+    L.aprilx_session_set_search_options.argtypes = [vp, C.POINTER(AprilxSearchOptions)]; L.aprilx_session_set_search_options.restype = C.c_int
+    L.aprilx_session_search_options.argtypes = [vp, C.POINTER(AprilxSearchOptions)]; L.aprilx_session_search_options.restype = C.c_int
+    L.aprilx_run_decide_opts.argtypes = [vp, C.c_int, C.c_int, vp, C.c_float, vp, C.c_int, vp, vp, vp, vp, vp]; L.aprilx_run_decide_opts.restype = C.c_int
+    L.aprilx_greedy_set_search_options.argtypes = [vp, C.POINTER(AprilxSearchOptions)]; L.aprilx_greedy_set_search_options.restype = C.c_int
     _lib = L
     return L
 

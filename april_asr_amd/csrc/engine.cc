@@ -365,6 +365,8 @@ Engine::~Engine()
     for (auto &b : bias_sets_) if (b.dev) (void)hipFree(b.dev);
     for (void *p : {(void *)bias_set_d_, (void *)bias_state_d_, (void *)bias_desc_d_}) if (p) (void)hipFree(p);
     for (void *p : {(void *)bias_set_h_, (void *)bias_desc_h_}) if (p) (void)hipHostFree(p);
+    if (opt_d_) (void)hipFree(opt_d_);
+    if (opt_h_) (void)hipHostFree(opt_h_);
     if (ws_g_) (void)hipFree(ws_g_);
     if (conv_wt_) (void)hipFree(conv_wt_);
     if (dec_table_) (void)hipFree(dec_table_);
@@ -450,6 +452,7 @@ void Engine::free_slot(int slot)
     // the next flight is launched (begin_flight), stream-ordered ahead of any later use of the slot
     if (conf_ever_.load(std::memory_order_relaxed)) set_slot_confidence(slot, 0);     // the next owner starts with confidences off
     if (bias_ever_.load(std::memory_order_relaxed)) set_slot_bias(slot, nullptr);      // ... without a bias set, at the root
+    if (opt_ever_.load(std::memory_order_relaxed)) set_slot_search_options(slot, SearchOpt{0u, 0.0f});      // ... and without search options
     std::lock_guard<std::mutex> g(slot_mu_);
     zero_pending_.push_back(slot);
     --live_;
@@ -977,6 +980,7 @@ void Engine::run_greedy_rounds(int n, const GreedyIo &io)
         a.run_flags = flags_d_; a.rerun_flags = flags_d_ + 4;
         a.conf_k = conf_k_d_; a.conf_ring = conf_d_;          // (null until a session of this engine asks for confidences)
         a.bias_set = bias_set_d_; a.bias_state = bias_state_d_; a.bias_desc = bias_desc_d_;      // (null until a session of this engine has a bias set)
+        a.opt = opt_d_;                                       // (null until a session of this engine has search options)
         timed_begin(T_DEC); launch_decide(a, search_stream_); timed_end(T_DEC);
         if (!dec_table_) run_decproj(n, d_slots, dirty_d_, flags_d_ + 4 + round, gen);
     }
@@ -1542,6 +1546,32 @@ void Engine::apply_bias_pending()
     HIP_CHECK(hipMemcpyAsync(bias_set_d_, bias_set_h_, (size_t)cfg_.max_slots * 4, hipMemcpyHostToDevice, stream_));
 }
 
+// ---------------------------------------------------------------- search options
+// Stepping thread, between two flights' enqueues (as apply_confidence_pending): the first opt-in drops the captured graphs, whose
+// decision launches hold the null pointer; from then on the pointer never changes.  The slots that change belong to idle sessions.
+void Engine::apply_search_options_pending()
+{
+    std::vector<std::pair<int, SearchOpt>> todo;
+    { std::lock_guard<std::mutex> g(opt_mu_); todo.swap(opt_pending_); opt_has_pending_.store(false, std::memory_order_release); }
+    if (!opt_h_) {
+        bool any = false;
+        for (const auto &t : todo) any = any || t.second.endpoint_ms != 0;
+        if (!any) return;
+        std::lock_guard<std::mutex> cg(capture_mu_);
+        HipLegacyLock legacy;
+        sync();
+        drop_graphs();
+        const size_t S = (size_t)cfg_.max_slots;
+        opt_d_ = dmalloc<SearchOpt>(S); opt_h_ = hmalloc<SearchOpt>(S);
+        memset(opt_h_, 0, S * sizeof(SearchOpt));
+        LOGI("engine: search options on");
+    }
+    for (const auto &t : todo) if (t.first >= 0 && t.first < cfg_.max_slots) opt_h_[t.first] = t.second;
+    // whole table, stream-ordered ahead of this flight's steps; entries of other sessions keep their values
+    std::lock_guard<std::mutex> cg(capture_mu_);
+    HIP_CHECK(hipMemcpyAsync(opt_d_, opt_h_, (size_t)cfg_.max_slots * sizeof(SearchOpt), hipMemcpyHostToDevice, stream_));
+}
+
 int Engine::read_bias_state(int slot)
 {
     if (!bias_ever_.load(std::memory_order_relaxed)) return 0;
@@ -1585,6 +1615,7 @@ void Engine::begin_flight()
     if (flight_open_[p]) { HIP_CHECK(hipEventSynchronize(flight_done_[p])); flight_open_[p] = false; }
     if (conf_has_pending_.load(std::memory_order_acquire)) apply_confidence_pending();
     if (bias_has_pending_.load(std::memory_order_acquire)) apply_bias_pending();
+    if (opt_has_pending_.load(std::memory_order_acquire)) apply_search_options_pending();
     conf_spans_.clear();
     ring_base_ = (size_t)p * ring_cap_; rec_base_ = (size_t)p * rec_cap_;
     ring_pos_ = ring_base_; rec_pos_ = rec_base_; flight_steps_ = 0;
@@ -1805,9 +1836,16 @@ void Engine::debug_decide_biased(int n, int op, const float *logits, float early
     debug_decide_impl(n, op, logits, early_emit, now_ms, round, state_io, rec_out, &set, bias_state_io);
 }
 
+void Engine::debug_decide_opts(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
+                               const BiasSet *set, int32_t *bias_state_io, const SearchOpt *opts)
+{
+    debug_decide_impl(n, op, logits, early_emit, now_ms, round, state_io, rec_out, set, bias_state_io, opts);
+}
+
 // `set` non-null: tables of its own for the call -- row i uses the set from state bias_state_io[i], or none when that is -1
+// `opts` non-null: a table of its own likewise -- row i (= slot i) has opts[i]
 void Engine::debug_decide_impl(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
-                               const BiasSet *set, int32_t *bias_state_io)
+                               const BiasSet *set, int32_t *bias_state_io, const SearchOpt *opts)
 {
     std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order everywhere: bias_mu_ first where it is needed -- apply_bias_pending, read_bias_state --, then capture_mu_, then the process-wide legacy-stream lock; step() takes the last two in that order)
     HipLegacyLock legacy;
@@ -1832,6 +1870,11 @@ void Engine::debug_decide_impl(int n, int op, const float *logits, float early_e
         HIP_CHECK(hipMemcpy(bstate_d, bstate.data(), (size_t)n * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(bdesc_d, &desc, sizeof desc, hipMemcpyHostToDevice));
     }
+    SearchOpt *opt_d = nullptr;
+    if (opts) {
+        opt_d = dmalloc<SearchOpt>((size_t)n);
+        HIP_CHECK(hipMemcpy(opt_d, opts, (size_t)n * sizeof(SearchOpt), hipMemcpyHostToDevice));
+    }
     if (op == 1) {
         DecRowsArgs a; a.slot_idx = slots_d; a.M = n; a.op = 1; a.blank = P_.blank_id; a.state = gstate_; a.dec = dec_params(); a.de_out = nullptr;
         a.bias_state = bstate_d;
@@ -1852,6 +1895,7 @@ void Engine::debug_decide_impl(int n, int op, const float *logits, float early_e
         a.slot_idx = slots_d; a.now_ms = now_d; a.active = active_d; a.dirty = dirty_d; a.tok_class = cls_; a.state = gstate_;
         a.rec = rec_d; a.round = round; a.gen = 1; a.dec = dec_params(); a.de_out = nullptr;
         a.bias_set = bset_d; a.bias_state = bstate_d; a.bias_desc = bdesc_d;
+        a.opt = opt_d;
         launch_decide(a, stream_);
         sync();
         HIP_CHECK(hipMemcpy(rec_out, rec_d, (size_t)n * sizeof(StepRecord), hipMemcpyDeviceToHost));
@@ -1865,6 +1909,7 @@ void Engine::debug_decide_impl(int n, int op, const float *logits, float early_e
         for (int i = 0; i < n; ++i) if (bias_state_io[i] >= 0) bias_state_io[i] = bstate[(size_t)i];
         for (void *p : {(void *)bset_d, (void *)bstate_d, (void *)bdesc_d, barrays_d}) (void)hipFree(p);
     }
+    if (opt_d) (void)hipFree(opt_d);
     (void)hipFree(slots_d); (void)hipFree(now_d); (void)hipFree(active_d); (void)hipFree(dirty_d); (void)hipFree(rec_d);
     zero_slots(n);
 }

@@ -215,6 +215,20 @@ public:
     // aprilx_run_decide_biased: debug_decide with `set` on the rows whose bias_state_io is >= 0 (-1: a row without a set)
     void debug_decide_biased(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
                              const BiasSet &set, int32_t *bias_state_io);
+    // ---- search options, the same life cycle: set_slot_search_options() only QUEUES the slot's entry (any thread,
+    // for an idle session's slot; endpoint_ms 0 = no options); begin_flight() applies it on the stepping thread: the first opt-in of an
+    // engine allocates the per-slot table (device + pinned host; the captured pointer never changes afterwards) and drops the captured graphs.
+    void set_slot_search_options(int slot, SearchOpt o)
+    {
+        std::lock_guard<std::mutex> g(opt_mu_);
+        if (o.endpoint_ms == 0 && !opt_ever_.load(std::memory_order_relaxed)) return;      // nothing was ever on
+        opt_pending_.push_back(std::make_pair(slot, o));
+        if (o.endpoint_ms) opt_ever_.store(true, std::memory_order_relaxed);
+        opt_has_pending_.store(true, std::memory_order_release);
+    }
+    // aprilx_run_decide_opts: debug_decide with opts[i] on row i (endpoint_ms 0 = a row without options); `set` may be null
+    void debug_decide_opts(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
+                           const BiasSet *set, int32_t *bias_state_io, const SearchOpt *opts);
     void sync();                               // stepping thread (or under capture_mu_): waits for the three streams and clears the cross-stream dependency flags
     void sync_streams();                       // any thread: waits for the three streams, nothing else
 
@@ -365,9 +379,15 @@ private:
     int32_t *bias_set_d_ = nullptr, *bias_set_h_ = nullptr, *bias_state_d_ = nullptr;     // [slots] device, pinned host mirror; [slots] device
     BiasDesc *bias_desc_d_ = nullptr, *bias_desc_h_ = nullptr;                           // [kBiasSets]
     void apply_bias_pending();
+    // search options
+    std::mutex opt_mu_;
+    std::vector<std::pair<int, SearchOpt>> opt_pending_;   // (slot, entry) not yet applied (opt_mu_)
+    std::atomic<bool> opt_has_pending_{false}, opt_ever_{false};
+    SearchOpt *opt_d_ = nullptr, *opt_h_ = nullptr;        // [slots] device, pinned host mirror (stepping thread)
+    void apply_search_options_pending();
     BiasDesc upload_bias(const BiasSet &set, void **dev, hipStream_t st);
     void debug_decide_impl(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
-                           const BiasSet *set, int32_t *bias_state_io);
+                           const BiasSet *set, int32_t *bias_state_io, const SearchOpt *opts = nullptr);
     void note_conf_step(int k, const int *slots, int m, size_t records);
     bool flight_open_[2] = {false, false};     // flight_done_[p] has been recorded and not yet waited for by begin_flight (wait_flight leaves it set: waiting twice is free)
     // streams (engine.cc "streams"): front end / search beside the layer chain, the per-parity buffers that make it safe

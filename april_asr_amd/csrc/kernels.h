@@ -226,6 +226,11 @@ enum TokClassBits { TKC_WORD_START = 1, TKC_SENT_END = 2, TKC_COMMA = 4, TKC_DOT
 // Phrase boosting (bias.h): one bias set on the device -- the effective token edges of every trie state, CSR
 struct BiasDesc { const int32_t *state_off = nullptr, *edge_tok = nullptr, *edge_next = nullptr; const float *edge_bonus = nullptr; int32_t n_states = 0, flags = 0; };      // flags: BiasSet::flags (kBiasStrict)
 
+// Per-session search options: one entry per slot.  endpoint_ms == 0: the slot's session has none (the decision
+// runs its unchanged lines); else the silence that ends an utterance in ms (200 .. 60000) and the blank penalty p (bl' = bl - p).
+struct SearchOpt { uint32_t endpoint_ms; float blank_penalty; };
+static_assert(sizeof(SearchOpt) == 8, "SearchOpt is 2 x 32 bit");
+
 struct DecEmbedParams {
     const float *emb = nullptr;            // [vocab][d]
     const float *conv_w = nullptr;         // [d][d/groups][context]
@@ -270,6 +275,8 @@ struct DecideArgs {
     const int32_t *bias_set = nullptr;     // [slots]
     int32_t *bias_state = nullptr;         // [slots]
     const BiasDesc *bias_desc = nullptr;
+    // search options: null unless a session of the engine opted in
+    const SearchOpt *opt = nullptr;        // [slots]
 };
 void launch_decide(const DecideArgs &a, hipStream_t s);
 

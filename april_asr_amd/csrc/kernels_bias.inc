@@ -77,8 +77,8 @@ __device__ __forceinline__ void bias_scan(const DecideArgs &a, int m, const Bias
     }
 }
 
-// thread 0, after the decision: a non-blank decision follows the token's effective edge (else the root); the >= 2200 ms silence
-// branch returns to the root whether or not the context was cleared
+// thread 0, after the decision: a non-blank decision follows the token's effective edge (else the root); the silence branch (>= 2200 ms, or
+// the session's own endpoint silence) returns to the root whether or not the context was cleared
 __device__ __forceinline__ void bias_row_end(const DecideArgs &a, const BiasRow &br, int slot, bool is_blank, int tok, bool silence)
 {
     int s = br.state;

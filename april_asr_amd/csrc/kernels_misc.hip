@@ -133,7 +133,10 @@ __device__ __forceinline__ void dec_embed_row(const DecEmbedParams &p, int tok0,
 // CONF = true adds the side record of rows whose session asked for it (kernels_confidence.inc), after the decision.
 // BIAS = true (engines where a session has a phrase-boosting set; kernels_bias.inc): rows whose slot has a set
 // take the arg-max on v' = v + bonus(state, n) and move the slot's trie state with the decision; the other rows run the lines below.
-template <bool CONF, bool BIAS>
+// OPT = true (engines where a session has search options): thread 0 loads the slot's SearchOpt after the
+// GreedyState; a row whose slot has options (endpoint_ms != 0) compares bl' = bl - p in place of bl and ends the utterance after its
+// own silence E in place of 2200 ms.  The record keeps the raw blank logit.  The other rows, and OPT = false, run the lines as they were.
+template <bool CONF, bool BIAS, bool OPT>
 __device__ __forceinline__ void decide_body(const DecideArgs &a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char bias_lds[];      // BIAS: bonus[V] | next[V] (bias_lds_bytes)
@@ -182,12 +185,14 @@ __device__ __forceinline__ void decide_body(const DecideArgs &a)
             if (oi >= 0 && (bi < 0 || ov > b || (ov == b && oi < bi))) { b = ov; bi = oi; }
         }
         // the blank logit sits in exactly one wave; the others contributed +0.0f
-        const float bl = s_blank[(a.blank & 255) >> 6];
+        float bl = s_blank[(a.blank & 255) >> 6];
         rec->idx = bi; rec->max_val = b; rec->blank_val = bl;
 
         // ---- decision (Greedy::on_joint on the host replays exactly this from the record)
         const int slot = a.slot_idx[m];
         GreedyState st = a.state[slot];
+        SearchOpt so; so.endpoint_ms = 0u; so.blank_penalty = 0.0f;
+        if (OPT) { so = a.opt[slot]; if (so.endpoint_ms) bl = bl - so.blank_penalty; }      // bl' (the record above holds the raw value)
         int tok = bi; float tv = b;
         if (tok < 0) { tok = a.blank == 0 ? 1 : 0; tv = -9999999999.0f; }        // no logit beat the initial value (NaNs)
         const bool cleared = st.ctx1 == a.blank;                                  // :322
@@ -200,7 +205,7 @@ __device__ __forceinline__ void decide_body(const DecideArgs &a)
         if (!cleared && punct && !same && tv > (bl - 3.5f)) is_blank = false;     // :356-358
         const unsigned now = (unsigned)a.now_ms[m];
         unsigned flags = REC_VALID;
-        bool rerun = false;
+        bool rerun = false, silence = false;
         if (!is_blank) {                                                          // :361-400
             st.last_emit_ms = now;
             st.ctx0 = st.ctx1; st.ctx1 = tok;
@@ -208,7 +213,9 @@ __device__ __forceinline__ void decide_body(const DecideArgs &a)
             rerun = true;
         } else {                                                                  // :401-426
             flags |= REC_BLANK;
-            if (now - st.last_emit_ms >= 2200u) {                                 // FINAL, clear context, SILENCE
+            if (OPT && so.endpoint_ms) silence = now - st.last_emit_ms >= so.endpoint_ms;   // a row with options: its own endpoint silence E
+            else if (now - st.last_emit_ms >= 2200u) { silence = true; }          // (the line tests/mutate_device_decide.py edits)
+            if (silence) {                                                        // FINAL, clear context, SILENCE
                 st.last_tok = -1;
                 if (st.ctx0 != a.blank) { st.ctx0 = a.blank; st.ctx1 = a.blank; rerun = true; }   // :296-301
             }
@@ -217,7 +224,7 @@ __device__ __forceinline__ void decide_body(const DecideArgs &a)
         if (rerun) flags |= REC_CTX;
         rec->flags = flags;
         a.state[slot] = st;
-        if (BIAS && br.bonus) bias_row_end(a, br, slot, is_blank, tok, is_blank && now - st.last_emit_ms >= 2200u);
+        if (BIAS && br.bonus) bias_row_end(a, br, slot, is_blank, tok, OPT ? silence : is_blank && now - st.last_emit_ms >= 2200u);      // (!OPT: the argument as it was, so that the bias forms compile to what they were)
         a.dirty[m] = rerun ? 1 : 0;
         if (a.run_flags) {
             if (!is_blank && a.round < 2) a.run_flags[a.round + 1] = a.gen;   // plain stores of the same value: no atomics needed
@@ -236,10 +243,14 @@ __device__ __forceinline__ void decide_body(const DecideArgs &a)
     }
 }
 
-__global__ __launch_bounds__(256) void decide_kernel(DecideArgs a) { decide_body<false, false>(a); }
-__global__ __launch_bounds__(256) void decide_conf_kernel(DecideArgs a) { decide_body<true, false>(a); }
-__global__ __launch_bounds__(256) void decide_bias_kernel(DecideArgs a) { decide_body<false, true>(a); }
-__global__ __launch_bounds__(256) void decide_conf_bias_kernel(DecideArgs a) { decide_body<true, true>(a); }
+__global__ __launch_bounds__(256) void decide_kernel(DecideArgs a) { decide_body<false, false, false>(a); }
+__global__ __launch_bounds__(256) void decide_conf_kernel(DecideArgs a) { decide_body<true, false, false>(a); }
+__global__ __launch_bounds__(256) void decide_bias_kernel(DecideArgs a) { decide_body<false, true, false>(a); }
+__global__ __launch_bounds__(256) void decide_conf_bias_kernel(DecideArgs a) { decide_body<true, true, false>(a); }
+__global__ __launch_bounds__(256) void decide_opt_kernel(DecideArgs a) { decide_body<false, false, true>(a); }
+__global__ __launch_bounds__(256) void decide_conf_opt_kernel(DecideArgs a) { decide_body<true, false, true>(a); }
+__global__ __launch_bounds__(256) void decide_bias_opt_kernel(DecideArgs a) { decide_body<false, true, true>(a); }
+__global__ __launch_bounds__(256) void decide_conf_bias_opt_kernel(DecideArgs a) { decide_body<true, true, true>(a); }
 
 void launch_decide(const DecideArgs &a, hipStream_t s)
 {
@@ -247,8 +258,16 @@ void launch_decide(const DecideArgs &a, hipStream_t s)
     if (a.bias_set) {
         if (a.n_valid > 8192 || !a.bias_state || !a.bias_desc) { fprintf(stderr, "libapril(mi355x): launch_decide: phrase boosting needs a vocabulary of at most 8192 tokens and all three tables\n"); abort(); }
         const size_t lds = bias_lds_bytes(a.n_valid);
-        if (conf) hipLaunchKernelGGL(decide_conf_bias_kernel, dim3((unsigned)a.M), dim3(256), lds, s, a);
+        if (a.opt) {
+            if (conf) hipLaunchKernelGGL(decide_conf_bias_opt_kernel, dim3((unsigned)a.M), dim3(256), lds, s, a);
+            else hipLaunchKernelGGL(decide_bias_opt_kernel, dim3((unsigned)a.M), dim3(256), lds, s, a);
+        }
+        else if (conf) hipLaunchKernelGGL(decide_conf_bias_kernel, dim3((unsigned)a.M), dim3(256), lds, s, a);
         else hipLaunchKernelGGL(decide_bias_kernel, dim3((unsigned)a.M), dim3(256), lds, s, a);
+    }
+    else if (a.opt) {
+        if (conf) hipLaunchKernelGGL(decide_conf_opt_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(decide_opt_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a);
     }
     else if (conf) hipLaunchKernelGGL(decide_conf_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(decide_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a);

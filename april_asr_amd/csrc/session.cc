@@ -41,6 +41,7 @@ void Greedy::init(const ModelParams *p, const std::vector<uint8_t> *cls)
     head_ = last_call_head_ = 0;
     conf_k_ = 0; side_ = nullptr; evals_ = 0;
     bias_.reset(); bias_state_ = 0;
+    set_search_options(nullptr); first_ms_ = 0;
     emitted_silence_ = true;                       // april_session.c:64
     last_emit_ms_ = 0;
     ctx[0] = ctx[1] = 0;
@@ -142,7 +143,8 @@ bool Greedy::on_joint(const JointResult &r, float early_emit, size_t now_ms, std
     int best = r.idx;
     float best_v = r.max_val;
     if (best < 0) { best = blank == 0 ? 1 : 0; best_v = -9999999999.0f; }   // no logit beat the initial value (NaNs)
-    const float blank_v = r.blank_val;
+    const float blank_raw = r.blank_val;
+    const float blank_v = has_opt_ ? blank_raw - blank_penalty_ : blank_raw;      // bl' (DESIGN.md section 14); the token's logprob and the record keep the raw value
 
     const bool cleared = ctx[1] == blank;           // :322
     const bool same = ctx[1] == best;               // :326
@@ -182,15 +184,23 @@ bool Greedy::on_joint(const JointResult &r, float early_emit, size_t now_ms, std
                 prev.flags = (AprilTokenFlagBits)(prev.flags | APRIL_TOKEN_FLAG_SENTENCE_END_BIT);
             if (prev_eos) fin = true;
         }
+        // the utterance cap U: a word that begins U ms or more after the utterance's first token finalises what came before
+        if (has_opt_ && max_utt_ms_ && head_ > 0 && (flags & APRIL_TOKEN_FLAG_WORD_BOUNDARY_BIT) && now_ms - first_ms_ >= (size_t)max_utt_ms_) fin = true;
         if (fin) finalize_before_word(tok, out);
         if (head_ >= (size_t)(kMaxActive - 1)) { LOGE("No room left even after finalizing previous words"); head_ = 0; }
+        if (head_ == 0) first_ms_ = now_ms;
         emit_partial(&tok, best, true, out);
         emitted_silence_ = false;
     } else {                                        // :401-426
         const size_t gap = now_ms - last_emit_ms_;
         const float decayed = best_v - (float)gap / 3000.0f;
         const bool confident = !same && decayed > (blank_v - 4.0f);
-        if (gap >= 2200) {
+        bool endpoint;
+        if (has_opt_) endpoint = gap >= (size_t)endpoint_ms_;      // the session's own endpoint silence E
+        // (without options the literal line, in this shape: tests/mutate_product_state_machine.py edits the text of the next line up to its first brace, which
+        // must occur exactly once and must decide for every session without options; folding it into `gap >= endpoint_ms_` breaks that yardstick)
+        else if (gap >= 2200) { endpoint = true; } else endpoint = false;
+        if (endpoint) {
             finalize_all(out);
             clear_context();
             bias_state_ = 0;
@@ -499,6 +509,16 @@ bool Scheduler::set_confidence(Session *s, int k)
         if (k == s->greedy.confidence()) return true;
         s->greedy.set_confidence(k);
         eng_->set_slot_confidence(s->slot, k);          // (queued: the stepping thread applies it before the session's next flight)
+        return true;
+    });
+}
+
+bool Scheduler::set_search_options(Session *s, const AprilxSearchOptions *o)
+{
+    return configure(s, [&] {
+        s->greedy.set_search_options(o);
+        // (queued: the stepping thread applies it before the session's next flight; U is the host's alone)
+        eng_->set_slot_search_options(s->slot, o ? SearchOpt{o->endpoint_silence_ms, o->blank_penalty} : SearchOpt{0u, 0.0f});
         return true;
     });
 }

@@ -74,6 +74,15 @@ public:
     void set_bias(std::shared_ptr<const BiasSet> set) { bias_ = std::move(set); bias_state_ = 0; }
     const BiasSet *bias() const { return bias_.get(); }
     int bias_state() const { return bias_state_; }
+    // search options: null = none (the lines below run as they always did); else the endpoint silence E replaces
+    // the 2200 ms, bl' = bl - p replaces the blank logit in the three comparisons, and U > 0 caps the utterance length at a word boundary
+    void set_search_options(const AprilxSearchOptions *o)
+    {
+        has_opt_ = o != nullptr;
+        endpoint_ms_ = o ? o->endpoint_silence_ms : 2200; max_utt_ms_ = o ? o->max_utterance_ms : 0; blank_penalty_ = o ? o->blank_penalty : 0.0f;
+    }
+    bool has_search_options() const { return has_opt_; }
+    AprilxSearchOptions search_options() const { return AprilxSearchOptions{(uint32_t)sizeof(AprilxSearchOptions), endpoint_ms_, max_utt_ms_, blank_penalty_}; }
     int ctx[2] = {0, 0};
     bool ctx_dirty = false;                   // decoder must be re-run for this session
 
@@ -101,6 +110,10 @@ private:
     size_t head_ = 0, last_call_head_ = 0;
     bool emitted_silence_ = true;
     size_t last_emit_ms_ = 0;
+    bool has_opt_ = false;
+    uint32_t endpoint_ms_ = 2200, max_utt_ms_ = 0;
+    float blank_penalty_ = 0.0f;
+    size_t first_ms_ = 0;                     // time_ms of the first token put into active_[] since it was last emptied (head_ > 0)
 };
 
 struct FrameBook {
@@ -222,6 +235,8 @@ public:
     bool set_confidence(Session *s, int k);
     // aprilx_session_set_bias: the same rule; null = off.  False also when the engine has no room for another set
     bool set_bias(Session *s, std::shared_ptr<const BiasSet> set);
+    // aprilx_session_set_search_options: the same rule; null = back to no options
+    bool set_search_options(Session *s, const AprilxSearchOptions *o);
     void wait_idle_many(Session *const *ss, int n);
     // until every listed session has at most `max_open` feeds that were submitted and not completed yet (pipelined group feeds)
     void wait_backlog(Session *const *ss, int n, uint64_t max_open);

@@ -5,6 +5,7 @@
 //
 //   g++ -O2 -std=c++17 examples/serve_many.cpp -I include -L april_asr_amd -laprilasr -Wl,-rpath,$PWD/april_asr_amd -o serve_many
 //   ./serve_many model.april audio.raw [sessions=64] [mode=pipelined|lockstep] [input_rate] [--alternatives K] [--bias FILE [--bias-strict]]
+//               [--endpoint-ms N] [--blank-penalty X]
 //
 // Every session gets the same PCM16 file, rotated by (session index x 0.37 s) so that the streams differ.  With `input_rate` the file
 // is PCM16 at that rate and every session is told so (aprilx_session_set_input_rate): the library converts it to the model's rate on
@@ -16,6 +17,8 @@
 // (aprilx_bias_create / aprilx_session_set_bias, one set shared by all sessions); `--bias-sessions N` gives the set to the first N
 // sessions only (the others are unbiased neighbours on an engine that has opted in).  `--bias-strict` builds the set as a closed
 // phrase list (APRILX_BIAS_STRICT): the sessions that have it emit only sequences of the file's phrases.
+// `--endpoint-ms N` / `--blank-penalty X` (anywhere on the line): every session gets search options (aprilx_session_set_search_options):
+// an utterance ends N ms after its last token instead of 2200, X is subtracted from the blank logit in the decision.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -48,6 +51,22 @@ int main(int argc, char **argv)
     const char *bias_file = nullptr;
     int bias_sessions = -1;
     bool bias_strict = false;
+    long endpoint_ms = -1;
+    const char *blank_penalty = nullptr;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!strcmp(argv[i], "--endpoint-ms")) {
+            endpoint_ms = atol(argv[i + 1]);
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!strcmp(argv[i], "--blank-penalty")) {
+            blank_penalty = argv[i + 1];
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
     for (int i = 1; i < argc; ++i)
         if (!strcmp(argv[i], "--bias-strict")) {
             bias_strict = true;
@@ -129,6 +148,12 @@ int main(int argc, char **argv)
         if (argc > 5 && aprilx_session_set_input_rate(sessions[(size_t)i], (uint32_t)rate) != 0) { fprintf(stderr, "input rate %zu refused\n", rate); return 1; }
         if (alternatives && aprilx_session_set_confidence(sessions[(size_t)i], alternatives) != 0) { fprintf(stderr, "%d alternatives refused\n", alternatives); return 1; }
         if (bias && (bias_sessions < 0 || i < bias_sessions) && aprilx_session_set_bias(sessions[(size_t)i], bias) != 0) { fprintf(stderr, "bias set refused by session %d\n", i); return 1; }
+        if (endpoint_ms >= 0 || blank_penalty) {
+            AprilxSearchOptions so;
+            so.size = (uint32_t)sizeof so; so.endpoint_silence_ms = endpoint_ms >= 0 ? (uint32_t)endpoint_ms : 2200u; so.max_utterance_ms = 0;
+            so.blank_penalty = blank_penalty ? strtof(blank_penalty, nullptr) : 0.0f;
+            if (aprilx_session_set_search_options(sessions[(size_t)i], &so) != 0) { fprintf(stderr, "search options refused\n"); return 1; }
+        }
         const size_t rot = ((size_t)i * (size_t)(0.37 * rate)) % pcm.size();
         audio[(size_t)i].assign(pcm.begin() + (long)rot, pcm.end());
         audio[(size_t)i].insert(audio[(size_t)i].end(), pcm.begin(), pcm.begin() + (long)rot);
@@ -153,6 +178,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "%d alternatives: %.3f ms per 100 ms step, mean confidence of %zu final tokens %.3f\n", alternatives, ms / (double)steps, cnt, cnt ? sum / (double)cnt : 0.0);
     }
     if (bias) fprintf(stderr, "phrase boosting: %.3f ms per 100 ms step\n", ms / (double)steps);
+    if (endpoint_ms >= 0 || blank_penalty) fprintf(stderr, "search options: %.3f ms per 100 ms step\n", ms / (double)steps);
     if (argc > 5) fprintf(stderr, "input at %zu Hz: %.3f ms per 100 ms step\n", rate, ms / (double)steps);
     for (AprilASRSession s : sessions) aas_free(s);
     if (bias) aprilx_bias_free(bias);

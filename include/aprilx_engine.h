@@ -218,6 +218,33 @@ APRIL_EXPORT int aprilx_run_decide_biased(AprilASRModel model, int n, int op, co
 APRIL_EXPORT int aprilx_run_confidence_biased(AprilASRModel model, int n, const float *logits, int k, AprilxBias bias, const int32_t *bias_state,
                                               AprilxTokenInfo *out);
 
+/* ---- search options: endpointing and blank penalty -----------------------------------------
+ * The reference ends an utterance (FINAL, then SILENCE) 2200 ms after the last token (src/april_session.c:411) and compares the raw
+ * blank logit.  A session can have its own values (DESIGN.md section 14 has the contract); they act where the decision is taken, on
+ * the GPU, and the host replays the same lines.  With all three at their defaults a session behaves bit for bit as one without options.
+ *   endpoint_silence_ms  200 .. 60000, default 2200: the silence after the last token that ends the utterance
+ *   max_utterance_ms     0 (off, default) or 1000 .. 600000: a word that begins this long after the utterance's first token finalises
+ *                        what came before it (FINAL only: no SILENCE, the context is kept)
+ *   blank_penalty        finite, |p| <= 100, default 0: subtracted from the blank logit in the decision's comparisons (positive: fewer
+ *                        deletions, more insertions).  AprilToken.logprob, confidences and traced logits keep the raw values. */
+typedef struct AprilxSearchOptions {
+    uint32_t size;                  /* sizeof(AprilxSearchOptions) as the caller was built; checked */
+    uint32_t endpoint_silence_ms;
+    uint32_t max_utterance_ms;
+    float blank_penalty;
+} AprilxSearchOptions;
+/* Extends aas_create_session: NULL = back to no options (the defaults).  The options persist across aas_flush.  0 on success; -1, and
+ * nothing changes, on a wrong size, a value out of range, or when the session has audio queued or fed since its creation / last
+ * completed aas_flush (the rule of aprilx_session_set_input_rate). */
+APRIL_EXPORT int aprilx_session_set_search_options(AprilASRSession session, const AprilxSearchOptions *options);
+/* The session's options (the defaults when it has none).  Returns 1 when the session has options, 0 when not, -1 on bad arguments.  Only
+ * reads: it never waits for queued audio and may be called from the session's own handler. */
+APRIL_EXPORT int aprilx_session_search_options(AprilASRSession session, AprilxSearchOptions *out);
+/* Tests only, beside aprilx_run_decide_biased: row i decides with opts[i]; opts[i].size == 0 = a row without options.  bias may be NULL
+ * (then bias_state_io is ignored).  max_utterance_ms is the host's alone and is ignored here. */
+APRIL_EXPORT int aprilx_run_decide_opts(AprilASRModel model, int n, int op, const float *logits, float early_emit, const int32_t *now_ms, int round,
+                                        int32_t *state_io, void *records_out, AprilxBias bias, int32_t *bias_state_io, const AprilxSearchOptions *opts);
+
 /* ---- tracing / statistics ---------------------------------------------------------------*/
 /* every joiner evaluation of this session appends `vocab` floats to buf (tests only; chunk steps of a traced session are
    issued eagerly and waited for one by one) */
@@ -284,6 +311,8 @@ APRIL_EXPORT void aprilx_greedy_free(AprilxGreedy g);
 /* the state machine's own copy of the phrase-boosting state: attach a set (NULL = off; the state returns to the root), read the state */
 APRIL_EXPORT int aprilx_greedy_set_bias(AprilxGreedy g, AprilxBias bias);
 APRIL_EXPORT int aprilx_greedy_bias_state(AprilxGreedy g);
+/* the state machine with search options (NULL = none); -1 on a wrong size or a value out of range */
+APRIL_EXPORT int aprilx_greedy_set_search_options(AprilxGreedy g, const AprilxSearchOptions *options);
 
 /* A result handler implemented in C, for load generators and benchmarks (a Python or JNI callback costs more than
    the GPU step at thousands of sessions).  userdata -> uint64_t[6]: calls, partial, final, cant_keep_up, silence, tokens */
