@@ -306,6 +306,13 @@ class Model:
         self._L.aprilx_model_stats(self._handle, device_index, C.byref(s))
         return s
 
+    def ramp_stats(self, device_index: int = 0):
+        """(ramp_hosted, ramp_eligible): feeds whose first macro steps ran inside the previous feed's last ones, and split feeds that could have been"""
+        h, e = C.c_uint64(0), C.c_uint64(0)
+        if self._L.aprilx_model_ramp_stats(self._handle, device_index, C.byref(h), C.byref(e)) != 0:
+            raise ValueError("aprilx_model_ramp_stats refused the call")
+        return int(h.value), int(e.value)
+
     def feed_latencies(self, device_index: int = 0, reset: bool = False) -> np.ndarray:
         """hand-over -> delivery latency (ms) of the last completed ticks of one GPU's stepping thread, oldest first"""
         n = int(self._L.aprilx_model_feed_latency(self._handle, device_index, None, 0, 0))

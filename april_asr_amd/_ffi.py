@@ -79,6 +79,7 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_run_decide_biased", "aprilx_greedy_set_bias", "aprilx_greedy_bias_state",
     "aprilx_bias_create_ex", "aprilx_bias_flags", "aprilx_run_confidence_biased",
     "aprilx_session_set_search_options", "aprilx_session_search_options", "aprilx_run_decide_opts", "aprilx_greedy_set_search_options",
+    "aprilx_ramp_window", "aprilx_model_ramp_stats",
 ]
 
 _lib = None
@@ -127,6 +128,8 @@ def lib():
     L.aprilx_run_joiner.argtypes = [vp, C.c_int, vp, vp, vp]; L.aprilx_run_joiner.restype = C.c_int
     L.aprilx_run_fbank.argtypes = [vp, C.c_int, vp, vp]; L.aprilx_run_fbank.restype = C.c_int
     L.aprilx_plan_gemm.argtypes = [C.c_int] * 6 + [vp]; L.aprilx_plan_gemm.restype = C.c_int
+    L.aprilx_ramp_window.argtypes = [C.c_int] * 3 + [vp, C.c_int]; L.aprilx_ramp_window.restype = C.c_int
+    L.aprilx_model_ramp_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]; L.aprilx_model_ramp_stats.restype = C.c_int
     L.aprilx_stream_form.argtypes = [C.c_int] * 6; L.aprilx_stream_form.restype = C.c_int
     L.aprilx_run_decide.argtypes = [vp, C.c_int, C.c_int, vp, C.c_float, vp, C.c_int, vp, vp]; L.aprilx_run_decide.restype = C.c_int
     L.aprilx_session_trace_logits.argtypes = [vp, vp, sz, C.POINTER(sz)]; L.aprilx_session_trace_logits.restype = None

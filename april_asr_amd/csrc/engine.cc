@@ -223,8 +223,9 @@ Engine::Engine(const EngineConfig &cfg, const PackedLayout &layout, const float 
         if (f16_tile_) {
             kzx_hr_ = pick_kz(d.hidden, d.d_model, 32); kzx_ff2_ = pick_kz(d.ffn, d.d_model, 32);
             for (int p = 0; p < 2; ++p) y16_buf_[p] = dmalloc<uint16_t>(MB * d.d_model);
-            y16_ = y16_buf_[0]; xb16_ = dmalloc<uint16_t>(MB * d.d_model);
-            u16_ = dmalloc<uint16_t>(MB * d.hidden); ff16_ = dmalloc<uint16_t>(MB * d.ffn);
+            y16_ = y16_buf_[0];
+            for (int p = 0; p < 2; ++p) { xb16_buf_[p] = dmalloc<uint16_t>(MB * d.d_model); u16_buf_[p] = dmalloc<uint16_t>(MB * d.hidden); ff16_buf_[p] = dmalloc<uint16_t>(MB * d.ffn); }
+            xb16_ = xb16_buf_[0]; u16_ = u16_buf_[0]; ff16_ = ff16_buf_[0];
             h16_ = dmalloc<uint16_t>((size_t)d.n_layers * S * d.d_model);
             HIP_CHECK(hipMemset(h16_, 0, (size_t)d.n_layers * S * d.d_model * 2));
         }
@@ -243,9 +244,12 @@ Engine::Engine(const EngineConfig &cfg, const PackedLayout &layout, const float 
     y_ = y_buf_[0]; ssq_ = ssq_buf_[0];
     ws_fe_ = dmalloc<float>((size_t)kz_embed_ * d.d_model * MB);      // the front end's own split-K planes (embed at small batches)
     ws_sr_ = dmalloc<float>((size_t)std::max(kz_proj_ * d.joiner, d.d_model) * MB);      // encoder_proj's, when it runs on the search stream
-    xb_ = dmalloc<float>(MB * d.d_model);
-    u_ = dmalloc<float>(MB * d.hidden);
-    ff_ = dmalloc<float>(MB * d.ffn);
+    // ... and the scratch rows of a macro step (u, xb, ff): a hosting layer graph runs problems of both parities in one launch ("ramp merge")
+    for (int p = 0; p < 2; ++p) { xb_buf_[p] = dmalloc<float>(MB * d.d_model); u_buf_[p] = dmalloc<float>(MB * d.hidden); ff_buf_[p] = dmalloc<float>(MB * d.ffn); }
+    xb_ = xb_buf_[0]; u_ = u_buf_[0]; ff_ = ff_buf_[0];
+    ramp_mode_ = env_int("APRIL_RAMP_MERGE", 1);
+    if (ramp_mode_ < 0 || ramp_mode_ > 2) ramp_mode_ = 1;
+    ramp_d_ = dmalloc<RampState>(1); HIP_CHECK(hipMemset(ramp_d_, 0, sizeof(RampState)));
     de_ = dmalloc<float>(MB * d.d_model);
     HIP_CHECK(hipMemset(de_, 0, MB * d.d_model * 4));            // rows whose context did not change are read (never stored) by the decoder projection
     logits_ = dmalloc<float>(3 * MB * d.vocab);
@@ -348,6 +352,10 @@ Engine::~Engine()
     (void)hipSetDevice(cfg_.device);
     (void)hipStreamSynchronize(f_stream_); (void)hipStreamSynchronize(stream_); (void)hipStreamSynchronize(s_stream_);
     dump_stream_trace();
+    if (ramp_d_ && ramp_eligible_.load() > 0) {
+        unsigned h = 0;
+        if (hipMemcpy(&h, &ramp_d_->hosted, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) LOGI("engine: ramp merge: %u of %llu hostable split feeds were hosted by their predecessor", h, (unsigned long long)ramp_eligible_.load());
+    }
     for (StreamTrace &t : trace_) for (hipEvent_t e : t.ev) if (e) (void)hipEventDestroy(e);
     if (trace_base_) (void)hipEventDestroy(trace_base_);
     for (hipEvent_t e : join_ev_) (void)hipEventDestroy(e);
@@ -372,12 +380,13 @@ Engine::~Engine()
     if (dec_table_) (void)hipFree(dec_table_);
     if (p_lm_) (void)hipFree(p_lm_);
     for (int p = 0; p < 2; ++p)
-        for (void *q : {(void *)eout_lm_buf_[p], (void *)y16_buf_[p], (void *)y_buf_[p], (void *)ssq_buf_[p], (void *)rec_off_buf_[p], (void *)flags_buf_[p], (void *)step_buf_[p]}) if (q) (void)hipFree(q);
+        for (void *q : {(void *)eout_lm_buf_[p], (void *)y16_buf_[p], (void *)y_buf_[p], (void *)ssq_buf_[p], (void *)xb_buf_[p], (void *)u_buf_[p], (void *)ff_buf_[p],
+                        (void *)xb16_buf_[p], (void *)u16_buf_[p], (void *)ff16_buf_[p], (void *)rec_off_buf_[p], (void *)flags_buf_[p], (void *)step_buf_[p]}) if (q) (void)hipFree(q);
     if (ws_fe_) (void)hipFree(ws_fe_);
     if (ws_sr_) (void)hipFree(ws_sr_);
-    for (void *p : {(void *)wx_, (void *)xb16_, (void *)u16_, (void *)ff16_, (void *)h16_}) if (p) (void)hipFree(p);      // fp16 tile path
+    for (void *p : {(void *)wx_, (void *)h16_, (void *)ramp_d_}) if (p) (void)hipFree(p);      // (fp16 tile path; ramp merge)
     for (void *p : {(void *)w_, (void *)wh_, (void *)h_, (void *)c_, (void *)ring_, (void *)eout_, (void *)dout_, (void *)gstate_, (void *)cls_, (void *)ws_, (void *)xin_,
-                    (void *)a3_, (void *)xb_, (void *)u_, (void *)ff_, (void *)de_, (void *)logits_, (void *)rec_d_, (void *)counter_d_,
+                    (void *)a3_, (void *)de_, (void *)logits_, (void *)rec_d_, (void *)counter_d_,
                     (void *)active_d_, (void *)dirty_d_, (void *)dec_slots_d_,
                     (void *)ds_desc_[0], (void *)ds_desc_[1], (void *)ds_pcm_[0], (void *)ds_pcm_[1]})
         if (p) (void)hipFree(p);
@@ -431,6 +440,7 @@ void Engine::zero_pending_slots()
     // Teardown-tolerant: sessions may be freed while the process is exiting and the HIP runtime is already gone.
     if (hipSetDevice(cfg_.device) == hipSuccess) {
         std::lock_guard<std::mutex> cg(capture_mu_);           // never enqueue into a stream that is being captured (step())
+        m_touched();
         const NetDims &d = L_.dims;
         for (size_t o = 0; o < zero_pending_.size(); o += 64) {
             ZeroSlotArgs z;
@@ -471,6 +481,7 @@ void Engine::sync_streams()
 // fbank and set one; it uses sync_streams(), a stale "unseen" only costs a redundant event.
 void Engine::sync()
 {
+    m_touched();
     sync_streams();
     f_unseen_by_m_ = s_unseen_by_m_ = m_unseen_by_f_ = m_unseen_by_s_ = false;
     if (profiling_) collect_timing();
@@ -517,6 +528,7 @@ template <typename Chain> hipGraphExec_t Engine::cached_graph(GraphCache &cache,
 template <typename Capture> void Engine::capture_both_parities(Capture &&capture)
 {
     const int par = flight_parity_;
+    m_touched();
     for (int q : {1 - par, par}) { select_parity(q); capture(); }
 }
 
@@ -577,6 +589,7 @@ void Engine::join(hipStream_t waiter, hipStream_t src)
 
 void Engine::general_prologue()
 {
+    m_touched();
     if (f_unseen_by_m_) { join(stream_, f_stream_); f_unseen_by_m_ = false; }
     if (s_unseen_by_m_) { join(stream_, s_stream_); s_unseen_by_m_ = false; }
     m_unseen_by_f_ = m_unseen_by_s_ = true;
@@ -719,6 +732,7 @@ void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<con
     a.t = ft_; a.pcm = ds_pcm_[b]; a.desc = reinterpret_cast<const FbankFrameDesc *>(reinterpret_cast<const char *>(ds_pcm_[b]) + doff); a.n_frames = n_frames; a.ring = ring_; a.ring_frames = ring_frames_; a.pad_value = pad_value_;
     if (n_rs) { ra.in = ds_pcm_[b]; ra.out = ds_pcm_[b]; ra.desc = reinterpret_cast<const ResampleDesc *>(reinterpret_cast<const char *>(ds_pcm_[b]) + roff); }
     if (profiling_) {        // (the per-class hipEvents live on M: a profiled fbank runs there, behind its upload)
+        m_touched();
         join(stream_, f_stream_);
         if (n_rs) { timed_begin(T_RESAMPLE); launch_resample(ra, stream_); timed_end(T_RESAMPLE); }
         timed_begin(T_FBANK); launch_fbank(a, stream_); timed_end(T_FBANK);
@@ -1224,34 +1238,100 @@ Engine::SwPlan &Engine::sw_plan(int m, int T)
         gclk_used_ = 0;                               // ... then every slot is free again
     }
     SwPlan &p = sw_plans_[key];
+    build_sw_chain(p, p.one, m, T, false);
+    // (clocked runs never take the split flavour: run_feed_wavefront)
+    if (ramp_mode_ != 0 && !gclk_) build_sw_chain(p, p.split, m, T, true);
+    return p;
+}
+
+// ---------------------------------------------------------------- ramp merge
+// The first and the last macro steps of a feed's wavefront hold one or two problems per launch, and a launch costs ~27 us whatever
+// it holds.  Under the pipelined ingest the next feed's front end is through long before this feed's layers reach their tail, so
+// the tail [2, 1] of feed k and the head [1, 2] of feed k + 1 run as [3, 3]: the split-flavour plan of (m, T, parity p) carries, in
+// its last RAMP_R macro steps, GUEST argument blocks for the first RAMP_R macro steps of a feed of m sessions of the other parity
+// (their rows t * m in that parity's buffers: they depend on m only).  Guest blocks run only when the word the latch kernel wrote
+// for them holds 1; the own blocks of every split plan's first RAMP_R macro steps run only while head_live[p] holds 1.  The
+// decision is the device's (kernels_misc.hip, ramp_latch_kernel); the scheduler and the flight life cycle know nothing of it.
+std::vector<RampStep> ramp_window(int L, int T, int R, int max_problems)
+{
+    std::vector<RampStep> w;
+    if (L <= 2 * R || T < 1 || R < 1) return w;
+    for (int j = 1; j <= R; ++j) {
+        RampStep s; s.macro = L + T - 1 - R + j;
+        for (int l = 0; l < L; ++l) { const int t = s.macro - 1 - l; if (t >= 0 && t < T) ++s.own; }
+        for (int t = 0; t < j; ++t) s.guests.push_back(std::make_pair(j - 1 - t, t));
+        if (s.own + (int)s.guests.size() > max_problems) return std::vector<RampStep>();
+        w.push_back(s);
+    }
+    return w;
+}
+
+void Engine::ramp_counts(uint64_t *hosted, uint64_t *eligible)
+{
+    unsigned h = 0;
+    {
+        HipLegacyLock legacy;                         // (a legacy-stream copy: not while an engine captures a graph, see engine.h)
+        if (hipSetDevice(cfg_.device) == hipSuccess) HIP_CHECK(hipMemcpy(&h, &ramp_d_->hosted, sizeof h, hipMemcpyDeviceToHost));
+    }
+    *hosted = h; *eligible = ramp_eligible_.load(std::memory_order_relaxed);
+}
+
+void Engine::build_sw_chain(SwPlan &p, SwPlan::Chain &c, int m, int T, bool ramp)
+{
     const NetDims &d = L_.dims;
     const int L = d.n_layers;
+    const int par = flight_parity_;
+    const int tk = f16_tile_ ? 2 : tile_ok();
+    // does a launch of n problems of this kind need a row finisher? (projection and FFN down on the GM_TILE schedule, see below)
+    auto needs_rows = [&](int kind, int n) {
+        const int kz = kind == 1 ? kz_hr() : kz_ff2();
+        return (kind == 1 || kind == 3) && tk && (tk == 2 || gemm_tile_planned(m, d.d_model, kz, n)) && !gemm_fullk(m, d.d_model, kz, false, n, tk);
+    };
+    // hosting: own + guest problems fit the three-problem forms in both window steps and no launch of the window needs a row finisher
+    std::vector<RampStep> window;
+    if (ramp && m <= RAMP_MAX_M && T <= RAMP_MAX_T) {
+        window = ramp_window(L, T, RAMP_R);
+        for (const RampStep &s : window) if (needs_rows(1, s.own + (int)s.guests.size()) || needs_rows(3, s.own + (int)s.guests.size())) { window.clear(); break; }
+    }
+    if (ramp) p.hosts = !window.empty();
     std::vector<GemmArgs> items;
     std::vector<RowArgs> rows;
     for (int W = 0; W <= T + L; ++W) {
+        const RampStep *host = nullptr; int wj = 0;
+        for (size_t j = 0; j < window.size(); ++j) if (window[j].macro == W) { host = &window[j]; wj = (int)j; }
+        if (host && wj == 0) { SwPlan::Batch b; b.off = c.host.size(); b.n = 0; b.macro = W; b.kind = 4; b.roff = c.rhost.size(); b.rn = 0; c.batches.push_back(b); }      // the latch
         for (int kind = 0; kind < 4; ++kind) {
             items.clear(); rows.clear();
             int n_act = 0;
             for (int l = 0; l < L; ++l) { const int t = W - 1 - l; if (t >= 0 && t < T) ++n_act; }
             if (n_act == 0) continue;
+            if (host) n_act += (int)host->guests.size();      // (planned and staged for own + guest problems)
             // The N = d_model GEMMs (projection, FFN down) on the GM_TILE schedule: when the n_act problems of this launch give the
             // chip too few 64 x 64 tiles, K is cut across workgroups and ONE z-batched row launch finishes the slab tree with the
             // epilogue (state write + residual / bias + residual + sums of squares) -- the same arithmetic as the fused form.
             const int kz = kind == 1 ? kz_hr() : kz_ff2();
-            const int tk = f16_tile_ ? 2 : tile_ok();
-            const bool split = (kind == 1 || kind == 3) && tk && (tk == 2 || gemm_tile_planned(m, d.d_model, kz, n_act)) && !gemm_fullk(m, d.d_model, kz, false, n_act, tk);
-            for (int l = 0; l < L; ++l) {
-                const int t = W - 1 - l;
-                if (t < 0 || t >= T) continue;
+            const bool split = needs_rows(kind, n_act);
+            auto problem = [&](int l, int t, const int *run_flag) {
                 const size_t r0 = (size_t)t * m;
                 GemmArgs g = kind == 0 ? args_gates(l, r0, m, GATES_ALL) : kind == 1 ? args_whr(l, r0, m) : kind == 2 ? args_ff1(l, r0, m) : args_ff2(l, r0, m);
                 if (kind == 0 && cfg_.precision == 0) g.tile_ok = gates_tile_rows((long)m * n_act) ? 2 : 0;
+                if (run_flag) { g.run_flag = run_flag; g.run_gen = 1; }
                 if (split) {
                     float *ws = ws_ + r0 * d.d_model;
                     rows.push_back(row_form(g, ws, ws_mstride_, gemm_partials(m, d.d_model, kz, n_act, tk)));
                     g = partial_form(g, ws, ws_mstride_);
                 } else if (tk == 2) g.force_fullk = 0;
                 items.push_back(g);
+            };
+            for (int l = 0; l < L; ++l) {
+                const int t = W - 1 - l;
+                if (t < 0 || t >= T) continue;
+                problem(l, t, ramp && W <= RAMP_R ? &ramp_d_->head_live[par] : nullptr);
+            }
+            if (host) {
+                select_parity(1 - par);
+                for (const auto &lt : host->guests) problem(lt.first, lt.second, &ramp_d_->guest_live[par][wj][lt.second]);
+                select_parity(par);
             }
             // The gates launch of four and more problems (merged flights: two feeds stepped as one wavefront of up to seven chunk steps) goes
             // out as launches of two or three: the hand-scheduled 64 x 64 kernel holds 512 workgroups at a time, two problems are exactly one
@@ -1268,37 +1348,37 @@ Engine::SwPlan &Engine::sw_plan(int m, int T)
             size_t first = 0;
             for (size_t gi = 0; gi < groups.size(); ++gi) {
                 const int gn = groups[gi];
-                if (kind == 0 && gclk_ && gclk_slots_ && gclk_used_ < GCLK_SLOTS) {      // one slot per gates LAUNCH: all its problems point at it
+                if (kind == 0 && !ramp && gclk_ && gclk_slots_ && gclk_used_ < GCLK_SLOTS) {      // one slot per gates LAUNCH: all its problems point at it
                     p.stamp_slots.push_back(std::make_pair(gclk_used_, (long)m * gn)); p.stamp_n.push_back(gn);
                     for (int i = 0; i < gn; ++i) items[first + (size_t)i].stamp = gclk_slots_ + (size_t)gclk_used_ * STAMP_WORDS;
                     ++gclk_used_;
-                } else if (kind == 0 && gclk_ && gclk_slots_ && !gclk_warned_) {
+                } else if (kind == 0 && !ramp && gclk_ && gclk_slots_ && !gclk_warned_) {
                     gclk_warned_ = true; LOGW("engine: the gates clock is out of stamp slots (%d): the gates launches of further plans are not timed", GCLK_SLOTS);
                 }
-                SwPlan::Batch b; b.off = p.host.size(); b.n = gn; b.macro = W; b.kind = kind; b.roff = p.rhost.size(); b.rn = gi == 0 ? (int)rows.size() : 0;
-                p.host.resize(p.host.size() + (size_t)gn);
-                stage_gemm_z(items.data() + first, gn, p.host.data() + b.off);
-                if (gi == 0) p.rhost.insert(p.rhost.end(), rows.begin(), rows.end());
-                p.batches.push_back(b);
+                SwPlan::Batch b; b.off = c.host.size(); b.n = gn; b.macro = W; b.kind = kind; b.roff = c.rhost.size(); b.rn = gi == 0 ? (int)rows.size() : 0;
+                c.host.resize(c.host.size() + (size_t)gn);
+                stage_gemm_z(items.data() + first, gn, c.host.data() + b.off);
+                if (gi == 0) c.rhost.insert(c.rhost.end(), rows.begin(), rows.end());
+                c.batches.push_back(b);
                 first += (size_t)gn;
             }
         }
     }
-    p.dev = dmalloc<GemmArgs>(p.host.size());
+    m_touched();
+    c.dev = dmalloc<GemmArgs>(c.host.size());
     // (stream-ordered on the engine's own stream: a blocking hipMemcpy goes through the legacy stream, which HIP refuses while
     // ANOTHER engine's stepping thread is capturing a graph -- two engines on one device, several models in one process)
-    HIP_CHECK(hipMemcpyAsync(p.dev, p.host.data(), p.host.size() * sizeof(GemmArgs), hipMemcpyHostToDevice, stream_));
-    if (!p.rhost.empty()) {
-        p.rdev = dmalloc<RowArgs>(p.rhost.size());
-        HIP_CHECK(hipMemcpyAsync(p.rdev, p.rhost.data(), p.rhost.size() * sizeof(RowArgs), hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(c.dev, c.host.data(), c.host.size() * sizeof(GemmArgs), hipMemcpyHostToDevice, stream_));
+    if (!c.rhost.empty()) {
+        c.rdev = dmalloc<RowArgs>(c.rhost.size());
+        HIP_CHECK(hipMemcpyAsync(c.rdev, c.rhost.data(), c.rhost.size() * sizeof(RowArgs), hipMemcpyHostToDevice, stream_));
     }
-    return p;
 }
 
 void Engine::free_sw_plans()
 {
     if (!sw_plans_.empty()) LOGI("engine: feed wavefront plans emptied (%zu plans)", sw_plans_.size());
-    for (auto &p : sw_plans_) { if (p.second.dev) (void)hipFree(p.second.dev); if (p.second.rdev) (void)hipFree(p.second.rdev); }
+    for (auto &p : sw_plans_) for (SwPlan::Chain *c : {&p.second.one, &p.second.split}) { if (c->dev) (void)hipFree(c->dev); if (c->rdev) (void)hipFree(c->rdev); }
     sw_graphs_.clear(); sw_plans_.clear();
 }
 
@@ -1316,10 +1396,12 @@ void Engine::run_sw_chain(int m, int T, bool dump_logits, const SwPlan &p, int p
     }
     if (part < 0 || part == 1) {
         static const int cls_of[4] = {T_GATES, T_GEMM_OTHER, T_GEMM_OTHER, T_GEMM_OTHER};
-        for (size_t bi = 0; bi < p.batches.size(); ++bi) {      // macro steps in order; inside one: gates, projection, FFN up, FFN down of the active layers
-            const SwPlan::Batch &b = p.batches[bi];
-            timed_begin(cls_of[b.kind]); launch_gemm_z(p.host.data() + b.off, b.n, p.dev + b.off, st); timed_end(cls_of[b.kind]);
-            if (b.rn > 0) { timed_begin(T_ROW); launch_row_z(p.rhost.data() + b.roff, b.rn, p.rdev + b.roff, st); timed_end(T_ROW); }
+        const SwPlan::Chain &c = p.layers(part == 1);           // (a split feed's layer graph: the ramp-merge flavour, when it is on)
+        for (size_t bi = 0; bi < c.batches.size(); ++bi) {      // macro steps in order; inside one: gates, projection, FFN up, FFN down of the active layers
+            const SwPlan::Batch &b = c.batches[bi];
+            if (b.kind == 4) { launch_ramp_latch(ramp_d_, flight_parity_, m, st); continue; }
+            timed_begin(cls_of[b.kind]); launch_gemm_z(c.host.data() + b.off, b.n, c.dev + b.off, st); timed_end(cls_of[b.kind]);
+            if (b.rn > 0) { timed_begin(T_ROW); launch_row_z(c.rhost.data() + b.roff, b.rn, c.rdev + b.roff, st); timed_end(T_ROW); }
         }
         if (part < 0) lm_stage_proj(m, 0, T, st, ws_);
     }
@@ -1397,8 +1479,17 @@ void Engine::launch_split_feed(int m, int T, hipStream_t fe)
         if (tr) HIP_CHECK(hipEventRecord(tr->ev[2 * i + 1], st));
     };
     part(0, fe);
+    if (ramp_mode_ != 0) {
+        // the feed's front end is through: arm its head and tell the previous feed's latch.  hostable: that feed's layer graph is still the last thing M was
+        // given (m_quiet_, engine.h), and the front end ran beside it on F.  Read before this feed's own enqueues on M.
+        const bool hostable = ramp_mode_ == 1 && fe == f_stream_ && m_quiet_.load(std::memory_order_acquire);
+        if (hostable) ramp_eligible_.fetch_add(1, std::memory_order_relaxed);
+        launch_ramp_ready(ramp_d_, flight_parity_, m, T, hostable ? 1 : 0, fe);
+    }
     if (fe == f_stream_) { join(stream_, f_stream_); f_unseen_by_m_ = false; }
-    part(1, stream_); join(s_stream_, stream_); part(2, s_stream_);
+    part(1, stream_);
+    if (ramp_mode_ != 0) m_quiet_.store(true, std::memory_order_release);
+    join(s_stream_, stream_); part(2, s_stream_);
     if (tr) { tr->m = m; tr->T = T; tr->used = true; }
     s_unseen_by_m_ = true; flight_tail_s_ = true;
     if (fe != f_stream_) m_unseen_by_f_ = true;          // (front-end kernels on M read ring rows: the next fbank waits for them)
@@ -1468,6 +1559,7 @@ void Engine::apply_confidence_pending()
     // whole table, stream-ordered ahead of this flight's steps.  Slots of other sessions keep their values (a flight still in
     // the air reads the same bytes before and after); the slots that change belong to idle sessions.
     std::lock_guard<std::mutex> cg(capture_mu_);
+    m_touched();
     HIP_CHECK(hipMemcpyAsync(conf_k_d_, conf_k_h_, (size_t)cfg_.max_slots, hipMemcpyHostToDevice, stream_));
 }
 
@@ -1507,6 +1599,7 @@ void Engine::apply_bias_pending()
     todo.swap(bias_pending_);
     bias_has_pending_.store(false, std::memory_order_release);
     std::lock_guard<std::mutex> cg(capture_mu_);
+    m_touched();
     if (!bias_set_h_) {
         bool any = false;
         for (const auto &t : todo) any = any || t.second >= 0;
@@ -1569,6 +1662,7 @@ void Engine::apply_search_options_pending()
     for (const auto &t : todo) if (t.first >= 0 && t.first < cfg_.max_slots) opt_h_[t.first] = t.second;
     // whole table, stream-ordered ahead of this flight's steps; entries of other sessions keep their values
     std::lock_guard<std::mutex> cg(capture_mu_);
+    m_touched();
     HIP_CHECK(hipMemcpyAsync(opt_d_, opt_h_, (size_t)cfg_.max_slots * sizeof(SearchOpt), hipMemcpyHostToDevice, stream_));
 }
 
@@ -1602,6 +1696,7 @@ void Engine::note_conf_step(int k, const int *slots, int m, size_t records)
 void Engine::select_parity(int p)
 {
     flight_parity_ = p;
+    xb_ = xb_buf_[p]; u_ = u_buf_[p]; ff_ = ff_buf_[p]; xb16_ = xb16_buf_[p]; u16_ = u16_buf_[p]; ff16_ = ff16_buf_[p];
     y_ = y_buf_[p]; ssq_ = ssq_buf_[p]; y16_ = y16_buf_[p]; step_d_ = step_buf_[p]; flags_d_ = flags_buf_[p]; rec_off_d_ = rec_off_buf_[p]; eout_lm_ = eout_lm_buf_[p];
 }
 

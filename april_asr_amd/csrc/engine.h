@@ -89,6 +89,13 @@ struct GraphCache {
     std::map<Key, hipGraphExec_t> map_; std::map<std::pair<int, int>, int> uses_;
 };
 
+// Ramp merge, the pure part: which problems of the NEXT feed's first R macro steps the last R macro steps of a feed of T chunks over
+// L layers can hold.  Window step j (1..R) is own macro step L + T - 1 - R + j and takes the guests of the next feed's step j:
+// (layer j - 1 - t, chunk t), t < j.  Empty when the window would reach into the feed's own head or a guest would meet a layer
+// before the feed's last chunk has left it (L <= 2 R), or when own + guest problems exceed `max_problems` in some step.
+struct RampStep { int macro = 0, own = 0; std::vector<std::pair<int, int>> guests; };      // guests: (layer, chunk)
+std::vector<RampStep> ramp_window(int L, int T, int R, int max_problems = 3);
+
 class Engine {
 public:
     Engine(const EngineConfig &cfg, const PackedLayout &layout, const float *blob_host, const float *blob_device,
@@ -258,6 +265,9 @@ public:
     // (one problem: gemm_f32_kernel, two: gemm_f32_zkernel, three at 256 sessions: gemm_f32_zkernel_walk) map onto it one to one
     void gates_clock_by_n(double *ms4, long *launches4) const { for (int i = 0; i < 4; ++i) { ms4[i] = gclk_ms_n_[i]; launches4[i] = gclk_launches_n_[i]; } }
     KernelTiming timing(int cls) const { return timing_[cls]; }
+    // ramp merge: feeds whose head a predecessor's layer graph ran (the device's count, read back: exact once the streams are idle) and
+    // split feeds launched as hostable (any thread)
+    void ramp_counts(uint64_t *hosted, uint64_t *eligible);
     void reset_timing();
     enum { T_GATES = 0, T_GEMM_OTHER = 1, T_ROW = 2, T_CONV = 3, T_FBANK = 4, T_DEC = 5, T_RESAMPLE = 6, T_COUNT = 7 };
     long kernels_per_step() const { return kernels_per_step_.load(std::memory_order_relaxed); }    // launches of the last eagerly issued chunk chain
@@ -292,15 +302,19 @@ private:
     void run_lm_chain(int m, int T, bool dump_logits);
     void run_lm_wavefront(int m, int T, bool dump_logits);
     struct SwPlan {                          // argument blocks + launch list of run_sw_chain for one (m, T, parity); its captured graphs live in sw_graphs_
-        struct Batch { size_t off; int n, macro, kind; size_t roff; int rn; };      // rn > 0: the GEMMs write partial planes, rn row problems finish them
-        std::vector<GemmArgs> host; GemmArgs *dev = nullptr; std::vector<Batch> batches;
-        std::vector<RowArgs> rhost; RowArgs *rdev = nullptr;
+        struct Batch { size_t off; int n, macro, kind; size_t roff; int rn; };      // rn > 0: the GEMMs write partial planes, rn row problems finish them; kind 4: the ramp latch
+        struct Chain { std::vector<GemmArgs> host; GemmArgs *dev = nullptr; std::vector<Batch> batches; std::vector<RowArgs> rhost; RowArgs *rdev = nullptr; };
+        Chain one;                           // the one-stream graph and the eager path
+        Chain split;                         // the layer graph of a split feed while the ramp merge is on (else empty: `one` serves it); head steps behind head_live
+        bool hosts = false;                  // `split` carries guest blocks and the latch in its last RAMP_R macro steps
+        const Chain &layers(bool split_feed) const { return split_feed && !split.batches.empty() ? split : one; }
         std::vector<std::pair<int, long>> stamp_slots; std::vector<int> stamp_n;  // gates clock: (slot, rows) and problem count of every gates launch of a plan built while it was on
     };
     // keys of the current flight parity (it selects buffers); plans built under the gates clock carry stamp slots: -m; part 0: the one-stream graph, 1..3: a split feed's
     GraphCache::Key graph_key(int m, int T = 0, int part = 0) const { return {m, T, flight_parity_ * 4 + part}; }
     GraphCache::Key sw_key(int m, int T, int part = 0) const { return graph_key(gclk_ ? -m : m, T, part); }
     SwPlan &sw_plan(int m, int T);
+    void build_sw_chain(SwPlan &p, SwPlan::Chain &c, int m, int T, bool ramp);
     void free_sw_plans();                    // every plan's device blocks and graphs (streams drained, legacy lock held)
     void run_sw_chain(int m, int T, bool dump_logits, const SwPlan &p, int part, hipStream_t st);
     int stage_step(int m, int T, const int *slots, const int *ring_tails, const int *now_ms); void read_back_logits(int k, int rows, float *out);
@@ -396,6 +410,18 @@ private:
     bool f_unseen_by_m_ = false, s_unseen_by_m_ = false, m_unseen_by_f_ = false, m_unseen_by_s_ = false, flight_tail_s_ = false;
     bool overlap_hint_ = false;
     int split_streams_ = 2;                    // APRIL_SPLIT_STREAMS: 0 = one stream, 1 = search on S, 2 = search on S + front end on F
+    // ramp merge (engine.cc "ramp merge"): APRIL_RAMP_MERGE 0 = off, 1 = on, 2 = hosting plans and both kernels but never hostable
+    int ramp_mode_ = 1;
+    RampState *ramp_d_ = nullptr;            // the device words (kernels.h)
+    // INVARIANT: m_quiet_ is true exactly while the layer graph of a split feed is the LAST thing enqueued on stream_ (M).  launch_split_feed sets it
+    // behind that graph; every other enqueue on M -- general_prologue() and the direct users: slot zeroing, plan / option / bias / confidence uploads, a
+    // profiled fbank, the debug entry points through sync() -- clears it BEFORE it enqueues.  Only then may the previous feed's window run this
+    // feed's head: the guest problems overtake nothing that M was given in between.  (atomic: aas_free resets slots from client threads)
+    std::atomic<bool> m_quiet_{false};
+    void m_touched() { m_quiet_.store(false, std::memory_order_release); }
+    std::atomic<uint64_t> ramp_eligible_{0};
+    float *xb_buf_[2] = {nullptr, nullptr}, *u_buf_[2] = {nullptr, nullptr}, *ff_buf_[2] = {nullptr, nullptr};      // per parity since guests of the other parity share a launch
+    uint16_t *xb16_buf_[2] = {nullptr, nullptr}, *u16_buf_[2] = {nullptr, nullptr}, *ff16_buf_[2] = {nullptr, nullptr};
     float *y_buf_[2] = {nullptr, nullptr}, *ssq_buf_[2] = {nullptr, nullptr}, *eout_lm_buf_[2] = {nullptr, nullptr}, *ws_fe_ = nullptr, *ws_sr_ = nullptr;
     uint16_t *y16_buf_[2] = {nullptr, nullptr};
     int *step_buf_[2] = {nullptr, nullptr}, *flags_buf_[2] = {nullptr, nullptr}, *rec_off_buf_[2] = {nullptr, nullptr};

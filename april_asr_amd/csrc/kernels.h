@@ -207,6 +207,24 @@ void launch_row(const RowArgs &r, hipStream_t s);
 // n row problems of one mode and shape (same M, N, parts) in one launch: blockIdx.y picks the argument block (device array)
 void launch_row_z(const RowArgs *host_args, int n, const RowArgs *dev_args, hipStream_t s);
 
+// ---------------------------------------------------------------- ramp merge (engine.cc "ramp merge")
+// The device words through which the layer graph of split feed k decides, once, whether its last RAMP_R macro steps also run the
+// first RAMP_R macro steps of split feed k + 1 (the other flight parity).  One allocation per engine, zeroed at start.
+constexpr int RAMP_R = 2;
+struct RampState {
+    unsigned long long ready[2];           // per parity: ramp_record(generation, m, T, hostable) of the last split feed whose front end is through
+    int head_live[2];                      // per parity: 1 = the feed's first RAMP_R macro steps run in its own layer graph, 0 = a host ran them
+    int guest_live[2][RAMP_R][RAMP_R];     // [host parity][j - 1][t]: 1 = guest problem (layer j - 1 - t, chunk t) runs in the host's window step j
+    unsigned generation;                   // split feeds made ready so far (ramp_ready_kernel is its only writer)
+    unsigned hosted;                       // feeds whose head a predecessor ran (ramp_latch_kernel is its only writer)
+};
+// a record: generation << 32 | m << 12 | T << 4 | hostable -- ONE 8-byte word, so a reader never sees a record half written
+constexpr int RAMP_MAX_M = 0xFFFFF, RAMP_MAX_T = 0xFF;
+// on the front-end stream, behind the front end of a split feed of parity q (never captured: `hostable` is the host's word of the moment)
+void launch_ramp_ready(RampState *rs, int q, int m, int T, int hostable, hipStream_t s);
+// on the layer stream, in front of the first window step of a hosting plan of parity p and m sessions
+void launch_ramp_latch(RampState *rs, int p, int m, hipStream_t s);
+
 // ---------------------------------------------------------------- greedy search on the device
 // Per-slot search state (reference AprilASRSession_i: context tensor, last_emission_time_ms, the class of the
 // last active token; src/april_session.h:32-73).  The host keeps the token list and runs the callbacks; the

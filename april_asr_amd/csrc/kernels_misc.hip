@@ -100,6 +100,61 @@ void launch_row_z(const RowArgs *host_args, int n, const RowArgs *dev_args, hipS
     }
 }
 
+// ---------------------------------------------------------------- ramp merge: the two one-wave kernels
+// Split feed k (parity p, layers on stream M) may run the first RAMP_R macro steps of split feed k + 1 (parity 1 - p) inside its
+// own last RAMP_R macro steps.  Whether it does is decided ONCE, on the device, in M's stream order, by ramp_latch_kernel; the
+// host never waits for a successor.  The hand-off is payload -> agent release -> one 8-byte flag word, agent-scope loads on the reader.
+//
+// Why the decision is safe:
+// - ready[q] is written by ramp_ready_kernel on F BEHIND the front end of the feed it describes: whoever sees the record can
+//   rely on that front end's kernels having ended (their kernel-end release has written y / ssq / the step tables back).  The
+//   hosted launches start after the latch kernel has ended: their kernel-start acquire comes after that release.  No event
+//   between F and M is involved, and none is needed.
+// - A stale record never matches: generations only grow, and the latch asks for exactly its own generation + 1.
+// - head_live[q] is set to 1 by every feed's own ready kernel, which M joins before that feed's layer graph starts; only a latch
+//   that has SEEN that very record (so: after the 1 was stored) sets it back to 0.  Both are write-through agent-scope stores.
+// - A latch that runs before the record appears does not host: the guest words are 0 and the successor's head runs in its own
+//   graph, as without the merge.  The latch looks once; nothing spins.
+// - Every later launch of M -- the window's guest problems and the successor's head steps -- reads the words the latch left
+//   (plain loads behind a kernel boundary on the same stream), so all of them see the same decision.
+__global__ __launch_bounds__(64) void ramp_ready_kernel(RampState *rs, int q, int m, int T, int hostable)
+{
+    if (threadIdx.x != 0) return;
+    __hip_atomic_store(&rs->head_live[q], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned g = __hip_atomic_load(&rs->generation, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
+    __hip_atomic_store(&rs->generation, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the compiler may drop the fence's own wait: MI355X notes, "compiler hazard")
+    const unsigned long long rec = ((unsigned long long)g << 32) | ((unsigned long long)(unsigned)m << 12) | ((unsigned long long)(unsigned)T << 4) | (unsigned long long)(hostable & 1);
+    __hip_atomic_store(&rs->ready[q], rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(64) void ramp_latch_kernel(RampState *rs, int p, int m)
+{
+    if (threadIdx.x != 0) return;
+    const unsigned long long mine = __hip_atomic_load(&rs->ready[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long next = __hip_atomic_load(&rs->ready[1 - p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned g = (unsigned)(mine >> 32);
+    const int next_m = (int)((next >> 12) & RAMP_MAX_M), next_T = (int)((next >> 4) & RAMP_MAX_T);
+    const bool host = (unsigned)(next >> 32) == g + 1u && next_m == m && (int)((mine >> 12) & RAMP_MAX_M) == m && (next & 1ull) != 0;
+    if (host) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        __hip_atomic_store(&rs->head_live[1 - p], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        rs->hosted += 1u;
+    }
+    for (int j = 1; j <= RAMP_R; ++j)
+        for (int t = 0; t < RAMP_R; ++t) rs->guest_live[p][j - 1][t] = (host && t < j && t < next_T) ? 1 : 0;
+}
+
+void launch_ramp_ready(RampState *rs, int q, int m, int T, int hostable, hipStream_t s)
+{
+    hipLaunchKernelGGL(ramp_ready_kernel, dim3(1), dim3(64), 0, s, rs, q, m, T, hostable);
+}
+void launch_ramp_latch(RampState *rs, int p, int m, hipStream_t s)
+{
+    hipLaunchKernelGGL(ramp_latch_kernel, dim3(1), dim3(64), 0, s, rs, p, m);
+}
+
 // ---------------------------------------------------------------- decoder front end (device function)
 // Embedding gather of the `context` previous tokens, grouped Conv1d over the context axis
 // (kernel = context, so one output position), ReLU.  Pure function of the token context

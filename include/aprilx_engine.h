@@ -116,6 +116,13 @@ APRIL_EXPORT int aprilx_run_decide(AprilASRModel model, int n, int op, const flo
  * needed; tests only (the engine and the kernels consult the same functions, so their decisions cannot diverge). */
 APRIL_EXPORT int aprilx_plan_gemm(int M, int N, int kz, int zcount, int tile_ok, int force, int32_t *out);
 
+/* Ramp merge, the pure host part: which problems of the NEXT feed's first R macro steps the last R macro steps
+ * of a feed of T chunks over L layers can hold.  Writes one record of 3 + 2 R words per window step to out (cap words): own macro step
+ * (1-based, L + T - 1 - R + j), own problems in it, guests in it, then the guests as (layer, chunk) pairs, unused words -1.  Returns the
+ * number of window steps -- 0 when nothing can be hosted (own + guest problems exceed three somewhere, or L <= 2 R) --, -1 on bad
+ * arguments.  No GPU needed; tests only (the engine builds its launch plans from the same function). */
+APRIL_EXPORT int aprilx_ramp_window(int L, int T, int R, int32_t *out, int cap);
+
 /* Which weight-stream kernel (csrc/kernels_recur.hip; layer GEMMs at <= 16 rows) takes a layer GEMM of this shape: kind 0 = the
  * one-launch gates GEMM of a chunk step, 1 = its recurrent half (long feeds), 2 = its input half (long feeds), 3 = FFN up,
  * 4 = LSTM projection, 5 = FFN down; K in `kz` slabs, `groups` sum-of-squares partials per row.  Returns 0 when the general GEMM
@@ -287,6 +294,11 @@ typedef struct AprilxStats {
     uint64_t confidence_records; /* side records (aprilx_session_set_confidence) copied to the host so far; 0 while no session has opted in */
 } AprilxStats;
 APRIL_EXPORT void aprilx_model_stats(AprilASRModel model, int device_index, AprilxStats *out);
+/* Ramp merge counters of one GPU's engine: *ramp_eligible = split feeds launched with nothing enqueued on the layer stream since the
+ * previous feed's layer graph (only those can be hosted), *ramp_hosted = feeds whose first two macro steps ran inside the previous
+ * feed's last two (counted on the device by the kernel that decides it; exact once the streams are idle).  Returns 0, -1 on bad
+ * arguments.  (Not part of AprilxStats: that struct's layout is pinned.) */
+APRIL_EXPORT int aprilx_model_ramp_stats(AprilASRModel model, int device_index, uint64_t *ramp_hosted, uint64_t *ramp_eligible);
 /* Hand-over -> delivery latency of the last (up to 8192) completed ticks of one GPU's stepping thread, in ms, oldest first: from the
  * feed call (aas_feed_pcm16 / aprilx_feed_many / aprilx_feed_many_pipelined / flush) that queued the oldest work a flight served to
  * the moment that flight's results were delivered (asynchronous and pipelined sessions: their handlers have run; synchronous callers:
