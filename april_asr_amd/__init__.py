@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _ffi
 
-__all__ = ["Result", "Token", "Model", "Session", "SessionGroup", "Bias", "resampler_taps"]
+__all__ = ["Result", "Token", "Model", "Session", "SessionGroup", "Bias", "resampler_taps", "decode_host"]
 
 
 class Result(IntEnum):
@@ -242,6 +242,24 @@ class Model:
             raise ValueError("aprilx_resample refused %d samples at %d Hz" % (a.size, in_rate))
         return out[:n]
 
+    def decode(self, data, fmt) -> np.ndarray:
+        """`data` (bytes or an array, taken as raw bytes) in the input format `fmt` -- (encoding, channels, channel), see
+        Session.set_input_format -- decoded to int16 by the device kernel alone (aprilx_decode; tests)."""
+        f = _input_format(*fmt)
+        a = _raw_bytes(data)
+        out = np.zeros(max(a.size, 1), np.int16)
+        n = int(self._L.aprilx_decode(self._handle, C.byref(f), a.ctypes.data, a.size, out.ctypes.data, out.size))
+        if n < 0:
+            raise ValueError("aprilx_decode refused %d bytes of %r" % (a.size, (fmt,)))
+        return out[:n]
+
+    def decode_stats(self, device_index: int = 0):
+        """(launches, frames, ms) of the decode launches of sessions with an input format (aprilx_model_decode_stats); ms under profile(1) only"""
+        l, f, ms = C.c_uint64(0), C.c_uint64(0), C.c_double(0)
+        if self._L.aprilx_model_decode_stats(self._handle, device_index, C.byref(l), C.byref(f), C.byref(ms)) != 0:
+            raise ValueError("aprilx_model_decode_stats refused the call")
+        return int(l.value), int(f.value), float(ms.value)
+
     def run_confidence(self, logits, k: int):
         """The side records of GIVEN logits rows [n][vocab] with k alternatives through the device code the search uses
         (aprilx_run_confidence; tests): an array of n _ffi.AprilxTokenInfo."""
@@ -393,7 +411,8 @@ _HANDLER = _ffi.HANDLER(_dispatch)
 class Session:
     def __init__(self, model: Model, callback: Callable[[Result, List[Token]], None], asynchronous: bool = False,
                  no_rt: bool = False, speaker_name: str = "", raw_events: bool = False, counters=None, input_sample_rate=None,
-                 alternatives=None, bias=None, endpoint_silence_ms=None, blank_penalty=None, max_utterance_ms=None):
+                 alternatives=None, bias=None, endpoint_silence_ms=None, blank_penalty=None, max_utterance_ms=None,
+                 input_format=None, channels: int = 1, channel: int = 0):
         """`counters`: a uint64 ndarray of 6 entries; when given, results are only counted by a C handler inside the
         library (calls, partial, final, cant_keep_up, silence, tokens) and `callback` is never invoked.
         `input_sample_rate`: the rate of the PCM this session will receive (converted to the model's rate on the GPU); None: the
@@ -401,7 +420,9 @@ class Session:
         `alternatives`: K in 1..8: every delivered Token carries its log-softmax, the blank's and the K best candidates
         (set_confidence); None / 0: off.
         `bias`: a Bias (Model.bias): the search boosts the tokens that continue one of its phrases (set_bias); None: off.
-        `endpoint_silence_ms`, `blank_penalty`, `max_utterance_ms`: the session's search options (set_search_options); all None: none."""
+        `endpoint_silence_ms`, `blank_penalty`, `max_utterance_ms`: the session's search options (set_search_options); all None: none.
+        `input_format`, `channels`, `channel`: the format of the audio this session will receive (set_input_format): "mulaw", "alaw",
+        "f32" or "s16", 1..8 interleaved channels, the channel to take or -1 for their downmix; None: mono PCM16."""
         self._L = model._L
         self.info_log = None      # tests: a list that receives (type, [the token's AprilxTokenInfo as bytes, or None]) per result
         self.model = model
@@ -426,6 +447,8 @@ class Session:
         model._sessions.add(self)
         if input_sample_rate is not None:
             self.set_input_rate(input_sample_rate)
+        if input_format is not None:
+            self.set_input_format(input_format, channels, channel)
         if alternatives:
             self.set_confidence(alternatives)
         if bias is not None:
@@ -456,8 +479,33 @@ class Session:
             a = np.ascontiguousarray(data, np.int16)
             self._L.aas_feed_pcm16(self._handle, a.ctypes.data, a.size)
 
+    def feed(self, data) -> None:
+        """Audio in the session's input format (aprilx_session_feed_bytes): bytes, or a uint8 / int16 / float32 array taken as its raw
+        bytes.  A session without a format takes PCM16.  ValueError when `data` is not a whole number of frames (nothing is queued)."""
+        a = _raw_bytes(data)
+        if self._L.aprilx_session_feed_bytes(self._handle, a.ctypes.data, a.size) != 0:
+            raise ValueError("%d bytes are not a whole number of the session's frames" % a.size)
+
     def flush(self) -> None:
         self._L.aas_flush(self._handle)
+
+    def set_input_format(self, encoding="s16", channels: int = 1, channel: int = 0) -> None:
+        """The audio fed from now on is `encoding` ("s16", "mulaw", "alaw", "f32", or the APRILX_ENC_* number) with `channels`
+        interleaved channels, of which `channel` is taken (-1: their downmix); it is decoded on the GPU (aprilx_session_set_input_format,
+        DESIGN.md section 15).  Allowed right after creation and after a completed flush; None or ("s16", 1, 0) restores mono PCM16."""
+        if encoding is None:
+            rc = self._L.aprilx_session_set_input_format(self._handle, None)
+        else:
+            rc = self._L.aprilx_session_set_input_format(self._handle, C.byref(_input_format(encoding, channels, channel)))
+        if rc != 0:
+            raise ValueError("input format %r refused (a value out of range, or audio fed since the last flush)" % ((encoding, channels, channel),))
+
+    def input_format(self):
+        """(encoding name, channels, channel) of the session, or None when it takes mono PCM16"""
+        f = _ffi.AprilxInputFormat()
+        if self._L.aprilx_session_input_format(self._handle, C.byref(f)) != 1:
+            return None
+        return _ENC_NAMES[int(f.encoding)], int(f.channels), int(f.channel)
 
     def set_input_rate(self, rate_hz: int) -> None:
         """The PCM fed from now on is at `rate_hz` (aprilx_session_set_input_rate): allowed right after creation and after a
@@ -610,11 +658,55 @@ class SessionGroup:
             self._counts[i] = a.size
         self._L.aprilx_feed_many_pipelined(len(keep), self._handles, self._ptrs, self._counts, depth)      # (samples are copied inside)
 
+    def feed_bytes(self, data_list, depth: int = 0):
+        """One buffer per session in that session's input format (aprilx_feed_many_bytes; a session without one takes PCM16): bytes or
+        arrays taken as their raw bytes.  depth 0 blocks like feed(); depth >= 1 is the pipelined form (the bytes are copied; call
+        drain() at the end).  ValueError when a buffer is not a whole number of its session's frames (nothing is queued)."""
+        keep = [_raw_bytes(d) for d in data_list]
+        for i, a in enumerate(keep):
+            self._ptrs[i] = a.ctypes.data
+            self._counts[i] = a.size
+        if self._L.aprilx_feed_many_bytes(len(keep), self._handles, self._ptrs, self._counts, int(depth)) != 0:
+            raise ValueError("a buffer is not a whole number of its session's frames")
+
+    def feed_bytes_pipelined(self, data_list, depth: int = 2):
+        self.feed_bytes(data_list, depth)
+
     def drain(self):
         self._L.aprilx_drain_many(len(self.sessions), self._handles)
 
     def flush(self):
         self._L.aprilx_flush_many(len(self.sessions), self._handles)
+
+
+ENCODINGS = {"s16": 0, "mulaw": 1, "alaw": 2, "f32": 3}      # APRILX_ENC_*
+_ENC_NAMES = {v: k for k, v in ENCODINGS.items()}
+
+
+def _input_format(encoding, channels=1, channel=0):
+    enc = ENCODINGS[encoding] if isinstance(encoding, str) else int(encoding)
+    return _ffi.AprilxInputFormat(C.sizeof(_ffi.AprilxInputFormat), enc, int(channels), int(channel))
+
+
+def _raw_bytes(data) -> np.ndarray:
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return np.frombuffer(bytes(data), np.uint8)
+    if not isinstance(data, np.ndarray) or data.dtype not in (np.uint8, np.int16, np.float32):
+        raise TypeError("raw audio must be bytes or a uint8, int16 or float32 array, not %r" % (getattr(data, "dtype", type(data)),))
+    return np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+
+
+def decode_host(data, fmt) -> np.ndarray:
+    """`data` in the input format `fmt` = (encoding, channels, channel) decoded to int16 by the contract in plain C++
+    (aprilx_decode_host; no GPU)."""
+    L = _ffi.lib()
+    f = _input_format(*fmt)
+    a = _raw_bytes(data)
+    out = np.zeros(max(a.size, 1), np.int16)
+    n = int(L.aprilx_decode_host(C.byref(f), a.ctypes.data, a.size, out.ctypes.data, out.size))
+    if n < 0:
+        raise ValueError("aprilx_decode_host refused %d bytes of %r" % (a.size, (fmt,)))
+    return out[:n]
 
 
 def resampler_taps(in_rate: int, out_rate: int):

@@ -61,6 +61,10 @@ class AprilxLoadInfo(C.Structure):
                 ("ranks", C.c_int32), ("used_rccl", C.c_int32)]
 
 
+class AprilxInputFormat(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("encoding", C.c_uint32), ("channels", C.c_uint32), ("channel", C.c_int32)]
+
+
 EXPORTED_REFERENCE_SYMBOLS = [
     "aam_api_init", "aam_create_model", "aam_get_name", "aam_get_description", "aam_get_language",
     "aam_get_sample_rate", "aam_free", "aas_create_session", "aas_feed_pcm16", "aas_flush",
@@ -80,6 +84,8 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_bias_create_ex", "aprilx_bias_flags", "aprilx_run_confidence_biased",
     "aprilx_session_set_search_options", "aprilx_session_search_options", "aprilx_run_decide_opts", "aprilx_greedy_set_search_options",
     "aprilx_ramp_window", "aprilx_model_ramp_stats",
+    "aprilx_session_set_input_format", "aprilx_session_input_format", "aprilx_session_feed_bytes", "aprilx_feed_many_bytes",
+    "aprilx_decode_host", "aprilx_decode", "aprilx_model_decode_stats",
 ]
 
 _lib = None
@@ -170,6 +176,13 @@ def lib():
     L.aprilx_session_search_options.argtypes = [vp, C.POINTER(AprilxSearchOptions)]; L.aprilx_session_search_options.restype = C.c_int
     L.aprilx_run_decide_opts.argtypes = [vp, C.c_int, C.c_int, vp, C.c_float, vp, C.c_int, vp, vp, vp, vp, vp]; L.aprilx_run_decide_opts.restype = C.c_int
     L.aprilx_greedy_set_search_options.argtypes = [vp, C.POINTER(AprilxSearchOptions)]; L.aprilx_greedy_set_search_options.restype = C.c_int
+    L.aprilx_session_set_input_format.argtypes = [vp, C.POINTER(AprilxInputFormat)]; L.aprilx_session_set_input_format.restype = C.c_int
+    L.aprilx_session_input_format.argtypes = [vp, C.POINTER(AprilxInputFormat)]; L.aprilx_session_input_format.restype = C.c_int
+    L.aprilx_session_feed_bytes.argtypes = [vp, vp, sz]; L.aprilx_session_feed_bytes.restype = C.c_int
+    L.aprilx_feed_many_bytes.argtypes = [sz, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.c_int]; L.aprilx_feed_many_bytes.restype = C.c_int
+    L.aprilx_decode_host.argtypes = [C.POINTER(AprilxInputFormat), vp, sz, vp, sz]; L.aprilx_decode_host.restype = C.c_int64
+    L.aprilx_decode.argtypes = [vp, C.POINTER(AprilxInputFormat), vp, sz, vp, sz]; L.aprilx_decode.restype = C.c_int64
+    L.aprilx_model_decode_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]; L.aprilx_model_decode_stats.restype = C.c_int
     _lib = L
     return L
 

@@ -25,6 +25,7 @@ namespace aprilx { int g_loglevel = LOG_WARNING; }
 
 struct AprilASRModel_i { Model m; };
 struct AprilASRSession_i { Session s; };
+#include "group_feed.h"
 
 namespace {
 bool g_inited = false;
@@ -303,36 +304,6 @@ void free_host_weights(HostModel &h)
     std::vector<float>().swap(h.w_decproj); std::vector<float>().swap(h.w_out);
 }
 
-// ---- group calls: the listed sessions by scheduler (GPU), in the order of the list, with their PCM when the call carries some
-struct SchedGroup { Scheduler *sched; std::vector<Session *> ss; std::vector<const short *> pcm; std::vector<size_t> counts; };
-
-std::vector<SchedGroup> group_by_scheduler(size_t n, AprilASRSession *sessions, const short *const *pcm16, const size_t *short_counts)
-{
-    std::vector<SchedGroup> groups;
-    for (size_t i = 0; i < n; ++i) {
-        Session *s = &sessions[i]->s;
-        auto g = std::find_if(groups.begin(), groups.end(), [&](const SchedGroup &x) { return x.sched == s->sched; });
-        if (g == groups.end()) { groups.emplace_back(); g = groups.end() - 1; g->sched = s->sched; }
-        g->ss.push_back(s);
-        if (pcm16) { g->pcm.push_back(pcm16[i]); g->counts.push_back(short_counts[i]); }
-    }
-    return groups;
-}
-
-void deliver_sync_events_all(size_t n, AprilASRSession *sessions)
-{
-    for (size_t i = 0; i < n; ++i) if (sessions[i]->s.sync_mode) sessions[i]->s.sched->deliver_sync_events(&sessions[i]->s);
-}
-
-// a group feed: each scheduler's sessions are submitted at once so that they step together; every GPU is queued first (no wait),
-// then `wait` runs per group, so the GPUs work concurrently
-template <class Wait> void feed_groups(size_t n, AprilASRSession *sessions, const short *const *pcm16, const size_t *short_counts, bool borrow, Wait wait)
-{
-    std::vector<SchedGroup> groups = group_by_scheduler(n, sessions, pcm16, short_counts);
-    for (SchedGroup &g : groups) g.sched->submit((int)g.ss.size(), g.ss.data(), g.pcm.data(), g.counts.data(), false, false, borrow);
-    for (SchedGroup &g : groups) wait(g);
-    deliver_sync_events_all(n, sessions);
-}
 }  // namespace
 
 namespace {
@@ -713,14 +684,14 @@ int aprilx_model_load_info(AprilASRModel model, AprilxLoadInfo *out)
 void aprilx_feed_many(size_t n, AprilASRSession *sessions, const short *const *pcm16, const size_t *short_counts)
 {
     // the sessions' buffers are lent until every session is idle again
-    feed_groups(n, sessions, pcm16, short_counts, /*borrow=*/true, [](SchedGroup &g) { g.sched->wait_idle_many(g.ss.data(), (int)g.ss.size()); });
+    feed_groups(n, sessions, pcm16, short_counts, /*borrow=*/true, /*bytes=*/false, [](SchedGroup &g) { g.sched->wait_idle_many(g.ss.data(), (int)g.ss.size()); });
 }
 
 void aprilx_feed_many_pipelined(size_t n, AprilASRSession *sessions, const short *const *pcm16, const size_t *short_counts, int depth)
 {
     // the samples are copied into the sessions' queues (the caller may reuse its buffers at once)
     const uint64_t max_open = (uint64_t)(std::max(depth, 1) - 1);
-    feed_groups(n, sessions, pcm16, short_counts, /*borrow=*/false, [&](SchedGroup &g) { g.sched->wait_backlog(g.ss.data(), (int)g.ss.size(), max_open); });
+    feed_groups(n, sessions, pcm16, short_counts, /*borrow=*/false, /*bytes=*/false, [&](SchedGroup &g) { g.sched->wait_backlog(g.ss.data(), (int)g.ss.size(), max_open); });
 }
 
 void aprilx_drain_many(size_t n, AprilASRSession *sessions)

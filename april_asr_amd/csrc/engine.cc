@@ -667,10 +667,16 @@ void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<con
     const std::pair<const int16_t *, size_t> *in_parts = rs_in_parts_;
     const size_t n_in_parts = n_rs ? rs_n_in_parts_ : 0, n_in = n_rs ? rs_n_in_ : 0;
     rs_n_ = 0;
+    const int n_dc = n_frames > 0 ? std::max(dc_n_, 0) : 0;
+    const DecodeDesc *dc = dc_desc_;
+    const std::pair<const uint8_t *, size_t> *raw_parts = dc_raw_parts_;
+    const size_t n_raw_parts = n_dc ? dc_n_raw_parts_ : 0, n_raw = n_dc ? dc_n_raw_ : 0;
+    const size_t raw_units = n_dc ? (n_raw + 1) / 2 + 8 : 0;      // the raw region in int16 units, with its alignment
+    dc_n_ = 0;
     if (n_frames <= 0) return;
     HIP_CHECK(hipSetDevice(cfg_.device));
     for (int i = 0; i < n_rs; ++i) rs[i].taps = resample_table(rs_specs_[i]);      // (uploaded at a conversion's first use)
-    if (n_frames > desc_cap_ || n_pcm + n_in > pcm_cap_ || (size_t)n_rs > rs_cap_) {
+    if (n_frames > desc_cap_ || n_pcm + n_in + raw_units > pcm_cap_ || (size_t)n_rs > rs_cap_ || (size_t)n_dc > dc_cap_) {
         sync();
         HipLegacyLock regrow_guard;                   // (frees imply a device synchronisation: not beside another engine's capture; order: capture_mu_, then this)
         for (int b = 0; b < 2; ++b) {
@@ -678,12 +684,14 @@ void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<con
             if (hs_pcm_[b]) { (void)hipHostFree(hs_pcm_[b]); (void)hipFree(ds_pcm_[b]); }
         }
         desc_cap_ = std::max({n_frames * 2, desc_cap_, 1024});
-        pcm_cap_ = std::max({(n_pcm + n_in) * 2, pcm_cap_, (size_t)1 << 16});
+        pcm_cap_ = std::max({(n_pcm + n_in + raw_units) * 2, pcm_cap_, (size_t)1 << 16});
         rs_cap_ = std::max({(size_t)n_rs * 2, rs_cap_, n_rs ? (size_t)256 : (size_t)0});
+        dc_cap_ = std::max({(size_t)n_dc * 2, dc_cap_, n_dc ? (size_t)256 : (size_t)0});
         // one staging buffer per flip: the PCM windows (model-rate regions, then the input-rate spans of resampled sessions), then
-        // (16-byte aligned, right behind the samples of THIS call) the frame descriptors and the resample descriptors -> one
-        // host-to-device copy per call
-        const size_t units = pcm_cap_ + 8 + ((size_t)desc_cap_ * sizeof(FbankFrameDesc) + 1) / 2 + 8 + rs_cap_ * sizeof(ResampleDesc) / 2;
+        // (16-byte aligned) the raw bytes of formatted sessions, then (16-byte aligned, right behind the samples of THIS call) the
+        // frame descriptors, the resample descriptors and the decode descriptors -> one host-to-device copy per call
+        const size_t units = pcm_cap_ + 8 + ((size_t)desc_cap_ * sizeof(FbankFrameDesc) + 1) / 2 + 8 + rs_cap_ * sizeof(ResampleDesc) / 2
+                             + 8 + dc_cap_ * sizeof(DecodeDesc) / 2;
         for (int b = 0; b < 2; ++b) {
             hs_pcm_[b] = hmalloc<int16_t>(units); ds_pcm_[b] = dmalloc<int16_t>(units);
             hs_desc_[b] = nullptr; ds_desc_[b] = nullptr;
@@ -693,9 +701,12 @@ void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<con
     const int b = fb_flip_;
     fb_flip_ ^= 1;
     HIP_CHECK(hipEventSynchronize(fb_done_[b]));          // the launch that used this pair two calls ago has consumed it
-    const size_t doff = ((n_pcm + n_in) * sizeof(int16_t) + 15) / 16 * 16;          // byte offset of the descriptors
-    const size_t roff = (doff + (size_t)n_frames * sizeof(FbankFrameDesc) + 15) / 16 * 16;      // ... and of the resample descriptors
-    const size_t bytes = n_rs ? roff + (size_t)n_rs * sizeof(ResampleDesc) : doff + (size_t)n_frames * sizeof(FbankFrameDesc);
+    const size_t woff = ((n_pcm + n_in) * sizeof(int16_t) + 15) / 16 * 16;          // byte offset of the raw region (empty without formatted sessions)
+    const size_t doff = (woff + n_raw + 15) / 16 * 16;                              // ... of the descriptors
+    const size_t roff = (doff + (size_t)n_frames * sizeof(FbankFrameDesc) + 15) / 16 * 16;      // ... of the resample descriptors
+    const size_t coff = (roff + (size_t)n_rs * sizeof(ResampleDesc) + 15) / 16 * 16;            // ... and of the decode descriptors
+    const size_t bytes = n_dc ? coff + (size_t)n_dc * sizeof(DecodeDesc)
+                              : (n_rs ? roff + (size_t)n_rs * sizeof(ResampleDesc) : doff + (size_t)n_frames * sizeof(FbankFrameDesc));
     char *hs = reinterpret_cast<char *>(hs_pcm_[b]);
     memcpy(hs + doff, desc, (size_t)n_frames * sizeof(FbankFrameDesc));
     ResampleArgs ra;
@@ -710,34 +721,56 @@ void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<con
         }
         ra.n_desc = n_rs; ra.max_blocks = (int)blocks; ra.lds_floats = (int)lds;
     }
-    // the PCM: windows of default sessions are copied, the model-rate regions of resampled windows only reserved (null pointer)
-    auto stage = [&](const std::pair<const int16_t *, size_t> *pp, size_t np, size_t base) {
+    DecodeArgs da;
+    if (n_dc) {
+        DecodeDesc *hd = reinterpret_cast<DecodeDesc *>(hs + coff);
+        int64_t blocks = 0; uint64_t frames = 0;
+        for (int i = 0; i < n_dc; ++i) {
+            hd[i] = dc[i];
+            if (dc[i].dst_in) hd[i].dst += (int32_t)n_pcm;
+            blocks = std::max<int64_t>(blocks, (dc[i].out_cnt + kDecodeBlock - 1) / kDecodeBlock);
+            frames += (uint64_t)dc[i].n_src;
+        }
+        da.n_desc = n_dc; da.max_blocks = (int)blocks;
+        dc_launches_.fetch_add(1, std::memory_order_relaxed); dc_frames_.fetch_add(frames, std::memory_order_relaxed);
+    }
+    // the PCM: windows of default sessions are copied, the model-rate regions of resampled windows only reserved (null pointer);
+    // `base` is the parts' first element in the staging buffer, parts and base in units of the parts' own element (int16, raw byte)
+    auto stage = [&](const auto *pp, size_t np, size_t base) {
+        const size_t el = sizeof(*pp[0].first);
+        char *dst = hs;
         if (pool && np >= 256) {
             part_off_.resize(np);
             size_t off = base;
             for (size_t i = 0; i < np; ++i) { part_off_[i] = off; off += pp[i].second; }
-            int16_t *dst = hs_pcm_[b];
-            pool->run(np, 64, [&](size_t i) { if (pp[i].first) memcpy(dst + part_off_[i], pp[i].first, pp[i].second * sizeof(int16_t)); });
+            pool->run(np, 64, [&](size_t i) { if (pp[i].first) memcpy(dst + part_off_[i] * el, pp[i].first, pp[i].second * el); });
         } else {
             size_t off = base;
-            for (size_t i = 0; i < np; ++i) { if (pp[i].first) memcpy(hs_pcm_[b] + off, pp[i].first, pp[i].second * sizeof(int16_t)); off += pp[i].second; }
+            for (size_t i = 0; i < np; ++i) { if (pp[i].first) memcpy(dst + off * el, pp[i].first, pp[i].second * el); off += pp[i].second; }
         }
     };
     stage(parts, n_parts, 0);
     if (n_in_parts) stage(in_parts, n_in_parts, n_pcm);
+    if (n_raw_parts) stage(raw_parts, n_raw_parts, woff);
     std::lock_guard<std::mutex> cg(capture_mu_);
     if (m_unseen_by_f_) { join(f_stream_, stream_); m_unseen_by_f_ = false; }      // (general-path work may still read ring rows this call overwrites)
     HIP_CHECK(hipMemcpyAsync(ds_pcm_[b], hs_pcm_[b], bytes, hipMemcpyHostToDevice, f_stream_));
     FbankArgs a;
     a.t = ft_; a.pcm = ds_pcm_[b]; a.desc = reinterpret_cast<const FbankFrameDesc *>(reinterpret_cast<const char *>(ds_pcm_[b]) + doff); a.n_frames = n_frames; a.ring = ring_; a.ring_frames = ring_frames_; a.pad_value = pad_value_;
     if (n_rs) { ra.in = ds_pcm_[b]; ra.out = ds_pcm_[b]; ra.desc = reinterpret_cast<const ResampleDesc *>(reinterpret_cast<const char *>(ds_pcm_[b]) + roff); }
+    if (n_dc) {
+        da.raw = reinterpret_cast<const uint8_t *>(ds_pcm_[b]) + woff; da.out = ds_pcm_[b];
+        da.desc = reinterpret_cast<const DecodeDesc *>(reinterpret_cast<const char *>(ds_pcm_[b]) + coff);
+    }
     if (profiling_) {        // (the per-class hipEvents live on M: a profiled fbank runs there, behind its upload)
         m_touched();
         join(stream_, f_stream_);
+        if (n_dc) { timed_begin(T_DECODE); launch_decode(da, stream_); timed_end(T_DECODE); }      // (decode feeds both)
         if (n_rs) { timed_begin(T_RESAMPLE); launch_resample(ra, stream_); timed_end(T_RESAMPLE); }
         timed_begin(T_FBANK); launch_fbank(a, stream_); timed_end(T_FBANK);
         join(f_stream_, stream_);
     } else {
+        if (n_dc) launch_decode(da, f_stream_);
         if (n_rs) launch_resample(ra, f_stream_);
         launch_fbank(a, f_stream_);
     }
@@ -2095,6 +2128,31 @@ void Engine::debug_resample(const ResampleSpec *spec, const int16_t *pcm, size_t
     HIP_CHECK(hipStreamSynchronize(st));
     HIP_CHECK(hipStreamDestroy(st));
     HIP_CHECK(hipMemcpy(out, d + n, n_out * sizeof(int16_t), hipMemcpyDeviceToHost));
+    (void)hipFree(d); (void)hipFree(dd);
+}
+
+void Engine::debug_decode(uint32_t encoding, uint32_t channels, int32_t channel, const void *data, size_t n_frames, int16_t *out)
+{
+    if (!n_frames) return;
+    const size_t bytes = n_frames * channels * encoding_bytes(encoding);
+    HipLegacyLock legacy;
+    HIP_CHECK(hipSetDevice(cfg_.device));
+    uint8_t *d = dmalloc<uint8_t>((bytes + 15) / 16 * 16 + n_frames * sizeof(int16_t));      // (hipMalloc: aligned far beyond the contract's 4 bytes)
+    DecodeDesc *dd = dmalloc<DecodeDesc>(1);
+    DecodeDesc r;
+    r.src_off = 0; r.dst = 0; r.out_cnt = r.n_src = (int32_t)n_frames;
+    r.encoding = (uint8_t)encoding; r.channels = (uint8_t)channels; r.channel = (int8_t)channel;
+    HIP_CHECK(hipMemcpy(d, data, bytes, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dd, &r, sizeof r, hipMemcpyHostToDevice));
+    DecodeArgs a;
+    a.raw = d; a.out = reinterpret_cast<int16_t *>(d + (bytes + 15) / 16 * 16); a.desc = dd; a.n_desc = 1;
+    a.max_blocks = (int)((n_frames + kDecodeBlock - 1) / kDecodeBlock);
+    hipStream_t st = nullptr;                 // (its own stream, as debug_resample)
+    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    launch_decode(a, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipStreamDestroy(st));
+    HIP_CHECK(hipMemcpy(out, a.out, n_frames * sizeof(int16_t), hipMemcpyDeviceToHost));
     (void)hipFree(d); (void)hipFree(dd);
 }
 

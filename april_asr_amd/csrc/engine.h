@@ -29,6 +29,7 @@
 #include "bias.h"
 #include "fbank_tables.h"
 #include "resample.h"
+#include "input_format.h"
 #include "kernels.h"
 #include "host_pool.h"
 #include "model_loader.h"
@@ -137,6 +138,20 @@ public:
                            size_t n_in_parts, size_t n_in)
     {
         rs_n_ = n; rs_desc_ = rs; rs_specs_ = specs; rs_in_parts_ = in_parts; rs_n_in_parts_ = n_in_parts; rs_n_in_ = n_in;
+    }
+    // Sessions with an input format (aprilx_session_set_input_format), for the NEXT fbank() call only: their raw bytes `raw_parts`
+    // (n_raw bytes; every span starts on a 4-byte boundary, `raw_parts` carries the padding as null parts) form a third staged region
+    // behind the two int16 ones, 16-byte aligned, in the same staging buffer and the same upload.  The n descriptors (src_off relative
+    // to that region; dst absolute, or counted from the input-rate spans when dst_in is set) fill int16 regions that were only reserved,
+    // in one decode launch before the resample and the fbank launch.  Without this call fbank() issues exactly the launches it always did.
+    void set_decode_pass(int n, const DecodeDesc *dc, const std::pair<const uint8_t *, size_t> *raw_parts, size_t n_raw_parts, size_t n_raw)
+    {
+        dc_n_ = n; dc_desc_ = dc; dc_raw_parts_ = raw_parts; dc_n_raw_parts_ = n_raw_parts; dc_n_raw_ = n_raw;
+    }
+    // decode launches and the frames they decoded so far (any thread)
+    void decode_counts(uint64_t *launches, uint64_t *frames) const
+    {
+        *launches = dc_launches_.load(std::memory_order_relaxed); *frames = dc_frames_.load(std::memory_order_relaxed);
     }
     void begin_flight();
     bool flight_has_room(int rows, int nsteps = 1) const;   // `nsteps` more steps with `rows` rows in total fit into the index / record rings
@@ -252,6 +267,8 @@ public:
     void debug_fbank(int n_frames, const int16_t *pcm_frames /*[n][padded]*/, float *out /*[n][nbins]*/);
     // one whole segment through resample_kernel (aprilx_resample); out holds resample_total(n) samples
     void debug_resample(const ResampleSpec *spec, const int16_t *pcm, size_t n, int16_t *out);
+    // n_frames frames of `channels` interleaved values through decode_kernel (aprilx_decode); out holds n_frames samples
+    void debug_decode(uint32_t encoding, uint32_t channels, int32_t channel, const void *data, size_t n_frames, int16_t *out);
     void read_ring(int slot, int row, int n_rows, float *out);
     void read_greedy_state(int slot, GreedyState *out);
 
@@ -269,7 +286,7 @@ public:
     // split feeds launched as hostable (any thread)
     void ramp_counts(uint64_t *hosted, uint64_t *eligible);
     void reset_timing();
-    enum { T_GATES = 0, T_GEMM_OTHER = 1, T_ROW = 2, T_CONV = 3, T_FBANK = 4, T_DEC = 5, T_RESAMPLE = 6, T_COUNT = 7 };
+    enum { T_GATES = 0, T_GEMM_OTHER = 1, T_ROW = 2, T_CONV = 3, T_FBANK = 4, T_DEC = 5, T_RESAMPLE = 6, T_DECODE = 7, T_COUNT = 8 };
     long kernels_per_step() const { return kernels_per_step_.load(std::memory_order_relaxed); }    // launches of the last eagerly issued chunk chain
 
 private:
@@ -440,6 +457,12 @@ private:
     const ResampleSpec *const *rs_specs_ = nullptr;
     const std::pair<const int16_t *, size_t> *rs_in_parts_ = nullptr;
     size_t rs_n_in_parts_ = 0, rs_n_in_ = 0;
+    size_t dc_cap_ = 0;                        // decode descriptors the staging buffers have room for
+    int dc_n_ = 0;                             // set_decode_pass(): the decode work of the next fbank() call
+    const DecodeDesc *dc_desc_ = nullptr;
+    const std::pair<const uint8_t *, size_t> *dc_raw_parts_ = nullptr;
+    size_t dc_n_raw_parts_ = 0, dc_n_raw_ = 0;
+    std::atomic<uint64_t> dc_launches_{0}, dc_frames_{0};
     std::mutex rs_mu_;
     std::map<const ResampleSpec *, const float *> rs_tables_;     // phase tables on the device, uploaded at first use (freed with table_allocs_)
     const float *resample_table(const ResampleSpec *spec);

@@ -431,4 +431,27 @@ struct ResampleArgs {
 };
 void launch_resample(const ResampleArgs &a, hipStream_t s);
 
+// ---------------------------------------------------------------- decode (sessions with an input format)
+// Raw bytes -> int16 into the staging buffer resample_kernel and fbank_kernel read, by the contract of input_format.h: one int16 per
+// audio frame of `channels` interleaved values.  One descriptor per staged span: outputs [0, n_src) are decoded from the frames that
+// start at raw byte src_off, outputs [n_src, out_cnt) are written as 0 (the flush zeros behind a segment).  CONTRACT: src_off is a
+// multiple of 4 (the host starts every raw span on a 4-byte boundary of the raw region, whose base is 16-byte aligned), so a frame's
+// values are naturally aligned -- 2 bytes for S16, 4 for F32 -- and every load is an aligned load of one value.
+constexpr int kDecodeBlock = 256;
+struct DecodeDesc {
+    int64_t src_off = 0;                   // byte offset of the first frame inside the raw region
+    int32_t dst = 0;                       // int16 staging offset of the first output
+    int32_t out_cnt = 0, n_src = 0;        // outputs written, of which decoded
+    uint8_t encoding = 0, channels = 1; int8_t channel = 0;
+    uint8_t dst_in = 0;                    // (host only) dst counts from the start of the input-rate spans: Engine::fbank adds the model-rate samples
+};
+struct DecodeArgs {
+    const uint8_t *raw = nullptr;          // raw region
+    int16_t *out = nullptr;                // staging buffer
+    const DecodeDesc *desc = nullptr;
+    int n_desc = 0;
+    int max_blocks = 0;                    // max over descriptors of ceil(out_cnt / kDecodeBlock)
+};
+void launch_decode(const DecodeArgs &a, hipStream_t s);
+
 }  // namespace aprilx

@@ -241,12 +241,13 @@ FbankFrameDesc FrameBook::write_row(int slot, int pcm_off)
 
 void FrameBook::compact()
 {
-    if (ext) return;                                   // positions may point into the lent buffer: settle() does it
-    if (rs) {
+    if (lent()) return;                                // positions may point into the lent buffer: settle() does it
+    if (segmented()) {
         while (segs.size() > 1 && segs[1].pos <= (int64_t)fifo_pos) segs.pop_front();      // segments frames no longer reach
         const int64_t drop = rs_keep() - in_drop;
-        if (drop > 0 && (drop >= 8192 || drop == (int64_t)fifo.size())) {
-            fifo.erase(fifo.begin(), fifo.begin() + (long)drop);
+        if (drop > 0 && (drop >= 8192 || drop == (int64_t)held())) {
+            if (fmt) raw.drop((size_t)drop);
+            else fifo.erase(fifo.begin(), fifo.begin() + (long)drop);
             in_drop += drop;
         }
         return;
@@ -259,6 +260,7 @@ void FrameBook::compact()
 
 void FrameBook::absorb_ext()
 {
+    if (fmt) { raw.absorb(); return; }
     if (!ext) return;
     fifo.insert(fifo.end(), ext, ext + ext_cnt);
     ext = nullptr; ext_cnt = 0;
@@ -266,7 +268,10 @@ void FrameBook::absorb_ext()
 
 void FrameBook::settle()
 {
-    if (ext && rs) {
+    if (fmt) {
+        const int64_t keep = rs_keep() - in_drop;       // (index into raw's bytes ++ ext)
+        if (raw.settle((size_t)keep)) in_drop += keep;
+    } else if (ext && rs) {
         const int64_t keep = rs_keep() - in_drop;       // (index into fifo ++ ext)
         if (keep >= (int64_t)fifo.size()) {
             fifo.assign(ext + (keep - (int64_t)fifo.size()), ext + ext_cnt);
@@ -290,8 +295,8 @@ void FrameBook::settle()
 
 void FrameBook::rs_update()
 {
-    if (!rs) return;
-    const int64_t total = in_drop + (int64_t)(fifo.size() + ext_cnt);
+    if (!segmented()) return;
+    const int64_t total = in_drop + (int64_t)held();
     RsSeg *c = &segs.back();
     if (c->closed) {
         if (total == c->in_start + c->n_in) return;
@@ -301,17 +306,17 @@ void FrameBook::rs_update()
         c = &segs.back();
     }
     c->n_in = total - c->in_start;
-    c->n_out = resample_avail(c->n_in, rs->L, rs->M, rs->K);
+    c->n_out = rs ? resample_avail(c->n_in, rs->L, rs->M, rs->K) : c->n_in;
     rs_end = c->pos + c->n_out;
 }
 
 void FrameBook::rs_close()
 {
-    if (!rs) return;
+    if (!segmented()) return;
     RsSeg &c = segs.back();
     if (c.closed) return;                              // (nothing was fed since the last flush: an empty segment adds no outputs)
     c.closed = true;
-    c.n_out = resample_total(c.n_in, rs->L, rs->M);
+    c.n_out = rs ? resample_total(c.n_in, rs->L, rs->M) : c.n_in;
     rs_end = c.pos + c.n_out + c.zeros;
 }
 
@@ -328,20 +333,21 @@ int64_t FrameBook::rs_keep() const
     const RsSeg &g = segs[i];
     const int64_t j = (int64_t)fifo_pos - g.pos;
     int64_t k = g.n_in;
-    if (!(g.closed && j >= g.n_out)) k = std::min(g.n_in, std::max<int64_t>(0, resample_k0(j, rs->L, rs->M) - rs->K + 1));
+    if (!(g.closed && j >= g.n_out)) k = std::min(g.n_in, std::max<int64_t>(0, rs ? resample_k0(j, rs->L, rs->M) - rs->K + 1 : j));
     return g.in_start + k;
 }
 
-void FrameBook::set_rate(const ResampleSpec *spec)
+void FrameBook::set_input(const ResampleSpec *spec, const InputFormat &f)
 {
     // only on an idle session after creation or a completed flush: what frames have not consumed yet is less than a frame of the
     // flush zeros (or nothing), so it carries over as zeros
     const int64_t left = (int64_t)(stream_end() - fifo_pos);
     ext = nullptr; ext_cnt = 0;
     fifo.clear();
+    raw.clear(); raw.fbytes = f ? f.frame_bytes : 1;
     segs.clear();
     in_drop = 0;
-    if (spec) {
+    if (spec || f) {
         RsSeg z;
         z.pos = (int64_t)fifo_pos; z.closed = true; z.zeros = left;
         segs.push_back(z);
@@ -351,7 +357,7 @@ void FrameBook::set_rate(const ResampleSpec *spec)
         fifo_pos = 0;
         rs_end = 0;
     }
-    rs = spec;
+    rs = spec; fmt = f;
 }
 
 // ---------------------------------------------------------------- model
@@ -422,7 +428,7 @@ bool Scheduler::detach(Session *s)
     s->closing = true;
     cv_done_.wait(lk, [&] { return !s->busy; });
     sessions_.erase(std::remove(sessions_.begin(), sessions_.end(), s), sessions_.end());
-    s->inbox.clear();
+    s->inbox.clear(); s->raw_inbox.clear();
     s->borrow_ptr = nullptr; s->borrow_cnt = 0;
     return true;
 }
@@ -440,7 +446,7 @@ size_t Scheduler::latencies(double *out, size_t cap, bool reset)
     return ret;
 }
 
-void Scheduler::submit(int n, Session *const *ss, const short *const *pcm, const size_t *counts, bool flush, bool wait, bool borrow)
+bool Scheduler::submit(int n, Session *const *ss, const short *const *pcm, const size_t *counts, bool flush, bool wait, bool borrow, bool bytes)
 {
     std::vector<Session *> overflowed;
     std::vector<uint64_t> tickets((size_t)n, 0);
@@ -448,17 +454,26 @@ void Scheduler::submit(int n, Session *const *ss, const short *const *pcm, const
     const auto t_sub = std::chrono::steady_clock::now();
     {
         std::unique_lock<std::mutex> lk(mu_);
+        if (bytes && !flush)
+            for (int i = 0; i < n; ++i) if (counts[i] % (ss[i]->frame_bytes ? ss[i]->frame_bytes : sizeof(int16_t))) return false;      // a partial frame: nothing is queued
         for (int i = 0; i < n; ++i) {
             Session *s = ss[i];
             if (s->closing) continue;
+            if (!flush && !bytes && s->frame_bytes && (counts[i] * sizeof(short)) % s->frame_bytes) {
+                LOGE("feed of %zu bytes is not a whole number of the session's %zu-byte frames: dropped", counts[i] * sizeof(short), s->frame_bytes);
+                continue;
+            }
             if (!s->has_oldest) { s->oldest_submit = t_sub; s->has_oldest = true; }
             if (flush) s->flush_requested = true;
             else {
-                const size_t cnt = counts[i];
+                // positions: samples, or the frames of a session with a format (the bound below counts frames)
+                const size_t unit = s->frame_bytes ? s->frame_bytes : sizeof(int16_t);
+                const size_t cnt = s->frame_bytes || bytes ? counts[i] * (bytes ? 1 : sizeof(short)) / unit : counts[i];
                 // the reference's ring refuses a push that would make it hold MAX_AUDIO samples or more (src/audio_provider.c:61)
-                if (!s->sync_mode && s->inbox.size() + s->borrow_cnt + cnt >= s->ring_limit) { overflowed.push_back(s); continue; }   // april_session.c:482-492
+                if (!s->sync_mode && s->queued() + s->borrow_cnt + cnt >= s->ring_limit) { overflowed.push_back(s); continue; }   // april_session.c:482-492
                 if (cnt) {
-                    if (borrow && !s->borrow_cnt && s->inbox.empty()) { s->borrow_ptr = pcm[i]; s->borrow_cnt = cnt; }
+                    if (borrow && !s->borrow_cnt && s->queued() == 0) { s->borrow_ptr = pcm[i]; s->borrow_cnt = cnt; }
+                    else if (s->frame_bytes) { const uint8_t *b = reinterpret_cast<const uint8_t *>(pcm[i]); s->raw_inbox.insert(s->raw_inbox.end(), b, b + cnt * unit); }
                     else s->inbox.insert(s->inbox.end(), pcm[i], pcm[i] + cnt);
                 }
                 s->fed = true;
@@ -472,13 +487,14 @@ void Scheduler::submit(int n, Session *const *ss, const short *const *pcm, const
     work_seq_.fetch_add(1, std::memory_order_release);
     cv_work_.notify_one();
     for (Session *s : overflowed) s->handler(s->userdata, APRIL_RESULT_ERROR_CANT_KEEP_UP, 0, nullptr);
-    if (!wait) return;
+    if (!wait) return true;
     spin_while_unchanged(done_seq_, done_seen, spin_wait_us_);
     std::unique_lock<std::mutex> lk(mu_);
     cv_done_.wait(lk, [&] {
         for (int i = 0; i < n; ++i) if (tickets[(size_t)i] && ss[i]->completed < tickets[(size_t)i] && !ss[i]->closing) return false;
         return true;
     });
+    return true;
 }
 
 void Scheduler::wait_idle(Session *s)
@@ -499,6 +515,15 @@ bool Scheduler::set_input_rate(Session *s, const ResampleSpec *spec)
     return configure(s, [&] {
         s->fb.set_rate(spec);
         s->ring_limit = spec ? (size_t)(48000ull * spec->in_rate / spec->out_rate) : 48000;
+        return true;
+    });
+}
+
+bool Scheduler::set_input_format(Session *s, const InputFormat &f)
+{
+    return configure(s, [&] {
+        s->fb.set_input(s->fb.rs, f);
+        s->frame_bytes = f.frame_bytes;
         return true;
     });
 }
@@ -610,13 +635,20 @@ bool Scheduler::collect(std::vector<Session *> &work, std::vector<uint64_t> &tak
         if (s->has_oldest) { if (!collect_has_sub_ || s->oldest_submit < collect_t_sub_) collect_t_sub_ = s->oldest_submit; collect_has_sub_ = true; s->has_oldest = false; }
         s->busy = true;
         s->inflight += 1;
-        if (s->borrow_cnt) {
+        if (s->borrow_cnt && s->frame_bytes) {
+            const uint8_t *b = reinterpret_cast<const uint8_t *>(s->borrow_ptr);
+            RawFifo &raw = s->fb.raw;
+            if (s->raw_inbox.empty() && !raw.ext) { raw.ext = b; raw.ext_cnt = s->borrow_cnt; }      // read in place during this tick
+            else { raw.absorb(); raw.append(b, s->borrow_cnt); }
+            s->borrow_ptr = nullptr; s->borrow_cnt = 0;
+        } else if (s->borrow_cnt) {
             if (s->inbox.empty() && !s->fb.ext) { s->fb.ext = s->borrow_ptr; s->fb.ext_cnt = s->borrow_cnt; }   // read in place during this tick
             else { s->fb.absorb_ext(); s->fb.fifo.insert(s->fb.fifo.end(), s->borrow_ptr, s->borrow_ptr + s->borrow_cnt); }   // something queued behind it: keep the order
             s->borrow_ptr = nullptr; s->borrow_cnt = 0;
         }
         if (!s->inbox.empty()) { s->fb.absorb_ext(); s->fb.fifo.insert(s->fb.fifo.end(), s->inbox.begin(), s->inbox.end()); s->inbox.clear(); }
-        if (s->fb.rs) s->fb.rs_update();
+        if (!s->raw_inbox.empty()) { s->fb.raw.absorb(); s->fb.raw.append(s->raw_inbox.data(), s->raw_inbox.size() / s->frame_bytes); s->raw_inbox.clear(); }
+        if (s->fb.segmented()) s->fb.rs_update();
         if (s->fed) { s->was_flushed = false; s->seg_open = true; }         // april_session.c:510
         s->fed = false;
         if (s->flush_requested) {                                           // :547-552
@@ -810,7 +842,10 @@ void Scheduler::stage_resampled(const FrameBook &fb, int64_t first, int64_t last
         d.in_base = k_lo; d.in_n = (int32_t)std::max<int64_t>(0, k_hi - k_lo); d.in_off = (int32_t)staged_in;
         if (d.in_n > 0) {
             const size_t l0 = (size_t)(g.in_start + k_lo - fb.in_drop);
-            fb.append_span(l0, l0 + (size_t)d.in_n, in_parts_);
+            if (fb.fmt) {                              // the span is only reserved: the decode launch fills it
+                in_parts_.emplace_back(nullptr, (size_t)d.in_n);
+                stage_raw(fb, l0, d.in_n, d.in_n, (int32_t)staged_in, true);
+            } else fb.append_span(l0, l0 + (size_t)d.in_n, in_parts_);
             staged_in += (size_t)d.in_n;
         }
         rdesc_.push_back(d);
@@ -818,11 +853,44 @@ void Scheduler::stage_resampled(const FrameBook &fb, int64_t first, int64_t last
     }
 }
 
+// Frames [l0, l0 + n_src) of a formatted session's raw queue go into the raw staging region, on a 4-byte boundary (DecodeDesc's
+// contract), and one decode descriptor writes out_cnt int16 at `dst`: the decoded frames, then zeros.
+void Scheduler::stage_raw(const FrameBook &fb, size_t l0, int32_t n_src, int32_t out_cnt, int32_t dst, bool dst_in)
+{
+    const size_t pad = (4 - staged_raw_ % 4) % 4;
+    if (pad) { raw_parts_.emplace_back(nullptr, pad); staged_raw_ += pad; }
+    DecodeDesc d;
+    d.src_off = (int64_t)staged_raw_; d.dst = dst; d.out_cnt = out_cnt; d.n_src = n_src;
+    d.encoding = (uint8_t)fb.fmt.encoding; d.channels = (uint8_t)fb.fmt.channels; d.channel = (int8_t)fb.fmt.channel; d.dst_in = dst_in ? 1 : 0;
+    if (n_src > 0) {
+        fb.raw.span(l0, l0 + (size_t)n_src, raw_parts_);
+        staged_raw_ += (size_t)n_src * fb.fmt.frame_bytes;
+    }
+    ddesc_.push_back(d);
+}
+
+// A formatted session's window [first, last_end) at the model's rate: its staging region at `base` is only reserved; per segment it
+// overlaps, one decode descriptor fills it -- the segment's frames, then the flush zeros behind them.
+void Scheduler::stage_decoded(const FrameBook &fb, int64_t first, int64_t last_end, size_t base)
+{
+    pcm_parts_.emplace_back(nullptr, (size_t)(last_end - first));
+    for (size_t si = 0; si < fb.segs.size(); ++si) {
+        const FrameBook::RsSeg &g = fb.segs[si];
+        const int64_t lo = std::max(first, g.pos);
+        const int64_t hi = si + 1 < fb.segs.size() ? std::min(last_end, fb.segs[si + 1].pos) : last_end;
+        if (lo >= hi) continue;
+        const int64_t j0 = lo - g.pos, jb = std::min(hi - g.pos, g.n_out);
+        stage_raw(fb, (size_t)std::max<int64_t>(0, g.in_start + j0 - fb.in_drop), (int32_t)std::max<int64_t>(0, jb - j0), (int32_t)(hi - lo),
+                  (int32_t)(base + (size_t)(lo - first)), false);
+    }
+}
+
 void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
 {
     Lap lap;
-    desc_.clear(); pcm_parts_.clear(); in_parts_.clear(); rdesc_.clear(); rspec_.clear();
+    desc_.clear(); pcm_parts_.clear(); in_parts_.clear(); rdesc_.clear(); rspec_.clear(); ddesc_.clear(); raw_parts_.clear(); staged_raw_ = 0;
     size_t staged = 0, staged_in = 0;           // model-rate samples (windows), input-rate samples (spans of resampled windows)
+    auto used = [&] { return staged + staged_in + (staged_raw_ + 1) / 2; };      // what the pass has staged so far, raw bytes of formatted sessions in sample units
     std::vector<Session *> finishers;
     // FbankFrameDesc::pcm_off is a 32-bit sample offset into ONE staging buffer: a pass stages at most `stage_limit` samples
     // (default 2^30; 1640 sessions x a full 8192-frame ring of backlog would pass 2^31) and carries the rest to the next pass
@@ -836,17 +904,21 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
         FrameBook &fb = s->fb;
         // new real frames: frame k covers stream samples [k*shift, k*shift + padded)  (fbank.c:195-236)
         if (fb.can_cut()) {
-            // what a window of c frames stages: its model-rate samples and, for a resampled session, at most this many input samples
+            // what a window of c frames stages: its model-rate samples, for a resampled session at most this many input samples, and for
+            // a formatted session the raw bytes of the one or the other (in sample units, with the spans' alignment)
             auto need = [&](int c) {
                 const size_t m = (size_t)(c - 1) * fb.shift + (size_t)fb.padded;
-                return fb.rs ? m + (m * fb.rs->M + fb.rs->L - 1) / fb.rs->L + 1 + 3 * (2 * (size_t)fb.rs->K + 2) : m;
+                const size_t in = fb.rs ? (m * fb.rs->M + fb.rs->L - 1) / fb.rs->L + 1 + 3 * (2 * (size_t)fb.rs->K + 2) : 0;
+                return m + in + (fb.fmt ? ((fb.rs ? in : m) * fb.fmt.frame_bytes + 1) / 2 + 8 : 0);
             };
-            if (staged + staged_in + need(1) > stage_limit) { progressed = true; continue; }      // next pass
+            // (an empty pass always takes a frame: a frame that passes the limit alone would otherwise never be staged)
+            const size_t used0 = used();
+            if (used0 && used0 + need(1) > stage_limit) { progressed = true; continue; }      // next pass
             const size_t base = staged;
             const size_t first = fb.fifo_pos;
             int cut = 0;
             // (up to a ring's worth per pass: a long feed then yields ~70 chunks per session at once for the layer-major step)
-            while (fb.can_cut() && cut < fb.ring_frames && staged + staged_in + need(cut + 1) <= stage_limit) {
+            while (fb.can_cut() && cut < fb.ring_frames && ((!used0 && !cut) || used0 + need(cut + 1) <= stage_limit)) {
                 desc_.push_back(fb.write_row(s->slot, (int)(base + (size_t)cut * fb.shift)));
                 fb.avail_shadow = fb.avail;                       // fbank.c:300
                 fb.fifo_pos += (size_t)fb.shift;
@@ -854,6 +926,7 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
             }
             const size_t last_end = first + (size_t)(cut - 1) * fb.shift + (size_t)fb.padded;
             if (fb.rs) stage_resampled(fb, (int64_t)first, (int64_t)last_end, base, staged_in);
+            else if (fb.fmt) stage_decoded(fb, (int64_t)first, (int64_t)last_end, base);
             else fb.append_span(first, last_end, pcm_parts_);                 // (contiguous in staging)
             staged += last_end - first;
             s->compact_pending = true;                 // the fifo must not move until the window has been staged
@@ -888,7 +961,7 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
             progressed = true;
             break;
         case 2:
-            if (fb.rs) fb.rs_zeros(2 * 3200);                                // (model-rate zeros behind the closed segment)
+            if (fb.segmented()) fb.rs_zeros(2 * 3200);                                // (model-rate zeros behind the closed segment)
             else { fb.absorb_ext(); fb.fifo.insert(fb.fifo.end(), (size_t)2 * 3200, (int16_t)0); }      // april_session.c:555-556
             s->flush_phase = 3;
             progressed = true;
@@ -906,6 +979,7 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
     }
     tick_.host_ms[1] += lap();
     if (!desc_.empty()) {
+        if (!ddesc_.empty()) eng_->set_decode_pass((int)ddesc_.size(), ddesc_.data(), raw_parts_.data(), raw_parts_.size(), staged_raw_);
         if (!rdesc_.empty()) eng_->set_resample_pass((int)rdesc_.size(), rdesc_.data(), rspec_.data(), in_parts_.data(), in_parts_.size(), staged_in);
         eng_->fbank((int)desc_.size(), desc_.data(), pcm_parts_.data(), pcm_parts_.size(), staged, &pool_);
         pool_.run(work.size(), 64, [&](size_t i) { Session *s = work[i]; if (s->compact_pending) { s->fb.compact(); s->compact_pending = false; } });

@@ -137,12 +137,22 @@ struct FrameBook {
     std::deque<RsSeg> segs;                     // segments whose outputs frames may still need; the last one is the current one
     int64_t in_drop = 0;
     int64_t rs_end = 0;                         // model-rate stream end (available outputs + flush zeros)
-    size_t stream_end() const { return rs ? (size_t)rs_end : fifo.size() + ext_cnt; }
+    // Input format (aprilx_session_set_input_format; `fmt` set): the queued and unconsumed audio is `raw` -- bytes, one
+    // frame per position -- in place of fifo ++ ext, and the positions are kept by the segments above as for resampled input: with an
+    // input rate the raw frames are the resampler's input samples, without one they are the stream's samples themselves (the identity
+    // conversion L = M = 1, K = 0, which runs no resampler).  Flush zeros are int16 zeros behind a segment either way, never encoded.
+    InputFormat fmt;
+    RawFifo raw;
+    bool segmented() const { return rs || fmt; }
+    size_t held() const { return fmt ? raw.count() : fifo.size() + ext_cnt; }      // positions held in fifo ++ ext
+    bool lent() const { return fmt ? raw.ext != nullptr : ext != nullptr; }
+    size_t stream_end() const { return segmented() ? (size_t)rs_end : fifo.size() + ext_cnt; }
     void rs_update();                           // after samples were appended: the current segment's input count and available outputs
     void rs_close();                            // flush: the current segment is complete, all its outputs become available
     void rs_zeros(int64_t n);                   // flush zeros behind the closed segment
     int64_t rs_keep() const;                    // first input sample (numbered across segments) that frames may still need
-    void set_rate(const ResampleSpec *spec);    // idle session after creation / a completed flush
+    void set_rate(const ResampleSpec *spec) { set_input(spec, fmt); }      // idle session after creation / a completed flush
+    void set_input(const ResampleSpec *spec, const InputFormat &f);         // the same for rate and format together
     bool chunk_ready() const { return avail >= seg_count; }
     bool can_cut() const { return stream_end() - fifo_pos >= (size_t)padded && avail + 1 <= ring_frames; }
     void absorb_ext();              // ext -> fifo (keeps stream positions valid)
@@ -168,6 +178,10 @@ struct Session {
 
     // ---- guarded by Scheduler::mu_
     std::vector<int16_t> inbox;               // queued PCM (appended by callers; capacity is reused across feeds)
+    // a session with an input format: frame_bytes > 0, its queue is raw_inbox (whole frames) and borrow_ptr / borrow_cnt lend raw FRAMES
+    size_t frame_bytes = 0;
+    std::vector<uint8_t> raw_inbox;
+    size_t queued() const { return frame_bytes ? raw_inbox.size() / frame_bytes : inbox.size(); }      // positions in the inbox
     const short *borrow_ptr = nullptr;        // PCM lent by a caller that blocks until the work is done (sync feed, feed_many):
     size_t borrow_cnt = 0;                    //   copied once, by the stepping thread, outside the lock
     bool fed = false;                         // a feed arrived since the last collection (even an empty one)
@@ -182,7 +196,7 @@ struct Session {
     // (both read under Scheduler::mu_) everything queued so far has been processed ...
     bool idle() const { return closing || (completed >= submitted && !busy && !fed && !flush_requested); }
     // ... and nothing is queued, no segment is open, no flush is under way: the session's options may change
-    bool settable() const { return !(closing || busy || fed || flush_requested || !inbox.empty() || borrow_cnt || seg_open || flush_phase); }
+    bool settable() const { return !(closing || busy || fed || flush_requested || !inbox.empty() || !raw_inbox.empty() || borrow_cnt || seg_open || flush_phase); }
 
     // ---- owned by the stepping thread while busy
     FrameBook fb;
@@ -226,11 +240,16 @@ public:
     // queue work for n sessions at once and (for sync sessions / wait=true) block until it is done
     // `borrow`: the caller keeps the PCM buffers alive and unchanged until the sessions are idle again (it blocks in this
     // call, or drains afterwards), so they are read in place by the stepping thread instead of being copied under the lock
-    void submit(int n, Session *const *ss, const short *const *pcm, const size_t *counts, bool flush, bool wait, bool borrow = false);
+    // `bytes`: counts are bytes (aprilx_session_feed_bytes); else shorts, which a session with a format reads as 2 x count bytes.  A count
+    // that is not a whole number of the session's frames: with `bytes`, false and nothing is queued for any session; else that session's
+    // feed is dropped with an error message
+    bool submit(int n, Session *const *ss, const short *const *pcm, const size_t *counts, bool flush, bool wait, bool borrow = false, bool bytes = false);
     void deliver_sync_events(Session *s);          // caller-thread delivery for sync sessions
     void wait_idle(Session *s);                    // everything queued so far has been processed
     // aprilx_session_set_input_rate: false when audio is queued or the session has an open segment
     bool set_input_rate(Session *s, const ResampleSpec *spec);
+    // aprilx_session_set_input_format: the same rule; frame_bytes 0 = back to mono PCM16
+    bool set_input_format(Session *s, const InputFormat &f);
     // aprilx_session_set_confidence: the same rule
     bool set_confidence(Session *s, int k);
     // aprilx_session_set_bias: the same rule; null = off.  False also when the engine has no room for another set
@@ -266,6 +285,8 @@ private:
     void complete_flight(Flight &f);
     void cut_frames(std::vector<Session *> &work, bool &progressed);
     void stage_resampled(const FrameBook &fb, int64_t first, int64_t last_end, size_t base, size_t &staged_in);
+    void stage_decoded(const FrameBook &fb, int64_t first, int64_t last_end, size_t base);
+    void stage_raw(const FrameBook &fb, size_t l0, int32_t n_src, int32_t out_cnt, int32_t dst, bool dst_in);
     bool step_chunks(std::vector<Session *> &ready);     // false: the flight's rings are full, (some) work is left for the next flight
     // how advance() runs its T chunks: one chunk step (T == 1, Engine::step), or Engine::lm_step as a feed wavefront / layer-major
     enum StepPath { STEP_CHUNK, STEP_WAVE, STEP_LAYER_MAJOR };
@@ -305,6 +326,9 @@ private:
     FrameBook::Parts in_parts_;                    // input-rate spans of resampled sessions' windows, in order
     std::vector<ResampleDesc> rdesc_;
     std::vector<const ResampleSpec *> rspec_;
+    std::vector<DecodeDesc> ddesc_;                // decode work of formatted sessions' windows
+    RawFifo::Parts raw_parts_;                     // their raw bytes, in order (null parts: the padding in front of a span)
+    size_t staged_raw_ = 0;                        // bytes of raw_parts_
     std::vector<int> slots_, tails_, now_;
     std::vector<float> logit_stage_;
 };

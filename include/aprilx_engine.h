@@ -149,6 +149,45 @@ APRIL_EXPORT int aprilx_resampler_taps(uint32_t in_rate, uint32_t out_rate, int3
  * samples (-1 on refusal or cap too small).  Tests only (extends aprilx_run_fbank's parity role to the resampler). */
 APRIL_EXPORT int64_t aprilx_resample(AprilASRModel model, uint32_t in_rate, const int16_t *pcm, size_t n, int16_t *out, size_t cap);
 
+/* ---- input format -------------------------------------------------------------------------
+ * The reference takes mono PCM16 only (reference april_api.h:183 aas_feed_pcm16).  A session can instead be told the format of the
+ * audio it will receive -- G.711 mu-law or A-law, float32, little-endian int16; 1..8 interleaved channels, one of them or their
+ * downmix -- and is then fed raw bytes; the library decodes them on the GPU, inside the ingest, in front of the resampler and the
+ * filterbank (DESIGN.md section 15 has the contract, bit for bit).  Decoding yields one int16 sample per audio frame, and everything
+ * behind it sees exactly what it would have seen had those samples been fed through aas_feed_pcm16.  The format is independent of
+ * the input rate (frames per second); the two may be set in either order.                                                        */
+enum { APRILX_ENC_S16 = 0, APRILX_ENC_MULAW = 1, APRILX_ENC_ALAW = 2, APRILX_ENC_F32 = 3 };
+typedef struct AprilxInputFormat {
+    uint32_t size;               /* sizeof(AprilxInputFormat) */
+    uint32_t encoding;           /* APRILX_ENC_* */
+    uint32_t channels;           /* 1..8, interleaved; a frame is channels x bytes-per-value bytes */
+    int32_t channel;             /* 0..channels-1: that channel; -1: the downmix floor((2 S + C) / (2 C)) of the frame's decoded values */
+} AprilxInputFormat;
+/* The audio this session receives from now on has this format; NULL or {S16, 1, 0} restores the default (mono PCM16: the session runs
+ * the path it always ran and no decode work is issued for it).  0 on success; -1 on a wrong size, an encoding > 3, channels outside
+ * 1..8, a channel outside -1..channels-1 (nothing changes), or when the session has audio queued or fed since its creation / last
+ * completed aas_flush.  The format persists across aas_flush. */
+APRIL_EXPORT int aprilx_session_set_input_format(AprilASRSession session, const AprilxInputFormat *format);
+/* Reads the session's format into *out: 1 when it has one, 0 when it runs the default (out = {S16, 1, 0}), -1 on bad arguments. */
+APRIL_EXPORT int aprilx_session_input_format(AprilASRSession session, AprilxInputFormat *out);
+/* aas_feed_pcm16 in bytes: `bytes` bytes of the session's format (a session without one: PCM16).  0, or -1 -- nothing is queued --
+ * when that is not a whole number of frames.  On a session WITH a format aas_feed_pcm16, aprilx_feed_many and
+ * aprilx_feed_many_pipelined mean "2 x short_count bytes at this pointer"; a partial frame there is logged and that session's feed
+ * is dropped. */
+APRIL_EXPORT int aprilx_session_feed_bytes(AprilASRSession session, const void *data, size_t bytes);
+/* The group feeds in bytes: depth 0 is aprilx_feed_many (blocks; the buffers are lent), depth >= 1 aprilx_feed_many_pipelined (the
+ * bytes are copied).  Sessions with and without a format may share a call.  0, or -1 -- nothing is queued for any session -- when
+ * one count is not a whole number of its session's frames. */
+APRIL_EXPORT int aprilx_feed_many_bytes(size_t n, AprilASRSession *sessions, const void *const *data, const size_t *byte_counts, int depth);
+/* The decode contract in plain C++ (no GPU, no model): writes and returns bytes / frame-size samples; -1 on a bad format, a
+ * partial frame or cap too small. */
+APRIL_EXPORT int64_t aprilx_decode_host(const AprilxInputFormat *format, const void *data, size_t bytes, int16_t *out, size_t cap);
+/* The same through the device kernel alone.  Tests only (the role of aprilx_resample). */
+APRIL_EXPORT int64_t aprilx_decode(AprilASRModel model, const AprilxInputFormat *format, const void *data, size_t bytes, int16_t *out, size_t cap);
+/* Decode launches of one GPU's engine, the frames they decoded (windows overlap: at least the frames fed), and under
+ * aprilx_model_profile(model, 1) their time in ms.  0, -1 on bad arguments.  (Not part of AprilxStats: that struct's layout is pinned.) */
+APRIL_EXPORT int aprilx_model_decode_stats(AprilASRModel model, int device_index, uint64_t *launches, uint64_t *frames, double *ms);
+
 /* ---- per-token confidence and alternatives ------------------------------------------------
  * AprilToken.logprob (reference april_api.h:118-137) is the raw joiner logit of the token -- the reference does no softmax -- which
  * cannot be compared between tokens, sessions or models.  A session can ask for the log-softmax of every token it delivers, the
