@@ -63,7 +63,8 @@ __device__ __forceinline__ void bias_row_begin(const DecideArgs &a, int m, unsig
 
 // decide_body's arg-max loop on v' = v + bonus(s, n): the same statements, the bonus added between the logit dump (which keeps
 // the network's output) and the comparisons.  It is a COPY of that loop (whose lines stay as they are for the mutation yardstick,
-// tests/mutate_device_decide.py, which edits only the original): any change to one has to be made in the other.
+// tests/mutate_device_decide.py, which edits the original in its first list and this copy in its list of the opt-in lines): any change
+// to one has to be made in the other.
 __device__ __forceinline__ void bias_scan(const DecideArgs &a, int m, const BiasRow &br, float &best, int &best_i, float &blank_v)
 {
     for (int n = threadIdx.x; n < a.n_valid; n += 256) {

@@ -212,7 +212,8 @@ __device__ __forceinline__ void decide_body(const DecideArgs &a)
     BiasRow br;
     if (BIAS) bias_row_begin(a, m, bias_lds, br);
     // (bias_scan in kernels_bias.inc is a COPY of the loop below with the bonus added: a change to the loop -- the dump, the blank test,
-    // the comparison -- has to be made in both; tests/mutate_device_decide.py edits only this one)
+    // the comparison -- has to be made in both; tests/mutate_device_decide.py edits each of the two, this one in its first list and the copy
+    // in its list of the opt-in lines)
     if (BIAS && br.bonus) bias_scan(a, m, br, best, best_i, blank_v);
     else
     for (int n = tid; n < a.n_valid; n += 256) {

@@ -409,9 +409,11 @@ def build_joiner(dims, w, variant):
 
 
 # ------------------------------------------------------------------ vocabulary + params + container
-def make_tokens(vocab, seed=7, punctuation=True):
-    """Deterministic BPE-like vocabulary. id 0 = <blk>; optional punctuation and digits so the
-    reference's punctuation / digit-dot branches (april_session.c:340-358) are reachable."""
+def make_tokens(vocab, seed=7, punctuation=True, blank_id=0):
+    """Deterministic BPE-like vocabulary. id `blank_id` (default 0) = <blk>; optional punctuation and digits so the
+    reference's punctuation / digit-dot branches (april_session.c:340-358) are reachable.  A blank that is not token 0 is
+    moved there from the front of the same list, so the other tokens keep their order."""
+    assert 0 <= blank_id < vocab
     rng = np.random.RandomState(seed)
     toks = ["<blk>"]
     special = [".", ",", "?", "!", " 1", "2", " 3", "4"] if punctuation else []
@@ -429,6 +431,8 @@ def make_tokens(vocab, seed=7, punctuation=True):
             continue
         seen.add(s)
         toks.append(s)
+    if blank_id:
+        toks.insert(blank_id, toks.pop(0))
     return toks
 
 
@@ -482,17 +486,19 @@ def container_bytes(networks, params, name="synthetic", description="seeded synt
 
 
 def write_model(path, dims=None, seed=2023, variant=None, punctuation=True, joiner_gain=6.0, blank_bias=4.7,
-                name=None, params=None, tokens=None):
+                name=None, params=None, tokens=None, blank_id=0):
     """Write a synthetic .april file; returns (dims, weights, tokens).  `params`: keyword overrides of the PARAMS block
     (rate, shift_ms, length_ms, round_pow2, mel_low, mel_high -- e.g. round_pow2=0 for a 400-point FFT at 16 kHz / 25 ms).
-    `tokens`: a hand-made token list of dims["vocab"] entries (id 0 the blank) instead of the generated one."""
+    `tokens`: a hand-made token list of dims["vocab"] entries (id `blank_id` the blank) instead of the generated one.
+    `blank_id`: the id of the blank (the reference's exporter writes sp.piece_to_id("<blk>"); any 0 <= id < vocab is legal): it gets the
+    blank bias of the joiner, the PARAMS block names it and the generated token list puts "<blk>" there."""
     dims = dict(dims or APRILV0_DIMS)
     variant = dict(variant or {})
-    w = make_weights(dims, seed=seed, joiner_gain=joiner_gain, blank_bias=blank_bias)
-    toks = list(tokens) if tokens is not None else make_tokens(dims["vocab"], punctuation=punctuation)
+    w = make_weights(dims, seed=seed, joiner_gain=joiner_gain, blank_bias=blank_bias, blank_id=blank_id)
+    toks = list(tokens) if tokens is not None else make_tokens(dims["vocab"], punctuation=punctuation, blank_id=blank_id)
     assert len(toks) == dims["vocab"], "the token list must have dims['vocab'] entries"
     nets = [build_encoder(dims, w, variant), build_decoder(dims, w, variant), build_joiner(dims, w, variant)]
-    blob = container_bytes(nets, params_block(dims, toks, **dict(params or {})), name=name or ("synthetic-L%d-d%d" % (dims["n_layers"], dims["d_model"])))
+    blob = container_bytes(nets, params_block(dims, toks, **dict(dict(blank_id=blank_id) if blank_id else {}, **dict(params or {}))), name=name or ("synthetic-L%d-d%d" % (dims["n_layers"], dims["d_model"])))
     with open(path, "wb") as f:
         f.write(blob)
     return dims, w, toks

@@ -1,6 +1,9 @@
-"""Runs every hand-derived state-machine case (tests/golden/state_machine_cases.py) through the DEVICE's copy of the search decision
-(csrc/kernels_misc.hip decide_kernel, via aprilx_run_decide) of the library named by APRIL_ASR_LIB -- a mutant built by
-tests/mutate_device_decide.py.  Needs a GPU.  Exit status 0 = every case passed (the mutant SURVIVES), 1 = a case caught it."""
+"""Runs the reference-based checks of the plain search decision through the DEVICE's copy of it (csrc/kernels_misc.hip decide_kernel, via
+aprilx_run_decide) of the library named by APRIL_ASR_LIB -- a mutant built by tests/mutate_device_decide.py.  Needs a GPU.
+    python device_decide_mutant_worker.py MODEL.april [MODEL.april ...]
+For every model: each hand-derived state-machine case (tests/golden/state_machine_cases.py) and the NaN row; for a model of 500 tokens or
+more also the ties between ids of one lane.  The code is tests/test_gpu_decide.py's own.  Exit status 0 = every check passed (the
+mutant SURVIVES), 1 = a check caught it."""
 import os
 import sys
 
@@ -14,35 +17,26 @@ import state_machine_cases as G  # noqa: E402
 
 def main():
     import april_asr_amd as A
-    from test_gpu_decide import DeviceSearch
-    from test_state_machine_golden import product_rounds, symbols
-    m = A.Model(sys.argv[1])
-    sym = symbols([m.token(i) for i in range(m.dims.vocab)])
-    for case in G.CASES:
+    from test_gpu_decide import check_hand_derived_case, check_nan_row, check_same_lane_ties
+    from test_state_machine_golden import symbols
+    for path in sys.argv[1:]:
+        m = A.Model(path)
+        tokens = [m.token(i) for i in range(m.dims.vocab)]
+        sym = symbols(tokens)
+        what = "%s: " % os.path.basename(path)
         try:
-            dev = DeviceSearch(m)
-            exp = iter(case["rounds"])
-            rnd = 0
-            for it in product_rounds(case, sym):
-                if it[0] == "flush":
-                    assert next(exp) == "FLUSH"
-                    dev.flush()
-                    want_ctx, want_last = case["flush_state"]
-                    assert dev.ctx == (sym[want_ctx[0]], sym[want_ctx[1]]) and dev.last_tok == (-1 if want_last is None else sym[want_last]), "state after flush"
-                    continue
-                _, idx, mx, bl, early, now, scripted, tie = it
-                rnd = 0 if early == 1.0 else rnd + 1
-                blank = dev.round(idx, mx, bl, early, now, rnd, tie)
-                if not scripted:
-                    assert blank, "filler round"
-                    continue
-                e = next(exp)
-                assert blank == e[0], "blank flag"
-                assert dev.ctx == (sym[e[1][0]], sym[e[1][1]]), "context"
-                assert dev.last_tok == (-1 if e[2] is None else sym[e[2]]), "last active token"
+            for case in G.CASES:
+                what = "%s %s: " % (os.path.basename(path), case["name"])
+                check_hand_derived_case(m, case, sym)
+            what = "%s NaN row: " % os.path.basename(path)
+            check_nan_row(m, tokens)
+            if m.dims.vocab >= 500:
+                what = "%s same-lane ties: " % os.path.basename(path)
+                check_same_lane_ties(m)
         except AssertionError as e:
-            print("KILLED by %s: %s" % (case["name"], str(e)[:200]))
+            print("KILLED by %s%s" % (what, str(e)[:200].replace("\n", " ")))
             return 1
+        m.close()
     print("SURVIVED")
     return 0
 

@@ -26,7 +26,7 @@ def symbols(tokens):
     w2 = first(lambda t: t.startswith(" ") and len(t) > 2 and not t[1].isdigit(), (w1,))
     c1 = first(lambda t: not t.startswith(" ") and t.isalpha() and len(t) > 1)
     c2 = first(lambda t: not t.startswith(" ") and t.isalpha() and len(t) > 1, (c1,))
-    return {"W1": w1, "W2": w2, "C1": c1, "C2": c2, "DOT": tokens.index("."), "COMMA": tokens.index(","), "D2": tokens.index("2"), "<blk>": 0}
+    return {"W1": w1, "W2": w2, "C1": c1, "C2": c2, "DOT": tokens.index("."), "COMMA": tokens.index(","), "D2": tokens.index("2"), "<blk>": tokens.index("<blk>")}
 
 
 def make_options(opts, size_delta=0):

@@ -7,14 +7,16 @@ import numpy as np
 import pytest
 
 import bias_ref as R
+import blank_models as BM
 
 
 def host_model(request, which):
     import april_asr_amd as A
-    info = request.getfixturevalue(which + "_model")
+    info = BM.model_info(which, request)
     m = A.Model.load_host_only(info["path"])
     texts = [t.encode("utf-8") for t in info["tokens"]]
-    assert len(texts) == m.dims.vocab == dict(tiny=40, medium=131, v0=500)[which]
+    assert len(texts) == m.dims.vocab == dict(tiny=40, medium=131, v0=500, blank39=40, blank255=500)[which]
+    assert m.dims.blank_id == info["blank"] and texts[info["blank"]] == b"<blk>"
     return m, texts
 
 
@@ -38,7 +40,7 @@ def random_phrases(rng, texts, blank, n):
     return out
 
 
-@pytest.mark.parametrize("which", ["tiny", "medium", "v0"])
+@pytest.mark.parametrize("which", ["tiny", "medium", "v0", "blank39", "blank255"])
 def test_builder_equals_the_reference(which, request):
     m, texts = host_model(request, which)
     blank = m.dims.blank_id
@@ -62,7 +64,7 @@ def test_builder_equals_the_reference(which, request):
         assert blank not in tok, "the blank never has an edge"
         b.close(); b2.close()
     print("%s: %d tested phrases have two or more segmentations" % (which, multi))
-    if which != "tiny":                                    # (40 tokens: the tiny list has no token that two others spell)
+    if which not in ("tiny", "blank39"):                   # (40 tokens: the tiny list has no token that two others spell)
         assert multi >= 1, "at least one tested phrase must have two segmentations into the model's tokens"
 
 

@@ -124,14 +124,16 @@ def test_non_strict_sets_are_unchanged_and_flags_are_checked(hand):
         A.Bias(m, p, flags=4)
 
 
-@pytest.mark.parametrize("which", ["tiny", "medium", "v0"])
+@pytest.mark.parametrize("which", ["tiny", "medium", "v0", "blank39", "blank255"])
 def test_builder_equals_the_reference_on_random_sets(which, request):
     import april_asr_amd as A
+    import blank_models as BM
     from test_bias_cpu import random_phrases
-    info = request.getfixturevalue(which + "_model")
+    info = BM.model_info(which, request)
     m = A.Model.load_host_only(info["path"])
     texts = [t.encode("utf-8") for t in info["tokens"]]
     blank = m.dims.blank_id
+    assert blank == info["blank"] and texts[blank] == b"<blk>"
     rng = np.random.default_rng(100 + len(texts))
     for trial in range(5):
         phrases = random_phrases(rng, texts, blank, 3 + 6 * trial)

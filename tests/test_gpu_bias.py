@@ -14,6 +14,7 @@ import pytest
 
 import bias_ref as R
 import bias_worker as W
+import blank_models as BM
 import confidence_ref as CR
 
 pytestmark = pytest.mark.gpu
@@ -32,9 +33,10 @@ def load(which, request, model_dir):
         path = str(model_dir / "tiny_vocab1100.april")
         SM.write_model(path, dict(SM.TINY_DIMS, vocab=1100))
     else:
-        path = request.getfixturevalue(which + "_model")["path"]
+        path = BM.model_info(which, request)["path"]
     gm = A.Model(path)
-    assert gm.dims.vocab == dict(tiny=40, medium=131, v0=500, vocab1100=1100)[which]
+    assert gm.dims.vocab == dict(tiny=40, medium=131, v0=500, vocab1100=1100, **{k: v[0] for k, v in BM.MODELS.items()})[which]
+    assert gm.dims.blank_id == BM.MODELS.get(which, (0, 0))[1]
     return gm
 
 
@@ -66,9 +68,16 @@ def check_rows(gm, ref, bias, searches, rows, ee, now, rnd, what):
 
 
 # ---------------------------------------------------------------- 1. the decision kernel on given rows
-@pytest.mark.parametrize("which", ["tiny", "medium", "v0", "vocab1100"])
+@pytest.mark.parametrize("which", ["tiny", "medium", "v0", "vocab1100", "blank64", "blank255", "blank1050"])
 def test_scripted_rounds(which, request, model_dir):
     gm = load(which, request, model_dir)
+    check_scripted_rounds(gm)
+    gm.close()
+
+
+def check_scripted_rounds(gm, trials=2):
+    """the biased decision kernel on hand-made rows and on random rounds against bias_ref, bit for bit (also what
+    tests/device_optin_mutant_worker.py runs against every mutant of the bias lines)"""
     texts, blank, V = W.model_texts(gm), gm.dims.blank_id, gm.dims.vocab
     cls = R.token_classes(texts)
     words = [i for i, t in enumerate(texts) if t[:1] == b" " and i != blank]
@@ -103,6 +112,28 @@ def test_scripted_rounds(which, request, model_dir):
         plain, _ = decide_plain(gm, r[None], ee, [40], 0, [[blank, c, -1, 0]])
         assert rec[1].tobytes() == plain[0].tobytes(), "a row without a set differs from aprilx_run_decide: " + what
     assert bits(np.float32(3.0) + two) == bits(np.float32(5.0))
+    # ties between ids that ONE lane of bias_scan compares (n, n + 256, ...): the lower id wins only because ids ascend within a lane and
+    # the comparison is strict.  d: unboosted ids in a's lane; x: a lane without a boosted token
+    lane_a = [n for n in range(a + 256, V, 256) if n != blank and n not in ref.eff[0]]
+    x = next(n for n in range(20, 256) if all(m != blank and m not in ref.eff[0] for m in range(n, V, 256)))
+    lane_x = list(range(x + 256, V, 256))
+    ties = []
+    for d in lane_a:
+        ties.append(("a tie that exists only after the bonus, %d apart: the boosted lower id" % (d - a), row(**{"t%d" % a: 3.0, "t%d" % d: 5.0}), a))
+        ties.append(("the boosted token behind by less than its bonus: the higher id", row(**{"t%d" % a: 2.75, "t%d" % d: 5.0}), d))
+    for d in lane_x:
+        ties.append(("a raw tie %d apart in a row with a set" % (d - x), row(**{"t%d" % x: 5.0, "t%d" % d: 5.0}), x))
+    if len(lane_x) >= 2:
+        ties.append(("a raw tie of three in one lane", row(**{"t%d" % n: 5.0 for n in [x] + lane_x[:2]}), x))
+        ties.append(("a raw tie of the lane's second and third id", row(**{"t%d" % n: 5.0 for n in lane_x[:2]}), lane_x[0]))
+    assert (len(ties) >= 3) == (V >= 500)
+    for what, r, want_idx in ties:
+        s_b, s_0 = R.Search(cls, blank, ref), R.Search(cls, blank, None)
+        s_b.ctx = [blank, c]; s_0.ctx = [blank, c]
+        rec, _ = check_rows(gm, ref, bias, [s_b, s_0], np.stack([r, r]), 0.0, np.array([40, 40], np.int32), 0, what)
+        assert int(rec["idx"][0]) == want_idx and not (rec["flags"][0] & BLANK), (what, int(rec["idx"][0]), want_idx)
+        plain, _ = decide_plain(gm, r[None], 0.0, [40], 0, [[blank, c, -1, 0]])
+        assert rec[1].tobytes() == plain[0].tobytes(), "a row without a set differs from aprilx_run_decide: " + what
     # punctuation override reached through the bonus: a phrase that ends in the comma token; 2.0 + 2 > 5.0 - 3.5 but 2.0 is not
     comma = [i for i, t in enumerate(texts) if t == b","]
     if comma:
@@ -129,7 +160,7 @@ def test_scripted_rounds(which, request, model_dir):
     bias.close(); bias3.close()
 
     # ---- 2 x 1500 random rounds with random sets: 50 rows per launch (every fifth without a set), 30 launches in sequence
-    for trial in range(2):
+    for trial in range(trials):
         rng = np.random.default_rng(1000 * trial + V)
         phrases = W.session_phrases(texts, blank, rng, n=5 + 25 * trial)
         phrases[0] = (phrases[0][0], -2.0); phrases[1] = (phrases[1][0], 0.0)
@@ -154,7 +185,6 @@ def test_scripted_rounds(which, request, model_dir):
             moved += sum(1 for s in searches if s.s)
         assert moved > 100, "the random rounds must reach states inside phrases"
         bias.close()
-    gm.close()
 
 
 # ---------------------------------------------------------------- 2. whole sessions from their raw traced logits

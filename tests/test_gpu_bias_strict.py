@@ -15,6 +15,7 @@ import pytest
 import bias_ref as R
 import bias_strict_ref as SR
 import bias_worker as W
+import blank_models as BM
 import confidence_ref as CR
 from test_gpu_bias import bits, check_rows, decide_plain
 
@@ -25,9 +26,33 @@ FINAL, SILENCE = 2, 4
 
 def load(which, request):
     import april_asr_amd as A
-    gm = A.Model(request.getfixturevalue(which + "_model")["path"])
-    assert gm.dims.vocab == dict(tiny=40, v0=500)[which]
+    gm = A.Model(BM.model_info(which, request)["path"])
+    assert gm.dims.vocab == dict(tiny=40, v0=500, **{k: v[0] for k, v in BM.MODELS.items()})[which]
+    assert gm.dims.blank_id == BM.MODELS.get(which, (0, 0))[1]
     return gm
+
+
+def same_lane_sets(texts, blank, cls):
+    """For V >= 500, two strict one- and two-phrase lists whose permitted root tokens meet another id of their own lane (n, n + 256, ...):
+    (h, f): h permitted, f = h - 256 forbidden;  (p, q): p and q = p + 256 both permitted.  None below 500 tokens."""
+    V = len(texts)
+    if V < 500:
+        return None
+    words = [i for i, t in enumerate(texts) if t[:1] == b" " and len(t) >= 3 and i != blank and not (cls[i] & 22)]
+    hf = pq = None
+    for h in words:
+        f = h - 256
+        if hf is None and f >= 0 and f != blank and not (cls[f] & 6):
+            ref = SR.StrictRef(texts, blank, [(texts[h], 2.0)])
+            if h in ref.permitted(0) and f not in ref.permitted(0):
+                hf = (h, f, ref)
+        q = h + 256
+        if pq is None and q in words:
+            ref = SR.StrictRef(texts, blank, [(texts[h], 2.0), (texts[q], 2.0)])
+            if h in ref.permitted(0) and q in ref.permitted(0):
+                pq = (h, q, ref)
+    assert hf is not None and pq is not None, "the vocabulary has no word tokens 256 apart"
+    return hf, pq
 
 
 def pick_tokens(texts, blank, cls):
@@ -43,9 +68,16 @@ def pick_tokens(texts, blank, cls):
 
 
 # ---------------------------------------------------------------- 1. the decision kernel on given rows
-@pytest.mark.parametrize("which", ["tiny", "v0"])
+@pytest.mark.parametrize("which", ["tiny", "v0", "blank64", "blank255", "blank1050"])
 def test_given_rows(which, request):
     gm = load(which, request)
+    check_given_rows(gm)
+    gm.close()
+
+
+def check_given_rows(gm):
+    """the decision kernel with strict sets on hand-made rows and random rounds against bias_strict_ref, bit for bit (also what
+    tests/device_optin_mutant_worker.py runs against every mutant of the bias lines)"""
     texts, blank, V = W.model_texts(gm), gm.dims.blank_id, gm.dims.vocab
     cls = R.token_classes(texts)
     a, b, c = pick_tokens(texts, blank, cls)
@@ -91,6 +123,25 @@ def test_given_rows(which, request):
         alone, _ = decide_plain(gm, r[None], 0.0, [40], 0, [[blank, ctx_tok, -1, 0]])
         assert rec[1].tobytes() == alone[0].tobytes(), "a row without a set differs from aprilx_run_decide: " + what
 
+    # ---- ties inside one lane of bias_scan (ids 256 apart), V >= 500
+    lanes = same_lane_sets(texts, blank, cls)
+    if lanes:
+        (h, f, ref_h), (p, q, ref_pq) = lanes
+        bias_h, bias_pq = gm.bias([(texts[h], 2.0)], strict=True), gm.bias([(texts[p], 2.0), (texts[q], 2.0)], strict=True)
+        tie_cases = [
+            ("a tie after the bonus between a permitted id and the forbidden id 256 below it", ref_h, bias_h, row({f: 5.0, h: 3.0}), h),
+            ("the forbidden id 256 below the permitted one is the raw arg-max", ref_h, bias_h, row({f: 9.0, h: 3.0}), h),
+            ("a tie of two permitted ids 256 apart", ref_pq, bias_pq, row({p: 3.0, q: 3.0}), p),
+            ("two permitted ids 256 apart, the higher one ahead", ref_pq, bias_pq, row({p: 3.0, q: 3.5}), q),
+        ]
+        for what, rf, bs, r, want_idx in tie_cases:
+            srch = R.Search(cls, blank, rf)
+            srch.ctx = [blank, ctx_tok]
+            rec, _ = check_rows(gm, rf, bs, [srch], r[None], 0.0, np.array([40], np.int32), 0, what)
+            assert int(rec["idx"][0]) == want_idx and not (rec["flags"][0] & BLANK), (what, rec[0])
+            assert bits(rec["max"][0]) == bits(np.float32(r[want_idx]) + np.float32(2.0))
+        bias_h.close(); bias_pq.close()
+
     # ---- random rounds: 24 rows per launch (every fourth without a set), 12 launches in sequence, three rounds, silences
     rng = np.random.default_rng(V)
     phrases = W.session_phrases(texts, blank, rng, n=12)
@@ -128,13 +179,17 @@ def test_given_rows(which, request):
             assert int(rec["idx"][i]) == idx and bits(rec["max"][i]) == bits(mx) and bits(rec["blank"][i]) == bits(bl)
     for x in (bias, bias2, loose):
         x.close()
-    gm.close()
 
 
 # ---------------------------------------------------------------- 2. confidences of strict rows
-@pytest.mark.parametrize("which", ["tiny", "v0"])
+@pytest.mark.parametrize("which", ["tiny", "v0", "blank39", "blank1050"])
 def test_confidences_over_the_permitted_subset(which, request):
     gm = load(which, request)
+    check_confidences_over_the_permitted_subset(gm)
+    gm.close()
+
+
+def check_confidences_over_the_permitted_subset(gm):
     texts, blank, V = W.model_texts(gm), gm.dims.blank_id, gm.dims.vocab
     rng = np.random.default_rng(7 * V)
     phrases = W.session_phrases(texts, blank, rng, n=12)
@@ -179,7 +234,7 @@ def test_confidences_over_the_permitted_subset(which, request):
     out2 = gm.run_confidence_biased(rows[:4], K, loose, st2)
     for i, s in enumerate(st2):
         CR.check_info(out2[i], loose_ref.biased(rows[i], s) if s >= 0 else rows[i], blank, K, "boosting / plain row %d" % i)
-    bias.close(); loose.close(); gm.close()
+    bias.close(); loose.close()
 
 
 # ---------------------------------------------------------------- 3. live sessions

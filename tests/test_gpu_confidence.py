@@ -13,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+import blank_models as BM
 import confidence_ref as R
 from conftest import speech_like_pcm
 
@@ -95,6 +96,30 @@ def check_live(ev, log, lg, blank, k):
 
 
 # ---------------------------------------------------------------- 1. the device code against float64 on given rows
+def same_lane_ids(vocab, blank):
+    """Token ids that one lane of the 256 scans (n, n + 256, ...), none of them the blank: [(lower, higher, ...)].
+    V >= 500: a pair; V > 768: a triple; V > 1024 (past confidence_row's register window, kConfRegs * 256): a pair 1024 apart -- the
+    lower id held in a register, the higher one re-evaluated -- and a pair 256 apart on the two sides of the window."""
+    def free(n):
+        while any(m == blank for m in range(n % 256, vocab, 256)):
+            n += 1
+        return n
+    out = []
+    if vocab >= 500:
+        n = free(17)
+        out.append((n, n + 256))
+    if vocab > 768:
+        n = free(45)
+        out.append((n, n + 256, n + 512))
+    if vocab > 1024 + 64:
+        n = free(30)
+        out.append((n, n + 1024))
+        out.append((n + 768 + 1, n + 1024 + 1))
+    for ids in out:
+        assert all(0 <= i < vocab and i != blank for i in ids) and len({i % 256 for i in ids}) == 1
+    return out
+
+
 def case_rows(vocab, blank, rng):
     rows = [R.random_rows(rng, 48, vocab, s) for s in (1.0, 10.0, 100.0)]
     extra = []
@@ -105,13 +130,48 @@ def case_rows(vocab, blank, rng):
     a = t.copy(); a[[vocab - 1, 2]] = top; a[[9, 20, 21]] = top - 0.5; extra.append(a)      # ties at two levels, first and last lane
     a = t.copy(); a[blank] = top + 5.0; extra.append(a)                                     # the maximum at the blank
     a = t.copy(); a[blank] = top + 5.0; a[[4, 6]] = top; extra.append(a)
+    # the blank more than 90 above every other logit: a sum taken around a maximum that leaves the blank out overflows (expf(> 88.7))
+    a = t.copy(); a[blank] = top + 95.0; extra.append(a)
+    # ties between ids that ONE lane scans: the lower id wins only because ids ascend within a lane and the comparisons are strict
+    single = 1 if blank != 1 else 2
+    for ids in same_lane_ids(vocab, blank):
+        a = t.copy(); a[list(ids)] = top; extra.append(a)                                   # ... as the maximum
+        a = t.copy(); a[list(ids)] = top; a[single] = top + 1.0; extra.append(a)            # ... as the second best (offer at k >= 1)
+        a = t.copy(); a[list(ids)] = top; a[blank] = top + 5.0; extra.append(a)
     extra.append(np.full(vocab, 2.5, np.float32))                                            # a row of equal values
     extra.append(np.full(vocab, -300.0, np.float32))
     extra.append(np.full(vocab, np.nan, np.float32))                                         # a NaN row
     return np.concatenate(rows + [np.stack(extra)]).astype(np.float32)
 
 
-@pytest.mark.parametrize("which", ["tiny", "medium", "v0", "vocab1100"])
+def check_kernel_against_float64(gm, what, ks=(1, 4, 8)):
+    """aprilx_run_confidence on case_rows against confidence_ref (also what tests/device_optin_mutant_worker.py runs against every
+    mutant of confidence_row); returns the worst error / bound ratio"""
+    vocab, blank = gm.dims.vocab, gm.dims.blank_id
+    rows = case_rows(vocab, blank, np.random.default_rng(vocab))
+    worst = 0.0
+    for k in ks:
+        out = gm.run_confidence(rows, k)
+        for i in range(rows.shape[0]):
+            assert out[i].size == C.sizeof(A_ffi().AprilxTokenInfo) and out[i].eval_index == i
+            worst = max(worst, R.check_info(out[i], rows[i], blank, k, "%s row %d K=%d" % (what, i, k)))
+        for ids in same_lane_ids(vocab, blank):                     # (stated here as well: the lower id of a same-lane tie comes first)
+            masked = rows.copy(); masked[:, blank] = -np.inf
+            hit = [i for i in range(rows.shape[0]) if list(np.flatnonzero(masked[i] == masked[i].max())) == list(ids)]
+            assert len(hit) == 2
+            for i in hit:
+                assert [int(out[i].alt_id[j]) for j in range(min(k, len(ids)))] == list(ids)[:k], (what, i, k, ids)
+        eq = rows.shape[0] - 3                                     # the row of equal values: lse = v + log V
+        assert abs(float(out[eq].lse) - (2.5 + np.log(vocab))) <= R.lse_bound(2.5 + np.log(vocab))
+        assert int(out[eq].n_alt) == min(k, vocab - 1) and [int(out[eq].alt_id[j]) for j in range(out[eq].n_alt)] == [n for n in range(vocab) if n != blank][:k]
+        assert int(out[rows.shape[0] - 1].n_alt) == 0 and np.isnan(out[rows.shape[0] - 1].lse)
+    return worst
+
+
+VOCAB = dict(tiny=40, medium=131, v0=500, vocab1100=1100, **{k: v[0] for k, v in BM.MODELS.items()})
+
+
+@pytest.mark.parametrize("which", ["tiny", "medium", "v0", "vocab1100"] + list(BM.MODELS))
 def test_kernel_against_float64(which, request, model_dir):
     import april_asr_amd as A
     from april_asr_amd import synth_model as SM
@@ -119,24 +179,14 @@ def test_kernel_against_float64(which, request, model_dir):
         path = str(model_dir / "tiny_vocab1100.april")
         SM.write_model(path, dict(SM.TINY_DIMS, vocab=1100))
     else:
-        path = request.getfixturevalue(which + "_model")["path"]
+        path = BM.model_info(which, request)["path"]
     gm = A.Model(path)
-    vocab, blank = gm.dims.vocab, gm.dims.blank_id
-    assert vocab == dict(tiny=40, medium=131, v0=500, vocab1100=1100)[which]
-    rows = case_rows(vocab, blank, np.random.default_rng(vocab))
-    worst = 0.0
-    for k in (1, 4, 8):
-        out = gm.run_confidence(rows, k)
-        for i in range(rows.shape[0]):
-            assert out[i].size == C.sizeof(A_ffi().AprilxTokenInfo) and out[i].eval_index == i
-            worst = max(worst, R.check_info(out[i], rows[i], blank, k, "%s row %d K=%d" % (which, i, k)))
-        eq = rows.shape[0] - 3                                     # the row of equal values: lse = v + log V
-        assert abs(float(out[eq].lse) - (2.5 + np.log(vocab))) <= R.lse_bound(2.5 + np.log(vocab))
-        assert int(out[eq].n_alt) == min(k, vocab - 1) and [int(out[eq].alt_id[j]) for j in range(out[eq].n_alt)] == [n for n in range(vocab) if n != blank][:k]
-        assert int(out[rows.shape[0] - 1].n_alt) == 0 and np.isnan(out[rows.shape[0] - 1].lse)
+    vocab = gm.dims.vocab
+    assert vocab == VOCAB[which] and gm.dims.blank_id == BM.MODELS.get(which, (0, 0))[1]
+    worst = check_kernel_against_float64(gm, which)
     print("%s (V = %d): worst error = %.3f of the bound" % (which, vocab, worst))
     with pytest.raises(ValueError):
-        gm.run_confidence(rows[:1], 9)
+        gm.run_confidence(case_rows(vocab, gm.dims.blank_id, np.random.default_rng(vocab))[:1], 9)
     gm.close()
 
 

@@ -184,6 +184,29 @@ def test_session_transcript_tiny(gpu_tiny, orc_tiny, chunk):
     assert_same_transcript(want, got)
 
 
+def test_session_transcript_with_the_blank_at_the_last_id(request):
+    """blank39 (the blank is token 39, token 0 is "2"): a live session against the oracle -- the initial context (zero_slot_kernel,
+    dec_rows_kernel), the decoder table's row [blank][blank], the 2.2 s silence reset that clears the context to id 39, the flush."""
+    import april_asr_amd as A
+    import blank_models as BM
+    from oracle import orc_py as O
+    info = BM.model_info("blank39", request)
+    gm, om = A.Model(info["path"]), O.Model(info["path"])
+    assert gm.dims.blank_id == 39 and gm.token(0) == "2"
+    pcm = speech_like_pcm(4.0, seed=1, silence=(1.2, 3.8))
+    want, lg0, n0 = run_oracle(om, pcm, 1600)
+    got, lg1, n1 = run_gpu(gm, pcm, 1600)
+    assert n0 == n1 >= 10
+    assert lg0.shape == lg1.shape and np.abs(lg0 - lg1).max() < 1e-3
+    assert_same_transcript(want, got)
+    kinds = [t for t, _ in got]
+    assert 4 in kinds and kinds.index(4) < len(kinds) - 1, "the run must reach the silence reset before the flush (a SILENCE event, then more results)"
+    assert sum(len(toks) for t, toks in got if t == 2) >= 1, "the run must deliver a token"
+    assert all(tok[0] != b"<blk>" for _, toks in got for tok in toks)
+    assert gm.stats().replay_mismatch == 0
+    gm.close(); om.close()
+
+
 def test_session_transcript_tiny_async(gpu_tiny, orc_tiny):
     from oracle import orc_py as O
     pcm = O.lcg_pcm16_fast(16000 * 3, seed=4)
@@ -604,13 +627,31 @@ def test_decoder_table_equals_decoder_network(tiny_model, gpu_tiny):
     """The decoder output of EVERY 2-token context is computed once at load (Engine::build_dec_table) and the joiner reads the
     row of a session's context.  A model loaded with the table disabled runs the decoder network per context change as in
     round 1: decoder outputs, every joiner logit and every callback of the two are equal BIT FOR BIT."""
+    check_decoder_table(tiny_model["path"], gpu_tiny)
+
+
+def test_decoder_table_equals_decoder_network_with_the_blank_at_the_last_id(request):
+    """... on blank39: the initial and the cleared context are the table's row [39][39]"""
+    import april_asr_amd as A
+    import blank_models as BM
+    info = BM.model_info("blank39", request)
+    gm = A.Model(info["path"])
+    assert gm.dims.blank_id == 39
+    try:
+        check_decoder_table(info["path"], gm)
+    finally:
+        gm.close()
+
+
+def check_decoder_table(path, with_table):
     import os
     import april_asr_amd as A
     from oracle import orc_py as O
+    gpu_tiny = with_table
     old = os.environ.get("APRIL_DEC_TABLE_MB")
     os.environ["APRIL_DEC_TABLE_MB"] = "0"
     try:
-        direct = A.Model(tiny_model["path"])
+        direct = A.Model(path)
     finally:
         if old is None:
             del os.environ["APRIL_DEC_TABLE_MB"]

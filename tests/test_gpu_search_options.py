@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "gol
 import search_options_cases as G  # noqa: E402
 import search_options_ref as R  # noqa: E402
 import search_options_worker as W  # noqa: E402
+import blank_models as BM  # noqa: E402
 from conftest import speech_like_pcm  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -56,18 +57,28 @@ def tiny(tiny_model):
 
 
 # ---------------------------------------------------------------- 1. given rows: with, without and with default options in one launch
-@pytest.mark.parametrize("which", ["tiny", "vocab1100"])
-def test_mixed_rows_in_one_launch(which, tiny_model, model_dir):
-    """V = 40: three of the four waves hold no candidate; V = 1100: more than one logit per lane"""
+@pytest.mark.parametrize("which", ["tiny", "vocab1100", "blank64", "blank255", "blank1050"])
+def test_mixed_rows_in_one_launch(which, tiny_model, model_dir, request):
+    """V = 40: three of the four waves hold no candidate; V = 1100: more than one logit per lane; blank64 / blank255 / blank1050: the
+    blank logit in another wave than wave 0, in the last lane, past the first stride"""
     import april_asr_amd as A
     from april_asr_amd import synth_model as SM
     path = tiny_model["path"]
     if which == "vocab1100":
         path = str(model_dir / "tiny_vocab1100_so.april")
         SM.write_model(path, dict(SM.TINY_DIMS, vocab=1100))
+    elif which in BM.MODELS:
+        path = BM.model_info(which, request)["path"]
     gm = A.Model(path)
+    assert (gm.dims.vocab, gm.dims.blank_id) == dict(tiny=(40, 0), vocab1100=(1100, 0), **BM.MODELS)[which]
+    check_mixed_rows(gm)
+    gm.close()
+
+
+def check_mixed_rows(gm):
+    """rows with, without and with default options in one launch of the OPT forms against search_options_ref and aprilx_run_decide
+    (also what tests/device_optin_mutant_worker.py runs against every mutant of the OPT lines)"""
     V, blank = gm.dims.vocab, gm.dims.blank_id
-    assert V == (40 if which == "tiny" else 1100)
     cls = R.token_classes(texts_of(gm))
     rng = np.random.default_rng(V)
     n = 16
@@ -97,17 +108,36 @@ def test_mixed_rows_in_one_launch(which, tiny_model, model_dir):
             assert list(st[i]) == s.state(), (step, i, o)
             custom += rec[i].tobytes() != plain[i].tobytes() or st[i].tobytes() != pst[i].tobytes()
     assert custom > 0, "the rows with options of their own must decide differently somewhere"
-    gm.close()
 
 
 # ---------------------------------------------------------------- 2. the hand-derived cases on the device
-@pytest.mark.parametrize("case", [c for c in G.CASES if c["device"]], ids=[c["name"] for c in G.CASES if c["device"]])
+DEVICE_CASES = [c for c in G.CASES if c["device"]]
+
+
+@pytest.mark.parametrize("case", DEVICE_CASES, ids=[c["name"] for c in DEVICE_CASES])
 def test_device_matches_hand_derived(tiny, tiny_model, case):
     import april_asr_amd as A
-    gm = tiny
-    V, blank = gm.dims.vocab, gm.dims.blank_id
-    sym = W.symbols(tiny_model["tokens"])
     host = A.Model.load_host_only(tiny_model["path"])
+    check_device_case(tiny, host, case, W.symbols(tiny_model["tokens"]))
+    host.close()
+
+
+def test_device_matches_hand_derived_with_the_blank_at_the_last_id(request):
+    """every device case on blank39 in one test: the rows with and without options, the host state machine beside them"""
+    import april_asr_amd as A
+    info = BM.model_info("blank39", request)
+    gm, host = A.Model(info["path"]), A.Model.load_host_only(info["path"])
+    assert gm.dims.blank_id == 39
+    for case in DEVICE_CASES:
+        check_device_case(gm, host, case, W.symbols(info["tokens"]))
+    host.close(); gm.close()
+
+
+def check_device_case(gm, host, case, sym):
+    """one hand-derived case on the device, beside a row without options and beside the host state machine (also what
+    tests/device_optin_mutant_worker.py runs against every mutant of the OPT lines)"""
+    V, blank = gm.dims.vocab, gm.dims.blank_id
+    assert sym["<blk>"] == blank
     g = W.ProductGreedy(host, case["opts"])
     o = None if case["opts"] is None else (case["opts"][0], case["opts"][1])
     st = np.array([[blank, blank, -1, 0]] * 2, np.int32)
@@ -125,13 +155,16 @@ def test_device_matches_hand_derived(tiny, tiny_model, case):
         h_blank, h_ctx = g.step(sym[t], mx, bl, early, now)
         assert h_blank == exp[0] and list(h_ctx) == list(st[0][:2]), (case["name"], i)
     assert g.events == W.want_events(case, sym)
-    g.close(); host.close()
+    g.close()
 
 
 # ---------------------------------------------------------------- 3. with bias sets: back to the root at the session's own E
 @pytest.mark.parametrize("strict", [False, True])
 def test_bias_state_returns_to_the_root_at_E(tiny, strict):
-    gm = tiny
+    check_bias_state_returns_to_the_root_at_E(tiny, strict)
+
+
+def check_bias_state_returns_to_the_root_at_E(gm, strict):
     texts, V, blank = texts_of(gm), gm.dims.vocab, gm.dims.blank_id
     words = [i for i, t in enumerate(texts) if t[:1] == b" " and i != blank]
     a, b = words[3], words[5]

@@ -12,6 +12,7 @@ import search_options_cases as G  # noqa: E402
 import state_machine_cases as SMC  # noqa: E402
 
 import april_asr_amd as A  # noqa: E402
+import blank_models as BM  # noqa: E402
 import search_options_ref as R  # noqa: E402
 import search_options_worker as W  # noqa: E402
 
@@ -40,16 +41,34 @@ def test_the_cases_cover_what_the_contract_names():
     assert np.float32(np.float32(G.UP_6_5) - np.float32(1.5)) == np.nextafter(np.float32(5.0), np.float32(np.inf))
 
 
-@pytest.mark.parametrize("case", G.CASES, ids=[c["name"] for c in G.CASES])
-def test_product_matches_hand_derived(built, host_model, sym, case):
+CASE_PARAMS = BM.params(G.CASES, [c["name"] for c in G.CASES], ["blank39"])
+
+
+@pytest.fixture(scope="module")
+def blank39(request):
+    info = BM.model_info("blank39", request)
+    m = A.Model.load_host_only(info["path"])
+    assert m.dims.blank_id == 39
+    yield dict(info, model=m, sym=W.symbols(info["tokens"]))
+    m.close()
+
+
+@pytest.mark.parametrize("case,which", CASE_PARAMS)
+def test_product_matches_hand_derived(built, host_model, sym, blank39, case, which):
+    if which == "blank39":
+        host_model, sym = blank39["model"], blank39["sym"]
+        assert sym["<blk>"] == 39
     W.check_product_case(case, host_model, sym)
 
 
-@pytest.mark.parametrize("case", G.CASES, ids=[c["name"] for c in G.CASES])
-def test_reference_statement_matches_hand_derived(tiny_model, sym, case):
+@pytest.mark.parametrize("case,which", CASE_PARAMS)
+def test_reference_statement_matches_hand_derived(tiny_model, sym, blank39, case, which):
     """tests/search_options_ref.py (what the GPU tests replay live sessions with) on the same cases: events, decisions, device state"""
-    cls = R.token_classes(tiny_model["tokens"])
-    g, s = R.Greedy(cls, 0, case["opts"]), R.Search(cls, 0, case["opts"])
+    info = blank39 if which == "blank39" else dict(tiny_model, blank=0)
+    sym = blank39["sym"] if which == "blank39" else sym
+    blank = info["blank"]
+    cls = R.token_classes(info["tokens"])
+    g, s = R.Greedy(cls, blank, case["opts"]), R.Search(cls, blank, case["opts"])
     for i, ((t, mx, bl, early, now), exp) in enumerate(zip(case["rounds"], case["expect"])):
         is_blank = g.step(sym[t], mx, bl, early, now)
         d_blank, _, changed = s.step(sym[t], mx, bl, early, now)

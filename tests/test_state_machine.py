@@ -14,6 +14,8 @@ import april_asr_amd as A
 from april_asr_amd import _ffi
 from oracle import orc_py as O
 
+import blank_models as BM
+
 PARTIAL, FINAL, SILENCE = 1, 2, 4
 
 
@@ -93,13 +95,6 @@ def run_product(model, triples, n_chunks, finish):
     return ev, pos
 
 
-@pytest.fixture(scope="module")
-def host_model(tiny_model):
-    m = A.Model.load_host_only(tiny_model["path"])
-    yield m
-    m.close()
-
-
 def tok(tokens, text):
     return tokens.index(text)
 
@@ -176,19 +171,24 @@ def test_hand_derived_punctuation_and_digits(built, tiny_model):
     o.close()
 
 
-def random_triples(rng, vocab, n, special_ids):
+def random_triples(rng, vocab, n, special_ids, blank=0):
+    """`blank`: the id no triple names as its token.  The draws are those of blank = 0 (1 .. vocab - 1), mapped onto the ids without
+    the blank, so the default sequences are what they always were."""
+    def tok():
+        i = int(rng.randint(1, vocab))
+        return i if blank == 0 or i > blank else i - 1
     out = []
-    prev = 1
+    prev = 1 if blank != 1 else 0
     while len(out) < n:
         mode = rng.randint(0, 10)
         if mode == 0:                                   # long silence
-            out += [(int(rng.randint(1, vocab)), float(rng.uniform(-30, -10)), float(rng.uniform(5, 10)))] * int(rng.randint(50, 70))
+            out += [(tok(), float(rng.uniform(-30, -10)), float(rng.uniform(5, 10)))] * int(rng.randint(50, 70))
             continue
         if mode == 1:                                   # burst of tokens without word boundaries is possible (overflow path)
             for _ in range(int(rng.randint(5, 90))):
-                out.append((int(rng.randint(1, vocab)), float(rng.uniform(2, 8)), float(rng.uniform(-5, 1))))
+                out.append((tok(), float(rng.uniform(2, 8)), float(rng.uniform(-5, 1))))
             continue
-        idx = prev if rng.rand() < 0.25 else (int(rng.choice(special_ids)) if rng.rand() < 0.3 else int(rng.randint(1, vocab)))
+        idx = prev if rng.rand() < 0.25 else (int(rng.choice(special_ids)) if rng.rand() < 0.3 else tok())
         prev = idx
         bl = float(rng.uniform(-2, 12))
         mx = bl + float(rng.choice([-6, -4.2, -3.8, -3.4, -1.2, -0.8, -0.2, 0.2, 3.0])) + float(rng.uniform(-0.1, 0.1))
@@ -196,13 +196,17 @@ def random_triples(rng, vocab, n, special_ids):
     return out
 
 
-@pytest.mark.parametrize("seed", [0, 1, 2, 3])
-def test_product_greedy_matches_oracle(built, tiny_model, host_model, seed):
+@pytest.mark.parametrize("seed,which", BM.params([0, 1, 2, 3], [0, 1, 2, 3], [("blank39", [0])]))
+def test_product_greedy_matches_oracle(built, request, seed, which):
+    info = BM.model_info(which, request)
+    host_model = A.Model.load_host_only(info["path"])
+    assert host_model.dims.blank_id == info["blank"]
     rng = np.random.RandomState(seed)
-    special = [tiny_model["tokens"].index(t) for t in (".", ",", "?", "!", " 1", "2", " 3", "4")]
-    triples = random_triples(rng, len(tiny_model["tokens"]), 4000, special)
+    special = [info["tokens"].index(t) for t in (".", ",", "?", "!", " 1", "2", " 3", "4")]
+    triples = random_triples(rng, len(info["tokens"]), 4000, special, blank=info["blank"])
+    assert all(t[0] != info["blank"] for t in triples)
     n_chunks = 1200
-    o = ScriptedOracle(tiny_model["path"], triples)
+    o = ScriptedOracle(info["path"], triples)
     total = o.run_chunks(n_chunks, flush=True)
     got, used = run_product(host_model, triples, total, finish=True)
     assert used == o.pos
@@ -212,3 +216,4 @@ def test_product_greedy_matches_oracle(built, tiny_model, host_model, seed):
     for a, b in zip(o.events, got):
         assert a == b
     o.close()
+    host_model.close()

@@ -17,6 +17,7 @@ import state_machine_cases as G  # noqa: E402
 import april_asr_amd as A  # noqa: E402
 from april_asr_amd import _ffi  # noqa: E402
 from oracle import orc_py as O  # noqa: E402
+import blank_models as BM  # noqa: E402
 from test_state_machine import ScriptedOracle  # noqa: E402
 
 KIND = {"PARTIAL": 1, "FINAL": 2, "SILENCE": 4}
@@ -31,7 +32,7 @@ def symbols(tokens):
     w2 = first(lambda t: t.startswith(" ") and len(t) > 2 and not t[1].isdigit(), (w1,))
     c1 = first(lambda t: not t.startswith(" ") and t.isalpha() and len(t) > 1)
     c2 = first(lambda t: not t.startswith(" ") and t.isalpha() and len(t) > 1, (c1,))
-    return {"W1": w1, "W2": w2, "C1": c1, "C2": c2, "DOT": tokens.index("."), "COMMA": tokens.index(","), "D2": tokens.index("2"), "<blk>": 0}
+    return {"W1": w1, "W2": w2, "C1": c1, "C2": c2, "DOT": tokens.index("."), "COMMA": tokens.index(","), "D2": tokens.index("2"), "<blk>": tokens.index("<blk>")}
 
 
 def resolve_events(case, sym, post_base):
@@ -193,21 +194,36 @@ def run_product_case(case, model, sym):
 
 
 @pytest.fixture(scope="module")
-def host_model(tiny_model):
-    m = A.Model.load_host_only(tiny_model["path"])
-    yield m
-    m.close()
+def host_models():
+    """host-only models by path, loaded once per module"""
+    loaded = {}
+
+    def get(path):
+        if path not in loaded:
+            loaded[path] = A.Model.load_host_only(path)
+        return loaded[path]
+    yield get
+    for m in loaded.values():
+        m.close()
 
 
-@pytest.mark.parametrize("case", G.CASES, ids=[c["name"] for c in G.CASES])
-def test_oracle_matches_hand_derived(built, tiny_model, case):
-    sym = symbols(tiny_model["tokens"])
-    check_oracle_case(case, tiny_model["path"], sym)
+CASE_PARAMS = BM.params(G.CASES, [c["name"] for c in G.CASES], ["blank39"])
 
 
-@pytest.mark.parametrize("case", G.CASES, ids=[c["name"] for c in G.CASES])
-def test_product_host_state_machine_matches_hand_derived(built, tiny_model, host_model, case):
-    sym = symbols(tiny_model["tokens"])
+@pytest.mark.parametrize("case,which", CASE_PARAMS)
+def test_oracle_matches_hand_derived(built, request, case, which):
+    info = BM.model_info(which, request)
+    sym = symbols(info["tokens"])
+    assert sym["<blk>"] == info["blank"]
+    check_oracle_case(case, info["path"], sym)
+
+
+@pytest.mark.parametrize("case,which", CASE_PARAMS)
+def test_product_host_state_machine_matches_hand_derived(built, request, host_models, case, which):
+    info = BM.model_info(which, request)
+    sym = symbols(info["tokens"])
+    host_model = host_models(info["path"])
+    assert host_model.dims.blank_id == info["blank"] == sym["<blk>"]
     ev, decisions, post_base = run_product_case(case, host_model, sym)
     want = resolve_events(case, sym, post_base or 0)
     assert [e[0] for e in ev] == [e[0] for e in want]
