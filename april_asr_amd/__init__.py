@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _ffi
 
-__all__ = ["Result", "Token", "Model", "Session", "SessionGroup", "Bias", "resampler_taps", "decode_host"]
+__all__ = ["Result", "Token", "Model", "Session", "SessionGroup", "Bias", "VadEvent", "resampler_taps", "decode_host", "vad_plan", "vad_host", "vad_events_host"]
 
 
 class Result(IntEnum):
@@ -28,6 +28,23 @@ class Result(IntEnum):
     FINAL_RECOGNITION = 2     # final; the next call starts from an empty list
     ERROR_CANT_KEEP_UP = 3    # asynchronous sessions: ingest ring overflowed, audio dropped
     SILENCE = 4               # some silence passed; empty token list
+
+
+class VadEvent:
+    """A voice-activity event of a session (Session(vad=...)): `kind` is VadEvent.SPEECH_START or VadEvent.SPEECH_END, `time_ms` the
+    position in the session's audio on the frame clock."""
+    SPEECH_START, SPEECH_END = 1, 2
+    __slots__ = ("kind", "time_ms")
+
+    def __init__(self, kind, time_ms):
+        self.kind = int(kind)
+        self.time_ms = int(time_ms)
+
+    def __eq__(self, other):
+        return isinstance(other, VadEvent) and (self.kind, self.time_ms) == (other.kind, other.time_ms)
+
+    def __repr__(self):
+        return "VadEvent(%s, %d)" % ("SPEECH_START" if self.kind == 1 else "SPEECH_END", self.time_ms)
 
 
 class Token:
@@ -319,6 +336,31 @@ class Model:
             raise ValueError("aprilx_run_decide_opts refused the call")
         return rec, st, bs
 
+    def run_vad(self, options, rows_list, first_row=None, states=None):
+        """vad_kernel alone (aprilx_run_vad; tests): run r with options[r] (dicts / None as Session.set_vad) over rows_list[r] [n][mel], all
+        in ONE launch; first_row[r] places the run in its scratch ring of max(n) rows, states[r] (AprilxVadState) is the state the run starts
+        from (None: reset).  Returns ([bytes], [energies], [states after the runs])."""
+        k = len(rows_list)
+        opts = (_ffi.AprilxVadOptions * k)(*[_vad_options(o) for o in options])
+        n = np.array([len(r) for r in rows_list], np.int32)
+        fr = np.zeros(k, np.int32) if first_row is None else np.ascontiguousarray(first_row, np.int32)
+        rows = np.ascontiguousarray(np.concatenate([np.asarray(r, np.float32).reshape(len(r), -1) for r in rows_list]), np.float32)
+        assert rows.shape[1] == self.dims.mel
+        st = (_ffi.AprilxVadState * k)(*(states if states is not None else [vad_reset_state() for _ in range(k)]))
+        b = np.zeros(int(n.sum()), np.uint8); e = np.zeros(int(n.sum()), np.float32)
+        rc = self._L.aprilx_run_vad(self._handle, k, C.addressof(opts), n.ctypes.data, fr.ctypes.data, rows.ctypes.data, C.addressof(st), b.ctypes.data, e.ctypes.data)
+        if rc != 0:
+            raise ValueError("aprilx_run_vad refused its arguments")
+        cuts = np.cumsum(n)[:-1]
+        return np.split(b, cuts), np.split(e, cuts), [st[i] for i in range(k)]
+
+    def vad_stats(self, device_index: int = 0):
+        """(launches, frames, ms): VAD launches of one GPU's engine, the frames they covered, and (while profiling) the kernel's time"""
+        l, f, ms = C.c_uint64(0), C.c_uint64(0), C.c_double(0)
+        if self._L.aprilx_model_vad_stats(self._handle, device_index, C.byref(l), C.byref(f), C.byref(ms)) != 0:
+            raise ValueError("no such device")
+        return int(l.value), int(f.value), float(ms.value)
+
     def stats(self, device_index: int = 0):
         s = _ffi.AprilxStats()
         self._L.aprilx_model_stats(self._handle, device_index, C.byref(s))
@@ -408,11 +450,20 @@ def _dispatch(userdata, result_type, count, tokens):
 _HANDLER = _ffi.HANDLER(_dispatch)
 
 
+def _dispatch_vad(userdata, kind, time_ms):
+    sess = C.cast(userdata, C.py_object).value
+    if sess.vad_callback is not None:
+        sess.vad_callback(VadEvent(kind, time_ms))
+
+
+_VAD_HANDLER = _ffi.VAD_HANDLER(_dispatch_vad)
+
+
 class Session:
     def __init__(self, model: Model, callback: Callable[[Result, List[Token]], None], asynchronous: bool = False,
                  no_rt: bool = False, speaker_name: str = "", raw_events: bool = False, counters=None, input_sample_rate=None,
                  alternatives=None, bias=None, endpoint_silence_ms=None, blank_penalty=None, max_utterance_ms=None,
-                 input_format=None, channels: int = 1, channel: int = 0):
+                 input_format=None, channels: int = 1, channel: int = 0, vad=None, vad_callback=None):
         """`counters`: a uint64 ndarray of 6 entries; when given, results are only counted by a C handler inside the
         library (calls, partial, final, cant_keep_up, silence, tokens) and `callback` is never invoked.
         `input_sample_rate`: the rate of the PCM this session will receive (converted to the model's rate on the GPU); None: the
@@ -422,8 +473,11 @@ class Session:
         `bias`: a Bias (Model.bias): the search boosts the tokens that continue one of its phrases (set_bias); None: off.
         `endpoint_silence_ms`, `blank_penalty`, `max_utterance_ms`: the session's search options (set_search_options); all None: none.
         `input_format`, `channels`, `channel`: the format of the audio this session will receive (set_input_format): "mulaw", "alaw",
-        "f32" or "s16", 1..8 interleaved channels, the channel to take or -1 for their downmix; None: mono PCM16."""
+        "f32" or "s16", 1..8 interleaved channels, the channel to take or -1 for their downmix; None: mono PCM16.
+        `vad`, `vad_callback`: True or a dict of options (set_vad) switches the voice-activity detector on; `vad_callback` receives one
+        VadEvent per speech start / end, on the thread that delivers the session's results."""
         self._L = model._L
+        self.vad_callback = vad_callback
         self.info_log = None      # tests: a list that receives (type, [the token's AprilxTokenInfo as bytes, or None]) per result
         self.model = model
         self.callback = callback
@@ -455,6 +509,37 @@ class Session:
             self.set_bias(bias)
         if endpoint_silence_ms is not None or blank_penalty is not None or max_utterance_ms is not None:
             self.set_search_options(endpoint_silence_ms, blank_penalty, max_utterance_ms)
+        if vad:
+            self.set_vad(vad)
+
+    def set_vad(self, options=True, callback=None) -> None:
+        """Voice activity for this session (aprilx_session_set_vad): True for the defaults, or a dict with any of
+        band_lo_hz, band_hi_hz, onset_db, offset_db, onset_ms, hangover_ms, min_energy; None / False switches it off.  `callback`
+        replaces the session's vad_callback.  Allowed right after creation and after a completed flush; the detector starts afresh."""
+        if callback is not None:
+            self.vad_callback = callback
+        if not options:
+            rc = self._L.aprilx_session_set_vad(self._handle, None, C.cast(None, _ffi.VAD_HANDLER), None)
+        else:
+            rc = self._L.aprilx_session_set_vad(self._handle, C.byref(_vad_options(options)), _VAD_HANDLER, id(self))
+        if rc != 0:
+            raise ValueError("voice-activity options %r refused (a value out of range, or audio fed since the last flush)" % (options,))
+
+    def vad_info(self):
+        """None when the detector is off, else a dict: the options, the band [b0, b1), onset_frames, hangover_frames, frames_seen,
+        speech_frames, in_speech, segments (aprilx_session_vad).  Waits for the session to be idle."""
+        o, i = _ffi.AprilxVadOptions(), _ffi.AprilxVadInfo()
+        if self._L.aprilx_session_vad(self._handle, C.byref(o), C.byref(i)) != 1:
+            return None
+        d = {n: getattr(o, n) for n in _VAD_FIELDS}
+        d.update({n: int(getattr(i, n)) for n in ("b0", "b1", "onset_frames", "hangover_frames", "frames_seen", "speech_frames", "in_speech", "segments")})
+        return d
+
+    def frames_seen(self) -> int:
+        """real frames of the session since its creation (the frame clock of the voice-activity events)"""
+        i = _ffi.AprilxVadInfo()
+        self._L.aprilx_session_vad(self._handle, None, C.byref(i))
+        return int(i.frames_seen)
 
     def _on_result(self, result_type, count, tokens):
         if self.info_log is not None:
@@ -681,6 +766,65 @@ class SessionGroup:
 
 ENCODINGS = {"s16": 0, "mulaw": 1, "alaw": 2, "f32": 3}      # APRILX_ENC_*
 _ENC_NAMES = {v: k for k, v in ENCODINGS.items()}
+
+
+_VAD_FIELDS = ("band_lo_hz", "band_hi_hz", "onset_db", "offset_db", "onset_ms", "hangover_ms", "min_energy")
+_VAD_DEFAULTS = dict(band_lo_hz=200.0, band_hi_hz=4000.0, onset_db=5.0, offset_db=3.0, onset_ms=50, hangover_ms=300, min_energy=-12.0)
+
+
+def _vad_options(options):
+    if isinstance(options, _ffi.AprilxVadOptions):
+        return options
+    d = dict(_VAD_DEFAULTS)
+    if isinstance(options, dict):
+        unknown = set(options) - set(_VAD_FIELDS)
+        if unknown:
+            raise ValueError("unknown voice-activity options %r" % sorted(unknown))
+        d.update(options)
+    return _ffi.AprilxVadOptions(C.sizeof(_ffi.AprilxVadOptions), float(d["band_lo_hz"]), float(d["band_hi_hz"]), float(d["onset_db"]),
+                                 float(d["offset_db"]), int(d["onset_ms"]), int(d["hangover_ms"]), float(d["min_energy"]), 0)
+
+
+def vad_reset_state():
+    """the detector's reset state (AprilxVadState)"""
+    inf = float("inf")
+    return _ffi.AprilxVadState(0.0, inf, (C.c_float * 8)(*([inf] * 8)), 0, 0, 0, 0, 1, 0)
+
+
+def vad_plan(mel, sample_rate: int, frame_shift_ms: int, options=True):
+    """The detector's plan (AprilxVadPlan) from a mel table [nbins][nfft_bins] (Model.fbank_tables) on the host (aprilx_vad_plan_tables);
+    ValueError when the options are refused."""
+    m = np.ascontiguousarray(mel, np.float32)
+    plan = _ffi.AprilxVadPlan()
+    if _ffi.lib().aprilx_vad_plan_tables(m.ctypes.data, m.shape[0], m.shape[1], int(sample_rate), int(frame_shift_ms), C.byref(_vad_options(options)),
+                                         C.byref(plan)) != 0:
+        raise ValueError("voice-activity options %r refused" % (options,))
+    return plan
+
+
+def vad_host(plan, rows, state=None):
+    """The contract on the host (aprilx_vad_host): rows [n][nbins] through the detector from `state` (updated in place; None: reset).
+    Returns (bytes [n] uint8, energies [n] float32, state)."""
+    r = np.ascontiguousarray(rows, np.float32)
+    r = r.reshape(len(r), -1)
+    st = state if state is not None else vad_reset_state()
+    b = np.zeros(len(r), np.uint8); e = np.zeros(len(r), np.float32)
+    if _ffi.lib().aprilx_vad_host(C.byref(plan), len(r), r.shape[1] if len(r) else max(1, plan.b1), r.ctypes.data, C.byref(st), b.ctypes.data, e.ctypes.data) != 0:
+        raise ValueError("aprilx_vad_host refused its arguments")
+    return b, e, st
+
+
+def vad_events_host(plan, frame_shift_ms: int, t0: int, data, last_bit: int = 0):
+    """The events that follow from the bytes of frames [t0, t0 + n) (aprilx_vad_events_host): ([VadEvent], new last bit)"""
+    b = np.ascontiguousarray(data, np.uint8)
+    cap = len(b) + 1
+    kinds = np.zeros(cap, np.int32); times = np.zeros(cap, np.uint64)
+    last = C.c_int32(int(last_bit))
+    n = _ffi.lib().aprilx_vad_events_host(C.byref(plan), int(frame_shift_ms), int(t0), b.ctypes.data, len(b), C.byref(last), kinds.ctypes.data,
+                                          times.ctypes.data, cap)
+    if n < 0:
+        raise ValueError("aprilx_vad_events_host refused its arguments")
+    return [VadEvent(kinds[i], times[i]) for i in range(n)], int(last.value)
 
 
 def _input_format(encoding, channels=1, channel=0):

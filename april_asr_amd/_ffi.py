@@ -61,6 +61,29 @@ class AprilxLoadInfo(C.Structure):
                 ("ranks", C.c_int32), ("used_rccl", C.c_int32)]
 
 
+class AprilxVadOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("band_lo_hz", C.c_float), ("band_hi_hz", C.c_float), ("onset_db", C.c_float), ("offset_db", C.c_float),
+                ("onset_ms", C.c_uint32), ("hangover_ms", C.c_uint32), ("min_energy", C.c_float), ("flags", C.c_uint32)]
+
+
+class AprilxVadInfo(C.Structure):
+    _fields_ = [("b0", C.c_int32), ("b1", C.c_int32), ("onset_frames", C.c_int32), ("hangover_frames", C.c_int32),
+                ("frames_seen", C.c_uint64), ("speech_frames", C.c_uint64), ("in_speech", C.c_uint32), ("segments", C.c_uint32)]
+
+
+class AprilxVadPlan(C.Structure):
+    _fields_ = [("b0", C.c_int32), ("b1", C.c_int32), ("inv_nb", C.c_float), ("thr_on", C.c_float), ("thr_off", C.c_float),
+                ("min_energy", C.c_float), ("onset_frames", C.c_int32), ("hangover_frames", C.c_int32)]
+
+
+class AprilxVadState(C.Structure):
+    _fields_ = [("s", C.c_float), ("cur", C.c_float), ("hist", C.c_float * 8), ("cnt", C.c_int32), ("pos", C.c_int32), ("st", C.c_int32),
+                ("run", C.c_int32), ("first", C.c_int32), ("reserved", C.c_int32)]
+
+
+VAD_HANDLER = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_uint64)
+
+
 class AprilxInputFormat(C.Structure):
     _fields_ = [("size", C.c_uint32), ("encoding", C.c_uint32), ("channels", C.c_uint32), ("channel", C.c_int32)]
 
@@ -86,6 +109,8 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_ramp_window", "aprilx_model_ramp_stats",
     "aprilx_session_set_input_format", "aprilx_session_input_format", "aprilx_session_feed_bytes", "aprilx_feed_many_bytes",
     "aprilx_decode_host", "aprilx_decode", "aprilx_model_decode_stats",
+    "aprilx_session_set_vad", "aprilx_session_vad", "aprilx_vad_plan_tables", "aprilx_vad_host", "aprilx_vad_events_host", "aprilx_run_vad",
+    "aprilx_model_vad_stats",
 ]
 
 _lib = None
@@ -183,6 +208,13 @@ def lib():
     L.aprilx_decode_host.argtypes = [C.POINTER(AprilxInputFormat), vp, sz, vp, sz]; L.aprilx_decode_host.restype = C.c_int64
     L.aprilx_decode.argtypes = [vp, C.POINTER(AprilxInputFormat), vp, sz, vp, sz]; L.aprilx_decode.restype = C.c_int64
     L.aprilx_model_decode_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]; L.aprilx_model_decode_stats.restype = C.c_int
+    L.aprilx_session_set_vad.argtypes = [vp, C.POINTER(AprilxVadOptions), VAD_HANDLER, vp]; L.aprilx_session_set_vad.restype = C.c_int
+    L.aprilx_session_vad.argtypes = [vp, C.POINTER(AprilxVadOptions), C.POINTER(AprilxVadInfo)]; L.aprilx_session_vad.restype = C.c_int
+    L.aprilx_vad_plan_tables.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(AprilxVadOptions), C.POINTER(AprilxVadPlan)]; L.aprilx_vad_plan_tables.restype = C.c_int
+    L.aprilx_vad_host.argtypes = [C.POINTER(AprilxVadPlan), C.c_int, C.c_int, vp, C.POINTER(AprilxVadState), vp, vp]; L.aprilx_vad_host.restype = C.c_int
+    L.aprilx_vad_events_host.argtypes = [C.POINTER(AprilxVadPlan), C.c_int, C.c_uint64, vp, sz, C.POINTER(C.c_int32), vp, vp, C.c_int]; L.aprilx_vad_events_host.restype = C.c_int
+    L.aprilx_run_vad.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]; L.aprilx_run_vad.restype = C.c_int
+    L.aprilx_model_vad_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]; L.aprilx_model_vad_stats.restype = C.c_int
     _lib = L
     return L
 

@@ -375,6 +375,8 @@ Engine::~Engine()
     for (void *p : {(void *)bias_set_h_, (void *)bias_desc_h_}) if (p) (void)hipHostFree(p);
     if (opt_d_) (void)hipFree(opt_d_);
     if (opt_h_) (void)hipHostFree(opt_h_);
+    for (void *p : {(void *)vad_state_d_, (void *)vad_out_d_}) if (p) (void)hipFree(p);
+    for (VadBlock &k : vad_blocks_) (void)hipHostFree(k.h);
     if (ws_g_) (void)hipFree(ws_g_);
     if (conv_wt_) (void)hipFree(conv_wt_);
     if (dec_table_) (void)hipFree(dec_table_);
@@ -673,10 +675,14 @@ void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<con
     const size_t n_raw_parts = n_dc ? dc_n_raw_parts_ : 0, n_raw = n_dc ? dc_n_raw_ : 0;
     const size_t raw_units = n_dc ? (n_raw + 1) / 2 + 8 : 0;      // the raw region in int16 units, with its alignment
     dc_n_ = 0;
+    const int n_vd = n_frames > 0 ? std::max(vad_n_, 0) : 0;
+    const VadDesc *vd = vad_desc_;
+    const size_t vd_frames = n_vd ? vad_pass_frames_ : 0;
+    vad_n_ = 0; vad_last_h_ = nullptr;
     if (n_frames <= 0) return;
     HIP_CHECK(hipSetDevice(cfg_.device));
     for (int i = 0; i < n_rs; ++i) rs[i].taps = resample_table(rs_specs_[i]);      // (uploaded at a conversion's first use)
-    if (n_frames > desc_cap_ || n_pcm + n_in + raw_units > pcm_cap_ || (size_t)n_rs > rs_cap_ || (size_t)n_dc > dc_cap_) {
+    if (n_frames > desc_cap_ || n_pcm + n_in + raw_units > pcm_cap_ || (size_t)n_rs > rs_cap_ || (size_t)n_dc > dc_cap_ || (size_t)n_vd > vd_cap_) {
         sync();
         HipLegacyLock regrow_guard;                   // (frees imply a device synchronisation: not beside another engine's capture; order: capture_mu_, then this)
         for (int b = 0; b < 2; ++b) {
@@ -687,16 +693,39 @@ void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<con
         pcm_cap_ = std::max({(n_pcm + n_in + raw_units) * 2, pcm_cap_, (size_t)1 << 16});
         rs_cap_ = std::max({(size_t)n_rs * 2, rs_cap_, n_rs ? (size_t)256 : (size_t)0});
         dc_cap_ = std::max({(size_t)n_dc * 2, dc_cap_, n_dc ? (size_t)256 : (size_t)0});
+        vd_cap_ = std::max({(size_t)n_vd * 2, vd_cap_, n_vd ? (size_t)256 : (size_t)0});
         // one staging buffer per flip: the PCM windows (model-rate regions, then the input-rate spans of resampled sessions), then
         // (16-byte aligned) the raw bytes of formatted sessions, then (16-byte aligned, right behind the samples of THIS call) the
-        // frame descriptors, the resample descriptors and the decode descriptors -> one host-to-device copy per call
+        // frame descriptors, the resample descriptors, the decode descriptors and the VAD descriptors -> one host-to-device copy per call
         const size_t units = pcm_cap_ + 8 + ((size_t)desc_cap_ * sizeof(FbankFrameDesc) + 1) / 2 + 8 + rs_cap_ * sizeof(ResampleDesc) / 2
-                             + 8 + dc_cap_ * sizeof(DecodeDesc) / 2;
+                             + 8 + dc_cap_ * sizeof(DecodeDesc) / 2 + 8 + vd_cap_ * sizeof(VadDesc) / 2;
         for (int b = 0; b < 2; ++b) {
             hs_pcm_[b] = hmalloc<int16_t>(units); ds_pcm_[b] = dmalloc<int16_t>(units);
             hs_desc_[b] = nullptr; ds_desc_[b] = nullptr;
             if (!fb_done_[b]) HIP_CHECK(hipEventCreateWithFlags(&fb_done_[b], hipEventDisableTiming));
         }
+    }
+    VadBlock *vblock = nullptr;
+    if (n_vd) {
+        // the first VAD pass of the engine allocates the per-slot records; the device's byte buffer grows behind a sync (earlier
+        // passes' copies read it); a pass takes a pinned block nobody holds, or a new one (warm-up only)
+        if (!vad_state_d_) vad_state_d_ = dmalloc<VadState>((size_t)cfg_.max_slots);
+        if (vd_frames > vad_out_cap_) {
+            sync();
+            HipLegacyLock guard;
+            if (vad_out_d_) (void)hipFree(vad_out_d_);
+            vad_out_cap_ = std::max<size_t>(vd_frames * 2, 4096);
+            vad_out_d_ = dmalloc<uint8_t>(vad_out_cap_);
+        }
+        for (VadBlock &k : vad_blocks_) if (!k.busy && k.cap >= vd_frames && (!vblock || k.cap < vblock->cap)) vblock = &k;
+        if (!vblock) {
+            VadBlock k;
+            k.cap = 4096; while (k.cap < vd_frames) k.cap *= 2;
+            k.h = hmalloc<uint8_t>(k.cap);
+            vad_blocks_.push_back(k);
+            vblock = &vad_blocks_.back();
+        }
+        vblock->busy = true;
     }
     const int b = fb_flip_;
     fb_flip_ ^= 1;
@@ -705,10 +734,12 @@ void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<con
     const size_t doff = (woff + n_raw + 15) / 16 * 16;                              // ... of the descriptors
     const size_t roff = (doff + (size_t)n_frames * sizeof(FbankFrameDesc) + 15) / 16 * 16;      // ... of the resample descriptors
     const size_t coff = (roff + (size_t)n_rs * sizeof(ResampleDesc) + 15) / 16 * 16;            // ... and of the decode descriptors
-    const size_t bytes = n_dc ? coff + (size_t)n_dc * sizeof(DecodeDesc)
+    const size_t voff = (coff + (size_t)n_dc * sizeof(DecodeDesc) + 15) / 16 * 16;              // ... and of the VAD descriptors
+    const size_t bytes = n_vd ? voff + (size_t)n_vd * sizeof(VadDesc) : n_dc ? coff + (size_t)n_dc * sizeof(DecodeDesc)
                               : (n_rs ? roff + (size_t)n_rs * sizeof(ResampleDesc) : doff + (size_t)n_frames * sizeof(FbankFrameDesc));
     char *hs = reinterpret_cast<char *>(hs_pcm_[b]);
     memcpy(hs + doff, desc, (size_t)n_frames * sizeof(FbankFrameDesc));
+    if (n_vd) memcpy(hs + voff, vd, (size_t)n_vd * sizeof(VadDesc));
     ResampleArgs ra;
     if (n_rs) {
         ResampleDesc *hr = reinterpret_cast<ResampleDesc *>(hs + roff);
@@ -762,17 +793,29 @@ void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<con
         da.raw = reinterpret_cast<const uint8_t *>(ds_pcm_[b]) + woff; da.out = ds_pcm_[b];
         da.desc = reinterpret_cast<const DecodeDesc *>(reinterpret_cast<const char *>(ds_pcm_[b]) + coff);
     }
+    VadArgs va;
+    if (n_vd) {
+        va.ring = ring_; va.ring_frames = ring_frames_; va.nbins = ft_.nbins; va.state = vad_state_d_; va.out = vad_out_d_;
+        va.desc = reinterpret_cast<const VadDesc *>(reinterpret_cast<const char *>(ds_pcm_[b]) + voff); va.n_desc = n_vd;
+    }
     if (profiling_) {        // (the per-class hipEvents live on M: a profiled fbank runs there, behind its upload)
         m_touched();
         join(stream_, f_stream_);
         if (n_dc) { timed_begin(T_DECODE); launch_decode(da, stream_); timed_end(T_DECODE); }      // (decode feeds both)
         if (n_rs) { timed_begin(T_RESAMPLE); launch_resample(ra, stream_); timed_end(T_RESAMPLE); }
         timed_begin(T_FBANK); launch_fbank(a, stream_); timed_end(T_FBANK);
+        if (n_vd) { timed_begin(T_VAD); launch_vad(va, stream_); timed_end(T_VAD); }
         join(f_stream_, stream_);
     } else {
         if (n_dc) launch_decode(da, f_stream_);
         if (n_rs) launch_resample(ra, f_stream_);
         launch_fbank(a, f_stream_);
+        if (n_vd) launch_vad(va, f_stream_);
+    }
+    if (n_vd) {       // the pass's bytes -> its pinned block, in front of fb_done_; read after the flight's wait (close_flight)
+        HIP_CHECK(hipMemcpyAsync(vblock->h, vad_out_d_, vd_frames, hipMemcpyDeviceToHost, f_stream_));
+        vad_last_h_ = vblock->h; vad_flight_ = true;
+        vad_launches_.fetch_add(1, std::memory_order_relaxed); vad_frames_.fetch_add(vd_frames, std::memory_order_relaxed);
     }
     HIP_CHECK(hipEventRecord(fb_done_[b], f_stream_));       // no host wait here: the encoder launches queue right behind
     f_unseen_by_m_ = true;
@@ -1816,7 +1859,8 @@ int Engine::close_flight()
         tail = stream_;
         if (f_unseen_by_m_) { join(stream_, f_stream_); f_unseen_by_m_ = false; }
         if (s_unseen_by_m_) { join(stream_, s_stream_); s_unseen_by_m_ = false; }
-    }
+    } else if (vad_flight_) join(s_stream_, f_stream_);      // a VAD pass's bytes are read after this flight's wait: its copy comes first
+    vad_flight_ = false;
     if (rec_pos_ > rec_base_) HIP_CHECK(hipMemcpyAsync(rec_h_ + rec_base_, rec_d_ + rec_base_, (rec_pos_ - rec_base_) * sizeof(StepRecord), hipMemcpyDeviceToHost, tail));
     for (const auto &sp : conf_spans_) {          // side records: only the steps that hold a row of a session with confidences on
         HIP_CHECK(hipMemcpyAsync(conf_h_ + sp.first, conf_d_ + sp.first, sp.second * sizeof(ConfRecord), hipMemcpyDeviceToHost, tail));
@@ -2154,6 +2198,42 @@ void Engine::debug_decode(uint32_t encoding, uint32_t channels, int32_t channel,
     HIP_CHECK(hipStreamDestroy(st));
     HIP_CHECK(hipMemcpy(out, a.out, n_frames * sizeof(int16_t), hipMemcpyDeviceToHost));
     (void)hipFree(d); (void)hipFree(dd);
+}
+
+void Engine::debug_vad(int n_runs, const VadPlan *plans, const int32_t *n, const int32_t *first_row, int ring_rows, const float *rows, VadState *states_io,
+                       uint8_t *bytes_out, float *energy_out)
+{
+    const size_t nb = (size_t)ft_.nbins;
+    std::vector<VadDesc> desc((size_t)n_runs);
+    std::vector<float> ring((size_t)n_runs * (size_t)ring_rows * nb, 0.0f);
+    size_t total = 0;
+    for (int r = 0; r < n_runs; ++r) {
+        VadDesc &d = desc[(size_t)r];
+        d.slot = r; d.first_row = first_row[r]; d.n = n[r]; d.out_off = (int32_t)total; d.plan = plans[r];
+        for (int i = 0; i < n[r]; ++i)
+            memcpy(&ring[((size_t)r * (size_t)ring_rows + (size_t)((first_row[r] + i) % ring_rows)) * nb], rows + (total + (size_t)i) * nb, nb * sizeof(float));
+        total += (size_t)n[r];
+    }
+    HipLegacyLock legacy;
+    HIP_CHECK(hipSetDevice(cfg_.device));
+    float *ring_d = dmalloc<float>(ring.size()), *en_d = dmalloc<float>(total);
+    VadDesc *desc_d = dmalloc<VadDesc>((size_t)n_runs);
+    VadState *st_d = dmalloc<VadState>((size_t)n_runs);
+    uint8_t *out_d = dmalloc<uint8_t>(total);
+    HIP_CHECK(hipMemcpy(ring_d, ring.data(), ring.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(desc_d, desc.data(), desc.size() * sizeof(VadDesc), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(st_d, states_io, (size_t)n_runs * sizeof(VadState), hipMemcpyHostToDevice));
+    VadArgs a;
+    a.ring = ring_d; a.ring_frames = ring_rows; a.nbins = ft_.nbins; a.desc = desc_d; a.n_desc = n_runs; a.state = st_d; a.out = out_d; a.energy = en_d;
+    hipStream_t st = nullptr;                 // (its own stream, as debug_resample)
+    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    launch_vad(a, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipStreamDestroy(st));
+    HIP_CHECK(hipMemcpy(states_io, st_d, (size_t)n_runs * sizeof(VadState), hipMemcpyDeviceToHost));
+    if (total) HIP_CHECK(hipMemcpy(bytes_out, out_d, total, hipMemcpyDeviceToHost));
+    if (total && energy_out) HIP_CHECK(hipMemcpy(energy_out, en_d, total * sizeof(float), hipMemcpyDeviceToHost));
+    for (void *p : {(void *)ring_d, (void *)en_d, (void *)desc_d, (void *)st_d, (void *)out_d}) (void)hipFree(p);
 }
 
 void Engine::read_greedy_state(int slot, GreedyState *out)

@@ -153,6 +153,25 @@ public:
     {
         *launches = dc_launches_.load(std::memory_order_relaxed); *frames = dc_frames_.load(std::memory_order_relaxed);
     }
+    // ---- voice activity.  Inline over plain members: the scheduler harness links session.cc against an engine of
+    // its own.  set_vad_pass(), for the NEXT fbank() call only: the n descriptors (out_off counted from 0, `frames` bytes in all) are
+    // staged behind the decode descriptors in the same upload; vad_kernel runs right behind the fbank launch, and the pass's bytes are
+    // copied into a pinned block of their own before fb_done_ is recorded.  vad_pass_bytes() is that block (null: the last fbank() had
+    // no VAD pass): its bytes are complete once the flight that was open during the call has been waited for (close_flight() puts the
+    // copy in front of the flight's event), and the block is lent until vad_release().  Stepping thread only.  Without
+    // set_vad_pass(), fbank() issues exactly the launches it always did and nothing below is allocated.
+    void set_vad_pass(int n, const VadDesc *desc, size_t frames) { vad_n_ = n; vad_desc_ = desc; vad_pass_frames_ = frames; }
+    const uint8_t *vad_pass_bytes() const { return vad_last_h_; }
+    void vad_release(const uint8_t *p) { for (VadBlock &b : vad_blocks_) if (b.h == p) b.busy = false; }
+    // VAD launches and the frames they covered so far (any thread)
+    void vad_counts(uint64_t *launches, uint64_t *frames) const
+    {
+        *launches = vad_launches_.load(std::memory_order_relaxed); *frames = vad_frames_.load(std::memory_order_relaxed);
+    }
+    // aprilx_run_vad: n_runs runs in ONE launch over a scratch ring of ring_rows rows per run; run r's n[r] rows (consecutive in `rows`)
+    // sit at rows (first_row[r] + i) % ring_rows of its ring
+    void debug_vad(int n_runs, const VadPlan *plans, const int32_t *n, const int32_t *first_row, int ring_rows, const float *rows, VadState *states_io,
+                   uint8_t *bytes_out, float *energy_out);
     void begin_flight();
     bool flight_has_room(int rows, int nsteps = 1) const;   // `nsteps` more steps with `rows` rows in total fit into the index / record rings
     // one chunk for m sessions (m <= max_batch): returns the step's index inside the flight.  logits_out (tests): when
@@ -286,7 +305,7 @@ public:
     // split feeds launched as hostable (any thread)
     void ramp_counts(uint64_t *hosted, uint64_t *eligible);
     void reset_timing();
-    enum { T_GATES = 0, T_GEMM_OTHER = 1, T_ROW = 2, T_CONV = 3, T_FBANK = 4, T_DEC = 5, T_RESAMPLE = 6, T_DECODE = 7, T_COUNT = 8 };
+    enum { T_GATES = 0, T_GEMM_OTHER = 1, T_ROW = 2, T_CONV = 3, T_FBANK = 4, T_DEC = 5, T_RESAMPLE = 6, T_DECODE = 7, T_VAD = 8, T_COUNT = 9 };
     long kernels_per_step() const { return kernels_per_step_.load(std::memory_order_relaxed); }    // launches of the last eagerly issued chunk chain
 
 private:
@@ -463,6 +482,18 @@ private:
     const std::pair<const uint8_t *, size_t> *dc_raw_parts_ = nullptr;
     size_t dc_n_raw_parts_ = 0, dc_n_raw_ = 0;
     std::atomic<uint64_t> dc_launches_{0}, dc_frames_{0};
+    // voice activity: nothing below is allocated until a pass carries a VAD descriptor
+    size_t vd_cap_ = 0;                        // VAD descriptors the staging buffers have room for
+    int vad_n_ = 0;                            // set_vad_pass(): the VAD work of the next fbank() call
+    const VadDesc *vad_desc_ = nullptr;
+    size_t vad_pass_frames_ = 0;
+    VadState *vad_state_d_ = nullptr;          // [slots] (a session's first descriptor carries VAD_RESET: never initialised by the host)
+    uint8_t *vad_out_d_ = nullptr; size_t vad_out_cap_ = 0;      // one pass's bytes on the device (stream order keeps the passes apart)
+    struct VadBlock { uint8_t *h = nullptr; size_t cap = 0; bool busy = false; };
+    std::vector<VadBlock> vad_blocks_;         // pinned blocks, one per pass whose bytes the scheduler has not read yet; reused afterwards
+    const uint8_t *vad_last_h_ = nullptr;
+    bool vad_flight_ = false;                  // the open flight holds a VAD pass: its event must follow the copy on the front-end stream
+    std::atomic<uint64_t> vad_launches_{0}, vad_frames_{0};
     std::mutex rs_mu_;
     std::map<const ResampleSpec *, const float *> rs_tables_;     // phase tables on the device, uploaded at first use (freed with table_allocs_)
     const float *resample_table(const ResampleSpec *spec);

@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "vad.h"
 
 namespace aprilx {
 
@@ -453,5 +454,27 @@ struct DecodeArgs {
     int max_blocks = 0;                    // max over descriptors of ceil(out_cnt / kDecodeBlock)
 };
 void launch_decode(const DecodeArgs &a, hipStream_t s);
+
+// ---------------------------------------------------------------- voice activity (sessions that opted in; contract in vad.h)
+// One workgroup per descriptor: one session's contiguous run of real feature rows of this pass (rows wrap modulo ring_frames), in
+// frame order.  The descriptor carries the session's plan (32 bytes: no per-slot plan table to keep in step), and VAD_RESET when the
+// run is the first one after the options were set or a flush completed: the kernel then starts from the reset state instead of the
+// slot's record.  One byte per frame goes to out[out_off + i], the slot's 64-byte record is read once and written once.
+constexpr int kVadBlock = 256, kVadTile = 256;           // lanes per workgroup; frames whose energies one LDS tile holds
+enum : int32_t { VAD_RESET = 1 };
+struct VadDesc {
+    int32_t slot = 0, first_row = 0, n = 0, out_off = 0;  // ring rows (first_row + i) % ring_frames, i < n <= ring_frames
+    int32_t flags = 0, reserved[3] = {0, 0, 0};
+    VadPlan plan;
+};
+static_assert(sizeof(VadDesc) == 64, "staged behind the decode descriptors, 16-byte aligned");
+struct VadArgs {
+    const float *ring = nullptr; int ring_frames = 0, nbins = 0;      // [slots][ring_frames][nbins]
+    const VadDesc *desc = nullptr; int n_desc = 0;
+    VadState *state = nullptr;             // [slots]
+    uint8_t *out = nullptr;                // the pass's bytes
+    float *energy = nullptr;               // (tests) step 1's e of every frame, indexed like out; or null
+};
+void launch_vad(const VadArgs &a, hipStream_t s);
 
 }  // namespace aprilx

@@ -379,7 +379,8 @@ static int host_helpers()
 
 static int env_0_1M(const char *name, int def) { return std::max(0, std::min(1000000, env_int(name, def))); }
 
-Scheduler::Scheduler(Model *m, Engine *e) : eng_(e), stride_ms_(m->host.params.segment_step * m->host.params.frame_shift_ms), pool_(host_helpers())
+Scheduler::Scheduler(Model *m, Engine *e)
+    : shift_ms_(m->host.params.frame_shift_ms), eng_(e), stride_ms_(m->host.params.segment_step * m->host.params.frame_shift_ms), pool_(host_helpers())
 {
     spin_step_us_ = env_0_1M("APRIL_SPIN_STEP_US", 1000);     // (1 ms: a client that pauses for a barrier or a sync between two feeds finds the thread awake; 100 us until round 3)
     spin_wait_us_ = env_0_1M("APRIL_SPIN_WAIT_US", 3000);
@@ -548,6 +549,17 @@ bool Scheduler::set_search_options(Session *s, const AprilxSearchOptions *o)
     });
 }
 
+bool Scheduler::set_vad(Session *s, const VadOptions *o, const VadPlan *plan, AprilxVadHandler handler, void *userdata)
+{
+    return configure(s, [&] {
+        s->vad_on = plan != nullptr;
+        s->vad_opt = o ? *o : VadOptions(); s->vad_plan = plan ? *plan : VadPlan();
+        s->vad_handler = plan ? handler : nullptr; s->vad_userdata = plan ? userdata : nullptr;
+        s->vad_reset = true; s->vad_speech = 0; s->vad_segments = 0; s->vad_last = 0;
+        return true;
+    });
+}
+
 bool Scheduler::set_bias(Session *s, std::shared_ptr<const BiasSet> set)
 {
     return configure(s, [&] {
@@ -594,9 +606,12 @@ void Scheduler::wait_backlog(Session *const *ss, int n, uint64_t max_open)
     }
 }
 
-void deliver_events(std::vector<Event> &ev, AprilRecognitionResultHandler handler, void *userdata)
+void deliver_events(std::vector<Event> &ev, AprilRecognitionResultHandler handler, void *userdata, AprilxVadHandler vad, void *vad_userdata)
 {
-    for (auto &e : ev) handler(userdata, (AprilResultType)e.type, e.tokens.size(), e.tokens.empty() ? nullptr : e.tokens.data());
+    for (auto &e : ev) {
+        if (e.type >= kVadEventBase) { if (vad) vad(vad_userdata, e.type - kVadEventBase, e.vad_ms); }
+        else handler(userdata, (AprilResultType)e.type, e.tokens.size(), e.tokens.empty() ? nullptr : e.tokens.data());
+    }
     ev.clear();
 }
 
@@ -604,7 +619,7 @@ void Scheduler::deliver_sync_events(Session *s)
 {
     std::vector<Event> ev;
     { std::lock_guard<std::mutex> g(mu_); ev.swap(s->done_events); }
-    deliver_events(ev, s->handler, s->userdata);
+    deliver_events(ev, s->handler, s->userdata, s->vad_handler, s->vad_userdata);
 }
 
 // One stepping thread, TWO flights in the air.  A flight is launched (frames cut, chunk steps enqueued, record copy + event
@@ -672,6 +687,7 @@ Scheduler::Flight Scheduler::launch_flight(const std::vector<Session *> &work_in
     Flight f;
     f.work = work_in; f.taken = taken; f.t0 = std::chrono::steady_clock::now();
     f.t_sub = collect_t_sub_; f.has_sub = collect_has_sub_;      // (a follow-up flight of the same tick keeps the tick's hand-over time)
+    f.seq = ++flight_seq_;
     std::vector<Session *> &work = f.work;
     f.mark.resize(work.size()); f.chunks0.resize(work.size());
     for (size_t i = 0; i < work.size(); ++i) { f.mark[i] = (uint32_t)work[i]->replay.size(); f.chunks0[i] = work[i]->chunks; }
@@ -716,6 +732,7 @@ void Scheduler::complete_flight(Flight &f)
     Lap lap;
     eng_->wait_flight(f.parity);
     tick_.host_ms[4] += lap();
+    harvest_vad(f.seq);             // (in front of the flight's token events: no later than the chunks that hold the frames)
     replay(f);
     tick_.host_ms[5] += lap();
     std::vector<Session *> &work = f.work;
@@ -738,7 +755,7 @@ void Scheduler::complete_flight(Flight &f)
         }
     }
     // async sessions: deliver on this (library) thread, outside the lock
-    for (Session *s : work) if (!s->sync_mode) deliver_events(s->events, s->handler, s->userdata);
+    for (Session *s : work) if (!s->sync_mode) deliver_events(s->events, s->handler, s->userdata, s->vad_handler, s->vad_userdata);
     {
         std::lock_guard<std::mutex> g(mu_);
         for (size_t i = 0; i < work.size(); ++i) {
@@ -889,6 +906,8 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
 {
     Lap lap;
     desc_.clear(); pcm_parts_.clear(); in_parts_.clear(); rdesc_.clear(); rspec_.clear(); ddesc_.clear(); raw_parts_.clear(); staged_raw_ = 0;
+    vdesc_.clear(); vruns_.clear();
+    int32_t vad_frames = 0;                     // bytes of this pass's VAD output so far
     size_t staged = 0, staged_in = 0;           // model-rate samples (windows), input-rate samples (spans of resampled windows)
     auto used = [&] { return staged + staged_in + (staged_raw_ + 1) / 2; };      // what the pass has staged so far, raw bytes of formatted sessions in sample units
     std::vector<Session *> finishers;
@@ -929,6 +948,15 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
             else if (fb.fmt) stage_decoded(fb, (int64_t)first, (int64_t)last_end, base);
             else fb.append_span(first, last_end, pcm_parts_);                 // (contiguous in staging)
             staged += last_end - first;
+            if (s->vad_on) {                           // the run of real rows just cut: one descriptor, one byte per row
+                VadDesc v;
+                v.slot = s->slot; v.first_row = desc_[desc_.size() - (size_t)cut].ring_row; v.n = cut; v.out_off = vad_frames;
+                v.flags = s->vad_reset ? VAD_RESET : 0; v.plan = s->vad_plan;
+                vdesc_.push_back(v);
+                vruns_.push_back(VadRun{s, s->real_frames, cut, vad_frames});
+                vad_frames += cut; s->vad_reset = false;
+            }
+            s->real_frames += (uint64_t)cut;
             s->compact_pending = true;                 // the fifo must not move until the window has been staged
             progressed = true;
             continue;
@@ -971,6 +999,7 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
             // records of this flight; the device part (context reset + decoder refresh) is queued here
             s->replay.push_back(Session::Replay{-1, 0, 0, (uint32_t)s->now_ms, 1, 0});
             finishers.push_back(s);
+            if (s->vad_on) { vruns_.push_back(VadRun{s, s->real_frames, -1, 0}); s->vad_reset = true; }      // closes an open segment; the detector starts afresh
             s->flush_phase = 0;
             progressed = true;
             break;
@@ -981,11 +1010,13 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
     if (!desc_.empty()) {
         if (!ddesc_.empty()) eng_->set_decode_pass((int)ddesc_.size(), ddesc_.data(), raw_parts_.data(), raw_parts_.size(), staged_raw_);
         if (!rdesc_.empty()) eng_->set_resample_pass((int)rdesc_.size(), rdesc_.data(), rspec_.data(), in_parts_.data(), in_parts_.size(), staged_in);
+        if (!vdesc_.empty()) eng_->set_vad_pass((int)vdesc_.size(), vdesc_.data(), (size_t)vad_frames);
         eng_->fbank((int)desc_.size(), desc_.data(), pcm_parts_.data(), pcm_parts_.size(), staged, &pool_);
         pool_.run(work.size(), 64, [&](size_t i) { Session *s = work[i]; if (s->compact_pending) { s->fb.compact(); s->compact_pending = false; } });
         tick_.frames += desc_.size();
         tick_.host_ms[2] += lap();
     }
+    if (!vruns_.empty()) vad_pending_.push_back(VadPending{flight_seq_, vdesc_.empty() ? nullptr : eng_->vad_pass_bytes(), vruns_});
     if (!finishers.empty()) {
         slots_.clear();
         for (Session *s : finishers) slots_.push_back(s->slot);
@@ -1103,6 +1134,30 @@ bool Scheduler::step_chunks(std::vector<Session *> &ready)
     if (!eng_->flight_has_room(n, (n + MB - 1) / MB)) return false;
     for (int o = 0; o < n; o += MB) advance(one.data() + o, std::min(MB, n - o), 1, STEP_CHUNK);
     return true;
+}
+
+// After the flight's wait: the bytes of every VAD pass cut under it (and under the flights before it) are on the host.  Per run, in
+// pass order, the events that follow from bit 0 of consecutive bytes go to the session's event list; a completed flush closes an
+// open segment.  The sessions are alive: they stay busy until their flight completes.
+void Scheduler::harvest_vad(uint64_t flight)
+{
+    while (!vad_pending_.empty() && vad_pending_.front().flight <= flight) {
+        VadPending &p = vad_pending_.front();
+        for (const VadRun &r : p.runs) {
+            Session *s = r.s;
+            auto emit = [&](int kind, uint64_t ms) {
+                Event e; e.type = kVadEventBase + kind; e.vad_ms = ms;
+                s->events.push_back(std::move(e));
+                if (kind == VAD_SPEECH_START) s->vad_segments++;
+            };
+            if (r.n < 0) { if (s->vad_last) emit(VAD_SPEECH_END, r.t0 * (uint64_t)shift_ms_); s->vad_last = 0; continue; }
+            const uint8_t *b = p.bytes + r.off;
+            s->vad_last = vad_events(s->vad_plan, shift_ms_, r.t0, b, (size_t)r.n, s->vad_last, emit);
+            for (int32_t i = 0; i < r.n; ++i) s->vad_speech += b[i] & 1u;
+        }
+        if (p.bytes) eng_->vad_release(p.bytes);
+        vad_pending_.pop_front();
+    }
 }
 
 // After the flight: per session, in the order things happened, feed the device's per-round records to the search state

@@ -50,9 +50,13 @@ struct Event {
     // sessions with confidences on (aprilx_session_set_confidence): one entry per token, and tokens[i].reserved points to infos[i].
     // Events are only ever MOVED between containers (the vector's storage, and with it the pointers, stay where they are).
     std::vector<AprilxTokenInfo> infos;
+    // a voice-activity event: type = kVadEventBase + kind, for the session's AprilxVadHandler
+    uint64_t vad_ms = 0;
 };
-// the handler once per event, in order (null token pointer when an event has no tokens); `ev` is empty afterwards
-void deliver_events(std::vector<Event> &ev, AprilRecognitionResultHandler handler, void *userdata);
+constexpr int kVadEventBase = 0x100;
+// the handler once per event, in order (null token pointer when an event has no tokens); voice-activity events go to `vad`; `ev` is
+// empty afterwards
+void deliver_events(std::vector<Event> &ev, AprilRecognitionResultHandler handler, void *userdata, AprilxVadHandler vad = nullptr, void *vad_userdata = nullptr);
 
 class Greedy {
 public:
@@ -214,6 +218,14 @@ struct Session {
     size_t now_ms = 0;
     uint64_t chunks = 0;
     std::vector<Event> events;                // produced during the current tick
+    // voice activity.  Options, plan and handler change only while the session is settable; the counters are the
+    // stepping thread's while the session is busy.  real_frames counts every real frame cut since creation (VAD on or off): the frame clock.
+    bool vad_on = false;
+    VadOptions vad_opt; VadPlan vad_plan;
+    AprilxVadHandler vad_handler = nullptr; void *vad_userdata = nullptr;
+    bool vad_reset = true;                    // the session's next descriptor starts from the reset state
+    uint64_t real_frames = 0, vad_speech = 0;
+    uint32_t vad_segments = 0; int vad_last = 0;      // SPEECH_START events so far; bit 0 of the last byte read
     // tracing (tests): every joiner call appends `vocab` floats
     float *trace_buf = nullptr; size_t trace_cap = 0; size_t *trace_used = nullptr;
 };
@@ -256,6 +268,8 @@ public:
     bool set_bias(Session *s, std::shared_ptr<const BiasSet> set);
     // aprilx_session_set_search_options: the same rule; null = back to no options
     bool set_search_options(Session *s, const AprilxSearchOptions *o);
+    // aprilx_session_set_vad: the same rule; plan null = off.  The detector and its counters start afresh
+    bool set_vad(Session *s, const VadOptions *o, const VadPlan *plan, AprilxVadHandler handler, void *userdata);
     void wait_idle_many(Session *const *ss, int n);
     // until every listed session has at most `max_open` feeds that were submitted and not completed yet (pipelined group feeds)
     void wait_backlog(Session *const *ss, int n, uint64_t max_open);
@@ -278,6 +292,7 @@ private:
         std::chrono::steady_clock::time_point t0;
         std::chrono::steady_clock::time_point t_sub;          // hand-over of the oldest work in the flight (submit() of any of its sessions)
         bool has_sub = false;
+        uint64_t seq = 0;                                    // launch order: the VAD passes cut under this flight carry it
     };
     void loop();
     bool collect(std::vector<Session *> &work, std::vector<uint64_t> &taken, bool block, uint64_t &work_seen);
@@ -293,6 +308,14 @@ private:
     bool advance(Session *const *group, int m, int T, StepPath path);
     template <class Apply> bool configure(Session *s, Apply apply);     // the three set_* calls: wait_idle, lock, refuse unless settable, apply
     void replay(Flight &f);
+    // voice activity: what the passes of the open flights wrote, read once their flight has been waited for (complete_flight)
+    struct VadRun { Session *s; uint64_t t0; int32_t n, off; };          // frames [t0, t0 + n) at bytes[off ..]; n < 0: a flush completed at frame t0
+    struct VadPending { uint64_t flight; const uint8_t *bytes; std::vector<VadRun> runs; };
+    std::deque<VadPending> vad_pending_;
+    std::vector<VadDesc> vdesc_; std::vector<VadRun> vruns_;
+    uint64_t flight_seq_ = 0;
+    const int shift_ms_;
+    void harvest_vad(uint64_t flight);
     int split_sticky_ = 0;
     int pipeline_depth_ = 2;                             // APRIL_PIPELINE: 2 = launch the next flight before completing the current one, 1 = one flight at a time
 

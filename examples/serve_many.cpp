@@ -5,7 +5,7 @@
 //
 //   g++ -O2 -std=c++17 examples/serve_many.cpp -I include -L april_asr_amd -laprilasr -Wl,-rpath,$PWD/april_asr_amd -o serve_many
 //   ./serve_many model.april audio.raw [sessions=64] [mode=pipelined|lockstep] [input_rate] [--alternatives K] [--bias FILE [--bias-strict]]
-//               [--endpoint-ms N] [--blank-penalty X]
+//               [--endpoint-ms N] [--blank-penalty X] [--vad]
 //
 // Every session gets the same PCM16 file, rotated by (session index x 0.37 s) so that the streams differ.  With `input_rate` the file
 // is PCM16 at that rate and every session is told so (aprilx_session_set_input_rate): the library converts it to the model's rate on
@@ -19,6 +19,8 @@
 // phrase list (APRILX_BIAS_STRICT): the sessions that have it emit only sequences of the file's phrases.
 // `--endpoint-ms N` / `--blank-penalty X` (anywhere on the line): every session gets search options (aprilx_session_set_search_options):
 // an utterance ends N ms after its last token instead of 2200, X is subtracted from the blank logit in the decision.
+// `--vad` (anywhere on the line): every session gets the voice-activity detector with its default options (aprilx_session_set_vad); its line
+// then ends with " vad <segments> <speech seconds>", and the timing lines say what a step cost.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -30,7 +32,17 @@
 
 #include <cmath>
 
-struct Stream { size_t calls = 0, finals = 0, final_tokens = 0; std::string last_final; double conf_sum = 0; size_t conf_n = 0; };
+struct Stream {
+    size_t calls = 0, finals = 0, final_tokens = 0; std::string last_final; double conf_sum = 0; size_t conf_n = 0;
+    size_t vad_segments = 0; uint64_t vad_open_ms = 0, vad_speech_ms = 0;
+};
+
+static void on_vad(void *ud, int kind, uint64_t time_ms)
+{
+    Stream *s = static_cast<Stream *>(ud);
+    if (kind == APRILX_VAD_SPEECH_START) { s->vad_segments++; s->vad_open_ms = time_ms; }
+    else s->vad_speech_ms += time_ms - s->vad_open_ms;
+}
 
 static void on_result(void *ud, AprilResultType type, size_t count, const AprilToken *tokens)
 {
@@ -53,6 +65,14 @@ int main(int argc, char **argv)
     bool bias_strict = false;
     long endpoint_ms = -1;
     const char *blank_penalty = nullptr;
+    bool vad = false;
+    for (int i = 1; i < argc; ++i)
+        if (!strcmp(argv[i], "--vad")) {
+            vad = true;
+            for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+            argc -= 1;
+            break;
+        }
     for (int i = 1; i + 1 < argc; ++i)
         if (!strcmp(argv[i], "--endpoint-ms")) {
             endpoint_ms = atol(argv[i + 1]);
@@ -154,6 +174,10 @@ int main(int argc, char **argv)
             so.blank_penalty = blank_penalty ? strtof(blank_penalty, nullptr) : 0.0f;
             if (aprilx_session_set_search_options(sessions[(size_t)i], &so) != 0) { fprintf(stderr, "search options refused\n"); return 1; }
         }
+        if (vad) {
+            AprilxVadOptions vo = {(uint32_t)sizeof vo, 200.0f, 4000.0f, 5.0f, 3.0f, 50u, 300u, -12.0f, 0u};
+            if (aprilx_session_set_vad(sessions[(size_t)i], &vo, on_vad, &streams[(size_t)i]) != 0) { fprintf(stderr, "voice-activity options refused\n"); return 1; }
+        }
         const size_t rot = ((size_t)i * (size_t)(0.37 * rate)) % pcm.size();
         audio[(size_t)i].assign(pcm.begin() + (long)rot, pcm.end());
         audio[(size_t)i].insert(audio[(size_t)i].end(), pcm.begin(), pcm.begin() + (long)rot);
@@ -169,7 +193,12 @@ int main(int argc, char **argv)
     if (pipelined) aprilx_drain_many((size_t)n, sessions.data());
     aprilx_flush_many((size_t)n, sessions.data());
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (int i = 0; i < n; ++i) printf("%d %zu %zu %zu %s\n", i, streams[(size_t)i].calls, streams[(size_t)i].finals, streams[(size_t)i].final_tokens, streams[(size_t)i].last_final.c_str());
+    for (int i = 0; i < n; ++i) {
+        const Stream &s = streams[(size_t)i];
+        printf("%d %zu %zu %zu %s", i, s.calls, s.finals, s.final_tokens, s.last_final.c_str());
+        if (vad) printf(" vad %zu %.2f", s.vad_segments, (double)s.vad_speech_ms * 1e-3);      // (the flush has closed every open segment)
+        printf("\n");
+    }
     fprintf(stderr, "%d streams x %.1f s of audio in %.1f ms (%s feed): %.0f audio-seconds per second\n", n, steps * 0.1, ms, pipelined ? "pipelined" : "lock-step",
             n * steps * 0.1 / (ms * 1e-3));
     if (alternatives) {
@@ -179,6 +208,13 @@ int main(int argc, char **argv)
     }
     if (bias) fprintf(stderr, "phrase boosting: %.3f ms per 100 ms step\n", ms / (double)steps);
     if (endpoint_ms >= 0 || blank_penalty) fprintf(stderr, "search options: %.3f ms per 100 ms step\n", ms / (double)steps);
+    if (vad) {
+        uint64_t launches = 0, frames = 0; double kms = 0; size_t segs = 0; double secs = 0;
+        aprilx_model_vad_stats(model, 0, &launches, &frames, &kms);
+        for (const Stream &s : streams) { segs += s.vad_segments; secs += (double)s.vad_speech_ms * 1e-3; }
+        fprintf(stderr, "voice activity: %.3f ms per 100 ms step, %zu segments, %.1f speech seconds, %llu launches over %llu frames on device 0\n", ms / (double)steps, segs, secs,
+                (unsigned long long)launches, (unsigned long long)frames);
+    }
     if (argc > 5) fprintf(stderr, "input at %zu Hz: %.3f ms per 100 ms step\n", rate, ms / (double)steps);
     for (AprilASRSession s : sessions) aas_free(s);
     if (bias) aprilx_bias_free(bias);

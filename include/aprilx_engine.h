@@ -309,6 +309,62 @@ APRIL_EXPORT uint64_t aprilx_session_read_frames(AprilASRSession session, uint64
    and must agree; tests only. */
 APRIL_EXPORT void aprilx_session_context(AprilASRSession session, int32_t *host_ctx, int32_t *device_state);
 
+/* ---- voice activity.  A session that opts in gets SPEECH_START / SPEECH_END events from a detector that runs
+ * on the GPU, on the log-mel rows the filterbank has just written: band energy, an exponential average, a running minimum over the
+ * last 256..288 frames as the noise floor, two thresholds with onset and hangover counts.  The feature only observes: the session's
+ * callbacks, feature rows and chunk count are those of a session without it, and an engine none of whose sessions has opted in
+ * launches nothing new.  Times are on the FRAME clock: frame t of the session (real frames since its creation, flush zeros
+ * included, never reset) starts at t * frame_shift ms of its audio; AprilToken.time_ms runs on the chunk-stride clock.
+ * Events are delivered in frame order, no later than the token callbacks of the chunks that hold their frames, on the thread that
+ * delivers those (the caller's for synchronous sessions); aas_flush / a drain returns after every event of the flushed audio.  A
+ * flush that completes inside speech closes the segment with a SPEECH_END at frames_seen * frame_shift, and resets the detector. */
+typedef struct AprilxVadOptions {
+    uint32_t size;                      /* sizeof(AprilxVadOptions) */
+    float band_lo_hz, band_hi_hz;       /* 200, 4000: 0 <= lo < hi <= rate / 2, and the band holds at least one mel bin (peak in [lo, hi]) */
+    float onset_db, offset_db;          /* 5.0, 3.0: finite, 0 < offset <= onset <= 60; dB of band energy above the noise floor */
+    uint32_t onset_ms, hangover_ms;     /* 50, 300: 10..1000 and 10..10000; frames = ms / frame_shift_ms, at least 1 */
+    float min_energy;                   /* -12.0: finite; floor of the band-mean log-mel energy (digital silence is -15.94) */
+    uint32_t flags;                     /* 0 */
+} AprilxVadOptions;
+typedef enum AprilxVadEventKind { APRILX_VAD_SPEECH_START = 1, APRILX_VAD_SPEECH_END = 2 } AprilxVadEventKind;
+typedef void (*AprilxVadHandler)(void *userdata, int kind, uint64_t time_ms);
+typedef struct AprilxVadInfo {
+    int32_t b0, b1;                     /* the band: mel bins [b0, b1) */
+    int32_t onset_frames, hangover_frames;
+    uint64_t frames_seen;               /* real frames of the session since its creation */
+    uint64_t speech_frames;             /* frames whose byte had the speech bit, since the detector was last set */
+    uint32_t in_speech, segments;       /* the last frame's speech bit; SPEECH_START events since the detector was last set */
+} AprilxVadInfo;
+/* the plan the kernel works from, and a session's detector state (64 bytes); tests and users of aprilx_vad_host */
+typedef struct AprilxVadPlan { int32_t b0, b1; float inv_nb, thr_on, thr_off, min_energy; int32_t onset_frames, hangover_frames; } AprilxVadPlan;
+typedef struct AprilxVadState { float s, cur, hist[8]; int32_t cnt, pos, st, run, first, reserved; } AprilxVadState;
+/* options = NULL: off.  0, or -1 and nothing changes: a wrong size, a value out of range, non-zero flags, a NULL handler with
+ * options, or a session with audio fed since its last completed flush (the rule of aprilx_session_set_search_options).  Setting
+ * resets the detector and its counters; frames_seen runs on. */
+APRIL_EXPORT int aprilx_session_set_vad(AprilASRSession session, const AprilxVadOptions *options, AprilxVadHandler handler, void *userdata);
+/* 1 and the options / info when the detector is on, 0 (info: frames_seen only) when it is off, -1 on bad arguments; either pointer
+ * may be NULL.  Waits for the session to be idle. */
+APRIL_EXPORT int aprilx_session_vad(AprilASRSession session, AprilxVadOptions *options_out, AprilxVadInfo *out);
+/* The plan from a mel table mel[nbins][nfft_bins] (aprilx_model_fbank_tables: nfft_bins = fft_size / 2): 0, or -1 as above.  No GPU. */
+APRIL_EXPORT int aprilx_vad_plan_tables(const float *mel, int nbins, int nfft_bins, int sample_rate, int frame_shift_ms,
+                                        const AprilxVadOptions *options, AprilxVadPlan *plan_out);
+/* The contract on the host: n rows of nbins floats through steps 1-9 from *state_inout (reset state: cur and hist +inf, first 1,
+ * the rest 0), one byte per row (bit 0 speech, bit 1 raw), energy_out (may be NULL) step 1's band mean of every row.  No GPU. */
+APRIL_EXPORT int aprilx_vad_host(const AprilxVadPlan *plan, int n, int nbins, const float *rows, AprilxVadState *state_inout, uint8_t *bytes_out,
+                                 float *energy_out);
+/* Events from the bytes of frames [t0, t0 + n), last_bit the speech bit of frame t0 - 1: kinds_out / times_out (cap entries each)
+ * receive them in order; returns their number (may exceed cap: nothing is written past it), *last_bit the new one.  No GPU. */
+APRIL_EXPORT int aprilx_vad_events_host(const AprilxVadPlan *plan, int frame_shift_ms, uint64_t t0, const uint8_t *bytes, size_t n, int32_t *last_bit,
+                                        int32_t *kinds_out, uint64_t *times_out, int cap);
+/* Tests only: vad_kernel on n_runs runs in ONE launch over a scratch ring of R = max(n[]) rows per run.  Run r has its own options
+ * (as a plan derived from the model's tables), n[r] rows -- consecutive in rows[sum n][mel] -- placed at ring rows
+ * (first_row[r] + i) % R (0 <= first_row[r] < R: a run that wraps), and its state states_inout[r].  bytes_out / energy_out[sum n].
+ * 0, or -1 on bad arguments. */
+APRIL_EXPORT int aprilx_run_vad(AprilASRModel model, int n_runs, const AprilxVadOptions *options, const int32_t *n, const int32_t *first_row,
+                                const float *rows, AprilxVadState *states_inout, uint8_t *bytes_out, float *energy_out);
+/* VAD launches and the frames they covered on one GPU's engine, and (while profiling) the kernel's accumulated ms.  0, or -1. */
+APRIL_EXPORT int aprilx_model_vad_stats(AprilASRModel model, int device_index, uint64_t *launches, uint64_t *frames, double *ms);
+
 typedef struct AprilxStats {
     uint64_t ticks, steps, chunks, rounds, frames, max_batch_seen;
     /* per kernel class: accumulated ms and launch counts while profiling is enabled
