@@ -23,8 +23,7 @@ using namespace aprilx;
 
 namespace aprilx { int g_loglevel = LOG_WARNING; }
 
-struct AprilASRModel_i { Model m; };
-struct AprilASRSession_i { Session s; };
+#include "api_handles.h"
 #include "group_feed.h"
 
 namespace {
@@ -737,7 +736,7 @@ int aprilx_run_decide(AprilASRModel model, int n, int op, const float *logits, f
 {
     if (!model || n <= 0 || model->m.engines.empty() || n > model->m.engines[0]->max_slots() || !state_io) return -1;
     if (op == 0 && (!logits || !now_ms || !records_out || round < 0 || round > 2)) return -1;
-    model->m.engines[0]->debug_decide(n, op, logits, early_emit, (const int *)now_ms, round, state_io, (StepRecord *)records_out);
+    model->m.engines[0]->debug_decide(DecideRequest::round_of(n, op, logits, early_emit, now_ms, round, state_io, records_out));
     return 0;
 }
 int aprilx_plan_gemm(int M, int N, int kz, int zcount, int tile_ok, int force, int32_t *out)
@@ -848,10 +847,6 @@ void aprilx_model_profile(AprilASRModel model, int enable)
     }
 }
 
-struct AprilxGreedy_i {
-    Greedy g; AprilRecognitionResultHandler handler; void *ud; std::vector<Event> ev;
-    void flush_events() { deliver_events(ev, handler, ud); }
-};
 
 AprilxGreedy aprilx_greedy_create(AprilASRModel model, AprilRecognitionResultHandler handler, void *userdata)
 {

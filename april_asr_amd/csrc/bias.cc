@@ -13,16 +13,9 @@
 #include "bias.h"
 #include "common.h"
 #include "session.h"
+#include "api_handles.h"
 
 using namespace aprilx;
-
-struct AprilASRModel_i { Model m; };          // (the same definitions as april_api.cc)
-struct AprilASRSession_i { Session s; };
-struct AprilxGreedy_i {
-    Greedy g; AprilRecognitionResultHandler handler; void *ud; std::vector<Event> ev;
-    void flush_events() { deliver_events(ev, handler, ud); }
-};
-struct AprilxBias_i { std::shared_ptr<const BiasSet> set; };
 
 namespace {
 
@@ -238,7 +231,9 @@ int aprilx_run_decide_biased(AprilASRModel model, int n, int op, const float *lo
     if (op == 0 && (!logits || !now_ms || !records_out || round < 0 || round > 2)) return -1;
     if (!bias || !bias_state_io || bias->set->vocab != model->m.host.params.token_count || bias->set->vocab_hash != bias_vocab_hash(model->m.host.params)) return -1;
     for (int i = 0; i < n; ++i) if (bias_state_io[i] < -1 || bias_state_io[i] >= bias->set->states()) return -1;
-    model->m.engines[0]->debug_decide_biased(n, op, logits, early_emit, (const int *)now_ms, round, state_io, (StepRecord *)records_out, *bias->set, bias_state_io);
+    DecideRequest q = DecideRequest::round_of(n, op, logits, early_emit, now_ms, round, state_io, records_out);
+    q.set = bias->set.get(); q.bias_state_io = bias_state_io;
+    model->m.engines[0]->debug_decide(q);
     return 0;
 }
 

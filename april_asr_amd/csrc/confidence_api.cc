@@ -9,12 +9,9 @@
 #include "bias.h"
 #include "common.h"
 #include "session.h"
+#include "api_handles.h"
 
 using namespace aprilx;
-
-struct AprilASRModel_i { Model m; };          // (the same definitions as april_api.cc)
-struct AprilASRSession_i { Session s; };
-struct AprilxBias_i { std::shared_ptr<const BiasSet> set; };      // (as bias.cc)
 
 namespace {
 
@@ -23,7 +20,10 @@ int run_confidence(AprilASRModel model, int n, const float *logits, int k, April
     if (!model || n <= 0 || model->m.engines.empty() || n > model->m.engines[0]->max_slots() || n > model->m.engines[0]->max_batch()) return -1;
     if (!logits || !out || k < 1 || k > kConfMaxAlt) return -1;
     std::vector<ConfRecord> rec((size_t)n);
-    model->m.engines[0]->debug_confidence(n, logits, k, rec.data(), set, bias_state);
+    std::vector<int32_t> trie(bias_state, bias_state + (set ? n : 0));      // (the request's states are in/out)
+    DecideRequest q;
+    q.n = n; q.logits = logits; q.conf_k = k; q.conf_out = rec.data(); q.set = set; q.bias_state_io = trie.data();
+    model->m.engines[0]->debug_decide(q);
     // the same conversion a live session's tokens get (Greedy::fill_info)
     for (int i = 0; i < n; ++i) {
         const ConfRecord &c = rec[(size_t)i];

@@ -133,6 +133,42 @@ void pack_weights(const HostModel &m, PackedLayout &L, std::vector<float> &blob)
 template <typename T> static T *dmalloc(size_t n) { HipLegacyLock legacy; T *p = nullptr; HIP_CHECK(hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T))); return p; }
 template <typename T> static T *hmalloc(size_t n) { HipLegacyLock legacy; T *p = nullptr; HIP_CHECK(hipHostMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault)); return p; }
 
+template <typename T> void DeviceTable<T>::alloc(size_t count, const T &off)
+{
+    n = count; d = dmalloc<T>(n); h = hmalloc<T>(n);
+    for (size_t i = 0; i < n; ++i) h[i] = off;
+}
+template <typename T> void DeviceTable<T>::upload(hipStream_t st) const { HIP_CHECK(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, st)); }
+template <typename T> void DeviceTable<T>::release()
+{
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+    d = h = nullptr; n = 0;
+}
+
+// The device scratch of one debug call: freed when the call leaves, whichever way
+struct DeviceScratch {
+    std::vector<void *> ptrs;
+    DeviceScratch() = default;
+    DeviceScratch(const DeviceScratch &) = delete;
+    DeviceScratch &operator=(const DeviceScratch &) = delete;
+    ~DeviceScratch() { for (void *p : ptrs) (void)hipFree(p); }
+    void adopt(void *p) { ptrs.push_back(p); }
+    template <typename T> T *alloc(size_t n) { T *p = dmalloc<T>(n); ptrs.push_back(p); return p; }
+    template <typename T> T *zeros(size_t n) { T *p = alloc<T>(n); HIP_CHECK(hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T))); return p; }
+    template <typename T> T *upload(const T *src, size_t n) { T *p = alloc<T>(n); if (n) HIP_CHECK(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice)); return p; }
+};
+
+// A debug launch on a stream of its own: live sessions' work on the engine's streams is neither waited for nor delayed
+template <typename Launch> static void run_on_private_stream(Launch &&launch)
+{
+    hipStream_t st = nullptr;
+    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    launch(st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipStreamDestroy(st));
+}
+
 std::recursive_mutex &hip_legacy_mutex() { static std::recursive_mutex m; return m; }
 
 static int pick_kz(int K, int N, int kblk = 16)
@@ -366,15 +402,11 @@ Engine::~Engine()
     if (zargs_h_) { (void)hipHostFree(zargs_h_); (void)hipFree(zargs_d_); }
     for (int i = 0; i < 3; ++i) if (zargs_done_[i]) (void)hipEventDestroy(zargs_done_[i]);
     for (void *p : {(void *)lm_now_d_, (void *)lm_rows_d_, (void *)lm_rec_off_d_}) if (p) (void)hipFree(p);
-    if (conf_k_d_) (void)hipFree(conf_k_d_);
+    conf_k_.release(); bias_set_.release(); bias_desc_.release(); opt_.release();
     if (conf_d_) (void)hipFree(conf_d_);
-    if (conf_k_h_) (void)hipHostFree(conf_k_h_);
     if (conf_h_) (void)hipHostFree(conf_h_);
     for (auto &b : bias_sets_) if (b.dev) (void)hipFree(b.dev);
-    for (void *p : {(void *)bias_set_d_, (void *)bias_state_d_, (void *)bias_desc_d_}) if (p) (void)hipFree(p);
-    for (void *p : {(void *)bias_set_h_, (void *)bias_desc_h_}) if (p) (void)hipHostFree(p);
-    if (opt_d_) (void)hipFree(opt_d_);
-    if (opt_h_) (void)hipHostFree(opt_h_);
+    if (bias_state_d_) (void)hipFree(bias_state_d_);
     for (void *p : {(void *)vad_state_d_, (void *)vad_out_d_}) if (p) (void)hipFree(p);
     for (VadBlock &k : vad_blocks_) (void)hipHostFree(k.h);
     if (ws_g_) (void)hipFree(ws_g_);
@@ -390,9 +422,9 @@ Engine::~Engine()
     for (void *p : {(void *)w_, (void *)wh_, (void *)h_, (void *)c_, (void *)ring_, (void *)eout_, (void *)dout_, (void *)gstate_, (void *)cls_, (void *)ws_, (void *)xin_,
                     (void *)a3_, (void *)de_, (void *)logits_, (void *)rec_d_, (void *)counter_d_,
                     (void *)active_d_, (void *)dirty_d_, (void *)dec_slots_d_,
-                    (void *)ds_desc_[0], (void *)ds_desc_[1], (void *)ds_pcm_[0], (void *)ds_pcm_[1]})
+                    (void *)ds_pcm_[0], (void *)ds_pcm_[1]})
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)ring_h_, (void *)step_off_h_, (void *)rec_off_h_, (void *)rec_h_, (void *)logits_h_, (void *)hs_desc_[0], (void *)hs_desc_[1], (void *)hs_pcm_[0], (void *)hs_pcm_[1]})
+    for (void *p : {(void *)ring_h_, (void *)step_off_h_, (void *)rec_off_h_, (void *)rec_h_, (void *)logits_h_, (void *)hs_pcm_[0], (void *)hs_pcm_[1]})
         if (p) (void)hipHostFree(p);
     for (int b = 0; b < 2; ++b) if (fb_done_[b]) (void)hipEventDestroy(fb_done_[b]);
     for (int b = 0; b < 2; ++b) if (flight_done_[b]) (void)hipEventDestroy(flight_done_[b]);
@@ -462,9 +494,8 @@ void Engine::free_slot(int slot)
     // the slot goes back to the free list once it has been reset to the reference's calloc'd tensors (april_session.c:40-58)
     // and a [blank, blank] context -- in a batch: when 256 freed slots have gathered, when the free list runs dry, or before
     // the next flight is launched (begin_flight), stream-ordered ahead of any later use of the slot
-    if (conf_ever_.load(std::memory_order_relaxed)) set_slot_confidence(slot, 0);     // the next owner starts with confidences off
-    if (bias_ever_.load(std::memory_order_relaxed)) set_slot_bias(slot, nullptr);      // ... without a bias set, at the root
-    if (opt_ever_.load(std::memory_order_relaxed)) set_slot_search_options(slot, SearchOpt{0u, 0.0f});      // ... and without search options
+    // the next owner starts with confidences off, without a bias set (at the root) and without search options (dropped at the push while nothing was ever on)
+    set_slot_confidence(slot, 0); set_slot_bias(slot, nullptr); set_slot_search_options(slot, SearchOpt{0u, 0.0f});
     std::lock_guard<std::mutex> g(slot_mu_);
     zero_pending_.push_back(slot);
     --live_;
@@ -662,46 +693,29 @@ void Engine::collect_timing()
 }
 
 // ---------------------------------------------------------------- fbank
-void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<const int16_t *, size_t> *parts, size_t n_parts, size_t n_pcm, HostPool *pool)
+const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<const int16_t *, size_t> *parts, size_t n_parts, size_t n_pcm, HostPool *pool,
+                             const FrontPass &pass)
 {
-    const int n_rs = n_frames > 0 ? std::max(rs_n_, 0) : 0;
-    ResampleDesc *rs = rs_desc_;
-    const std::pair<const int16_t *, size_t> *in_parts = rs_in_parts_;
-    const size_t n_in_parts = n_rs ? rs_n_in_parts_ : 0, n_in = n_rs ? rs_n_in_ : 0;
-    rs_n_ = 0;
-    const int n_dc = n_frames > 0 ? std::max(dc_n_, 0) : 0;
-    const DecodeDesc *dc = dc_desc_;
-    const std::pair<const uint8_t *, size_t> *raw_parts = dc_raw_parts_;
-    const size_t n_raw_parts = n_dc ? dc_n_raw_parts_ : 0, n_raw = n_dc ? dc_n_raw_ : 0;
-    const size_t raw_units = n_dc ? (n_raw + 1) / 2 + 8 : 0;      // the raw region in int16 units, with its alignment
-    dc_n_ = 0;
-    const int n_vd = n_frames > 0 ? std::max(vad_n_, 0) : 0;
-    const VadDesc *vd = vad_desc_;
-    const size_t vd_frames = n_vd ? vad_pass_frames_ : 0;
-    vad_n_ = 0; vad_last_h_ = nullptr;
-    if (n_frames <= 0) return;
+    if (n_frames <= 0) return nullptr;
+    const int n_rs = std::max(pass.n_rs, 0), n_dc = std::max(pass.n_dc, 0), n_vd = std::max(pass.n_vd, 0);
+    ResampleDesc *rs = pass.rs;
+    const DecodeDesc *dc = pass.dc;
+    const size_t n_in_parts = n_rs ? pass.n_in_parts : 0, n_raw_parts = n_dc ? pass.n_raw_parts : 0, vd_frames = n_vd ? pass.vad_bytes : 0;
+    StagingCounts cnt;
+    cnt.n_pcm = n_pcm; cnt.n_in = n_rs ? pass.n_in : 0; cnt.n_raw = n_dc ? pass.n_raw : 0;
+    cnt.n_frames = (size_t)n_frames; cnt.n_rs = (size_t)n_rs; cnt.n_dc = (size_t)n_dc; cnt.n_vd = (size_t)n_vd;
+    const StagingSizes el{sizeof(FbankFrameDesc), sizeof(ResampleDesc), sizeof(DecodeDesc), sizeof(VadDesc)};
+    const StagingLayout lay = staging_layout(cnt, el);
     HIP_CHECK(hipSetDevice(cfg_.device));
-    for (int i = 0; i < n_rs; ++i) rs[i].taps = resample_table(rs_specs_[i]);      // (uploaded at a conversion's first use)
-    if (n_frames > desc_cap_ || n_pcm + n_in + raw_units > pcm_cap_ || (size_t)n_rs > rs_cap_ || (size_t)n_dc > dc_cap_ || (size_t)n_vd > vd_cap_) {
+    for (int i = 0; i < n_rs; ++i) rs[i].taps = resample_table(pass.rs_specs[i]);      // (uploaded at a conversion's first use)
+    if (!fb_caps_.holds(cnt, lay)) {
         sync();
         HipLegacyLock regrow_guard;                   // (frees imply a device synchronisation: not beside another engine's capture; order: capture_mu_, then this)
-        for (int b = 0; b < 2; ++b) {
-            if (hs_desc_[b]) { (void)hipHostFree(hs_desc_[b]); (void)hipFree(ds_desc_[b]); }
-            if (hs_pcm_[b]) { (void)hipHostFree(hs_pcm_[b]); (void)hipFree(ds_pcm_[b]); }
-        }
-        desc_cap_ = std::max({n_frames * 2, desc_cap_, 1024});
-        pcm_cap_ = std::max({(n_pcm + n_in + raw_units) * 2, pcm_cap_, (size_t)1 << 16});
-        rs_cap_ = std::max({(size_t)n_rs * 2, rs_cap_, n_rs ? (size_t)256 : (size_t)0});
-        dc_cap_ = std::max({(size_t)n_dc * 2, dc_cap_, n_dc ? (size_t)256 : (size_t)0});
-        vd_cap_ = std::max({(size_t)n_vd * 2, vd_cap_, n_vd ? (size_t)256 : (size_t)0});
-        // one staging buffer per flip: the PCM windows (model-rate regions, then the input-rate spans of resampled sessions), then
-        // (16-byte aligned) the raw bytes of formatted sessions, then (16-byte aligned, right behind the samples of THIS call) the
-        // frame descriptors, the resample descriptors, the decode descriptors and the VAD descriptors -> one host-to-device copy per call
-        const size_t units = pcm_cap_ + 8 + ((size_t)desc_cap_ * sizeof(FbankFrameDesc) + 1) / 2 + 8 + rs_cap_ * sizeof(ResampleDesc) / 2
-                             + 8 + dc_cap_ * sizeof(DecodeDesc) / 2 + 8 + vd_cap_ * sizeof(VadDesc) / 2;
+        for (int b = 0; b < 2; ++b) if (hs_pcm_[b]) { (void)hipHostFree(hs_pcm_[b]); (void)hipFree(ds_pcm_[b]); }
+        fb_caps_.grow(cnt, lay);
+        const size_t units = fb_caps_.units(el);
         for (int b = 0; b < 2; ++b) {
             hs_pcm_[b] = hmalloc<int16_t>(units); ds_pcm_[b] = dmalloc<int16_t>(units);
-            hs_desc_[b] = nullptr; ds_desc_[b] = nullptr;
             if (!fb_done_[b]) HIP_CHECK(hipEventCreateWithFlags(&fb_done_[b], hipEventDisableTiming));
         }
     }
@@ -730,16 +744,10 @@ void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<con
     const int b = fb_flip_;
     fb_flip_ ^= 1;
     HIP_CHECK(hipEventSynchronize(fb_done_[b]));          // the launch that used this pair two calls ago has consumed it
-    const size_t woff = ((n_pcm + n_in) * sizeof(int16_t) + 15) / 16 * 16;          // byte offset of the raw region (empty without formatted sessions)
-    const size_t doff = (woff + n_raw + 15) / 16 * 16;                              // ... of the descriptors
-    const size_t roff = (doff + (size_t)n_frames * sizeof(FbankFrameDesc) + 15) / 16 * 16;      // ... of the resample descriptors
-    const size_t coff = (roff + (size_t)n_rs * sizeof(ResampleDesc) + 15) / 16 * 16;            // ... and of the decode descriptors
-    const size_t voff = (coff + (size_t)n_dc * sizeof(DecodeDesc) + 15) / 16 * 16;              // ... and of the VAD descriptors
-    const size_t bytes = n_vd ? voff + (size_t)n_vd * sizeof(VadDesc) : n_dc ? coff + (size_t)n_dc * sizeof(DecodeDesc)
-                              : (n_rs ? roff + (size_t)n_rs * sizeof(ResampleDesc) : doff + (size_t)n_frames * sizeof(FbankFrameDesc));
+    const size_t woff = lay.raw, doff = lay.frames, roff = lay.rs, coff = lay.dc, voff = lay.vd, bytes = lay.bytes;      // (staging_layout.h)
     char *hs = reinterpret_cast<char *>(hs_pcm_[b]);
     memcpy(hs + doff, desc, (size_t)n_frames * sizeof(FbankFrameDesc));
-    if (n_vd) memcpy(hs + voff, vd, (size_t)n_vd * sizeof(VadDesc));
+    if (n_vd) memcpy(hs + voff, pass.vd, (size_t)n_vd * sizeof(VadDesc));
     ResampleArgs ra;
     if (n_rs) {
         ResampleDesc *hr = reinterpret_cast<ResampleDesc *>(hs + roff);
@@ -781,8 +789,8 @@ void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<con
         }
     };
     stage(parts, n_parts, 0);
-    if (n_in_parts) stage(in_parts, n_in_parts, n_pcm);
-    if (n_raw_parts) stage(raw_parts, n_raw_parts, woff);
+    if (n_in_parts) stage(pass.in_parts, n_in_parts, n_pcm);
+    if (n_raw_parts) stage(pass.raw_parts, n_raw_parts, woff);
     std::lock_guard<std::mutex> cg(capture_mu_);
     if (m_unseen_by_f_) { join(f_stream_, stream_); m_unseen_by_f_ = false; }      // (general-path work may still read ring rows this call overwrites)
     HIP_CHECK(hipMemcpyAsync(ds_pcm_[b], hs_pcm_[b], bytes, hipMemcpyHostToDevice, f_stream_));
@@ -814,11 +822,12 @@ void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<con
     }
     if (n_vd) {       // the pass's bytes -> its pinned block, in front of fb_done_; read after the flight's wait (close_flight)
         HIP_CHECK(hipMemcpyAsync(vblock->h, vad_out_d_, vd_frames, hipMemcpyDeviceToHost, f_stream_));
-        vad_last_h_ = vblock->h; vad_flight_ = true;
+        vad_flight_ = true;
         vad_launches_.fetch_add(1, std::memory_order_relaxed); vad_frames_.fetch_add(vd_frames, std::memory_order_relaxed);
     }
     HIP_CHECK(hipEventRecord(fb_done_[b], f_stream_));       // no host wait here: the encoder launches queue right behind
     f_unseen_by_m_ = true;
+    return vblock ? vblock->h : nullptr;
 }
 
 const float *Engine::resample_table(const ResampleSpec *spec)
@@ -1068,9 +1077,9 @@ void Engine::run_greedy_rounds(int n, const GreedyIo &io)
         a.logits_dump = io.dump ? io.dump + (size_t)round * n * d.vocab : nullptr;
         a.dec = dec_params(); a.de_out = dec_table_ ? nullptr : de_; a.ld_de = d.d_model;
         a.run_flags = flags_d_; a.rerun_flags = flags_d_ + 4;
-        a.conf_k = conf_k_d_; a.conf_ring = conf_d_;          // (null until a session of this engine asks for confidences)
-        a.bias_set = bias_set_d_; a.bias_state = bias_state_d_; a.bias_desc = bias_desc_d_;      // (null until a session of this engine has a bias set)
-        a.opt = opt_d_;                                       // (null until a session of this engine has search options)
+        a.conf_k = conf_k_.d; a.conf_ring = conf_d_;          // (null until a session of this engine asks for confidences)
+        a.bias_set = bias_set_.d; a.bias_state = bias_state_d_; a.bias_desc = bias_desc_.d;      // (null until a session of this engine has a bias set)
+        a.opt = opt_.d;                                        // (null until a session of this engine has search options)
         timed_begin(T_DEC); launch_decide(a, search_stream_); timed_end(T_DEC);
         if (!dec_table_) run_decproj(n, d_slots, dirty_d_, flags_d_ + 4 + round, gen);
     }
@@ -1595,7 +1604,7 @@ int Engine::stage_step(int m, int T, const int *slots, const int *ring_tails, co
     for (int t = 0; t < T; ++t) memcpy(blk + m + 2 * rows + (size_t)t * m, slots, (size_t)m * 4);
     step_off_h_[k] = (int)ring_pos_; rec_off_h_[k] = (int)rec_pos_;
     ring_pos_ += (size_t)m + (T ? 3 : 2) * rows; rec_pos_ += 3 * rows;
-    if (conf_k_h_) note_conf_step(k, slots, m, 3 * rows);
+    if (conf_k_.on()) note_conf_step(k, slots, m, 3 * rows);
     return k;
 }
 
@@ -1607,36 +1616,6 @@ void Engine::read_back_logits(int k, int rows, float *out)
     HIP_CHECK(hipMemcpyAsync(rec_h_ + rec_off_h_[k], rec_d_ + rec_off_h_[k], (size_t)3 * rows * sizeof(StepRecord), hipMemcpyDeviceToHost, stream_));
     sync();
     memcpy(out, logits_h_, n * 4);
-}
-
-// ---------------------------------------------------------------- confidences
-// Stepping thread, between two flights' enqueues.  The decision launches carry the per-slot K bytes and the side ring as kernel
-// arguments, null while nobody has opted in: graphs captured until then hold the null pointers, so the first opt-in drops every
-// captured graph (they are captured again at their next use) after the streams have drained.  From then on the pointers never change.
-void Engine::apply_confidence_pending()
-{
-    std::vector<std::pair<int, int>> todo;
-    { std::lock_guard<std::mutex> g(conf_mu_); todo.swap(conf_pending_); conf_has_pending_.store(false, std::memory_order_release); }
-    if (!conf_k_h_) {
-        bool any = false;
-        for (const auto &t : todo) any = any || t.second > 0;
-        if (!any) return;
-        std::lock_guard<std::mutex> cg(capture_mu_);
-        HipLegacyLock legacy;
-        sync();
-        drop_graphs();
-        const size_t S = (size_t)cfg_.max_slots;
-        conf_k_d_ = dmalloc<uint8_t>(S); conf_k_h_ = hmalloc<uint8_t>(S);
-        memset(conf_k_h_, 0, S);
-        conf_d_ = dmalloc<ConfRecord>(2 * rec_cap_); conf_h_ = hmalloc<ConfRecord>(2 * rec_cap_);
-        LOGI("engine: confidences on (side ring %.0f MB on the device and pinned)", 2.0 * rec_cap_ * sizeof(ConfRecord) / 1e6);
-    }
-    for (const auto &t : todo) if (t.first >= 0 && t.first < cfg_.max_slots) conf_k_h_[t.first] = (uint8_t)t.second;
-    // whole table, stream-ordered ahead of this flight's steps.  Slots of other sessions keep their values (a flight still in
-    // the air reads the same bytes before and after); the slots that change belong to idle sessions.
-    std::lock_guard<std::mutex> cg(capture_mu_);
-    m_touched();
-    HIP_CHECK(hipMemcpyAsync(conf_k_d_, conf_k_h_, (size_t)cfg_.max_slots, hipMemcpyHostToDevice, stream_));
 }
 
 void Engine::drop_graphs()
@@ -1666,87 +1645,86 @@ BiasDesc Engine::upload_bias(const BiasSet &set, void **dev, hipStream_t st)
     return d;
 }
 
-// Stepping thread, between two flights' enqueues (as apply_confidence_pending).  The slots that change belong to idle sessions, so
-// no flight in the air reads their entries; a set nobody uses any more is read by no flight either.
-void Engine::apply_bias_pending()
+// ---------------------------------------------------------------- slot tables (DESIGN.md sections 12-14)
+// Stepping thread, between two flights' enqueues: the queued changes of the three per-slot opt-in tables -> the tables.  The decision
+// launches carry the tables (and the side ring) as kernel arguments, null while nobody has opted in: graphs captured until then hold
+// the null pointers, so a table's first opt-in drops every captured graph (they are captured again at their next use) after the streams
+// have drained -- once per call, however many tables turn on in it.  From then on the pointers never change.  The whole table is
+// uploaded, stream-ordered ahead of this flight's steps: the slots that change belong to idle sessions, so no flight in the air reads
+// their entries, and the other slots keep their values; a bias set nobody uses any more is read by no flight either.
+// LOCK ORDER, here and everywhere: bias_q_.mutex() (the bias books; read_bias_state holds it over its read) -> capture_mu_ -> the
+// process-wide legacy-stream lock (step() and the debug entry points take the last two in that order).  The mutexes inside conf_q_ and
+// opt_q_ are leaves: held for a push or a take, nothing is locked under them.
+void Engine::apply_slot_tables()
 {
-    std::lock_guard<std::mutex> bg(bias_mu_);
-    std::vector<std::pair<int, int>> todo;
-    todo.swap(bias_pending_);
-    bias_has_pending_.store(false, std::memory_order_release);
+    std::lock_guard<std::mutex> bg(bias_q_.mutex());
+    const auto bias_todo = bias_q_.take_locked();
+    const auto conf_todo = conf_q_.take();
+    const auto opt_todo = opt_q_.take();
+    const size_t S = (size_t)cfg_.max_slots;
+    auto in_range = [S](int slot) { return slot >= 0 && (size_t)slot < S; };
+    const bool conf_first = !conf_k_.on() && std::any_of(conf_todo.begin(), conf_todo.end(), [](const std::pair<int, int> &t) { return t.second > 0; });
+    const bool bias_first = !bias_set_.on() && std::any_of(bias_todo.begin(), bias_todo.end(), [](const std::pair<int, int> &t) { return t.second >= 0; });
+    const bool opt_first = !opt_.on() && std::any_of(opt_todo.begin(), opt_todo.end(), [](const std::pair<int, SearchOpt> &t) { return t.second.endpoint_ms != 0; });
     std::lock_guard<std::mutex> cg(capture_mu_);
-    m_touched();
-    if (!bias_set_h_) {
-        bool any = false;
-        for (const auto &t : todo) any = any || t.second >= 0;
-        if (!any) return;
+    if (conf_first || bias_first || opt_first) {
         HipLegacyLock legacy;
         sync();
         drop_graphs();
-        const size_t S = (size_t)cfg_.max_slots;
-        bias_set_d_ = dmalloc<int32_t>(S); bias_set_h_ = hmalloc<int32_t>(S); bias_state_d_ = dmalloc<int32_t>(S);
-        bias_desc_d_ = dmalloc<BiasDesc>(kBiasSets); bias_desc_h_ = hmalloc<BiasDesc>(kBiasSets);
-        for (size_t i = 0; i < S; ++i) bias_set_h_[i] = -1;
-        for (int i = 0; i < kBiasSets; ++i) bias_desc_h_[i] = BiasDesc();
-        HIP_CHECK(hipMemsetAsync(bias_state_d_, 0, S * 4, stream_));
-        LOGI("engine: phrase boosting on");
-    }
-    bool tables = false;
-    for (int i = 0; i < kBiasSets; ++i) {
-        BiasEntry &b = bias_sets_[(size_t)i];
-        if (b.set && b.users > 0 && !b.dev) {                     // first use on this engine
-            HipLegacyLock legacy;
-            bias_desc_h_[i] = upload_bias(*b.set, &b.dev, stream_);
-            HIP_CHECK(hipStreamSynchronize(stream_));             // (the source is pageable memory; rare)
-            tables = true;
-        } else if (b.set && b.users == 0) {                       // the last slot has let go of it
-            if (b.dev) { HipLegacyLock legacy; sync_streams(); (void)hipFree(b.dev); b.dev = nullptr; }
-            bias_desc_h_[i] = BiasDesc();
-            b.set.reset();
-            tables = true;
+        if (conf_first) {
+            conf_k_.alloc(S, 0);
+            conf_d_ = dmalloc<ConfRecord>(2 * rec_cap_); conf_h_ = hmalloc<ConfRecord>(2 * rec_cap_);
+            LOGI("engine: confidences on (side ring %.0f MB on the device and pinned)", 2.0 * rec_cap_ * sizeof(ConfRecord) / 1e6);
         }
+        if (bias_first) {
+            bias_set_.alloc(S, -1); bias_desc_.alloc(kBiasSets, BiasDesc()); bias_state_d_ = dmalloc<int32_t>(S);
+            LOGI("engine: phrase boosting on");
+        }
+        if (opt_first) { opt_.alloc(S, SearchOpt{0u, 0.0f}); LOGI("engine: search options on"); }
     }
-    for (const auto &t : todo) {
-        bias_set_h_[t.first] = t.second;
-        HIP_CHECK(hipMemsetAsync(bias_state_d_ + t.first, 0, 4, stream_));      // every change starts at the root
-    }
-    // whole tables, stream-ordered ahead of this flight's steps; entries of other sessions keep their values
-    if (tables) HIP_CHECK(hipMemcpyAsync(bias_desc_d_, bias_desc_h_, sizeof(BiasDesc) * kBiasSets, hipMemcpyHostToDevice, stream_));
-    HIP_CHECK(hipMemcpyAsync(bias_set_d_, bias_set_h_, (size_t)cfg_.max_slots * 4, hipMemcpyHostToDevice, stream_));
-}
-
-// ---------------------------------------------------------------- search options
-// Stepping thread, between two flights' enqueues (as apply_confidence_pending): the first opt-in drops the captured graphs, whose
-// decision launches hold the null pointer; from then on the pointer never changes.  The slots that change belong to idle sessions.
-void Engine::apply_search_options_pending()
-{
-    std::vector<std::pair<int, SearchOpt>> todo;
-    { std::lock_guard<std::mutex> g(opt_mu_); todo.swap(opt_pending_); opt_has_pending_.store(false, std::memory_order_release); }
-    if (!opt_h_) {
-        bool any = false;
-        for (const auto &t : todo) any = any || t.second.endpoint_ms != 0;
-        if (!any) return;
-        std::lock_guard<std::mutex> cg(capture_mu_);
-        HipLegacyLock legacy;
-        sync();
-        drop_graphs();
-        const size_t S = (size_t)cfg_.max_slots;
-        opt_d_ = dmalloc<SearchOpt>(S); opt_h_ = hmalloc<SearchOpt>(S);
-        memset(opt_h_, 0, S * sizeof(SearchOpt));
-        LOGI("engine: search options on");
-    }
-    for (const auto &t : todo) if (t.first >= 0 && t.first < cfg_.max_slots) opt_h_[t.first] = t.second;
-    // whole table, stream-ordered ahead of this flight's steps; entries of other sessions keep their values
-    std::lock_guard<std::mutex> cg(capture_mu_);
+    const bool conf_up = conf_k_.on() && !conf_todo.empty(), bias_up = bias_set_.on() && !bias_todo.empty(), opt_up = opt_.on() && !opt_todo.empty();
+    if (!conf_up && !bias_up && !opt_up) return;
     m_touched();
-    HIP_CHECK(hipMemcpyAsync(opt_d_, opt_h_, (size_t)cfg_.max_slots * sizeof(SearchOpt), hipMemcpyHostToDevice, stream_));
+    if (conf_up) {
+        for (const auto &t : conf_todo) if (in_range(t.first)) conf_k_.h[t.first] = (uint8_t)t.second;
+        conf_k_.upload(stream_);
+    }
+    if (bias_up) {
+        if (bias_first) HIP_CHECK(hipMemsetAsync(bias_state_d_, 0, S * 4, stream_));
+        bool sets = false;
+        for (int i = 0; i < kBiasSets; ++i) {
+            BiasEntry &b = bias_sets_[(size_t)i];
+            if (b.set && b.users > 0 && !b.dev) {                     // first use on this engine
+                HipLegacyLock legacy;
+                bias_desc_.h[i] = upload_bias(*b.set, &b.dev, stream_);
+                HIP_CHECK(hipStreamSynchronize(stream_));             // (the source is pageable memory; rare)
+                sets = true;
+            } else if (b.set && b.users == 0) {                       // the last slot has let go of it
+                if (b.dev) { HipLegacyLock legacy; sync_streams(); (void)hipFree(b.dev); b.dev = nullptr; }
+                bias_desc_.h[i] = BiasDesc();
+                b.set.reset();
+                sets = true;
+            }
+        }
+        for (const auto &t : bias_todo) {
+            if (!in_range(t.first)) continue;
+            bias_set_.h[t.first] = t.second;
+            HIP_CHECK(hipMemsetAsync(bias_state_d_ + t.first, 0, 4, stream_));      // every change starts at the root
+        }
+        if (sets) bias_desc_.upload(stream_);
+        bias_set_.upload(stream_);
+    }
+    if (opt_up) {
+        for (const auto &t : opt_todo) if (in_range(t.first)) opt_.h[t.first] = t.second;
+        opt_.upload(stream_);
+    }
 }
 
 int Engine::read_bias_state(int slot)
 {
-    if (!bias_ever_.load(std::memory_order_relaxed)) return 0;
-    std::lock_guard<std::mutex> bg(bias_mu_);             // (apply_bias_pending allocates the table under it)
-    for (const auto &t : bias_pending_) if (t.first == slot) return 0;
+    if (!bias_q_.ever()) return 0;
+    std::lock_guard<std::mutex> bg(bias_q_.mutex());      // (apply_slot_tables allocates the table under it)
+    if (bias_q_.pending_locked(slot)) return 0;
     HipLegacyLock legacy;
     HIP_CHECK(hipSetDevice(cfg_.device));
     sync_streams();
@@ -1758,7 +1736,7 @@ int Engine::read_bias_state(int slot)
 void Engine::note_conf_step(int k, const int *slots, int m, size_t records)
 {
     bool any = false;
-    for (int i = 0; i < m && !any; ++i) any = conf_k_h_[slots[i]] != 0;
+    for (int i = 0; i < m && !any; ++i) any = conf_k_.h[slots[i]] != 0;
     if (!any) return;
     const size_t first = (size_t)rec_off_h_[k];
     if (!conf_spans_.empty() && conf_spans_.back().first + conf_spans_.back().second == first) conf_spans_.back().second += records;
@@ -1784,9 +1762,7 @@ void Engine::begin_flight()
     // previous one: it must have completed -- the scheduler keeps at most two flights open and completes them in order, so the event
     // is done long ago and this costs nothing; any other caller would silently overwrite an in-flight search
     if (flight_open_[p]) { HIP_CHECK(hipEventSynchronize(flight_done_[p])); flight_open_[p] = false; }
-    if (conf_has_pending_.load(std::memory_order_acquire)) apply_confidence_pending();
-    if (bias_has_pending_.load(std::memory_order_acquire)) apply_bias_pending();
-    if (opt_has_pending_.load(std::memory_order_acquire)) apply_search_options_pending();
+    if (conf_q_.has_pending() || bias_q_.has_pending() || opt_q_.has_pending()) apply_slot_tables();
     conf_spans_.clear();
     ring_base_ = (size_t)p * ring_cap_; rec_base_ = (size_t)p * rec_cap_;
     ring_pos_ = ring_base_; rec_pos_ = rec_base_; flight_steps_ = 0;
@@ -1906,7 +1882,7 @@ void Engine::zero_slots(int n)
 
 void Engine::debug_encoder(int n, const float *x, const float *h, const float *c, float *eout, float *h2, float *c2)
 {
-    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order everywhere: bias_mu_ first where it is needed -- apply_bias_pending, read_bias_state --, then capture_mu_, then the process-wide legacy-stream lock; step() takes the last two in that order)
+    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order: apply_slot_tables)
     HipLegacyLock legacy;
     HIP_CHECK(hipSetDevice(cfg_.device));
     const NetDims &d = L_.dims;
@@ -1940,7 +1916,7 @@ void Engine::debug_encoder(int n, const float *x, const float *h, const float *c
 
 void Engine::debug_decoder(int n, const int64_t *ctx, float *dout)
 {
-    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order everywhere: bias_mu_ first where it is needed -- apply_bias_pending, read_bias_state --, then capture_mu_, then the process-wide legacy-stream lock; step() takes the last two in that order)
+    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order: apply_slot_tables)
     HipLegacyLock legacy;
     HIP_CHECK(hipSetDevice(cfg_.device));
     const NetDims &d = L_.dims;
@@ -1971,7 +1947,7 @@ void Engine::debug_decoder(int n, const int64_t *ctx, float *dout)
 
 void Engine::debug_joiner(int n, const float *eout, const float *dout, float *logits)
 {
-    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order everywhere: bias_mu_ first where it is needed -- apply_bias_pending, read_bias_state --, then capture_mu_, then the process-wide legacy-stream lock; step() takes the last two in that order)
+    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order: apply_slot_tables)
     HipLegacyLock legacy;
     const NetDims &d = L_.dims;
     HIP_CHECK(hipSetDevice(cfg_.device));
@@ -1997,140 +1973,64 @@ void Engine::debug_joiner(int n, const float *eout, const float *dout, float *lo
     zero_slots(n);
 }
 
-void Engine::debug_decide(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out)
+// slots 0..n-1, row i = slot i; the bias tables and the option table are the call's own
+void Engine::debug_decide(const DecideRequest &q)
 {
-    debug_decide_impl(n, op, logits, early_emit, now_ms, round, state_io, rec_out, nullptr, nullptr);
-}
-
-void Engine::debug_decide_biased(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
-                                 const BiasSet &set, int32_t *bias_state_io)
-{
-    debug_decide_impl(n, op, logits, early_emit, now_ms, round, state_io, rec_out, &set, bias_state_io);
-}
-
-void Engine::debug_decide_opts(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
-                               const BiasSet *set, int32_t *bias_state_io, const SearchOpt *opts)
-{
-    debug_decide_impl(n, op, logits, early_emit, now_ms, round, state_io, rec_out, set, bias_state_io, opts);
-}
-
-// `set` non-null: tables of its own for the call -- row i uses the set from state bias_state_io[i], or none when that is -1
-// `opts` non-null: a table of its own likewise -- row i (= slot i) has opts[i]
-void Engine::debug_decide_impl(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
-                               const BiasSet *set, int32_t *bias_state_io, const SearchOpt *opts)
-{
-    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order everywhere: bias_mu_ first where it is needed -- apply_bias_pending, read_bias_state --, then capture_mu_, then the process-wide legacy-stream lock; step() takes the last two in that order)
+    std::lock_guard<std::mutex> cg(capture_mu_);      // (lock order: apply_slot_tables)
     HipLegacyLock legacy;
     const NetDims &d = L_.dims;
+    const int n = q.n;
     HIP_CHECK(hipSetDevice(cfg_.device));
     if (n > cfg_.max_batch || n > cfg_.max_slots) { LOGE("debug_decide: n too large"); abort(); }
     static_assert(sizeof(GreedyState) == 16, "GreedyState is 4 x int32 in the ABI");
-    std::vector<int> slots((size_t)n);
+    DeviceScratch ds;
+    std::vector<int> slots((size_t)n), ones((size_t)n, 1), zeros((size_t)n, 0);
     for (int i = 0; i < n; ++i) slots[(size_t)i] = i;
-    int *slots_d = dmalloc<int>((size_t)n), *now_d = dmalloc<int>((size_t)n), *active_d = dmalloc<int>((size_t)n), *dirty_d = dmalloc<int>((size_t)n);
-    StepRecord *rec_d = dmalloc<StepRecord>((size_t)n);
-    HIP_CHECK(hipMemcpy(slots_d, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(gstate_, state_io, (size_t)n * sizeof(GreedyState), hipMemcpyHostToDevice));
-    int32_t *bset_d = nullptr, *bstate_d = nullptr; BiasDesc *bdesc_d = nullptr; void *barrays_d = nullptr;
-    if (set) {
+    const int *slots_d = ds.upload(slots.data(), slots.size());
+    if (q.state_io) HIP_CHECK(hipMemcpy(gstate_, q.state_io, (size_t)n * sizeof(GreedyState), hipMemcpyHostToDevice));
+    int32_t *bset_d = nullptr, *bstate_d = nullptr; BiasDesc *bdesc_d = nullptr;
+    if (q.set) {
         std::vector<int32_t> bset((size_t)n), bstate((size_t)n);
-        for (int i = 0; i < n; ++i) { bset[(size_t)i] = bias_state_io[i] < 0 ? -1 : 0; bstate[(size_t)i] = std::max(0, bias_state_io[i]); }
-        bset_d = dmalloc<int32_t>((size_t)n); bstate_d = dmalloc<int32_t>((size_t)n); bdesc_d = dmalloc<BiasDesc>(1);
-        const BiasDesc desc = upload_bias(*set, &barrays_d, stream_);
+        for (int i = 0; i < n; ++i) { bset[(size_t)i] = q.bias_state_io[i] < 0 ? -1 : 0; bstate[(size_t)i] = std::max(0, q.bias_state_io[i]); }
+        void *arrays = nullptr;
+        const BiasDesc desc = upload_bias(*q.set, &arrays, stream_);
+        ds.adopt(arrays);
         HIP_CHECK(hipStreamSynchronize(stream_));
-        HIP_CHECK(hipMemcpy(bset_d, bset.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(bstate_d, bstate.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(bdesc_d, &desc, sizeof desc, hipMemcpyHostToDevice));
+        bset_d = ds.upload(bset.data(), bset.size()); bstate_d = ds.upload(bstate.data(), bstate.size()); bdesc_d = ds.upload(&desc, 1);
     }
-    SearchOpt *opt_d = nullptr;
-    if (opts) {
-        opt_d = dmalloc<SearchOpt>((size_t)n);
-        HIP_CHECK(hipMemcpy(opt_d, opts, (size_t)n * sizeof(SearchOpt), hipMemcpyHostToDevice));
-    }
-    if (op == 1) {
+    const SearchOpt *opt_d = q.opts ? ds.upload(q.opts, (size_t)n) : nullptr;
+    if (q.op == 1) {
         DecRowsArgs a; a.slot_idx = slots_d; a.M = n; a.op = 1; a.blank = P_.blank_id; a.state = gstate_; a.dec = dec_params(); a.de_out = nullptr;
         a.bias_state = bstate_d;
         launch_dec_rows(a, stream_);
     } else {
         // the logits enter as ONE partial plane with a zero bias: decide_kernel's tree sum + bias returns them unchanged
         std::vector<float> plane((size_t)n * L_.vocab_pad, -1000.0f);
-        for (int i = 0; i < n; ++i) memcpy(plane.data() + (size_t)i * L_.vocab_pad, logits + (size_t)i * d.vocab, (size_t)d.vocab * 4);
-        float *plane_d = dmalloc<float>(plane.size()), *zero_d = dmalloc<float>((size_t)L_.vocab_pad);
-        HIP_CHECK(hipMemcpy(plane_d, plane.data(), plane.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(zero_d, 0, (size_t)L_.vocab_pad * 4));
-        std::vector<int> gen((size_t)n, 1);
-        HIP_CHECK(hipMemcpy(active_d, gen.data(), (size_t)n * 4, hipMemcpyHostToDevice));      // every row still searches
-        HIP_CHECK(hipMemcpy(now_d, now_ms, (size_t)n * 4, hipMemcpyHostToDevice));
+        for (int i = 0; i < n; ++i) memcpy(plane.data() + (size_t)i * L_.vocab_pad, q.logits + (size_t)i * d.vocab, (size_t)d.vocab * 4);
+        StepRecord *rec_d = ds.alloc<StepRecord>((size_t)n);
+        ConfRecord *conf_d = q.conf_k > 0 ? ds.zeros<ConfRecord>((size_t)n) : nullptr;
         DecideArgs a;
-        a.ws = plane_d; a.parts = 1; a.m_stride = n; a.N = L_.vocab_pad; a.M = n; a.n_valid = d.vocab;
-        a.bias = zero_d; a.blank = P_.blank_id; a.early_emit = early_emit;
-        a.slot_idx = slots_d; a.now_ms = now_d; a.active = active_d; a.dirty = dirty_d; a.tok_class = cls_; a.state = gstate_;
-        a.rec = rec_d; a.round = round; a.gen = 1; a.dec = dec_params(); a.de_out = nullptr;
+        a.ws = ds.upload(plane.data(), plane.size()); a.parts = 1; a.m_stride = n; a.N = L_.vocab_pad; a.M = n; a.n_valid = d.vocab;
+        a.bias = ds.zeros<float>((size_t)L_.vocab_pad); a.blank = P_.blank_id; a.early_emit = q.early_emit;
+        a.slot_idx = slots_d; a.now_ms = ds.upload(q.now_ms ? q.now_ms : zeros.data(), (size_t)n);
+        a.active = ds.upload(ones.data(), ones.size());      // every row still searches
+        a.dirty = ds.alloc<int>((size_t)n); a.tok_class = cls_; a.state = gstate_;
+        a.rec = rec_d; a.round = q.round; a.gen = 1; a.dec = dec_params(); a.de_out = nullptr;
         a.bias_set = bset_d; a.bias_state = bstate_d; a.bias_desc = bdesc_d;
         a.opt = opt_d;
+        if (conf_d) { a.conf = conf_d; a.conf_k_all = q.conf_k; }
         launch_decide(a, stream_);
         sync();
-        HIP_CHECK(hipMemcpy(rec_out, rec_d, (size_t)n * sizeof(StepRecord), hipMemcpyDeviceToHost));
-        (void)hipFree(plane_d); (void)hipFree(zero_d);
+        if (q.rec_out) HIP_CHECK(hipMemcpy(q.rec_out, rec_d, (size_t)n * sizeof(StepRecord), hipMemcpyDeviceToHost));
+        if (conf_d) HIP_CHECK(hipMemcpy(q.conf_out, conf_d, (size_t)n * sizeof(ConfRecord), hipMemcpyDeviceToHost));
     }
     sync();
-    HIP_CHECK(hipMemcpy(state_io, gstate_, (size_t)n * sizeof(GreedyState), hipMemcpyDeviceToHost));
-    if (set) {
+    if (q.state_io) HIP_CHECK(hipMemcpy(q.state_io, gstate_, (size_t)n * sizeof(GreedyState), hipMemcpyDeviceToHost));
+    if (q.set) {
         std::vector<int32_t> bstate((size_t)n);
         HIP_CHECK(hipMemcpy(bstate.data(), bstate_d, (size_t)n * 4, hipMemcpyDeviceToHost));
-        for (int i = 0; i < n; ++i) if (bias_state_io[i] >= 0) bias_state_io[i] = bstate[(size_t)i];
-        for (void *p : {(void *)bset_d, (void *)bstate_d, (void *)bdesc_d, barrays_d}) (void)hipFree(p);
+        for (int i = 0; i < n; ++i) if (q.bias_state_io[i] >= 0) q.bias_state_io[i] = bstate[(size_t)i];
     }
-    if (opt_d) (void)hipFree(opt_d);
-    (void)hipFree(slots_d); (void)hipFree(now_d); (void)hipFree(active_d); (void)hipFree(dirty_d); (void)hipFree(rec_d);
-    zero_slots(n);
-}
-
-void Engine::debug_confidence(int n, const float *logits, int k, ConfRecord *out, const BiasSet *set, const int32_t *bias_state)
-{
-    std::lock_guard<std::mutex> cg(capture_mu_);
-    HipLegacyLock legacy;
-    const NetDims &d = L_.dims;
-    HIP_CHECK(hipSetDevice(cfg_.device));
-    if (n > cfg_.max_batch || n > cfg_.max_slots) { LOGE("debug_confidence: n too large"); abort(); }
-    std::vector<int> slots((size_t)n), zeros((size_t)n, 0), gen((size_t)n, 1);
-    for (int i = 0; i < n; ++i) slots[(size_t)i] = i;
-    int *slots_d = dmalloc<int>((size_t)n), *now_d = dmalloc<int>((size_t)n), *active_d = dmalloc<int>((size_t)n), *dirty_d = dmalloc<int>((size_t)n);
-    StepRecord *rec_d = dmalloc<StepRecord>((size_t)n);
-    ConfRecord *conf_d = dmalloc<ConfRecord>((size_t)n);
-    // as debug_decide: the logits enter as ONE partial plane with a zero bias, so the kernel sees them unchanged
-    std::vector<float> plane((size_t)n * L_.vocab_pad, -1000.0f);
-    for (int i = 0; i < n; ++i) memcpy(plane.data() + (size_t)i * L_.vocab_pad, logits + (size_t)i * d.vocab, (size_t)d.vocab * 4);
-    float *plane_d = dmalloc<float>(plane.size()), *zero_d = dmalloc<float>((size_t)L_.vocab_pad);
-    HIP_CHECK(hipMemcpy(slots_d, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(plane_d, plane.data(), plane.size() * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemset(zero_d, 0, (size_t)L_.vocab_pad * 4));
-    HIP_CHECK(hipMemset(conf_d, 0, (size_t)n * sizeof(ConfRecord)));
-    HIP_CHECK(hipMemcpy(active_d, gen.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(now_d, zeros.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    DecideArgs a;
-    a.ws = plane_d; a.parts = 1; a.m_stride = n; a.N = L_.vocab_pad; a.M = n; a.n_valid = d.vocab;
-    a.bias = zero_d; a.blank = P_.blank_id; a.early_emit = 1.0f;
-    a.slot_idx = slots_d; a.now_ms = now_d; a.active = active_d; a.dirty = dirty_d; a.tok_class = cls_; a.state = gstate_;
-    a.rec = rec_d; a.round = 0; a.gen = 1; a.dec = dec_params(); a.de_out = nullptr;
-    a.conf = conf_d; a.conf_k_all = k;
-    int32_t *bset_d = nullptr, *bstate_d = nullptr; BiasDesc *bdesc_d = nullptr; void *barrays_d = nullptr;
-    if (set) {                                             // tables of its own for the call, as debug_decide_impl
-        std::vector<int32_t> bset((size_t)n), bstate((size_t)n);
-        for (int i = 0; i < n; ++i) { bset[(size_t)i] = bias_state[i] < 0 ? -1 : 0; bstate[(size_t)i] = std::max(0, bias_state[i]); }
-        bset_d = dmalloc<int32_t>((size_t)n); bstate_d = dmalloc<int32_t>((size_t)n); bdesc_d = dmalloc<BiasDesc>(1);
-        const BiasDesc desc = upload_bias(*set, &barrays_d, stream_);
-        HIP_CHECK(hipStreamSynchronize(stream_));
-        HIP_CHECK(hipMemcpy(bset_d, bset.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(bstate_d, bstate.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(bdesc_d, &desc, sizeof desc, hipMemcpyHostToDevice));
-        a.bias_set = bset_d; a.bias_state = bstate_d; a.bias_desc = bdesc_d;
-    }
-    launch_decide(a, stream_);
-    sync();
-    HIP_CHECK(hipMemcpy(out, conf_d, (size_t)n * sizeof(ConfRecord), hipMemcpyDeviceToHost));
-    if (set) for (void *p : {(void *)bset_d, (void *)bstate_d, (void *)bdesc_d, barrays_d}) (void)hipFree(p);
-    for (void *p : {(void *)slots_d, (void *)now_d, (void *)active_d, (void *)dirty_d, (void *)rec_d, (void *)conf_d, (void *)plane_d, (void *)zero_d}) (void)hipFree(p);
     zero_slots(n);
 }
 
@@ -2155,24 +2055,18 @@ void Engine::debug_resample(const ResampleSpec *spec, const int16_t *pcm, size_t
     const float *taps = resample_table(spec);
     HipLegacyLock legacy;
     HIP_CHECK(hipSetDevice(cfg_.device));
-    int16_t *d = dmalloc<int16_t>(n + n_out);
-    ResampleDesc *dd = dmalloc<ResampleDesc>(1);
+    DeviceScratch ds;
+    int16_t *d = ds.alloc<int16_t>(n + n_out);
     ResampleDesc r;
     r.taps = taps; r.in_base = 0; r.out_first = 0; r.out_end = (int64_t)n_out;
     r.in_off = 0; r.in_n = (int32_t)n; r.out_dst = (int32_t)n; r.out_cnt = (int32_t)n_out;
     r.L = spec->L; r.M = spec->M; r.K = spec->K; r.ldt = spec->ldt;
     if (n) HIP_CHECK(hipMemcpy(d, pcm, n * sizeof(int16_t), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dd, &r, sizeof r, hipMemcpyHostToDevice));
     ResampleArgs a;
-    a.in = d; a.out = d; a.desc = dd; a.n_desc = 1;
+    a.in = d; a.out = d; a.desc = ds.upload(&r, 1); a.n_desc = 1;
     a.max_blocks = (int)((n_out + kResampleBlock - 1) / kResampleBlock); a.lds_floats = (int)resample_lds_floats(spec->L, spec->M, spec->K);
-    hipStream_t st = nullptr;                 // (its own stream: live sessions' work on the engine's streams is neither waited for nor delayed)
-    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    launch_resample(a, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-    HIP_CHECK(hipStreamDestroy(st));
+    run_on_private_stream([&](hipStream_t st) { launch_resample(a, st); });
     HIP_CHECK(hipMemcpy(out, d + n, n_out * sizeof(int16_t), hipMemcpyDeviceToHost));
-    (void)hipFree(d); (void)hipFree(dd);
 }
 
 void Engine::debug_decode(uint32_t encoding, uint32_t channels, int32_t channel, const void *data, size_t n_frames, int16_t *out)
@@ -2181,23 +2075,17 @@ void Engine::debug_decode(uint32_t encoding, uint32_t channels, int32_t channel,
     const size_t bytes = n_frames * channels * encoding_bytes(encoding);
     HipLegacyLock legacy;
     HIP_CHECK(hipSetDevice(cfg_.device));
-    uint8_t *d = dmalloc<uint8_t>((bytes + 15) / 16 * 16 + n_frames * sizeof(int16_t));      // (hipMalloc: aligned far beyond the contract's 4 bytes)
-    DecodeDesc *dd = dmalloc<DecodeDesc>(1);
+    DeviceScratch ds;
+    uint8_t *d = ds.alloc<uint8_t>((bytes + 15) / 16 * 16 + n_frames * sizeof(int16_t));      // (hipMalloc: aligned far beyond the contract's 4 bytes)
     DecodeDesc r;
     r.src_off = 0; r.dst = 0; r.out_cnt = r.n_src = (int32_t)n_frames;
     r.encoding = (uint8_t)encoding; r.channels = (uint8_t)channels; r.channel = (int8_t)channel;
     HIP_CHECK(hipMemcpy(d, data, bytes, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dd, &r, sizeof r, hipMemcpyHostToDevice));
     DecodeArgs a;
-    a.raw = d; a.out = reinterpret_cast<int16_t *>(d + (bytes + 15) / 16 * 16); a.desc = dd; a.n_desc = 1;
+    a.raw = d; a.out = reinterpret_cast<int16_t *>(d + (bytes + 15) / 16 * 16); a.desc = ds.upload(&r, 1); a.n_desc = 1;
     a.max_blocks = (int)((n_frames + kDecodeBlock - 1) / kDecodeBlock);
-    hipStream_t st = nullptr;                 // (its own stream, as debug_resample)
-    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    launch_decode(a, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-    HIP_CHECK(hipStreamDestroy(st));
+    run_on_private_stream([&](hipStream_t st) { launch_decode(a, st); });
     HIP_CHECK(hipMemcpy(out, a.out, n_frames * sizeof(int16_t), hipMemcpyDeviceToHost));
-    (void)hipFree(d); (void)hipFree(dd);
 }
 
 void Engine::debug_vad(int n_runs, const VadPlan *plans, const int32_t *n, const int32_t *first_row, int ring_rows, const float *rows, VadState *states_io,
@@ -2216,24 +2104,17 @@ void Engine::debug_vad(int n_runs, const VadPlan *plans, const int32_t *n, const
     }
     HipLegacyLock legacy;
     HIP_CHECK(hipSetDevice(cfg_.device));
-    float *ring_d = dmalloc<float>(ring.size()), *en_d = dmalloc<float>(total);
-    VadDesc *desc_d = dmalloc<VadDesc>((size_t)n_runs);
-    VadState *st_d = dmalloc<VadState>((size_t)n_runs);
-    uint8_t *out_d = dmalloc<uint8_t>(total);
-    HIP_CHECK(hipMemcpy(ring_d, ring.data(), ring.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(desc_d, desc.data(), desc.size() * sizeof(VadDesc), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(st_d, states_io, (size_t)n_runs * sizeof(VadState), hipMemcpyHostToDevice));
+    DeviceScratch ds;
+    float *en_d = ds.alloc<float>(total);
+    VadState *st_d = ds.upload(states_io, (size_t)n_runs);
+    uint8_t *out_d = ds.alloc<uint8_t>(total);
     VadArgs a;
-    a.ring = ring_d; a.ring_frames = ring_rows; a.nbins = ft_.nbins; a.desc = desc_d; a.n_desc = n_runs; a.state = st_d; a.out = out_d; a.energy = en_d;
-    hipStream_t st = nullptr;                 // (its own stream, as debug_resample)
-    HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    launch_vad(a, st);
-    HIP_CHECK(hipStreamSynchronize(st));
-    HIP_CHECK(hipStreamDestroy(st));
+    a.ring = ds.upload(ring.data(), ring.size()); a.ring_frames = ring_rows; a.nbins = ft_.nbins; a.desc = ds.upload(desc.data(), desc.size()); a.n_desc = n_runs;
+    a.state = st_d; a.out = out_d; a.energy = en_d;
+    run_on_private_stream([&](hipStream_t st) { launch_vad(a, st); });
     HIP_CHECK(hipMemcpy(states_io, st_d, (size_t)n_runs * sizeof(VadState), hipMemcpyDeviceToHost));
     if (total) HIP_CHECK(hipMemcpy(bytes_out, out_d, total, hipMemcpyDeviceToHost));
     if (total && energy_out) HIP_CHECK(hipMemcpy(energy_out, en_d, total * sizeof(float), hipMemcpyDeviceToHost));
-    for (void *p : {(void *)ring_d, (void *)en_d, (void *)desc_d, (void *)st_d, (void *)out_d}) (void)hipFree(p);
 }
 
 void Engine::read_greedy_state(int slot, GreedyState *out)

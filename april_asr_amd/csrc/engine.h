@@ -32,6 +32,8 @@
 #include "input_format.h"
 #include "kernels.h"
 #include "host_pool.h"
+#include "slot_queue.h"
+#include "staging_layout.h"
 #include "model_loader.h"
 
 namespace aprilx {
@@ -97,6 +99,56 @@ struct GraphCache {
 struct RampStep { int macro = 0, own = 0; std::vector<std::pair<int, int>> guests; };      // guests: (layer, chunk)
 std::vector<RampStep> ramp_window(int L, int T, int R, int max_problems = 3);
 
+// One per-slot opt-in table on the engine's side ("life cycle"): device array + pinned host mirror.  Nothing exists
+// until alloc() -- the decision launches carry a null pointer until then --, and the device pointer never changes afterwards (captured
+// graphs hold it).  The stepping thread writes the mirror and uploads the WHOLE table, stream-ordered ahead of the flight's steps.
+template <typename T> struct DeviceTable {
+    T *d = nullptr, *h = nullptr; size_t n = 0;
+    bool on() const { return h != nullptr; }
+    void alloc(size_t count, const T &off);         // every entry `off` (legacy lock held by the caller or taken inside: recursive)
+    void upload(hipStream_t st) const;
+    void release();
+};
+
+// The front-end passes that ride along with one Engine::fbank() call (default: none, and fbank() issues exactly the launches it always did).
+// All arrays are the caller's and are read during the call only.
+struct FrontPass {
+    // Resampled sessions (aprilx_session_set_input_rate): a PCM part with a null pointer only RESERVES its model-rate region; the input-rate
+    // spans `in_parts` (n_in samples) follow the model-rate regions in the same staging buffer, and the n_rs descriptors (in_off relative to
+    // the first input span, out_dst absolute; rs_specs[i] is descriptor i's conversion, whose device table fbank() fills in) fill the
+    // reserved regions in one resample launch before the fbank launch.
+    int n_rs = 0; ResampleDesc *rs = nullptr; const ResampleSpec *const *rs_specs = nullptr;
+    const std::pair<const int16_t *, size_t> *in_parts = nullptr; size_t n_in_parts = 0, n_in = 0;
+    // Sessions with an input format (aprilx_session_set_input_format): their raw bytes `raw_parts` (n_raw bytes; every span starts on a
+    // 4-byte boundary, `raw_parts` carries the padding as null parts) form a third staged region behind the two int16 ones.  The n_dc
+    // descriptors (src_off relative to that region; dst absolute, or counted from the input-rate spans when dst_in is set) fill int16
+    // regions that were only reserved, in one decode launch before the resample and the fbank launch.
+    int n_dc = 0; const DecodeDesc *dc = nullptr;
+    const std::pair<const uint8_t *, size_t> *raw_parts = nullptr; size_t n_raw_parts = 0, n_raw = 0;
+    // Voice activity: the n_vd descriptors (out_off counted from 0, `vad_bytes` bytes in all); vad_kernel runs
+    // right behind the fbank launch.
+    int n_vd = 0; const VadDesc *vd = nullptr; size_t vad_bytes = 0;
+};
+
+// One call of the decision kernel on GIVEN rows (the parity tests' entry point, Engine::debug_decide): slots 0..n-1, row i = slot i.
+struct DecideRequest {
+    int n = 0, op = 0;                         // op 0: one decide_kernel round; 1: the end-of-flush reset
+    const float *logits = nullptr;             // [n][vocab] (op 0)
+    float early_emit = 1.0f; const int *now_ms = nullptr /* null: 0 */; int round = 0;
+    int32_t *state_io = nullptr;               // [n] GreedyState in and out; null: the slots' reset state
+    StepRecord *rec_out = nullptr;             // [n] (op 0)
+    const BiasSet *set = nullptr; int32_t *bias_state_io = nullptr;      // tables of their own for the call: row i uses the set from trie state bias_state_io[i], or none when that is -1
+    const SearchOpt *opts = nullptr;           // a table of its own likewise: opts[i] on row i (endpoint_ms 0 = a row without options)
+    int conf_k = 0; ConfRecord *conf_out = nullptr;                      // conf_k > 0: the side records of the rows with conf_k alternatives
+    // the arguments the aprilx_run_decide* family shares
+    static DecideRequest round_of(int n, int op, const float *logits, float early_emit, const int32_t *now_ms, int round, int32_t *state_io, void *records_out)
+    {
+        DecideRequest q;
+        q.n = n; q.op = op; q.logits = logits; q.early_emit = early_emit; q.now_ms = (const int *)now_ms; q.round = round; q.state_io = state_io; q.rec_out = (StepRecord *)records_out;
+        return q;
+    }
+};
+
 class Engine {
 public:
     Engine(const EngineConfig &cfg, const PackedLayout &layout, const float *blob_host, const float *blob_device,
@@ -127,41 +179,18 @@ public:
     // chunk steps (encoder + the three joiner/decision/decoder rounds, all on the device) and decoder refreshes are queued
     // back to back, and the host reads the 16-byte-per-round records once, at end_flight().
     // pcm arrives as `n_parts` windows that are gathered straight into pinned staging (total n_pcm samples)
-    void fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<const int16_t *, size_t> *parts, size_t n_parts, size_t n_pcm,
-               HostPool *pool = nullptr);
-    // Resampled sessions (aprilx_session_set_input_rate), for the NEXT fbank() call only: there a part with a null pointer only
-    // RESERVES its model-rate region; the input-rate spans `in_parts` (n_in samples) follow the model-rate regions in the same staging
-    // buffer, and the n descriptors (in_off relative to the first input span, out_dst absolute; specs[i] is descriptor i's conversion,
-    // whose device table fbank() fills in) fill the reserved regions in one resample launch before the fbank launch.  Without this
-    // call fbank() issues exactly the launches it always did.
-    void set_resample_pass(int n, ResampleDesc *rs, const ResampleSpec *const *specs, const std::pair<const int16_t *, size_t> *in_parts,
-                           size_t n_in_parts, size_t n_in)
-    {
-        rs_n_ = n; rs_desc_ = rs; rs_specs_ = specs; rs_in_parts_ = in_parts; rs_n_in_parts_ = n_in_parts; rs_n_in_ = n_in;
-    }
-    // Sessions with an input format (aprilx_session_set_input_format), for the NEXT fbank() call only: their raw bytes `raw_parts`
-    // (n_raw bytes; every span starts on a 4-byte boundary, `raw_parts` carries the padding as null parts) form a third staged region
-    // behind the two int16 ones, 16-byte aligned, in the same staging buffer and the same upload.  The n descriptors (src_off relative
-    // to that region; dst absolute, or counted from the input-rate spans when dst_in is set) fill int16 regions that were only reserved,
-    // in one decode launch before the resample and the fbank launch.  Without this call fbank() issues exactly the launches it always did.
-    void set_decode_pass(int n, const DecodeDesc *dc, const std::pair<const uint8_t *, size_t> *raw_parts, size_t n_raw_parts, size_t n_raw)
-    {
-        dc_n_ = n; dc_desc_ = dc; dc_raw_parts_ = raw_parts; dc_n_raw_parts_ = n_raw_parts; dc_n_raw_ = n_raw;
-    }
+    // `pass`: the resample / decode / VAD work of this call.  Returns the pinned block that receives the pass's VAD bytes (null: no VAD
+    // descriptors): its bytes are complete once the flight that was open during the call has been waited for (close_flight() puts the
+    // copy in front of the flight's event), and the block is lent until vad_release().  Stepping thread only.
+    const uint8_t *fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<const int16_t *, size_t> *parts, size_t n_parts, size_t n_pcm,
+                         HostPool *pool = nullptr, const FrontPass &pass = FrontPass());
     // decode launches and the frames they decoded so far (any thread)
     void decode_counts(uint64_t *launches, uint64_t *frames) const
     {
         *launches = dc_launches_.load(std::memory_order_relaxed); *frames = dc_frames_.load(std::memory_order_relaxed);
     }
     // ---- voice activity.  Inline over plain members: the scheduler harness links session.cc against an engine of
-    // its own.  set_vad_pass(), for the NEXT fbank() call only: the n descriptors (out_off counted from 0, `frames` bytes in all) are
-    // staged behind the decode descriptors in the same upload; vad_kernel runs right behind the fbank launch, and the pass's bytes are
-    // copied into a pinned block of their own before fb_done_ is recorded.  vad_pass_bytes() is that block (null: the last fbank() had
-    // no VAD pass): its bytes are complete once the flight that was open during the call has been waited for (close_flight() puts the
-    // copy in front of the flight's event), and the block is lent until vad_release().  Stepping thread only.  Without
-    // set_vad_pass(), fbank() issues exactly the launches it always did and nothing below is allocated.
-    void set_vad_pass(int n, const VadDesc *desc, size_t frames) { vad_n_ = n; vad_desc_ = desc; vad_pass_frames_ = frames; }
-    const uint8_t *vad_pass_bytes() const { return vad_last_h_; }
+    // its own.  Nothing is allocated until a pass carries a VAD descriptor.
     void vad_release(const uint8_t *p) { for (VadBlock &b : vad_blocks_) if (b.h == p) b.busy = false; }
     // VAD launches and the frames they covered so far (any thread)
     void vad_counts(uint64_t *launches, uint64_t *frames) const
@@ -201,31 +230,25 @@ public:
     // splitting over the three streams; a lone flight runs on one stream (the events between the streams cost it ~50 us)
     void set_overlap_hint(bool on) { overlap_hint_ = on; }
     const StepRecord *records(int step_index) const { return rec_h_ + rec_off_h_[step_index]; }   // [3][m], valid after end_flight()
-    // ---- per-token confidences.  Inline over plain members: the scheduler harness links session.cc
-    // against an engine of its own.  set_slot_confidence() only QUEUES the change (any thread, for an idle session's slot);
-    // begin_flight() applies it on the stepping thread: the first K > 0 of an engine allocates the per-slot bytes and the side
-    // ring (device + pinned host) and drops the captured graphs, whose decision launches were captured without them.
-    void set_slot_confidence(int slot, int k)
-    {
-        std::lock_guard<std::mutex> g(conf_mu_);
-        conf_pending_.push_back(std::make_pair(slot, k));
-        if (k > 0) conf_ever_.store(true, std::memory_order_relaxed);
-        conf_has_pending_.store(true, std::memory_order_release);
-    }
+    // ---- the per-slot opt-in tables: confidences, bias sets, search options (DESIGN.md sections 12-14).  ONE life cycle: set_slot_*()
+    // only QUEUES the change (any thread, for an idle session's slot; inline over plain members: the scheduler harness links session.cc
+    // against an engine of its own); an off value is dropped while nothing was ever on.  begin_flight() applies the queues on the stepping
+    // thread (apply_slot_tables): the first opt-in of a table allocates it (device + pinned mirror; the captured pointer never changes
+    // afterwards) and drops the captured graphs, whose decision launches were captured without it.
+    // Confidences: K alternatives per slot (0 = off); the side ring is allocated with the table.
+    void set_slot_confidence(int slot, int k) { conf_q_.push(slot, k, k > 0); }
     // side records of a step, indexed like records(); null while no session of the engine has opted in.  Valid after the
     // flight's wait for rows of opted-in sessions whose StepRecord is valid.
     const ConfRecord *conf_records(int step_index) const { return conf_h_ ? conf_h_ + rec_off_h_[step_index] : nullptr; }
     uint64_t confidence_records() const { return conf_copied_.load(std::memory_order_relaxed); }     // side records copied to the host so far
-    // ---- phrase boosting, the life cycle of the confidences above: set_slot_bias() only QUEUES the change (any
-    // thread, for an idle session's slot; null = off) and keeps the books -- which of the engine's kBiasSets table entries holds the
-    // set, how many slots use it --; begin_flight() applies it on the stepping thread: the first set of an engine allocates the
-    // per-slot tables and the descriptor table (fixed capacity: captured pointers never change afterwards) and drops the captured
-    // graphs; a set is uploaded the first time a slot of this engine uses it and freed when no slot uses it any more.  The slot's
-    // trie state returns to the root with every change.  False: the table is full or the vocabulary is too large for the kernel.
+    // Phrase boosting: set_slot_bias() (null = off) also keeps the books -- which of the engine's kBiasSets table entries holds the set,
+    // how many slots use it -- in the same critical section as the push; a set is uploaded the first time a slot of this engine uses it
+    // and freed when no slot uses it any more (the descriptor table has a fixed capacity).  The slot's trie state returns to the root
+    // with every change.  False: the table is full or the vocabulary is too large for the kernel.
     static constexpr int kBiasSets = 64;
     bool set_slot_bias(int slot, const std::shared_ptr<const BiasSet> &set)
     {
-        std::lock_guard<std::mutex> g(bias_mu_);
+        std::lock_guard<std::mutex> g(bias_q_.mutex());
         if (slot < 0 || slot >= cfg_.max_slots) return false;
         if (bias_slot_set_.empty()) {
             if (!set) return true;                               // nothing was ever on
@@ -245,31 +268,14 @@ public:
         if (old < 0 && idx < 0) return true;                     // no set before, none now (every aas_free comes through here): nothing to apply
         if (old >= 0) --bias_sets_[(size_t)old].users;
         bias_slot_set_[(size_t)slot] = idx;
-        bias_pending_.push_back(std::make_pair(slot, idx));
-        if (set) bias_ever_.store(true, std::memory_order_relaxed);
-        bias_has_pending_.store(true, std::memory_order_release);
+        bias_q_.push_locked(slot, idx, idx >= 0);
         return true;
     }
     // the device's trie state of a slot; waits for the streams.  0 while no session of the engine has a set, and for a slot with a queued
     // change (begin_flight returns it to the root before the slot's next step)
     int read_bias_state(int slot);
-    // aprilx_run_decide_biased: debug_decide with `set` on the rows whose bias_state_io is >= 0 (-1: a row without a set)
-    void debug_decide_biased(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
-                             const BiasSet &set, int32_t *bias_state_io);
-    // ---- search options, the same life cycle: set_slot_search_options() only QUEUES the slot's entry (any thread,
-    // for an idle session's slot; endpoint_ms 0 = no options); begin_flight() applies it on the stepping thread: the first opt-in of an
-    // engine allocates the per-slot table (device + pinned host; the captured pointer never changes afterwards) and drops the captured graphs.
-    void set_slot_search_options(int slot, SearchOpt o)
-    {
-        std::lock_guard<std::mutex> g(opt_mu_);
-        if (o.endpoint_ms == 0 && !opt_ever_.load(std::memory_order_relaxed)) return;      // nothing was ever on
-        opt_pending_.push_back(std::make_pair(slot, o));
-        if (o.endpoint_ms) opt_ever_.store(true, std::memory_order_relaxed);
-        opt_has_pending_.store(true, std::memory_order_release);
-    }
-    // aprilx_run_decide_opts: debug_decide with opts[i] on row i (endpoint_ms 0 = a row without options); `set` may be null
-    void debug_decide_opts(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
-                           const BiasSet *set, int32_t *bias_state_io, const SearchOpt *opts);
+    // Search options: endpoint_ms 0 = no options
+    void set_slot_search_options(int slot, SearchOpt o) { opt_q_.push(slot, o, o.endpoint_ms != 0); }
     void sync();                               // stepping thread (or under capture_mu_): waits for the three streams and clears the cross-stream dependency flags
     void sync_streams();                       // any thread: waits for the three streams, nothing else
 
@@ -277,12 +283,9 @@ public:
     void debug_encoder(int n, const float *x, const float *h, const float *c, float *eout, float *h2, float *c2);
     void debug_decoder(int n, const int64_t *ctx, float *dout);
     void debug_joiner(int n, const float *eout, const float *dout, float *logits);
-    // parity tests of the device's copy of the search decision: one decide_kernel round (op 0) or the end-of-flush reset
-    // (op 1) on slots 0..n-1 with GIVEN logits rows and search states; returns the records and the new states
-    void debug_decide(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out);
-    // the side records of n GIVEN logits rows with k alternatives through decide_kernel's confidence code (aprilx_run_confidence)
-    // (`set` non-null: on the rows whose bias_state[i] >= 0, from that trie state -- aprilx_run_confidence_biased)
-    void debug_confidence(int n, const float *logits, int k, ConfRecord *out, const BiasSet *set = nullptr, const int32_t *bias_state = nullptr);
+    // parity tests of the device's copy of the search decision (aprilx_run_decide*, aprilx_run_confidence*): returns the records, the side
+    // records and the new states
+    void debug_decide(const DecideRequest &q);
     void debug_fbank(int n_frames, const int16_t *pcm_frames /*[n][padded]*/, float *out /*[n][nbins]*/);
     // one whole segment through resample_kernel (aprilx_resample); out holds resample_total(n) samples
     void debug_resample(const ResampleSpec *spec, const int16_t *pcm, size_t n, int16_t *out);
@@ -409,35 +412,21 @@ private:
     int flight_parity_ = 0, next_parity_ = 0; size_t ring_base_ = 0, rec_base_ = 0; int flight_steps_ = 0;
     uint64_t step_seq_ = 0;                    // steps enqueued since the engine started = the device's step counter (advance_kernel)
     hipEvent_t flight_done_[2] = {nullptr, nullptr};
-    // confidences: nothing below is allocated until a session opts in
-    std::mutex conf_mu_;
-    std::vector<std::pair<int, int>> conf_pending_;   // (slot, K) not yet applied (conf_mu_)
-    std::atomic<bool> conf_has_pending_{false}, conf_ever_{false};     // conf_ever_: some session of this engine has asked for K > 0
-    uint8_t *conf_k_d_ = nullptr, *conf_k_h_ = nullptr;      // [slots] K per slot: device, pinned host mirror (stepping thread)
-    ConfRecord *conf_d_ = nullptr, *conf_h_ = nullptr;       // [2 * rec_cap_] side ring, indexed like rec_d_ / rec_h_
+    // the per-slot opt-in tables: nothing below is allocated until a session opts in
+    SlotQueue<int> conf_q_; DeviceTable<uint8_t> conf_k_;    // K per slot
+    ConfRecord *conf_d_ = nullptr, *conf_h_ = nullptr;       // [2 * rec_cap_] side ring, indexed like rec_d_ / rec_h_ (allocated with conf_k_)
     std::vector<std::pair<size_t, size_t>> conf_spans_;      // (first record, count) of this flight's steps that hold an opted-in row
     std::atomic<uint64_t> conf_copied_{0};
-    void apply_confidence_pending();
+    void apply_slot_tables();                  // begin_flight: the three queues -> the tables (engine.cc "slot tables")
     void drop_graphs();                        // (capture_mu_ held, streams drained) every captured graph; they are captured again at their next use
-    // phrase boosting: nothing below is allocated until a session opts in
     struct BiasEntry { std::shared_ptr<const BiasSet> set; int users = 0; void *dev = nullptr; };      // dev: one allocation holding the four arrays
-    std::mutex bias_mu_;
-    std::vector<BiasEntry> bias_sets_;                // [kBiasSets] (bias_mu_)
-    std::vector<int> bias_slot_set_;                  // [slots] the queued set of every slot (bias_mu_)
-    std::vector<std::pair<int, int>> bias_pending_;   // (slot, table entry or -1) not yet applied (bias_mu_)
-    std::atomic<bool> bias_has_pending_{false}, bias_ever_{false};
-    int32_t *bias_set_d_ = nullptr, *bias_set_h_ = nullptr, *bias_state_d_ = nullptr;     // [slots] device, pinned host mirror; [slots] device
-    BiasDesc *bias_desc_d_ = nullptr, *bias_desc_h_ = nullptr;                           // [kBiasSets]
-    void apply_bias_pending();
-    // search options
-    std::mutex opt_mu_;
-    std::vector<std::pair<int, SearchOpt>> opt_pending_;   // (slot, entry) not yet applied (opt_mu_)
-    std::atomic<bool> opt_has_pending_{false}, opt_ever_{false};
-    SearchOpt *opt_d_ = nullptr, *opt_h_ = nullptr;        // [slots] device, pinned host mirror (stepping thread)
-    void apply_search_options_pending();
+    SlotQueue<int> bias_q_; DeviceTable<int32_t> bias_set_;  // the table entry of every slot's set, or -1
+    std::vector<BiasEntry> bias_sets_;                // [kBiasSets] (bias_q_.mutex())
+    std::vector<int> bias_slot_set_;                  // [slots] the queued set of every slot (bias_q_.mutex())
+    int32_t *bias_state_d_ = nullptr;                 // [slots] trie states
+    DeviceTable<BiasDesc> bias_desc_;                 // [kBiasSets]
+    SlotQueue<SearchOpt> opt_q_; DeviceTable<SearchOpt> opt_;
     BiasDesc upload_bias(const BiasSet &set, void **dev, hipStream_t st);
-    void debug_decide_impl(int n, int op, const float *logits, float early_emit, const int *now_ms, int round, int32_t *state_io, StepRecord *rec_out,
-                           const BiasSet *set, int32_t *bias_state_io, const SearchOpt *opts = nullptr);
     void note_conf_step(int k, const int *slots, int m, size_t records);
     bool flight_open_[2] = {false, false};     // flight_done_[p] has been recorded and not yet waited for by begin_flight (wait_flight leaves it set: waiting twice is free)
     // streams (engine.cc "streams"): front end / search beside the layer chain, the per-parity buffers that make it safe
@@ -465,33 +454,17 @@ private:
     int *dec_slots_d_ = nullptr;
     float *logits_h_ = nullptr;
     // fbank staging is double-buffered so the next call can fill one pair while the previous copy is in flight
-    FbankFrameDesc *hs_desc_[2] = {nullptr, nullptr}, *ds_desc_[2] = {nullptr, nullptr}; int desc_cap_ = 0;
-    int16_t *hs_pcm_[2] = {nullptr, nullptr}, *ds_pcm_[2] = {nullptr, nullptr}; size_t pcm_cap_ = 0;
+    int16_t *hs_pcm_[2] = {nullptr, nullptr}, *ds_pcm_[2] = {nullptr, nullptr};      // one staging buffer per flip (staging_layout.h)
+    StagingCaps fb_caps_;                      // what they have room for
     int fb_flip_ = 0;
     hipEvent_t fb_done_[2] = {nullptr, nullptr};
     std::vector<size_t> part_off_;             // staging offsets of the PCM windows of one fbank call
-    size_t rs_cap_ = 0;                        // resample descriptors the staging buffers have room for
-    int rs_n_ = 0;                             // set_resample_pass(): the resample work of the next fbank() call
-    ResampleDesc *rs_desc_ = nullptr;
-    const ResampleSpec *const *rs_specs_ = nullptr;
-    const std::pair<const int16_t *, size_t> *rs_in_parts_ = nullptr;
-    size_t rs_n_in_parts_ = 0, rs_n_in_ = 0;
-    size_t dc_cap_ = 0;                        // decode descriptors the staging buffers have room for
-    int dc_n_ = 0;                             // set_decode_pass(): the decode work of the next fbank() call
-    const DecodeDesc *dc_desc_ = nullptr;
-    const std::pair<const uint8_t *, size_t> *dc_raw_parts_ = nullptr;
-    size_t dc_n_raw_parts_ = 0, dc_n_raw_ = 0;
     std::atomic<uint64_t> dc_launches_{0}, dc_frames_{0};
     // voice activity: nothing below is allocated until a pass carries a VAD descriptor
-    size_t vd_cap_ = 0;                        // VAD descriptors the staging buffers have room for
-    int vad_n_ = 0;                            // set_vad_pass(): the VAD work of the next fbank() call
-    const VadDesc *vad_desc_ = nullptr;
-    size_t vad_pass_frames_ = 0;
     VadState *vad_state_d_ = nullptr;          // [slots] (a session's first descriptor carries VAD_RESET: never initialised by the host)
     uint8_t *vad_out_d_ = nullptr; size_t vad_out_cap_ = 0;      // one pass's bytes on the device (stream order keeps the passes apart)
     struct VadBlock { uint8_t *h = nullptr; size_t cap = 0; bool busy = false; };
     std::vector<VadBlock> vad_blocks_;         // pinned blocks, one per pass whose bytes the scheduler has not read yet; reused afterwards
-    const uint8_t *vad_last_h_ = nullptr;
     bool vad_flight_ = false;                  // the open flight holds a VAD pass: its event must follow the copy on the front-end stream
     std::atomic<uint64_t> vad_launches_{0}, vad_frames_{0};
     std::mutex rs_mu_;

@@ -7,11 +7,10 @@
 #include "../../include/aprilx_engine.h"
 #include "common.h"
 #include "session.h"
+#include "api_handles.h"
 
 using namespace aprilx;
 
-struct AprilASRModel_i { Model m; };          // (the same definitions as april_api.cc)
-struct AprilASRSession_i { Session s; };
 #include "group_feed.h"
 
 namespace {

@@ -6,10 +6,9 @@
 #include "../../include/aprilx_engine.h"
 #include "common.h"
 #include "session.h"
+#include "api_handles.h"
 
 using namespace aprilx;
-
-struct AprilASRModel_i { Model m; };          // (the same definition as april_api.cc)
 
 extern "C" {
 

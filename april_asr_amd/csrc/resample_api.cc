@@ -6,11 +6,9 @@
 #include "../../include/aprilx_engine.h"
 #include "common.h"
 #include "session.h"
+#include "api_handles.h"
 
 using namespace aprilx;
-
-struct AprilASRModel_i { Model m; };          // (the same definitions as april_api.cc)
-struct AprilASRSession_i { Session s; };
 
 // ---- input sample rate (the reference takes PCM16 at aam_get_sample_rate() only, april-docs/src/python.md:79)
 namespace {

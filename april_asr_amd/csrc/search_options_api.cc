@@ -9,16 +9,9 @@
 #include "bias.h"
 #include "common.h"
 #include "session.h"
+#include "api_handles.h"
 
 using namespace aprilx;
-
-struct AprilASRModel_i { Model m; };          // (the same definitions as april_api.cc)
-struct AprilASRSession_i { Session s; };
-struct AprilxBias_i { std::shared_ptr<const BiasSet> set; };      // (as bias.cc)
-struct AprilxGreedy_i {
-    Greedy g; AprilRecognitionResultHandler handler; void *ud; std::vector<Event> ev;
-    void flush_events() { deliver_events(ev, handler, ud); }
-};
 
 namespace {
 
@@ -66,8 +59,10 @@ int aprilx_run_decide_opts(AprilASRModel model, int n, int op, const float *logi
         if (!valid(opts[i])) return -1;
         so[(size_t)i] = SearchOpt{opts[i].endpoint_silence_ms, opts[i].blank_penalty};
     }
-    model->m.engines[0]->debug_decide_opts(n, op, logits, early_emit, (const int *)now_ms, round, state_io, (StepRecord *)records_out,
-                                           bias ? bias->set.get() : nullptr, bias ? bias_state_io : nullptr, so.data());
+    DecideRequest q = DecideRequest::round_of(n, op, logits, early_emit, now_ms, round, state_io, records_out);
+    if (bias) { q.set = bias->set.get(); q.bias_state_io = bias_state_io; }
+    q.opts = so.data();
+    model->m.engines[0]->debug_decide(q);
     return 0;
 }
 

@@ -1007,16 +1007,18 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
         }
     }
     tick_.host_ms[1] += lap();
+    const uint8_t *vad_bytes = nullptr;         // the pinned block this pass's VAD bytes arrive in
     if (!desc_.empty()) {
-        if (!ddesc_.empty()) eng_->set_decode_pass((int)ddesc_.size(), ddesc_.data(), raw_parts_.data(), raw_parts_.size(), staged_raw_);
-        if (!rdesc_.empty()) eng_->set_resample_pass((int)rdesc_.size(), rdesc_.data(), rspec_.data(), in_parts_.data(), in_parts_.size(), staged_in);
-        if (!vdesc_.empty()) eng_->set_vad_pass((int)vdesc_.size(), vdesc_.data(), (size_t)vad_frames);
-        eng_->fbank((int)desc_.size(), desc_.data(), pcm_parts_.data(), pcm_parts_.size(), staged, &pool_);
+        FrontPass pass;
+        pass.n_dc = (int)ddesc_.size(); pass.dc = ddesc_.data(); pass.raw_parts = raw_parts_.data(); pass.n_raw_parts = raw_parts_.size(); pass.n_raw = staged_raw_;
+        pass.n_rs = (int)rdesc_.size(); pass.rs = rdesc_.data(); pass.rs_specs = rspec_.data(); pass.in_parts = in_parts_.data(); pass.n_in_parts = in_parts_.size(); pass.n_in = staged_in;
+        pass.n_vd = (int)vdesc_.size(); pass.vd = vdesc_.data(); pass.vad_bytes = (size_t)vad_frames;
+        vad_bytes = eng_->fbank((int)desc_.size(), desc_.data(), pcm_parts_.data(), pcm_parts_.size(), staged, &pool_, pass);
         pool_.run(work.size(), 64, [&](size_t i) { Session *s = work[i]; if (s->compact_pending) { s->fb.compact(); s->compact_pending = false; } });
         tick_.frames += desc_.size();
         tick_.host_ms[2] += lap();
     }
-    if (!vruns_.empty()) vad_pending_.push_back(VadPending{flight_seq_, vdesc_.empty() ? nullptr : eng_->vad_pass_bytes(), vruns_});
+    if (!vruns_.empty()) vad_pending_.push_back(VadPending{flight_seq_, vad_bytes, vruns_});
     if (!finishers.empty()) {
         slots_.clear();
         for (Session *s : finishers) slots_.push_back(s->slot);

@@ -7,11 +7,9 @@
 #include "../../include/aprilx_engine.h"
 #include "common.h"
 #include "session.h"
+#include "api_handles.h"
 
 using namespace aprilx;
-
-struct AprilASRModel_i { Model m; };          // (the same definitions as april_api.cc)
-struct AprilASRSession_i { Session s; };
 
 static_assert(sizeof(AprilxVadPlan) == sizeof(VadPlan) && sizeof(AprilxVadState) == sizeof(VadState), "the public structs are the runtime's");
 

@@ -14,7 +14,7 @@
 //     joiner results that depend only on the session's own time line -- so the device flags the scheduler replays against are
 //     exactly consistent (replay_mismatch must stay 0) and the callbacks of a session do not depend on the ingest mode;
 //   * fbank() reads every staged PCM window (a lent caller buffer that was freed or changed too early is an ASan / TSan report)
-//     and checks the frame descriptors against the staged range.
+//     and checks the frame descriptors against the staged range, and a pass's counts and spans against each other.
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -116,22 +116,37 @@ void Engine::free_slot(int slot)
     free_.push_back(slot); --live_;
 }
 
-void Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<const int16_t *, size_t> *parts, size_t n_parts, size_t n_pcm, HostPool *)
+const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<const int16_t *, size_t> *parts, size_t n_parts, size_t n_pcm, HostPool *,
+                             const FrontPass &pass)
 {
     FakeState &f = st(this);
-    uint64_t sum = 0; size_t total = 0;
-    for (size_t p = 0; p < n_parts; ++p) {                      // every staged sample is read, as the pinned-staging gather does
-        const int16_t *q = parts[p].first;
-        for (size_t i = 0; i < parts[p].second; ++i) sum += (uint16_t)q[i];
-        total += parts[p].second;
-    }
+    uint64_t sum = 0;
+    auto read_all = [&sum](const auto *pp, size_t np) {         // every staged element is read, as the pinned-staging gather does (null: a reserved region)
+        size_t total = 0;
+        for (size_t p = 0; p < np; ++p) {
+            if (pp[p].first) for (size_t i = 0; i < pp[p].second; ++i) sum += (uint16_t)pp[p].first[i];
+            total += pp[p].second;
+        }
+        return total;
+    };
+    const size_t total = read_all(parts, n_parts);
     if (total != n_pcm) { LOGE("fake engine: fbank: windows hold %zu samples, caller says %zu", total, n_pcm); abort(); }
+    // a pass without descriptors carries nothing, and its spans hold what the caller says they hold
+    if (pass.n_rs < 0 || pass.n_dc < 0 || pass.n_vd < 0 || (!pass.n_rs && (pass.n_in_parts || pass.n_in)) || (!pass.n_dc && (pass.n_raw_parts || pass.n_raw)) ||
+        (!pass.n_vd && pass.vad_bytes) || (pass.n_rs && (!pass.rs || !pass.rs_specs)) || (pass.n_dc && !pass.dc) || (pass.n_vd && !pass.vd) ||
+        read_all(pass.in_parts, pass.n_in_parts) != pass.n_in || read_all(pass.raw_parts, pass.n_raw_parts) != pass.n_raw) {
+        LOGE("fake engine: fbank: inconsistent front-end pass"); abort();
+    }
+    size_t vad_rows = 0;
+    for (int i = 0; i < pass.n_vd; ++i) vad_rows += (size_t)pass.vd[i].n;
+    if (vad_rows != pass.vad_bytes) { LOGE("fake engine: fbank: VAD descriptors cover %zu rows, caller says %zu", vad_rows, pass.vad_bytes); abort(); }
     for (int i = 0; i < n_frames; ++i) {
         if (desc[i].slot < 0 || desc[i].slot >= cfg_.max_slots || desc[i].ring_row < 0 || desc[i].ring_row >= ring_frames_) { LOGE("fake engine: fbank: bad descriptor"); abort(); }
         if (desc[i].pcm_off >= 0 && (size_t)desc[i].pcm_off + (size_t)1 > n_pcm) { LOGE("fake engine: fbank: frame window outside the staged samples"); abort(); }
     }
     f.pcm_sum.fetch_add(sum, std::memory_order_relaxed);
     f.frames += (uint64_t)n_frames;
+    return nullptr;
 }
 
 void Engine::begin_flight()
@@ -263,7 +278,7 @@ void Engine::read_greedy_state(int slot, GreedyState *out)
 void Engine::debug_encoder(int, const float *, const float *, const float *, float *, float *, float *) { abort(); }
 void Engine::debug_decoder(int, const int64_t *, float *) { abort(); }
 void Engine::debug_joiner(int, const float *, const float *, float *) { abort(); }
-void Engine::debug_decide(int, int, const float *, float, const int *, int, int32_t *, StepRecord *) { abort(); }
+void Engine::debug_decide(const DecideRequest &) { abort(); }
 void Engine::debug_fbank(int, const int16_t *, float *) { abort(); }
 
 // planner entry points of the kernel files that april_api.cc exposes for CPU-side tests: not part of this harness

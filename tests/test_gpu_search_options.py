@@ -474,3 +474,57 @@ def test_first_opt_in_with_captured_graphs(tiny_model, baseline):
     for s in ss + [late]:
         s.close()
     gm.close()
+
+
+def test_three_first_opt_ins_in_one_flight_with_captured_graphs(tiny_model, baseline):
+    """the engine's first bias set, first K > 0 and first search options arrive together, with one session, while four plain sessions run
+    on captured graphs: all three tables are applied in the same begin_flight.  The plain sessions keep their transcripts; the late
+    session's events and side records are those of the same session alone on a fresh model where the three were set before any audio."""
+    import april_asr_amd as A
+    import bias_worker as BW
+    pcms, base = baseline
+    half = (pcms[0].size // 3200) * 1600
+    late_pcm = pcms[4][:pcms[0].size - half]
+
+    def late_session(gm, ev):
+        texts = texts_of(gm)
+        bias = gm.bias(BW.session_phrases(texts, gm.dims.blank_id, np.random.default_rng(3)))
+        s = A.Session(gm, lambda t, toks: ev.append((t, toks)), raw_events=True, bias=bias, alternatives=4, endpoint_silence_ms=300, blank_penalty=1.5)
+        s.info_log = []
+        return s, bias
+
+    def states_agree(s):
+        h, d = s.bias_state()
+        assert h == d, "trie state: host %d, device %d" % (h, d)
+
+    gm = A.Model(tiny_model["path"])
+    evs = [[] for _ in range(5)]
+    ss = [A.Session(gm, (lambda q: (lambda t, toks: evs[q].append((t, toks))))(i), raw_events=True) for i in range(4)]
+    g = A.SessionGroup(ss)
+    for off in range(0, half, 1600):
+        g.feed([p[off:off + 1600] for p in pcms[:4]])
+    late, bias = late_session(gm, evs[4])                          # the engine's first opt-in of all three kinds
+    g5 = A.SessionGroup(ss + [late])
+    for off in range(half, pcms[0].size, 1600):
+        g5.feed([p[off:off + 1600] for p in pcms[:4]] + [late_pcm[off - half:off - half + 1600]])
+        states_agree(late)
+    g5.flush()
+    for i in range(4):
+        assert evs[i] == base[i][0], "session %d changed when the engine's first opt-ins arrived" % i
+    assert gm.stats().replay_mismatch == 0
+    log = late.info_log
+    for s in ss + [late]:
+        s.close()
+    bias.close(); gm.close()
+
+    gm = A.Model(tiny_model["path"])
+    ev1 = []
+    alone, bias = late_session(gm, ev1)
+    for off in range(0, late_pcm.size, 1600):
+        alone.feed_pcm16(late_pcm[off:off + 1600])
+        states_agree(alone)
+    alone.flush()
+    assert len(evs[4]) > 0 and evs[4] == ev1, "the late session differs from the same session alone"
+    assert [(t, [bytes(r) for r in infos]) for t, infos in log] == [(t, [bytes(r) for r in infos]) for t, infos in alone.info_log] and len(log) > 0
+    assert gm.stats().replay_mismatch == 0
+    alone.close(); bias.close(); gm.close()
