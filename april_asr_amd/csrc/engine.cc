@@ -976,9 +976,10 @@ void Engine::launch_rowepi(GemmArgs f, float *ws, hipStream_t st, bool force, in
 {
     const int row_cls = cls == T_DEC ? T_DEC : T_ROW;
     f.force_fullk = force ? 1 : 0;
-    if (gemm_fullk(f.M, f.N, f.kz, force, 1, f.tile_ok)) { timed_begin(cls); launch_gemm(f, st); timed_end(cls); return; }
+    const GemmPlan p = gemm_plan(f);
+    if (p.fused) { timed_begin(cls); launch_gemm(f, st); timed_end(cls); return; }
     timed_begin(cls); launch_gemm(partial_form(f, ws, ws_mstride_), st); timed_end(cls);
-    timed_begin(row_cls); launch_row(row_form(f, ws, ws_mstride_, gemm_partials(f.M, f.N, f.kz, 1, f.tile_ok)), st); timed_end(row_cls);
+    timed_begin(row_cls); launch_row(row_form(f, ws, ws_mstride_, p.planes), st); timed_end(row_cls);
 }
 
 // conv front end + embed linear of rows [r0, r0 + rows) -> y, ssq (and y16: layer 0 of an fp16 tile engine reads binary16 rows).
@@ -1060,6 +1061,7 @@ void Engine::run_greedy_rounds(int n, const GreedyIo &io)
     const int gen = io.gen;
     const int *d_slots = step_d_;
     for (int round = 0; round < 3; ++round) {
+        int planes;
         {   // logits = tanh(eout + dout) x Wout (+ bias in the decision kernel)
             GemmArgs g; g.a0b = dout_; g.lda0 = d.joiner; g.K0 = d.joiner; g.a_op = AOP_TANH_ADD;
             if (dec_table_) { g.a0b = dec_table_; g.ctx_state = gstate_; g.ctx_vocab = d.vocab; }     // dout = the table row of the slot's context
@@ -1067,10 +1069,11 @@ void Engine::run_greedy_rounds(int n, const GreedyIo &io)
             else { g.a0 = eout_; g.aidx0 = d_slots; }
             lin(g, L_.w_out); g.M = n; g.N = L_.vocab_pad; g.K = d.joiner; g.kz = kz_out_; g.epi = EPI_PARTIAL; g.out = ws_g_; g.m_stride = ws_mstride_;
             if (round > 0) { g.run_flag = flags_d_ + round; g.run_gen = gen; }
+            planes = gemm_plan(g).planes;
             timed_begin(T_DEC); launch_gemm(g, search_stream_); timed_end(T_DEC);
         }
         DecideArgs a;
-        a.ws = ws_g_; a.parts = gemm_partials(n, L_.vocab_pad, kz_out_); a.m_stride = ws_mstride_; a.N = L_.vocab_pad; a.M = n; a.n_valid = d.vocab;
+        a.ws = ws_g_; a.parts = planes; a.m_stride = ws_mstride_; a.N = L_.vocab_pad; a.M = n; a.n_valid = d.vocab;
         a.bias = w_ + L_.b_out; a.blank = P_.blank_id; a.early_emit = round == 0 ? 1.0f : 0.0f;
         a.slot_idx = d_slots; a.now_ms = io.now; a.active = active_d_; a.dirty = dirty_d_; a.tok_class = cls_; a.state = gstate_;
         a.rec_ring = rec_d_; a.rec_off = io.rec_off; a.round = round; a.gen = gen; a.rec_slot = io.rec_slot0 + round;
@@ -1366,11 +1369,15 @@ void Engine::build_sw_chain(SwPlan &p, SwPlan::Chain &c, int m, int T, bool ramp
     const NetDims &d = L_.dims;
     const int L = d.n_layers;
     const int par = flight_parity_;
-    const int tk = f16_tile_ ? 2 : tile_ok();
-    // does a launch of n problems of this kind need a row finisher? (projection and FFN down on the GM_TILE schedule, see below)
+    // Does a launch of n problems of this kind need a row finisher, and over how many planes?  (Projection and FFN down on the GM_TILE
+    // schedule, see below.)  The chain asks without force: GM_TILE's K cut is a matter of occupancy; every other plan is launched
+    // fused, forced (force_fullk as args_whr / args_ff2 build it).
     auto needs_rows = [&](int kind, int n) {
-        const int kz = kind == 1 ? kz_hr() : kz_ff2();
-        return (kind == 1 || kind == 3) && tk && (tk == 2 || gemm_tile_planned(m, d.d_model, kz, n)) && !gemm_fullk(m, d.d_model, kz, false, n, tk);
+        if (kind != 1 && kind != 3) return 0;
+        GemmArgs g = kind == 1 ? args_whr(0, 0, m) : args_ff2(0, 0, m);
+        g.force_fullk = 0; g.zcount = n;
+        const GemmPlan p = gemm_plan(g);
+        return p.mode == GM_TILE && !p.fused ? p.planes : 0;
     };
     // hosting: own + guest problems fit the three-problem forms in both window steps and no launch of the window needs a row finisher
     std::vector<RampStep> window;
@@ -1394,8 +1401,8 @@ void Engine::build_sw_chain(SwPlan &p, SwPlan::Chain &c, int m, int T, bool ramp
             // The N = d_model GEMMs (projection, FFN down) on the GM_TILE schedule: when the n_act problems of this launch give the
             // chip too few 64 x 64 tiles, K is cut across workgroups and ONE z-batched row launch finishes the slab tree with the
             // epilogue (state write + residual / bias + residual + sums of squares) -- the same arithmetic as the fused form.
-            const int kz = kind == 1 ? kz_hr() : kz_ff2();
-            const bool split = needs_rows(kind, n_act);
+            const int planes = needs_rows(kind, n_act);
+            const bool split = planes > 0;
             auto problem = [&](int l, int t, const int *run_flag) {
                 const size_t r0 = (size_t)t * m;
                 GemmArgs g = kind == 0 ? args_gates(l, r0, m, GATES_ALL) : kind == 1 ? args_whr(l, r0, m) : kind == 2 ? args_ff1(l, r0, m) : args_ff2(l, r0, m);
@@ -1403,9 +1410,9 @@ void Engine::build_sw_chain(SwPlan &p, SwPlan::Chain &c, int m, int T, bool ramp
                 if (run_flag) { g.run_flag = run_flag; g.run_gen = 1; }
                 if (split) {
                     float *ws = ws_ + r0 * d.d_model;
-                    rows.push_back(row_form(g, ws, ws_mstride_, gemm_partials(m, d.d_model, kz, n_act, tk)));
+                    rows.push_back(row_form(g, ws, ws_mstride_, planes));
                     g = partial_form(g, ws, ws_mstride_);
-                } else if (tk == 2) g.force_fullk = 0;
+                } else if (f16_tile_) g.force_fullk = 0;      // (launched as asked: GM_TILE always takes an fp16 tile GEMM)
                 items.push_back(g);
             };
             for (int l = 0; l < L; ++l) {
@@ -1584,9 +1591,8 @@ void Engine::launch_split_feed(int m, int T, hipStream_t fe)
 void Engine::run_layer_major(int m, int T, bool dump_logits)
 {
     general_prologue();
-    const NetDims &d = L_.dims; const int tk = f16_tile_ ? 2 : tile_ok();
     const bool wavefront = lm_wavefront_on() && !profiling_ && T > LM_WAVEFRONT_MIN_CHUNKS &&
-                           gemm_fullk(m, d.d_model, kz_hr(), true, 1, tk) && gemm_fullk(m, d.d_model, kz_ff2(), true, 1, tk);
+                           gemm_plan(args_whr(0, 0, m)).fused && gemm_plan(args_ff2(0, 0, m)).fused;      // (forced, one problem: as the wavefront's forms are built)
     if (wavefront) { run_lm_wavefront(m, T, dump_logits); return; }       // long feed: all layers of a wavefront per launch
     if (!use_graphs_ || profiling_ || dump_logits) { launch_count_ = 0; run_lm_chain(m, T, dump_logits); kernels_per_step_ = launch_count_ + 1; return; }
     const GraphCache::Key key = graph_key(m, T);
@@ -1962,7 +1968,7 @@ void Engine::debug_joiner(int n, const float *eout, const float *dout, float *lo
     launch_gemm(g, stream_);
     // logits = tree + bias for all padded columns; the host keeps the first `vocab` of each row
     float *lg = dmalloc<float>((size_t)n * L_.vocab_pad);
-    RowArgs r; r.mode = ROW_SLOT_STORE; r.ws = ws_; r.parts = gemm_partials(n, L_.vocab_pad, kz_out_); r.m_stride = ws_mstride_; r.N = L_.vocab_pad; r.M = n;
+    RowArgs r; r.mode = ROW_SLOT_STORE; r.ws = ws_; r.parts = gemm_plan(g).planes; r.m_stride = ws_mstride_; r.N = L_.vocab_pad; r.M = n;
     r.bias = w_ + L_.b_out; r.out = lg; r.ldo = L_.vocab_pad;
     launch_row(r, stream_);
     sync();

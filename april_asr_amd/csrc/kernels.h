@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "vad.h"
+#include "gemm_plan.h"
 
 namespace aprilx {
 
@@ -36,23 +37,12 @@ namespace aprilx {
 //   s * sum_y + sum_h.  EPI_XPART leaves s * sum_y, EPI_LSTM + p_add continues the chain from it.  No chunk sums: the accumulator is the
 //   only register set, which is what lets GM_PP hold 256 x 128 tiles with double-buffered fragments.  Still a property of the layer:
 //   every batch size, streamed or layer-major, runs the same chain.  fp32 operands keep the chunk / slab / tree form above.
-enum GemmEpilogue {
-    EPI_PARTIAL = 0,      // ws[z][m][n] = tree sum of this workgroup's slabs      (consumer: row kernels; FULLK: one plane)
-    EPI_LSTM = 1,         // columns are unit-major (unit*4 + gate i,f,g,o): cell update, c in place, u out
-    EPI_BIAS_DSWISH = 2,  // out = y * sigmoid(y - 1), y = acc + bias
-    EPI_HR = 3,           // LSTM projection: state[slot] = acc ; out = resid * rowscale(resid) + acc
-    EPI_RESID_SSQ = 4,    // y = resid + (acc + bias) (resid optional) ; out = y ; ssq[m][n/32] = sum of y^2 over 32 columns
-    EPI_SLOT_STORE = 5,   // out[slot] = acc + bias, rows with row_mask[m] == 0 skipped (mask optional)
-    EPI_XPART = 6         // layer-major schedule: out = (p0 + p1) (* x_scale) = the input half of the gate pre-activations
-};
-// A-operand prologues
-enum GemmAOp { AOP_NONE = 0, AOP_TANH_ADD = 1 };
+// (the epilogue, prologue and mode enumerators: gemm_plan.h)
 // BasicNorm never runs as a kernel.  A layer leaves y and its per-32-column sums of squares (EPI_RESID_SSQ); the consumers
 // of x = y * scale(y), scale = (mean(y^2) + eps)^-1/2, fold the row scale in where it is cheapest:
 //   - a GEMM over x (LSTM gates' input half, encoder_proj) runs over y and multiplies the finished partial sum by the row's
 //     scale in its epilogue (`x_scale`): scale * sum_k(y_k w_k), one rounding away from sum_k((scale y_k) w_k);
 //   - the residual x + h' reads y and multiplies (`r_scale`).
-enum GemmMode { GM_SLAB = 0, GM_FULLK = 1, GM_TILE = 2, GM_KW = 3, GM_PP = 4 };
 //     GM_TILE   (kernels_gemm_tile.hip) the four waves split the OUTPUT tile and share both operands through LDS; every wave
 //               folds chunk -> slab -> tree in registers over the workgroup's zs slabs.  zs == kz: row epilogue fused;
 //               zs < kz: kz / zs partial planes, finished by the row kernels exactly as for GM_SLAB.
@@ -125,8 +115,7 @@ struct GemmArgs {
     int force_fullk = 0;                   // take the full-K plan even when it yields few workgroups (latency-bound sequential steps: one launch
                                            // instead of split-K + row kernel matters more than filling the chip)
     int zcount = 1;                        // same-shape problems sharing the launch (set by stage_gemm_z): an occupancy hint for the tile planner
-    int tile_ok = 0;                       // the caller planned this GEMM with gemm_fullk / gemm_partials(..., tile_ok): 1 = GM_TILE may be chosen by
-                                           // the planner's occupancy rule (fp32 A in one K segment, N % 64 == 0, row epilogue or partial planes);
+    int tile_ok = 0;                       // 1 = GM_TILE may be chosen by the planner's occupancy rule (fp32 A in one K segment, N % 64 == 0, row epilogue or partial planes);
                                            // 2 = GM_TILE always (the fp16 tile path of an fp16 engine: every batch size runs the same chains)
     int asm_loop = 0;                      // != 0: hand-scheduled K loop (gemm_mainloop_asm.inc) in the fused-epilogue 64x64 fp32 tiles
     unsigned long long *trace = nullptr;   // measurement only: per-workgroup s_memtime stamps [wg][8] (wave 0, lane 0)
@@ -158,7 +147,6 @@ bool gemm_pw_ok(const GemmArgs &g);
 void launch_gemm_pw(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t s);
 // measurement only (tools/pp_bench): enable -1 = environment default (APRIL_GM_PP), 0 / 1 = off / on; mt = 0 (planner) or pinned 16 / 8
 void gemm_pp_pin(int enable, int mt);
-bool gemm_kw_has_kernel(const GemmArgs &g, int mt, int nt);      // a GM_KW kernel exists for this GEMM on 16 mt x 16 nt tiles
 void launch_gemm_kw(const GemmArgs &g, int mt, int nt, const GemmArgs *dev_args, int n, hipStream_t s);
 // measurement only (tools/kw_bench): enable -1 = environment default (APRIL_GM_KW), 0 / 1 = off / on; mt = 0 (planner) or pinned tile rows / 16
 void gemm_kw_pin(int enable, int mt);
@@ -168,18 +156,14 @@ int recur_form(const GemmArgs &g);
 void launch_recur(const GemmArgs &g, int form, const GemmArgs *dev_args, int n, hipStream_t s);
 // n independent GEMMs of ONE shape (same M, N, K, kz, epilogue; any pointers) in one launch.  stage_gemm_z finalizes the
 // argument blocks on the host; launch_gemm_z launches once they are in device memory at dev_args (in stream order).
-// Fused-epilogue forms only (EPI_LSTM, EPI_XPART, EPI_BIAS_DSWISH, and EPI_HR / EPI_RESID_SSQ where gemm_fullk says so).
+// Fused-epilogue forms only (EPI_LSTM, EPI_XPART, EPI_BIAS_DSWISH, and EPI_HR / EPI_RESID_SSQ where gemm_plan says fused).
 void stage_gemm_z(const GemmArgs *items, int n, GemmArgs *staged);
 void launch_gemm_z(const GemmArgs *staged, int n, const GemmArgs *dev_args, hipStream_t s);
-// number of partial planes launch_gemm will write for an EPI_PARTIAL GEMM of this shape
-// (zcount = same-shape problems sharing a z-batched launch; tile_ok = the GM_TILE schedule is allowed for this call site:
-// callers pass the same values here and in GemmArgs::zcount / tile_ok so that both sides make the same plan)
-int gemm_partials(int M, int N, int kz, int zcount = 1, int tile_ok = 0);
-// true when launch_gemm runs a GEMM of this shape on the full-K schedule, i.e. the caller may (must, for the row
-// epilogues EPI_HR / EPI_RESID_SSQ / EPI_SLOT_STORE) fuse the row work; false: EPI_PARTIAL + row kernel
-bool gemm_fullk(int M, int N, int kz, bool force = false, int zcount = 1, int tile_ok = 0);
-// true when a tile_ok GEMM of this shape runs on the GM_TILE schedule (whose K split is a matter of occupancy, not of need)
-bool gemm_tile_planned(int M, int N, int kz, int zcount = 1);
+// The plan of g (gemm_plan.h): the query is built from g, capabilities included, and planned with the
+// process's knobs.  A caller about to launch a row-epilogue GEMM (EPI_HR / EPI_RESID_SSQ / EPI_SLOT_STORE) asks with its fused
+// form and zcount = the launch's problem count: fused -> launch it as it is; else launch its EPI_PARTIAL form, which writes
+// `planes` planes, and a row kernel behind it.  For an EPI_PARTIAL g, `planes` is what its launch writes.
+GemmPlan gemm_plan(const GemmArgs &g);
 // measurement only (tools/tile_bench): enable -1 = environment default, 0 / 1 = off / on; mt, zs = 0 (planner's choice) or pinned
 void gemm_tile_pin(int enable, int mt, int zs);
 

@@ -22,6 +22,7 @@
 // Replaces the ORT MatMul/Gemm nodes of the encoder/decoder/joiner graphs
 // (reference call sites src/april_session.c:145,160,176).
 #include "kernels.h"
+#include "../../include/aprilx_engine.h"
 #include "device_utils.h"
 #include "env.h"
 // the head of the hand-scheduled K loop on an 8-byte boundary: every instruction of the loop is an 8-byte encoding, so the phase of the
@@ -187,7 +188,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int zg, const
 
     // pairwise (balanced-tree) slab accumulation (GM_SLAB): level b holds the sum of 2^b consecutive slabs.  A workgroup
     // that owns zs = 2^t slabs needs t levels; the 64x64 tile is capped at zs = 4 (2 levels, 32 registers) so that it stays
-    // within 256 registers and two workgroups share a CU (launch_gemm / gemm_partials apply the same cap)
+    // within 256 registers and two workgroups share a CU (the planner applies the same cap: gemm_plan.h plan_tiles)
     constexpr int NLVL = !TREE ? 1 : ((MT == 4 && NT == 4) ? 2 : 3);
     f32x4 lvl[NLVL][QPT];
     int top = 0;
@@ -737,309 +738,77 @@ __global__ __launch_bounds__(256, 1) void gemm_f32_zkernel_mixed(const GemmArgs 
 }
 
 // ---------------------------------------------------------------- host side
-struct TilePlan { int mt, nt, zs, mode; };
-
 ProfileEvents &tl_profile_events() { static thread_local ProfileEvents pe; return pe; }
 void gemm_profile_next_launch(hipEvent_t start, hipEvent_t stop) { ProfileEvents &pe = tl_profile_events(); pe.a = start; pe.b = stop; }
 bool gemm_profile_pending() { return tl_profile_events().a != nullptr; }
 
-// The full-K schedule pays once output tiles alone occupy a good part of the chip.  Tiles: at most 64x32 (three
-// accumulator-sized register sets: chain, slab, tree level), at least 16x32 (a sum-of-squares granule is 32 columns).
-static bool plan_fullk(int M, int N, int kz, TilePlan &t, bool force = false, int zcount = 1)
+// The process's knobs (gemm_plan.h): the environment, read once, and the bench tools' pins
+static GemmKnobs &knobs()
 {
-    static const int enabled = env_int("APRIL_FULLK", 1);
-    constexpr int min_wgs = 96;
-    if (!enabled || N % 32 != 0) return false;
-    const int ncols = N / 32;
-    int mt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
-    // (zcount same-shape problems share a launch: the chip is filled by all of them together, so each can use larger tiles)
-    while (mt > 1 && (long)ncols * ((M + 16 * mt - 1) / (16 * mt)) * zcount < 256) mt >>= 1;
-    const long wgs = (long)ncols * ((M + 16 * mt - 1) / (16 * mt)) * zcount;
-    if (wgs < min_wgs && !force) return false;
-    t.mt = mt; t.nt = 2; t.zs = kz; t.mode = kz >= 4 ? GM_FULLK : GM_SLAB;    // kz 1 or 2: one workgroup walks the slabs (<= 2 meets)
-    return true;
+    static GemmKnobs k = [] {
+        GemmKnobs e;
+        e.fullk = env_int("APRIL_FULLK", 1); e.gm_tile = env_int("APRIL_GM_TILE", 1);
+        e.gm_pp = env_int("APRIL_GM_PP", 1); e.pp_mt = env_int("APRIL_PP_MT", 0); e.pp_wide = env_int("APRIL_PP_WIDE", 1);
+        e.tile_big = env_int("APRIL_TILE_BIG", 1); e.tile_f16_fullk = env_int("APRIL_TILE_F16_FULLK", 1);
+        e.gm_kw = env_int("APRIL_GM_KW", 1); e.kw_mt = env_int("APRIL_KW_MT", 0); e.kw_over_tile = env_int("APRIL_KW_OVER_TILE", 1);
+        e.z_tiles = env_int("APRIL_Z_TILES", 2);
+        return e;
+    }();
+    return k;
+}
+void gemm_tile_pin(int enable, int mt, int zs) { GemmKnobs &k = knobs(); k.tile_enable = enable; k.tile_pin_mt = mt; k.tile_pin_zs = zs; }
+void gemm_pp_pin(int enable, int mt) { GemmKnobs &k = knobs(); k.pp_enable = enable; k.pp_pin_mt = mt; }
+void gemm_kw_pin(int enable, int mt) { GemmKnobs &k = knobs(); k.kw_enable = enable; k.kw_pin_mt = mt; }
+
+static GemmQuery gemm_query(const GemmArgs &g)
+{
+    GemmQuery q;
+    q.M = g.M; q.N = g.N; q.K = g.K; q.K0 = g.K0; q.K1 = g.K1; q.kz = g.kz; q.epi = g.epi; q.a_op = g.a_op; q.wt = g.wt; q.wave_mask = g.wave_mask;
+    q.has_p_add = g.p_add != nullptr; q.has_x_scale = g.x_scale.ssq != nullptr;
+    q.zcount = g.zcount; q.tile_ok = g.tile_ok; q.force_fullk = g.force_fullk;
+    q.recur_form = recur_form(g); q.kw_ok = gemm_kw_waves(g) != 0; q.pp_ok = gemm_pp_ok(g, 16); q.pw_ok = gemm_pw_ok(g);
+    return q;
+}
+GemmPlan gemm_plan(const GemmArgs &g) { return plan_gemm(gemm_query(g), knobs()); }
+
+[[noreturn]] static void plan_die(const GemmArgs &g, int error)
+{
+    switch (error) {
+    case PLAN_ALWAYS_TILE_OPERANDS: fprintf(stderr, "libapril(mi355x): launch_gemm: always-tile GEMM with a prologue / wave mask / odd N\n"); break;
+    case PLAN_NO_TILE_PLAN: fprintf(stderr, "libapril(mi355x): launch_gemm: no GM_TILE plan for an always-tile GEMM (M=%d N=%d kz=%d)\n", g.M, g.N, g.kz); break;
+    case PLAN_ROW_NEEDS_FULLK: fprintf(stderr, "libapril(mi355x): launch_gemm: row epilogue %d needs the full-K plan (M=%d N=%d kz=%d)\n", g.epi, g.M, g.N, g.kz); break;
+    default: fprintf(stderr, "libapril(mi355x): launch_gemm: x_scale needs K0 == K / 2 and kz == 1\n"); break;
+    }
+    abort();
 }
 
-// GM_TILE (kernels_gemm_tile.hip): 64-column tiles of 32 (or 64) rows whose waves share the operands through LDS.
-// Measured on MI355X (tools/tile_bench, profiles/r03_tile_bench.txt; us per launch, round-2 schedule -> GM_TILE):
-//   FFN down 2048 rows x 2 problems 110 -> 83 (32-row tiles, all of K per workgroup), 1024 x 2: 60 -> 46, projection 2048 x 2:
-//   64 -> 51, larger encoder 512 x 3: 105 -> 77 (K cut in four, row kernel);  256 rows x 1..3 problems: no gain (a launch of a few
-//   hundred short workgroups is bound by its fixed costs -- pipeline fill, the second launch), so small launches keep the
-//   round-2 schedules.  Rule: no GM_TILE below 256 32-row tiles per launch; 64-row tiles once the launch holds 512 of them,
-//   32-row tiles otherwise; slabs per workgroup from a small cost model (below).
-// gemm_tile_pin (tools/tile_bench) pins the choice for measurements.
-static int g_tile_pin_mt = 0, g_tile_pin_zs = 0, g_tile_enable = -1;
-void gemm_tile_pin(int enable, int mt, int zs) { g_tile_enable = enable; g_tile_pin_mt = mt; g_tile_pin_zs = zs; }
-
-// GM_PP (kernels_gemm_pp.hip): the fp16 gates / FFN-up GEMMs on 256 (128) x 128 ping-pong tiles.  One workgroup per CU (144 KB of stage
-// buffers), so a launch is ceil(tiles / 256) rounds of one tile time; 256-row tiles are the efficient ones (85 flop per operand byte,
-// 16 MFMAs per 8 fragment reads), 128-row tiles fill the chip at fewer rows.  APRIL_GM_PP=0 keeps the round-3 GM_TILE forms;
-// APRIL_PP_MT pins the tile rows / 16 (gemm_pp_pin for tools/pp_bench).
-static int g_pp_enable = -1, g_pp_pin_mt = 0;
-void gemm_pp_pin(int enable, int mt) { g_pp_enable = enable; g_pp_pin_mt = mt; }
-static bool plan_pp(int M, int N, int zcount, TilePlan &t, bool wide_ok = false)
-{
-    static const int enabled = env_int("APRIL_GM_PP", 1), env_mt = env_int("APRIL_PP_MT", 0);
-    constexpr int min_tiles = 128;
-    static const int wide = env_int("APRIL_PP_WIDE", 1);      // 256 x 192 tiles (kernels_gemm_pw.hip) where they save a round of workgroups
-    if (!(g_pp_enable < 0 ? enabled : g_pp_enable) || N % 128 != 0) return false;
-    const long zc = std::max(1, zcount);
-    const long t16 = (long)(N / 128) * ((M + 255) / 256) * zc, t8 = (long)(N / 128) * ((M + 127) / 128) * zc;
-    int mt = g_pp_pin_mt ? g_pp_pin_mt : env_mt;
-    int nt = 8;
-    if (mt == 12) { if (!wide_ok) return false; mt = 16; nt = 12; }      // (pinned: the wide form or nothing)
-    else if (mt != 16 && mt != 8) {
-        if (t8 < min_tiles) return false;                 // a handful of tiles: the small-batch forms stream the weights with more workgroups
-        // rounds of one workgroup per CU; a 128-row tile costs ~0.6 of a 256-row one (half the MFMAs, the same weight pieces), a
-        // 256 x 192 tile 1.5 of it: the larger encoder's gates at three 512-row problems are 288 tiles of 256 x 128 (two rounds) but 192
-        // of 256 x 192 (one)
-        const long c16 = ((t16 + 255) / 256) * 100, c8 = ((t8 + 255) / 256) * 60;
-        mt = c16 <= c8 ? 16 : 8;
-        if (wide && wide_ok && N % 192 == 0) {
-            const long tw = (long)(N / 192) * ((M + 255) / 256) * zc, cw = ((tw + 255) / 256) * 150;
-            if (cw < std::min(c16, c8)) { mt = 16; nt = 12; }
-        }
-    }
-    t.mt = mt; t.nt = nt; t.zs = 1; t.mode = GM_PP;
-    return true;
-}
-
-static bool plan_tile(int M, int N, int kz, int zcount, bool force_full, TilePlan &t, bool always = false, bool big_ok = false, bool wide_ok = false, int pp_ok = 0)
-{
-    static const int enabled = env_int("APRIL_GM_TILE", 1);
-    constexpr int min_rows = 32, fused_tiles = 512, split_tiles = 256;      // (the rule above)
-    const int pin_mt = g_tile_pin_mt, pin_zs = g_tile_pin_zs;
-    if (N % 64 != 0) return false;
-    if (!always && (!(g_tile_enable < 0 ? enabled : g_tile_enable) || M < min_rows)) return false;
-    const long zc = std::max(1, zcount);
-    const long tiles4 = (long)(N / 64) * ((M + 63) / 64) * zc, tiles2 = (long)(N / 64) * ((M + 31) / 32) * zc;
-    // (fp16 tile engines: 64-row tiles for the N = d_model GEMMs measured no better than 32-row ones at 512 sessions -- 13.2 vs 12.7 ms
-    // of projection + FFN time per 10 feeds -- so the same rule serves both precisions)
-    const int mt = pin_mt ? (pin_mt == 4 ? 4 : 2) : (tiles4 >= fused_tiles ? 4 : 2);
-    const long tiles = mt == 4 ? tiles4 : tiles2;
-    if ((pp_ok & 1) && kz == 1 && pin_mt == 0 && plan_pp(M, N, zcount, t, (pp_ok & 2) != 0)) return true;
-    if (big_ok && kz == 1 && N % 128 == 0 && pin_mt == 0) {
-        // fp16 gates / FFN up: 128 x 128 tiles (eight waves) once they give most CUs a workgroup -- twice the flops per operand byte
-        static const int big = env_int("APRIL_TILE_BIG", 1);
-        constexpr int big_tiles = 192;
-        const long tiles8 = (long)(N / 128) * ((M + 127) / 128) * zc;
-        if (big && tiles8 >= big_tiles) { t.mt = 8; t.nt = 8; t.zs = 1; t.mode = GM_TILE; return true; }
-    }
-    int zs = kz;
-    // fp16 N = d_model GEMMs (projection, FFN down) keep all of K in the workgroup, i.e. their fused row epilogue: the cost model below
-    // prices a K cut at 5 % + 300, but the row kernel behind the planes and its launch boundary cost ~8 us at these sizes -- configs[4]
-    // at 512 sessions 1.887 -> 1.820 ms per step with the cut forbidden (round 6; APRIL_TILE_F16_FULLK=0 restores the model's choice)
-    // -- from 192 tiles per launch (one 512-row problem); below that the cut is what spreads the weights over the chip
-    static const int f16_fullk = env_int("APRIL_TILE_F16_FULLK", 1);
-    constexpr int f16_fullk_tiles = 192;
-    if (always && f16_fullk && wide_ok && tiles >= f16_fullk_tiles) { }
-    else if (pin_zs > 0) { if (!force_full) zs = std::min(kz, pin_zs); }
-    else if (pin_mt > 0) { /* measurement: pinned tile rows, all of K */ }
-    else {
-        if (tiles2 < split_tiles && !always) return false;          // small launches keep the round-2 schedules
-        if (!force_full) {
-            // workgroups are dealt to the 256 CUs round robin, a CU works through its share at the MFMA rate: cost = (workgroups
-            // per CU) x (stages per workgroup + ~3 stages of fill / epilogue), a K cut pays the row kernel on top (~5 %).  A slab is
-            // taken as 8 stages (chunks of 4 k blocks); mt = 4 stages hold twice the MFMAs of mt = 2 stages (same for every zs).
-            long best = -1;
-            for (int z = kz; z >= 1; z >>= 1) {
-                const long wgs = tiles * (kz / z), per_cu = (wgs + 255) / 256;
-                long cost = per_cu * (8L * z + 3) * 100;
-                if (z < kz) cost += cost / 20 + 300;
-                if (best < 0 || cost < best) { best = cost; zs = z; }
-            }
-        }
-    }
-    t.mt = mt; t.nt = 4; t.zs = zs; t.mode = GM_TILE;
-    return true;
-}
-
-bool gemm_tile_planned(int M, int N, int kz, int zcount) { TilePlan t; return plan_tile(M, N, kz, zcount, false, t); }
-
-bool gemm_fullk(int M, int N, int kz, bool force, int zcount, int tile_ok)
-{
-    TilePlan t;
-    // (tile_ok == 2 on a row-epilogue GEMM = the fp16 tile path: its wide tiles take part in the plan, here as in launch_gemm)
-    if (tile_ok && plan_tile(M, N, kz, zcount, force, t, tile_ok == 2, false, tile_ok == 2)) return t.zs == kz;
-    return plan_fullk(M, N, kz, t, force);
-}
-
-// Tile shape and slabs per workgroup.  Depends on M only through occupancy; numerics are tile-independent.
-static TilePlan plan_tiles(int M, int N, int kz, int epi, bool force_fullk = false, int zcount = 1, int tile_ok = 0, int zcount_true = 1, bool f16 = false, int pp_ok = 0)
-{
-    TilePlan t;
-    if (tile_ok && (epi == EPI_PARTIAL || epi == EPI_HR || epi == EPI_RESID_SSQ || epi == EPI_SLOT_STORE || epi == EPI_LSTM || epi == EPI_BIAS_DSWISH || (epi == EPI_XPART && tile_ok == 2))) {
-        // the caller asked gemm_fullk first: a row epilogue arrives only when that plan keeps all of K in the workgroup
-        if (plan_tile(M, N, kz, zcount_true, force_fullk || epi != EPI_PARTIAL, t, tile_ok == 2, f16 && tile_ok == 2 && (epi == EPI_LSTM || epi == EPI_BIAS_DSWISH || epi == EPI_XPART),
-                      tile_ok == 2 && (epi == EPI_PARTIAL || epi == EPI_HR || epi == EPI_RESID_SSQ), (f16 && tile_ok == 2) ? pp_ok : 0)) return t;
-        if (tile_ok == 2) { fprintf(stderr, "libapril(mi355x): launch_gemm: no GM_TILE plan for an always-tile GEMM (M=%d N=%d kz=%d)\n", M, N, kz); abort(); }
-    }
-    if (epi != EPI_LSTM && epi != EPI_BIAS_DSWISH && epi != EPI_XPART && plan_fullk(M, N, kz, t, force_fullk, zcount)) return t;
-    const int ntiles = N / 16;
-    t.mode = GM_SLAB;
-    t.mt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
-    const int mblocks = (M + t.mt * 16 - 1) / (t.mt * 16);
-    t.nt = 4;
-    // (problems sharing a z-batched launch fill the chip together: wider tiles, i.e. the hand-scheduled 64x32 / 64x64 forms, at
-    // fewer rows.  Only for 64-row tiles: the 16-row weight streams of the offline recurrence lose 12 % with 16x64 tiles.)
-    const int zc = t.mt == 4 ? zcount : 1;
-    while (t.nt > 1 && ((ntiles % t.nt) != 0 || (long)(ntiles / t.nt) * mblocks * kz * zc < 256)) t.nt >>= 1;
-    t.zs = 1;
-    if (epi == EPI_PARTIAL) {
-        // slabs per workgroup grow once the output tiles alone fill the chip; the 64x64 tile has registers for two
-        // tree levels only (NLVL in the kernel)
-        const long tiles = (long)(ntiles / t.nt) * mblocks;
-        const int zs_max = (t.mt == 4 && t.nt == 4) ? 4 : 8;
-        while (t.zs < kz && t.zs < zs_max && tiles * (kz / (t.zs * 2)) >= 256) t.zs *= 2;
-    }
-    return t;
-}
-
-int gemm_partials(int M, int N, int kz, int zcount, int tile_ok)
-{
-    const TilePlan t = plan_tiles(M, N, kz, EPI_PARTIAL, false, 1, tile_ok, zcount);
-    return t.mode == GM_FULLK ? 1 : kz / t.zs;
-}
-
-template <int MT, int NT, int EPI, int AOP, int MODE>
-static void launch_one(const GemmArgs &g, hipStream_t s)
-{
-    constexpr bool HAS_ASM = MODE == GM_SLAB && MT == 4 && (NT == 4 || NT == 2) && AOP == AOP_NONE && (EPI == EPI_LSTM || EPI == EPI_BIAS_DSWISH);
-    using Cfg = TileCfg<MT, NT>;
-    dim3 grid((unsigned)(g.N / Cfg::BN), (unsigned)((g.M + Cfg::BM - 1) / Cfg::BM), (unsigned)(MODE == GM_FULLK ? 1 : g.kz / g.zs));
-    const size_t lds = (Cfg::LDS_FLOATS + scale_lds_floats(g, Cfg::BM)) * sizeof(float);
-    if (g.wt == 1) { APRIL_LAUNCH((gemm_f32_kernel<MT, NT, EPI, AOP, 1, MODE, 0>), grid, dim3(256), lds, s, g); return; }
-    if constexpr (HAS_ASM) {
-        if (g.asm_loop && g.debug != 1) { APRIL_LAUNCH((gemm_f32_kernel<MT, NT, EPI, AOP, 0, MODE, 1>), grid, dim3(256), lds, s, g); return; }
-    }
-    APRIL_LAUNCH((gemm_f32_kernel<MT, NT, EPI, AOP, 0, MODE, 0>), grid, dim3(256), lds, s, g);
-}
-
-// (epilogue, prologue, schedule) combinations that exist; everything else is a programming error
-template <int MT, int NT>
-static bool dispatch(const GemmArgs &g, hipStream_t s)
-{
-#define CASE(E, A, MD) if (g.epi == E && g.a_op == A && g.mode == MD) { launch_one<MT, NT, E, A, MD>(g, s); return true; }
-    if constexpr (NT == 2) {        // the full-K schedule uses 16/32/64 x 32 tiles only
-        CASE(EPI_PARTIAL, AOP_TANH_ADD, GM_FULLK)
-        CASE(EPI_HR, AOP_NONE, GM_FULLK) CASE(EPI_RESID_SSQ, AOP_NONE, GM_FULLK) CASE(EPI_SLOT_STORE, AOP_NONE, GM_FULLK)
-        CASE(EPI_HR, AOP_NONE, GM_SLAB) CASE(EPI_RESID_SSQ, AOP_NONE, GM_SLAB) CASE(EPI_SLOT_STORE, AOP_NONE, GM_SLAB)
-    }
-    CASE(EPI_PARTIAL, AOP_NONE, GM_SLAB) CASE(EPI_PARTIAL, AOP_TANH_ADD, GM_SLAB)
-    CASE(EPI_LSTM, AOP_NONE, GM_SLAB) CASE(EPI_XPART, AOP_NONE, GM_SLAB)
-    CASE(EPI_BIAS_DSWISH, AOP_NONE, GM_SLAB)
-#undef CASE
-    return false;
-}
-
-// GM_KW (kernels_gemm_kw.hip) takes over a fused full-K plan of the K-split kernels -- the row-epilogue GEMMs on 16..64 x 32
-// GM_FULLK / GM_SLAB tiles -- when the operands allow it (gemm_kw_waves) and the launch is a few hundred rows: below KW_MIN_ROWS
-// the launch is latency-bound either way, above the GM_TILE threshold plan_tile has already taken it.  The decision never changes a
-// caller-visible property of the plan (all of K in the workgroup, row work in the epilogue), so gemm_fullk / gemm_partials need not know.
-constexpr int KW_MIN_ROWS = 3;
-static int g_kw_enable = -1, g_kw_pin_mt = 0;
-void gemm_kw_pin(int enable, int mt) { g_kw_enable = enable; g_kw_pin_mt = mt; }
-static bool kw_enabled() { static const int enabled = env_int("APRIL_GM_KW", 1); return (g_kw_enable < 0 ? enabled : g_kw_enable) != 0; }
-static void plan_kw(const GemmArgs &g, TilePlan &t, int zc)
-{
-    static const int env_mt = env_int("APRIL_KW_MT", 0);
-    if (!kw_enabled() || t.zs != g.kz) return;
-    if (t.mode == GM_TILE) {
-        // a FUSED GM_TILE plan (all of K in the workgroup: the same caller-visible shape) keeps the launch unless its tiles fill the 512
-        // resident slots badly: half a round or less, or a small remainder behind whole rounds (tools/kw_bench, FFN down: 512 x 2 rows
-        // 31.3 (GM_TILE) vs 29.6 us (GM_KW); 768 x 3: 64.8 vs 59.0; 2300 x 2: 117 vs 112; but 1024 x 2: 47 vs 54, 2048 x 3: 123 vs 147)
-        static const int over_tile = env_int("APRIL_KW_OVER_TILE", 1);
-        if (!over_tile || t.nt != 4) return;
-        const long tiles = (long)(g.N / 64) * ((g.M + 16 * t.mt - 1) / (16 * t.mt)) * zc;
-        const long rem = tiles % 512;
-        if (!(tiles <= 256 || (tiles > 512 && rem > 0 && rem <= 128))) return;
-    }
-    if (g.M < KW_MIN_ROWS || (g.epi != EPI_HR && g.epi != EPI_RESID_SSQ)) return;
-    if (!gemm_kw_waves(g)) return;
-    int mt = g_kw_pin_mt ? g_kw_pin_mt : env_mt;
-    if (!mt) {
-        // 32-row tiles are the efficient ones (one memory instruction per four MFMAs; 16-row tiles: three per eight), 16-row tiles the
-        // finer grain: the launch takes ceil(tiles / 256 CUs) rounds, a 16-row round costs ~0.55 of a 32-row one (tools/kw_bench)
-        const long t32 = (long)(g.N / 32) * ((g.M + 31) / 32) * zc, t16 = (long)(g.N / 32) * ((g.M + 15) / 16) * zc;
-        mt = ((t16 + 255) / 256) * 55 < ((t32 + 255) / 256) * 100 ? 1 : 2;
-    }
-    const int nt = (mt == 4 && g.N % 64 == 0) ? 4 : 2;      // (pinned 64-row tiles: 64 x 64, a wave tile of one memory instruction per eight MFMAs)
-    // APRIL_KW_MT and gemm_kw_pin can ask for shapes that were never instantiated (64-row tiles at N % 64 != 0 ...): the previous plan
-    // stays instead of an abort in launch_gemm_kw
-    if (!gemm_kw_has_kernel(g, mt, nt)) return;
-    t.mt = mt; t.nt = nt; t.zs = g.kz; t.mode = GM_KW;
-}
-
-// plan + checks + measurement knobs: everything launch_gemm decides on the host
-static TilePlan finalize_gemm(GemmArgs &g)
+// the plan and the measurement knobs into the argument block
+static void finalize_gemm(GemmArgs &g, const GemmPlan &p)
 {
     static const int dbg = env_int("APRIL_GEMM_DEBUG", 0);
-    g.debug = dbg;
     static const int asm_loop = env_int("APRIL_GEMM_ASM", 1);     // 0 = compiler-scheduled loop everywhere (A/B)
-    static const int z_tiles = env_int("APRIL_Z_TILES", 2);      // A/B: 0 = plan z-batched problems as if each had the chip to itself, 1 = hint everywhere, 2 = fused-epilogue slab tiles only, 3 = full-K tiles only
-    const int zc = std::max(1, g.zcount);
-    const bool is_slab_epi = g.epi == EPI_LSTM || g.epi == EPI_BIAS_DSWISH || g.epi == EPI_XPART;
-    // GM_TILE eligibility: planner-rule GEMMs (tile_ok 1) are the fp32 row-epilogue / partial GEMMs over one A segment; always-tile
-    // GEMMs (tile_ok 2, fp16 tile engines) may also carry two segments and the LSTM / DoubleSwish epilogues
-    // (the fp16 tile kernels also have the layer-major halves of the gate GEMM: wave_mask 0x3 + EPI_XPART, 0xC + p_add + EPI_LSTM)
-    const bool lm_half = g.tile_ok == 2 && g.wt == 1 && ((g.epi == EPI_XPART && g.wave_mask == 0x3 && !g.p_add) || (g.epi == EPI_LSTM && g.wave_mask == 0xC && g.p_add));
-    const bool plain = g.a_op == AOP_NONE && g.N % 64 == 0 && ((g.wave_mask == 0xF && !g.p_add) || lm_half);
-    const int tile_ok = !plain ? 0 : (g.tile_ok == 2 ? 2 : ((g.tile_ok == 1 && g.K1 == 0 && g.wt == 0 && g.epi != EPI_LSTM && g.epi != EPI_BIAS_DSWISH) ? 1 : 0));
-    if (g.tile_ok == 2 && !tile_ok) { fprintf(stderr, "libapril(mi355x): launch_gemm: always-tile GEMM with a prologue / wave mask / odd N\n"); abort(); }
-    TilePlan t = plan_tiles(g.M, g.N, g.kz, g.epi, g.force_fullk != 0, (z_tiles == 1 || (z_tiles == 2 && is_slab_epi) || (z_tiles == 3 && !is_slab_epi)) ? zc : 1, tile_ok, zc, g.wt == 1,
-                            (g.wt == 1 && is_slab_epi && gemm_pp_ok(g, 16)) ? (1 | (gemm_pw_ok(g) ? 2 : 0)) : 0);
-    plan_kw(g, t, zc);
-    const bool row_epi = g.epi == EPI_HR || g.epi == EPI_RESID_SSQ || g.epi == EPI_SLOT_STORE;
-    if (row_epi && t.zs != g.kz) { fprintf(stderr, "libapril(mi355x): launch_gemm: row epilogue %d needs the full-K plan (M=%d N=%d kz=%d)\n", g.epi, g.M, g.N, g.kz); abort(); }
-    g.zs = t.zs; g.mode = t.mode;
-    // EPI_LSTM with x_scale scales the partial sums of waves 0 and 1: they must hold exactly A segment 0
-    if ((g.epi == EPI_LSTM || g.epi == EPI_XPART) && (g.x_scale.ssq || g.p_add || g.wave_mask != 0xF) && (g.kz != 1 || g.K0 * 2 != g.K)) { fprintf(stderr, "libapril(mi355x): launch_gemm: x_scale needs K0 == K / 2 and kz == 1\n"); abort(); }
+    if (p.error) plan_die(g, p.error);
+    g.zs = p.zs; g.mode = p.mode; g.debug = dbg;
     // hand-scheduled K loop wherever it exists (fused-epilogue 64x64 / 64x32 fp32 tiles).  Round-2 measurements
     // (tools/gemm_bench, gates [M,1024]x[1024,4096] + LSTM cell, us per launch at M = 512 / 1024 / 2048):
     //   hand loop, no skew 42.2 / 85.6 / 159.2   hand loop, skew 2: 85.5 / 174.3   compiler loop, skew 2 (round-1 choice at two
     //   workgroups per CU): 91.3 / 170.4   compiler loop, no skew: 56.5 / 100.7 / 180.2;  FFN-up [2048,512]x[512,2048]: 42.3 vs 45.7
     g.asm_loop = asm_loop != 0;
-    return t;
 }
 
-// GM_KW instead of the weight-stream row kernel of kernels_recur.hip for the FFN-down GEMM from KW_MIN_ROWS (3) rows:
-// 16 x 32 tiles on eight waves against two 16-column tiles on sixteen waves -- 4 / 8 / 16 sessions 0.499 / 0.537 / 0.602 -> 0.475 / 0.496 / 0.527 ms
-// per 100 ms feed, one or two rows the same within the noise (they stay on the stream kernels, as does the recurrent pair of a long feed)
-static bool kw_before_recur(const GemmArgs &g)
+// One K-split kernel: g itself (dev_args == null) or, where the z-batched kernel exists (Z), n problems of g's shape at dev_args
+template <int MT, int NT, int EPI, int AOP, int MODE, bool Z>
+static void launch_one(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t s)
 {
-    static_assert(KW_MIN_ROWS <= 16, "the row range below is [KW_MIN_ROWS, 16]");
-    // (FFN down only: 9.5 .. 12.8 -> 8.2 us per launch at 8 .. 16 rows; the projection's stream kernel is the faster one there, 4.7 .. 5.4 vs 5.8 us)
-    return kw_enabled() && g.M >= KW_MIN_ROWS && g.M <= 16 && g.epi == EPI_RESID_SSQ && gemm_kw_waves(g) != 0;
-}
-
-void launch_gemm(const GemmArgs &g_in, hipStream_t s)
-{
-    GemmArgs g = g_in;
-    if (!kw_before_recur(g)) if (const int rf = recur_form(g)) { launch_recur(g, rf, nullptr, 1, s); return; }
-    const TilePlan t = finalize_gemm(g);
-    if (t.mode == GM_PP) { if (t.nt == 12) launch_gemm_pw(g, nullptr, 0, s); else launch_gemm_pp(g, t.mt, nullptr, 0, s); return; }
-    if (t.mode == GM_TILE) { launch_gemm_tile(g, t.mt, t.nt, nullptr, 0, s); return; }
-    if (t.mode == GM_KW) { launch_gemm_kw(g, t.mt, t.nt, nullptr, 0, s); return; }
-    const int mt = t.mt, nt = t.nt;
-    bool ok = false;
-    if (mt == 1) { if (nt == 4) ok = dispatch<1, 4>(g, s); else if (nt == 2) ok = dispatch<1, 2>(g, s); else ok = dispatch<1, 1>(g, s); }
-    else if (mt == 2) { if (nt == 4) ok = dispatch<2, 4>(g, s); else if (nt == 2) ok = dispatch<2, 2>(g, s); else ok = dispatch<2, 1>(g, s); }
-    else { if (nt == 4) ok = dispatch<4, 4>(g, s); else if (nt == 2) ok = dispatch<4, 2>(g, s); else ok = dispatch<4, 1>(g, s); }
-    if (!ok) { fprintf(stderr, "libapril(mi355x): launch_gemm: no kernel for epi %d a_op %d mode %d tile %dx%d\n", g.epi, g.a_op, g.mode, mt, nt); abort(); }
-}
-
-// ---- n independent problems of one shape in one launch (gemm_f32_zkernel)
-template <int MT, int NT, int EPI, int AOP, int MODE>
-static void launch_one_z(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t s)
-{
+    constexpr bool HAS_ASM = MODE == GM_SLAB && MT == 4 && (NT == 4 || NT == 2) && AOP == AOP_NONE && (EPI == EPI_LSTM || EPI == EPI_BIAS_DSWISH);
     using Cfg = TileCfg<MT, NT>;
     const int zdiv = MODE == GM_FULLK ? 1 : g.kz / g.zs;
-    dim3 grid((unsigned)(g.N / Cfg::BN), (unsigned)((g.M + Cfg::BM - 1) / Cfg::BM), (unsigned)(zdiv * n));
+    dim3 grid((unsigned)(g.N / Cfg::BN), (unsigned)((g.M + Cfg::BM - 1) / Cfg::BM), (unsigned)(zdiv * (dev_args ? n : 1)));
     const size_t lds = (Cfg::LDS_FLOATS + scale_lds_floats(g, Cfg::BM)) * sizeof(float);
-    constexpr bool HAS_ASM = MODE == GM_SLAB && MT == 4 && (NT == 4 || NT == 2) && AOP == AOP_NONE && (EPI == EPI_LSTM || EPI == EPI_BIAS_DSWISH);
-    if (g.wt == 1) { APRIL_LAUNCH((gemm_f32_zkernel<MT, NT, EPI, AOP, 1, MODE, 0>), grid, dim3(256), lds, s, dev_args, zdiv); return; }
-    if constexpr (HAS_ASM) {
-        if (g.asm_loop && g.debug != 1) {
+    const bool hand_loop = HAS_ASM && g.asm_loop && g.debug != 1;
+    if constexpr (Z) if (dev_args) {
+        if (g.wt == 1) { APRIL_LAUNCH((gemm_f32_zkernel<MT, NT, EPI, AOP, 1, MODE, 0>), grid, dim3(256), lds, s, dev_args, zdiv); return; }
+        if constexpr (HAS_ASM) if (hand_loop) {
             if constexpr (EPI == EPI_LSTM && MT == 4 && NT == 4) {
                 // APRIL_GEMM_WALK (1): 512 walking workgroups when the launch is more than one round of the chip's 512 resident
                 // 64 x 64 gate workgroups but not a whole number of rounds
@@ -1061,33 +830,71 @@ static void launch_one_z(const GemmArgs &g, const GemmArgs *dev_args, int n, hip
             }
             APRIL_LAUNCH((gemm_f32_zkernel<MT, NT, EPI, AOP, 0, MODE, 1>), grid, dim3(256), lds, s, dev_args, zdiv); return;
         }
+        APRIL_LAUNCH((gemm_f32_zkernel<MT, NT, EPI, AOP, 0, MODE, 0>), grid, dim3(256), lds, s, dev_args, zdiv); return;
     }
-    APRIL_LAUNCH((gemm_f32_zkernel<MT, NT, EPI, AOP, 0, MODE, 0>), grid, dim3(256), lds, s, dev_args, zdiv);
+    if (g.wt == 1) { APRIL_LAUNCH((gemm_f32_kernel<MT, NT, EPI, AOP, 1, MODE, 0>), grid, dim3(256), lds, s, g); return; }
+    if constexpr (HAS_ASM) if (hand_loop) { APRIL_LAUNCH((gemm_f32_kernel<MT, NT, EPI, AOP, 0, MODE, 1>), grid, dim3(256), lds, s, g); return; }
+    APRIL_LAUNCH((gemm_f32_kernel<MT, NT, EPI, AOP, 0, MODE, 0>), grid, dim3(256), lds, s, g);
 }
 
+// (epilogue, prologue, schedule) combinations that exist, and whether the z-batched kernel does (Z); everything else is a programming error
 template <int MT, int NT>
-static bool dispatch_z(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t s)
+static bool dispatch(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t s)
 {
-#define CASE(E, MD) if (g.epi == E && g.a_op == AOP_NONE && g.mode == MD) { launch_one_z<MT, NT, E, AOP_NONE, MD>(g, dev_args, n, s); return true; }
-    if constexpr (NT == 2) {
-        CASE(EPI_HR, GM_FULLK) CASE(EPI_RESID_SSQ, GM_FULLK)
-        CASE(EPI_HR, GM_SLAB) CASE(EPI_RESID_SSQ, GM_SLAB)
+#define CASE(E, A, MD, Z) if (g.epi == E && g.a_op == A && g.mode == MD && (Z || !dev_args)) { launch_one<MT, NT, E, A, MD, Z>(g, dev_args, n, s); return true; }
+    if constexpr (NT == 2) {        // the full-K schedule uses 16/32/64 x 32 tiles only
+        CASE(EPI_PARTIAL, AOP_TANH_ADD, GM_FULLK, false)
+        CASE(EPI_HR, AOP_NONE, GM_FULLK, true) CASE(EPI_RESID_SSQ, AOP_NONE, GM_FULLK, true) CASE(EPI_SLOT_STORE, AOP_NONE, GM_FULLK, false)
+        CASE(EPI_HR, AOP_NONE, GM_SLAB, true) CASE(EPI_RESID_SSQ, AOP_NONE, GM_SLAB, true) CASE(EPI_SLOT_STORE, AOP_NONE, GM_SLAB, false)
     }
-    CASE(EPI_LSTM, GM_SLAB) CASE(EPI_XPART, GM_SLAB) CASE(EPI_BIAS_DSWISH, GM_SLAB)
+    CASE(EPI_PARTIAL, AOP_NONE, GM_SLAB, false) CASE(EPI_PARTIAL, AOP_TANH_ADD, GM_SLAB, false)
+    CASE(EPI_LSTM, AOP_NONE, GM_SLAB, true) CASE(EPI_XPART, AOP_NONE, GM_SLAB, true)
+    CASE(EPI_BIAS_DSWISH, AOP_NONE, GM_SLAB, true)
 #undef CASE
     return false;
 }
+// the runtime tile of the K-split kernels (16 mt x 16 nt) as template arguments
+template <int MT>
+static bool dispatch_nt(int nt, const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t s)
+{
+    return nt == 4 ? dispatch<MT, 4>(g, dev_args, n, s) : nt == 2 ? dispatch<MT, 2>(g, dev_args, n, s) : dispatch<MT, 1>(g, dev_args, n, s);
+}
 
+// The one dispatch: g finalized with plan p; dev_args != null: n problems of g's shape in device memory
+static void launch_planned(const GemmArgs &g, const GemmPlan &p, const GemmArgs *dev_args, int n, hipStream_t s)
+{
+    switch (p.route) {
+    case ROUTE_STREAM: launch_recur(g, p.form, dev_args, dev_args ? n : 1, s); return;
+    case ROUTE_PW: launch_gemm_pw(g, dev_args, n, s); return;
+    case ROUTE_PP: launch_gemm_pp(g, p.mt, dev_args, n, s); return;
+    case ROUTE_TILE: launch_gemm_tile(g, p.mt, p.nt, dev_args, n, s); return;
+    case ROUTE_KW: launch_gemm_kw(g, p.mt, p.nt, dev_args, n, s); return;
+    }
+    const bool ok = p.mt == 1 ? dispatch_nt<1>(p.nt, g, dev_args, n, s) : p.mt == 2 ? dispatch_nt<2>(p.nt, g, dev_args, n, s) : dispatch_nt<4>(p.nt, g, dev_args, n, s);
+    if (!ok) { fprintf(stderr, "libapril(mi355x): %s: no kernel for epi %d a_op %d mode %d tile %dx%d\n", dev_args ? "launch_gemm_z" : "launch_gemm", g.epi, g.a_op, g.mode, p.mt, p.nt); abort(); }
+}
+
+// (a launch runs what plan_launch says of exactly this block: the engine's question, gemm_plan, is asked before the block is chosen)
+void launch_gemm(const GemmArgs &g_in, hipStream_t s)
+{
+    GemmArgs g = g_in;
+    const GemmPlan p = plan_launch(gemm_query(g), knobs());
+    if (p.route != ROUTE_STREAM) finalize_gemm(g, p);      // (the stream kernels read neither the plan nor the knobs)
+    launch_planned(g, p, nullptr, 0, s);
+}
+
+// ---- n independent problems of one shape in one launch
 void stage_gemm_z(const GemmArgs *items, int n, GemmArgs *staged)
 {
-    TilePlan t0{0, 0, 0, 0};
+    GemmPlan p0;
     for (int i = 0; i < n; ++i) {
         staged[i] = items[i];
         staged[i].zcount = n;
-        const TilePlan t = finalize_gemm(staged[i]);
-        if (i == 0) t0 = t;
+        const GemmPlan p = plan_launch(gemm_query(staged[i]), knobs());
+        finalize_gemm(staged[i], p);
+        if (i == 0) p0 = p;
         const GemmArgs &a = staged[i], &b = staged[0];
-        if (t.mt != t0.mt || t.nt != t0.nt || t.zs != t0.zs || t.mode != t0.mode || a.M != b.M || a.N != b.N || a.K != b.K || a.kz != b.kz || a.epi != b.epi || a.wt != b.wt ||
+        if (p.mt != p0.mt || p.nt != p0.nt || p.zs != p0.zs || p.mode != p0.mode || a.M != b.M || a.N != b.N || a.K != b.K || a.kz != b.kz || a.epi != b.epi || a.wt != b.wt ||
             a.a_op != AOP_NONE || a.x_scale.groups != b.x_scale.groups || a.r_scale.groups != b.r_scale.groups || (a.x_scale.ssq == nullptr) != (b.x_scale.ssq == nullptr)) {
             fprintf(stderr, "libapril(mi355x): stage_gemm_z: the problems of one launch must have one shape\n"); abort();
         }
@@ -1097,23 +904,46 @@ void stage_gemm_z(const GemmArgs *items, int n, GemmArgs *staged)
 void launch_gemm_z(const GemmArgs *staged, int n, const GemmArgs *dev_args, hipStream_t s)
 {
     if (n <= 0) return;
-    const GemmArgs &g = staged[0];
-    if (!kw_before_recur(g)) if (const int rf = recur_form(g)) { launch_recur(g, rf, dev_args, n, s); return; }      // (stage_gemm_z checked that the n problems have one shape)
-    GemmArgs probe = g;
-    const TilePlan t = finalize_gemm(probe);
-    if (t.mode == GM_PP) {
-        if (t.nt == 12) launch_gemm_pw(g, dev_args, n, s);
-        else launch_gemm_pp(g, t.mt, dev_args, n, s);
-        return;
-    }
-    if (t.mode == GM_TILE) { launch_gemm_tile(g, t.mt, t.nt, dev_args, n, s); return; }
-    if (t.mode == GM_KW) { launch_gemm_kw(g, t.mt, t.nt, dev_args, n, s); return; }
-    const int mt = t.mt, nt = t.nt;
-    bool ok = false;
-    if (mt == 1) { if (nt == 4) ok = dispatch_z<1, 4>(g, dev_args, n, s); else if (nt == 2) ok = dispatch_z<1, 2>(g, dev_args, n, s); else ok = dispatch_z<1, 1>(g, dev_args, n, s); }
-    else if (mt == 2) { if (nt == 4) ok = dispatch_z<2, 4>(g, dev_args, n, s); else if (nt == 2) ok = dispatch_z<2, 2>(g, dev_args, n, s); else ok = dispatch_z<2, 1>(g, dev_args, n, s); }
-    else { if (nt == 4) ok = dispatch_z<4, 4>(g, dev_args, n, s); else if (nt == 2) ok = dispatch_z<4, 2>(g, dev_args, n, s); else ok = dispatch_z<4, 1>(g, dev_args, n, s); }
-    if (!ok) { fprintf(stderr, "libapril(mi355x): launch_gemm_z: no kernel for epi %d mode %d tile %dx%d\n", g.epi, g.mode, mt, nt); abort(); }
+    // (stage_gemm_z checked that the n problems have one shape, and finalized them)
+    launch_planned(staged[0], plan_launch(gemm_query(staged[0]), knobs()), dev_args, n, s);
 }
 
+// ---- the planner for CPU-side tests (include/aprilx_engine.h): no GPU call
 }  // namespace aprilx
+using namespace aprilx;
+
+int aprilx_plan_gemm(int M, int N, int kz, int zcount, int tile_ok, int force, int32_t *out)
+{
+    if (!out || M <= 0 || N <= 0 || kz <= 0 || zcount <= 0) return -1;
+    // the question of a row-epilogue GEMM of this shape: fused?  planes of its partial form; would the occupancy rule (tile_ok 1) plan GM_TILE?
+    GemmQuery q; q.M = M; q.N = N; q.kz = kz; q.zcount = zcount; q.tile_ok = tile_ok; q.force_fullk = force; q.epi = EPI_HR;
+    const GemmPlan part = plan_partial_form(q, knobs());
+    if (part.error) return -1;
+    out[0] = row_fused(q, knobs()) ? 1 : 0;
+    out[1] = part.planes;
+    q.tile_ok = 1;
+    out[2] = plan_partial_form(q, knobs()).mode == GM_TILE ? 1 : 0;
+    return 0;
+}
+// in: M N K K0 K1 kz epi a_op wt wave_mask p_add? x_scale? zcount tile_ok force_fullk lda0 x_scale.groups r_scale.groups(0: none) out? out16? state16? ssq_out?
+// out: the capabilities gemm_query finds (recur_form, kw, pp, pw) and gemm_plan's route form mode mt nt zs planes fused error.  No GPU call.
+int aprilx_gemm_plan_debug(const int32_t *in, int32_t *out)
+{
+    if (!in || !out) return -1;
+    static float dummy[4];
+    GemmArgs g;                                       // only which pointers are set matters to the capability predicates
+    g.M = in[0]; g.N = in[1]; g.K = in[2]; g.K0 = in[3]; g.K1 = in[4]; g.kz = in[5]; g.epi = in[6]; g.a_op = in[7]; g.wt = in[8]; g.wave_mask = in[9];
+    if (in[10]) g.p_add = dummy;
+    if (in[11]) { g.x_scale.ssq = dummy; g.x_scale.groups = in[16]; }
+    g.zcount = in[12]; g.tile_ok = in[13]; g.force_fullk = in[14]; g.lda0 = in[15];
+    if (in[17]) { g.r_scale.ssq = dummy; g.r_scale.groups = in[17]; }
+    if (in[18]) g.out = dummy;
+    if (in[19]) g.out16 = dummy;
+    if (in[20]) g.state16 = dummy;
+    if (in[21]) g.ssq_out = dummy;
+    const GemmQuery q = gemm_query(g);
+    const GemmPlan p = gemm_plan(g);
+    const int32_t r[13] = {q.recur_form, q.kw_ok, q.pp_ok, q.pw_ok, p.route, p.form, p.mode, p.mt, p.nt, p.zs, p.planes, p.fused, p.error};
+    std::copy(r, r + 13, out);
+    return 0;
+}

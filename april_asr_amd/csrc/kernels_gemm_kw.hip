@@ -454,14 +454,15 @@ void launch_kw_one(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream
     launch_gemm_pair<&gemm_kw_kernel<MT, NT, EPI, CPW>, &gemm_kw_zkernel<MT, NT, EPI, CPW>>(grid, dim3(G::NTH), lds, true, s, g, dev_args);
 }
 
+// (every GEMM gemm_kw_waves accepts has one of these: EPI_HR / EPI_RESID_SSQ, kz 8 / 2 = 4 / 1 chunks per wave)
 template <int MT, int NT>
-bool dispatch_kw(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t s, bool dry)
+bool dispatch_kw(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t s)
 {
     const int cpw = 4 * g.kz / NW;
-    if (g.epi == EPI_HR && cpw == 4) { if (!dry) launch_kw_one<MT, NT, EPI_HR, 4>(g, dev_args, n, s); return true; }
-    if (g.epi == EPI_HR && cpw == 1) { if (!dry) launch_kw_one<MT, NT, EPI_HR, 1>(g, dev_args, n, s); return true; }
-    if (g.epi == EPI_RESID_SSQ && cpw == 4) { if (!dry) launch_kw_one<MT, NT, EPI_RESID_SSQ, 4>(g, dev_args, n, s); return true; }
-    if (g.epi == EPI_RESID_SSQ && cpw == 1) { if (!dry) launch_kw_one<MT, NT, EPI_RESID_SSQ, 1>(g, dev_args, n, s); return true; }
+    if (g.epi == EPI_HR && cpw == 4) { launch_kw_one<MT, NT, EPI_HR, 4>(g, dev_args, n, s); return true; }
+    if (g.epi == EPI_HR && cpw == 1) { launch_kw_one<MT, NT, EPI_HR, 1>(g, dev_args, n, s); return true; }
+    if (g.epi == EPI_RESID_SSQ && cpw == 4) { launch_kw_one<MT, NT, EPI_RESID_SSQ, 4>(g, dev_args, n, s); return true; }
+    if (g.epi == EPI_RESID_SSQ && cpw == 1) { launch_kw_one<MT, NT, EPI_RESID_SSQ, 1>(g, dev_args, n, s); return true; }
     return false;
 }
 
@@ -484,27 +485,18 @@ int gemm_kw_waves(const GemmArgs &g)
     return NW;
 }
 
-// launch of a GEMM whose plan chose GM_KW: tile 16 mt x 16 nt, g.zs == g.kz
-// the kernel of (g, tile): launched, or (dry) only looked up -- ONE table for plan_kw's question and for the launch
-static bool kw_find(const GemmArgs &g, int mt, int nt, const GemmArgs *dev_args, int n, hipStream_t s, bool dry)
-{
-    if (!gemm_kw_waves(g)) return false;
-    if (mt == 4 && nt == 4) return dispatch_kw<4, 4>(g, dev_args, n, s, dry);
-    if (mt == 2 && nt == 2) return dispatch_kw<2, 2>(g, dev_args, n, s, dry);
-    if (mt == 1 && nt == 2) return dispatch_kw<1, 2>(g, dev_args, n, s, dry);
-    return false;
-}
-
-// is there a GM_KW kernel for this GEMM on 16 mt x 16 nt tiles?  (plan_kw asks before it commits to the schedule: pinned tile shapes and
-// environment knobs must never pick a form that was not instantiated)
-bool gemm_kw_has_kernel(const GemmArgs &g, int mt, int nt) { return kw_find(g, mt, nt, nullptr, 0, nullptr, true); }
-
+// launch of a GEMM whose plan chose GM_KW: tile 16 mt x 16 nt, g.zs == g.kz.  The tiles are APRIL_KW_TILES (gemm_plan.h): the planner
+// asks the same list before it commits to the schedule, so pinned tile shapes and environment knobs never pick a form that was not
+// instantiated
 void launch_gemm_kw(const GemmArgs &g, int mt, int nt, const GemmArgs *dev_args, int n, hipStream_t s)
 {
-    if (!kw_find(g, mt, nt, dev_args, n, s, false)) {
-        fprintf(stderr, "libapril(mi355x): launch_gemm_kw: no kernel for epi %d tile %d x %d, %d waves\n", g.epi, 16 * mt, 16 * nt, gemm_kw_waves(g));
-        abort();
+    if (gemm_kw_waves(g)) {
+#define X(a, b) if (mt == a && nt == b && dispatch_kw<a, b>(g, dev_args, n, s)) return;
+        APRIL_KW_TILES(X)
+#undef X
     }
+    fprintf(stderr, "libapril(mi355x): launch_gemm_kw: no kernel for epi %d tile %d x %d, %d waves\n", g.epi, 16 * mt, 16 * nt, gemm_kw_waves(g));
+    abort();
 }
 
 }  // namespace aprilx

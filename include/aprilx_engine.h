@@ -113,8 +113,13 @@ APRIL_EXPORT int aprilx_run_decide(AprilASRModel model, int n, int op, const flo
  * tile_ok 0 = round-2 schedules, 1 = GM_TILE by the occupancy rule, 2 = GM_TILE always (fp16 tile path); force = the caller
  * needs the fused form): out[0] = 1 when the plan keeps all of K in the workgroup (row epilogue fused into the GEMM), out[1] =
  * partial planes the split form writes (finished by the row kernel), out[2] = 1 when the occupancy rule picks GM_TILE.  No GPU
- * needed; tests only (the engine and the kernels consult the same functions, so their decisions cannot diverge). */
+ * needed; tests only (the engine and the launch wrappers plan with the same function, csrc/gemm_plan.h). */
 APRIL_EXPORT int aprilx_plan_gemm(int M, int N, int kz, int zcount, int tile_ok, int force, int32_t *out);
+/* The plan of one GEMM argument block as the launch wrappers see it (csrc/kernels.h gemm_plan).  in[22]: M N K K0 K1 kz epi a_op wt
+ * wave_mask p_add? x_scale? zcount tile_ok force_fullk lda0 x_scale.groups r_scale.groups (0: none) out? out16? state16? ssq_out?
+ * out[13]: the capabilities found for it (stream-kernel form, GM_KW, GM_PP, 192-column GM_PP), then route form mode mt nt zs planes
+ * fused error (csrc/gemm_plan.h).  No GPU needed; tests only. */
+APRIL_EXPORT int aprilx_gemm_plan_debug(const int32_t *in, int32_t *out);
 
 /* Ramp merge, the pure host part: which problems of the NEXT feed's first R macro steps the last R macro steps
  * of a feed of T chunks over L layers can hold.  Writes one record of 3 + 2 R words per window step to out (cap words): own macro step

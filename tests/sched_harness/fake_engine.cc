@@ -282,9 +282,6 @@ void Engine::debug_decide(const DecideRequest &) { abort(); }
 void Engine::debug_fbank(int, const int16_t *, float *) { abort(); }
 
 // planner entry points of the kernel files that april_api.cc exposes for CPU-side tests: not part of this harness
-bool gemm_fullk(int, int, int, bool, int, int) { return true; }
-int gemm_partials(int, int, int, int, int) { return 1; }
-bool gemm_tile_planned(int, int, int, int) { return false; }
 int recur_form(const GemmArgs &) { return 0; }
 int gemm_kw_waves(const GemmArgs &) { return 0; }
 

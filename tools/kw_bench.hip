@@ -156,7 +156,8 @@ int main(int argc, char **argv)
         const std::vector<float> want = snapshot(ps);
         const double t_ref = time_chain(ref, s, iters);
         printf("%-13s M=%d N=%d K=%d kz=%d x%d | round-4 schedule (mode %d): %7.2f us (%.3f of peak)\n", sh.name, sh.M, sh.N, sh.K, sh.kz, sh.n, ref.gh[0].mode, t_ref, flops / (t_ref * 1e-6) / 157.3e12);
-        if (gemm_tile_planned(sh.M, sh.N, sh.kz, sh.n) && gemm_fullk(sh.M, sh.N, sh.kz, true, sh.n, 1)) {
+        const GemmPlan tp = gemm_plan(gemm_of(ps[0], sh.n, 1));
+        if (tp.fused && tp.mode == GM_TILE) {
             // GM_TILE with the row work fused, where the engine's planner would take it (for the crossover between the two)
             gemm_kw_pin(0, 0);
             Chain ct = make_chain(ps, 1);

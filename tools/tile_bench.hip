@@ -98,14 +98,17 @@ static Chain make_chain(const std::vector<Problem> &ps, bool tile_ok)
 {
     Chain c; c.n = (int)ps.size();
     const Problem &p0 = ps[0];
-    const bool fused = gemm_fullk(p0.M, p0.N, p0.kz, /*force*/ !tile_ok && c.n > 1, c.n, tile_ok ? 1 : 0);
+    GemmArgs q = gemm_of(p0, true, tile_ok, c.n);
+    q.force_fullk = !tile_ok && c.n > 1;
+    const GemmPlan plan = gemm_plan(q);
+    const bool fused = plan.fused;
     c.split = !fused;
     std::vector<GemmArgs> items;
     for (const Problem &p : ps) {
         GemmArgs g = gemm_of(p, fused, tile_ok, c.n);
         if (fused && !tile_ok && c.n > 1) g.force_fullk = 1;         // what the round-2 feed wavefront does
         items.push_back(g);
-        if (!fused) c.rh.push_back(row_of(p, gemm_partials(p.M, p.N, p.kz, c.n, tile_ok ? 1 : 0)));
+        if (!fused) c.rh.push_back(row_of(p, plan.planes));
     }
     if (c.n == 1) c.gh = items;
     else {
@@ -204,7 +207,7 @@ int main(int argc, char **argv)
         for (const Pin &pin : pins) {
             if (only_mt >= 0 && (pin.mt != only_mt || pin.zs != only_zs)) continue;
             gemm_tile_pin(1, pin.mt, pin.zs);
-            if (!gemm_tile_planned(sh.M, sh.N, sh.kz, sh.n)) { printf("    (GM_TILE not planned for this shape)\n"); break; }
+            if (gemm_plan(gemm_of(ps[0], false, true, sh.n)).mode != GM_TILE) { printf("    (GM_TILE not planned for this shape)\n"); break; }
             Chain c = make_chain(ps, true);
             clear_outputs(ps); c.run(s); CK(hipStreamSynchronize(s));
             const std::vector<float> got = snapshot(ps);
