@@ -20,7 +20,8 @@ import numpy as np
 
 from . import _ffi
 
-__all__ = ["Result", "Token", "Model", "Session", "SessionGroup", "Bias", "VadEvent", "resampler_taps", "decode_host", "vad_plan", "vad_host", "vad_events_host"]
+__all__ = ["Result", "Token", "Model", "Session", "SessionGroup", "Bias", "VadEvent", "resampler_taps", "decode_host", "vad_plan", "vad_host", "vad_events_host",
+           "DtmfEvent", "dtmf_plan", "dtmf_tables", "dtmf_host", "dtmf_decide_host", "dtmf_events_host"]
 
 
 class Result(IntEnum):
@@ -45,6 +46,24 @@ class VadEvent:
 
     def __repr__(self):
         return "VadEvent(%s, %d)" % ("SPEECH_START" if self.kind == 1 else "SPEECH_END", self.time_ms)
+
+
+class DtmfEvent:
+    """A DTMF event of a session (Session(dtmf=...)): `kind` is DtmfEvent.DOWN or DtmfEvent.UP, `digit` one of "123A456B789C*0#D",
+    `time_ms` the position in the session's audio on the frame clock."""
+    DOWN, UP = 1, 2
+    __slots__ = ("kind", "digit", "time_ms")
+
+    def __init__(self, kind, digit, time_ms):
+        self.kind = int(kind)
+        self.digit = digit.decode("ascii") if isinstance(digit, bytes) else str(digit)
+        self.time_ms = int(time_ms)
+
+    def __eq__(self, other):
+        return isinstance(other, DtmfEvent) and (self.kind, self.digit, self.time_ms) == (other.kind, other.digit, other.time_ms)
+
+    def __repr__(self):
+        return "DtmfEvent(%s, %r, %d)" % ("DOWN" if self.kind == 1 else "UP", self.digit, self.time_ms)
 
 
 class Token:
@@ -354,6 +373,34 @@ class Model:
         cuts = np.cumsum(n)[:-1]
         return np.split(b, cuts), np.split(e, cuts), [st[i] for i in range(k)]
 
+    def run_dtmf(self, options, frames_list, powers: bool = True):
+        """dtmf_kernel alone (aprilx_run_dtmf; tests): run r with options[r] (dicts / True as Session.set_dtmf) over frames_list[r]
+        [n][fft_size] int16, all in ONE launch.  Returns ([codes], [powers [n][9]])."""
+        k = len(frames_list)
+        opts = (_ffi.AprilxDtmfOptions * k)(*[_dtmf_options(o) for o in options])
+        n = np.array([len(f) for f in frames_list], np.int32)
+        fr = np.ascontiguousarray(np.concatenate([np.asarray(f, np.int16).reshape(len(f), -1) for f in frames_list]), np.int16)
+        codes = np.zeros(int(n.sum()), np.uint8); pw = np.zeros((int(n.sum()), 9), np.float32)
+        if self._L.aprilx_run_dtmf(self._handle, C.addressof(opts), k, n.ctypes.data, fr.ctypes.data, codes.ctypes.data, pw.ctypes.data if powers else None) != 0:
+            raise ValueError("aprilx_run_dtmf refused its arguments")
+        cuts = np.cumsum(n)[:-1]
+        return np.split(codes, cuts), np.split(pw, cuts)
+
+    def run_dtmf_decide(self, options, powers9):
+        """the kernel's decision alone on given rows [n][9] of P[0..8), E (aprilx_run_dtmf_decide; tests): codes [n]"""
+        q = np.ascontiguousarray(powers9, np.float32).reshape(-1, 9)
+        codes = np.zeros(len(q), np.uint8)
+        if self._L.aprilx_run_dtmf_decide(self._handle, C.byref(_dtmf_options(options)), len(q), q.ctypes.data, codes.ctypes.data) != 0:
+            raise ValueError("aprilx_run_dtmf_decide refused its arguments")
+        return codes
+
+    def dtmf_stats(self, device_index: int = 0):
+        """(launches, frames, ms): DTMF launches of one GPU's engine, the frames they covered, and (while profiling) the kernel's time"""
+        l, f, ms = C.c_uint64(0), C.c_uint64(0), C.c_double(0)
+        if self._L.aprilx_model_dtmf_stats(self._handle, device_index, C.byref(l), C.byref(f), C.byref(ms)) != 0:
+            raise ValueError("no such device")
+        return int(l.value), int(f.value), float(ms.value)
+
     def vad_stats(self, device_index: int = 0):
         """(launches, frames, ms): VAD launches of one GPU's engine, the frames they covered, and (while profiling) the kernel's time"""
         l, f, ms = C.c_uint64(0), C.c_uint64(0), C.c_double(0)
@@ -459,11 +506,21 @@ def _dispatch_vad(userdata, kind, time_ms):
 _VAD_HANDLER = _ffi.VAD_HANDLER(_dispatch_vad)
 
 
+def _dispatch_dtmf(userdata, kind, digit, time_ms):
+    sess = C.cast(userdata, C.py_object).value
+    if sess.dtmf_callback is not None:
+        sess.dtmf_callback(DtmfEvent(kind, digit, time_ms))
+
+
+_DTMF_HANDLER = _ffi.DTMF_HANDLER(_dispatch_dtmf)
+
+
 class Session:
     def __init__(self, model: Model, callback: Callable[[Result, List[Token]], None], asynchronous: bool = False,
                  no_rt: bool = False, speaker_name: str = "", raw_events: bool = False, counters=None, input_sample_rate=None,
                  alternatives=None, bias=None, endpoint_silence_ms=None, blank_penalty=None, max_utterance_ms=None,
-                 input_format=None, channels: int = 1, channel: int = 0, vad=None, vad_callback=None):
+                 input_format=None, channels: int = 1, channel: int = 0, vad=None, vad_callback=None,
+                 dtmf=None, dtmf_callback=None):
         """`counters`: a uint64 ndarray of 6 entries; when given, results are only counted by a C handler inside the
         library (calls, partial, final, cant_keep_up, silence, tokens) and `callback` is never invoked.
         `input_sample_rate`: the rate of the PCM this session will receive (converted to the model's rate on the GPU); None: the
@@ -475,7 +532,10 @@ class Session:
         `input_format`, `channels`, `channel`: the format of the audio this session will receive (set_input_format): "mulaw", "alaw",
         "f32" or "s16", 1..8 interleaved channels, the channel to take or -1 for their downmix; None: mono PCM16.
         `vad`, `vad_callback`: True or a dict of options (set_vad) switches the voice-activity detector on; `vad_callback` receives one
-        VadEvent per speech start / end, on the thread that delivers the session's results."""
+        VadEvent per speech start / end, on the thread that delivers the session's results.
+        `dtmf`, `dtmf_callback`: True or a dict of options (set_dtmf) switches the DTMF detector on; `dtmf_callback` receives one DtmfEvent
+        per key down / key up, on the same thread."""
+        self.dtmf_callback = dtmf_callback
         self._L = model._L
         self.vad_callback = vad_callback
         self.info_log = None      # tests: a list that receives (type, [the token's AprilxTokenInfo as bytes, or None]) per result
@@ -511,6 +571,33 @@ class Session:
             self.set_search_options(endpoint_silence_ms, blank_penalty, max_utterance_ms)
         if vad:
             self.set_vad(vad)
+        if dtmf:
+            self.set_dtmf(dtmf)
+
+    def set_dtmf(self, options=True, callback=None) -> None:
+        """DTMF digits for this session (aprilx_session_set_dtmf): True for the defaults, or a dict with any of
+        min_level_dbfs, twist_hi_db, twist_lo_db, rel_peak_db, min_share, min_tone_ms, min_pause_ms; None / False switches it off.
+        `callback` replaces the session's dtmf_callback.  Allowed right after creation and after a completed flush; the machine and
+        its counters start afresh."""
+        if callback is not None:
+            self.dtmf_callback = callback
+        if not options:
+            rc = self._L.aprilx_session_set_dtmf(self._handle, None, C.cast(None, _ffi.DTMF_HANDLER), None)
+        else:
+            rc = self._L.aprilx_session_set_dtmf(self._handle, C.byref(_dtmf_options(options)), _DTMF_HANDLER, id(self))
+        if rc != 0:
+            raise ValueError("DTMF options %r refused (a value out of range, a model the detector refuses, or audio fed since the last flush)" % (options,))
+
+    def dtmf_info(self):
+        """None when the detector is off, else a dict: the options, Wd, on_frames, off_frames, frames_seen, tone_frames, digits, held (the
+        digit held after the last frame, or "") (aprilx_session_dtmf).  Waits for the session to be idle."""
+        o, i = _ffi.AprilxDtmfOptions(), _ffi.AprilxDtmfInfo()
+        if self._L.aprilx_session_dtmf(self._handle, C.byref(o), C.byref(i)) != 1:
+            return None
+        d = {n: getattr(o, n) for n in _DTMF_FIELDS}
+        d.update({n: int(getattr(i, n)) for n in ("Wd", "on_frames", "off_frames", "frames_seen", "tone_frames", "digits")})
+        d["held"] = chr(i.held) if i.held else ""
+        return d
 
     def set_vad(self, options=True, callback=None) -> None:
         """Voice activity for this session (aprilx_session_set_vad): True for the defaults, or a dict with any of
@@ -783,6 +870,73 @@ def _vad_options(options):
         d.update(options)
     return _ffi.AprilxVadOptions(C.sizeof(_ffi.AprilxVadOptions), float(d["band_lo_hz"]), float(d["band_hi_hz"]), float(d["onset_db"]),
                                  float(d["offset_db"]), int(d["onset_ms"]), int(d["hangover_ms"]), float(d["min_energy"]), 0)
+
+
+_DTMF_FIELDS = ("min_level_dbfs", "twist_hi_db", "twist_lo_db", "rel_peak_db", "min_share", "min_tone_ms", "min_pause_ms")
+_DTMF_DEFAULTS = dict(min_level_dbfs=-40.0, twist_hi_db=4.0, twist_lo_db=8.0, rel_peak_db=8.0, min_share=0.6, min_tone_ms=20, min_pause_ms=20)
+
+
+def _dtmf_options(options):
+    if isinstance(options, _ffi.AprilxDtmfOptions):
+        return options
+    d = dict(_DTMF_DEFAULTS)
+    if isinstance(options, dict):
+        unknown = set(options) - set(_DTMF_FIELDS)
+        if unknown:
+            raise ValueError("unknown DTMF options %r" % sorted(unknown))
+        d.update(options)
+    return _ffi.AprilxDtmfOptions(C.sizeof(_ffi.AprilxDtmfOptions), float(d["min_level_dbfs"]), float(d["twist_hi_db"]), float(d["twist_lo_db"]),
+                                  float(d["rel_peak_db"]), float(d["min_share"]), int(d["min_tone_ms"]), int(d["min_pause_ms"]), 0)
+
+
+def dtmf_plan(sample_rate: int, fft_size: int, frame_shift_ms: int, options=True):
+    """The detector's plan (AprilxDtmfPlan) of a model with this rate, fft size and frame shift, on the host (aprilx_dtmf_plan);
+    ValueError when the options or the model are refused."""
+    plan = _ffi.AprilxDtmfPlan()
+    if _ffi.lib().aprilx_dtmf_plan(int(sample_rate), int(fft_size), int(frame_shift_ms), C.byref(_dtmf_options(options)), C.byref(plan)) != 0:
+        raise ValueError("DTMF options %r refused" % (options,))
+    return plan
+
+
+def dtmf_tables(sample_rate: int, Wd: int):
+    """The detector's tables [16][Wd] float32 (aprilx_dtmf_tables): rows 0..7 cos, 8..15 sin of the eight frequencies"""
+    t = np.zeros((16, int(Wd)), np.float32)
+    if _ffi.lib().aprilx_dtmf_tables(int(sample_rate), int(Wd), t.ctypes.data, t.size) != t.size:
+        raise ValueError("aprilx_dtmf_tables refused its arguments")
+    return t
+
+
+def dtmf_host(plan, tables, frames):
+    """The contract on the host (aprilx_dtmf_host): frames [n][>= Wd] int16 -> (codes [n] uint8, powers [n][9] float32)"""
+    f = np.ascontiguousarray(frames, np.int16)
+    f = f.reshape(len(f), -1)
+    t = np.ascontiguousarray(tables, np.float32)
+    assert t.shape == (16, plan.Wd)
+    codes = np.zeros(len(f), np.uint8); pw = np.zeros((len(f), 9), np.float32)
+    if _ffi.lib().aprilx_dtmf_host(C.byref(plan), t.ctypes.data, len(f), f.ctypes.data, f.shape[1] if len(f) else plan.Wd, codes.ctypes.data, pw.ctypes.data) != 0:
+        raise ValueError("aprilx_dtmf_host refused its arguments")
+    return codes, pw
+
+
+def dtmf_decide_host(plan, powers9) -> int:
+    """steps 3-4 on one row of P[0..8), E (aprilx_dtmf_decide_host): the code"""
+    q = np.ascontiguousarray(powers9, np.float32)
+    assert q.shape == (9,)
+    return int(_ffi.lib().aprilx_dtmf_decide_host(C.byref(plan), q.ctypes.data))
+
+
+def dtmf_events_host(plan, frame_shift_ms: int, t0: int, codes, machine=None, flush: bool = False):
+    """The events that follow from the codes of frames [t0, t0 + n) (aprilx_dtmf_events_host) from `machine` (AprilxDtmfMachine, updated
+    in place; None: idle); `flush`: a flush completes behind them.  Returns ([DtmfEvent], machine)."""
+    b = np.ascontiguousarray(codes, np.uint8)
+    cap = 2 * len(b) + 2              # (on_frames = off_frames = 1: a frame can give UP and DOWN; a flush one more UP)
+    kinds = np.zeros(cap, np.int32); digits = np.zeros(cap, np.uint8); times = np.zeros(cap, np.uint64)
+    m = machine if machine is not None else _ffi.AprilxDtmfMachine(0, 0, 0)
+    n = _ffi.lib().aprilx_dtmf_events_host(C.byref(plan), int(frame_shift_ms), int(t0), b.ctypes.data, len(b), 1 if flush else 0, C.byref(m),
+                                           kinds.ctypes.data, digits.ctypes.data, times.ctypes.data, cap)
+    if n < 0:
+        raise ValueError("aprilx_dtmf_events_host refused its arguments")
+    return [DtmfEvent(kinds[i], chr(digits[i]), times[i]) for i in range(n)], m
 
 
 def vad_reset_state():

@@ -84,6 +84,28 @@ class AprilxVadState(C.Structure):
 VAD_HANDLER = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_uint64)
 
 
+class AprilxDtmfOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("min_level_dbfs", C.c_float), ("twist_hi_db", C.c_float), ("twist_lo_db", C.c_float), ("rel_peak_db", C.c_float),
+                ("min_share", C.c_float), ("min_tone_ms", C.c_uint32), ("min_pause_ms", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class AprilxDtmfInfo(C.Structure):
+    _fields_ = [("Wd", C.c_int32), ("on_frames", C.c_int32), ("off_frames", C.c_int32), ("held", C.c_uint32),
+                ("frames_seen", C.c_uint64), ("tone_frames", C.c_uint64), ("digits", C.c_uint64)]
+
+
+class AprilxDtmfPlan(C.Structure):
+    _fields_ = [("Wd", C.c_int32), ("half_w", C.c_float), ("min_power", C.c_float), ("twist_hi", C.c_float), ("twist_lo", C.c_float),
+                ("rel_peak", C.c_float), ("min_share", C.c_float), ("on_frames", C.c_int32), ("off_frames", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AprilxDtmfMachine(C.Structure):
+    _fields_ = [("held", C.c_int32), ("cand", C.c_int32), ("run", C.c_int32)]
+
+
+DTMF_HANDLER = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_char, C.c_uint64)
+
+
 class AprilxInputFormat(C.Structure):
     _fields_ = [("size", C.c_uint32), ("encoding", C.c_uint32), ("channels", C.c_uint32), ("channel", C.c_int32)]
 
@@ -111,6 +133,8 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_decode_host", "aprilx_decode", "aprilx_model_decode_stats",
     "aprilx_session_set_vad", "aprilx_session_vad", "aprilx_vad_plan_tables", "aprilx_vad_host", "aprilx_vad_events_host", "aprilx_run_vad",
     "aprilx_model_vad_stats",
+    "aprilx_session_set_dtmf", "aprilx_session_dtmf", "aprilx_dtmf_plan", "aprilx_dtmf_tables", "aprilx_dtmf_host", "aprilx_dtmf_decide_host",
+    "aprilx_dtmf_events_host", "aprilx_run_dtmf", "aprilx_run_dtmf_decide", "aprilx_model_dtmf_stats",
 ]
 
 _lib = None
@@ -216,6 +240,17 @@ def lib():
     L.aprilx_vad_events_host.argtypes = [C.POINTER(AprilxVadPlan), C.c_int, C.c_uint64, vp, sz, C.POINTER(C.c_int32), vp, vp, C.c_int]; L.aprilx_vad_events_host.restype = C.c_int
     L.aprilx_run_vad.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]; L.aprilx_run_vad.restype = C.c_int
     L.aprilx_model_vad_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]; L.aprilx_model_vad_stats.restype = C.c_int
+    L.aprilx_session_set_dtmf.argtypes = [vp, C.POINTER(AprilxDtmfOptions), DTMF_HANDLER, vp]; L.aprilx_session_set_dtmf.restype = C.c_int
+    L.aprilx_session_dtmf.argtypes = [vp, C.POINTER(AprilxDtmfOptions), C.POINTER(AprilxDtmfInfo)]; L.aprilx_session_dtmf.restype = C.c_int
+    L.aprilx_dtmf_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(AprilxDtmfOptions), C.POINTER(AprilxDtmfPlan)]; L.aprilx_dtmf_plan.restype = C.c_int
+    L.aprilx_dtmf_tables.argtypes = [C.c_int, C.c_int, vp, sz]; L.aprilx_dtmf_tables.restype = C.c_int
+    L.aprilx_dtmf_host.argtypes = [C.POINTER(AprilxDtmfPlan), vp, C.c_int, vp, sz, vp, vp]; L.aprilx_dtmf_host.restype = C.c_int
+    L.aprilx_dtmf_decide_host.argtypes = [C.POINTER(AprilxDtmfPlan), vp]; L.aprilx_dtmf_decide_host.restype = C.c_int
+    L.aprilx_dtmf_events_host.argtypes = [C.POINTER(AprilxDtmfPlan), C.c_int, C.c_uint64, vp, sz, C.c_int, C.POINTER(AprilxDtmfMachine), vp, vp, vp, C.c_int]
+    L.aprilx_dtmf_events_host.restype = C.c_int
+    L.aprilx_run_dtmf.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]; L.aprilx_run_dtmf.restype = C.c_int
+    L.aprilx_run_dtmf_decide.argtypes = [vp, C.POINTER(AprilxDtmfOptions), C.c_int, vp, vp]; L.aprilx_run_dtmf_decide.restype = C.c_int
+    L.aprilx_model_dtmf_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]; L.aprilx_model_dtmf_stats.restype = C.c_int
     _lib = L
     return L
 

@@ -407,8 +407,9 @@ Engine::~Engine()
     if (conf_h_) (void)hipHostFree(conf_h_);
     for (auto &b : bias_sets_) if (b.dev) (void)hipFree(b.dev);
     if (bias_state_d_) (void)hipFree(bias_state_d_);
-    for (void *p : {(void *)vad_state_d_, (void *)vad_out_d_}) if (p) (void)hipFree(p);
-    for (VadBlock &k : vad_blocks_) (void)hipHostFree(k.h);
+    for (void *p : {(void *)vad_state_d_, (void *)pass_out_d_}) if (p) (void)hipFree(p);
+    for (PassBlock &k : pass_blocks_) (void)hipHostFree(k.h);
+    for (int b = 0; b < 2; ++b) if (dt_desc_h_[b]) { (void)hipHostFree(dt_desc_h_[b]); (void)hipFree(dt_desc_d_[b]); }
     if (ws_g_) (void)hipFree(ws_g_);
     if (conv_wt_) (void)hipFree(conv_wt_);
     if (dec_table_) (void)hipFree(dec_table_);
@@ -697,10 +698,11 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
                              const FrontPass &pass)
 {
     if (n_frames <= 0) return nullptr;
-    const int n_rs = std::max(pass.n_rs, 0), n_dc = std::max(pass.n_dc, 0), n_vd = std::max(pass.n_vd, 0);
+    const int n_rs = std::max(pass.n_rs, 0), n_dc = std::max(pass.n_dc, 0), n_vd = std::max(pass.n_vd, 0), n_dt = std::max(pass.n_dt, 0);
     ResampleDesc *rs = pass.rs;
     const DecodeDesc *dc = pass.dc;
     const size_t n_in_parts = n_rs ? pass.n_in_parts : 0, n_raw_parts = n_dc ? pass.n_raw_parts : 0, vd_frames = n_vd ? pass.vad_bytes : 0;
+    const size_t dt_frames = n_dt ? pass.dtmf_bytes : 0, out_bytes = vd_frames + dt_frames;      // the pass's bytes: VAD, then DTMF
     StagingCounts cnt;
     cnt.n_pcm = n_pcm; cnt.n_in = n_rs ? pass.n_in : 0; cnt.n_raw = n_dc ? pass.n_raw : 0;
     cnt.n_frames = (size_t)n_frames; cnt.n_rs = (size_t)n_rs; cnt.n_dc = (size_t)n_dc; cnt.n_vd = (size_t)n_vd;
@@ -719,25 +721,35 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
             if (!fb_done_[b]) HIP_CHECK(hipEventCreateWithFlags(&fb_done_[b], hipEventDisableTiming));
         }
     }
-    VadBlock *vblock = nullptr;
-    if (n_vd) {
-        // the first VAD pass of the engine allocates the per-slot records; the device's byte buffer grows behind a sync (earlier
+    PassBlock *vblock = nullptr;
+    const float *dt_tables = n_dt ? dtmf_tables() : nullptr;
+    if (n_dt && (size_t)n_dt > dt_cap_) {
+        // the DTMF descriptors travel in a pinned array of their own per flip (not in the staging buffer: its layout stays as it is)
+        sync();
+        HipLegacyLock guard;
+        for (int b = 0; b < 2; ++b) if (dt_desc_h_[b]) { (void)hipHostFree(dt_desc_h_[b]); (void)hipFree(dt_desc_d_[b]); }
+        dt_cap_ = std::max<size_t>((size_t)n_dt * 2, 256);
+        for (int b = 0; b < 2; ++b) { dt_desc_h_[b] = hmalloc<DtmfDesc>(dt_cap_); dt_desc_d_[b] = dmalloc<DtmfDesc>(dt_cap_); }
+    }
+    if (n_vd || n_dt) {
+        // a pass with VAD or DTMF descriptors: the first VAD pass of the engine allocates the per-slot records; the device's byte buffer
+        // (the pass's VAD bytes, then its DTMF bytes) grows behind a sync (earlier
         // passes' copies read it); a pass takes a pinned block nobody holds, or a new one (warm-up only)
-        if (!vad_state_d_) vad_state_d_ = dmalloc<VadState>((size_t)cfg_.max_slots);
-        if (vd_frames > vad_out_cap_) {
+        if (n_vd && !vad_state_d_) vad_state_d_ = dmalloc<VadState>((size_t)cfg_.max_slots);
+        if (out_bytes > pass_out_cap_) {
             sync();
             HipLegacyLock guard;
-            if (vad_out_d_) (void)hipFree(vad_out_d_);
-            vad_out_cap_ = std::max<size_t>(vd_frames * 2, 4096);
-            vad_out_d_ = dmalloc<uint8_t>(vad_out_cap_);
+            if (pass_out_d_) (void)hipFree(pass_out_d_);
+            pass_out_cap_ = std::max<size_t>(out_bytes * 2, 4096);
+            pass_out_d_ = dmalloc<uint8_t>(pass_out_cap_);
         }
-        for (VadBlock &k : vad_blocks_) if (!k.busy && k.cap >= vd_frames && (!vblock || k.cap < vblock->cap)) vblock = &k;
+        for (PassBlock &k : pass_blocks_) if (!k.busy && k.cap >= out_bytes && (!vblock || k.cap < vblock->cap)) vblock = &k;
         if (!vblock) {
-            VadBlock k;
-            k.cap = 4096; while (k.cap < vd_frames) k.cap *= 2;
+            PassBlock k;
+            k.cap = 4096; while (k.cap < out_bytes) k.cap *= 2;
             k.h = hmalloc<uint8_t>(k.cap);
-            vad_blocks_.push_back(k);
-            vblock = &vad_blocks_.back();
+            pass_blocks_.push_back(k);
+            vblock = &pass_blocks_.back();
         }
         vblock->busy = true;
     }
@@ -748,6 +760,19 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
     char *hs = reinterpret_cast<char *>(hs_pcm_[b]);
     memcpy(hs + doff, desc, (size_t)n_frames * sizeof(FbankFrameDesc));
     if (n_vd) memcpy(hs + voff, pass.vd, (size_t)n_vd * sizeof(VadDesc));
+    DtmfArgs ta;
+    if (n_dt) {       // (fb_done_[b] has been waited for: the launch that read this flip's descriptor array is through)
+        for (int i = 0; i < n_dt; ++i) {
+            const DtmfDesc &t = pass.dt[i];
+            if (t.n <= 0 || t.first < 0 || t.first + t.n > n_frames || t.out_off < 0 || (size_t)t.out_off + (size_t)t.n > dt_frames || t.plan.Wd != dt_wd_) {
+                LOGE("fbank: DTMF descriptor %d outside the pass", i); abort();
+            }
+            for (int k = 0; k < t.n; ++k) if (desc[t.first + k].pcm_off < 0) { LOGE("fbank: a padding row inside DTMF run %d", i); abort(); }
+            dt_desc_h_[b][i] = t;
+            ta.max_n = std::max(ta.max_n, t.n);
+        }
+        ta.n_desc = n_dt; ta.tables = dt_tables; ta.wd = dt_wd_;
+    }
     ResampleArgs ra;
     if (n_rs) {
         ResampleDesc *hr = reinterpret_cast<ResampleDesc *>(hs + roff);
@@ -803,31 +828,58 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
     }
     VadArgs va;
     if (n_vd) {
-        va.ring = ring_; va.ring_frames = ring_frames_; va.nbins = ft_.nbins; va.state = vad_state_d_; va.out = vad_out_d_;
+        va.ring = ring_; va.ring_frames = ring_frames_; va.nbins = ft_.nbins; va.state = vad_state_d_; va.out = pass_out_d_;
         va.desc = reinterpret_cast<const VadDesc *>(reinterpret_cast<const char *>(ds_pcm_[b]) + voff); va.n_desc = n_vd;
+    }
+    if (n_dt) {
+        HIP_CHECK(hipMemcpyAsync(dt_desc_d_[b], dt_desc_h_[b], (size_t)n_dt * sizeof(DtmfDesc), hipMemcpyHostToDevice, f_stream_));
+        ta.pcm = ds_pcm_[b]; ta.frames = a.desc; ta.desc = dt_desc_d_[b]; ta.out = pass_out_d_ + vd_frames;
     }
     if (profiling_) {        // (the per-class hipEvents live on M: a profiled fbank runs there, behind its upload)
         m_touched();
         join(stream_, f_stream_);
         if (n_dc) { timed_begin(T_DECODE); launch_decode(da, stream_); timed_end(T_DECODE); }      // (decode feeds both)
         if (n_rs) { timed_begin(T_RESAMPLE); launch_resample(ra, stream_); timed_end(T_RESAMPLE); }
+        if (n_dt) { timed_begin(T_DTMF); launch_dtmf(ta, stream_); timed_end(T_DTMF); }
         timed_begin(T_FBANK); launch_fbank(a, stream_); timed_end(T_FBANK);
         if (n_vd) { timed_begin(T_VAD); launch_vad(va, stream_); timed_end(T_VAD); }
         join(f_stream_, stream_);
     } else {
         if (n_dc) launch_decode(da, f_stream_);
         if (n_rs) launch_resample(ra, f_stream_);
+        if (n_dt) launch_dtmf(ta, f_stream_);          // (reads the samples fbank_kernel reads; the staging pair is recycled after fb_done_)
         launch_fbank(a, f_stream_);
         if (n_vd) launch_vad(va, f_stream_);
     }
-    if (n_vd) {       // the pass's bytes -> its pinned block, in front of fb_done_; read after the flight's wait (close_flight)
-        HIP_CHECK(hipMemcpyAsync(vblock->h, vad_out_d_, vd_frames, hipMemcpyDeviceToHost, f_stream_));
-        vad_flight_ = true;
-        vad_launches_.fetch_add(1, std::memory_order_relaxed); vad_frames_.fetch_add(vd_frames, std::memory_order_relaxed);
+    if (n_vd || n_dt) {       // the pass's bytes -> its pinned block, in front of fb_done_; read after the flight's wait (close_flight)
+        HIP_CHECK(hipMemcpyAsync(vblock->h, pass_out_d_, out_bytes, hipMemcpyDeviceToHost, f_stream_));
+        pass_bytes_flight_ = true;
+        if (n_vd) { vad_launches_.fetch_add(1, std::memory_order_relaxed); vad_frames_.fetch_add(vd_frames, std::memory_order_relaxed); }
+        if (n_dt) { dt_launches_.fetch_add(1, std::memory_order_relaxed); dt_frames_.fetch_add(dt_frames, std::memory_order_relaxed); }
     }
     HIP_CHECK(hipEventRecord(fb_done_[b], f_stream_));       // no host wait here: the encoder launches queue right behind
     f_unseen_by_m_ = true;
     return vblock ? vblock->h : nullptr;
+}
+
+// the DTMF tables of this engine's model (dtmf.h), uploaded at the first DTMF pass or debug call
+const float *Engine::dtmf_tables()
+{
+    std::lock_guard<std::mutex> g(rs_mu_);
+    if (dt_tables_) return dt_tables_;
+    const int wd = dtmf_window(P_.sample_rate, ft_.padded);
+    if (!wd) { LOGE("DTMF on a model it refuses"); abort(); }
+    std::vector<float> t((size_t)kDtmfRows * (size_t)wd);
+    dtmf_make_tables(P_.sample_rate, wd, t.data());
+    HIP_CHECK(hipSetDevice(cfg_.device));
+    float *d = dmalloc<float>(t.size());
+    {
+        HipLegacyLock legacy;
+        HIP_CHECK(hipMemcpy(d, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+        table_allocs_.push_back(d);
+    }
+    dt_wd_ = wd; dt_tables_ = d;
+    return d;
 }
 
 const float *Engine::resample_table(const ResampleSpec *spec)
@@ -1841,8 +1893,8 @@ int Engine::close_flight()
         tail = stream_;
         if (f_unseen_by_m_) { join(stream_, f_stream_); f_unseen_by_m_ = false; }
         if (s_unseen_by_m_) { join(stream_, s_stream_); s_unseen_by_m_ = false; }
-    } else if (vad_flight_) join(s_stream_, f_stream_);      // a VAD pass's bytes are read after this flight's wait: its copy comes first
-    vad_flight_ = false;
+    } else if (pass_bytes_flight_) join(s_stream_, f_stream_);      // a pass's VAD / DTMF bytes are read after this flight's wait: their copy comes first
+    pass_bytes_flight_ = false;
     if (rec_pos_ > rec_base_) HIP_CHECK(hipMemcpyAsync(rec_h_ + rec_base_, rec_d_ + rec_base_, (rec_pos_ - rec_base_) * sizeof(StepRecord), hipMemcpyDeviceToHost, tail));
     for (const auto &sp : conf_spans_) {          // side records: only the steps that hold a row of a session with confidences on
         HIP_CHECK(hipMemcpyAsync(conf_h_ + sp.first, conf_d_ + sp.first, sp.second * sizeof(ConfRecord), hipMemcpyDeviceToHost, tail));
@@ -2121,6 +2173,44 @@ void Engine::debug_vad(int n_runs, const VadPlan *plans, const int32_t *n, const
     HIP_CHECK(hipMemcpy(states_io, st_d, (size_t)n_runs * sizeof(VadState), hipMemcpyDeviceToHost));
     if (total) HIP_CHECK(hipMemcpy(bytes_out, out_d, total, hipMemcpyDeviceToHost));
     if (total && energy_out) HIP_CHECK(hipMemcpy(energy_out, en_d, total * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+void Engine::debug_dtmf(int n_runs, const DtmfPlan *plans, const int32_t *n, const int16_t *frames, uint8_t *codes_out, float *powers_out)
+{
+    // frame i of the call sits at sample i * padded of a scratch staging buffer, as in debug_fbank
+    const size_t padded = (size_t)ft_.padded;
+    const float *tables = dtmf_tables();
+    std::vector<DtmfDesc> desc((size_t)n_runs);
+    size_t total = 0;
+    int max_n = 0;
+    for (int r = 0; r < n_runs; ++r) {
+        DtmfDesc &d = desc[(size_t)r];
+        d.first = (int32_t)total; d.n = n[r]; d.out_off = (int32_t)total; d.plan = plans[r];
+        total += (size_t)n[r]; max_n = std::max(max_n, n[r]);
+    }
+    std::vector<FbankFrameDesc> fd(total);
+    for (size_t i = 0; i < total; ++i) { fd[i].slot = 0; fd[i].ring_row = 0; fd[i].pcm_off = (int32_t)(i * padded); }
+    HipLegacyLock legacy;
+    HIP_CHECK(hipSetDevice(cfg_.device));
+    DeviceScratch ds;
+    DtmfArgs a;
+    a.pcm = ds.upload(frames, total * padded); a.frames = ds.upload(fd.data(), fd.size()); a.desc = ds.upload(desc.data(), desc.size()); a.n_desc = n_runs;
+    a.max_n = max_n; a.tables = tables; a.wd = dt_wd_;
+    a.out = ds.alloc<uint8_t>(total); a.powers = ds.alloc<float>(total * 9);
+    run_on_private_stream([&](hipStream_t st) { launch_dtmf(a, st); });
+    HIP_CHECK(hipMemcpy(codes_out, a.out, total, hipMemcpyDeviceToHost));
+    if (powers_out) HIP_CHECK(hipMemcpy(powers_out, a.powers, total * 9 * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+void Engine::debug_dtmf_decide(const DtmfPlan &plan, int n, const float *powers9, uint8_t *codes_out)
+{
+    HipLegacyLock legacy;
+    HIP_CHECK(hipSetDevice(cfg_.device));
+    DeviceScratch ds;
+    const float *p = ds.upload(powers9, (size_t)n * 9);
+    uint8_t *out = ds.alloc<uint8_t>((size_t)n);
+    run_on_private_stream([&](hipStream_t st) { launch_dtmf_decide(plan, n, p, out, st); });
+    HIP_CHECK(hipMemcpy(codes_out, out, (size_t)n, hipMemcpyDeviceToHost));
 }
 
 void Engine::read_greedy_state(int slot, GreedyState *out)

@@ -128,6 +128,10 @@ struct FrontPass {
     // Voice activity: the n_vd descriptors (out_off counted from 0, `vad_bytes` bytes in all); vad_kernel runs
     // right behind the fbank launch.
     int n_vd = 0; const VadDesc *vd = nullptr; size_t vad_bytes = 0;
+    // DTMF: the n_dt descriptors (out_off counted from 0, `dtmf_bytes` bytes in all; `first` indexes the frame
+    // descriptors of this call).  They travel in a small upload of their own; dtmf_kernel runs behind the resample launch.  The pass's
+    // bytes follow its VAD bytes in the block fbank() returns: at [vad_bytes, vad_bytes + dtmf_bytes).
+    int n_dt = 0; const DtmfDesc *dt = nullptr; size_t dtmf_bytes = 0;
 };
 
 // One call of the decision kernel on GIVEN rows (the parity tests' entry point, Engine::debug_decide): slots 0..n-1, row i = slot i.
@@ -179,8 +183,8 @@ public:
     // chunk steps (encoder + the three joiner/decision/decoder rounds, all on the device) and decoder refreshes are queued
     // back to back, and the host reads the 16-byte-per-round records once, at end_flight().
     // pcm arrives as `n_parts` windows that are gathered straight into pinned staging (total n_pcm samples)
-    // `pass`: the resample / decode / VAD work of this call.  Returns the pinned block that receives the pass's VAD bytes (null: no VAD
-    // descriptors): its bytes are complete once the flight that was open during the call has been waited for (close_flight() puts the
+    // `pass`: the resample / decode / VAD / DTMF work of this call.  Returns the pinned block that receives the pass's VAD bytes and, behind
+    // them, its DTMF bytes (null: neither VAD nor DTMF descriptors): its bytes are complete once the flight that was open during the call has been waited for (close_flight() puts the
     // copy in front of the flight's event), and the block is lent until vad_release().  Stepping thread only.
     const uint8_t *fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<const int16_t *, size_t> *parts, size_t n_parts, size_t n_pcm,
                          HostPool *pool = nullptr, const FrontPass &pass = FrontPass());
@@ -191,12 +195,25 @@ public:
     }
     // ---- voice activity.  Inline over plain members: the scheduler harness links session.cc against an engine of
     // its own.  Nothing is allocated until a pass carries a VAD descriptor.
-    void vad_release(const uint8_t *p) { for (VadBlock &b : vad_blocks_) if (b.h == p) b.busy = false; }
+    // vad_release(): gives back the block a fbank() call lent -- the block of the pass's VAD bytes AND its DTMF bytes; the scheduler calls it
+    // once per block, after both have been read
+    void vad_release(const uint8_t *p) { for (PassBlock &b : pass_blocks_) if (b.h == p) b.busy = false; }
     // VAD launches and the frames they covered so far (any thread)
     void vad_counts(uint64_t *launches, uint64_t *frames) const
     {
         *launches = vad_launches_.load(std::memory_order_relaxed); *frames = vad_frames_.load(std::memory_order_relaxed);
     }
+    // ---- DTMF.  Launches and the frames they covered so far (any thread); nothing is allocated until a pass
+    // carries a DTMF descriptor.
+    void dtmf_counts(uint64_t *launches, uint64_t *frames) const
+    {
+        *launches = dt_launches_.load(std::memory_order_relaxed); *frames = dt_frames_.load(std::memory_order_relaxed);
+    }
+    // aprilx_run_dtmf: n_runs runs in ONE launch; run r's n[r] frames (consecutive in `frames`, `padded` samples each) with plans[r].
+    // powers_out (may be null): [sum n][9]
+    void debug_dtmf(int n_runs, const DtmfPlan *plans, const int32_t *n, const int16_t *frames, uint8_t *codes_out, float *powers_out);
+    // aprilx_run_dtmf_decide: the decision alone on n given rows of P[0..8), E
+    void debug_dtmf_decide(const DtmfPlan &plan, int n, const float *powers9, uint8_t *codes_out);
     // aprilx_run_vad: n_runs runs in ONE launch over a scratch ring of ring_rows rows per run; run r's n[r] rows (consecutive in `rows`)
     // sit at rows (first_row[r] + i) % ring_rows of its ring
     void debug_vad(int n_runs, const VadPlan *plans, const int32_t *n, const int32_t *first_row, int ring_rows, const float *rows, VadState *states_io,
@@ -308,7 +325,7 @@ public:
     // split feeds launched as hostable (any thread)
     void ramp_counts(uint64_t *hosted, uint64_t *eligible);
     void reset_timing();
-    enum { T_GATES = 0, T_GEMM_OTHER = 1, T_ROW = 2, T_CONV = 3, T_FBANK = 4, T_DEC = 5, T_RESAMPLE = 6, T_DECODE = 7, T_VAD = 8, T_COUNT = 9 };
+    enum { T_GATES = 0, T_GEMM_OTHER = 1, T_ROW = 2, T_CONV = 3, T_FBANK = 4, T_DEC = 5, T_RESAMPLE = 6, T_DECODE = 7, T_VAD = 8, T_DTMF = 9, T_COUNT = 10 };
     long kernels_per_step() const { return kernels_per_step_.load(std::memory_order_relaxed); }    // launches of the last eagerly issued chunk chain
 
 private:
@@ -462,11 +479,16 @@ private:
     std::atomic<uint64_t> dc_launches_{0}, dc_frames_{0};
     // voice activity: nothing below is allocated until a pass carries a VAD descriptor
     VadState *vad_state_d_ = nullptr;          // [slots] (a session's first descriptor carries VAD_RESET: never initialised by the host)
-    uint8_t *vad_out_d_ = nullptr; size_t vad_out_cap_ = 0;      // one pass's bytes on the device (stream order keeps the passes apart)
-    struct VadBlock { uint8_t *h = nullptr; size_t cap = 0; bool busy = false; };
-    std::vector<VadBlock> vad_blocks_;         // pinned blocks, one per pass whose bytes the scheduler has not read yet; reused afterwards
-    bool vad_flight_ = false;                  // the open flight holds a VAD pass: its event must follow the copy on the front-end stream
+    uint8_t *pass_out_d_ = nullptr; size_t pass_out_cap_ = 0;      // one pass's bytes on the device, VAD then DTMF (stream order keeps the passes apart)
+    struct PassBlock { uint8_t *h = nullptr; size_t cap = 0; bool busy = false; };
+    std::vector<PassBlock> pass_blocks_;         // pinned blocks, one per pass whose bytes (VAD, then DTMF) the scheduler has not read yet: lent by fbank(), busy until vad_release()
+    bool pass_bytes_flight_ = false;                  // the open flight holds a pass with VAD or DTMF bytes: its event must follow their copy on the front-end stream
     std::atomic<uint64_t> vad_launches_{0}, vad_frames_{0};
+    // DTMF: nothing below is allocated until a pass carries a DTMF descriptor (the bytes share the VAD's device buffer and pinned blocks)
+    const float *dt_tables_ = nullptr; int dt_wd_ = 0;      // [16][Wd] on the device, uploaded once (freed with table_allocs_)
+    DtmfDesc *dt_desc_h_[2] = {nullptr, nullptr}, *dt_desc_d_[2] = {nullptr, nullptr}; size_t dt_cap_ = 0;      // one descriptor array per staging flip
+    std::atomic<uint64_t> dt_launches_{0}, dt_frames_{0};
+    const float *dtmf_tables();
     std::mutex rs_mu_;
     std::map<const ResampleSpec *, const float *> rs_tables_;     // phase tables on the device, uploaded at first use (freed with table_allocs_)
     const float *resample_table(const ResampleSpec *spec);

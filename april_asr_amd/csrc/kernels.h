@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "vad.h"
+#include "dtmf.h"
 #include "gemm_plan.h"
 
 namespace aprilx {
@@ -460,5 +461,29 @@ struct VadArgs {
     float *energy = nullptr;               // (tests) step 1's e of every frame, indexed like out; or null
 };
 void launch_vad(const VadArgs &a, hipStream_t s);
+
+// ---------------------------------------------------------------- DTMF (sessions that opted in; contract in dtmf.h)
+// One descriptor per run of consecutive real frames of a session in this pass: frame i of the run is frame descriptor first + i of the
+// SAME pass (its pcm_off: no sample is staged twice), one byte per frame goes to out[out_off + i].  The descriptor carries the session's
+// plan; the kernel keeps no state.  One wave per frame, kDtmfBlock / 64 waves per workgroup, a wave walks every (waves of its
+// descriptor)-th frame of the run.
+constexpr int kDtmfBlock = 256, kDtmfWaveFrames = 4, kDtmfMaxBlocks = 64;      // lanes per workgroup; frames a wave walks before another workgroup is worth it
+struct DtmfDesc {
+    int32_t first = 0, n = 0, out_off = 0, reserved[3] = {0, 0, 0};
+    DtmfPlan plan;
+};
+static_assert(sizeof(DtmfDesc) == 64, "uploaded as an array");
+struct DtmfArgs {
+    const int16_t *pcm = nullptr;          // staged samples
+    const FbankFrameDesc *frames = nullptr;
+    const DtmfDesc *desc = nullptr; int n_desc = 0;
+    int max_n = 0;                         // max over descriptors of n
+    const float *tables = nullptr; int wd = 0;      // [16][wd] (dtmf_make_tables); every descriptor's plan.Wd is wd
+    uint8_t *out = nullptr;                // the pass's bytes
+    float *powers = nullptr;               // (tests) P[0..8) and E of every frame, [.][9] indexed like out; or null
+};
+void launch_dtmf(const DtmfArgs &a, hipStream_t s);
+// (tests) the decision alone on GIVEN rows of P[0..8), E: codes_out[i] = dtmf_decide(plan, powers9 + 9 i)
+void launch_dtmf_decide(const DtmfPlan &plan, int n, const float *powers9, uint8_t *codes_out, hipStream_t s);
 
 }  // namespace aprilx

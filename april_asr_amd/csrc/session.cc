@@ -560,6 +560,17 @@ bool Scheduler::set_vad(Session *s, const VadOptions *o, const VadPlan *plan, Ap
     });
 }
 
+bool Scheduler::set_dtmf(Session *s, const DtmfOptions *o, const DtmfPlan *plan, AprilxDtmfHandler handler, void *userdata)
+{
+    return configure(s, [&] {
+        s->dtmf_on = plan != nullptr;
+        s->dtmf_opt = o ? *o : DtmfOptions(); s->dtmf_plan = plan ? *plan : DtmfPlan();
+        s->dtmf_handler = plan ? handler : nullptr; s->dtmf_userdata = plan ? userdata : nullptr;
+        s->dtmf_m = DtmfMachine(); s->dtmf_tone = 0; s->dtmf_digits = 0;
+        return true;
+    });
+}
+
 bool Scheduler::set_bias(Session *s, std::shared_ptr<const BiasSet> set)
 {
     return configure(s, [&] {
@@ -606,10 +617,12 @@ void Scheduler::wait_backlog(Session *const *ss, int n, uint64_t max_open)
     }
 }
 
-void deliver_events(std::vector<Event> &ev, AprilRecognitionResultHandler handler, void *userdata, AprilxVadHandler vad, void *vad_userdata)
+void deliver_events(std::vector<Event> &ev, AprilRecognitionResultHandler handler, void *userdata, AprilxVadHandler vad, void *vad_userdata,
+                    AprilxDtmfHandler dtmf, void *dtmf_userdata)
 {
     for (auto &e : ev) {
-        if (e.type >= kVadEventBase) { if (vad) vad(vad_userdata, e.type - kVadEventBase, e.vad_ms); }
+        if (e.type >= kDtmfEventBase) { if (dtmf) dtmf(dtmf_userdata, e.type - kDtmfEventBase, e.dtmf_digit, e.vad_ms); }
+        else if (e.type >= kVadEventBase) { if (vad) vad(vad_userdata, e.type - kVadEventBase, e.vad_ms); }
         else handler(userdata, (AprilResultType)e.type, e.tokens.size(), e.tokens.empty() ? nullptr : e.tokens.data());
     }
     ev.clear();
@@ -619,7 +632,7 @@ void Scheduler::deliver_sync_events(Session *s)
 {
     std::vector<Event> ev;
     { std::lock_guard<std::mutex> g(mu_); ev.swap(s->done_events); }
-    deliver_events(ev, s->handler, s->userdata, s->vad_handler, s->vad_userdata);
+    deliver_events(ev, s->handler, s->userdata, s->vad_handler, s->vad_userdata, s->dtmf_handler, s->dtmf_userdata);
 }
 
 // One stepping thread, TWO flights in the air.  A flight is launched (frames cut, chunk steps enqueued, record copy + event
@@ -733,6 +746,11 @@ void Scheduler::complete_flight(Flight &f)
     eng_->wait_flight(f.parity);
     tick_.host_ms[4] += lap();
     harvest_vad(f.seq);             // (in front of the flight's token events: no later than the chunks that hold the frames)
+    harvest_dtmf(f.seq);
+    while (!blocks_pending_.empty() && blocks_pending_.front().first <= f.seq) {      // both have read them: back to the engine
+        eng_->vad_release(blocks_pending_.front().second);
+        blocks_pending_.pop_front();
+    }
     replay(f);
     tick_.host_ms[5] += lap();
     std::vector<Session *> &work = f.work;
@@ -755,7 +773,7 @@ void Scheduler::complete_flight(Flight &f)
         }
     }
     // async sessions: deliver on this (library) thread, outside the lock
-    for (Session *s : work) if (!s->sync_mode) deliver_events(s->events, s->handler, s->userdata, s->vad_handler, s->vad_userdata);
+    for (Session *s : work) if (!s->sync_mode) deliver_events(s->events, s->handler, s->userdata, s->vad_handler, s->vad_userdata, s->dtmf_handler, s->dtmf_userdata);
     {
         std::lock_guard<std::mutex> g(mu_);
         for (size_t i = 0; i < work.size(); ++i) {
@@ -906,8 +924,8 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
 {
     Lap lap;
     desc_.clear(); pcm_parts_.clear(); in_parts_.clear(); rdesc_.clear(); rspec_.clear(); ddesc_.clear(); raw_parts_.clear(); staged_raw_ = 0;
-    vdesc_.clear(); vruns_.clear();
-    int32_t vad_frames = 0;                     // bytes of this pass's VAD output so far
+    vdesc_.clear(); vruns_.clear(); tdesc_.clear(); truns_.clear();
+    int32_t vad_frames = 0, dtmf_frames = 0;    // bytes of this pass's VAD / DTMF output so far
     size_t staged = 0, staged_in = 0;           // model-rate samples (windows), input-rate samples (spans of resampled windows)
     auto used = [&] { return staged + staged_in + (staged_raw_ + 1) / 2; };      // what the pass has staged so far, raw bytes of formatted sessions in sample units
     std::vector<Session *> finishers;
@@ -956,6 +974,13 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
                 vruns_.push_back(VadRun{s, s->real_frames, cut, vad_frames});
                 vad_frames += cut; s->vad_reset = false;
             }
+            if (s->dtmf_on) {                          // the same run: its frames' descriptors are the last `cut` of this pass
+                DtmfDesc t;
+                t.first = (int32_t)(desc_.size() - (size_t)cut); t.n = cut; t.out_off = dtmf_frames; t.plan = s->dtmf_plan;
+                tdesc_.push_back(t);
+                truns_.push_back(VadRun{s, s->real_frames, cut, dtmf_frames});
+                dtmf_frames += cut;
+            }
             s->real_frames += (uint64_t)cut;
             s->compact_pending = true;                 // the fifo must not move until the window has been staged
             progressed = true;
@@ -1000,6 +1025,7 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
             s->replay.push_back(Session::Replay{-1, 0, 0, (uint32_t)s->now_ms, 1, 0});
             finishers.push_back(s);
             if (s->vad_on) { vruns_.push_back(VadRun{s, s->real_frames, -1, 0}); s->vad_reset = true; }      // closes an open segment; the detector starts afresh
+            if (s->dtmf_on) truns_.push_back(VadRun{s, s->real_frames, -1, 0});                              // closes a held digit; the machine starts afresh
             s->flush_phase = 0;
             progressed = true;
             break;
@@ -1007,18 +1033,22 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
         }
     }
     tick_.host_ms[1] += lap();
-    const uint8_t *vad_bytes = nullptr;         // the pinned block this pass's VAD bytes arrive in
+    const uint8_t *block = nullptr;             // the pinned block this pass's VAD bytes and, behind them, its DTMF bytes arrive in
     if (!desc_.empty()) {
         FrontPass pass;
         pass.n_dc = (int)ddesc_.size(); pass.dc = ddesc_.data(); pass.raw_parts = raw_parts_.data(); pass.n_raw_parts = raw_parts_.size(); pass.n_raw = staged_raw_;
         pass.n_rs = (int)rdesc_.size(); pass.rs = rdesc_.data(); pass.rs_specs = rspec_.data(); pass.in_parts = in_parts_.data(); pass.n_in_parts = in_parts_.size(); pass.n_in = staged_in;
         pass.n_vd = (int)vdesc_.size(); pass.vd = vdesc_.data(); pass.vad_bytes = (size_t)vad_frames;
-        vad_bytes = eng_->fbank((int)desc_.size(), desc_.data(), pcm_parts_.data(), pcm_parts_.size(), staged, &pool_, pass);
+        pass.n_dt = (int)tdesc_.size(); pass.dt = tdesc_.data(); pass.dtmf_bytes = (size_t)dtmf_frames;
+        block = eng_->fbank((int)desc_.size(), desc_.data(), pcm_parts_.data(), pcm_parts_.size(), staged, &pool_, pass);
         pool_.run(work.size(), 64, [&](size_t i) { Session *s = work[i]; if (s->compact_pending) { s->fb.compact(); s->compact_pending = false; } });
         tick_.frames += desc_.size();
         tick_.host_ms[2] += lap();
     }
-    if (!vruns_.empty()) vad_pending_.push_back(VadPending{flight_seq_, vad_bytes, vruns_});
+    // the block is lent until this flight has been waited for and BOTH harvests have read it: complete_flight() gives it back, nobody else
+    if (block) blocks_pending_.emplace_back(flight_seq_, block);
+    if (!vruns_.empty()) vad_pending_.push_back(VadPending{flight_seq_, vdesc_.empty() ? nullptr : block, vruns_});
+    if (!truns_.empty()) dtmf_pending_.push_back(VadPending{flight_seq_, block && !tdesc_.empty() ? block + vad_frames : nullptr, truns_});
     if (!finishers.empty()) {
         slots_.clear();
         for (Session *s : finishers) slots_.push_back(s->slot);
@@ -1157,8 +1187,30 @@ void Scheduler::harvest_vad(uint64_t flight)
             s->vad_last = vad_events(s->vad_plan, shift_ms_, r.t0, b, (size_t)r.n, s->vad_last, emit);
             for (int32_t i = 0; i < r.n; ++i) s->vad_speech += b[i] & 1u;
         }
-        if (p.bytes) eng_->vad_release(p.bytes);
         vad_pending_.pop_front();
+    }
+}
+
+// The same for the DTMF bytes: the codes of consecutive real frames go through the session's event machine (dtmf.h); a completed flush
+// closes a held digit.  A pass whose engine lent no block (the scheduler harness's) contributes no codes.
+void Scheduler::harvest_dtmf(uint64_t flight)
+{
+    while (!dtmf_pending_.empty() && dtmf_pending_.front().flight <= flight) {
+        VadPending &p = dtmf_pending_.front();
+        for (const VadRun &r : p.runs) {
+            Session *s = r.s;
+            auto emit = [&](int kind, char digit, uint64_t ms) {
+                Event e; e.type = kDtmfEventBase + kind; e.vad_ms = ms; e.dtmf_digit = digit;
+                s->events.push_back(std::move(e));
+                if (kind == DTMF_DOWN) s->dtmf_digits++;
+            };
+            if (r.n < 0) { dtmf_flush(shift_ms_, r.t0, s->dtmf_m, emit); continue; }
+            if (!p.bytes) continue;
+            const uint8_t *b = p.bytes + r.off;
+            dtmf_events(s->dtmf_plan, shift_ms_, r.t0, b, (size_t)r.n, s->dtmf_m, emit);
+            for (int32_t i = 0; i < r.n; ++i) s->dtmf_tone += b[i] ? 1u : 0u;
+        }
+        dtmf_pending_.pop_front();
     }
 }
 

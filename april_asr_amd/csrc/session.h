@@ -52,11 +52,14 @@ struct Event {
     std::vector<AprilxTokenInfo> infos;
     // a voice-activity event: type = kVadEventBase + kind, for the session's AprilxVadHandler
     uint64_t vad_ms = 0;
+    // a DTMF event: type = kDtmfEventBase + kind, for the session's AprilxDtmfHandler; its time is vad_ms
+    char dtmf_digit = 0;
 };
-constexpr int kVadEventBase = 0x100;
-// the handler once per event, in order (null token pointer when an event has no tokens); voice-activity events go to `vad`; `ev` is
-// empty afterwards
-void deliver_events(std::vector<Event> &ev, AprilRecognitionResultHandler handler, void *userdata, AprilxVadHandler vad = nullptr, void *vad_userdata = nullptr);
+constexpr int kVadEventBase = 0x100, kDtmfEventBase = 0x200;
+// the handler once per event, in order (null token pointer when an event has no tokens); voice-activity events go to `vad`,
+// DTMF events to `dtmf`; `ev` is empty afterwards
+void deliver_events(std::vector<Event> &ev, AprilRecognitionResultHandler handler, void *userdata, AprilxVadHandler vad = nullptr, void *vad_userdata = nullptr,
+                    AprilxDtmfHandler dtmf = nullptr, void *dtmf_userdata = nullptr);
 
 class Greedy {
 public:
@@ -226,6 +229,12 @@ struct Session {
     bool vad_reset = true;                    // the session's next descriptor starts from the reset state
     uint64_t real_frames = 0, vad_speech = 0;
     uint32_t vad_segments = 0; int vad_last = 0;      // SPEECH_START events so far; bit 0 of the last byte read
+    // DTMF: the same rules.  The device keeps nothing; the machine and the counters are the stepping thread's.
+    bool dtmf_on = false;
+    DtmfOptions dtmf_opt; DtmfPlan dtmf_plan;
+    AprilxDtmfHandler dtmf_handler = nullptr; void *dtmf_userdata = nullptr;
+    DtmfMachine dtmf_m;
+    uint64_t dtmf_tone = 0, dtmf_digits = 0;          // frames with a non-zero code, DOWN events, since the detector was last set
     // tracing (tests): every joiner call appends `vocab` floats
     float *trace_buf = nullptr; size_t trace_cap = 0; size_t *trace_used = nullptr;
 };
@@ -270,6 +279,8 @@ public:
     bool set_search_options(Session *s, const AprilxSearchOptions *o);
     // aprilx_session_set_vad: the same rule; plan null = off.  The detector and its counters start afresh
     bool set_vad(Session *s, const VadOptions *o, const VadPlan *plan, AprilxVadHandler handler, void *userdata);
+    // aprilx_session_set_dtmf: the same rule; plan null = off.  The machine and its counters start afresh
+    bool set_dtmf(Session *s, const DtmfOptions *o, const DtmfPlan *plan, AprilxDtmfHandler handler, void *userdata);
     void wait_idle_many(Session *const *ss, int n);
     // until every listed session has at most `max_open` feeds that were submitted and not completed yet (pipelined group feeds)
     void wait_backlog(Session *const *ss, int n, uint64_t max_open);
@@ -316,6 +327,14 @@ private:
     uint64_t flight_seq_ = 0;
     const int shift_ms_;
     void harvest_vad(uint64_t flight);
+    // DTMF: the same queue discipline; a pass's DTMF bytes follow its VAD bytes in the same block (`bytes` points at the DTMF part; null:
+    // an engine that lends no block)
+    std::deque<VadPending> dtmf_pending_;
+    // the blocks Engine::fbank() lent (one per pass with VAD or DTMF descriptors), by flight: complete_flight() gives each back once, after
+    // harvest_vad and harvest_dtmf have read it; the harvests never release
+    std::deque<std::pair<uint64_t, const uint8_t *>> blocks_pending_;
+    std::vector<DtmfDesc> tdesc_; std::vector<VadRun> truns_;
+    void harvest_dtmf(uint64_t flight);
     int split_sticky_ = 0;
     int pipeline_depth_ = 2;                             // APRIL_PIPELINE: 2 = launch the next flight before completing the current one, 1 = one flight at a time
 

@@ -5,7 +5,7 @@
 //
 //   g++ -O2 -std=c++17 examples/serve_many.cpp -I include -L april_asr_amd -laprilasr -Wl,-rpath,$PWD/april_asr_amd -o serve_many
 //   ./serve_many model.april audio.raw [sessions=64] [mode=pipelined|lockstep] [input_rate] [--alternatives K] [--bias FILE [--bias-strict]]
-//               [--endpoint-ms N] [--blank-penalty X] [--vad]
+//               [--endpoint-ms N] [--blank-penalty X] [--vad] [--dtmf]
 //
 // Every session gets the same PCM16 file, rotated by (session index x 0.37 s) so that the streams differ.  With `input_rate` the file
 // is PCM16 at that rate and every session is told so (aprilx_session_set_input_rate): the library converts it to the model's rate on
@@ -21,6 +21,8 @@
 // an utterance ends N ms after its last token instead of 2200, X is subtracted from the blank logit in the decision.
 // `--vad` (anywhere on the line): every session gets the voice-activity detector with its default options (aprilx_session_set_vad); its line
 // then ends with " vad <segments> <speech seconds>", and the timing lines say what a step cost.
+// `--dtmf` (anywhere on the line): every session gets the DTMF detector with its default options (aprilx_session_set_dtmf); its line then
+// ends with " dtmf <digits>" ("-" when no key was found).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -35,7 +37,13 @@
 struct Stream {
     size_t calls = 0, finals = 0, final_tokens = 0; std::string last_final; double conf_sum = 0; size_t conf_n = 0;
     size_t vad_segments = 0; uint64_t vad_open_ms = 0, vad_speech_ms = 0;
+    std::string dtmf_digits;
 };
+
+static void on_dtmf(void *ud, int kind, char digit, uint64_t)
+{
+    if (kind == APRILX_DTMF_DOWN) static_cast<Stream *>(ud)->dtmf_digits.push_back(digit);
+}
 
 static void on_vad(void *ud, int kind, uint64_t time_ms)
 {
@@ -65,7 +73,14 @@ int main(int argc, char **argv)
     bool bias_strict = false;
     long endpoint_ms = -1;
     const char *blank_penalty = nullptr;
-    bool vad = false;
+    bool vad = false, dtmf = false;
+    for (int i = 1; i < argc; ++i)
+        if (!strcmp(argv[i], "--dtmf")) {
+            dtmf = true;
+            for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+            argc -= 1;
+            break;
+        }
     for (int i = 1; i < argc; ++i)
         if (!strcmp(argv[i], "--vad")) {
             vad = true;
@@ -178,6 +193,10 @@ int main(int argc, char **argv)
             AprilxVadOptions vo = {(uint32_t)sizeof vo, 200.0f, 4000.0f, 5.0f, 3.0f, 50u, 300u, -12.0f, 0u};
             if (aprilx_session_set_vad(sessions[(size_t)i], &vo, on_vad, &streams[(size_t)i]) != 0) { fprintf(stderr, "voice-activity options refused\n"); return 1; }
         }
+        if (dtmf) {
+            AprilxDtmfOptions dopt = {(uint32_t)sizeof dopt, -40.0f, 4.0f, 8.0f, 8.0f, 0.6f, 20u, 20u, 0u};
+            if (aprilx_session_set_dtmf(sessions[(size_t)i], &dopt, on_dtmf, &streams[(size_t)i]) != 0) { fprintf(stderr, "DTMF options refused\n"); return 1; }
+        }
         const size_t rot = ((size_t)i * (size_t)(0.37 * rate)) % pcm.size();
         audio[(size_t)i].assign(pcm.begin() + (long)rot, pcm.end());
         audio[(size_t)i].insert(audio[(size_t)i].end(), pcm.begin(), pcm.begin() + (long)rot);
@@ -197,6 +216,7 @@ int main(int argc, char **argv)
         const Stream &s = streams[(size_t)i];
         printf("%d %zu %zu %zu %s", i, s.calls, s.finals, s.final_tokens, s.last_final.c_str());
         if (vad) printf(" vad %zu %.2f", s.vad_segments, (double)s.vad_speech_ms * 1e-3);      // (the flush has closed every open segment)
+        if (dtmf) printf(" dtmf %s", s.dtmf_digits.empty() ? "-" : s.dtmf_digits.c_str());
         printf("\n");
     }
     fprintf(stderr, "%d streams x %.1f s of audio in %.1f ms (%s feed): %.0f audio-seconds per second\n", n, steps * 0.1, ms, pipelined ? "pipelined" : "lock-step",
@@ -213,6 +233,13 @@ int main(int argc, char **argv)
         aprilx_model_vad_stats(model, 0, &launches, &frames, &kms);
         for (const Stream &s : streams) { segs += s.vad_segments; secs += (double)s.vad_speech_ms * 1e-3; }
         fprintf(stderr, "voice activity: %.3f ms per 100 ms step, %zu segments, %.1f speech seconds, %llu launches over %llu frames on device 0\n", ms / (double)steps, segs, secs,
+                (unsigned long long)launches, (unsigned long long)frames);
+    }
+    if (dtmf) {
+        uint64_t launches = 0, frames = 0; double kms = 0; size_t keys = 0;
+        aprilx_model_dtmf_stats(model, 0, &launches, &frames, &kms);
+        for (const Stream &s : streams) keys += s.dtmf_digits.size();
+        fprintf(stderr, "DTMF: %.3f ms per 100 ms step, %zu keys, %llu launches over %llu frames on device 0\n", ms / (double)steps, keys,
                 (unsigned long long)launches, (unsigned long long)frames);
     }
     if (argc > 5) fprintf(stderr, "input at %zu Hz: %.3f ms per 100 ms step\n", rate, ms / (double)steps);

@@ -370,6 +370,67 @@ APRIL_EXPORT int aprilx_run_vad(AprilASRModel model, int n_runs, const AprilxVad
 /* VAD launches and the frames they covered on one GPU's engine, and (while profiling) the kernel's accumulated ms.  0, or -1. */
 APRIL_EXPORT int aprilx_model_vad_stats(AprilASRModel model, int device_index, uint64_t *launches, uint64_t *frames, double *ms);
 
+/* ---- DTMF.  A session that opts in gets key-down / key-up events for in-band DTMF digits from a detector that
+ * runs on the GPU, on the model-rate samples the filterbank reads (after decode and resampling): per frame the correlation of its first
+ * Wd samples with the eight DTMF frequencies, level, twist, peak and energy-share checks -> one code per frame; the host turns
+ * consecutive codes into events.  The feature only observes, as voice activity does, and an engine none of whose sessions has opted in
+ * launches and copies nothing new.  Times are on the FRAME clock of the voice-activity events; delivery follows their rules.  A flush
+ * that completes inside a held digit closes it with an UP at frames_seen * frame_shift, and resets the machine.  The digits are
+ * "123A456B789C*0#D"[code - 1].  Second-harmonic talk-off rejection is not part of the contract. */
+typedef struct AprilxDtmfOptions {
+    uint32_t size;                      /* sizeof(AprilxDtmfOptions) */
+    float min_level_dbfs;               /* -40: -70..0; level floor per tone */
+    float twist_hi_db, twist_lo_db;     /* 4, 8: 0..20; column group over row group, row group over column group */
+    float rel_peak_db;                  /* 8: 3..30; the peak over the other rows / columns */
+    float min_share;                    /* 0.6: 0 < s <= 1; share of the frame's energy in the two tones */
+    uint32_t min_tone_ms, min_pause_ms; /* 20, 20: 10..1000; frames = ms / frame_shift_ms, at least 1 */
+    uint32_t flags;                     /* 0 */
+} AprilxDtmfOptions;
+enum { APRILX_DTMF_DOWN = 1, APRILX_DTMF_UP = 2 };
+typedef void (*AprilxDtmfHandler)(void *userdata, int kind, char digit, uint64_t time_ms);
+typedef struct AprilxDtmfInfo {
+    int32_t Wd, on_frames, off_frames;
+    uint32_t held;                      /* the digit held after the last frame read (a character), or 0 */
+    uint64_t frames_seen;               /* real frames of the session since its creation */
+    uint64_t tone_frames;               /* frames with a non-zero code, since the detector was last set */
+    uint64_t digits;                    /* DOWN events since the detector was last set */
+} AprilxDtmfInfo;
+/* the plan the kernel and the event machine work from (40 bytes); tests and users of aprilx_dtmf_host */
+typedef struct AprilxDtmfPlan {
+    int32_t Wd; float half_w, min_power, twist_hi, twist_lo, rel_peak, min_share; int32_t on_frames, off_frames, reserved;
+} AprilxDtmfPlan;
+/* the event machine's state between calls of aprilx_dtmf_events_host: all zero at the start and after a flush */
+typedef struct AprilxDtmfMachine { int32_t held, cand, run; } AprilxDtmfMachine;
+/* options = NULL: off.  0, or -1 and nothing changes: a wrong size, a value out of range, non-zero flags, a NULL handler with options,
+ * a model the detector refuses (a window Wd / rate below 12 ms, a rate below 4000 Hz, Wd above 4096), or a session with audio fed
+ * since its last completed flush (the rule of aprilx_session_set_vad).  Setting resets the machine and its counters. */
+APRIL_EXPORT int aprilx_session_set_dtmf(AprilASRSession session, const AprilxDtmfOptions *options, AprilxDtmfHandler handler, void *userdata);
+/* 1 and the options / info when the detector is on, 0 (info: frames_seen only) when it is off, -1 on bad arguments; either pointer
+ * may be NULL.  Waits for the session to be idle. */
+APRIL_EXPORT int aprilx_session_dtmf(AprilASRSession session, AprilxDtmfOptions *options_out, AprilxDtmfInfo *out);
+/* The plan of a model with this rate, fft size (aprilx_model_fbank_tables: 2 nfft_bins) and frame shift: 0, or -1 as above.  No GPU. */
+APRIL_EXPORT int aprilx_dtmf_plan(int sample_rate, int fft_size, int frame_shift_ms, const AprilxDtmfOptions *options, AprilxDtmfPlan *plan_out);
+/* The tables [16][Wd] (rows 0..7 cos, 8..15 sin of the eight frequencies) into out[cap]: 16 Wd, or -1 (cap too small, bad Wd).  No GPU. */
+APRIL_EXPORT int aprilx_dtmf_tables(int sample_rate, int Wd, float *out, size_t cap);
+/* The contract on the host: frame i at frames + i * ld (ld >= Wd samples) through steps 1-5; codes_out[n], powers_out [n][9]
+ * (P[0..8) and E) or NULL.  No GPU. */
+APRIL_EXPORT int aprilx_dtmf_host(const AprilxDtmfPlan *plan, const float *tables, int n, const int16_t *frames, size_t ld, uint8_t *codes_out,
+                                  float *powers_out);
+/* steps 3-4 on one row of P[0..8), E: the code, or -1 on bad arguments.  No GPU. */
+APRIL_EXPORT int aprilx_dtmf_decide_host(const AprilxDtmfPlan *plan, const float *powers9);
+/* Events from the codes of frames [t0, t0 + n) from *machine: kinds_out / digits_out / times_out (cap entries each) receive them in
+ * order; flush != 0: a flush then completes at frame t0 + n.  Returns their number (may exceed cap: nothing is written past it).  No GPU. */
+APRIL_EXPORT int aprilx_dtmf_events_host(const AprilxDtmfPlan *plan, int frame_shift_ms, uint64_t t0, const uint8_t *codes, size_t n, int flush,
+                                         AprilxDtmfMachine *machine, int32_t *kinds_out, char *digits_out, uint64_t *times_out, int cap);
+/* Tests only: dtmf_kernel on n_runs runs in ONE launch.  Run r has its own options and n[r] frames, consecutive in
+ * frames[sum n][fft_size] as for aprilx_run_fbank; codes_out[sum n], powers_out [sum n][9] or NULL.  0, or -1 on bad arguments. */
+APRIL_EXPORT int aprilx_run_dtmf(AprilASRModel model, const AprilxDtmfOptions *options, int n_runs, const int32_t *n, const int16_t *frames,
+                                 uint8_t *codes_out, float *powers_out);
+/* Tests only: the kernel's decision alone on n given rows of P[0..8), E.  0, or -1. */
+APRIL_EXPORT int aprilx_run_dtmf_decide(AprilASRModel model, const AprilxDtmfOptions *options, int n, const float *powers9, uint8_t *codes_out);
+/* DTMF launches and the frames they covered on one GPU's engine, and (while profiling) the kernel's accumulated ms.  0, or -1. */
+APRIL_EXPORT int aprilx_model_dtmf_stats(AprilASRModel model, int device_index, uint64_t *launches, uint64_t *frames, double *ms);
+
 typedef struct AprilxStats {
     uint64_t ticks, steps, chunks, rounds, frames, max_batch_seen;
     /* per kernel class: accumulated ms and launch counts while profiling is enabled
