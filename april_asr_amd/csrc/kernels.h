@@ -165,6 +165,8 @@ void launch_gemm_z(const GemmArgs *staged, int n, const GemmArgs *dev_args, hipS
 // form and zcount = the launch's problem count: fused -> launch it as it is; else launch its EPI_PARTIAL form, which writes
 // `planes` planes, and a row kernel behind it.  For an EPI_PARTIAL g, `planes` is what its launch writes.
 GemmPlan gemm_plan(const GemmArgs &g);
+// The query gemm_plan builds from g: its scalar fields and the capabilities the kernel files state for it (test entries report them)
+GemmQuery gemm_query(const GemmArgs &g);
 // measurement only (tools/tile_bench): enable -1 = environment default, 0 / 1 = off / on; mt, zs = 0 (planner's choice) or pinned
 void gemm_tile_pin(int enable, int mt, int zs);
 

@@ -760,7 +760,7 @@ void gemm_tile_pin(int enable, int mt, int zs) { GemmKnobs &k = knobs(); k.tile_
 void gemm_pp_pin(int enable, int mt) { GemmKnobs &k = knobs(); k.pp_enable = enable; k.pp_pin_mt = mt; }
 void gemm_kw_pin(int enable, int mt) { GemmKnobs &k = knobs(); k.kw_enable = enable; k.kw_pin_mt = mt; }
 
-static GemmQuery gemm_query(const GemmArgs &g)
+GemmQuery gemm_query(const GemmArgs &g)
 {
     GemmQuery q;
     q.M = g.M; q.N = g.N; q.K = g.K; q.K0 = g.K0; q.K1 = g.K1; q.kz = g.kz; q.epi = g.epi; q.a_op = g.a_op; q.wt = g.wt; q.wave_mask = g.wave_mask;

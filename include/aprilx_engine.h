@@ -120,6 +120,28 @@ APRIL_EXPORT int aprilx_plan_gemm(int M, int N, int kz, int zcount, int tile_ok,
  * out[13]: the capabilities found for it (stream-kernel form, GM_KW, GM_PP, 192-column GM_PP), then route form mode mt nt zs planes
  * fused error (csrc/gemm_plan.h).  No GPU needed; tests only. */
 APRIL_EXPORT int aprilx_gemm_plan_debug(const int32_t *in, int32_t *out);
+/* ONE GEMM launch of csrc/kernels.h against host arrays, the way the engine launches it (csrc/gemm_debug_api.cc; needs a GPU, no
+ * model; tests only: tests/gemm_ref.py states the mathematics it is compared with).  n = 1..3 problems of one shape.
+ * desc[48], int32: 0 n, 1 M, 2 N, 3 K, 4 K0, 5 K1, 6 kz, 7 epi, 8 a_op, 9 wt, 10 wave_mask, 11 tile_ok, 12 force_fullk, 13 hidden,
+ *   14 ldo, 15 lda0, 16 lda1, 17 ldr, 18 ld_state, 19 ldp, 20 value of the run_flag word (-1: no run_flag), 21 run_gen, 22 ctx_vocab,
+ *   23 same_idx_b, 24 rows_alloc (rows of every row-indexed device array; >= M rounded up to 256), 25 slots (rows of the slot tables),
+ *   26 a0 rows, 27 a1 rows, 28 a0b rows, 29 x_scale.groups, 30 r_scale.groups, 31 out != null, 32 out16 != null, 33 state16 != null,
+ *   34..36 gemm_tile_pin(enable, mt, zs), 37..38 gemm_kw_pin(enable, mt), 39..40 gemm_pp_pin(enable, mt) -- applied for this call and
+ *   put back to (-1, 0, 0) / (-1, 0) before it returns; the rest 0.
+ * fdesc[4]: x_scale.inv_n, x_scale.eps, r_scale.inv_n, r_scale.eps.
+ * in[n][17], host pointers or NULL: 0 a0 fp32 [a0 rows][lda0], 1 a1 [a1 rows][lda1], 2 a0b [a0b rows][lda0], 3 aidx0 [M], 4 aidx1 [M],
+ *   5 aidx0b [M], 6 slot_idx [M], 7 row_mask [M], 8 ctx_state [slots][4 x int32], 9 bias [N], 10 resid [M][ldr], 11 p_add [M][ldp],
+ *   12 x_scale partials [M][groups], 13 r_scale partials [M][groups], 14 c_state [slots][hidden] (in), 15 reserved, 16 W [K x N] in the
+ *   x4 packed fp32 order at the top of csrc/kernels.h.  wt == 1: the binary16 operands are made on the device by launch_cvt_f16, and
+ *   for tile_ok == 2 by launch_repack_x32 with binary16 activation rows (a0, a1), as an fp16 engine holds them.
+ * out[n][7], host pointers or NULL; every device array behind them is filled with 0xFF bytes before the launch (c_state: the input):
+ *   0 out fp32 [R][ldo], R = slots for EPI_SLOT_STORE with slot_idx, else rows_alloc, 1 out16 [R][ldo] binary16, 2 state
+ *   [slots][ld_state], 3 state16, 4 c_state [slots][hidden], 5 ssq_out [rows_alloc][N / 32], 6 the partial planes
+ *   [8][rows_alloc][N] of an EPI_PARTIAL problem or of a row-epilogue problem that ran as planes + row kernel.
+ * plan_out[16]: the capabilities gemm_query found (stream form, GM_KW, GM_PP, 192-column GM_PP), then gemm_plan's route form mode mt
+ *   nt zs planes fused error, then 1 when planes + row kernel ran.
+ * Returns 0; -1 bad arguments; -2 a HIP call failed; -3 the plan carries an error (nothing launched). */
+APRIL_EXPORT int aprilx_run_gemm(const int32_t *desc, const float *fdesc, const void *const *in, void *const *out, int32_t *plan_out);
 
 /* Ramp merge, the pure host part: which problems of the NEXT feed's first R macro steps the last R macro steps
  * of a feed of T chunks over L layers can hold.  Writes one record of 3 + 2 R words per window step to out (cap words): own macro step

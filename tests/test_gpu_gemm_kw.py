@@ -5,7 +5,9 @@ so all of them must produce the same bits:
   * tools/kw_bench compares every output (rows, state rows, sums of squares) of GM_KW against the round-4 schedules bitwise on 27
     shapes (ragged rows, z-batched 1..3 problems, both tile heights, the larger encoder's kz = 2 chunk form, FFN up on four waves);
   * whole sessions streamed with GM_KW switched off and on (and with either tile height pinned) give identical logits and callbacks,
-    at sizes where the projection / FFN-down launches cross the schedule boundaries inside one run."""
+    at sizes where the projection / FFN-down launches cross the schedule boundaries inside one run.
+What "the same bits" are the bits OF is pinned elsewhere: tests/test_gpu_gemm_launch.py compares single GM_KW launches (every tile,
+ragged rows, z-batched) and the schedules they are compared with here against a float64 reference (tests/gemm_ref.py)."""
 import os
 import subprocess
 import sys

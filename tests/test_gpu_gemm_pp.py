@@ -8,7 +8,10 @@ tiles whose two wave groups work one phase apart.  Smaller launches keep GM_TILE
     callbacks at a size where the gates launches cross the schedule boundary inside one run (wavefront of 1..3 chunk steps);
   * the 256 x 192 form (csrc/kernels_gemm_pw.hip: N a multiple of 192, i.e. the larger encoder's gates) is one of pp_bench's pinned forms
     ("ppw") and is switched off / on under whole sessions of the larger encoder at 512 sessions, where the three-problem launches of
-    the feed wavefront take it."""
+    the feed wavefront take it.
+What "the same bits" are the bits OF is pinned elsewhere: tests/test_gpu_gemm_launch.py compares single GM_PP launches (both tile
+heights, the halves, the 192-column form, ragged rows) and the GM_TILE forms they are compared with here against a float64
+reference (tests/gemm_ref.py)."""
 import os
 import subprocess
 import sys
