@@ -394,19 +394,19 @@ class Model:
             raise ValueError("aprilx_run_dtmf_decide refused its arguments")
         return codes
 
-    def dtmf_stats(self, device_index: int = 0):
-        """(launches, frames, ms): DTMF launches of one GPU's engine, the frames they covered, and (while profiling) the kernel's time"""
+    def _detector_stats(self, entry, device_index):
         l, f, ms = C.c_uint64(0), C.c_uint64(0), C.c_double(0)
-        if self._L.aprilx_model_dtmf_stats(self._handle, device_index, C.byref(l), C.byref(f), C.byref(ms)) != 0:
+        if entry(self._handle, device_index, C.byref(l), C.byref(f), C.byref(ms)) != 0:
             raise ValueError("no such device")
         return int(l.value), int(f.value), float(ms.value)
 
+    def dtmf_stats(self, device_index: int = 0):
+        """(launches, frames, ms): DTMF launches of one GPU's engine, the frames they covered, and (while profiling) the kernel's time"""
+        return self._detector_stats(self._L.aprilx_model_dtmf_stats, device_index)
+
     def vad_stats(self, device_index: int = 0):
         """(launches, frames, ms): VAD launches of one GPU's engine, the frames they covered, and (while profiling) the kernel's time"""
-        l, f, ms = C.c_uint64(0), C.c_uint64(0), C.c_double(0)
-        if self._L.aprilx_model_vad_stats(self._handle, device_index, C.byref(l), C.byref(f), C.byref(ms)) != 0:
-            raise ValueError("no such device")
-        return int(l.value), int(f.value), float(ms.value)
+        return self._detector_stats(self._L.aprilx_model_vad_stats, device_index)
 
     def stats(self, device_index: int = 0):
         s = _ffi.AprilxStats()
@@ -859,34 +859,30 @@ _VAD_FIELDS = ("band_lo_hz", "band_hi_hz", "onset_db", "offset_db", "onset_ms", 
 _VAD_DEFAULTS = dict(band_lo_hz=200.0, band_hi_hz=4000.0, onset_db=5.0, offset_db=3.0, onset_ms=50, hangover_ms=300, min_energy=-12.0)
 
 
-def _vad_options(options):
-    if isinstance(options, _ffi.AprilxVadOptions):
-        return options
-    d = dict(_VAD_DEFAULTS)
-    if isinstance(options, dict):
-        unknown = set(options) - set(_VAD_FIELDS)
-        if unknown:
-            raise ValueError("unknown voice-activity options %r" % sorted(unknown))
-        d.update(options)
-    return _ffi.AprilxVadOptions(C.sizeof(_ffi.AprilxVadOptions), float(d["band_lo_hz"]), float(d["band_hi_hz"]), float(d["onset_db"]),
-                                 float(d["offset_db"]), int(d["onset_ms"]), int(d["hangover_ms"]), float(d["min_energy"]), 0)
-
-
 _DTMF_FIELDS = ("min_level_dbfs", "twist_hi_db", "twist_lo_db", "rel_peak_db", "min_share", "min_tone_ms", "min_pause_ms")
 _DTMF_DEFAULTS = dict(min_level_dbfs=-40.0, twist_hi_db=4.0, twist_lo_db=8.0, rel_peak_db=8.0, min_share=0.6, min_tone_ms=20, min_pause_ms=20)
 
 
-def _dtmf_options(options):
-    if isinstance(options, _ffi.AprilxDtmfOptions):
+def _detector_options(options, struct, fields, defaults, what):
+    """a detector's public options struct (size, `fields` in the struct's order, flags) from True / a dict over `defaults` / the struct itself"""
+    if isinstance(options, struct):
         return options
-    d = dict(_DTMF_DEFAULTS)
+    d = dict(defaults)
     if isinstance(options, dict):
-        unknown = set(options) - set(_DTMF_FIELDS)
+        unknown = set(options) - set(fields)
         if unknown:
-            raise ValueError("unknown DTMF options %r" % sorted(unknown))
+            raise ValueError("unknown %s options %r" % (what, sorted(unknown)))
         d.update(options)
-    return _ffi.AprilxDtmfOptions(C.sizeof(_ffi.AprilxDtmfOptions), float(d["min_level_dbfs"]), float(d["twist_hi_db"]), float(d["twist_lo_db"]),
-                                  float(d["rel_peak_db"]), float(d["min_share"]), int(d["min_tone_ms"]), int(d["min_pause_ms"]), 0)
+    kinds = dict(struct._fields_)
+    return struct(C.sizeof(struct), *[(float if kinds[n] is C.c_float else int)(d[n]) for n in fields], 0)
+
+
+def _vad_options(options):
+    return _detector_options(options, _ffi.AprilxVadOptions, _VAD_FIELDS, _VAD_DEFAULTS, "voice-activity")
+
+
+def _dtmf_options(options):
+    return _detector_options(options, _ffi.AprilxDtmfOptions, _DTMF_FIELDS, _DTMF_DEFAULTS, "DTMF")
 
 
 def dtmf_plan(sample_rate: int, fft_size: int, frame_shift_ms: int, options=True):

@@ -14,5 +14,5 @@ struct AprilASRSession_i { aprilx::Session s; };
 struct AprilxBias_i { std::shared_ptr<const aprilx::BiasSet> set; };
 struct AprilxGreedy_i {
     aprilx::Greedy g; AprilRecognitionResultHandler handler; void *ud; std::vector<aprilx::Event> ev;
-    void flush_events() { aprilx::deliver_events(ev, handler, ud); }
+    void flush_events() { aprilx::deliver_events(ev, aprilx::Handlers{handler, ud}); }
 };

@@ -391,7 +391,7 @@ AprilASRSession aas_create_session(AprilASRModel model, AprilConfig config)
     AprilASRSession_i *h = new AprilASRSession_i();
     Session &s = h->s;
     s.model = &m; s.eng = m.engines[best]; s.sched = m.scheds[best]; s.slot = slot;
-    s.handler = config.handler; s.userdata = config.userdata;
+    s.handlers.result = config.handler; s.handlers.userdata = config.userdata;
     s.sync_mode = (config.flags & (APRIL_CONFIG_FLAG_ASYNC_RT_BIT | APRIL_CONFIG_FLAG_ASYNC_NO_RT_BIT)) == 0;   // :28
     s.realtime_flag = (config.flags & APRIL_CONFIG_FLAG_ASYNC_RT_BIT) != 0;
     s.fb.shift = m.ftab.shift; s.fb.padded = m.ftab.padded;

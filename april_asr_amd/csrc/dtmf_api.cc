@@ -48,20 +48,20 @@ int aprilx_session_dtmf(AprilASRSession session, AprilxDtmfOptions *options_out,
     Session *s = &session->s;
     s->sched->wait_idle(s);
     if (options_out) {
-        const DtmfOptions &o = s->dtmf_opt;
+        const DtmfOptions &o = s->dtmf.opt;
         *options_out = AprilxDtmfOptions{(uint32_t)sizeof(AprilxDtmfOptions), o.min_level_dbfs, o.twist_hi_db, o.twist_lo_db, o.rel_peak_db, o.min_share,
                                          o.min_tone_ms, o.min_pause_ms, 0u};
     }
     if (out) {
         memset(out, 0, sizeof *out);
         out->frames_seen = s->real_frames;
-        if (s->dtmf_on) {
-            out->Wd = s->dtmf_plan.Wd; out->on_frames = s->dtmf_plan.on_frames; out->off_frames = s->dtmf_plan.off_frames;
-            out->held = s->dtmf_m.held ? (uint32_t)(unsigned char)kDtmfDigits[s->dtmf_m.held - 1] : 0u;
-            out->tone_frames = s->dtmf_tone; out->digits = s->dtmf_digits;
+        if (s->dtmf.on) {
+            out->Wd = s->dtmf.plan.Wd; out->on_frames = s->dtmf.plan.on_frames; out->off_frames = s->dtmf.plan.off_frames;
+            out->held = s->dtmf.m.held ? (uint32_t)(unsigned char)kDtmfDigits[s->dtmf.m.held - 1] : 0u;
+            out->tone_frames = s->dtmf.tone; out->digits = s->dtmf.digits;
         }
     }
-    return s->dtmf_on ? 1 : 0;
+    return s->dtmf.on ? 1 : 0;
 }
 
 int aprilx_dtmf_plan(int sample_rate, int fft_size, int frame_shift_ms, const AprilxDtmfOptions *options, AprilxDtmfPlan *plan_out)

@@ -410,7 +410,6 @@ Engine::~Engine()
     if (bias_state_d_) (void)hipFree(bias_state_d_);
     for (void *p : {(void *)vad_state_d_, (void *)pass_out_d_}) if (p) (void)hipFree(p);
     for (PassBlock &k : pass_blocks_) (void)hipHostFree(k.h);
-    for (int b = 0; b < 2; ++b) if (dt_desc_h_[b]) { (void)hipHostFree(dt_desc_h_[b]); (void)hipFree(dt_desc_d_[b]); }
     if (ws_g_) (void)hipFree(ws_g_);
     if (conv_wt_) (void)hipFree(conv_wt_);
     if (dec_table_) (void)hipFree(dec_table_);
@@ -706,8 +705,8 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
     const size_t dt_frames = n_dt ? pass.dtmf_bytes : 0, out_bytes = vd_frames + dt_frames;      // the pass's bytes: VAD, then DTMF
     StagingCounts cnt;
     cnt.n_pcm = n_pcm; cnt.n_in = n_rs ? pass.n_in : 0; cnt.n_raw = n_dc ? pass.n_raw : 0;
-    cnt.n_frames = (size_t)n_frames; cnt.n_rs = (size_t)n_rs; cnt.n_dc = (size_t)n_dc; cnt.n_vd = (size_t)n_vd;
-    const StagingSizes el{sizeof(FbankFrameDesc), sizeof(ResampleDesc), sizeof(DecodeDesc), sizeof(VadDesc)};
+    cnt.n_frames = (size_t)n_frames; cnt.n_rs = (size_t)n_rs; cnt.n_dc = (size_t)n_dc; cnt.n_vd = (size_t)n_vd; cnt.n_dt = (size_t)n_dt;
+    const StagingSizes el{sizeof(FbankFrameDesc), sizeof(ResampleDesc), sizeof(DecodeDesc), sizeof(VadDesc), sizeof(DtmfDesc)};
     const StagingLayout lay = staging_layout(cnt, el);
     HIP_CHECK(hipSetDevice(cfg_.device));
     for (int i = 0; i < n_rs; ++i) rs[i].taps = resample_table(pass.rs_specs[i]);      // (uploaded at a conversion's first use)
@@ -722,20 +721,12 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
             if (!fb_done_[b]) HIP_CHECK(hipEventCreateWithFlags(&fb_done_[b], hipEventDisableTiming));
         }
     }
-    PassBlock *vblock = nullptr;
-    const float *dt_tables = n_dt ? dtmf_tables() : nullptr;
-    if (n_dt && (size_t)n_dt > dt_cap_) {
-        // the DTMF descriptors travel in a pinned array of their own per flip (not in the staging buffer: its layout stays as it is)
-        sync();
-        HipLegacyLock guard;
-        for (int b = 0; b < 2; ++b) if (dt_desc_h_[b]) { (void)hipHostFree(dt_desc_h_[b]); (void)hipFree(dt_desc_d_[b]); }
-        dt_cap_ = std::max<size_t>((size_t)n_dt * 2, 256);
-        for (int b = 0; b < 2; ++b) { dt_desc_h_[b] = hmalloc<DtmfDesc>(dt_cap_); dt_desc_d_[b] = dmalloc<DtmfDesc>(dt_cap_); }
-    }
+    PassBlock *block = nullptr;
+    const float *dt_tables = n_dt ? dtmf_tables() : nullptr;      // (sets dt_wd_)
     if (n_vd || n_dt) {
         // a pass with VAD or DTMF descriptors: the first VAD pass of the engine allocates the per-slot records; the device's byte buffer
-        // (the pass's VAD bytes, then its DTMF bytes) grows behind a sync (earlier
-        // passes' copies read it); a pass takes a pinned block nobody holds, or a new one (warm-up only)
+        // (the pass's VAD bytes, then its DTMF bytes) grows behind a sync (earlier passes' copies read it); a pass takes a pinned block
+        // nobody holds, or a new one (warm-up only)
         if (n_vd && !vad_state_d_) vad_state_d_ = dmalloc<VadState>((size_t)cfg_.max_slots);
         if (out_bytes > pass_out_cap_) {
             sync();
@@ -744,35 +735,37 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
             pass_out_cap_ = std::max<size_t>(out_bytes * 2, 4096);
             pass_out_d_ = dmalloc<uint8_t>(pass_out_cap_);
         }
-        for (PassBlock &k : pass_blocks_) if (!k.busy && k.cap >= out_bytes && (!vblock || k.cap < vblock->cap)) vblock = &k;
-        if (!vblock) {
+        for (PassBlock &k : pass_blocks_) if (!k.busy && k.cap >= out_bytes && (!block || k.cap < block->cap)) block = &k;
+        if (!block) {
             PassBlock k;
             k.cap = 4096; while (k.cap < out_bytes) k.cap *= 2;
             k.h = hmalloc<uint8_t>(k.cap);
             pass_blocks_.push_back(k);
-            vblock = &pass_blocks_.back();
+            block = &pass_blocks_.back();
         }
-        vblock->busy = true;
+        block->busy = true;
     }
     const int b = fb_flip_;
     fb_flip_ ^= 1;
     HIP_CHECK(hipEventSynchronize(fb_done_[b]));          // the launch that used this pair two calls ago has consumed it
-    const size_t woff = lay.raw, doff = lay.frames, roff = lay.rs, coff = lay.dc, voff = lay.vd, bytes = lay.bytes;      // (staging_layout.h)
+    const size_t woff = lay.raw, doff = lay.frames, roff = lay.rs, coff = lay.dc, voff = lay.vd, toff = lay.dt, bytes = lay.bytes;      // (staging_layout.h)
     char *hs = reinterpret_cast<char *>(hs_pcm_[b]);
     memcpy(hs + doff, desc, (size_t)n_frames * sizeof(FbankFrameDesc));
     if (n_vd) memcpy(hs + voff, pass.vd, (size_t)n_vd * sizeof(VadDesc));
     DtmfArgs ta;
-    if (n_dt) {       // (fb_done_[b] has been waited for: the launch that read this flip's descriptor array is through)
+    if (n_dt) {
+        memcpy(hs + toff, pass.dt, (size_t)n_dt * sizeof(DtmfDesc));
         for (int i = 0; i < n_dt; ++i) {
             const DtmfDesc &t = pass.dt[i];
             if (t.n <= 0 || t.first < 0 || t.first + t.n > n_frames || t.out_off < 0 || (size_t)t.out_off + (size_t)t.n > dt_frames || t.plan.Wd != dt_wd_) {
                 LOGE("fbank: DTMF descriptor %d outside the pass", i); abort();
             }
             for (int k = 0; k < t.n; ++k) if (desc[t.first + k].pcm_off < 0) { LOGE("fbank: a padding row inside DTMF run %d", i); abort(); }
-            dt_desc_h_[b][i] = t;
             ta.max_n = std::max(ta.max_n, t.n);
         }
-        ta.n_desc = n_dt; ta.tables = dt_tables; ta.wd = dt_wd_;
+        const char *dev = reinterpret_cast<const char *>(ds_pcm_[b]);
+        ta.pcm = ds_pcm_[b]; ta.frames = reinterpret_cast<const FbankFrameDesc *>(dev + doff); ta.out = pass_out_d_ + vd_frames;
+        ta.desc = reinterpret_cast<const DtmfDesc *>(dev + toff); ta.n_desc = n_dt; ta.tables = dt_tables; ta.wd = dt_wd_;
     }
     ResampleArgs ra;
     if (n_rs) {
@@ -832,10 +825,6 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
         va.ring = ring_; va.ring_frames = ring_frames_; va.nbins = ft_.nbins; va.state = vad_state_d_; va.out = pass_out_d_;
         va.desc = reinterpret_cast<const VadDesc *>(reinterpret_cast<const char *>(ds_pcm_[b]) + voff); va.n_desc = n_vd;
     }
-    if (n_dt) {
-        HIP_CHECK(hipMemcpyAsync(dt_desc_d_[b], dt_desc_h_[b], (size_t)n_dt * sizeof(DtmfDesc), hipMemcpyHostToDevice, f_stream_));
-        ta.pcm = ds_pcm_[b]; ta.frames = a.desc; ta.desc = dt_desc_d_[b]; ta.out = pass_out_d_ + vd_frames;
-    }
     if (profiling_) {        // (the per-class hipEvents live on M: a profiled fbank runs there, behind its upload)
         m_touched();
         join(stream_, f_stream_);
@@ -853,15 +842,17 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
         if (n_vd) launch_vad(va, f_stream_);
     }
     if (n_vd || n_dt) {       // the pass's bytes -> its pinned block, in front of fb_done_; read after the flight's wait (close_flight)
-        HIP_CHECK(hipMemcpyAsync(vblock->h, pass_out_d_, out_bytes, hipMemcpyDeviceToHost, f_stream_));
+        HIP_CHECK(hipMemcpyAsync(block->h, pass_out_d_, out_bytes, hipMemcpyDeviceToHost, f_stream_));
         pass_bytes_flight_ = true;
         if (n_vd) { vad_launches_.fetch_add(1, std::memory_order_relaxed); vad_frames_.fetch_add(vd_frames, std::memory_order_relaxed); }
         if (n_dt) { dt_launches_.fetch_add(1, std::memory_order_relaxed); dt_frames_.fetch_add(dt_frames, std::memory_order_relaxed); }
     }
     HIP_CHECK(hipEventRecord(fb_done_[b], f_stream_));       // no host wait here: the encoder launches queue right behind
     f_unseen_by_m_ = true;
-    return vblock ? vblock->h : nullptr;
+    return block ? block->h : nullptr;
 }
+
+void Engine::release_pass_block(const uint8_t *p) { for (PassBlock &b : pass_blocks_) if (b.h == p) b.busy = false; }
 
 // the DTMF tables of this engine's model (dtmf.h), uploaded at the first DTMF pass or debug call
 const float *Engine::dtmf_tables()

@@ -125,12 +125,11 @@ struct FrontPass {
     // regions that were only reserved, in one decode launch before the resample and the fbank launch.
     int n_dc = 0; const DecodeDesc *dc = nullptr;
     const std::pair<const uint8_t *, size_t> *raw_parts = nullptr; size_t n_raw_parts = 0, n_raw = 0;
-    // Voice activity: the n_vd descriptors (out_off counted from 0, `vad_bytes` bytes in all); vad_kernel runs
-    // right behind the fbank launch.
+    // The two detectors (DESIGN.md sections 16 and 17) write one byte per real frame of an opted-in session into the block fbank() returns:
+    // the pass's `vad_bytes` VAD bytes, then its `dtmf_bytes` DTMF bytes; a descriptor's out_off counts from the start of its detector's part.
+    // Voice activity: the n_vd descriptors name ring rows; vad_kernel runs right behind the fbank launch.
     int n_vd = 0; const VadDesc *vd = nullptr; size_t vad_bytes = 0;
-    // DTMF: the n_dt descriptors (out_off counted from 0, `dtmf_bytes` bytes in all; `first` indexes the frame
-    // descriptors of this call).  They travel in a small upload of their own; dtmf_kernel runs behind the resample launch.  The pass's
-    // bytes follow its VAD bytes in the block fbank() returns: at [vad_bytes, vad_bytes + dtmf_bytes).
+    // DTMF: the n_dt descriptors (`first` indexes the frame descriptors of this call); dtmf_kernel runs behind the resample launch.
     int n_dt = 0; const DtmfDesc *dt = nullptr; size_t dtmf_bytes = 0;
 };
 
@@ -184,8 +183,9 @@ public:
     // back to back, and the host reads the 16-byte-per-round records once, at end_flight().
     // pcm arrives as `n_parts` windows that are gathered straight into pinned staging (total n_pcm samples)
     // `pass`: the resample / decode / VAD / DTMF work of this call.  Returns the pinned block that receives the pass's VAD bytes and, behind
-    // them, its DTMF bytes (null: neither VAD nor DTMF descriptors): its bytes are complete once the flight that was open during the call has been waited for (close_flight() puts the
-    // copy in front of the flight's event), and the block is lent until vad_release().  Stepping thread only.
+    // them, its DTMF bytes (null: neither VAD nor DTMF descriptors): its bytes are complete once the flight that was open during the call
+    // has been waited for (close_flight() puts the copy in front of the flight's event), and the block is lent until
+    // release_pass_block().  Stepping thread only.
     const uint8_t *fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<const int16_t *, size_t> *parts, size_t n_parts, size_t n_pcm,
                          HostPool *pool = nullptr, const FrontPass &pass = FrontPass());
     // decode launches and the frames they decoded so far (any thread)
@@ -193,11 +193,10 @@ public:
     {
         *launches = dc_launches_.load(std::memory_order_relaxed); *frames = dc_frames_.load(std::memory_order_relaxed);
     }
-    // ---- voice activity.  Inline over plain members: the scheduler harness links session.cc against an engine of
-    // its own.  Nothing is allocated until a pass carries a VAD descriptor.
-    // vad_release(): gives back the block a fbank() call lent -- the block of the pass's VAD bytes AND its DTMF bytes; the scheduler calls it
-    // once per block, after both have been read
-    void vad_release(const uint8_t *p) { for (PassBlock &b : pass_blocks_) if (b.h == p) b.busy = false; }
+    // gives back the block a fbank() call lent; the scheduler calls it once per block, when it has read the pass's bytes.  Stepping thread only.
+    void release_pass_block(const uint8_t *p);
+    // ---- voice activity.  The counters are inline over plain members: the scheduler harness links session.cc
+    // against an engine of its own.  Nothing is allocated until a pass carries a VAD descriptor.
     // VAD launches and the frames they covered so far (any thread)
     void vad_counts(uint64_t *launches, uint64_t *frames) const
     {
@@ -481,12 +480,11 @@ private:
     VadState *vad_state_d_ = nullptr;          // [slots] (a session's first descriptor carries VAD_RESET: never initialised by the host)
     uint8_t *pass_out_d_ = nullptr; size_t pass_out_cap_ = 0;      // one pass's bytes on the device, VAD then DTMF (stream order keeps the passes apart)
     struct PassBlock { uint8_t *h = nullptr; size_t cap = 0; bool busy = false; };
-    std::vector<PassBlock> pass_blocks_;         // pinned blocks, one per pass whose bytes (VAD, then DTMF) the scheduler has not read yet: lent by fbank(), busy until vad_release()
+    std::vector<PassBlock> pass_blocks_;         // pinned blocks, one per pass whose bytes (VAD, then DTMF) the scheduler has not read yet: lent by fbank(), busy until release_pass_block()
     bool pass_bytes_flight_ = false;                  // the open flight holds a pass with VAD or DTMF bytes: its event must follow their copy on the front-end stream
     std::atomic<uint64_t> vad_launches_{0}, vad_frames_{0};
-    // DTMF: nothing below is allocated until a pass carries a DTMF descriptor (the bytes share the VAD's device buffer and pinned blocks)
+    // DTMF: nothing below is allocated until a pass carries a DTMF descriptor
     const float *dt_tables_ = nullptr; int dt_wd_ = 0;      // [16][Wd] on the device, uploaded once (freed with table_allocs_)
-    DtmfDesc *dt_desc_h_[2] = {nullptr, nullptr}, *dt_desc_d_[2] = {nullptr, nullptr}; size_t dt_cap_ = 0;      // one descriptor array per staging flip
     std::atomic<uint64_t> dt_launches_{0}, dt_frames_{0};
     const float *dtmf_tables();
     std::mutex rs_mu_;

@@ -474,7 +474,7 @@ struct DtmfDesc {
     int32_t first = 0, n = 0, out_off = 0, reserved[3] = {0, 0, 0};
     DtmfPlan plan;
 };
-static_assert(sizeof(DtmfDesc) == 64, "uploaded as an array");
+static_assert(sizeof(DtmfDesc) == 64, "staged behind the VAD descriptors, 16-byte aligned");
 struct DtmfArgs {
     const int16_t *pcm = nullptr;          // staged samples
     const FbankFrameDesc *frames = nullptr;

@@ -487,7 +487,7 @@ bool Scheduler::submit(int n, Session *const *ss, const short *const *pcm, const
     }
     work_seq_.fetch_add(1, std::memory_order_release);
     cv_work_.notify_one();
-    for (Session *s : overflowed) s->handler(s->userdata, APRIL_RESULT_ERROR_CANT_KEEP_UP, 0, nullptr);
+    for (Session *s : overflowed) s->handlers.result(s->handlers.userdata, APRIL_RESULT_ERROR_CANT_KEEP_UP, 0, nullptr);
     if (!wait) return true;
     spin_while_unchanged(done_seq_, done_seen, spin_wait_us_);
     std::unique_lock<std::mutex> lk(mu_);
@@ -552,10 +552,9 @@ bool Scheduler::set_search_options(Session *s, const AprilxSearchOptions *o)
 bool Scheduler::set_vad(Session *s, const VadOptions *o, const VadPlan *plan, AprilxVadHandler handler, void *userdata)
 {
     return configure(s, [&] {
-        s->vad_on = plan != nullptr;
-        s->vad_opt = o ? *o : VadOptions(); s->vad_plan = plan ? *plan : VadPlan();
-        s->vad_handler = plan ? handler : nullptr; s->vad_userdata = plan ? userdata : nullptr;
-        s->vad_reset = true; s->vad_speech = 0; s->vad_segments = 0; s->vad_last = 0;
+        s->vad = Session::Vad();
+        if (plan) { s->vad.on = true; s->vad.opt = *o; s->vad.plan = *plan; }
+        s->handlers.vad = plan ? handler : nullptr; s->handlers.vad_userdata = plan ? userdata : nullptr;
         return true;
     });
 }
@@ -563,10 +562,9 @@ bool Scheduler::set_vad(Session *s, const VadOptions *o, const VadPlan *plan, Ap
 bool Scheduler::set_dtmf(Session *s, const DtmfOptions *o, const DtmfPlan *plan, AprilxDtmfHandler handler, void *userdata)
 {
     return configure(s, [&] {
-        s->dtmf_on = plan != nullptr;
-        s->dtmf_opt = o ? *o : DtmfOptions(); s->dtmf_plan = plan ? *plan : DtmfPlan();
-        s->dtmf_handler = plan ? handler : nullptr; s->dtmf_userdata = plan ? userdata : nullptr;
-        s->dtmf_m = DtmfMachine(); s->dtmf_tone = 0; s->dtmf_digits = 0;
+        s->dtmf = Session::Dtmf();
+        if (plan) { s->dtmf.on = true; s->dtmf.opt = *o; s->dtmf.plan = *plan; }
+        s->handlers.dtmf = plan ? handler : nullptr; s->handlers.dtmf_userdata = plan ? userdata : nullptr;
         return true;
     });
 }
@@ -617,13 +615,12 @@ void Scheduler::wait_backlog(Session *const *ss, int n, uint64_t max_open)
     }
 }
 
-void deliver_events(std::vector<Event> &ev, AprilRecognitionResultHandler handler, void *userdata, AprilxVadHandler vad, void *vad_userdata,
-                    AprilxDtmfHandler dtmf, void *dtmf_userdata)
+void deliver_events(std::vector<Event> &ev, const Handlers &to)
 {
     for (auto &e : ev) {
-        if (e.type >= kDtmfEventBase) { if (dtmf) dtmf(dtmf_userdata, e.type - kDtmfEventBase, e.dtmf_digit, e.vad_ms); }
-        else if (e.type >= kVadEventBase) { if (vad) vad(vad_userdata, e.type - kVadEventBase, e.vad_ms); }
-        else handler(userdata, (AprilResultType)e.type, e.tokens.size(), e.tokens.empty() ? nullptr : e.tokens.data());
+        if (e.type >= kDtmfEventBase) { if (to.dtmf) to.dtmf(to.dtmf_userdata, e.type - kDtmfEventBase, e.digit, e.time_ms); }
+        else if (e.type >= kVadEventBase) { if (to.vad) to.vad(to.vad_userdata, e.type - kVadEventBase, e.time_ms); }
+        else to.result(to.userdata, (AprilResultType)e.type, e.tokens.size(), e.tokens.empty() ? nullptr : e.tokens.data());
     }
     ev.clear();
 }
@@ -632,7 +629,7 @@ void Scheduler::deliver_sync_events(Session *s)
 {
     std::vector<Event> ev;
     { std::lock_guard<std::mutex> g(mu_); ev.swap(s->done_events); }
-    deliver_events(ev, s->handler, s->userdata, s->vad_handler, s->vad_userdata, s->dtmf_handler, s->dtmf_userdata);
+    deliver_events(ev, s->handlers);
 }
 
 // One stepping thread, TWO flights in the air.  A flight is launched (frames cut, chunk steps enqueued, record copy + event
@@ -745,12 +742,7 @@ void Scheduler::complete_flight(Flight &f)
     Lap lap;
     eng_->wait_flight(f.parity);
     tick_.host_ms[4] += lap();
-    harvest_vad(f.seq);             // (in front of the flight's token events: no later than the chunks that hold the frames)
-    harvest_dtmf(f.seq);
-    while (!blocks_pending_.empty() && blocks_pending_.front().first <= f.seq) {      // both have read them: back to the engine
-        eng_->vad_release(blocks_pending_.front().second);
-        blocks_pending_.pop_front();
-    }
+    harvest(f.seq);                 // (in front of the flight's token events: no later than the chunks that hold the frames)
     replay(f);
     tick_.host_ms[5] += lap();
     std::vector<Session *> &work = f.work;
@@ -773,7 +765,7 @@ void Scheduler::complete_flight(Flight &f)
         }
     }
     // async sessions: deliver on this (library) thread, outside the lock
-    for (Session *s : work) if (!s->sync_mode) deliver_events(s->events, s->handler, s->userdata, s->vad_handler, s->vad_userdata, s->dtmf_handler, s->dtmf_userdata);
+    for (Session *s : work) if (!s->sync_mode) deliver_events(s->events, s->handlers);
     {
         std::lock_guard<std::mutex> g(mu_);
         for (size_t i = 0; i < work.size(); ++i) {
@@ -924,7 +916,8 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
 {
     Lap lap;
     desc_.clear(); pcm_parts_.clear(); in_parts_.clear(); rdesc_.clear(); rspec_.clear(); ddesc_.clear(); raw_parts_.clear(); staged_raw_ = 0;
-    vdesc_.clear(); vruns_.clear(); tdesc_.clear(); truns_.clear();
+    vdesc_.clear(); tdesc_.clear();
+    PassPending rec{flight_seq_, nullptr, 0, {}, {}};      // this pass's record in the pass queue: its runs and flush markers, then its block
     int32_t vad_frames = 0, dtmf_frames = 0;    // bytes of this pass's VAD / DTMF output so far
     size_t staged = 0, staged_in = 0;           // model-rate samples (windows), input-rate samples (spans of resampled windows)
     auto used = [&] { return staged + staged_in + (staged_raw_ + 1) / 2; };      // what the pass has staged so far, raw bytes of formatted sessions in sample units
@@ -966,19 +959,19 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
             else if (fb.fmt) stage_decoded(fb, (int64_t)first, (int64_t)last_end, base);
             else fb.append_span(first, last_end, pcm_parts_);                 // (contiguous in staging)
             staged += last_end - first;
-            if (s->vad_on) {                           // the run of real rows just cut: one descriptor, one byte per row
+            if (s->vad.on) {                           // the run of real rows just cut: one descriptor, one byte per row
                 VadDesc v;
                 v.slot = s->slot; v.first_row = desc_[desc_.size() - (size_t)cut].ring_row; v.n = cut; v.out_off = vad_frames;
-                v.flags = s->vad_reset ? VAD_RESET : 0; v.plan = s->vad_plan;
+                v.flags = s->vad.reset ? VAD_RESET : 0; v.plan = s->vad.plan;
                 vdesc_.push_back(v);
-                vruns_.push_back(VadRun{s, s->real_frames, cut, vad_frames});
-                vad_frames += cut; s->vad_reset = false;
+                rec.vad.push_back(PassRun{s, s->real_frames, cut, vad_frames});
+                vad_frames += cut; s->vad.reset = false;
             }
-            if (s->dtmf_on) {                          // the same run: its frames' descriptors are the last `cut` of this pass
+            if (s->dtmf.on) {                          // the same run: its frames' descriptors are the last `cut` of this pass
                 DtmfDesc t;
-                t.first = (int32_t)(desc_.size() - (size_t)cut); t.n = cut; t.out_off = dtmf_frames; t.plan = s->dtmf_plan;
+                t.first = (int32_t)(desc_.size() - (size_t)cut); t.n = cut; t.out_off = dtmf_frames; t.plan = s->dtmf.plan;
                 tdesc_.push_back(t);
-                truns_.push_back(VadRun{s, s->real_frames, cut, dtmf_frames});
+                rec.dtmf.push_back(PassRun{s, s->real_frames, cut, dtmf_frames});
                 dtmf_frames += cut;
             }
             s->real_frames += (uint64_t)cut;
@@ -1024,8 +1017,8 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
             // records of this flight; the device part (context reset + decoder refresh) is queued here
             s->replay.push_back(Session::Replay{-1, 0, 0, (uint32_t)s->now_ms, 1, 0});
             finishers.push_back(s);
-            if (s->vad_on) { vruns_.push_back(VadRun{s, s->real_frames, -1, 0}); s->vad_reset = true; }      // closes an open segment; the detector starts afresh
-            if (s->dtmf_on) truns_.push_back(VadRun{s, s->real_frames, -1, 0});                              // closes a held digit; the machine starts afresh
+            if (s->vad.on) { rec.vad.push_back(PassRun{s, s->real_frames, -1, 0}); s->vad.reset = true; }      // closes an open segment; the detector starts afresh
+            if (s->dtmf.on) rec.dtmf.push_back(PassRun{s, s->real_frames, -1, 0});                              // closes a held digit; the machine starts afresh
             s->flush_phase = 0;
             progressed = true;
             break;
@@ -1033,22 +1026,20 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
         }
     }
     tick_.host_ms[1] += lap();
-    const uint8_t *block = nullptr;             // the pinned block this pass's VAD bytes and, behind them, its DTMF bytes arrive in
     if (!desc_.empty()) {
         FrontPass pass;
         pass.n_dc = (int)ddesc_.size(); pass.dc = ddesc_.data(); pass.raw_parts = raw_parts_.data(); pass.n_raw_parts = raw_parts_.size(); pass.n_raw = staged_raw_;
         pass.n_rs = (int)rdesc_.size(); pass.rs = rdesc_.data(); pass.rs_specs = rspec_.data(); pass.in_parts = in_parts_.data(); pass.n_in_parts = in_parts_.size(); pass.n_in = staged_in;
         pass.n_vd = (int)vdesc_.size(); pass.vd = vdesc_.data(); pass.vad_bytes = (size_t)vad_frames;
         pass.n_dt = (int)tdesc_.size(); pass.dt = tdesc_.data(); pass.dtmf_bytes = (size_t)dtmf_frames;
-        block = eng_->fbank((int)desc_.size(), desc_.data(), pcm_parts_.data(), pcm_parts_.size(), staged, &pool_, pass);
+        rec.block = eng_->fbank((int)desc_.size(), desc_.data(), pcm_parts_.data(), pcm_parts_.size(), staged, &pool_, pass);
         pool_.run(work.size(), 64, [&](size_t i) { Session *s = work[i]; if (s->compact_pending) { s->fb.compact(); s->compact_pending = false; } });
         tick_.frames += desc_.size();
         tick_.host_ms[2] += lap();
     }
-    // the block is lent until this flight has been waited for and BOTH harvests have read it: complete_flight() gives it back, nobody else
-    if (block) blocks_pending_.emplace_back(flight_seq_, block);
-    if (!vruns_.empty()) vad_pending_.push_back(VadPending{flight_seq_, vdesc_.empty() ? nullptr : block, vruns_});
-    if (!truns_.empty()) dtmf_pending_.push_back(VadPending{flight_seq_, block && !tdesc_.empty() ? block + vad_frames : nullptr, truns_});
+    // the block is lent until this flight has been waited for and harvest() has read it
+    rec.dtmf_at = (size_t)vad_frames;
+    if (rec.block || !rec.vad.empty() || !rec.dtmf.empty()) pass_pending_.push_back(std::move(rec));
     if (!finishers.empty()) {
         slots_.clear();
         for (Session *s : finishers) slots_.push_back(s->slot);
@@ -1168,50 +1159,52 @@ bool Scheduler::step_chunks(std::vector<Session *> &ready)
     return true;
 }
 
-// After the flight's wait: the bytes of every VAD pass cut under it (and under the flights before it) are on the host.  Per run, in
-// pass order, the events that follow from bit 0 of consecutive bytes go to the session's event list; a completed flush closes an
-// open segment.  The sessions are alive: they stay busy until their flight completes.
-void Scheduler::harvest_vad(uint64_t flight)
+// After the flight's wait: the bytes of every pass cut under it (and under the flights before it) are on the host.  The records up to
+// the flight are walked twice -- all VAD runs of all of them, then all DTMF runs: the order of a session's detector events in front of
+// the flight's token events --, then each gives its block back and goes.  The sessions are alive: they stay busy until their flight
+// completes.  An engine that lent no block to a pass with descriptors: that pass's bytes are skipped by both detectors alike.
+void Scheduler::harvest(uint64_t flight)
 {
-    while (!vad_pending_.empty() && vad_pending_.front().flight <= flight) {
-        VadPending &p = vad_pending_.front();
-        for (const VadRun &r : p.runs) {
-            Session *s = r.s;
-            auto emit = [&](int kind, uint64_t ms) {
-                Event e; e.type = kVadEventBase + kind; e.vad_ms = ms;
-                s->events.push_back(std::move(e));
-                if (kind == VAD_SPEECH_START) s->vad_segments++;
-            };
-            if (r.n < 0) { if (s->vad_last) emit(VAD_SPEECH_END, r.t0 * (uint64_t)shift_ms_); s->vad_last = 0; continue; }
-            const uint8_t *b = p.bytes + r.off;
-            s->vad_last = vad_events(s->vad_plan, shift_ms_, r.t0, b, (size_t)r.n, s->vad_last, emit);
-            for (int32_t i = 0; i < r.n; ++i) s->vad_speech += b[i] & 1u;
-        }
-        vad_pending_.pop_front();
+    size_t n = 0;
+    while (n < pass_pending_.size() && pass_pending_[n].flight <= flight) ++n;
+    for (size_t i = 0; i < n; ++i) for (const PassRun &r : pass_pending_[i].vad) harvest_vad(pass_pending_[i], r);
+    for (size_t i = 0; i < n; ++i) for (const PassRun &r : pass_pending_[i].dtmf) harvest_dtmf(pass_pending_[i], r);
+    for (; n; --n) {
+        if (pass_pending_.front().block) eng_->release_pass_block(pass_pending_.front().block);
+        pass_pending_.pop_front();
     }
 }
 
-// The same for the DTMF bytes: the codes of consecutive real frames go through the session's event machine (dtmf.h); a completed flush
-// closes a held digit.  A pass whose engine lent no block (the scheduler harness's) contributes no codes.
-void Scheduler::harvest_dtmf(uint64_t flight)
+// One VAD run: the events that follow from bit 0 of consecutive bytes go to the session's event list; a completed flush closes an open segment.
+void Scheduler::harvest_vad(const PassPending &p, const PassRun &r)
 {
-    while (!dtmf_pending_.empty() && dtmf_pending_.front().flight <= flight) {
-        VadPending &p = dtmf_pending_.front();
-        for (const VadRun &r : p.runs) {
-            Session *s = r.s;
-            auto emit = [&](int kind, char digit, uint64_t ms) {
-                Event e; e.type = kDtmfEventBase + kind; e.vad_ms = ms; e.dtmf_digit = digit;
-                s->events.push_back(std::move(e));
-                if (kind == DTMF_DOWN) s->dtmf_digits++;
-            };
-            if (r.n < 0) { dtmf_flush(shift_ms_, r.t0, s->dtmf_m, emit); continue; }
-            if (!p.bytes) continue;
-            const uint8_t *b = p.bytes + r.off;
-            dtmf_events(s->dtmf_plan, shift_ms_, r.t0, b, (size_t)r.n, s->dtmf_m, emit);
-            for (int32_t i = 0; i < r.n; ++i) s->dtmf_tone += b[i] ? 1u : 0u;
-        }
-        dtmf_pending_.pop_front();
-    }
+    Session *s = r.s;
+    auto emit = [&](int kind, uint64_t ms) {
+        Event e; e.type = kVadEventBase + kind; e.time_ms = ms;
+        s->events.push_back(std::move(e));
+        if (kind == VAD_SPEECH_START) s->vad.segments++;
+    };
+    if (r.n < 0) { if (s->vad.last) emit(VAD_SPEECH_END, r.t0 * (uint64_t)shift_ms_); s->vad.last = 0; return; }
+    if (!p.block) return;
+    const uint8_t *b = p.block + r.off;
+    s->vad.last = vad_events(s->vad.plan, shift_ms_, r.t0, b, (size_t)r.n, s->vad.last, emit);
+    for (int32_t i = 0; i < r.n; ++i) s->vad.speech += b[i] & 1u;
+}
+
+// One DTMF run: the codes of consecutive real frames go through the session's event machine (dtmf.h); a completed flush closes a held digit.
+void Scheduler::harvest_dtmf(const PassPending &p, const PassRun &r)
+{
+    Session *s = r.s;
+    auto emit = [&](int kind, char digit, uint64_t ms) {
+        Event e; e.type = kDtmfEventBase + kind; e.time_ms = ms; e.digit = digit;
+        s->events.push_back(std::move(e));
+        if (kind == DTMF_DOWN) s->dtmf.digits++;
+    };
+    if (r.n < 0) { dtmf_flush(shift_ms_, r.t0, s->dtmf.m, emit); return; }
+    if (!p.block) return;
+    const uint8_t *b = p.block + p.dtmf_at + r.off;
+    dtmf_events(s->dtmf.plan, shift_ms_, r.t0, b, (size_t)r.n, s->dtmf.m, emit);
+    for (int32_t i = 0; i < r.n; ++i) s->dtmf.tone += b[i] ? 1u : 0u;
 }
 
 // After the flight: per session, in the order things happened, feed the device's per-round records to the search state

@@ -50,16 +50,20 @@ struct Event {
     // sessions with confidences on (aprilx_session_set_confidence): one entry per token, and tokens[i].reserved points to infos[i].
     // Events are only ever MOVED between containers (the vector's storage, and with it the pointers, stay where they are).
     std::vector<AprilxTokenInfo> infos;
-    // a voice-activity event: type = kVadEventBase + kind, for the session's AprilxVadHandler
-    uint64_t vad_ms = 0;
-    // a DTMF event: type = kDtmfEventBase + kind, for the session's AprilxDtmfHandler; its time is vad_ms
-    char dtmf_digit = 0;
+    // a detector's event: type = kVadEventBase + kind or kDtmfEventBase + kind (section 17) at time_ms; `digit` is
+    // a DTMF event's key
+    uint64_t time_ms = 0;
+    char digit = 0;
 };
 constexpr int kVadEventBase = 0x100, kDtmfEventBase = 0x200;
-// the handler once per event, in order (null token pointer when an event has no tokens); voice-activity events go to `vad`,
-// DTMF events to `dtmf`; `ev` is empty afterwards
-void deliver_events(std::vector<Event> &ev, AprilRecognitionResultHandler handler, void *userdata, AprilxVadHandler vad = nullptr, void *vad_userdata = nullptr,
-                    AprilxDtmfHandler dtmf = nullptr, void *dtmf_userdata = nullptr);
+// where a session's events go: token events to `result`, voice-activity events to `vad`, DTMF events to `dtmf` (null: dropped)
+struct Handlers {
+    AprilRecognitionResultHandler result = nullptr; void *userdata = nullptr;
+    AprilxVadHandler vad = nullptr; void *vad_userdata = nullptr;
+    AprilxDtmfHandler dtmf = nullptr; void *dtmf_userdata = nullptr;
+};
+// the handler once per event, in order (null token pointer when an event has no tokens); `ev` is empty afterwards
+void deliver_events(std::vector<Event> &ev, const Handlers &to);
 
 class Greedy {
 public:
@@ -179,8 +183,7 @@ struct Session {
     Scheduler *sched = nullptr;
     Engine *eng = nullptr;
     int slot = -1;
-    AprilRecognitionResultHandler handler = nullptr;
-    void *userdata = nullptr;
+    Handlers handlers;                        // (the detectors' handlers change with their options, below)
     bool sync_mode = true, realtime_flag = false;
 
     // ---- guarded by Scheduler::mu_
@@ -221,20 +224,19 @@ struct Session {
     size_t now_ms = 0;
     uint64_t chunks = 0;
     std::vector<Event> events;                // produced during the current tick
-    // voice activity.  Options, plan and handler change only while the session is settable; the counters are the
-    // stepping thread's while the session is busy.  real_frames counts every real frame cut since creation (VAD on or off): the frame clock.
-    bool vad_on = false;
-    VadOptions vad_opt; VadPlan vad_plan;
-    AprilxVadHandler vad_handler = nullptr; void *vad_userdata = nullptr;
-    bool vad_reset = true;                    // the session's next descriptor starts from the reset state
-    uint64_t real_frames = 0, vad_speech = 0;
-    uint32_t vad_segments = 0; int vad_last = 0;      // SPEECH_START events so far; bit 0 of the last byte read
-    // DTMF: the same rules.  The device keeps nothing; the machine and the counters are the stepping thread's.
-    bool dtmf_on = false;
-    DtmfOptions dtmf_opt; DtmfPlan dtmf_plan;
-    AprilxDtmfHandler dtmf_handler = nullptr; void *dtmf_userdata = nullptr;
-    DtmfMachine dtmf_m;
-    uint64_t dtmf_tone = 0, dtmf_digits = 0;          // frames with a non-zero code, DOWN events, since the detector was last set
+    // The detectors (DESIGN.md sections 16 and 17).  Options, plan and handler (in `handlers`) change only while the session is settable; the
+    // rest is the stepping thread's while the session is busy.  real_frames: every real frame cut since creation, the frame clock of both.
+    uint64_t real_frames = 0;
+    struct Vad {
+        bool on = false; VadOptions opt; VadPlan plan;
+        bool reset = true;                    // the session's next descriptor starts from the reset state (the device keeps the detector's state)
+        uint64_t speech = 0; uint32_t segments = 0; int last = 0;      // since the detector was last set: frames with the speech bit, SPEECH_START events; bit 0 of the last byte read
+    } vad;
+    struct Dtmf {
+        bool on = false; DtmfOptions opt; DtmfPlan plan;
+        DtmfMachine m;                        // (the device keeps nothing)
+        uint64_t tone = 0, digits = 0;        // frames with a non-zero code, DOWN events, since the detector was last set
+    } dtmf;
     // tracing (tests): every joiner call appends `vocab` floats
     float *trace_buf = nullptr; size_t trace_cap = 0; size_t *trace_used = nullptr;
 };
@@ -303,7 +305,7 @@ private:
         std::chrono::steady_clock::time_point t0;
         std::chrono::steady_clock::time_point t_sub;          // hand-over of the oldest work in the flight (submit() of any of its sessions)
         bool has_sub = false;
-        uint64_t seq = 0;                                    // launch order: the VAD passes cut under this flight carry it
+        uint64_t seq = 0;                                    // launch order: the pass records cut under this flight carry it
     };
     void loop();
     bool collect(std::vector<Session *> &work, std::vector<uint64_t> &taken, bool block, uint64_t &work_seen);
@@ -319,22 +321,19 @@ private:
     bool advance(Session *const *group, int m, int T, StepPath path);
     template <class Apply> bool configure(Session *s, Apply apply);     // the three set_* calls: wait_idle, lock, refuse unless settable, apply
     void replay(Flight &f);
-    // voice activity: what the passes of the open flights wrote, read once their flight has been waited for (complete_flight)
-    struct VadRun { Session *s; uint64_t t0; int32_t n, off; };          // frames [t0, t0 + n) at bytes[off ..]; n < 0: a flush completed at frame t0
-    struct VadPending { uint64_t flight; const uint8_t *bytes; std::vector<VadRun> runs; };
-    std::deque<VadPending> vad_pending_;
-    std::vector<VadDesc> vdesc_; std::vector<VadRun> vruns_;
+    // The pass queue: what the detectors' kernels wrote for the passes of the open flights ("the pass's bytes").
+    // cut_frames() pushes one record per pass that has runs, under the flight that is open; harvest(), once that flight has been waited
+    // for, turns the runs into events, gives the block back to the engine and pops the record.  The record is the block's one owner.
+    struct PassRun { Session *s; uint64_t t0; int32_t n, off; };      // frames [t0, t0 + n) at off in its detector's part; n < 0: a flush completed at frame t0
+    // block: Engine::fbank()'s, the pass's VAD bytes and from dtmf_at its DTMF bytes; null: a pass of flush markers only
+    struct PassPending { uint64_t flight; const uint8_t *block; size_t dtmf_at; std::vector<PassRun> vad, dtmf; };
+    std::deque<PassPending> pass_pending_;
+    std::vector<VadDesc> vdesc_; std::vector<DtmfDesc> tdesc_;       // scratch of cut_frames()
     uint64_t flight_seq_ = 0;
     const int shift_ms_;
-    void harvest_vad(uint64_t flight);
-    // DTMF: the same queue discipline; a pass's DTMF bytes follow its VAD bytes in the same block (`bytes` points at the DTMF part; null:
-    // an engine that lends no block)
-    std::deque<VadPending> dtmf_pending_;
-    // the blocks Engine::fbank() lent (one per pass with VAD or DTMF descriptors), by flight: complete_flight() gives each back once, after
-    // harvest_vad and harvest_dtmf have read it; the harvests never release
-    std::deque<std::pair<uint64_t, const uint8_t *>> blocks_pending_;
-    std::vector<DtmfDesc> tdesc_; std::vector<VadRun> truns_;
-    void harvest_dtmf(uint64_t flight);
+    void harvest(uint64_t flight);
+    void harvest_vad(const PassPending &p, const PassRun &r);
+    void harvest_dtmf(const PassPending &p, const PassRun &r);
     int split_sticky_ = 0;
     int pipeline_depth_ = 2;                             // APRIL_PIPELINE: 2 = launch the next flight before completing the current one, 1 = one flight at a time
 

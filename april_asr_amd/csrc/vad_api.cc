@@ -46,18 +46,18 @@ int aprilx_session_vad(AprilASRSession session, AprilxVadOptions *options_out, A
     Session *s = &session->s;
     s->sched->wait_idle(s);
     if (options_out) {
-        const VadOptions &o = s->vad_opt;
+        const VadOptions &o = s->vad.opt;
         *options_out = AprilxVadOptions{(uint32_t)sizeof(AprilxVadOptions), o.band_lo_hz, o.band_hi_hz, o.onset_db, o.offset_db, o.onset_ms, o.hangover_ms, o.min_energy, 0u};
     }
     if (out) {
         memset(out, 0, sizeof *out);
         out->frames_seen = s->real_frames;
-        if (s->vad_on) {
-            out->b0 = s->vad_plan.b0; out->b1 = s->vad_plan.b1; out->onset_frames = s->vad_plan.onset_frames; out->hangover_frames = s->vad_plan.hangover_frames;
-            out->speech_frames = s->vad_speech; out->in_speech = (uint32_t)s->vad_last; out->segments = s->vad_segments;
+        if (s->vad.on) {
+            out->b0 = s->vad.plan.b0; out->b1 = s->vad.plan.b1; out->onset_frames = s->vad.plan.onset_frames; out->hangover_frames = s->vad.plan.hangover_frames;
+            out->speech_frames = s->vad.speech; out->in_speech = (uint32_t)s->vad.last; out->segments = s->vad.segments;
         }
     }
-    return s->vad_on ? 1 : 0;
+    return s->vad.on ? 1 : 0;
 }
 
 int aprilx_vad_plan_tables(const float *mel, int nbins, int nfft_bins, int sample_rate, int frame_shift_ms, const AprilxVadOptions *options, AprilxVadPlan *plan_out)

@@ -3,6 +3,9 @@
 // expression, its regrow condition, its five capacity updates and its capacity expression, restated literally below (with the
 // descriptor sizes as constants, since the descriptor structs live in a HIP header).  Every field must be equal for all eight on/off
 // combinations of the three passes, on counts that break every alignment, and along sequences of calls that grow the buffers.
+// The old text knew no DTMF array: every comparison with it is a call with n_dt = 0, which must give what it always gave.  Calls with
+// n_dt > 0 are held against what the layout promises instead: the array 16-byte aligned behind the VAD array, the upload ending where it
+// ends, inside a buffer of `units`, and a regrow exactly when a count exceeds its capacity.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -16,7 +19,7 @@ static long checks = 0;
 #define CHECK(c) do { ++checks; if (!(c)) { if (fails < 20) printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); ++fails; } } while (0)
 
 // the descriptor sizes of one sweep, under the names the old text used through sizeof()
-static size_t S_FbankFrameDesc, S_ResampleDesc, S_DecodeDesc, S_VadDesc;
+static size_t S_FbankFrameDesc, S_ResampleDesc, S_DecodeDesc, S_VadDesc, S_DtmfDesc;
 
 // ---- the old text: members ...
 struct Old {
@@ -57,14 +60,14 @@ struct Old {
 
 // ---- the new text, as Engine::fbank() uses it
 struct New {
-    StagingCaps caps; size_t units = 0; bool regrew = false; StagingLayout lay;
-    void call(int n_frames, size_t n_pcm, int n_rs, size_t n_in, int n_dc, size_t n_raw, int n_vd)
+    StagingCaps caps; size_t units = 0; bool regrew = false; StagingLayout lay; StagingCounts cnt;
+    void call(int n_frames, size_t n_pcm, int n_rs, size_t n_in, int n_dc, size_t n_raw, int n_vd, int n_dt = 0)
     {
-        n_rs = std::max(n_rs, 0); n_dc = std::max(n_dc, 0); n_vd = std::max(n_vd, 0);
-        StagingCounts cnt;
+        n_rs = std::max(n_rs, 0); n_dc = std::max(n_dc, 0); n_vd = std::max(n_vd, 0); n_dt = std::max(n_dt, 0);
+        cnt = StagingCounts();
         cnt.n_pcm = n_pcm; cnt.n_in = n_rs ? n_in : 0; cnt.n_raw = n_dc ? n_raw : 0;
-        cnt.n_frames = (size_t)n_frames; cnt.n_rs = (size_t)n_rs; cnt.n_dc = (size_t)n_dc; cnt.n_vd = (size_t)n_vd;
-        const StagingSizes el{S_FbankFrameDesc, S_ResampleDesc, S_DecodeDesc, S_VadDesc};
+        cnt.n_frames = (size_t)n_frames; cnt.n_rs = (size_t)n_rs; cnt.n_dc = (size_t)n_dc; cnt.n_vd = (size_t)n_vd; cnt.n_dt = (size_t)n_dt;
+        const StagingSizes el{S_FbankFrameDesc, S_ResampleDesc, S_DecodeDesc, S_VadDesc, S_DtmfDesc};
         lay = staging_layout(cnt, el);
         regrew = !caps.holds(cnt, lay);
         if (regrew) { caps.grow(cnt, lay); units = caps.units(el); }
@@ -81,16 +84,37 @@ static void compare(const Old &o, const New &n)
     CHECK(n.lay.raw % 16 == 0 && n.lay.frames % 16 == 0 && n.lay.rs % 16 == 0 && n.lay.dc % 16 == 0 && n.lay.vd % 16 == 0);
 }
 
+// a call with DTMF descriptors, `before` the capacities it met
+static void check_dt(const New &n, const StagingCaps &before)
+{
+    const StagingCounts &c = n.cnt;
+    CHECK(c.n_dt > 0);
+    CHECK(n.lay.dt % 16 == 0 && n.lay.dt >= n.lay.vd + c.n_vd * S_VadDesc && n.lay.dt < n.lay.vd + c.n_vd * S_VadDesc + 16);
+    CHECK(n.lay.bytes == n.lay.dt + c.n_dt * S_DtmfDesc);
+    CHECK(n.lay.bytes <= n.lay.units * 2);              // a buffer of exactly these counts holds the upload ...
+    CHECK(n.lay.bytes <= n.units * 2);                  // ... and so do the buffers as they are after the call
+    const bool exceeds = c.n_frames > before.frames || n.lay.pcm_units > before.pcm_units || c.n_rs > before.rs || c.n_dc > before.dc ||
+                         c.n_vd > before.vd || c.n_dt > before.dt;
+    CHECK(n.regrew == exceeds);
+    CHECK(n.caps.holds(c, n.lay));
+    if (!n.regrew)
+        CHECK(n.caps.frames == before.frames && n.caps.pcm_units == before.pcm_units && n.caps.rs == before.rs && n.caps.dc == before.dc &&
+              n.caps.vd == before.vd && n.caps.dt == before.dt);
+    else
+        CHECK(n.caps.frames >= before.frames && n.caps.pcm_units >= before.pcm_units && n.caps.rs >= before.rs && n.caps.dc >= before.dc &&
+              n.caps.vd >= before.vd && n.caps.dt >= std::max(before.dt, c.n_dt));
+}
+
 int main()
 {
-    const size_t sizes[][4] = {{12, 64, 24, 48}, {16, 56, 20, 44}, {13, 6, 2, 10}};      // (even sizes as the structs have them, and sizes that divide nothing)
+    const size_t sizes[][5] = {{12, 64, 24, 48, 64}, {16, 56, 20, 44, 40}, {13, 6, 2, 10, 7}};      // (even sizes as the structs have them, and sizes that divide nothing)
     const size_t pcm[] = {400, 401, 65535, 70001};
     const size_t in[] = {0, 1, 882, 883};
     const size_t raw[] = {0, 1, 15, 16, 17};
     const int frames[] = {1, 3};
     const int descs[] = {0, 1, 5};
     for (const auto &sz : sizes) {
-        S_FbankFrameDesc = sz[0]; S_ResampleDesc = sz[1]; S_DecodeDesc = sz[2]; S_VadDesc = sz[3];
+        S_FbankFrameDesc = sz[0]; S_ResampleDesc = sz[1]; S_DecodeDesc = sz[2]; S_VadDesc = sz[3]; S_DtmfDesc = sz[4];
         // every call on fresh buffers: all eight on/off combinations are among the descriptor counts {0, 1, 5}^3
         for (size_t n_pcm : pcm) for (size_t n_in : in) for (size_t n_raw : raw) for (int n_frames : frames)
             for (int n_rs : descs) for (int n_dc : descs) for (int n_vd : descs) {
@@ -99,6 +123,13 @@ int main()
                 n.call(n_frames, n_pcm, n_rs, n_in, n_dc, n_raw, n_vd);
                 compare(o, n);
                 CHECK(((n_pcm + (n_rs ? n_in : 0)) & 1) == 0 || n.lay.raw != (n_pcm + (n_rs ? n_in : 0)) * 2);      // (odd sample counts do leave a gap)
+                for (int n_dt : {1, 5}) {                // the same call with DTMF descriptors: nothing in front of them moves
+                    New d;
+                    d.call(n_frames, n_pcm, n_rs, n_in, n_dc, n_raw, n_vd, n_dt);
+                    check_dt(d, StagingCaps());
+                    CHECK(d.lay.raw == n.lay.raw && d.lay.frames == n.lay.frames && d.lay.rs == n.lay.rs && d.lay.dc == n.lay.dc && d.lay.vd == n.lay.vd);
+                    CHECK(d.lay.pcm_units == n.lay.pcm_units && d.caps.dt == 256 && d.units > n.units);
+                }
             }
         // one pair of buffers through a sequence of calls: passes come and go, counts cross the floors and the doubled capacities
         Old o; New n;
@@ -117,6 +148,26 @@ int main()
             regrows += o.regrew;
         }
         CHECK(regrows > 5);
+        // the same sweep with DTMF passes that come and go; calls without one must still upload what the old text uploaded
+        New d; Old od;
+        int dt_regrows = 0, dt_calls = 0;
+        for (int i = 0; i < 4000; ++i) {
+            const int scale = 1 << rnd(12);
+            const int n_frames = 1 + (int)rnd(3u * (unsigned)scale);
+            const size_t n_pcm = 1 + rnd(400u * (unsigned)scale);
+            const int n_rs = rnd(2) ? (int)rnd((unsigned)scale) : 0, n_dc = rnd(2) ? (int)rnd((unsigned)scale) : 0, n_vd = rnd(2) ? (int)rnd((unsigned)scale) : 0;
+            const int n_dt = rnd(2) ? 1 + (int)rnd((unsigned)scale) : 0;
+            const size_t n_in = rnd(900u * (unsigned)scale), n_raw = rnd(1700u * (unsigned)scale);
+            const StagingCaps before = d.caps;
+            d.call(n_frames, n_pcm, n_rs, n_in, n_dc, n_raw, n_vd, n_dt);
+            if (n_dt) { check_dt(d, before); ++dt_calls; dt_regrows += d.regrew && (size_t)n_dt > before.dt; }
+            else {
+                od.call(n_frames, n_pcm, n_rs, n_in, n_dc, n_raw, n_vd);
+                CHECK(od.woff == d.lay.raw && od.doff == d.lay.frames && od.roff == d.lay.rs && od.coff == d.lay.dc && od.voff == d.lay.vd && od.bytes == d.lay.bytes);
+                CHECK(d.lay.bytes <= d.units * 2);
+            }
+        }
+        CHECK(dt_calls > 1000 && dt_regrows > 2);
     }
     if (fails) { printf("%d of %ld checks FAILED\n", fails, checks); return 1; }
     printf("all checks passed (%ld)\n", checks);

@@ -1,5 +1,5 @@
-"""Worker for tests/test_gpu_dtmf.py: DTMF digits per session (aprilx_session_set_dtmf) and the kernel alone (aprilx_run_dtmf,
-aprilx_run_dtmf_decide), one scenario per process.  Prints one line "RESULT <json>".
+"""Worker for tests/test_gpu_dtmf.py: DTMF digits per session (aprilx_session_set_dtmf), beside voice activity in the same passes
+(mode "both"), and the kernel alone (aprilx_run_dtmf, aprilx_run_dtmf_decide), one scenario per process.  Prints one line "RESULT <json>".
 usage: dtmf_worker.py model.april mode [args ...]
 
 What the detector must give comes from the numpy statement of the contract (tests/dtmf_ref.py), never from the product; only the
@@ -21,6 +21,7 @@ from april_asr_amd import _ffi  # noqa: E402
 import dtmf_ref as R  # noqa: E402
 import input_format_ref as IF  # noqa: E402
 from vad_worker import Book, cuts, shift_ms_of  # noqa: E402
+from vad_worker import expected as vad_expected  # noqa: E402
 
 N_SET = (1, 3, 4, 5, 63, 64, 65, 257)            # around a workgroup's four waves, its 16 frames, and the frames one pass of 64 workgroups walks
 
@@ -269,6 +270,61 @@ def mode_rules(m):
     return out
 
 
+BOTH_BURSTS = [(0.15, 0.55), (0.9, 1.35)]        # two of vad_worker's bursts in 1.5 s ...
+BOTH_KEYS = [("7", 0.30), ("#", 0.66)]            # ... a key of 100 ms inside the first, and one between them that the flush falls into
+BOTH_FLUSH_AT = 0.70
+
+
+def mode_both(m):
+    """both detectors in the same passes: session 0 with VAD and DTMF, 1 with VAD, 2 with DTMF, 3 with neither, one group, the same samples.
+    A pass's DTMF bytes then sit behind its VAD bytes, and session 0's runs are at different offsets in the two parts"""
+    import vad_ref as V
+    sr, fft, shift, sh = geometry(m)
+    assert sr == 16000
+    _, mel = m.fbank_tables()
+    sig = V.burst_signal(1.5, BOTH_BURSTS, -50.0, 20.0, seed=50).astype(np.int32)
+    for d, at in BOTH_KEYS:
+        tone, onsets = R.digit_signal(d, 100, 0, sr, -200.0, seed=0, tail_ms=0)      # (the digit alone: noise far below one int16 step)
+        a = int(at * sr)
+        sig[a:a + sr // 10] += tone[onsets[0]:onsets[0] + sr // 10]
+    pcm = np.clip(sig, -32768, 32767).astype(np.int16)
+    vplan = V.make_plan(mel, sr, sh, V.options())
+    dplan = A.dtmf_plan(sr, fft, sh)
+    p, tab = plan_dict(dplan), A.dtmf_tables(sr, dplan.Wd)
+    runs = []
+    for vad, dtmf in ((True, True), (True, None), (None, True), (None, None)):
+        got = []
+        runs.append(Run(m, dtmf=dtmf, vad=vad, vad_callback=lambda e, got=got: got.append((e.kind, e.time_ms))))
+        runs[-1].vad = got
+    grp = A.SessionGroup([r.s for r in runs])
+    v0, d0 = m.vad_stats(), m.dtmf_stats()
+    book, seg_ends, stream, single = Book(m.dims), [], [], 0
+    cut_at = int(BOTH_FLUSH_AT * sr)
+    for si, (s0, s1) in enumerate([(0, cut_at), (cut_at, len(pcm))]):
+        bounds = cuts(s1 - s0, "irregular", sr // 10, seed=25 + si)      # (seeds whose cuts hold single-frame feeds in both segments)
+        for f0, f1 in zip(bounds[:-1], bounds[1:]):
+            single += int(f1 - f0 == shift)
+            grp.feed([pcm[s0 + f0:s0 + f1]] * len(runs))
+        grp.flush(); grp.drain()
+        book.feed(s1 - s0); book.flush()
+        seg_ends.append(int(book.frames))
+        stream += [pcm[s0:s1], np.zeros(6400, np.int16)]
+    rows = [r.s.frames() for r in runs]
+    if len(rows[0]) != len(book.real):
+        raise RuntimeError("the test's frame bookkeeping gives %d ring rows, the session wrote %d" % (len(book.real), len(rows[0])))
+    want_vad, _ = vad_expected(vplan, sh, rows[0][np.array(book.real)], seg_ends)
+    _, want_keys = expected(p, tab, sh, np.concatenate(stream), fft, shift, seg_ends)
+    v1, d1 = m.vad_stats(), m.dtmf_stats()
+    out = dict(vad=[r.vad for r in runs], keys=[r.keys for r in runs], want_vad=want_vad, want_keys=want_keys, single_frame_feeds=single,
+               events=[r.ev == runs[0].ev for r in runs], n_events=len(runs[0].ev), chunks=[r.s.chunks() for r in runs],
+               frames=[bool(x.shape == rows[0].shape and (x.view(np.uint32) == rows[0].view(np.uint32)).all()) for x in rows],
+               vad_frames=v1[1] - v0[1], dtmf_frames=d1[1] - d0[1], real=seg_ends[-1], launches=[v1[0] - v0[0], d1[0] - d0[0]],
+               mismatch=int(m.stats().replay_mismatch))
+    for r in runs:
+        r.s.close()
+    return out
+
+
 def main():
     path, mode = sys.argv[1], sys.argv[2]
     m = A.Model(path)
@@ -276,6 +332,8 @@ def main():
         res = mode_kernel(m)
     elif mode == "live":
         res = {c: mode_live(m, sys.argv[3], c) for c in sys.argv[4:]}
+    elif mode == "both":
+        res = mode_both(m)
     else:
         res = mode_rules(m)
     print("RESULT " + json.dumps(res))

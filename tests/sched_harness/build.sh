@@ -7,5 +7,5 @@ C=april_asr_amd/csrc
 OUT=$2
 mkdir -p "$(dirname "$OUT")"
 $CXX -std=c++17 -O1 -g -fno-omit-frame-pointer $1 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I$C -Wno-unused-result \
-    $C/session.cc $C/april_api.cc $C/model_loader.cc $C/onnx_reader.cc $C/fbank_tables.cc tests/sched_harness/fake_engine.cc tests/sched_harness/driver.cc \
+    $C/session.cc $C/april_api.cc $C/vad_api.cc $C/dtmf_api.cc $C/model_loader.cc $C/onnx_reader.cc $C/fbank_tables.cc tests/sched_harness/fake_engine.cc tests/sched_harness/driver.cc \
     -lpthread -o "$OUT"

@@ -1,7 +1,9 @@
 // Drives the REAL host runtime (csrc/april_api.cc + session.cc + host_pool.h + loader) against tests/sched_harness/fake_engine.cc
 // through the C ABI only, in the scenarios of tests/test_gpu_pipeline.py / test_gpu_concurrency.py: lock-step and pipelined group
 // feeds, asynchronous sessions, many client threads with their own synchronous sessions, sessions created and freed while others
-// stream, frees from inside result handlers, queue overflow, irregular feed sizes, a long feed beside short ones.  Built with
+// stream, frees from inside result handlers, queue overflow, irregular feed sizes, a long feed beside short ones.  A fixed share of the sessions
+// opts into voice activity, DTMF, both or neither (the fake engine lends their passes a block of bytes that follow from the samples):
+// their events are part of a session's digest, under tags of their own.  Built with
 // -fsanitize=thread and with -fsanitize=address,undefined by tests/test_sched_sanitizers.py; exits non-zero on any inconsistency
 // (the sanitizers abort on their own findings).
 // usage: driver model.april
@@ -24,8 +26,14 @@ struct Sess {
     AprilASRSession h = nullptr;
     uint64_t digest = 1469598103934665603ull;
     int calls = 0, tokens = 0, cant_keep_up = 0;
+    int det = 0, vad_events = 0, dtmf_events = 0;      // det: bit 0 voice activity, bit 1 DTMF
     std::vector<short> pcm;
-    void mix(const void *p, size_t n) { const unsigned char *b = (const unsigned char *)p; for (size_t i = 0; i < n; ++i) { digest ^= b[i]; digest *= 1099511628211ull; } }
+    // the events of each detector in their own order: WHERE they fall between the token events depends on how much audio a flight took
+    // in (they are delivered in front of the token events of the flight that cut their frames), which the ingest modes do not share
+    uint64_t vad_digest = 1469598103934665603ull, dtmf_digest = 1469598103934665603ull;
+    static void mix_into(uint64_t &d, const void *p, size_t n) { const unsigned char *b = (const unsigned char *)p; for (size_t i = 0; i < n; ++i) { d ^= b[i]; d *= 1099511628211ull; } }
+    void mix(const void *p, size_t n) { mix_into(digest, p, n); }
+    uint64_t total() const { uint64_t d = digest; mix_into(d, &vad_digest, sizeof vad_digest); mix_into(d, &dtmf_digest, sizeof dtmf_digest); return d; }
 };
 
 static void handler(void *ud, AprilResultType type, size_t count, const AprilToken *toks)
@@ -43,6 +51,22 @@ static void handler(void *ud, AprilResultType type, size_t count, const AprilTok
     }
 }
 
+// detector events: a tag no AprilResultType has, so that no token event can stand in for one
+static void vad_handler(void *ud, int kind, uint64_t ms)
+{
+    Sess *s = (Sess *)ud;
+    const int tag = 0x56414400 + kind;
+    Sess::mix_into(s->vad_digest, &tag, sizeof tag); Sess::mix_into(s->vad_digest, &ms, sizeof ms);
+    s->vad_events++;
+}
+static void dtmf_handler(void *ud, int kind, char digit, uint64_t ms)
+{
+    Sess *s = (Sess *)ud;
+    const int tag = 0x44544d00 + kind;
+    Sess::mix_into(s->dtmf_digest, &tag, sizeof tag); Sess::mix_into(s->dtmf_digest, &digit, 1); Sess::mix_into(s->dtmf_digest, &ms, sizeof ms);
+    s->dtmf_events++;
+}
+
 static std::vector<short> lcg_pcm(size_t n, unsigned seed)
 {
     std::vector<short> v(n);
@@ -51,7 +75,9 @@ static std::vector<short> lcg_pcm(size_t n, unsigned seed)
     return v;
 }
 
-static Sess *make(AprilASRModel m, unsigned seed, size_t samples, int flags)
+// `det`: the detectors the session opts into, with the shortest onset / tone / pause the options allow: the fake engine's bytes are
+// hash-like, and every run of them must give events
+static Sess *make(AprilASRModel m, unsigned seed, size_t samples, int flags, int det = 0)
 {
     Sess *s = new Sess();
     s->pcm = lcg_pcm(samples, seed);
@@ -59,15 +85,25 @@ static Sess *make(AprilASRModel m, unsigned seed, size_t samples, int flags)
     cfg.handler = handler; cfg.userdata = s; cfg.flags = (AprilConfigFlagBits)flags;
     s->h = aas_create_session(m, cfg);
     if (!s->h) { fprintf(stderr, "aas_create_session failed\n"); exit(2); }
+    s->det = det;
+    if (det & 1) {
+        const AprilxVadOptions o = {(uint32_t)sizeof(AprilxVadOptions), 200.0f, 4000.0f, 5.0f, 3.0f, 10u, 10u, -12.0f, 0u};
+        if (aprilx_session_set_vad(s->h, &o, vad_handler, s) != 0) { fprintf(stderr, "aprilx_session_set_vad failed\n"); exit(2); }
+    }
+    if (det & 2) {
+        const AprilxDtmfOptions o = {(uint32_t)sizeof(AprilxDtmfOptions), -40.0f, 4.0f, 8.0f, 8.0f, 0.6f, 10u, 10u, 0u};
+        if (aprilx_session_set_dtmf(s->h, &o, dtmf_handler, s) != 0) { fprintf(stderr, "aprilx_session_set_dtmf failed\n"); exit(2); }
+    }
     return s;
 }
 
-// one pass over nsess sessions x steps feeds of `feed` samples in an ingest mode; returns the per-session digests
+// one pass over nsess sessions x steps feeds of `feed` samples in an ingest mode; returns the per-session digests.  Session i opts into
+// the detectors i & 3 (neither, voice activity, DTMF, both), here and wherever a session is compared with session i of such a pass
 enum Mode { LOCKSTEP, PIPE2, ASYNC_PIPE2, THREADS };
 static std::vector<uint64_t> stream(AprilASRModel m, int nsess, int steps, size_t feed, Mode mode, int *calls_out = nullptr)
 {
     std::vector<Sess *> ss;
-    for (int i = 0; i < nsess; ++i) ss.push_back(make(m, 4242u + (unsigned)i, feed * (size_t)steps, mode == ASYNC_PIPE2 ? APRIL_CONFIG_FLAG_ASYNC_NO_RT_BIT : 0));
+    for (int i = 0; i < nsess; ++i) ss.push_back(make(m, 4242u + (unsigned)i, feed * (size_t)steps, mode == ASYNC_PIPE2 ? APRIL_CONFIG_FLAG_ASYNC_NO_RT_BIT : 0, i & 3));
     std::vector<AprilASRSession> hs; for (Sess *s : ss) hs.push_back(s->h);
     std::vector<const short *> ptr((size_t)nsess); std::vector<size_t> cnt((size_t)nsess, feed);
     if (mode == THREADS) {
@@ -109,7 +145,12 @@ static std::vector<uint64_t> stream(AprilASRModel m, int nsess, int steps, size_
     }
     std::vector<uint64_t> d;
     int calls = 0;
-    for (Sess *s : ss) { d.push_back(s->digest); calls += s->calls; CHECK(s->cant_keep_up == 0, "unexpected CANT_KEEP_UP"); }
+    for (Sess *s : ss) {
+        d.push_back(s->total()); calls += s->calls; CHECK(s->cant_keep_up == 0, "unexpected CANT_KEEP_UP");
+        // an opted-in session heard something of every kind it asked for, and nobody heard what they did not ask for
+        CHECK((s->vad_events > 0) == ((s->det & 1) != 0), "detectors %d: %d voice-activity events", s->det, s->vad_events);
+        CHECK((s->dtmf_events > 0) == ((s->det & 2) != 0), "detectors %d: %d DTMF events", s->det, s->dtmf_events);
+    }
     if (calls_out) *calls_out = calls;
     for (Sess *s : ss) { aas_free(s->h); delete s; }
     return d;
@@ -154,16 +195,16 @@ int main(int argc, char **argv)
         std::vector<uint64_t> got(4 * 5, 0);
         for (int t = 0; t < 4; ++t) th.emplace_back([&, t] {
             std::vector<Sess *> mine;
-            for (int i = 0; i < 5; ++i) mine.push_back(make(m, 4242u + (unsigned)(t * 5 + i), 1600 * (size_t)STEPS, 0));
+            for (int i = 0; i < 5; ++i) mine.push_back(make(m, 4242u + (unsigned)(t * 5 + i), 1600 * (size_t)STEPS, 0, (t * 5 + i) & 3));
             for (int k = 0; k < STEPS; ++k) for (Sess *s : mine) aas_feed_pcm16(s->h, s->pcm.data() + (size_t)k * 1600, 1600);
             for (Sess *s : mine) aas_flush(s->h);
-            for (int i = 0; i < 5; ++i) { got[(size_t)(t * 5 + i)] = mine[(size_t)i]->digest; aas_free(mine[(size_t)i]->h); delete mine[(size_t)i]; }
+            for (int i = 0; i < 5; ++i) { got[(size_t)(t * 5 + i)] = mine[(size_t)i]->total(); aas_free(mine[(size_t)i]->h); delete mine[(size_t)i]; }
         });
         for (int t = 0; t < 2; ++t) th.emplace_back([&, t] {
             unsigned n = 0;
             while (!stop.load()) {
                 ++n;
-                Sess *s = make(m, 9000u + (unsigned)t * 1000u + n, 4800, (n & 1) ? APRIL_CONFIG_FLAG_ASYNC_NO_RT_BIT : 0);
+                Sess *s = make(m, 9000u + (unsigned)t * 1000u + n, 4800, (n & 1) ? APRIL_CONFIG_FLAG_ASYNC_NO_RT_BIT : 0, (int)(n >> 1) & 3);
                 aas_feed_pcm16(s->h, s->pcm.data(), 3200);
                 if (n % 3 == 0) aas_flush(s->h);
                 aas_free(s->h);                     // (an asynchronous session may still have work queued: aas_free waits for it)
@@ -183,10 +224,10 @@ int main(int argc, char **argv)
         std::vector<uint64_t> got(12, 0);
         for (int t = 0; t < 3; ++t) th.emplace_back([&, t] {
             std::vector<Sess *> mine;
-            for (int i = 0; i < 4; ++i) mine.push_back(make(m, 4242u + (unsigned)(t * 4 + i), 1600 * (size_t)STEPS, 0));
+            for (int i = 0; i < 4; ++i) mine.push_back(make(m, 4242u + (unsigned)(t * 4 + i), 1600 * (size_t)STEPS, 0, (t * 4 + i) & 3));
             for (int k = 0; k < STEPS; ++k) for (Sess *s : mine) aas_feed_pcm16(s->h, s->pcm.data() + (size_t)k * 1600, 1600);
             for (Sess *s : mine) aas_flush(s->h);
-            for (int i = 0; i < 4; ++i) { got[(size_t)(t * 4 + i)] = mine[(size_t)i]->digest; aas_free(mine[(size_t)i]->h); delete mine[(size_t)i]; }
+            for (int i = 0; i < 4; ++i) { got[(size_t)(t * 4 + i)] = mine[(size_t)i]->total(); aas_free(mine[(size_t)i]->h); delete mine[(size_t)i]; }
         });
         std::vector<uint64_t> second;
         th.emplace_back([&] {

@@ -14,13 +14,18 @@
 //     joiner results that depend only on the session's own time line -- so the device flags the scheduler replays against are
 //     exactly consistent (replay_mismatch must stay 0) and the callbacks of a session do not depend on the ingest mode;
 //   * fbank() reads every staged PCM window (a lent caller buffer that was freed or changed too early is an ASan / TSan report)
-//     and checks the frame descriptors against the staged range, and a pass's counts and spans against each other.
+//     and checks the frame descriptors against the staged range, and a pass's counts and spans against each other;
+//   * a pass with VAD or DTMF descriptors is lent a heap block of exactly its bytes (VAD, then DTMF), allocated for the pass and freed
+//     when the scheduler gives it back -- a read past its end or after its release is an ASan report.  Every byte comes from a hash of
+//     the frame's own first two staged samples, so a session's detector events do not depend on the ingest mode either.  A block that
+//     is released without having been lent (or twice), lent while it is lent, or still lent when the engine goes, aborts.
 #include <atomic>
 #include <chrono>
 #include <cstring>
 #include <map>
 #include <memory>
 #include <random>
+#include <set>
 #include <thread>
 #include "engine.h"
 #include "session.h"
@@ -43,6 +48,7 @@ struct FakeState {
     int delay_lo = 20, delay_hi = 400;
     std::atomic<uint64_t> pcm_sum{0};
     uint64_t frames = 0, steps = 0;
+    std::set<const uint8_t *> lent;             // the pass blocks the scheduler holds
 };
 std::mutex g_mu;
 std::map<const Engine *, std::unique_ptr<FakeState>> g_state;
@@ -94,6 +100,7 @@ Engine::Engine(const EngineConfig &cfg, const PackedLayout &layout, const float 
 Engine::~Engine()
 {
     delete[] rec_h_; delete[] rec_off_h_; delete[] w_;
+    if (!st(this).lent.empty()) { LOGE("fake engine: %zu pass block(s) still lent when the engine is destroyed", st(this).lent.size()); abort(); }
     std::lock_guard<std::mutex> g(g_mu);
     g_state.erase(this);
 }
@@ -132,21 +139,64 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
     const size_t total = read_all(parts, n_parts);
     if (total != n_pcm) { LOGE("fake engine: fbank: windows hold %zu samples, caller says %zu", total, n_pcm); abort(); }
     // a pass without descriptors carries nothing, and its spans hold what the caller says they hold
-    if (pass.n_rs < 0 || pass.n_dc < 0 || pass.n_vd < 0 || (!pass.n_rs && (pass.n_in_parts || pass.n_in)) || (!pass.n_dc && (pass.n_raw_parts || pass.n_raw)) ||
-        (!pass.n_vd && pass.vad_bytes) || (pass.n_rs && (!pass.rs || !pass.rs_specs)) || (pass.n_dc && !pass.dc) || (pass.n_vd && !pass.vd) ||
+    if (pass.n_rs < 0 || pass.n_dc < 0 || pass.n_vd < 0 || pass.n_dt < 0 || (!pass.n_rs && (pass.n_in_parts || pass.n_in)) || (!pass.n_dc && (pass.n_raw_parts || pass.n_raw)) ||
+        (!pass.n_vd && pass.vad_bytes) || (!pass.n_dt && pass.dtmf_bytes) || (pass.n_rs && (!pass.rs || !pass.rs_specs)) || (pass.n_dc && !pass.dc) || (pass.n_vd && !pass.vd) ||
+        (pass.n_dt && !pass.dt) ||
         read_all(pass.in_parts, pass.n_in_parts) != pass.n_in || read_all(pass.raw_parts, pass.n_raw_parts) != pass.n_raw) {
         LOGE("fake engine: fbank: inconsistent front-end pass"); abort();
     }
     size_t vad_rows = 0;
     for (int i = 0; i < pass.n_vd; ++i) vad_rows += (size_t)pass.vd[i].n;
     if (vad_rows != pass.vad_bytes) { LOGE("fake engine: fbank: VAD descriptors cover %zu rows, caller says %zu", vad_rows, pass.vad_bytes); abort(); }
+    size_t dtmf_rows = 0;
+    for (int i = 0; i < pass.n_dt; ++i) dtmf_rows += (size_t)pass.dt[i].n;
+    if (dtmf_rows != pass.dtmf_bytes) { LOGE("fake engine: fbank: DTMF descriptors cover %zu frames, caller says %zu", dtmf_rows, pass.dtmf_bytes); abort(); }
     for (int i = 0; i < n_frames; ++i) {
         if (desc[i].slot < 0 || desc[i].slot >= cfg_.max_slots || desc[i].ring_row < 0 || desc[i].ring_row >= ring_frames_) { LOGE("fake engine: fbank: bad descriptor"); abort(); }
         if (desc[i].pcm_off >= 0 && (size_t)desc[i].pcm_off + (size_t)1 > n_pcm) { LOGE("fake engine: fbank: frame window outside the staged samples"); abort(); }
     }
     f.pcm_sum.fetch_add(sum, std::memory_order_relaxed);
     f.frames += (uint64_t)n_frames;
-    return nullptr;
+    if (!pass.n_vd && !pass.n_dt) return nullptr;
+    // the pass's block: one byte per frame of every run, from the frame's own samples; every byte written exactly once
+    std::vector<int16_t> flat;
+    flat.reserve(n_pcm);
+    for (size_t p = 0; p < n_parts; ++p)
+        if (parts[p].first) flat.insert(flat.end(), parts[p].first, parts[p].first + parts[p].second); else flat.resize(flat.size() + parts[p].second, 0);
+    const size_t bytes = pass.vad_bytes + pass.dtmf_bytes;
+    uint8_t *block = new uint8_t[bytes];
+    std::vector<uint8_t> written(bytes, 0);
+    auto put = [&](size_t at, int frame, bool dtmf) {
+        if (desc[frame].pcm_off < 0) { LOGE("fake engine: fbank: a padding row inside a %s run", dtmf ? "DTMF" : "VAD"); abort(); }
+        if (at >= bytes || written[at]++) { LOGE("fake engine: fbank: %s runs overlap or leave their part of the block", dtmf ? "DTMF" : "VAD"); abort(); }
+        const size_t o = (size_t)desc[frame].pcm_off;
+        const uint32_t h = mix((uint16_t)flat[o], o + 1 < flat.size() ? (uint16_t)flat[o + 1] : 0u, 5u);
+        block[at] = dtmf ? (uint8_t)((h >> 8) % 17u) : (uint8_t)(h & 3u);
+    };
+    for (int i = 0; i < pass.n_vd; ++i) {        // (a VAD descriptor names ring rows: its frames are the run that starts at that row of that slot)
+        const VadDesc &v = pass.vd[i];
+        int first = 0;
+        while (first < n_frames && !(desc[first].slot == v.slot && desc[first].ring_row == v.first_row && desc[first].pcm_off >= 0)) ++first;
+        if (v.n <= 0 || first + v.n > n_frames || v.out_off < 0 || (size_t)v.out_off + (size_t)v.n > pass.vad_bytes) { LOGE("fake engine: fbank: VAD descriptor %d outside the pass", i); abort(); }
+        for (int k = 0; k < v.n; ++k) {
+            if (desc[first + k].slot != v.slot) { LOGE("fake engine: fbank: VAD run %d crosses sessions", i); abort(); }
+            put((size_t)v.out_off + (size_t)k, first + k, false);
+        }
+    }
+    for (int i = 0; i < pass.n_dt; ++i) {
+        const DtmfDesc &t = pass.dt[i];
+        if (t.n <= 0 || t.first < 0 || t.first + t.n > n_frames || t.out_off < 0 || (size_t)t.out_off + (size_t)t.n > pass.dtmf_bytes) { LOGE("fake engine: fbank: DTMF descriptor %d outside the pass", i); abort(); }
+        for (int k = 0; k < t.n; ++k) put(pass.vad_bytes + (size_t)t.out_off + (size_t)k, t.first + k, true);
+    }
+    for (size_t i = 0; i < bytes; ++i) if (!written[i]) { LOGE("fake engine: fbank: byte %zu of the pass's block belongs to no run", i); abort(); }
+    if (!f.lent.insert(block).second) { LOGE("fake engine: fbank: a lent block lent again"); abort(); }
+    return block;
+}
+
+void Engine::release_pass_block(const uint8_t *p)
+{
+    if (!st(this).lent.erase(p)) { LOGE("fake engine: a pass block released that is not lent (never lent, or released twice)"); abort(); }
+    delete[] p;
 }
 
 void Engine::begin_flight()
@@ -280,6 +330,9 @@ void Engine::debug_decoder(int, const int64_t *, float *) { abort(); }
 void Engine::debug_joiner(int, const float *, const float *, float *) { abort(); }
 void Engine::debug_decide(const DecideRequest &) { abort(); }
 void Engine::debug_fbank(int, const int16_t *, float *) { abort(); }
+void Engine::debug_vad(int, const VadPlan *, const int32_t *, const int32_t *, int, const float *, VadState *, uint8_t *, float *) { abort(); }
+void Engine::debug_dtmf(int, const DtmfPlan *, const int32_t *, const int16_t *, uint8_t *, float *) { abort(); }
+void Engine::debug_dtmf_decide(const DtmfPlan &, int, const float *, uint8_t *) { abort(); }
 
 // planner entry points of the kernel files that april_api.cc exposes for CPU-side tests: not part of this harness
 int recur_form(const GemmArgs &) { return 0; }

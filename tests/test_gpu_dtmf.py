@@ -1,7 +1,8 @@
 """DTMF digits per session (aprilx_session_set_dtmf): dtmf_kernel against the numpy statement of the contract
 (tests/dtmf_ref.py), every bit of the codes and the nine powers; live sessions in every ingest mode, whose events must be the statement
 applied to the session's own samples; formatted streams (mu-law at 8 kHz, channel 1 of two) that must give the same keys; a twin
-without the detector, which must not differ in anything; and an engine without an opted-in session, which must launch nothing.
+without the detector, which must not differ in anything; sessions with both detectors, with one and with none in the same passes; and
+an engine without an opted-in session, which must launch nothing.
 Every scenario runs in a child process (tests/dtmf_worker.py)."""
 import json
 import os
@@ -94,3 +95,20 @@ def test_rules_and_costs_nothing_when_unused(built, tiny_model):
     assert r["after_flush"] == 0 and r["counters_restart"] == [0, 0, r["frames_seen"], 2], r
     assert r["off"] is None and r["off_launches_nothing"], r
     assert r["profiled_ms"] > 0 and r["profiled_digits"] == "159D" and r["mismatch"] == 0, r
+
+
+def test_both_detectors_in_the_same_passes(built, tiny_model):
+    """four sessions of one group on the same 1.5 s (two bursts, a key inside the first and a key between them that the flush falls into;
+    irregular feeds): VAD and DTMF, VAD only, DTMF only, neither.  The passes carry descriptors of both kinds, so their DTMF bytes sit
+    behind their VAD bytes; the session with both must hear what the single-detector sessions hear, which is what the two numpy
+    statements give, and nobody's transcript may move"""
+    r = run(tiny_model["path"], "both")
+    both, vad_only, dtmf_only, neither = range(4)
+    assert r["mismatch"] == 0 and r["single_frame_feeds"] >= 1, r["single_frame_feeds"]
+    assert len(r["want_vad"]) >= 2 and r["vad"][both] == r["vad"][vad_only] == r["want_vad"], (r["vad"][:2], r["want_vad"])
+    assert len(r["want_keys"]) >= 4 and r["keys"][both] == r["keys"][dtmf_only] == r["want_keys"], (r["keys"][::2], r["want_keys"])
+    assert r["vad"][dtmf_only] == r["vad"][neither] == [] and r["keys"][vad_only] == r["keys"][neither] == [], r
+    assert all(r["events"]) and all(r["frames"]) and r["n_events"] >= 2, r
+    assert len(set(r["chunks"])) == 1 and r["chunks"][0] >= 5, r["chunks"]
+    # two sessions opted into each detector: the same frames under both kernels
+    assert r["vad_frames"] == r["dtmf_frames"] == 2 * r["real"] and min(r["launches"]) > 0, r

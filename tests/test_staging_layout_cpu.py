@@ -1,6 +1,7 @@
 """The layout of Engine::fbank()'s staging buffer (csrc/staging_layout.h) as a stand-alone program under AddressSanitizer + UBSan
 (tests/cpp/staging_layout_test.cc): offsets, upload length, regrow condition and capacities against the formulas the function replaced,
-restated literally in the program, for all eight on/off combinations of the resample / decode / VAD passes."""
+restated literally in the program, for all eight on/off combinations of the resample / decode / VAD passes; the DTMF array, which those
+formulas did not know, against what the layout promises for it, and calls without it against the formulas unchanged."""
 import os
 import subprocess
 
