@@ -21,7 +21,8 @@ import numpy as np
 from . import _ffi
 
 __all__ = ["Result", "Token", "Model", "Session", "SessionGroup", "Bias", "VadEvent", "resampler_taps", "decode_host", "vad_plan", "vad_host", "vad_events_host",
-           "DtmfEvent", "dtmf_plan", "dtmf_tables", "dtmf_host", "dtmf_decide_host", "dtmf_events_host"]
+           "DtmfEvent", "dtmf_plan", "dtmf_tables", "dtmf_host", "dtmf_decide_host", "dtmf_events_host",
+           "ToneEvent", "tone_plan", "tone_tables", "tone_host", "tone_decide_host", "tone_events_host", "tone_name"]
 
 
 class Result(IntEnum):
@@ -64,6 +65,27 @@ class DtmfEvent:
 
     def __repr__(self):
         return "DtmfEvent(%s, %r, %d)" % ("DOWN" if self.kind == 1 else "UP", self.digit, self.time_ms)
+
+
+class ToneEvent:
+    """A tone event of a session (Session(tones=...)): `kind` is ToneEvent.ON or ToneEvent.OFF, `f1_hz` and `f2_hz` the measured
+    frequencies (a single tone: f2_hz == 0; a pair: f1_hz < f2_hz), `time_ms` the position in the session's audio on the frame clock
+    (DESIGN.md section 18).  `name` is tone_name() of the frequencies: "dial", "busy", "cp425", "cng", "ced", "sit1".."sit3" or None."""
+    ON, OFF = 1, 2
+    __slots__ = ("kind", "f1_hz", "f2_hz", "time_ms")
+
+    def __init__(self, kind, f1_hz, f2_hz, time_ms):
+        self.kind, self.f1_hz, self.f2_hz, self.time_ms = int(kind), int(f1_hz), int(f2_hz), int(time_ms)
+
+    @property
+    def name(self):
+        return tone_name(self.f1_hz, self.f2_hz)
+
+    def __eq__(self, other):
+        return isinstance(other, ToneEvent) and (self.kind, self.f1_hz, self.f2_hz, self.time_ms) == (other.kind, other.f1_hz, other.f2_hz, other.time_ms)
+
+    def __repr__(self):
+        return "ToneEvent(%s, %d, %d, %d)" % ("ON" if self.kind == 1 else "OFF", self.f1_hz, self.f2_hz, self.time_ms)
 
 
 class Token:
@@ -394,6 +416,33 @@ class Model:
             raise ValueError("aprilx_run_dtmf_decide refused its arguments")
         return codes
 
+    def run_tones(self, options, frames_list, powers: bool = True):
+        """tone_kernel alone (aprilx_run_tones; tests): run r with options[r] (dicts / True as Session.set_tones) over frames_list[r]
+        [n][fft_size] int16, all in ONE launch.  Returns ([records [n][2] uint16], [powers [n][F + 1]])."""
+        k = len(frames_list)
+        opts = (_ffi.AprilxToneOptions * k)(*[_tone_options(o) for o in options])
+        n = np.array([len(f) for f in frames_list], np.int32)
+        fr = np.ascontiguousarray(np.concatenate([np.asarray(f, np.int16).reshape(len(f), -1) for f in frames_list]), np.int16)
+        plan = tone_plan(self.dims.sample_rate, self.dims.fft_size, max(1, self.dims.frame_shift * 1000 // self.dims.sample_rate), options[0])
+        rec = np.zeros((int(n.sum()), 2), np.uint16); pw = np.zeros((int(n.sum()), plan.F + 1), np.float32)
+        if self._L.aprilx_run_tones(self._handle, C.addressof(opts), k, n.ctypes.data, fr.ctypes.data, rec.ctypes.data, pw.ctypes.data if powers else None) != 0:
+            raise ValueError("aprilx_run_tones refused its arguments")
+        cuts = np.cumsum(n)[:-1]
+        return np.split(rec, cuts), np.split(pw, cuts)
+
+    def run_tone_decide(self, options, powers):
+        """the kernel's decision alone on given rows [n][F + 1] of P[0..F), E (aprilx_run_tone_decide; tests): records [n][2] uint16"""
+        q = np.ascontiguousarray(powers, np.float32)
+        q = q.reshape(len(q), -1)
+        rec = np.zeros((len(q), 2), np.uint16)
+        if self._L.aprilx_run_tone_decide(self._handle, C.byref(_tone_options(options)), len(q), q.ctypes.data, rec.ctypes.data) != 0:
+            raise ValueError("aprilx_run_tone_decide refused its arguments")
+        return rec
+
+    def tone_stats(self, device_index: int = 0):
+        """(launches, frames, ms): tone launches of one GPU's engine, the frames they covered, and (while profiling) the kernel's time"""
+        return self._detector_stats(self._L.aprilx_model_tone_stats, device_index)
+
     def _detector_stats(self, entry, device_index):
         l, f, ms = C.c_uint64(0), C.c_uint64(0), C.c_double(0)
         if entry(self._handle, device_index, C.byref(l), C.byref(f), C.byref(ms)) != 0:
@@ -515,12 +564,21 @@ def _dispatch_dtmf(userdata, kind, digit, time_ms):
 _DTMF_HANDLER = _ffi.DTMF_HANDLER(_dispatch_dtmf)
 
 
+def _dispatch_tone(userdata, kind, f1_hz, f2_hz, time_ms):
+    sess = C.cast(userdata, C.py_object).value
+    if sess.tone_callback is not None:
+        sess.tone_callback(ToneEvent(kind, f1_hz, f2_hz, time_ms))
+
+
+_TONE_HANDLER = _ffi.TONE_HANDLER(_dispatch_tone)
+
+
 class Session:
     def __init__(self, model: Model, callback: Callable[[Result, List[Token]], None], asynchronous: bool = False,
                  no_rt: bool = False, speaker_name: str = "", raw_events: bool = False, counters=None, input_sample_rate=None,
                  alternatives=None, bias=None, endpoint_silence_ms=None, blank_penalty=None, max_utterance_ms=None,
                  input_format=None, channels: int = 1, channel: int = 0, vad=None, vad_callback=None,
-                 dtmf=None, dtmf_callback=None):
+                 dtmf=None, dtmf_callback=None, tones=None, tone_callback=None):
         """`counters`: a uint64 ndarray of 6 entries; when given, results are only counted by a C handler inside the
         library (calls, partial, final, cant_keep_up, silence, tokens) and `callback` is never invoked.
         `input_sample_rate`: the rate of the PCM this session will receive (converted to the model's rate on the GPU); None: the
@@ -534,8 +592,11 @@ class Session:
         `vad`, `vad_callback`: True or a dict of options (set_vad) switches the voice-activity detector on; `vad_callback` receives one
         VadEvent per speech start / end, on the thread that delivers the session's results.
         `dtmf`, `dtmf_callback`: True or a dict of options (set_dtmf) switches the DTMF detector on; `dtmf_callback` receives one DtmfEvent
-        per key down / key up, on the same thread."""
+        per key down / key up, on the same thread.
+        `tones`, `tone_callback`: True or a dict of options (set_tones) switches the tone detector on; `tone_callback` receives one ToneEvent
+        per tone on / tone off, on the same thread."""
         self.dtmf_callback = dtmf_callback
+        self.tone_callback = tone_callback
         self._L = model._L
         self.vad_callback = vad_callback
         self.info_log = None      # tests: a list that receives (type, [the token's AprilxTokenInfo as bytes, or None]) per result
@@ -573,6 +634,32 @@ class Session:
             self.set_vad(vad)
         if dtmf:
             self.set_dtmf(dtmf)
+        if tones:
+            self.set_tones(tones)
+
+    def set_tones(self, options=True, callback=None) -> None:
+        """Tone events for this session (aprilx_session_set_tones): True for the defaults, or a dict with any of
+        min_level_dbfs, second_db, min_share, tol_hz, min_tone_ms, min_pause_ms; None / False switches it off.  `callback` replaces the
+        session's tone_callback.  Allowed right after creation and after a completed flush; the machine and its counters start afresh."""
+        if callback is not None:
+            self.tone_callback = callback
+        if not options:
+            rc = self._L.aprilx_session_set_tones(self._handle, None, C.cast(None, _ffi.TONE_HANDLER), None)
+        else:
+            rc = self._L.aprilx_session_set_tones(self._handle, C.byref(_tone_options(options)), _TONE_HANDLER, id(self))
+        if rc != 0:
+            raise ValueError("tone options %r refused (a value out of range, a model the detector refuses, or audio fed since the last flush)" % (options,))
+
+    def tone_info(self):
+        """None when the detector is off, else a dict: the options, W, k_lo, F, on_frames, off_frames, frames_seen, tonal_frames, tones,
+        held (the (f1_hz, f2_hz) held after the last frame, or None) (aprilx_session_tones).  Waits for the session to be idle."""
+        o, i = _ffi.AprilxToneOptions(), _ffi.AprilxToneInfo()
+        if self._L.aprilx_session_tones(self._handle, C.byref(o), C.byref(i)) != 1:
+            return None
+        d = {n: getattr(o, n) for n in _TONE_FIELDS}
+        d.update({n: int(getattr(i, n)) for n in ("W", "k_lo", "F", "on_frames", "off_frames", "frames_seen", "tonal_frames", "tones")})
+        d["held"] = (int(i.held_f1), int(i.held_f2)) if i.held_f1 else None
+        return d
 
     def set_dtmf(self, options=True, callback=None) -> None:
         """DTMF digits for this session (aprilx_session_set_dtmf): True for the defaults, or a dict with any of
@@ -883,6 +970,74 @@ def _vad_options(options):
 
 def _dtmf_options(options):
     return _detector_options(options, _ffi.AprilxDtmfOptions, _DTMF_FIELDS, _DTMF_DEFAULTS, "DTMF")
+
+
+_TONE_FIELDS = ("min_level_dbfs", "second_db", "min_share", "tol_hz", "min_tone_ms", "min_pause_ms")
+_TONE_DEFAULTS = dict(min_level_dbfs=-40.0, second_db=10.0, min_share=0.7, tol_hz=20, min_tone_ms=60, min_pause_ms=30)
+
+
+def _tone_options(options):
+    return _detector_options(options, _ffi.AprilxToneOptions, _TONE_FIELDS, _TONE_DEFAULTS, "tone")
+
+
+def tone_plan(sample_rate: int, fft_size: int, frame_shift_ms: int, options=True):
+    """The detector's plan (AprilxTonePlan) of a model with this rate, fft size and frame shift, on the host (aprilx_tone_plan);
+    ValueError when the options or the model are refused."""
+    plan = _ffi.AprilxTonePlan()
+    if _ffi.lib().aprilx_tone_plan(int(sample_rate), int(fft_size), int(frame_shift_ms), C.byref(_tone_options(options)), C.byref(plan)) != 0:
+        raise ValueError("tone options %r refused" % (options,))
+    return plan
+
+
+def tone_tables(sample_rate: int, fft_size: int):
+    """The detector's tables [2F][W] float32 (aprilx_tone_tables): row k cos, row F + k sin of bin k_lo + k"""
+    plan = tone_plan(sample_rate, fft_size, 10)
+    t = np.zeros((2 * plan.F, plan.W), np.float32)
+    if _ffi.lib().aprilx_tone_tables(int(sample_rate), int(fft_size), t.ctypes.data, t.size) != t.size:
+        raise ValueError("aprilx_tone_tables refused its arguments")
+    return t
+
+
+def tone_host(plan, tables, frames):
+    """The contract on the host (aprilx_tone_host): frames [n][>= W] int16 -> (records [n][2] uint16, powers [n][F + 1] float32)"""
+    f = np.ascontiguousarray(frames, np.int16)
+    f = f.reshape(len(f), -1)
+    t = np.ascontiguousarray(tables, np.float32)
+    assert t.shape == (2 * plan.F, plan.W)
+    rec = np.zeros((len(f), 2), np.uint16); pw = np.zeros((len(f), plan.F + 1), np.float32)
+    if _ffi.lib().aprilx_tone_host(C.byref(plan), t.ctypes.data, len(f), f.ctypes.data, f.shape[1] if len(f) else plan.W, rec.ctypes.data, pw.ctypes.data) != 0:
+        raise ValueError("aprilx_tone_host refused its arguments")
+    return rec, pw
+
+
+def tone_decide_host(plan, powers):
+    """steps 3-7 on one row of P[0..F), E (aprilx_tone_decide_host): the record (f1_hz, f2_hz)"""
+    q = np.ascontiguousarray(powers, np.float32)
+    assert q.shape == (plan.F + 1,)
+    r = int(_ffi.lib().aprilx_tone_decide_host(C.byref(plan), q.ctypes.data))
+    if r < 0:
+        raise ValueError("aprilx_tone_decide_host refused its arguments")
+    return r & 0xffff, r >> 16
+
+
+def tone_events_host(plan, frame_shift_ms: int, t0: int, records, machine=None, flush: bool = False):
+    """The events that follow from the records [n][2] of frames [t0, t0 + n) (aprilx_tone_events_host) from `machine` (AprilxToneMachine,
+    updated in place; None: idle); `flush`: a flush completes behind them.  Returns ([ToneEvent], machine)."""
+    b = np.ascontiguousarray(records, np.uint16).reshape(-1, 2)
+    cap = 2 * len(b) + 2              # (on_frames = off_frames = 1: a frame can give OFF and ON; a flush one more OFF)
+    kinds = np.zeros(cap, np.int32); f1 = np.zeros(cap, np.uint32); f2 = np.zeros(cap, np.uint32); times = np.zeros(cap, np.uint64)
+    m = machine if machine is not None else _ffi.AprilxToneMachine(0, 0, 0, 0, 0, 0)
+    n = _ffi.lib().aprilx_tone_events_host(C.byref(plan), int(frame_shift_ms), int(t0), b.ctypes.data, len(b), 1 if flush else 0, C.byref(m),
+                                           kinds.ctypes.data, f1.ctypes.data, f2.ctypes.data, times.ctypes.data, cap)
+    if n < 0:
+        raise ValueError("aprilx_tone_events_host refused its arguments")
+    return [ToneEvent(kinds[i], f1[i], f2[i], times[i]) for i in range(n)], m
+
+
+def tone_name(f1_hz: int, f2_hz: int = 0, tol_hz: int = 20):
+    """"dial", "busy", "cp425", "cng", "ced", "sit1", "sit2", "sit3" or None (aprilx_tone_name)"""
+    s = _ffi.lib().aprilx_tone_name(int(f1_hz), int(f2_hz), int(tol_hz))
+    return s.decode() if s else None
 
 
 def dtmf_plan(sample_rate: int, fft_size: int, frame_shift_ms: int, options=True):

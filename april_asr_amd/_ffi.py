@@ -106,6 +106,30 @@ class AprilxDtmfMachine(C.Structure):
 DTMF_HANDLER = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_char, C.c_uint64)
 
 
+class AprilxToneOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("min_level_dbfs", C.c_float), ("second_db", C.c_float), ("min_share", C.c_float), ("tol_hz", C.c_uint32),
+                ("min_tone_ms", C.c_uint32), ("min_pause_ms", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class AprilxToneInfo(C.Structure):
+    _fields_ = [("W", C.c_int32), ("k_lo", C.c_int32), ("F", C.c_int32), ("on_frames", C.c_int32), ("off_frames", C.c_int32),
+                ("held_f1", C.c_uint32), ("held_f2", C.c_uint32), ("reserved", C.c_uint32),
+                ("frames_seen", C.c_uint64), ("tonal_frames", C.c_uint64), ("tones", C.c_uint64)]
+
+
+class AprilxTonePlan(C.Structure):
+    _fields_ = [("W", C.c_int32), ("k_lo", C.c_int32), ("F", C.c_int32), ("half_w", C.c_float), ("min_power", C.c_float), ("second_ratio", C.c_float),
+                ("min_share", C.c_float), ("bin_hz", C.c_float), ("tol_hz", C.c_int32), ("on_frames", C.c_int32), ("off_frames", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class AprilxToneMachine(C.Structure):
+    _fields_ = [("held", C.c_int32), ("h1", C.c_int32), ("h2", C.c_int32), ("c1", C.c_int32), ("c2", C.c_int32), ("run", C.c_int32)]
+
+
+TONE_HANDLER = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64)
+
+
 class AprilxInputFormat(C.Structure):
     _fields_ = [("size", C.c_uint32), ("encoding", C.c_uint32), ("channels", C.c_uint32), ("channel", C.c_int32)]
 
@@ -135,6 +159,8 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_model_vad_stats",
     "aprilx_session_set_dtmf", "aprilx_session_dtmf", "aprilx_dtmf_plan", "aprilx_dtmf_tables", "aprilx_dtmf_host", "aprilx_dtmf_decide_host",
     "aprilx_dtmf_events_host", "aprilx_run_dtmf", "aprilx_run_dtmf_decide", "aprilx_model_dtmf_stats",
+    "aprilx_session_set_tones", "aprilx_session_tones", "aprilx_tone_plan", "aprilx_tone_tables", "aprilx_tone_host", "aprilx_tone_decide_host",
+    "aprilx_tone_events_host", "aprilx_tone_name", "aprilx_run_tones", "aprilx_run_tone_decide", "aprilx_model_tone_stats",
 ]
 
 _lib = None
@@ -252,6 +278,18 @@ def lib():
     L.aprilx_run_dtmf.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]; L.aprilx_run_dtmf.restype = C.c_int
     L.aprilx_run_dtmf_decide.argtypes = [vp, C.POINTER(AprilxDtmfOptions), C.c_int, vp, vp]; L.aprilx_run_dtmf_decide.restype = C.c_int
     L.aprilx_model_dtmf_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]; L.aprilx_model_dtmf_stats.restype = C.c_int
+    L.aprilx_session_set_tones.argtypes = [vp, C.POINTER(AprilxToneOptions), TONE_HANDLER, vp]; L.aprilx_session_set_tones.restype = C.c_int
+    L.aprilx_session_tones.argtypes = [vp, C.POINTER(AprilxToneOptions), C.POINTER(AprilxToneInfo)]; L.aprilx_session_tones.restype = C.c_int
+    L.aprilx_tone_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(AprilxToneOptions), C.POINTER(AprilxTonePlan)]; L.aprilx_tone_plan.restype = C.c_int
+    L.aprilx_tone_tables.argtypes = [C.c_int, C.c_int, vp, sz]; L.aprilx_tone_tables.restype = C.c_int
+    L.aprilx_tone_host.argtypes = [C.POINTER(AprilxTonePlan), vp, C.c_int, vp, sz, vp, vp]; L.aprilx_tone_host.restype = C.c_int
+    L.aprilx_tone_decide_host.argtypes = [C.POINTER(AprilxTonePlan), vp]; L.aprilx_tone_decide_host.restype = C.c_int64
+    L.aprilx_tone_events_host.argtypes = [C.POINTER(AprilxTonePlan), C.c_int, C.c_uint64, vp, sz, C.c_int, C.POINTER(AprilxToneMachine), vp, vp, vp, vp, C.c_int]
+    L.aprilx_tone_events_host.restype = C.c_int
+    L.aprilx_tone_name.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]; L.aprilx_tone_name.restype = C.c_char_p
+    L.aprilx_run_tones.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]; L.aprilx_run_tones.restype = C.c_int
+    L.aprilx_run_tone_decide.argtypes = [vp, C.POINTER(AprilxToneOptions), C.c_int, vp, vp]; L.aprilx_run_tone_decide.restype = C.c_int
+    L.aprilx_model_tone_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]; L.aprilx_model_tone_stats.restype = C.c_int
     _lib = L
     return L
 

@@ -131,6 +131,10 @@ struct FrontPass {
     int n_vd = 0; const VadDesc *vd = nullptr; size_t vad_bytes = 0;
     // DTMF: the n_dt descriptors (`first` indexes the frame descriptors of this call); dtmf_kernel runs behind the resample launch.
     int n_dt = 0; const DtmfDesc *dt = nullptr; size_t dtmf_bytes = 0;
+    // Tones: the n_tn descriptors (`first` as DTMF's); tone_kernel runs beside dtmf_kernel.  Its records (four bytes
+    // per frame, `tone_bytes` in all) are the third part of the block, at the 4-byte aligned offset tone_at(); out_off counts records.
+    int n_tn = 0; const ToneDesc *tn = nullptr; size_t tone_bytes = 0;
+    size_t tone_at() const { return (vad_bytes + dtmf_bytes + 3) / 4 * 4; }
 };
 
 // One call of the decision kernel on GIVEN rows (the parity tests' entry point, Engine::debug_decide): slots 0..n-1, row i = slot i.
@@ -182,8 +186,8 @@ public:
     // chunk steps (encoder + the three joiner/decision/decoder rounds, all on the device) and decoder refreshes are queued
     // back to back, and the host reads the 16-byte-per-round records once, at end_flight().
     // pcm arrives as `n_parts` windows that are gathered straight into pinned staging (total n_pcm samples)
-    // `pass`: the resample / decode / VAD / DTMF work of this call.  Returns the pinned block that receives the pass's VAD bytes and, behind
-    // them, its DTMF bytes (null: neither VAD nor DTMF descriptors): its bytes are complete once the flight that was open during the call
+    // `pass`: the resample / decode / VAD / DTMF / tone work of this call.  Returns the pinned block that receives the pass's VAD bytes, behind
+    // them its DTMF bytes and behind those its tone records (null: no descriptors of the three): its bytes are complete once the flight that was open during the call
     // has been waited for (close_flight() puts the copy in front of the flight's event), and the block is lent until
     // release_pass_block().  Stepping thread only.
     const uint8_t *fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<const int16_t *, size_t> *parts, size_t n_parts, size_t n_pcm,
@@ -213,6 +217,16 @@ public:
     void debug_dtmf(int n_runs, const DtmfPlan *plans, const int32_t *n, const int16_t *frames, uint8_t *codes_out, float *powers_out);
     // aprilx_run_dtmf_decide: the decision alone on n given rows of P[0..8), E
     void debug_dtmf_decide(const DtmfPlan &plan, int n, const float *powers9, uint8_t *codes_out);
+    // ---- tones.  Launches and the frames they covered so far (any thread); nothing is allocated until a pass
+    // carries a tone descriptor.
+    void tone_counts(uint64_t *launches, uint64_t *frames) const
+    {
+        *launches = tn_launches_.load(std::memory_order_relaxed); *frames = tn_frames_.load(std::memory_order_relaxed);
+    }
+    // aprilx_run_tones: n_runs runs in ONE launch, as debug_dtmf; records_out [sum n] (lo | hi << 16), powers_out (may be null) [sum n][F + 1]
+    void debug_tones(int n_runs, const TonePlan *plans, const int32_t *n, const int16_t *frames, uint32_t *records_out, float *powers_out);
+    // aprilx_run_tone_decide: the decision alone on n given rows of P[0..F), E
+    void debug_tone_decide(const TonePlan &plan, int n, const float *powers, uint32_t *records_out);
     // aprilx_run_vad: n_runs runs in ONE launch over a scratch ring of ring_rows rows per run; run r's n[r] rows (consecutive in `rows`)
     // sit at rows (first_row[r] + i) % ring_rows of its ring
     void debug_vad(int n_runs, const VadPlan *plans, const int32_t *n, const int32_t *first_row, int ring_rows, const float *rows, VadState *states_io,
@@ -324,7 +338,7 @@ public:
     // split feeds launched as hostable (any thread)
     void ramp_counts(uint64_t *hosted, uint64_t *eligible);
     void reset_timing();
-    enum { T_GATES = 0, T_GEMM_OTHER = 1, T_ROW = 2, T_CONV = 3, T_FBANK = 4, T_DEC = 5, T_RESAMPLE = 6, T_DECODE = 7, T_VAD = 8, T_DTMF = 9, T_COUNT = 10 };
+    enum { T_GATES = 0, T_GEMM_OTHER = 1, T_ROW = 2, T_CONV = 3, T_FBANK = 4, T_DEC = 5, T_RESAMPLE = 6, T_DECODE = 7, T_VAD = 8, T_DTMF = 9, T_TONE = 10, T_COUNT = 11 };
     long kernels_per_step() const { return kernels_per_step_.load(std::memory_order_relaxed); }    // launches of the last eagerly issued chunk chain
 
 private:
@@ -478,7 +492,7 @@ private:
     std::atomic<uint64_t> dc_launches_{0}, dc_frames_{0};
     // voice activity: nothing below is allocated until a pass carries a VAD descriptor
     VadState *vad_state_d_ = nullptr;          // [slots] (a session's first descriptor carries VAD_RESET: never initialised by the host)
-    uint8_t *pass_out_d_ = nullptr; size_t pass_out_cap_ = 0;      // one pass's bytes on the device, VAD then DTMF (stream order keeps the passes apart)
+    uint8_t *pass_out_d_ = nullptr; size_t pass_out_cap_ = 0;      // one pass's bytes on the device, VAD, DTMF, then the tone records (stream order keeps the passes apart)
     struct PassBlock { uint8_t *h = nullptr; size_t cap = 0; bool busy = false; };
     std::vector<PassBlock> pass_blocks_;         // pinned blocks, one per pass whose bytes (VAD, then DTMF) the scheduler has not read yet: lent by fbank(), busy until release_pass_block()
     bool pass_bytes_flight_ = false;                  // the open flight holds a pass with VAD or DTMF bytes: its event must follow their copy on the front-end stream
@@ -487,6 +501,10 @@ private:
     const float *dt_tables_ = nullptr; int dt_wd_ = 0;      // [16][Wd] on the device, uploaded once (freed with table_allocs_)
     std::atomic<uint64_t> dt_launches_{0}, dt_frames_{0};
     const float *dtmf_tables();
+    // tones: nothing below is allocated until a pass carries a tone descriptor
+    const float *tn_tables_ = nullptr; int tn_w_ = 0, tn_f_ = 0;      // [2F][W] on the device, uploaded once (freed with table_allocs_)
+    std::atomic<uint64_t> tn_launches_{0}, tn_frames_{0};
+    const float *tone_tables();
     std::mutex rs_mu_;
     std::map<const ResampleSpec *, const float *> rs_tables_;     // phase tables on the device, uploaded at first use (freed with table_allocs_)
     const float *resample_table(const ResampleSpec *spec);

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include "vad.h"
 #include "dtmf.h"
+#include "tone.h"
 #include "gemm_plan.h"
 
 namespace aprilx {
@@ -487,5 +488,28 @@ struct DtmfArgs {
 void launch_dtmf(const DtmfArgs &a, hipStream_t s);
 // (tests) the decision alone on GIVEN rows of P[0..8), E: codes_out[i] = dtmf_decide(plan, powers9 + 9 i)
 void launch_dtmf_decide(const DtmfPlan &plan, int n, const float *powers9, uint8_t *codes_out, hipStream_t s);
+
+// ---------------------------------------------------------------- tones (sessions that opted in; contract in tone.h)
+// One descriptor per run of consecutive real frames of a session in this pass, laid out as DtmfDesc: frame i of the run is frame
+// descriptor first + i of the SAME pass, its record (two uint16, four bytes) goes to out + 4 (out_off + i).  The descriptor carries the
+// session's plan; the kernel keeps no state.  One wave per workgroup, kToneWaveFrames consecutive frames of a run per wave.
+constexpr int kToneBlock = 64, kToneWaveFrames = 4, kToneBins = 8;      // lanes per workgroup; frames a wave carries; bins per walk of the rows
+struct ToneDesc {
+    int32_t first = 0, n = 0, out_off = 0, reserved = 0;
+    TonePlan plan;
+};
+static_assert(sizeof(ToneDesc) == 64, "staged behind the DTMF descriptors, 16-byte aligned");
+struct ToneArgs {
+    const int16_t *pcm = nullptr;          // staged samples
+    const FbankFrameDesc *frames = nullptr;
+    const ToneDesc *desc = nullptr; int n_desc = 0;
+    int max_n = 0;                         // max over descriptors of n
+    const float *tables = nullptr; int w = 0, f = 0;      // [2 f][w] (tone_make_tables); every descriptor's plan.W is w and plan.F is f
+    uint32_t *out = nullptr;               // the pass's records (4-byte aligned)
+    float *powers = nullptr;               // (tests) P[0..f) and E of every frame, [.][f + 1] indexed like out; or null
+};
+void launch_tone(const ToneArgs &a, hipStream_t s);
+// (tests) the decision alone on GIVEN rows of P[0..F), E: records_out[i] = tone_decide(plan, powers + (F + 1) i)
+void launch_tone_decide(const TonePlan &plan, int n, const float *powers, uint32_t *records_out, hipStream_t s);
 
 }  // namespace aprilx

@@ -569,6 +569,16 @@ bool Scheduler::set_dtmf(Session *s, const DtmfOptions *o, const DtmfPlan *plan,
     });
 }
 
+bool Scheduler::set_tones(Session *s, const ToneOptions *o, const TonePlan *plan, AprilxToneHandler handler, void *userdata)
+{
+    return configure(s, [&] {
+        s->tones = Session::Tones();
+        if (plan) { s->tones.on = true; s->tones.opt = *o; s->tones.plan = *plan; }
+        s->handlers.tone = plan ? handler : nullptr; s->handlers.tone_userdata = plan ? userdata : nullptr;
+        return true;
+    });
+}
+
 bool Scheduler::set_bias(Session *s, std::shared_ptr<const BiasSet> set)
 {
     return configure(s, [&] {
@@ -618,7 +628,8 @@ void Scheduler::wait_backlog(Session *const *ss, int n, uint64_t max_open)
 void deliver_events(std::vector<Event> &ev, const Handlers &to)
 {
     for (auto &e : ev) {
-        if (e.type >= kDtmfEventBase) { if (to.dtmf) to.dtmf(to.dtmf_userdata, e.type - kDtmfEventBase, e.digit, e.time_ms); }
+        if (e.type >= kToneEventBase) { if (to.tone) to.tone(to.tone_userdata, e.type - kToneEventBase, e.f1, e.f2, e.time_ms); }
+        else if (e.type >= kDtmfEventBase) { if (to.dtmf) to.dtmf(to.dtmf_userdata, e.type - kDtmfEventBase, e.digit, e.time_ms); }
         else if (e.type >= kVadEventBase) { if (to.vad) to.vad(to.vad_userdata, e.type - kVadEventBase, e.time_ms); }
         else to.result(to.userdata, (AprilResultType)e.type, e.tokens.size(), e.tokens.empty() ? nullptr : e.tokens.data());
     }
@@ -916,9 +927,10 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
 {
     Lap lap;
     desc_.clear(); pcm_parts_.clear(); in_parts_.clear(); rdesc_.clear(); rspec_.clear(); ddesc_.clear(); raw_parts_.clear(); staged_raw_ = 0;
-    vdesc_.clear(); tdesc_.clear();
-    PassPending rec{flight_seq_, nullptr, 0, {}, {}};      // this pass's record in the pass queue: its runs and flush markers, then its block
+    vdesc_.clear(); tdesc_.clear(); ndesc_.clear();
+    PassPending rec{flight_seq_, nullptr, 0, 0, {}, {}, {}};      // this pass's record in the pass queue: its runs and flush markers, then its block
     int32_t vad_frames = 0, dtmf_frames = 0;    // bytes of this pass's VAD / DTMF output so far
+    int32_t tone_frames = 0;                    // records of its tone output so far
     size_t staged = 0, staged_in = 0;           // model-rate samples (windows), input-rate samples (spans of resampled windows)
     auto used = [&] { return staged + staged_in + (staged_raw_ + 1) / 2; };      // what the pass has staged so far, raw bytes of formatted sessions in sample units
     std::vector<Session *> finishers;
@@ -974,6 +986,13 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
                 rec.dtmf.push_back(PassRun{s, s->real_frames, cut, dtmf_frames});
                 dtmf_frames += cut;
             }
+            if (s->tones.on) {                         // likewise
+                ToneDesc t;
+                t.first = (int32_t)(desc_.size() - (size_t)cut); t.n = cut; t.out_off = tone_frames; t.plan = s->tones.plan;
+                ndesc_.push_back(t);
+                rec.tone.push_back(PassRun{s, s->real_frames, cut, tone_frames});
+                tone_frames += cut;
+            }
             s->real_frames += (uint64_t)cut;
             s->compact_pending = true;                 // the fifo must not move until the window has been staged
             progressed = true;
@@ -1019,6 +1038,7 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
             finishers.push_back(s);
             if (s->vad.on) { rec.vad.push_back(PassRun{s, s->real_frames, -1, 0}); s->vad.reset = true; }      // closes an open segment; the detector starts afresh
             if (s->dtmf.on) rec.dtmf.push_back(PassRun{s, s->real_frames, -1, 0});                              // closes a held digit; the machine starts afresh
+            if (s->tones.on) rec.tone.push_back(PassRun{s, s->real_frames, -1, 0});                             // closes a held tone likewise
             s->flush_phase = 0;
             progressed = true;
             break;
@@ -1032,6 +1052,7 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
         pass.n_rs = (int)rdesc_.size(); pass.rs = rdesc_.data(); pass.rs_specs = rspec_.data(); pass.in_parts = in_parts_.data(); pass.n_in_parts = in_parts_.size(); pass.n_in = staged_in;
         pass.n_vd = (int)vdesc_.size(); pass.vd = vdesc_.data(); pass.vad_bytes = (size_t)vad_frames;
         pass.n_dt = (int)tdesc_.size(); pass.dt = tdesc_.data(); pass.dtmf_bytes = (size_t)dtmf_frames;
+        pass.n_tn = (int)ndesc_.size(); pass.tn = ndesc_.data(); pass.tone_bytes = (size_t)tone_frames * 4;
         rec.block = eng_->fbank((int)desc_.size(), desc_.data(), pcm_parts_.data(), pcm_parts_.size(), staged, &pool_, pass);
         pool_.run(work.size(), 64, [&](size_t i) { Session *s = work[i]; if (s->compact_pending) { s->fb.compact(); s->compact_pending = false; } });
         tick_.frames += desc_.size();
@@ -1039,7 +1060,8 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
     }
     // the block is lent until this flight has been waited for and harvest() has read it
     rec.dtmf_at = (size_t)vad_frames;
-    if (rec.block || !rec.vad.empty() || !rec.dtmf.empty()) pass_pending_.push_back(std::move(rec));
+    rec.tone_at = ((size_t)vad_frames + (size_t)dtmf_frames + 3) / 4 * 4;      // (FrontPass::tone_at())
+    if (rec.block || !rec.vad.empty() || !rec.dtmf.empty() || !rec.tone.empty()) pass_pending_.push_back(std::move(rec));
     if (!finishers.empty()) {
         slots_.clear();
         for (Session *s : finishers) slots_.push_back(s->slot);
@@ -1160,15 +1182,16 @@ bool Scheduler::step_chunks(std::vector<Session *> &ready)
 }
 
 // After the flight's wait: the bytes of every pass cut under it (and under the flights before it) are on the host.  The records up to
-// the flight are walked twice -- all VAD runs of all of them, then all DTMF runs: the order of a session's detector events in front of
+// the flight are walked three times -- all VAD runs of all of them, then all DTMF runs, then all tone runs: the order of a session's detector events in front of
 // the flight's token events --, then each gives its block back and goes.  The sessions are alive: they stay busy until their flight
-// completes.  An engine that lent no block to a pass with descriptors: that pass's bytes are skipped by both detectors alike.
+// completes.  An engine that lent no block to a pass with descriptors: that pass's bytes are skipped by all detectors alike.
 void Scheduler::harvest(uint64_t flight)
 {
     size_t n = 0;
     while (n < pass_pending_.size() && pass_pending_[n].flight <= flight) ++n;
     for (size_t i = 0; i < n; ++i) for (const PassRun &r : pass_pending_[i].vad) harvest_vad(pass_pending_[i], r);
     for (size_t i = 0; i < n; ++i) for (const PassRun &r : pass_pending_[i].dtmf) harvest_dtmf(pass_pending_[i], r);
+    for (size_t i = 0; i < n; ++i) for (const PassRun &r : pass_pending_[i].tone) harvest_tone(pass_pending_[i], r);
     for (; n; --n) {
         if (pass_pending_.front().block) eng_->release_pass_block(pass_pending_.front().block);
         pass_pending_.pop_front();
@@ -1205,6 +1228,22 @@ void Scheduler::harvest_dtmf(const PassPending &p, const PassRun &r)
     const uint8_t *b = p.block + p.dtmf_at + r.off;
     dtmf_events(s->dtmf.plan, shift_ms_, r.t0, b, (size_t)r.n, s->dtmf.m, emit);
     for (int32_t i = 0; i < r.n; ++i) s->dtmf.tone += b[i] ? 1u : 0u;
+}
+
+// One tone run: the records of consecutive real frames go through the session's event machine (tone.h); a completed flush closes a held tone.
+void Scheduler::harvest_tone(const PassPending &p, const PassRun &r)
+{
+    Session *s = r.s;
+    auto emit = [&](int kind, uint32_t f1, uint32_t f2, uint64_t ms) {
+        Event e; e.type = kToneEventBase + kind; e.time_ms = ms; e.f1 = f1; e.f2 = f2;
+        s->events.push_back(std::move(e));
+        if (kind == TONE_ON) s->tones.tones++;
+    };
+    if (r.n < 0) { tone_flush(shift_ms_, r.t0, s->tones.m, emit); return; }
+    if (!p.block) return;
+    const uint32_t *b = reinterpret_cast<const uint32_t *>(p.block + p.tone_at) + r.off;      // (the block is pinned memory, tone_at a multiple of 4)
+    tone_events(s->tones.plan, shift_ms_, r.t0, b, (size_t)r.n, s->tones.m, emit);
+    for (int32_t i = 0; i < r.n; ++i) s->tones.tonal += (b[i] & 0xffffu) ? 1u : 0u;
 }
 
 // After the flight: per session, in the order things happened, feed the device's per-round records to the search state

@@ -50,17 +50,20 @@ struct Event {
     // sessions with confidences on (aprilx_session_set_confidence): one entry per token, and tokens[i].reserved points to infos[i].
     // Events are only ever MOVED between containers (the vector's storage, and with it the pointers, stay where they are).
     std::vector<AprilxTokenInfo> infos;
-    // a detector's event: type = kVadEventBase + kind or kDtmfEventBase + kind (section 17) at time_ms; `digit` is
-    // a DTMF event's key
+    // a detector's event: type = kVadEventBase + kind, kDtmfEventBase + kind (section 17) or kToneEventBase + kind
+    // (section 18) at time_ms; `digit` is a DTMF event's key, f1 and f2 a tone event's frequencies
     uint64_t time_ms = 0;
     char digit = 0;
+    uint32_t f1 = 0, f2 = 0;
 };
-constexpr int kVadEventBase = 0x100, kDtmfEventBase = 0x200;
-// where a session's events go: token events to `result`, voice-activity events to `vad`, DTMF events to `dtmf` (null: dropped)
+constexpr int kVadEventBase = 0x100, kDtmfEventBase = 0x200, kToneEventBase = 0x300;
+// where a session's events go: token events to `result`, voice-activity events to `vad`, DTMF events to `dtmf`, tone events to `tone`
+// (null: dropped)
 struct Handlers {
     AprilRecognitionResultHandler result = nullptr; void *userdata = nullptr;
     AprilxVadHandler vad = nullptr; void *vad_userdata = nullptr;
     AprilxDtmfHandler dtmf = nullptr; void *dtmf_userdata = nullptr;
+    AprilxToneHandler tone = nullptr; void *tone_userdata = nullptr;
 };
 // the handler once per event, in order (null token pointer when an event has no tokens); `ev` is empty afterwards
 void deliver_events(std::vector<Event> &ev, const Handlers &to);
@@ -224,8 +227,8 @@ struct Session {
     size_t now_ms = 0;
     uint64_t chunks = 0;
     std::vector<Event> events;                // produced during the current tick
-    // The detectors (DESIGN.md sections 16 and 17).  Options, plan and handler (in `handlers`) change only while the session is settable; the
-    // rest is the stepping thread's while the session is busy.  real_frames: every real frame cut since creation, the frame clock of both.
+    // The detectors (DESIGN.md sections 16, 17 and 18).  Options, plan and handler (in `handlers`) change only while the session is settable; the
+    // rest is the stepping thread's while the session is busy.  real_frames: every real frame cut since creation, the frame clock of all.
     uint64_t real_frames = 0;
     struct Vad {
         bool on = false; VadOptions opt; VadPlan plan;
@@ -237,6 +240,11 @@ struct Session {
         DtmfMachine m;                        // (the device keeps nothing)
         uint64_t tone = 0, digits = 0;        // frames with a non-zero code, DOWN events, since the detector was last set
     } dtmf;
+    struct Tones {
+        bool on = false; ToneOptions opt; TonePlan plan;
+        ToneMachine m;                        // (the device keeps nothing)
+        uint64_t tonal = 0, tones = 0;        // frames with a tonal record, ON events, since the detector was last set
+    } tones;
     // tracing (tests): every joiner call appends `vocab` floats
     float *trace_buf = nullptr; size_t trace_cap = 0; size_t *trace_used = nullptr;
 };
@@ -283,6 +291,8 @@ public:
     bool set_vad(Session *s, const VadOptions *o, const VadPlan *plan, AprilxVadHandler handler, void *userdata);
     // aprilx_session_set_dtmf: the same rule; plan null = off.  The machine and its counters start afresh
     bool set_dtmf(Session *s, const DtmfOptions *o, const DtmfPlan *plan, AprilxDtmfHandler handler, void *userdata);
+    // aprilx_session_set_tones: the same rule; plan null = off.  The machine and its counters start afresh
+    bool set_tones(Session *s, const ToneOptions *o, const TonePlan *plan, AprilxToneHandler handler, void *userdata);
     void wait_idle_many(Session *const *ss, int n);
     // until every listed session has at most `max_open` feeds that were submitted and not completed yet (pipelined group feeds)
     void wait_backlog(Session *const *ss, int n, uint64_t max_open);
@@ -325,15 +335,17 @@ private:
     // cut_frames() pushes one record per pass that has runs, under the flight that is open; harvest(), once that flight has been waited
     // for, turns the runs into events, gives the block back to the engine and pops the record.  The record is the block's one owner.
     struct PassRun { Session *s; uint64_t t0; int32_t n, off; };      // frames [t0, t0 + n) at off in its detector's part; n < 0: a flush completed at frame t0
-    // block: Engine::fbank()'s, the pass's VAD bytes and from dtmf_at its DTMF bytes; null: a pass of flush markers only
-    struct PassPending { uint64_t flight; const uint8_t *block; size_t dtmf_at; std::vector<PassRun> vad, dtmf; };
+    // block: Engine::fbank()'s, the pass's VAD bytes, from dtmf_at its DTMF bytes and from tone_at its tone records (a tone run's off
+    // counts records); null: a pass of flush markers only
+    struct PassPending { uint64_t flight; const uint8_t *block; size_t dtmf_at, tone_at; std::vector<PassRun> vad, dtmf, tone; };
     std::deque<PassPending> pass_pending_;
-    std::vector<VadDesc> vdesc_; std::vector<DtmfDesc> tdesc_;       // scratch of cut_frames()
+    std::vector<VadDesc> vdesc_; std::vector<DtmfDesc> tdesc_; std::vector<ToneDesc> ndesc_;       // scratch of cut_frames()
     uint64_t flight_seq_ = 0;
     const int shift_ms_;
     void harvest(uint64_t flight);
     void harvest_vad(const PassPending &p, const PassRun &r);
     void harvest_dtmf(const PassPending &p, const PassRun &r);
+    void harvest_tone(const PassPending &p, const PassRun &r);
     int split_sticky_ = 0;
     int pipeline_depth_ = 2;                             // APRIL_PIPELINE: 2 = launch the next flight before completing the current one, 1 = one flight at a time
 

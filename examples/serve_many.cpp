@@ -5,7 +5,7 @@
 //
 //   g++ -O2 -std=c++17 examples/serve_many.cpp -I include -L april_asr_amd -laprilasr -Wl,-rpath,$PWD/april_asr_amd -o serve_many
 //   ./serve_many model.april audio.raw [sessions=64] [mode=pipelined|lockstep] [input_rate] [--alternatives K] [--bias FILE [--bias-strict]]
-//               [--endpoint-ms N] [--blank-penalty X] [--vad] [--dtmf]
+//               [--endpoint-ms N] [--blank-penalty X] [--vad] [--dtmf] [--tones]
 //
 // Every session gets the same PCM16 file, rotated by (session index x 0.37 s) so that the streams differ.  With `input_rate` the file
 // is PCM16 at that rate and every session is told so (aprilx_session_set_input_rate): the library converts it to the model's rate on
@@ -23,6 +23,8 @@
 // then ends with " vad <segments> <speech seconds>", and the timing lines say what a step cost.
 // `--dtmf` (anywhere on the line): every session gets the DTMF detector with its default options (aprilx_session_set_dtmf); its line then
 // ends with " dtmf <digits>" ("-" when no key was found).
+// `--tones` (anywhere on the line): every session gets the tone detector with its default options (aprilx_session_set_tones); its line then
+// ends with " tones" and one "<name or f1[+f2]>@<on ms>-<off ms>" per tone ("-" when none was found), the names aprilx_tone_name()'s.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -38,7 +40,22 @@ struct Stream {
     size_t calls = 0, finals = 0, final_tokens = 0; std::string last_final; double conf_sum = 0; size_t conf_n = 0;
     size_t vad_segments = 0; uint64_t vad_open_ms = 0, vad_speech_ms = 0;
     std::string dtmf_digits;
+    std::string tones; size_t tone_count = 0;
 };
+
+static void on_tone(void *ud, int kind, uint32_t f1_hz, uint32_t f2_hz, uint64_t time_ms)
+{
+    Stream *s = static_cast<Stream *>(ud);
+    char buf[64];
+    if (kind == APRILX_TONE_ON) {
+        const char *name = aprilx_tone_name(f1_hz, f2_hz, 20);
+        if (name) snprintf(buf, sizeof buf, " %s@%llu", name, (unsigned long long)time_ms);
+        else if (f2_hz) snprintf(buf, sizeof buf, " %u+%u@%llu", f1_hz, f2_hz, (unsigned long long)time_ms);
+        else snprintf(buf, sizeof buf, " %u@%llu", f1_hz, (unsigned long long)time_ms);
+        s->tone_count++;
+    } else snprintf(buf, sizeof buf, "-%llu", (unsigned long long)time_ms);
+    s->tones += buf;
+}
 
 static void on_dtmf(void *ud, int kind, char digit, uint64_t)
 {
@@ -73,7 +90,14 @@ int main(int argc, char **argv)
     bool bias_strict = false;
     long endpoint_ms = -1;
     const char *blank_penalty = nullptr;
-    bool vad = false, dtmf = false;
+    bool vad = false, dtmf = false, tones = false;
+    for (int i = 1; i < argc; ++i)
+        if (!strcmp(argv[i], "--tones")) {
+            tones = true;
+            for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+            argc -= 1;
+            break;
+        }
     for (int i = 1; i < argc; ++i)
         if (!strcmp(argv[i], "--dtmf")) {
             dtmf = true;
@@ -197,6 +221,10 @@ int main(int argc, char **argv)
             AprilxDtmfOptions dopt = {(uint32_t)sizeof dopt, -40.0f, 4.0f, 8.0f, 8.0f, 0.6f, 20u, 20u, 0u};
             if (aprilx_session_set_dtmf(sessions[(size_t)i], &dopt, on_dtmf, &streams[(size_t)i]) != 0) { fprintf(stderr, "DTMF options refused\n"); return 1; }
         }
+        if (tones) {
+            AprilxToneOptions topt = {(uint32_t)sizeof topt, -40.0f, 10.0f, 0.7f, 20u, 60u, 30u, 0u};
+            if (aprilx_session_set_tones(sessions[(size_t)i], &topt, on_tone, &streams[(size_t)i]) != 0) { fprintf(stderr, "tone options refused\n"); return 1; }
+        }
         const size_t rot = ((size_t)i * (size_t)(0.37 * rate)) % pcm.size();
         audio[(size_t)i].assign(pcm.begin() + (long)rot, pcm.end());
         audio[(size_t)i].insert(audio[(size_t)i].end(), pcm.begin(), pcm.begin() + (long)rot);
@@ -217,6 +245,7 @@ int main(int argc, char **argv)
         printf("%d %zu %zu %zu %s", i, s.calls, s.finals, s.final_tokens, s.last_final.c_str());
         if (vad) printf(" vad %zu %.2f", s.vad_segments, (double)s.vad_speech_ms * 1e-3);      // (the flush has closed every open segment)
         if (dtmf) printf(" dtmf %s", s.dtmf_digits.empty() ? "-" : s.dtmf_digits.c_str());
+        if (tones) printf(" tones%s", s.tones.empty() ? " -" : s.tones.c_str());      // (the flush has closed every held tone)
         printf("\n");
     }
     fprintf(stderr, "%d streams x %.1f s of audio in %.1f ms (%s feed): %.0f audio-seconds per second\n", n, steps * 0.1, ms, pipelined ? "pipelined" : "lock-step",
@@ -240,6 +269,13 @@ int main(int argc, char **argv)
         aprilx_model_dtmf_stats(model, 0, &launches, &frames, &kms);
         for (const Stream &s : streams) keys += s.dtmf_digits.size();
         fprintf(stderr, "DTMF: %.3f ms per 100 ms step, %zu keys, %llu launches over %llu frames on device 0\n", ms / (double)steps, keys,
+                (unsigned long long)launches, (unsigned long long)frames);
+    }
+    if (tones) {
+        uint64_t launches = 0, frames = 0; double kms = 0; size_t found = 0;
+        aprilx_model_tone_stats(model, 0, &launches, &frames, &kms);
+        for (const Stream &s : streams) found += s.tone_count;
+        fprintf(stderr, "tones: %.3f ms per 100 ms step, %zu tones, %llu launches over %llu frames on device 0\n", ms / (double)steps, found,
                 (unsigned long long)launches, (unsigned long long)frames);
     }
     if (argc > 5) fprintf(stderr, "input at %zu Hz: %.3f ms per 100 ms step\n", rate, ms / (double)steps);

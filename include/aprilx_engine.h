@@ -453,6 +453,81 @@ APRIL_EXPORT int aprilx_run_dtmf_decide(AprilASRModel model, const AprilxDtmfOpt
 /* DTMF launches and the frames they covered on one GPU's engine, and (while profiling) the kernel's accumulated ms.  0, or -1. */
 APRIL_EXPORT int aprilx_model_dtmf_stats(AprilASRModel model, int device_index, uint64_t *launches, uint64_t *frames, double *ms);
 
+/* ---- Tones.  A session that opts in gets ON / OFF events for sustained tones -- the beep of an answering machine,
+ * fax CNG and CED, dial tone, busy and reorder, the 425 Hz tones of European networks, the segments of a special-information tone --
+ * from a detector that runs on the GPU, on the model-rate samples the filterbank reads: per frame the correlation of its first
+ * W = 64 floor(fft_size / 64) samples with every DFT bin of length W from 300 to 2300 Hz, the strongest bin and the strongest one at
+ * least three bins away, level, second-component and energy-share checks, and an interpolated frequency per component -> one record of
+ * two uint16 per frame ((hz, 0) a single tone, (lo, hi) a pair, (0, 0) none); the host turns consecutive records into events.  The
+ * frequencies are not fixed in advance: an event carries what was measured, and aprilx_tone_name() names the well-known ones.
+ * CADENCE IS THE CALLER'S: busy and reorder are the same pair at different rhythms, ringing is a tone that comes and goes; read them from
+ * the ON / OFF times.  Two components closer than three bins (93.75 Hz at 16 kHz / 512) are ONE tone: North American ringback
+ * (440 + 480 Hz), and dial tone on a model whose frames are not rounded up to a power of two.  Whistling and sung notes are tones.  A
+ * DTMF digit is a pair inside the grid and is reported here too, beside the DTMF detector's own event; neither suppresses the other.
+ * The feature only observes, as voice activity and DTMF do, and an engine none of whose sessions has opted in launches, copies and
+ * allocates nothing new.  Times are on the FRAME clock of the voice-activity events; delivery follows their rules.  A flush that
+ * completes inside a held tone closes it with an OFF at frames_seen * frame_shift, and resets the machine. */
+typedef struct AprilxToneOptions {
+    uint32_t size;                      /* sizeof(AprilxToneOptions) */
+    float min_level_dbfs;               /* -40: -70..0; level floor of the strongest component */
+    float second_db;                    /* 10: 3..30; how far the second component may lie below the first and still make a pair */
+    float min_share;                    /* 0.7: 0 < s <= 1; share of the frame's energy in the component(s) */
+    uint32_t tol_hz;                    /* 20: 1..200; two records are the same tone when each frequency differs by at most this */
+    uint32_t min_tone_ms, min_pause_ms; /* 60, 30: 10..5000; frames = ms / frame_shift_ms, at least 1 */
+    uint32_t flags;                     /* 0 */
+} AprilxToneOptions;
+enum { APRILX_TONE_ON = 1, APRILX_TONE_OFF = 2 };
+/* a single tone: f2_hz == 0; a pair: f1_hz < f2_hz (OFF carries the frequencies its ON carried) */
+typedef void (*AprilxToneHandler)(void *userdata, int kind, uint32_t f1_hz, uint32_t f2_hz, uint64_t time_ms);
+typedef struct AprilxToneInfo {
+    int32_t W, k_lo, F, on_frames, off_frames;
+    uint32_t held_f1, held_f2;          /* the tone held after the last frame read, or 0, 0 */
+    uint32_t reserved;
+    uint64_t frames_seen;               /* real frames of the session since its creation */
+    uint64_t tonal_frames;              /* frames with a tonal record, since the detector was last set */
+    uint64_t tones;                     /* ON events since the detector was last set */
+} AprilxToneInfo;
+/* the plan the kernel and the event machine work from (48 bytes); tests and users of aprilx_tone_host */
+typedef struct AprilxTonePlan {
+    int32_t W, k_lo, F; float half_w, min_power, second_ratio, min_share, bin_hz; int32_t tol_hz, on_frames, off_frames, reserved;
+} AprilxTonePlan;
+/* the event machine's state between calls of aprilx_tone_events_host: all zero at the start and after a flush */
+typedef struct AprilxToneMachine { int32_t held, h1, h2, c1, c2, run; } AprilxToneMachine;
+/* options = NULL: off.  0, or -1 and nothing changes: a wrong size, a value out of range, non-zero flags, a NULL handler with options,
+ * a model the detector refuses (W / rate below 20 ms, a rate below 6000 Hz, W above 4096, a grid of fewer than 8 or more than 128
+ * bins), or a session with audio fed since its last completed flush (the rule of aprilx_session_set_vad).  Setting resets the machine
+ * and its counters. */
+APRIL_EXPORT int aprilx_session_set_tones(AprilASRSession session, const AprilxToneOptions *options, AprilxToneHandler handler, void *userdata);
+/* 1 and the options / info when the detector is on, 0 (info: frames_seen only) when it is off, -1 on bad arguments; either pointer
+ * may be NULL.  Waits for the session to be idle. */
+APRIL_EXPORT int aprilx_session_tones(AprilASRSession session, AprilxToneOptions *options_out, AprilxToneInfo *out);
+/* The plan of a model with this rate, fft size and frame shift: 0, or -1 as above.  No GPU. */
+APRIL_EXPORT int aprilx_tone_plan(int sample_rate, int fft_size, int frame_shift_ms, const AprilxToneOptions *options, AprilxTonePlan *plan_out);
+/* The tables [2F][W] (row k cos, row F + k sin of bin k_lo + k) into out[cap]: 2 F W, or -1 (cap too small, a refused model).  No GPU. */
+APRIL_EXPORT int aprilx_tone_tables(int sample_rate, int fft_size, float *out, size_t cap);
+/* The contract on the host: frame i at frames + i * ld (ld >= W samples) through steps 1-7; records_out [n][2] uint16, powers_out
+ * [n][F + 1] (P[0..F) and E) or NULL.  No GPU. */
+APRIL_EXPORT int aprilx_tone_host(const AprilxTonePlan *plan, const float *tables, int n, const int16_t *frames, size_t ld, uint16_t *records_out,
+                                  float *powers_out);
+/* steps 3-7 on one row of P[0..F), E (F + 1 values): the record as lo | hi << 16, or -1 on bad arguments.  No GPU. */
+APRIL_EXPORT int64_t aprilx_tone_decide_host(const AprilxTonePlan *plan, const float *powers);
+/* Events from the records ([n][2] uint16) of frames [t0, t0 + n) from *machine: kinds_out / f1_out / f2_out / times_out (cap entries
+ * each) receive them in order; flush != 0: a flush then completes at frame t0 + n.  Returns their number (may exceed cap: nothing is
+ * written past it).  No GPU. */
+APRIL_EXPORT int aprilx_tone_events_host(const AprilxTonePlan *plan, int frame_shift_ms, uint64_t t0, const uint16_t *records, size_t n, int flush,
+                                         AprilxToneMachine *machine, int32_t *kinds_out, uint32_t *f1_out, uint32_t *f2_out, uint64_t *times_out, int cap);
+/* "dial" 350 + 440, "busy" 480 + 620, "cp425" 425, "cng" 1100, "ced" 2100, "sit1" 950, "sit2" 1400, "sit3" 1800 Hz: the static name
+ * of the first entry all of whose frequencies lie within tol_hz of the given ones, or NULL. */
+APRIL_EXPORT const char *aprilx_tone_name(uint32_t f1_hz, uint32_t f2_hz, uint32_t tol_hz);
+/* Tests only: tone_kernel on n_runs runs in ONE launch.  Run r has its own options and n[r] frames, consecutive in
+ * frames[sum n][fft_size] as for aprilx_run_fbank; records_out [sum n][2], powers_out [sum n][F + 1] or NULL.  0, or -1 on bad arguments. */
+APRIL_EXPORT int aprilx_run_tones(AprilASRModel model, const AprilxToneOptions *options, int n_runs, const int32_t *n, const int16_t *frames,
+                                  uint16_t *records_out, float *powers_out);
+/* Tests only: the kernel's decision alone on n given rows of P[0..F), E; records_out [n][2].  0, or -1. */
+APRIL_EXPORT int aprilx_run_tone_decide(AprilASRModel model, const AprilxToneOptions *options, int n, const float *powers, uint16_t *records_out);
+/* Tone launches and the frames they covered on one GPU's engine, and (while profiling) the kernel's accumulated ms.  0, or -1. */
+APRIL_EXPORT int aprilx_model_tone_stats(AprilASRModel model, int device_index, uint64_t *launches, uint64_t *frames, double *ms);
+
 typedef struct AprilxStats {
     uint64_t ticks, steps, chunks, rounds, frames, max_batch_seen;
     /* per kernel class: accumulated ms and launch counts while profiling is enabled
