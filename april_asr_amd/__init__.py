@@ -22,7 +22,8 @@ from . import _ffi
 
 __all__ = ["Result", "Token", "Model", "Session", "SessionGroup", "Bias", "VadEvent", "resampler_taps", "decode_host", "vad_plan", "vad_host", "vad_events_host",
            "DtmfEvent", "dtmf_plan", "dtmf_tables", "dtmf_host", "dtmf_decide_host", "dtmf_events_host",
-           "ToneEvent", "tone_plan", "tone_tables", "tone_host", "tone_decide_host", "tone_events_host", "tone_name"]
+           "ToneEvent", "tone_plan", "tone_tables", "tone_host", "tone_decide_host", "tone_events_host", "tone_name",
+           "snapshot_info"]
 
 
 class Result(IntEnum):
@@ -457,6 +458,13 @@ class Model:
         """(launches, frames, ms): VAD launches of one GPU's engine, the frames they covered, and (while profiling) the kernel's time"""
         return self._detector_stats(self._L.aprilx_model_vad_stats, device_index)
 
+    def snapshot_stats(self, device_index: int = 0):
+        """(gathers, scatters, gather_ms, scatter_ms): snapshot / restore launches of one GPU's engine and (while profiling) their kernel time"""
+        g, s, gm, sm = C.c_uint64(0), C.c_uint64(0), C.c_double(0), C.c_double(0)
+        if self._L.aprilx_model_snapshot_stats(self._handle, device_index, C.byref(g), C.byref(s), C.byref(gm), C.byref(sm)) != 0:
+            raise ValueError("no such device")
+        return int(g.value), int(s.value), float(gm.value), float(sm.value)
+
     def stats(self, device_index: int = 0):
         s = _ffi.AprilxStats()
         self._L.aprilx_model_stats(self._handle, device_index, C.byref(s))
@@ -825,6 +833,27 @@ class Session:
         """Asynchronous sessions: wait until everything queued so far was processed."""
         self._L.aprilx_session_drain(self._handle)
 
+    def snapshot(self) -> bytes:
+        """Everything dynamic the session holds, as a self-contained blob (aprilx_session_snapshot).  Waits until the
+        session is idle and leaves it as it is: it may go on (a fork) or be closed (a move).  RuntimeError inside a flush or a handler."""
+        n = int(self._L.aprilx_session_snapshot(self._handle, None, 0))
+        if n < 0:
+            raise RuntimeError("snapshot refused (a flush under way, or called from one of the session's handlers)")
+        buf = (C.c_char * n)()
+        got = int(self._L.aprilx_session_snapshot(self._handle, C.addressof(buf), n))
+        if got < 0:
+            raise RuntimeError("snapshot refused (the session changed between the two calls)")
+        return bytes(buf[:got])
+
+    def restore(self, blob) -> None:
+        """Loads a snapshot into this FRESH session (aprilx_session_restore): same model and precision, configured as the source was
+        (snapshot_info(blob) has the configuration).  From here on it continues the source's stream bit for bit.  ValueError with the
+        library's reason when refused; the session stays usable."""
+        b = bytes(blob)
+        err = C.create_string_buffer(256)
+        if self._L.aprilx_session_restore(self._handle, b, len(b), err, 256) != 0:
+            raise ValueError("restore refused: %s" % err.value.decode(errors="replace"))
+
     def chunks(self) -> int:
         return int(self._L.aprilx_session_chunks(self._handle))
 
@@ -936,6 +965,54 @@ class SessionGroup:
 
     def flush(self):
         self._L.aprilx_flush_many(len(self.sessions), self._handles)
+
+    def snapshot(self):
+        """One blob per session (aprilx_snapshot_many): the device state of all sessions of an engine moves in ONE gather launch.
+        RuntimeError when a session is refused."""
+        n = len(self.sessions)
+        sizes = (C.c_int64 * n)()
+        if self._L.aprilx_snapshot_many(n, self._handles, None, None, sizes) != 0:
+            raise RuntimeError("snapshot refused for sessions %r" % [i for i in range(n) if sizes[i] < 0])
+        bufs = [(C.c_char * int(sizes[i]))() for i in range(n)]
+        dsts = (C.c_void_p * n)(*[C.addressof(b) for b in bufs])
+        caps = (C.c_size_t * n)(*[int(sizes[i]) for i in range(n)])
+        if self._L.aprilx_snapshot_many(n, self._handles, dsts, caps, sizes) != 0:
+            raise RuntimeError("snapshot refused for sessions %r" % [i for i in range(n) if sizes[i] < 0])
+        return [bytes(bufs[i][:int(sizes[i])]) for i in range(n)]
+
+    def restore(self, blobs):
+        """blobs[i] into session i (aprilx_restore_many): one scatter launch per engine.  ValueError lists the sessions that were
+        refused (the library logs each reason); the others have been restored."""
+        n = len(self.sessions)
+        keep = [bytes(b) for b in blobs]
+        ptrs = (C.c_char_p * n)(*keep)
+        sizes = (C.c_size_t * n)(*[len(b) for b in keep])
+        status = (C.c_int * n)()
+        if self._L.aprilx_restore_many(n, self._handles, ptrs, sizes, status) != 0:
+            raise ValueError("restore refused for sessions %r" % [i for i in range(n) if status[i] != 0])
+
+
+def snapshot_info(blob) -> dict:
+    """The configuration, model identity and progress stored in a snapshot (aprilx_snapshot_info; no GPU, no model): enough to configure
+    a receiving session from the blob alone -- `input_rate`, `input_format` ((encoding, channels, channel) or None), `alternatives`,
+    `search_options` ((endpoint_silence_ms, blank_penalty, max_utterance_ms) or None), `vad` / `dtmf` / `tones` (option dicts or None),
+    `bias` ({flags, states, edges, hash} or None: the set itself is the caller's to rebuild).  ValueError when the blob does not parse."""
+    b = bytes(blob)
+    i = _ffi.AprilxSnapshotInfo()
+    if _ffi.lib().aprilx_snapshot_info(b, len(b), C.byref(i)) != 0:
+        raise ValueError("not a snapshot, or a corrupt one")
+    d = {n: int(getattr(i, n)) for n in ("version", "blob_size", "params_hash", "token_hash", "chunks", "frames_seen", "now_ms", "rows_written", "n_layers", "d_model",
+                                         "hidden", "ffn", "joiner", "vocab", "mel", "segment_size", "segment_step", "sample_rate", "frame_shift_ms", "blank_id",
+                                         "precision", "f16_tile", "input_rate", "ring_rows")}
+    d["name"], d["description"] = i.name.decode(errors="replace"), i.description.decode(errors="replace")
+    d["alternatives"] = int(i.confidence_k)
+    d["input_format"] = (_ENC_NAMES[int(i.format.encoding)], int(i.format.channels), int(i.format.channel)) if i.has_format else None
+    d["search_options"] = (int(i.search.endpoint_silence_ms), float(i.search.blank_penalty), int(i.search.max_utterance_ms)) if i.has_search_options else None
+    d["vad"] = {n: getattr(i.vad, n) for n in _VAD_FIELDS} if i.has_vad else None
+    d["dtmf"] = {n: getattr(i.dtmf, n) for n in _DTMF_FIELDS} if i.has_dtmf else None
+    d["tones"] = {n: getattr(i.tones, n) for n in _TONE_FIELDS} if i.has_tones else None
+    d["bias"] = dict(flags=int(i.bias_flags), states=int(i.bias_states), edges=int(i.bias_edges), hash=int(i.bias_hash)) if i.has_bias else None
+    return d
 
 
 ENCODINGS = {"s16": 0, "mulaw": 1, "alaw": 2, "f32": 3}      # APRILX_ENC_*

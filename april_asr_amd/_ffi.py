@@ -134,6 +134,18 @@ class AprilxInputFormat(C.Structure):
     _fields_ = [("size", C.c_uint32), ("encoding", C.c_uint32), ("channels", C.c_uint32), ("channel", C.c_int32)]
 
 
+class AprilxSnapshotInfo(C.Structure):
+    _fields_ = ([("size", C.c_uint32), ("version", C.c_uint32), ("blob_size", C.c_uint64), ("params_hash", C.c_uint64), ("token_hash", C.c_uint64),
+                 ("bias_hash", C.c_uint64), ("bias_edges", C.c_int64), ("chunks", C.c_uint64), ("frames_seen", C.c_uint64), ("now_ms", C.c_uint64),
+                 ("rows_written", C.c_uint64)]
+                + [(n, C.c_int32) for n in ("n_layers", "d_model", "hidden", "ffn", "joiner", "vocab", "mel", "segment_size", "segment_step", "sample_rate",
+                                            "frame_shift_ms", "blank_id")]
+                + [(n, C.c_uint32) for n in ("precision", "f16_tile", "input_rate", "confidence_k", "has_format", "has_search_options", "has_vad", "has_dtmf",
+                                             "has_tones", "has_bias", "bias_flags")]
+                + [("bias_states", C.c_int32), ("ring_rows", C.c_uint32), ("reserved", C.c_uint32), ("format", AprilxInputFormat), ("search", AprilxSearchOptions),
+                   ("vad", AprilxVadOptions), ("dtmf", AprilxDtmfOptions), ("tones", AprilxToneOptions), ("name", C.c_char * 64), ("description", C.c_char * 128)])
+
+
 EXPORTED_REFERENCE_SYMBOLS = [
     "aam_api_init", "aam_create_model", "aam_get_name", "aam_get_description", "aam_get_language",
     "aam_get_sample_rate", "aam_free", "aas_create_session", "aas_feed_pcm16", "aas_flush",
@@ -161,6 +173,7 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_dtmf_events_host", "aprilx_run_dtmf", "aprilx_run_dtmf_decide", "aprilx_model_dtmf_stats",
     "aprilx_session_set_tones", "aprilx_session_tones", "aprilx_tone_plan", "aprilx_tone_tables", "aprilx_tone_host", "aprilx_tone_decide_host",
     "aprilx_tone_events_host", "aprilx_tone_name", "aprilx_run_tones", "aprilx_run_tone_decide", "aprilx_model_tone_stats",
+    "aprilx_session_snapshot", "aprilx_session_restore", "aprilx_snapshot_info", "aprilx_snapshot_many", "aprilx_restore_many", "aprilx_model_snapshot_stats",
 ]
 
 _lib = None
@@ -290,6 +303,13 @@ def lib():
     L.aprilx_run_tones.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]; L.aprilx_run_tones.restype = C.c_int
     L.aprilx_run_tone_decide.argtypes = [vp, C.POINTER(AprilxToneOptions), C.c_int, vp, vp]; L.aprilx_run_tone_decide.restype = C.c_int
     L.aprilx_model_tone_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]; L.aprilx_model_tone_stats.restype = C.c_int
+    L.aprilx_session_snapshot.argtypes = [vp, vp, sz]; L.aprilx_session_snapshot.restype = C.c_int64
+    L.aprilx_session_restore.argtypes = [vp, vp, sz, vp, sz]; L.aprilx_session_restore.restype = C.c_int
+    L.aprilx_snapshot_info.argtypes = [vp, sz, C.POINTER(AprilxSnapshotInfo)]; L.aprilx_snapshot_info.restype = C.c_int
+    L.aprilx_snapshot_many.argtypes = [sz, vp, vp, vp, vp]; L.aprilx_snapshot_many.restype = C.c_int
+    L.aprilx_restore_many.argtypes = [sz, vp, vp, vp, vp]; L.aprilx_restore_many.restype = C.c_int
+    L.aprilx_model_snapshot_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.aprilx_model_snapshot_stats.restype = C.c_int
     _lib = L
     return L
 

@@ -410,6 +410,8 @@ Engine::~Engine()
     if (bias_state_d_) (void)hipFree(bias_state_d_);
     for (void *p : {(void *)vad_state_d_, (void *)pass_out_d_}) if (p) (void)hipFree(p);
     for (PassBlock &k : pass_blocks_) (void)hipHostFree(k.h);
+    if (snap_d_) (void)hipFree(snap_d_);
+    if (snap_h_) (void)hipHostFree(snap_h_);
     if (ws_g_) (void)hipFree(ws_g_);
     if (conv_wt_) (void)hipFree(conv_wt_);
     if (dec_table_) (void)hipFree(dec_table_);
@@ -2285,5 +2287,90 @@ void Engine::read_ring(int slot, int row, int n_rows, float *out)
     for (int i = 0; i < n_rows; ++i)
         HIP_CHECK(hipMemcpy(out + (size_t)i * nb, ring_ + ((size_t)slot * ring_frames_ + (row + i) % ring_frames_) * nb, (size_t)nb * 4, hipMemcpyDeviceToHost));
 }
+
+// ---------------------------------------------------------------- snapshot
+Engine::SnapLayout Engine::snapshot_layout() const
+{
+    const NetDims &d = L_.dims;
+    SnapLayout l;
+    const uint32_t L = (uint32_t)d.n_layers;
+    const uint32_t rows[SNAP_ARRAYS] = {L, L, h16_ ? L : 0u, 1u, 1u, 1u, 1u, 1u, 0u};
+    const uint32_t bytes[SNAP_ARRAYS] = {(uint32_t)d.d_model * 4u, (uint32_t)d.hidden * 4u, (uint32_t)d.d_model * 2u, (uint32_t)d.joiner * 4u, (uint32_t)d.joiner * 4u,
+                                         (uint32_t)sizeof(GreedyState), 4u, (uint32_t)sizeof(VadState), (uint32_t)d.mel * 4u};
+    uint32_t off = 0;
+    for (int i = 0; i < SNAP_ARRAYS; ++i) {
+        l.arr[i].layers = rows[i]; l.arr[i].row_bytes = bytes[i]; l.arr[i].off = off;
+        off += (rows[i] * bytes[i] + 15u) / 16u * 16u;
+    }
+    l.fixed = off;
+    return l;
+}
+
+// The one body of gather and scatter.  Stepping thread, between flights: the session's flights have completed, and sync() leaves no
+// stream with work the copy could overtake; a fresh slot's reset launch is in stream_, the scatter goes behind it on the same stream.
+bool Engine::snapshot_copy(int n, SnapRec *recs, uint8_t *const *blocks, bool scatter)
+{
+    if (n <= 0) return true;
+    if (n > 65535) return false;                                   // (grid.y; max_slots is far below)
+    HIP_CHECK(hipSetDevice(cfg_.device));
+    const NetDims &d = L_.dims;
+    const SnapLayout lay = snapshot_layout();
+    size_t total = ((size_t)n * sizeof(SnapRec) + 255) / 256 * 256;
+    uint32_t max_block = 0;
+    bool want_vad = false;
+    for (int i = 0; i < n; ++i) {
+        SnapRec &r = recs[i];
+        const int tail = scatter ? r.tgt_tail : r.tail;
+        if (r.slot < 0 || r.slot >= cfg_.max_slots || r.rows < 0 || r.rows > ring_frames_ || tail < 0 || tail >= ring_frames_) return false;
+        r.block_bytes = lay.block_bytes(r.rows); r.stage_off = total;
+        total += r.block_bytes;
+        max_block = std::max(max_block, r.block_bytes);
+        want_vad = want_vad || ((r.mask >> SNAP_VAD) & 1u);
+    }
+    // (the queues first: apply_slot_tables returns a slot with a queued bias change to the root, which must not follow a scatter)
+    if (conf_q_.has_pending() || bias_q_.has_pending() || opt_q_.has_pending()) apply_slot_tables();
+    std::lock_guard<std::mutex> cg(capture_mu_);
+    sync();                                                        // (m_touched() inside: the copy is an enqueue on M like any other)
+    if (scatter && want_vad && !vad_state_d_) vad_state_d_ = dmalloc<VadState>((size_t)cfg_.max_slots);
+    if (scatter) for (int i = 0; i < n; ++i) if (((recs[i].mask >> SNAP_BIAS) & 1u) && !bias_state_d_) return false;      // (a session with a set: its table exists)
+    if (total > snap_cap_) {
+        HipLegacyLock legacy;
+        if (snap_d_) { HIP_CHECK(hipFree(snap_d_)); HIP_CHECK(hipHostFree(snap_h_)); snap_d_ = snap_h_ = nullptr; }
+        snap_cap_ = std::max(total, 2 * snap_cap_);
+        snap_d_ = dmalloc<char>(snap_cap_); snap_h_ = hmalloc<char>(snap_cap_);
+    }
+    SnapArgs a;
+    const size_t S = (size_t)cfg_.max_slots;
+    char *const base[SNAP_ARRAYS] = {(char *)h_, (char *)c_, (char *)h16_, (char *)eout_, (char *)dout_, (char *)gstate_, (char *)bias_state_d_, (char *)vad_state_d_, (char *)ring_};
+    bool wide = ((uintptr_t)snap_d_ % 16) == 0;
+    for (int i = 0; i < SNAP_ARRAYS; ++i) {
+        SnapArray &x = a.arr[i];
+        x.base = base[i]; x.layers = lay.arr[i].layers; x.row_bytes = lay.arr[i].row_bytes; x.off = lay.arr[i].off; x.ring = i == SNAP_RING;
+        x.slot_stride = i == SNAP_RING ? (unsigned long long)ring_frames_ * (unsigned long long)d.mel * 4ull : x.row_bytes;
+        x.layer_stride = i == SNAP_RING ? x.row_bytes : (unsigned long long)S * x.row_bytes;
+        // (the trie state is one word per slot: the kernel moves that word alone, whatever the width of the other accesses)
+        if (x.base && (x.layers || x.ring) && x.row_bytes != 4) wide = wide && (uintptr_t)x.base % 16 == 0 && x.slot_stride % 16 == 0 && x.layer_stride % 16 == 0 && x.row_bytes % 16 == 0;
+    }
+    a.n_arr = SNAP_ARRAYS; a.n = n; a.recs = reinterpret_cast<const SnapRec *>(snap_d_); a.stage = snap_d_; a.ring_frames = ring_frames_;
+    a.scatter = scatter ? 1 : 0; a.vec = wide ? 16 : 4; a.max_block = max_block;
+    memcpy(snap_h_, recs, (size_t)n * sizeof(SnapRec));
+    if (scatter) {
+        for (int i = 0; i < n; ++i) memcpy(snap_h_ + recs[i].stage_off, blocks[i], recs[i].block_bytes);
+        HIP_CHECK(hipMemcpyAsync(snap_d_, snap_h_, total, hipMemcpyHostToDevice, stream_));
+    } else {
+        HIP_CHECK(hipMemcpyAsync(snap_d_, snap_h_, (size_t)n * sizeof(SnapRec), hipMemcpyHostToDevice, stream_));
+    }
+    const int cls = scatter ? T_SNAP_SCATTER : T_SNAP_GATHER;
+    timed_begin(cls); launch_snapshot_copy(a, stream_); timed_end(cls);
+    if (!scatter) HIP_CHECK(hipMemcpyAsync(snap_h_, snap_d_, total, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    if (profiling_) collect_timing();
+    if (!scatter) for (int i = 0; i < n; ++i) memcpy(blocks[i], snap_h_ + recs[i].stage_off, recs[i].block_bytes);
+    (scatter ? snap_scatters_ : snap_gathers_).fetch_add(1, std::memory_order_relaxed);
+    return true;
+}
+
+bool Engine::snapshot_gather(int n, SnapRec *recs, uint8_t *const *blocks_out) { return snapshot_copy(n, recs, blocks_out, false); }
+bool Engine::snapshot_scatter(int n, SnapRec *recs, const uint8_t *const *blocks) { return snapshot_copy(n, recs, const_cast<uint8_t *const *>(blocks), true); }
 
 }  // namespace aprilx

@@ -324,6 +324,28 @@ public:
     void read_ring(int slot, int row, int n_rows, float *out);
     void read_greedy_state(int slot, GreedyState *out);
 
+    // ---- session snapshot / restore (engine.cc "snapshot").  A session's DEVICE BLOCK is the bytes of its slot's
+    // rows of the arrays below, in this order, each at a 16-byte aligned offset; the ring contributes the rows the session's book can
+    // still name.  The layout depends on the model's dimensions and the precision only.
+    enum { SNAP_H = 0, SNAP_C = 1, SNAP_H16 = 2, SNAP_EOUT = 3, SNAP_DOUT = 4, SNAP_GSTATE = 5, SNAP_BIAS = 6, SNAP_VAD = 7, SNAP_RING = 8, SNAP_ARRAYS = 9 };
+    struct SnapLayout {
+        struct Arr { uint32_t layers = 0, row_bytes = 0, off = 0; } arr[SNAP_ARRAYS];      // (h16: 0 layers unless the engine keeps it; ring: layers 0, off = fixed)
+        uint32_t fixed = 0;                                                                   // bytes in front of the ring rows
+        uint32_t block_bytes(int ring_rows) const { return fixed + ((uint32_t)ring_rows * arr[SNAP_RING].row_bytes + 15u) / 16u * 16u; }
+    };
+    SnapLayout snapshot_layout() const;
+    // Both: stepping thread only, between flights (Scheduler::run_on_loop).  ONE kernel launch and one staging copy for all n sessions;
+    // they return after a stream wait.  recs[i]: slot, tail / tgt_tail, rows and mask from the caller (checked here: false, and nothing
+    // is launched, on a slot, a row count or a tail out of range); block_bytes and stage_off are filled in.  Queued slot-table changes
+    // are applied first (a restored trie state must not be returned to the root by a change that was still queued).
+    bool snapshot_gather(int n, SnapRec *recs, uint8_t *const *blocks_out);
+    bool snapshot_scatter(int n, SnapRec *recs, const uint8_t *const *blocks);
+    // gather and scatter launches so far (any thread)
+    void snapshot_counts(uint64_t *gathers, uint64_t *scatters) const
+    {
+        *gathers = snap_gathers_.load(std::memory_order_relaxed); *scatters = snap_scatters_.load(std::memory_order_relaxed);
+    }
+
     // ---- profiling: when enabled every launch of the named classes is bracketed by hipEvents
     void set_profiling(bool on);
     // Gates clock (bench.py's roofline): while it is on, the feed-wavefront launch plans are built with a stamp slot per gates launch
@@ -338,7 +360,8 @@ public:
     // split feeds launched as hostable (any thread)
     void ramp_counts(uint64_t *hosted, uint64_t *eligible);
     void reset_timing();
-    enum { T_GATES = 0, T_GEMM_OTHER = 1, T_ROW = 2, T_CONV = 3, T_FBANK = 4, T_DEC = 5, T_RESAMPLE = 6, T_DECODE = 7, T_VAD = 8, T_DTMF = 9, T_TONE = 10, T_COUNT = 11 };
+    enum { T_GATES = 0, T_GEMM_OTHER = 1, T_ROW = 2, T_CONV = 3, T_FBANK = 4, T_DEC = 5, T_RESAMPLE = 6, T_DECODE = 7, T_VAD = 8, T_DTMF = 9, T_TONE = 10,
+           T_SNAP_GATHER = 11, T_SNAP_SCATTER = 12, T_COUNT = 13 };
     long kernels_per_step() const { return kernels_per_step_.load(std::memory_order_relaxed); }    // launches of the last eagerly issued chunk chain
 
 private:
@@ -505,8 +528,12 @@ private:
     const float *tn_tables_ = nullptr; int tn_w_ = 0, tn_f_ = 0;      // [2F][W] on the device, uploaded once (freed with table_allocs_)
     std::atomic<uint64_t> tn_launches_{0}, tn_frames_{0};
     const float *tone_tables();
+    // snapshot / restore: nothing below is allocated until the first call
+    bool snapshot_copy(int n, SnapRec *recs, uint8_t *const *blocks, bool scatter);
+    char *snap_d_ = nullptr, *snap_h_ = nullptr; size_t snap_cap_ = 0;      // device staging and its pinned twin: the records, then the blocks
+    std::atomic<uint64_t> snap_gathers_{0}, snap_scatters_{0};
     std::mutex rs_mu_;
-    std::map<const ResampleSpec *, const float *> rs_tables_;     // phase tables on the device, uploaded at first use (freed with table_allocs_)
+    std::map<const ResampleSpec *, const float *> rs_tables_;    // phase tables on the device, uploaded at first use (freed with table_allocs_)
     const float *resample_table(const ResampleSpec *spec);
     // fbank tables on device
     FbankTables ft_;

@@ -336,6 +336,26 @@ struct ZeroSlotArgs {
 };
 void launch_zero_slot(const ZeroSlotArgs &a, hipStream_t s);
 
+// Session snapshot / restore: one launch moves the per-slot state of n sessions between the engine's arrays and a
+// staging buffer that holds one device block per session.  A block is the concatenation of the arrays below at 16-byte aligned offsets:
+// array i contributes `layers` rows of row_bytes bytes (row l of slot s at base + s * slot_stride + l * layer_stride) at block offset off.
+// The last array may be the feature ring (ring != 0): its row count comes from the session's record, row r of the block is ring row
+// (tail + r) % ring_frames.  Arrays whose bit is clear in the record's mask are skipped (gather leaves zeros, scatter leaves the slot's).
+constexpr int kSnapMaxArrays = 10;
+struct SnapArray { char *base = nullptr; unsigned long long slot_stride = 0, layer_stride = 0; uint32_t layers = 0, row_bytes = 0, off = 0, ring = 0; };
+struct SnapRec { int32_t slot = 0, tail = 0, rows = 0, tgt_tail = 0; uint32_t mask = 0, block_bytes = 0; unsigned long long stage_off = 0; };
+static_assert(sizeof(SnapRec) == 32, "uploaded as bytes");
+struct SnapArgs {
+    SnapArray arr[kSnapMaxArrays]; int n_arr = 0;
+    const SnapRec *recs = nullptr; int n = 0;      // device
+    char *stage = nullptr;                         // device: block i at stage + recs[i].stage_off
+    int ring_frames = 0;
+    int scatter = 0;                               // 0: arrays -> staging (ring rows from tail); 1: staging -> arrays (ring rows to tgt_tail)
+    int vec = 4;                                   // bytes per lane and access: 16 where every base, stride, width and offset is a multiple of 16, else 4
+    uint32_t max_block = 0;                        // the largest block of the call (sizes the grid)
+};
+void launch_snapshot_copy(const SnapArgs &a, hipStream_t s);
+
 // Search bookkeeping of one BLOCK of time steps of a layer-major step, so that the search's launch chain has arguments that do
 // not depend on the block (one captured graph serves every block): the block's session times and encoder-output row numbers
 // are copied to fixed places, the record offset of the block is derived from the step's, the round flags are cleared.

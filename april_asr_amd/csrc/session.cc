@@ -409,6 +409,8 @@ Scheduler::~Scheduler()
     { std::lock_guard<std::mutex> g(mu_); stop_ = true; }
     cv_work_.notify_all();
     if (thread_.joinable()) thread_.join();
+    { std::lock_guard<std::mutex> g(mu_); for (LoopCall *c : calls_) c->done = true; calls_.clear(); }      // (their fn never ran; the model is going away)
+    cv_done_.notify_all();
 }
 
 void Scheduler::attach(Session *s)
@@ -640,7 +642,25 @@ void Scheduler::deliver_sync_events(Session *s)
 {
     std::vector<Event> ev;
     { std::lock_guard<std::mutex> g(mu_); ev.swap(s->done_events); }
+    if (ev.empty()) return;
+    s->delivering_tid = std::this_thread::get_id();
+    s->delivering.store(true, std::memory_order_release);
     deliver_events(ev, s->handlers);
+    s->delivering.store(false, std::memory_order_release);
+}
+
+bool Scheduler::run_on_loop(const std::function<void()> &fn)
+{
+    if (on_loop_thread()) return false;
+    LoopCall call{&fn};
+    std::unique_lock<std::mutex> lk(mu_);
+    if (stop_) return false;
+    calls_.push_back(&call);
+    calls_waiting_.store((int)calls_.size(), std::memory_order_release);
+    work_seq_.fetch_add(1, std::memory_order_release);
+    cv_work_.notify_one();
+    cv_done_.wait(lk, [&] { return call.done; });
+    return true;
 }
 
 // One stepping thread, TWO flights in the air.  A flight is launched (frames cut, chunk steps enqueued, record copy + event
@@ -661,7 +681,8 @@ bool Scheduler::collect(std::vector<Session *> &work, std::vector<uint64_t> &tak
         for (Session *s : sessions_) if (!s->closing && (s->fed || s->flush_requested)) return true;
         return false;
     };
-    if (block) cv_work_.wait(lk, [&] { return stop_ || have(); });
+    if (block) cv_work_.wait(lk, [&] { return stop_ || have() || !calls_.empty(); });
+    if (!calls_.empty()) { work_seen = work_seq_.load(std::memory_order_acquire); return false; }      // run_on_loop() requests go first (loop())
     work_seen = work_seq_.load(std::memory_order_acquire);
     if (stop_) return false;
     lap();
@@ -812,6 +833,17 @@ void Scheduler::loop()
     bool have_pending = false, have_next = false, cont = false;
     Flight pending, next;
     for (;;) {
+        // ---- run_on_loop() requests: between flights.  Whatever is in the air lands first (a tick that continues in a next flight ends first);
+        // nothing is launched until the requests have run
+        if (!cont && calls_waiting_.load(std::memory_order_acquire)) {
+            if (have_pending) { complete_flight(pending); have_pending = false; }
+            if (have_next) { complete_flight(next); next = Flight(); have_next = false; }
+            std::vector<LoopCall *> todo;
+            { std::lock_guard<std::mutex> g(mu_); todo.swap(calls_); calls_waiting_.store(0, std::memory_order_release); }
+            for (LoopCall *c : todo) (*c->fn)();
+            { std::lock_guard<std::mutex> g(mu_); for (LoopCall *c : todo) c->done = true; }
+            cv_done_.notify_all();
+        }
         // ---- launch: the continuation of a tick whose flight filled the rings first, else whatever has been queued
         if (!have_next) {
             bool go = cont;

@@ -20,6 +20,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -42,6 +43,7 @@ enum TokClass : uint8_t {
 };
 std::vector<uint8_t> classify_tokens(const ModelParams &p);
 
+namespace snap { struct Access; }
 struct JointResult { int32_t idx; float max_val; float blank_val; };     // what one joiner round hands to the search
 
 struct Event {
@@ -101,6 +103,7 @@ public:
     bool ctx_dirty = false;                   // decoder must be re-run for this session
 
 private:
+    friend struct snap::Access;               // snapshot.h: the state below as an image and back
     void push_ctx(int tok);
     void clear_context();
     void finalize_all(std::vector<Event> &out);
@@ -206,6 +209,8 @@ struct Session {
     std::chrono::steady_clock::time_point oldest_submit;   // when the oldest work not yet collected by the stepping thread was handed over
     bool has_oldest = false;
     std::vector<Event> done_events;           // sync sessions: events waiting for the caller thread
+    std::atomic<bool> delivering{false};      // a caller thread is inside deliver_sync_events() for this session ...
+    std::thread::id delivering_tid;           // ... this one (written before `delivering` is set)
     // (both read under Scheduler::mu_) everything queued so far has been processed ...
     bool idle() const { return closing || (completed >= submitted && !busy && !fed && !flush_requested); }
     // ... and nothing is queued, no segment is open, no flush is under way: the session's options may change
@@ -302,6 +307,13 @@ public:
     size_t latencies(double *out, size_t cap, bool reset);
     Engine *engine() { return eng_; }
     bool on_loop_thread() const { return std::this_thread::get_id() == loop_tid_; }
+    // Runs `fn` on the stepping thread BETWEEN flights -- every flight that was launched has completed, none is launched until fn returns --
+    // and waits for it.  Work that must not meet a graph capture or a flight in the air (snapshot / restore) goes
+    // through here.  fn runs without mu_.  False, and fn does not run: called from the stepping thread itself (a handler), or the
+    // scheduler is stopping.
+    bool run_on_loop(const std::function<void()> &fn);
+    // the calling thread is inside one of this session's handlers right now (asynchronous: the stepping thread; synchronous: its caller's)
+    bool in_own_handler(const Session *s) const { return on_loop_thread() || (s->delivering.load(std::memory_order_acquire) && s->delivering_tid == std::this_thread::get_id()); }
 
 private:
     // one launched flight: the sessions it serves, their tickets, and how many replay items / chunks it added per session
@@ -364,6 +376,9 @@ private:
     static constexpr int wave_max_chunks_ = 7;       // ... of at most this many chunks
     int lm_min_chunks_ = 8;                          // APRIL_LM_MIN_CHUNKS: sessions with at least this many chunks waiting take the layer-major path (0 = never)
     std::vector<Session *> sessions_;
+    struct LoopCall { const std::function<void()> *fn; bool done = false; };
+    std::vector<LoopCall *> calls_;                // guarded by mu_: run_on_loop() requests the stepping thread has not served yet
+    std::atomic<int> calls_waiting_{0};
     bool stop_ = false;
     std::thread thread_;
     SchedStats stats_;                             // guarded by mu_

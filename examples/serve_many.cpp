@@ -5,7 +5,7 @@
 //
 //   g++ -O2 -std=c++17 examples/serve_many.cpp -I include -L april_asr_amd -laprilasr -Wl,-rpath,$PWD/april_asr_amd -o serve_many
 //   ./serve_many model.april audio.raw [sessions=64] [mode=pipelined|lockstep] [input_rate] [--alternatives K] [--bias FILE [--bias-strict]]
-//               [--endpoint-ms N] [--blank-penalty X] [--vad] [--dtmf] [--tones]
+//               [--endpoint-ms N] [--blank-penalty X] [--vad] [--dtmf] [--tones] [--migrate S]
 //
 // Every session gets the same PCM16 file, rotated by (session index x 0.37 s) so that the streams differ.  With `input_rate` the file
 // is PCM16 at that rate and every session is told so (aprilx_session_set_input_rate): the library converts it to the model's rate on
@@ -25,6 +25,8 @@
 // ends with " dtmf <digits>" ("-" when no key was found).
 // `--tones` (anywhere on the line): every session gets the tone detector with its default options (aprilx_session_set_tones); its line then
 // ends with " tones" and one "<name or f1[+f2]>@<on ms>-<off ms>" per tone ("-" when none was found), the names aprilx_tone_name()'s.
+// `--migrate S` (anywhere on the line): after S feeds every stream is snapshotted (aprilx_snapshot_many), freed, and restored into a new
+// session configured the same way (aprilx_restore_many), then the feeds go on: the printed lines equal those of a run without the flag.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -91,6 +93,14 @@ int main(int argc, char **argv)
     long endpoint_ms = -1;
     const char *blank_penalty = nullptr;
     bool vad = false, dtmf = false, tones = false;
+    long migrate = -1;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!strcmp(argv[i], "--migrate")) {
+            migrate = atol(argv[i + 1]);
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
     for (int i = 1; i < argc; ++i)
         if (!strcmp(argv[i], "--tones")) {
             tones = true;
@@ -197,7 +207,8 @@ int main(int argc, char **argv)
     std::vector<Stream> streams((size_t)n);
     std::vector<AprilASRSession> sessions((size_t)n);
     std::vector<std::vector<short>> audio((size_t)n);
-    for (int i = 0; i < n; ++i) {
+    // a session for stream i, configured by the command line: at the start, and again for the restored copy of a migrated stream
+    auto make_session = [&](int i) -> int {
         AprilConfig cfg;
         memset(&cfg, 0, sizeof cfg);
         cfg.handler = on_result; cfg.userdata = &streams[(size_t)i];
@@ -225,6 +236,10 @@ int main(int argc, char **argv)
             AprilxToneOptions topt = {(uint32_t)sizeof topt, -40.0f, 10.0f, 0.7f, 20u, 60u, 30u, 0u};
             if (aprilx_session_set_tones(sessions[(size_t)i], &topt, on_tone, &streams[(size_t)i]) != 0) { fprintf(stderr, "tone options refused\n"); return 1; }
         }
+        return 0;
+    };
+    for (int i = 0; i < n; ++i) {
+        if (make_session(i) != 0) return 1;
         const size_t rot = ((size_t)i * (size_t)(0.37 * rate)) % pcm.size();
         audio[(size_t)i].assign(pcm.begin() + (long)rot, pcm.end());
         audio[(size_t)i].insert(audio[(size_t)i].end(), pcm.begin(), pcm.begin() + (long)rot);
@@ -232,7 +247,23 @@ int main(int argc, char **argv)
     std::vector<const short *> ptrs((size_t)n);
     std::vector<size_t> counts((size_t)n, step);
     const auto t0 = std::chrono::steady_clock::now();
+    double migrate_ms = 0; size_t migrate_bytes = 0;
     for (size_t k = 0; k < steps; ++k) {
+        if (migrate >= 0 && k == (size_t)migrate) {
+            // every stream moves: one gather launch per engine, free, create + configure, one scatter launch per engine
+            const auto m0 = std::chrono::steady_clock::now();
+            if (pipelined) aprilx_drain_many((size_t)n, sessions.data());
+            std::vector<int64_t> sizes((size_t)n);
+            if (aprilx_snapshot_many((size_t)n, sessions.data(), nullptr, nullptr, sizes.data()) != 0) { fprintf(stderr, "snapshot refused\n"); return 1; }
+            std::vector<std::vector<char>> blobs((size_t)n); std::vector<void *> dsts((size_t)n); std::vector<const void *> srcs((size_t)n); std::vector<size_t> caps((size_t)n);
+            for (int i = 0; i < n; ++i) { blobs[(size_t)i].resize((size_t)sizes[(size_t)i]); dsts[(size_t)i] = blobs[(size_t)i].data(); srcs[(size_t)i] = dsts[(size_t)i]; caps[(size_t)i] = blobs[(size_t)i].size(); migrate_bytes += caps[(size_t)i]; }
+            if (aprilx_snapshot_many((size_t)n, sessions.data(), dsts.data(), caps.data(), sizes.data()) != 0) { fprintf(stderr, "snapshot refused\n"); return 1; }
+            for (AprilASRSession s : sessions) aas_free(s);
+            for (int i = 0; i < n; ++i) if (make_session(i) != 0) return 1;
+            std::vector<int> status((size_t)n);
+            if (aprilx_restore_many((size_t)n, sessions.data(), srcs.data(), caps.data(), status.data()) != 0) { fprintf(stderr, "restore refused\n"); return 1; }
+            migrate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - m0).count();
+        }
         for (int i = 0; i < n; ++i) ptrs[(size_t)i] = audio[(size_t)i].data() + k * step;
         if (pipelined) aprilx_feed_many_pipelined((size_t)n, sessions.data(), ptrs.data(), counts.data(), 2);
         else aprilx_feed_many((size_t)n, sessions.data(), ptrs.data(), counts.data());
@@ -250,6 +281,8 @@ int main(int argc, char **argv)
     }
     fprintf(stderr, "%d streams x %.1f s of audio in %.1f ms (%s feed): %.0f audio-seconds per second\n", n, steps * 0.1, ms, pipelined ? "pipelined" : "lock-step",
             n * steps * 0.1 / (ms * 1e-3));
+    if (migrate >= 0) fprintf(stderr, "migrated %d streams after %ld feeds: %.1f KB per stream, %.2f ms for snapshot, free, create and restore of all\n", n, migrate,
+                              migrate_bytes / 1024.0 / n, migrate_ms);
     if (alternatives) {
         double sum = 0; size_t cnt = 0;
         for (const Stream &s : streams) { sum += s.conf_sum; cnt += s.conf_n; }

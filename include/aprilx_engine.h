@@ -528,6 +528,61 @@ APRIL_EXPORT int aprilx_run_tone_decide(AprilASRModel model, const AprilxToneOpt
 /* Tone launches and the frames they covered on one GPU's engine, and (while profiling) the kernel's accumulated ms.  0, or -1. */
 APRIL_EXPORT int aprilx_model_tone_stats(AprilASRModel model, int device_index, uint64_t *launches, uint64_t *frames, double *ms);
 
+/* ---- session snapshot and restore.  A stream is otherwise pinned to the slot, engine and process that created
+ * it.  A snapshot is a self-contained blob of everything dynamic a session holds at an IDLE point -- the slot's recurrent state, the
+ * encoder / decoder outputs, the search and trie state, the detectors' state, the feature-ring rows not yet consumed, the host's result
+ * state machine, the unconsumed audio tail and the counters -- plus the configuration and the model's identity.  Restored into a fresh
+ * session of the same model and precision that was configured the same way, the stream continues bit for bit: fed the same remaining
+ * audio in the same feed sizes it delivers the same callbacks, events, feature rows and counters as the source would have.  The blob
+ * is little-endian bytes ("APXSNAP1", a version, the total size, block offsets, FNV-1a 64 over everything before the trailing hash);
+ * moving it is the caller's.  NOT carried: handlers and userdata, the bias set itself (only its identity), logit tracing, the latency
+ * ring, aas_realtime_get_speedup's average.  AprilConfig.speaker stays ignored.
+ * The device part of n sessions moves in ONE gather (or scatter) kernel launch and one staging copy per engine per call, on the
+ * engine's stepping thread between flights. */
+typedef struct AprilxSnapshotInfo {
+    uint32_t size;                  /* sizeof(AprilxSnapshotInfo) */
+    uint32_t version;               /* blob format version: 1 */
+    uint64_t blob_size;
+    uint64_t params_hash;           /* FNV-1a 64 of the model's PARAMS fields (the 13 int32 of the reference's params block, in its order) */
+    uint64_t token_hash;            /* of the token list (the hash bias sets are checked with) */
+    uint64_t bias_hash;             /* FNV-1a 64 of the set's state_off, edge_tok, edge_next and edge_bonus arrays; 0 without a set */
+    int64_t bias_edges;
+    uint64_t chunks, frames_seen, now_ms, rows_written;   /* where the stream stands */
+    int32_t n_layers, d_model, hidden, ffn, joiner, vocab, mel, segment_size, segment_step, sample_rate, frame_shift_ms, blank_id;
+    uint32_t precision;             /* 0 fp32, 1 fp16 operands */
+    uint32_t f16_tile;              /* the engine keeps a binary16 copy of h, which the blob carries */
+    uint32_t input_rate;            /* Hz: what aprilx_session_input_rate returns */
+    uint32_t confidence_k;
+    uint32_t has_format, has_search_options, has_vad, has_dtmf, has_tones, has_bias;      /* 0 / 1: the structs below are meaningful */
+    uint32_t bias_flags; int32_t bias_states;
+    uint32_t ring_rows;             /* feature-ring rows in the blob */
+    uint32_t reserved;
+    AprilxInputFormat format;
+    AprilxSearchOptions search;
+    AprilxVadOptions vad;
+    AprilxDtmfOptions dtmf;
+    AprilxToneOptions tones;
+    char name[64], description[128];   /* aam_get_name / aam_get_description, truncated, NUL padded */
+} AprilxSnapshotInfo;
+/* Waits until the session is idle -- everything queued has been processed and its events delivered, as aprilx_session_drain does --,
+ * then writes the blob and leaves the session as it is (it may go on, or be freed).  dst == NULL: returns the bytes needed.  Else the
+ * bytes written, or -1: cap too small, a flush under way, or called from a handler of the session. */
+APRIL_EXPORT int64_t aprilx_session_snapshot(AprilASRSession session, void *dst, size_t cap);
+/* Loads a blob into a FRESH session (never fed since its creation) of the same model and precision whose input rate, format, K, search
+ * options, detectors and bias set were set as the source's were.  0, or -1 with a message in err (may be NULL): a corrupt blob, another
+ * model or precision, a configuration that differs, a session that was fed.  A refused session is untouched and usable. */
+APRIL_EXPORT int aprilx_session_restore(AprilASRSession session, const void *blob, size_t size, char *err, size_t err_cap);
+/* The configuration, identity and progress stored in a blob, so that a receiver can configure its session from the blob alone (the bias
+ * set is the caller's to rebuild).  Needs no GPU and no model.  0, or -1 on a blob that does not parse (never reads past size). */
+APRIL_EXPORT int aprilx_snapshot_info(const void *blob, size_t size, AprilxSnapshotInfo *out);
+/* Both for n sessions at once, grouped by engine inside: one gather / scatter launch per engine.  snapshot_many: caps[i] bytes at dsts[i]
+ * (dsts == NULL: only sizes_out), sizes_out[i] = bytes written / needed, or -1.  restore_many: status_out[i] = 0 or -1.  Both return the
+ * number of sessions that failed. */
+APRIL_EXPORT int aprilx_snapshot_many(size_t n, AprilASRSession *sessions, void *const *dsts, const size_t *caps, int64_t *sizes_out);
+APRIL_EXPORT int aprilx_restore_many(size_t n, AprilASRSession *sessions, const void *const *blobs, const size_t *sizes, int *status_out);
+/* Gather and scatter launches of one GPU's engine so far, and (while profiling) their accumulated kernel ms.  0, or -1. */
+APRIL_EXPORT int aprilx_model_snapshot_stats(AprilASRModel model, int device_index, uint64_t *gathers, uint64_t *scatters, double *gather_ms, double *scatter_ms);
+
 typedef struct AprilxStats {
     uint64_t ticks, steps, chunks, rounds, frames, max_batch_seen;
     /* per kernel class: accumulated ms and launch counts while profiling is enabled
