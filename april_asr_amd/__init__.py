@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _ffi
 
-__all__ = ["Result", "Token", "Model", "Session", "SessionGroup", "Bias", "VadEvent", "resampler_taps", "decode_host", "vad_plan", "vad_host", "vad_events_host",
+__all__ = ["Result", "Token", "Model", "Session", "SessionGroup", "Bias", "Lm", "lm_info", "VadEvent", "resampler_taps", "decode_host", "vad_plan", "vad_host", "vad_events_host",
            "DtmfEvent", "dtmf_plan", "dtmf_tables", "dtmf_host", "dtmf_decide_host", "dtmf_events_host",
            "ToneEvent", "tone_plan", "tone_tables", "tone_host", "tone_decide_host", "tone_events_host", "tone_name",
            "snapshot_info"]
@@ -150,6 +150,12 @@ class Model:
             # session leaked by a failing caller cannot touch a freed model later (interpreter exit order is arbitrary)
             for s in list(getattr(self, "_sessions", ())):
                 s.close()
+            # ... and the ones the weak set no longer shows: when the model and its sessions become garbage together (sessions kept in
+            # a reference cycle by their callbacks), the collector clears every weak reference before it runs any finalizer, and may
+            # finalize the model first.  Their handles are kept as plain integers; Session.close() skips a session whose model is closed.
+            for h in list(getattr(self, "_open_sessions", ())):
+                self._L.aas_free(h)
+            self._open_sessions = set()
             self._L.aam_free(self._handle)
             self._handle = None
 
@@ -333,6 +339,54 @@ class Model:
         `boost` logit units, or of (phrase, boost) pairs.  Hand it to Session(..., bias=...) or Session.set_bias().
         `strict`: a closed phrase list -- the session emits only sequences of these phrases (APRILX_BIAS_STRICT)."""
         return Bias(self, phrases, boost, flags=BIAS_STRICT if strict else 0)
+
+    def lm(self, text, order: int = 5):
+        """A byte n-gram language model of `text` for this model's token list (aprilx_lm_create; no GPU needed):
+        `text` is a str or bytes, one utterance per line, written the way the tokens are written.  Hand it to Session(..., lm=...) or
+        Session.set_lm().  No accuracy is claimed for it: the default weight of a session is a placeholder until real audio has been run."""
+        return Lm(self, text, order)
+
+    def lm_stats(self, device_index: int = 0):
+        """(decision launches of the language-model forms issued, models resident on the device, model uploads): all zero while no
+        session of the engine has had a model (aprilx_model_lm_stats)"""
+        a, b, c = C.c_uint64(0), C.c_int32(0), C.c_uint64(0)
+        if self._L.aprilx_model_lm_stats(self._handle, int(device_index), C.byref(a), C.byref(b), C.byref(c)) != 0:
+            raise ValueError("no such device")
+        return int(a.value), int(b.value), int(c.value)
+
+    def run_decide_lm(self, logits, early_emit, now_ms, rnd, state, lm, lm_state, weight, token_bonus, opts=None, bias=None, bias_state=None, op: int = 0):
+        """One decision round on GIVEN logits rows with the language model on the rows whose lm_state is >= 0 (aprilx_run_decide_lm;
+        tests); opts / bias as run_decide_opts.  Returns (records, search states [n][4], bias states [n] or None, nodes [n])."""
+        st = np.ascontiguousarray(state, np.int32).reshape(-1, 4).copy()
+        n = st.shape[0]
+        lg = np.ascontiguousarray(logits, np.float32).reshape(n, self.dims.vocab)
+        now = np.ascontiguousarray(now_ms, np.int32).reshape(n)
+        bs = np.ascontiguousarray(bias_state, np.int32).reshape(n).copy() if bias is not None else None
+        ls = np.ascontiguousarray(lm_state, np.int32).reshape(n).copy()
+        arr = None
+        if opts is not None:
+            arr = (_ffi.AprilxSearchOptions * n)()
+            for i, o in enumerate(opts):
+                if o is not None:
+                    arr[i].size = C.sizeof(_ffi.AprilxSearchOptions); arr[i].endpoint_silence_ms = int(o[0]); arr[i].blank_penalty = float(o[1])
+        rec = np.zeros(n, np.dtype([("idx", np.int32), ("max", np.float32), ("blank", np.float32), ("flags", np.uint32)]))
+        rc = self._L.aprilx_run_decide_lm(self._handle, n, int(op), lg.ctypes.data, float(early_emit), now.ctypes.data, int(rnd), st.ctypes.data,
+                                          rec.ctypes.data, bias._handle if bias is not None else None, bs.ctypes.data if bs is not None else None,
+                                          C.cast(arr, C.c_void_p) if arr is not None else None, lm._handle, ls.ctypes.data, float(weight), float(token_bonus))
+        if rc != 0:
+            raise ValueError("aprilx_run_decide_lm refused the call")
+        return rec, st, bs, ls
+
+    def run_confidence_lm(self, logits, k: int, lm, lm_state, weight, token_bonus, bias=None, bias_state=None):
+        """run_confidence with the language model on the rows whose lm_state is >= 0 (aprilx_run_confidence_lm; tests)."""
+        a = np.ascontiguousarray(logits, np.float32).reshape(-1, self.dims.vocab)
+        ls = np.ascontiguousarray(lm_state, np.int32).reshape(a.shape[0])
+        bs = np.ascontiguousarray(bias_state, np.int32).reshape(a.shape[0]) if bias is not None else None
+        out = (_ffi.AprilxTokenInfo * a.shape[0])()
+        if self._L.aprilx_run_confidence_lm(self._handle, a.shape[0], a.ctypes.data, int(k), bias._handle if bias is not None else None,
+                                            bs.ctypes.data if bs is not None else None, lm._handle, ls.ctypes.data, float(weight), float(token_bonus), out) != 0:
+            raise ValueError("aprilx_run_confidence_lm refused n=%d k=%d" % (a.shape[0], k))
+        return out
 
     def run_confidence_biased(self, logits, k: int, bias, bias_state):
         """run_confidence with `bias` on the rows whose bias_state is >= 0 (aprilx_run_confidence_biased; tests)."""
@@ -546,6 +600,59 @@ class Bias:
             pass
 
 
+class Lm:
+    """A byte n-gram language model built from plain text.  Sessions that use it keep it alive after close()."""
+
+    def __init__(self, model: Model, text, order: int = 5):
+        self._L = model._L
+        raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+        err = C.create_string_buffer(256)
+        self._handle = self._L.aprilx_lm_create(model._handle, raw, len(raw), int(order), err, 256)
+        self.message = err.value.decode("utf-8", "replace")          # a note about dropped lines when the call succeeded
+        if not self._handle:
+            raise ValueError("language model refused: " + self.message)
+        for k, v in lm_info(self).items():
+            setattr(self, k, v)
+
+    def arrays(self):
+        """dict(node_off [nodes + 1], back, bow [nodes], arc_byte, arc_logp, arc_next [arcs], unk_logp) as the device receives them"""
+        nn, na = self.nodes, self.arcs
+        d = dict(node_off=np.zeros(nn + 1, np.int32), back=np.zeros(nn, np.int32), bow=np.zeros(nn, np.float32),
+                 arc_byte=np.zeros(na, np.uint8), arc_logp=np.zeros(na, np.float32), arc_next=np.zeros(na, np.int32))
+        unk = C.c_float(0)
+        rc = self._L.aprilx_lm_arrays(self._handle, *[d[k].ctypes.data for k in ("node_off", "back", "bow", "arc_byte", "arc_logp", "arc_next")], C.byref(unk), nn, na)
+        assert rc == 0
+        d["unk_logp"] = np.float32(unk.value)
+        return d
+
+    def score(self, state: int, tok: int):
+        """(score, next node) of the contract's walk on the host (aprilx_lm_score_host)"""
+        sc, nx = C.c_float(0), C.c_int32(0)
+        if self._L.aprilx_lm_score_host(self._handle, int(state), int(tok), C.byref(sc), C.byref(nx)) != 0:
+            raise ValueError("no such node or token")
+        return np.float32(sc.value), int(nx.value)
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            self._L.aprilx_lm_free(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def lm_info(lm: "Lm"):
+    """dict(order, nodes, arcs, start, alphabet, dropped_lines) of a language model (aprilx_lm_info)"""
+    o, n, st, al, a = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    dropped = int(lm._L.aprilx_lm_info(lm._handle, C.byref(o), C.byref(n), C.byref(a), C.byref(st), C.byref(al)))
+    if dropped < 0:
+        raise ValueError("no language model")
+    return dict(order=int(o.value), nodes=int(n.value), arcs=int(a.value), start=int(st.value), alphabet=int(al.value), dropped_lines=dropped)
+
+
 def _dispatch(userdata, result_type, count, tokens):
     sess = C.cast(userdata, C.py_object).value
     sess._on_result(result_type, count, tokens)
@@ -586,7 +693,7 @@ class Session:
                  no_rt: bool = False, speaker_name: str = "", raw_events: bool = False, counters=None, input_sample_rate=None,
                  alternatives=None, bias=None, endpoint_silence_ms=None, blank_penalty=None, max_utterance_ms=None,
                  input_format=None, channels: int = 1, channel: int = 0, vad=None, vad_callback=None,
-                 dtmf=None, dtmf_callback=None, tones=None, tone_callback=None):
+                 dtmf=None, dtmf_callback=None, tones=None, tone_callback=None, lm=None, lm_weight: float = 0.3, lm_token_bonus: float = 0.0):
         """`counters`: a uint64 ndarray of 6 entries; when given, results are only counted by a C handler inside the
         library (calls, partial, final, cant_keep_up, silence, tokens) and `callback` is never invoked.
         `input_sample_rate`: the rate of the PCM this session will receive (converted to the model's rate on the GPU); None: the
@@ -595,6 +702,8 @@ class Session:
         (set_confidence); None / 0: off.
         `bias`: a Bias (Model.bias): the search boosts the tokens that continue one of its phrases (set_bias); None: off.
         `endpoint_silence_ms`, `blank_penalty`, `max_utterance_ms`: the session's search options (set_search_options); all None: none.
+        `lm`, `lm_weight`, `lm_token_bonus`: an Lm (Model.lm): the search adds lm_weight * log P(token text) + lm_token_bonus to every
+        non-blank logit (set_lm); None: off.  The default weight is a placeholder: no accuracy has been measured.
         `input_format`, `channels`, `channel`: the format of the audio this session will receive (set_input_format): "mulaw", "alaw",
         "f32" or "s16", 1..8 interleaved channels, the channel to take or -1 for their downmix; None: mono PCM16.
         `vad`, `vad_callback`: True or a dict of options (set_vad) switches the voice-activity detector on; `vad_callback` receives one
@@ -628,6 +737,9 @@ class Session:
         if not hasattr(model, "_sessions"):
             model._sessions = weakref.WeakSet()
         model._sessions.add(self)
+        if not hasattr(model, "_open_sessions"):
+            model._open_sessions = set()
+        model._open_sessions.add(self._handle)             # (Model.close(): what the weak set cannot show during garbage collection)
         if input_sample_rate is not None:
             self.set_input_rate(input_sample_rate)
         if input_format is not None:
@@ -636,6 +748,8 @@ class Session:
             self.set_confidence(alternatives)
         if bias is not None:
             self.set_bias(bias)
+        if lm is not None:
+            self.set_lm(lm, lm_weight, lm_token_bonus)
         if endpoint_silence_ms is not None or blank_penalty is not None or max_utterance_ms is not None:
             self.set_search_options(endpoint_silence_ms, blank_penalty, max_utterance_ms)
         if vad:
@@ -793,6 +907,20 @@ class Session:
         if self._L.aprilx_session_set_bias(self._handle, bias._handle if bias is not None else None) != 0:
             raise ValueError("bias set refused (built for another token list, 64 sets in use on the engine already, or audio fed since the last flush)")
 
+    def set_lm(self, lm, weight: float = 0.3, token_bonus: float = 0.0) -> None:
+        """The search of this session uses the language model `lm` (Model.lm) from now on, starting at its start node; None switches it
+        off (aprilx_session_set_lm).  weight: 0..10; token_bonus: |b| <= 100.  Allowed right after creation and after a completed flush.
+        A session with a model cannot be snapshotted or restored into."""
+        if self._L.aprilx_session_set_lm(self._handle, lm._handle if lm is not None else None, float(weight), float(token_bonus)) != 0:
+            raise ValueError("language model refused (a value out of range, built for another token list, 8 models in use on the engine already, "
+                             "or audio fed since the last flush)")
+
+    def lm_state(self):
+        """(host, device) node of the session's language model -- derived independently, must agree (tests)"""
+        h, d = C.c_int32(0), C.c_int32(0)
+        self._L.aprilx_session_lm_state(self._handle, C.byref(h), C.byref(d))
+        return int(h.value), int(d.value)
+
     def set_search_options(self, endpoint_silence_ms=None, blank_penalty=None, max_utterance_ms=None) -> None:
         """The session's search options (aprilx_session_set_search_options): the silence after the last token that
         ends an utterance (200..60000 ms, default 2200), the constant subtracted from the blank logit in the decision (|p| <= 100, default
@@ -885,9 +1013,16 @@ class Session:
         return self._trace[: self._trace_used.value // self.model.dims.vocab]
 
     def close(self):
-        if getattr(self, "_handle", None):
-            self._L.aas_free(self._handle)
+        h = getattr(self, "_handle", None)
+        if h:
             self._handle = None
+            model = getattr(self, "model", None)
+            # a model that has been closed has freed its sessions with it (Model.close()): the handle is dangling, leave it alone
+            if model is not None and getattr(model, "_handle", None) is None:
+                return
+            if model is not None:
+                getattr(model, "_open_sessions", set()).discard(h)
+            self._L.aas_free(h)
 
     def __del__(self):
         try:

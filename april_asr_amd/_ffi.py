@@ -174,6 +174,8 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_session_set_tones", "aprilx_session_tones", "aprilx_tone_plan", "aprilx_tone_tables", "aprilx_tone_host", "aprilx_tone_decide_host",
     "aprilx_tone_events_host", "aprilx_tone_name", "aprilx_run_tones", "aprilx_run_tone_decide", "aprilx_model_tone_stats",
     "aprilx_session_snapshot", "aprilx_session_restore", "aprilx_snapshot_info", "aprilx_snapshot_many", "aprilx_restore_many", "aprilx_model_snapshot_stats",
+    "aprilx_lm_create", "aprilx_lm_free", "aprilx_lm_info", "aprilx_lm_arrays", "aprilx_lm_score_host", "aprilx_session_set_lm", "aprilx_session_lm_state",
+    "aprilx_greedy_set_lm", "aprilx_greedy_lm_state", "aprilx_model_lm_stats", "aprilx_run_decide_lm", "aprilx_run_confidence_lm",
 ]
 
 _lib = None
@@ -255,6 +257,18 @@ def lib():
     L.aprilx_bias_flags.argtypes = [vp]; L.aprilx_bias_flags.restype = C.c_int
     L.aprilx_run_confidence_biased.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp]; L.aprilx_run_confidence_biased.restype = C.c_int
     L.aprilx_bias_free.argtypes = [vp]; L.aprilx_bias_free.restype = None
+    L.aprilx_lm_create.argtypes = [vp, vp, sz, C.c_int, C.c_char_p, sz]; L.aprilx_lm_create.restype = vp
+    L.aprilx_lm_free.argtypes = [vp]; L.aprilx_lm_free.restype = None
+    L.aprilx_lm_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]; L.aprilx_lm_info.restype = C.c_int
+    L.aprilx_lm_arrays.argtypes = [vp] * 7 + [C.POINTER(C.c_float), sz, sz]; L.aprilx_lm_arrays.restype = C.c_int
+    L.aprilx_lm_score_host.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]; L.aprilx_lm_score_host.restype = C.c_int
+    L.aprilx_session_set_lm.argtypes = [vp, vp, C.c_float, C.c_float]; L.aprilx_session_set_lm.restype = C.c_int
+    L.aprilx_session_lm_state.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]; L.aprilx_session_lm_state.restype = C.c_int
+    L.aprilx_greedy_set_lm.argtypes = [vp, vp, C.c_float, C.c_float]; L.aprilx_greedy_set_lm.restype = C.c_int
+    L.aprilx_greedy_lm_state.argtypes = [vp]; L.aprilx_greedy_lm_state.restype = C.c_int
+    L.aprilx_model_lm_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]; L.aprilx_model_lm_stats.restype = C.c_int
+    L.aprilx_run_decide_lm.argtypes = [vp, C.c_int, C.c_int, vp, C.c_float, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float]; L.aprilx_run_decide_lm.restype = C.c_int
+    L.aprilx_run_confidence_lm.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_float, C.c_float, vp]; L.aprilx_run_confidence_lm.restype = C.c_int
     L.aprilx_bias_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]; L.aprilx_bias_info.restype = C.c_int
     L.aprilx_bias_edges.argtypes = [vp, C.c_int32, vp, vp, vp, sz]; L.aprilx_bias_edges.restype = C.c_int
     L.aprilx_session_set_bias.argtypes = [vp, vp]; L.aprilx_session_set_bias.restype = C.c_int

@@ -408,6 +408,9 @@ Engine::~Engine()
     if (conf_h_) (void)hipHostFree(conf_h_);
     for (auto &b : bias_sets_) if (b.dev) (void)hipFree(b.dev);
     if (bias_state_d_) (void)hipFree(bias_state_d_);
+    lm_slot_.release(); lm_desc_.release();
+    for (auto &e : lm_models_) if (e.dev) (void)hipFree(e.dev);
+    if (lm_state_d_) (void)hipFree(lm_state_d_);
     for (void *p : {(void *)vad_state_d_, (void *)pass_out_d_}) if (p) (void)hipFree(p);
     for (PassBlock &k : pass_blocks_) (void)hipHostFree(k.h);
     if (snap_d_) (void)hipFree(snap_d_);
@@ -498,7 +501,7 @@ void Engine::free_slot(int slot)
     // and a [blank, blank] context -- in a batch: when 256 freed slots have gathered, when the free list runs dry, or before
     // the next flight is launched (begin_flight), stream-ordered ahead of any later use of the slot
     // the next owner starts with confidences off, without a bias set (at the root) and without search options (dropped at the push while nothing was ever on)
-    set_slot_confidence(slot, 0); set_slot_bias(slot, nullptr); set_slot_search_options(slot, SearchOpt{0u, 0.0f});
+    set_slot_confidence(slot, 0); set_slot_bias(slot, nullptr); set_slot_lm(slot, nullptr, 0.0f, 0.0f); set_slot_search_options(slot, SearchOpt{0u, 0.0f});
     std::lock_guard<std::mutex> g(slot_mu_);
     zero_pending_.push_back(slot);
     --live_;
@@ -1153,6 +1156,7 @@ void Engine::run_greedy_rounds(int n, const GreedyIo &io)
         a.conf_k = conf_k_.d; a.conf_ring = conf_d_;          // (null until a session of this engine asks for confidences)
         a.bias_set = bias_set_.d; a.bias_state = bias_state_d_; a.bias_desc = bias_desc_.d;      // (null until a session of this engine has a bias set)
         a.opt = opt_.d;                                        // (null until a session of this engine has search options)
+        if (lm_slot_.d) { a.lm_slot = lm_slot_.d; a.lm_state = lm_state_d_; a.lm_desc = lm_desc_.d; lm_launches_.fetch_add(1, std::memory_order_relaxed); }      // (null until a session of this engine has a language model)
         timed_begin(T_DEC); launch_decide(a, search_stream_); timed_end(T_DEC);
         if (!dec_table_) run_decproj(n, d_slots, dirty_d_, flags_d_ + 4 + round, gen);
     }
@@ -1728,13 +1732,16 @@ BiasDesc Engine::upload_bias(const BiasSet &set, void **dev, hipStream_t st)
 // have drained -- once per call, however many tables turn on in it.  From then on the pointers never change.  The whole table is
 // uploaded, stream-ordered ahead of this flight's steps: the slots that change belong to idle sessions, so no flight in the air reads
 // their entries, and the other slots keep their values; a bias set nobody uses any more is read by no flight either.
-// LOCK ORDER, here and everywhere: bias_q_.mutex() (the bias books; read_bias_state holds it over its read) -> capture_mu_ -> the
+// LOCK ORDER, here and everywhere: bias_q_.mutex() (the bias books; read_bias_state holds it over its read) -> lm_q_.mutex() (the
+// language-model books, likewise; nobody takes the bias mutex under it) -> capture_mu_ -> the
 // process-wide legacy-stream lock (step() and the debug entry points take the last two in that order).  The mutexes inside conf_q_ and
 // opt_q_ are leaves: held for a push or a take, nothing is locked under them.
 void Engine::apply_slot_tables()
 {
     std::lock_guard<std::mutex> bg(bias_q_.mutex());
     const auto bias_todo = bias_q_.take_locked();
+    std::lock_guard<std::mutex> lg(lm_q_.mutex());
+    const auto lm_todo = lm_q_.take_locked();
     const auto conf_todo = conf_q_.take();
     const auto opt_todo = opt_q_.take();
     const size_t S = (size_t)cfg_.max_slots;
@@ -1742,8 +1749,9 @@ void Engine::apply_slot_tables()
     const bool conf_first = !conf_k_.on() && std::any_of(conf_todo.begin(), conf_todo.end(), [](const std::pair<int, int> &t) { return t.second > 0; });
     const bool bias_first = !bias_set_.on() && std::any_of(bias_todo.begin(), bias_todo.end(), [](const std::pair<int, int> &t) { return t.second >= 0; });
     const bool opt_first = !opt_.on() && std::any_of(opt_todo.begin(), opt_todo.end(), [](const std::pair<int, SearchOpt> &t) { return t.second.endpoint_ms != 0; });
+    const bool lm_first = !lm_slot_.on() && std::any_of(lm_todo.begin(), lm_todo.end(), [](const std::pair<int, LmSlot> &t) { return t.second.model >= 0; });
     std::lock_guard<std::mutex> cg(capture_mu_);
-    if (conf_first || bias_first || opt_first) {
+    if (conf_first || bias_first || opt_first || lm_first) {
         HipLegacyLock legacy;
         sync();
         drop_graphs();
@@ -1757,9 +1765,22 @@ void Engine::apply_slot_tables()
             LOGI("engine: phrase boosting on");
         }
         if (opt_first) { opt_.alloc(S, SearchOpt{0u, 0.0f}); LOGI("engine: search options on"); }
+        if (lm_first) {
+            // the LM forms of the decision kernel are built on the BIAS forms: the three bias tables exist from now on as well (every slot: no
+            // set; bias_first has allocated them above when a set arrives in the same call)
+            if (!bias_set_.on()) {
+                bias_set_.alloc(S, -1); bias_desc_.alloc(kBiasSets, BiasDesc()); bias_state_d_ = dmalloc<int32_t>(S);
+                HIP_CHECK(hipMemsetAsync(bias_state_d_, 0, S * 4, stream_));
+                bias_set_.upload(stream_); bias_desc_.upload(stream_);
+            }
+            lm_slot_.alloc(S, LmSlot{-1, 0.0f, 0.0f, 0}); lm_desc_.alloc(kLmModels, LmDesc()); lm_state_d_ = dmalloc<int32_t>(S);
+            HIP_CHECK(hipMemsetAsync(lm_state_d_, 0, S * 4, stream_));
+            LOGI("engine: language models on");
+        }
     }
     const bool conf_up = conf_k_.on() && !conf_todo.empty(), bias_up = bias_set_.on() && !bias_todo.empty(), opt_up = opt_.on() && !opt_todo.empty();
-    if (!conf_up && !bias_up && !opt_up) return;
+    const bool lm_up = lm_slot_.on() && !lm_todo.empty();
+    if (!conf_up && !bias_up && !opt_up && !lm_up) return;
     m_touched();
     if (conf_up) {
         for (const auto &t : conf_todo) if (in_range(t.first)) conf_k_.h[t.first] = (uint8_t)t.second;
@@ -1794,6 +1815,68 @@ void Engine::apply_slot_tables()
         for (const auto &t : opt_todo) if (in_range(t.first)) opt_.h[t.first] = t.second;
         opt_.upload(stream_);
     }
+    if (lm_up) {
+        bool models = false;
+        for (int i = 0; i < kLmModels; ++i) {
+            LmEntry &e = lm_models_[(size_t)i];
+            if (e.set && e.users > 0 && !e.dev) {                     // first use on this engine
+                HipLegacyLock legacy;
+                lm_desc_.h[i] = upload_lm(*e.set, &e.dev, stream_);
+                HIP_CHECK(hipStreamSynchronize(stream_));             // (the source is pageable memory; rare)
+                lm_uploads_.fetch_add(1, std::memory_order_relaxed); lm_resident_.fetch_add(1, std::memory_order_relaxed);
+                models = true;
+            } else if (e.set && e.users == 0) {                       // the last slot has let go of it
+                if (e.dev) { HipLegacyLock legacy; sync_streams(); (void)hipFree(e.dev); e.dev = nullptr; lm_resident_.fetch_sub(1, std::memory_order_relaxed); }
+                lm_desc_.h[i] = LmDesc();
+                e.set.reset();
+                models = true;
+            }
+        }
+        for (const auto &t : lm_todo) {
+            if (!in_range(t.first)) continue;
+            lm_slot_.h[t.first] = t.second;
+            // every change starts at the model's start node (the pinned mirror's entry is the source: it holds this value until the slot's next change)
+            HIP_CHECK(hipMemcpyAsync(lm_state_d_ + t.first, &lm_slot_.h[t.first].start, 4, hipMemcpyHostToDevice, stream_));
+        }
+        if (models) lm_desc_.upload(stream_);
+        lm_slot_.upload(stream_);
+    }
+}
+
+// The eight arrays of a model in ONE device allocation (16-byte aligned parts); the copies are queued on `st`
+LmDesc Engine::upload_lm(const LmSet &set, void **dev, hipStream_t st)
+{
+    auto pad = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t nn = (size_t)set.nodes(), na = std::max<size_t>((size_t)set.arcs(), 1), nt = std::max<size_t>(set.tok_bytes.size(), 1), nv = set.tok_off.size();
+    const size_t sz[8] = {pad((nn + 1) * 4), pad(nn * 4), pad(nn * 4), pad(na * 4), pad(na * 4), pad(na), pad(nv * 4), pad(nt)};
+    size_t off[9] = {0};
+    for (int i = 0; i < 8; ++i) off[i + 1] = off[i] + sz[i];
+    char *p = nullptr;
+    HIP_CHECK(hipMalloc((void **)&p, off[8]));
+    LmDesc d;
+    d.node_off = (const int32_t *)(p + off[0]); d.back = (const int32_t *)(p + off[1]); d.bow = (const float *)(p + off[2]);
+    d.arc_logp = (const float *)(p + off[3]); d.arc_next = (const int32_t *)(p + off[4]); d.arc_byte = (const uint8_t *)(p + off[5]);
+    d.tok_off = (const int32_t *)(p + off[6]); d.tok_bytes = (const uint8_t *)(p + off[7]);
+    d.n_nodes = set.nodes(); d.start = set.start; d.unk_logp = set.unk_logp;
+    auto put = [&](const void *dst, const void *src, size_t bytes) { if (bytes) HIP_CHECK(hipMemcpyAsync((void *)dst, src, bytes, hipMemcpyHostToDevice, st)); };
+    put(d.node_off, set.node_off.data(), (nn + 1) * 4); put(d.back, set.back.data(), nn * 4); put(d.bow, set.bow.data(), nn * 4);
+    put(d.arc_logp, set.arc_logp.data(), set.arc_logp.size() * 4); put(d.arc_next, set.arc_next.data(), set.arc_next.size() * 4); put(d.arc_byte, set.arc_byte.data(), set.arc_byte.size());
+    put(d.tok_off, set.tok_off.data(), nv * 4); put(d.tok_bytes, set.tok_bytes.data(), set.tok_bytes.size());
+    *dev = p;
+    return d;
+}
+
+int Engine::read_lm_state(int slot)
+{
+    if (!lm_q_.ever()) return 0;
+    std::lock_guard<std::mutex> lg(lm_q_.mutex());        // (apply_slot_tables allocates the table under it)
+    if (lm_q_.pending_locked(slot)) { const int i = lm_slot_model_[(size_t)slot]; return i >= 0 ? lm_models_[(size_t)i].set->start : 0; }
+    HipLegacyLock legacy;
+    HIP_CHECK(hipSetDevice(cfg_.device));
+    sync_streams();
+    int v = 0;
+    if (lm_state_d_) HIP_CHECK(hipMemcpy(&v, lm_state_d_ + slot, 4, hipMemcpyDeviceToHost));
+    return v;
 }
 
 int Engine::read_bias_state(int slot)
@@ -1838,7 +1921,7 @@ void Engine::begin_flight()
     // previous one: it must have completed -- the scheduler keeps at most two flights open and completes them in order, so the event
     // is done long ago and this costs nothing; any other caller would silently overwrite an in-flight search
     if (flight_open_[p]) { HIP_CHECK(hipEventSynchronize(flight_done_[p])); flight_open_[p] = false; }
-    if (conf_q_.has_pending() || bias_q_.has_pending() || opt_q_.has_pending()) apply_slot_tables();
+    if (conf_q_.has_pending() || bias_q_.has_pending() || opt_q_.has_pending() || lm_q_.has_pending()) apply_slot_tables();
     conf_spans_.clear();
     ring_base_ = (size_t)p * ring_cap_; rec_base_ = (size_t)p * rec_cap_;
     ring_pos_ = ring_base_; rec_pos_ = rec_base_; flight_steps_ = 0;
@@ -1895,6 +1978,7 @@ void Engine::decode_rows(int n, const int *slots, int op)
         HIP_CHECK(hipMemcpyAsync(dec_slots_d_, blk, (size_t)m * 4, hipMemcpyHostToDevice, stream_));
         DecRowsArgs a; a.slot_idx = dec_slots_d_; a.M = m; a.op = op; a.blank = P_.blank_id; a.state = gstate_; a.dec = dec_params(); a.de_out = dec_table_ ? nullptr : de_; a.ld_de = d.d_model;
         a.bias_state = bias_state_d_;
+        a.lm_slot = lm_slot_.d; a.lm_state = lm_state_d_;
         timed_begin(T_DEC); launch_dec_rows(a, stream_); timed_end(T_DEC);
         if (!dec_table_) run_decproj(m, dec_slots_d_, nullptr, nullptr, 1);
     }
@@ -2075,9 +2159,24 @@ void Engine::debug_decide(const DecideRequest &q)
         bset_d = ds.upload(bset.data(), bset.size()); bstate_d = ds.upload(bstate.data(), bstate.size()); bdesc_d = ds.upload(&desc, 1);
     }
     const SearchOpt *opt_d = q.opts ? ds.upload(q.opts, (size_t)n) : nullptr;
+    LmSlot *lslot_d = nullptr; int32_t *lstate_d = nullptr; LmDesc *ldesc_d = nullptr;
+    if (q.lm) {      // row i walks the model from node lm_state_io[i], or has none when that is -1
+        std::vector<LmSlot> lslot((size_t)n); std::vector<int32_t> lstate((size_t)n);
+        for (int i = 0; i < n; ++i) { const bool on = q.lm_state_io[i] >= 0; lslot[(size_t)i] = LmSlot{on ? 0 : -1, on ? q.lm_weight : 0.0f, on ? q.lm_bonus : 0.0f, on ? q.lm->start : 0}; lstate[(size_t)i] = std::max(0, q.lm_state_io[i]); }
+        void *arrays = nullptr;
+        const LmDesc desc = upload_lm(*q.lm, &arrays, stream_);
+        ds.adopt(arrays);
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        lslot_d = ds.upload(lslot.data(), lslot.size()); lstate_d = ds.upload(lstate.data(), lstate.size()); ldesc_d = ds.upload(&desc, 1);
+        if (!q.set) {      // the LM forms are built on the BIAS forms: bias tables in which no row has a set
+            std::vector<int32_t> none((size_t)n, -1), root((size_t)n, 0); const BiasDesc empty;
+            bset_d = ds.upload(none.data(), none.size()); bstate_d = ds.upload(root.data(), root.size()); bdesc_d = ds.upload(&empty, 1);
+        }
+    }
     if (q.op == 1) {
         DecRowsArgs a; a.slot_idx = slots_d; a.M = n; a.op = 1; a.blank = P_.blank_id; a.state = gstate_; a.dec = dec_params(); a.de_out = nullptr;
         a.bias_state = bstate_d;
+        a.lm_slot = lslot_d; a.lm_state = lstate_d;
         launch_dec_rows(a, stream_);
     } else {
         // the logits enter as ONE partial plane with a zero bias: decide_kernel's tree sum + bias returns them unchanged
@@ -2094,6 +2193,7 @@ void Engine::debug_decide(const DecideRequest &q)
         a.rec = rec_d; a.round = q.round; a.gen = 1; a.dec = dec_params(); a.de_out = nullptr;
         a.bias_set = bset_d; a.bias_state = bstate_d; a.bias_desc = bdesc_d;
         a.opt = opt_d;
+        a.lm_slot = lslot_d; a.lm_state = lstate_d; a.lm_desc = ldesc_d;
         if (conf_d) { a.conf = conf_d; a.conf_k_all = q.conf_k; }
         launch_decide(a, stream_);
         sync();
@@ -2106,6 +2206,11 @@ void Engine::debug_decide(const DecideRequest &q)
         std::vector<int32_t> bstate((size_t)n);
         HIP_CHECK(hipMemcpy(bstate.data(), bstate_d, (size_t)n * 4, hipMemcpyDeviceToHost));
         for (int i = 0; i < n; ++i) if (q.bias_state_io[i] >= 0) q.bias_state_io[i] = bstate[(size_t)i];
+    }
+    if (q.lm) {
+        std::vector<int32_t> lstate((size_t)n);
+        HIP_CHECK(hipMemcpy(lstate.data(), lstate_d, (size_t)n * 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) if (q.lm_state_io[i] >= 0) q.lm_state_io[i] = lstate[(size_t)i];
     }
     zero_slots(n);
 }
@@ -2328,7 +2433,7 @@ bool Engine::snapshot_copy(int n, SnapRec *recs, uint8_t *const *blocks, bool sc
         want_vad = want_vad || ((r.mask >> SNAP_VAD) & 1u);
     }
     // (the queues first: apply_slot_tables returns a slot with a queued bias change to the root, which must not follow a scatter)
-    if (conf_q_.has_pending() || bias_q_.has_pending() || opt_q_.has_pending()) apply_slot_tables();
+    if (conf_q_.has_pending() || bias_q_.has_pending() || opt_q_.has_pending() || lm_q_.has_pending()) apply_slot_tables();
     std::lock_guard<std::mutex> cg(capture_mu_);
     sync();                                                        // (m_touched() inside: the copy is an enqueue on M like any other)
     if (scatter && want_vad && !vad_state_d_) vad_state_d_ = dmalloc<VadState>((size_t)cfg_.max_slots);

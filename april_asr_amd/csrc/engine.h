@@ -27,6 +27,7 @@
 #include <utility>
 #include <vector>
 #include "bias.h"
+#include "lm.h"
 #include "fbank_tables.h"
 #include "resample.h"
 #include "input_format.h"
@@ -146,6 +147,7 @@ struct DecideRequest {
     StepRecord *rec_out = nullptr;             // [n] (op 0)
     const BiasSet *set = nullptr; int32_t *bias_state_io = nullptr;      // tables of their own for the call: row i uses the set from trie state bias_state_io[i], or none when that is -1
     const SearchOpt *opts = nullptr;           // a table of its own likewise: opts[i] on row i (endpoint_ms 0 = a row without options)
+    const LmSet *lm = nullptr; int32_t *lm_state_io = nullptr; float lm_weight = 0.0f, lm_bonus = 0.0f;      // likewise: row i walks the model from node lm_state_io[i], or has none when that is -1
     int conf_k = 0; ConfRecord *conf_out = nullptr;                      // conf_k > 0: the side records of the rows with conf_k alternatives
     // the arguments the aprilx_run_decide* family shares
     static DecideRequest round_of(int n, int op, const float *logits, float early_emit, const int32_t *now_ms, int round, int32_t *state_io, void *records_out)
@@ -304,6 +306,42 @@ public:
     // the device's trie state of a slot; waits for the streams.  0 while no session of the engine has a set, and for a slot with a queued
     // change (begin_flight returns it to the root before the slot's next step)
     int read_bias_state(int slot);
+    // Language models: the life cycle of the bias sets, with books of its own under lm_q_.mutex() -- a model is
+    // shared by shared_ptr identity, uploaded the first time a slot of this engine uses it and freed when its last slot lets go; the
+    // descriptor table holds kLmModels entries.  The slot's node returns to the model's start with every change.  False: all entries hold
+    // other models, or the model was built for another vocabulary size.
+    bool set_slot_lm(int slot, const std::shared_ptr<const LmSet> &set, float weight, float token_bonus)
+    {
+        std::lock_guard<std::mutex> g(lm_q_.mutex());
+        if (slot < 0 || slot >= cfg_.max_slots) return false;
+        if (lm_slot_model_.empty()) {
+            if (!set) return true;                               // nothing was ever on
+            lm_slot_model_.assign((size_t)cfg_.max_slots, -1); lm_models_.resize(kLmModels);
+        }
+        int idx = -1;
+        if (set) {
+            if (set->vocab != L_.dims.vocab || set->vocab > kLmMaxVocab) return false;
+            for (int i = 0; i < kLmModels && idx < 0; ++i) if (lm_models_[(size_t)i].set == set) idx = i;
+            for (int i = 0; i < kLmModels && idx < 0; ++i) if (!lm_models_[(size_t)i].set) idx = i;
+            if (idx < 0) return false;
+            lm_models_[(size_t)idx].set = set;
+            ++lm_models_[(size_t)idx].users;
+        }
+        const int old = lm_slot_model_[(size_t)slot];
+        if (old < 0 && idx < 0) return true;
+        if (old >= 0) --lm_models_[(size_t)old].users;
+        lm_slot_model_[(size_t)slot] = idx;
+        lm_q_.push_locked(slot, LmSlot{idx, idx >= 0 ? weight : 0.0f, idx >= 0 ? token_bonus : 0.0f, set ? set->start : 0}, idx >= 0);
+        return true;
+    }
+    // the device's node of a slot; waits for the streams.  For a slot with a queued change: the start node of the queued model (what
+    // begin_flight writes before the slot's next step); 0 while no session of the engine has a model
+    int read_lm_state(int slot);
+    // decision launches of the LM forms issued so far (one captured into a graph counts once), models resident on the device now, uploads so far
+    void lm_counts(uint64_t *launches, int32_t *resident, uint64_t *uploads) const
+    {
+        *launches = lm_launches_.load(std::memory_order_relaxed); *resident = lm_resident_.load(std::memory_order_relaxed); *uploads = lm_uploads_.load(std::memory_order_relaxed);
+    }
     // Search options: endpoint_ms 0 = no options
     void set_slot_search_options(int slot, SearchOpt o) { opt_q_.push(slot, o, o.endpoint_ms != 0); }
     void sync();                               // stepping thread (or under capture_mu_): waits for the three streams and clears the cross-stream dependency flags
@@ -480,6 +518,15 @@ private:
     DeviceTable<BiasDesc> bias_desc_;                 // [kBiasSets]
     SlotQueue<SearchOpt> opt_q_; DeviceTable<SearchOpt> opt_;
     BiasDesc upload_bias(const BiasSet &set, void **dev, hipStream_t st);
+    struct LmEntry { std::shared_ptr<const LmSet> set; int users = 0; void *dev = nullptr; };           // dev: one allocation holding the eight arrays
+    SlotQueue<LmSlot> lm_q_; DeviceTable<LmSlot> lm_slot_;    // the model, weight, bonus and start node of every slot (model -1 = none)
+    std::vector<LmEntry> lm_models_;                  // [kLmModels] (lm_q_.mutex())
+    std::vector<int> lm_slot_model_;                  // [slots] the queued model of every slot (lm_q_.mutex())
+    int32_t *lm_state_d_ = nullptr;                   // [slots] node ids
+    DeviceTable<LmDesc> lm_desc_;                     // [kLmModels]
+    std::atomic<uint64_t> lm_launches_{0}, lm_uploads_{0};
+    std::atomic<int32_t> lm_resident_{0};
+    LmDesc upload_lm(const LmSet &set, void **dev, hipStream_t st);
     void note_conf_step(int k, const int *slots, int m, size_t records);
     bool flight_open_[2] = {false, false};     // flight_done_[p] has been recorded and not yet waited for by begin_flight (wait_flight leaves it set: waiting twice is free)
     // streams (engine.cc "streams"): front end / search beside the layer chain, the per-parity buffers that make it safe

@@ -238,6 +238,18 @@ struct BiasDesc { const int32_t *state_off = nullptr, *edge_tok = nullptr, *edge
 struct SearchOpt { uint32_t endpoint_ms; float blank_penalty; };
 static_assert(sizeof(SearchOpt) == 8, "SearchOpt is 2 x 32 bit");
 
+// Text-corpus language model (lm.h): one model on the device -- the CSR of the back-off automaton and the token
+// text table --, and one entry per slot: the slot's model (index into the descriptor table, -1 = none), weight w, per-token bonus b and
+// the model's start node (what the end-of-flush reset writes).
+struct LmDesc {
+    const int32_t *node_off = nullptr, *back = nullptr, *arc_next = nullptr, *tok_off = nullptr;
+    const float *bow = nullptr, *arc_logp = nullptr;
+    const uint8_t *arc_byte = nullptr, *tok_bytes = nullptr;
+    int32_t n_nodes = 0, start = 0; float unk_logp = 0.0f; int32_t reserved = 0;
+};
+struct LmSlot { int32_t model; float w, b; int32_t start; };
+static_assert(sizeof(LmSlot) == 16, "LmSlot is 4 x 32 bit: one load");
+
 struct DecEmbedParams {
     const float *emb = nullptr;            // [vocab][d]
     const float *conv_w = nullptr;         // [d][d/groups][context]
@@ -284,6 +296,11 @@ struct DecideArgs {
     const BiasDesc *bias_desc = nullptr;
     // search options: null unless a session of the engine opted in
     const SearchOpt *opt = nullptr;        // [slots]
+    // language model (kernels_lm.inc): null unless a session of the engine opted in (then the three bias tables
+    // exist as well: the LM forms are built on the BIAS forms).  Last in the struct: the other forms' argument offsets stay what they were
+    const LmSlot *lm_slot = nullptr;       // [slots]
+    int32_t *lm_state = nullptr;           // [slots] node ids, read and written by the decision beside bias_state
+    const LmDesc *lm_desc = nullptr;
 };
 void launch_decide(const DecideArgs &a, hipStream_t s);
 
@@ -297,6 +314,8 @@ struct DecRowsArgs {
     DecEmbedParams dec;
     float *de_out = nullptr; int ld_de = 0;
     int32_t *bias_state = nullptr;         // [slots] or null: op 1 also returns the slot's phrase-boosting state to the root
+    const LmSlot *lm_slot = nullptr;       // [slots] or null: op 1 also returns the slot's language-model state to its model's start node
+    int32_t *lm_state = nullptr;
 };
 void launch_dec_rows(const DecRowsArgs &a, hipStream_t s);
 

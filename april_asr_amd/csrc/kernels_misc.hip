@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 namespace aprilx {
 
@@ -176,6 +177,7 @@ __device__ __forceinline__ void dec_embed_row(const DecEmbedParams &p, int tok0,
 }
 
 #include "kernels_bias.inc"
+#include "kernels_lm.inc"
 #include "kernels_confidence.inc"
 
 // ---------------------------------------------------------------- joiner decision
@@ -191,7 +193,9 @@ __device__ __forceinline__ void dec_embed_row(const DecEmbedParams &p, int tok0,
 // OPT = true (engines where a session has search options): thread 0 loads the slot's SearchOpt after the
 // GreedyState; a row whose slot has options (endpoint_ms != 0) compares bl' = bl - p in place of bl and ends the utterance after its
 // own silence E in place of 2200 ms.  The record keeps the raw blank logit.  The other rows, and OPT = false, run the lines as they were.
-template <bool CONF, bool BIAS, bool OPT>
+// LM = true (engines where a session has a language model; kernels_lm.inc), on top of BIAS = true: rows whose slot
+// has a model get term = w * score(node, n) + b combined into the dense table before the scan and move the slot's node with the decision.
+template <bool CONF, bool BIAS, bool OPT, bool LM = false>
 __device__ __forceinline__ void decide_body(const DecideArgs &a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char bias_lds[];      // BIAS: bonus[V] | next[V] (bias_lds_bytes)
@@ -211,6 +215,8 @@ __device__ __forceinline__ void decide_body(const DecideArgs &a)
     float blank_v = 0.0f;
     BiasRow br;
     if (BIAS) bias_row_begin(a, m, bias_lds, br);
+    typename std::conditional<LM, LmRow, LmNoRow>::type lr;      // (an empty struct in the other forms: they compile to what they were)
+    if constexpr (LM) lm_row_begin(a, m, bias_lds, br, lr);
     // (bias_scan in kernels_bias.inc is a COPY of the loop below with the bonus added: a change to the loop -- the dump, the blank test,
     // the comparison -- has to be made in both; tests/mutate_device_decide.py edits each of the two, this one in its first list and the copy
     // in its list of the opt-in lines)
@@ -280,6 +286,11 @@ __device__ __forceinline__ void decide_body(const DecideArgs &a)
         if (rerun) flags |= REC_CTX;
         rec->flags = flags;
         a.state[slot] = st;
+        if constexpr (LM) {
+            if (lr.model >= 0) lm_row_end(a, lr, slot, is_blank, tok, silence);
+            if (br.bonus && lr.bias) bias_row_end(a, br, slot, is_blank, tok, silence);
+        }
+        else
         if (BIAS && br.bonus) bias_row_end(a, br, slot, is_blank, tok, OPT ? silence : is_blank && now - st.last_emit_ms >= 2200u);      // (!OPT: the argument as it was, so that the bias forms compile to what they were)
         a.dirty[m] = rerun ? 1 : 0;
         if (a.run_flags) {
@@ -307,11 +318,25 @@ __global__ __launch_bounds__(256) void decide_opt_kernel(DecideArgs a) { decide_
 __global__ __launch_bounds__(256) void decide_conf_opt_kernel(DecideArgs a) { decide_body<true, false, true>(a); }
 __global__ __launch_bounds__(256) void decide_bias_opt_kernel(DecideArgs a) { decide_body<false, true, true>(a); }
 __global__ __launch_bounds__(256) void decide_conf_bias_opt_kernel(DecideArgs a) { decide_body<true, true, true>(a); }
+__global__ __launch_bounds__(256) void decide_lm_kernel(DecideArgs a) { decide_body<false, true, false, true>(a); }
+__global__ __launch_bounds__(256) void decide_conf_lm_kernel(DecideArgs a) { decide_body<true, true, false, true>(a); }
+__global__ __launch_bounds__(256) void decide_lm_opt_kernel(DecideArgs a) { decide_body<false, true, true, true>(a); }
+__global__ __launch_bounds__(256) void decide_conf_lm_opt_kernel(DecideArgs a) { decide_body<true, true, true, true>(a); }
 
 void launch_decide(const DecideArgs &a, hipStream_t s)
 {
     const bool conf = a.conf || a.conf_k;
-    if (a.bias_set) {
+    if (a.lm_slot) {
+        if (a.n_valid > 8192 || !a.lm_state || !a.lm_desc || !a.bias_set || !a.bias_state || !a.bias_desc) { fprintf(stderr, "libapril(mi355x): launch_decide: a language model needs a vocabulary of at most 8192 tokens, its three tables and the three bias tables\n"); abort(); }
+        const size_t lds = bias_lds_bytes(a.n_valid);
+        if (a.opt) {
+            if (conf) hipLaunchKernelGGL(decide_conf_lm_opt_kernel, dim3((unsigned)a.M), dim3(256), lds, s, a);
+            else hipLaunchKernelGGL(decide_lm_opt_kernel, dim3((unsigned)a.M), dim3(256), lds, s, a);
+        }
+        else if (conf) hipLaunchKernelGGL(decide_conf_lm_kernel, dim3((unsigned)a.M), dim3(256), lds, s, a);
+        else hipLaunchKernelGGL(decide_lm_kernel, dim3((unsigned)a.M), dim3(256), lds, s, a);
+    }
+    else if (a.bias_set) {
         if (a.n_valid > 8192 || !a.bias_state || !a.bias_desc) { fprintf(stderr, "libapril(mi355x): launch_decide: phrase boosting needs a vocabulary of at most 8192 tokens and all three tables\n"); abort(); }
         const size_t lds = bias_lds_bytes(a.n_valid);
         if (a.opt) {
@@ -342,6 +367,7 @@ __global__ __launch_bounds__(256) void dec_rows_kernel(DecRowsArgs a)
             if (st.ctx0 != a.blank) { st.ctx0 = a.blank; st.ctx1 = a.blank; }
             a.state[slot] = st;
             if (a.bias_state) a.bias_state[slot] = 0;
+            if (a.lm_state) a.lm_state[slot] = a.lm_slot[slot].start;
         }
         s_ctx[0] = st.ctx0; s_ctx[1] = st.ctx1;
     }

@@ -41,6 +41,7 @@ void Greedy::init(const ModelParams *p, const std::vector<uint8_t> *cls)
     head_ = last_call_head_ = 0;
     conf_k_ = 0; side_ = nullptr; evals_ = 0;
     bias_.reset(); bias_state_ = 0;
+    set_lm(nullptr, 0.0f, 0.0f);
     set_search_options(nullptr); first_ms_ = 0;
     emitted_silence_ = true;                       // april_session.c:64
     last_emit_ms_ = 0;
@@ -176,6 +177,7 @@ bool Greedy::on_joint(const JointResult &r, float early_emit, size_t now_ms, std
         last_emit_ms_ = now_ms;
         push_ctx(best);
         if (bias_) bias_state_ = bias_->next(bias_state_, best);
+        if (lm_) lm_state_ = lm_->next(lm_state_, best);
         bool fin = head_ >= (size_t)(kMaxActive - 1);
         if (head_ > 0 && (flags & APRIL_TOKEN_FLAG_WORD_BOUNDARY_BIT)) {
             AprilToken &prev = active_[head_ - 1];
@@ -204,6 +206,7 @@ bool Greedy::on_joint(const JointResult &r, float early_emit, size_t now_ms, std
             finalize_all(out);
             clear_context();
             bias_state_ = 0;
+            if (lm_) lm_state_ = lm_->start;
             emit_silence(out);
         } else if (confident) {
             tok.logprob -= 8.0f;
@@ -218,6 +221,7 @@ bool Greedy::on_joint(const JointResult &r, float early_emit, size_t now_ms, std
 void Greedy::finish_flush(std::vector<Event> &out)
 {
     bias_state_ = 0;
+    if (lm_) lm_state_ = lm_->start;
     finalize_all(out);
     clear_context();
     emit_silence(out);
@@ -587,6 +591,15 @@ bool Scheduler::set_bias(Session *s, std::shared_ptr<const BiasSet> set)
         if (set.get() == s->greedy.bias() && s->greedy.bias_state() == 0) return true;
         if (!eng_->set_slot_bias(s->slot, set)) return false;      // (queued: the stepping thread applies it before the session's next flight)
         s->greedy.set_bias(std::move(set));
+        return true;
+    });
+}
+
+bool Scheduler::set_lm(Session *s, std::shared_ptr<const LmSet> lm, float weight, float token_bonus)
+{
+    return configure(s, [&] {
+        if (!eng_->set_slot_lm(s->slot, lm, weight, token_bonus)) return false;      // (queued: the stepping thread applies it before the session's next flight)
+        s->greedy.set_lm(std::move(lm), weight, token_bonus);
         return true;
     });
 }

@@ -29,6 +29,7 @@
 #include "../../include/april_api.h"
 #include "../../include/aprilx_engine.h"
 #include "bias.h"
+#include "lm.h"
 #include "engine.h"
 #include "model_loader.h"
 
@@ -90,6 +91,17 @@ public:
     void set_bias(std::shared_ptr<const BiasSet> set) { bias_ = std::move(set); bias_state_ = 0; }
     const BiasSet *bias() const { return bias_.get(); }
     int bias_state() const { return bias_state_; }
+    // language model: the session's model and the host's own copy of its node, advanced wherever the bias state is
+    // advanced or cleared.  The replay does not need the model (the records carry the fused arg-max); the copy is the independent derivation
+    // the device's node is checked against (aprilx_session_lm_state).
+    void set_lm(std::shared_ptr<const LmSet> lm, float weight, float token_bonus)
+    {
+        lm_ = std::move(lm); lm_state_ = lm_ ? lm_->start : 0; lm_weight_ = lm_ ? weight : 0.0f; lm_bonus_ = lm_ ? token_bonus : 0.0f;
+    }
+    const LmSet *lm() const { return lm_.get(); }
+    int lm_state() const { return lm_state_; }
+    float lm_weight() const { return lm_weight_; }
+    float lm_token_bonus() const { return lm_bonus_; }
     // search options: null = none (the lines below run as they always did); else the endpoint silence E replaces
     // the 2200 ms, bl' = bl - p replaces the blank logit in the three comparisons, and U > 0 caps the utterance length at a word boundary
     void set_search_options(const AprilxSearchOptions *o)
@@ -123,6 +135,9 @@ private:
     const ConfRecord *side_ = nullptr;
     std::shared_ptr<const BiasSet> bias_;
     int bias_state_ = 0;
+    std::shared_ptr<const LmSet> lm_;
+    int lm_state_ = 0;
+    float lm_weight_ = 0.0f, lm_bonus_ = 0.0f;
     uint64_t evals_ = 0;                      // joiner evaluations consumed so far = rows aprilx_session_trace_logits has written
     size_t head_ = 0, last_call_head_ = 0;
     bool emitted_silence_ = true;
@@ -290,6 +305,7 @@ public:
     bool set_confidence(Session *s, int k);
     // aprilx_session_set_bias: the same rule; null = off.  False also when the engine has no room for another set
     bool set_bias(Session *s, std::shared_ptr<const BiasSet> set);
+    bool set_lm(Session *s, std::shared_ptr<const LmSet> lm, float weight, float token_bonus);
     // aprilx_session_set_search_options: the same rule; null = back to no options
     bool set_search_options(Session *s, const AprilxSearchOptions *o);
     // aprilx_session_set_vad: the same rule; plan null = off.  The detector and its counters start afresh

@@ -5,7 +5,7 @@
 //
 //   g++ -O2 -std=c++17 examples/serve_many.cpp -I include -L april_asr_amd -laprilasr -Wl,-rpath,$PWD/april_asr_amd -o serve_many
 //   ./serve_many model.april audio.raw [sessions=64] [mode=pipelined|lockstep] [input_rate] [--alternatives K] [--bias FILE [--bias-strict]]
-//               [--endpoint-ms N] [--blank-penalty X] [--vad] [--dtmf] [--tones] [--migrate S]
+//               [--endpoint-ms N] [--blank-penalty X] [--vad] [--dtmf] [--tones] [--migrate S] [--lm FILE [--lm-weight W]]
 //
 // Every session gets the same PCM16 file, rotated by (session index x 0.37 s) so that the streams differ.  With `input_rate` the file
 // is PCM16 at that rate and every session is told so (aprilx_session_set_input_rate): the library converts it to the model's rate on
@@ -17,6 +17,11 @@
 // (aprilx_bias_create / aprilx_session_set_bias, one set shared by all sessions); `--bias-sessions N` gives the set to the first N
 // sessions only (the others are unbiased neighbours on an engine that has opted in).  `--bias-strict` builds the set as a closed
 // phrase list (APRILX_BIAS_STRICT): the sessions that have it emit only sequences of the file's phrases.
+// `--lm FILE` (anywhere on the line): FILE is plain text from the caller's domain, one utterance per line, written the way the model's
+// tokens are written; the library estimates a byte 5-gram model from it (aprilx_lm_create) and every session's search adds
+// W * log P(token text) + B to its non-blank logits (aprilx_session_set_lm; `--lm-weight W`, default 0.3, a placeholder: no accuracy
+// has been measured; `--lm-bonus B`, default 0).  `--lm-sessions N` gives the model to the first N sessions only.  A session with a
+// model cannot be snapshotted: `--lm` with `--migrate` is refused.
 // `--endpoint-ms N` / `--blank-penalty X` (anywhere on the line): every session gets search options (aprilx_session_set_search_options):
 // an utterance ends N ms after its last token instead of 2200, X is subtracted from the blank logit in the decision.
 // `--vad` (anywhere on the line): every session gets the voice-activity detector with its default options (aprilx_session_set_vad); its line
@@ -87,13 +92,25 @@ static void on_result(void *ud, AprilResultType type, size_t count, const AprilT
 int main(int argc, char **argv)
 {
     int alternatives = 0;
-    const char *bias_file = nullptr;
+    const char *bias_file = nullptr, *lm_file = nullptr;
+    float lm_weight = 0.3f, lm_bonus = 0.0f;
+    int lm_sessions = -1;
     int bias_sessions = -1;
     bool bias_strict = false;
     long endpoint_ms = -1;
     const char *blank_penalty = nullptr;
     bool vad = false, dtmf = false, tones = false;
     long migrate = -1;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!strcmp(argv[i], "--lm") || !strcmp(argv[i], "--lm-weight") || !strcmp(argv[i], "--lm-bonus") || !strcmp(argv[i], "--lm-sessions")) {
+            if (!strcmp(argv[i], "--lm")) lm_file = argv[i + 1];
+            else if (!strcmp(argv[i], "--lm-weight")) lm_weight = strtof(argv[i + 1], nullptr);
+            else if (!strcmp(argv[i], "--lm-bonus")) lm_bonus = strtof(argv[i + 1], nullptr);
+            else lm_sessions = atoi(argv[i + 1]);
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2;
+            i = 0;
+        }
     for (int i = 1; i + 1 < argc; ++i)
         if (!strcmp(argv[i], "--migrate")) {
             migrate = atol(argv[i + 1]);
@@ -204,6 +221,23 @@ int main(int argc, char **argv)
         const int dropped = aprilx_bias_info(bias, &states, &edges);
         fprintf(stderr, "bias set%s: %zu phrases (%d left out as unspellable), %d states, %lld token edges\n", bias_strict ? " (strict)" : "", phrases.size(), dropped, states, (long long)edges);
     }
+    AprilxLm lm = nullptr;
+    if (lm_file) {
+        if (migrate >= 0) { fprintf(stderr, "--lm and --migrate exclude each other: a snapshot does not carry the language model's node\n"); return 1; }
+        FILE *lf = fopen(lm_file, "rb");
+        if (!lf) { fprintf(stderr, "cannot open %s\n", lm_file); return 1; }
+        std::string text;
+        char buf[65536];
+        for (size_t got; (got = fread(buf, 1, sizeof buf, lf)) > 0;) text.append(buf, got);
+        fclose(lf);
+        char err[256];
+        lm = aprilx_lm_create(model, text.data(), text.size(), 5, err, sizeof err);
+        if (!lm) { fprintf(stderr, "language model refused: %s\n", err); return 1; }
+        int32_t order = 0, nodes = 0, start = 0, alphabet = 0; int64_t arcs = 0;
+        const int dropped = aprilx_lm_info(lm, &order, &nodes, &arcs, &start, &alphabet);
+        fprintf(stderr, "language model: order %d, %d nodes, %lld arcs, %d bytes in the alphabet, %d lines left out; weight %.3f, bonus %.3f\n", order, nodes, (long long)arcs, alphabet, dropped,
+                lm_weight, lm_bonus);
+    }
     std::vector<Stream> streams((size_t)n);
     std::vector<AprilASRSession> sessions((size_t)n);
     std::vector<std::vector<short>> audio((size_t)n);
@@ -218,6 +252,7 @@ int main(int argc, char **argv)
         if (argc > 5 && aprilx_session_set_input_rate(sessions[(size_t)i], (uint32_t)rate) != 0) { fprintf(stderr, "input rate %zu refused\n", rate); return 1; }
         if (alternatives && aprilx_session_set_confidence(sessions[(size_t)i], alternatives) != 0) { fprintf(stderr, "%d alternatives refused\n", alternatives); return 1; }
         if (bias && (bias_sessions < 0 || i < bias_sessions) && aprilx_session_set_bias(sessions[(size_t)i], bias) != 0) { fprintf(stderr, "bias set refused by session %d\n", i); return 1; }
+        if (lm && (lm_sessions < 0 || i < lm_sessions) && aprilx_session_set_lm(sessions[(size_t)i], lm, lm_weight, lm_bonus) != 0) { fprintf(stderr, "language model refused by session %d\n", i); return 1; }
         if (endpoint_ms >= 0 || blank_penalty) {
             AprilxSearchOptions so;
             so.size = (uint32_t)sizeof so; so.endpoint_silence_ms = endpoint_ms >= 0 ? (uint32_t)endpoint_ms : 2200u; so.max_utterance_ms = 0;
@@ -289,6 +324,12 @@ int main(int argc, char **argv)
         fprintf(stderr, "%d alternatives: %.3f ms per 100 ms step, mean confidence of %zu final tokens %.3f\n", alternatives, ms / (double)steps, cnt, cnt ? sum / (double)cnt : 0.0);
     }
     if (bias) fprintf(stderr, "phrase boosting: %.3f ms per 100 ms step\n", ms / (double)steps);
+    if (lm) {
+        uint64_t launches = 0, uploads = 0; int32_t resident = 0;
+        aprilx_model_lm_stats(model, 0, &launches, &resident, &uploads);
+        fprintf(stderr, "language model: %.3f ms per 100 ms step, %llu decision launches of the LM forms issued, %d model(s) resident on device 0\n", ms / (double)steps,
+                (unsigned long long)launches, resident);
+    }
     if (endpoint_ms >= 0 || blank_penalty) fprintf(stderr, "search options: %.3f ms per 100 ms step\n", ms / (double)steps);
     if (vad) {
         uint64_t launches = 0, frames = 0; double kms = 0; size_t segs = 0; double secs = 0;
@@ -314,6 +355,7 @@ int main(int argc, char **argv)
     if (argc > 5) fprintf(stderr, "input at %zu Hz: %.3f ms per 100 ms step\n", rate, ms / (double)steps);
     for (AprilASRSession s : sessions) aas_free(s);
     if (bias) aprilx_bias_free(bias);
+    if (lm) aprilx_lm_free(lm);
     aam_free(model);
     return 0;
 }

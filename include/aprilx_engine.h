@@ -318,6 +318,50 @@ APRIL_EXPORT int aprilx_session_search_options(AprilASRSession session, AprilxSe
 APRIL_EXPORT int aprilx_run_decide_opts(AprilASRModel model, int n, int op, const float *logits, float early_emit, const int32_t *now_ms, int round,
                                         int32_t *state_io, void *records_out, AprilxBias bias, int32_t *bias_state_io, const AprilxSearchOptions *opts);
 
+/* ---- language model: a byte n-gram model of the caller's own text --------------------------
+ * "We have a pile of text from our domain; make the recogniser prefer what that text makes likely."  The library estimates a byte-level
+ * n-gram model (interpolated Witten-Bell, order 2 .. 8) from plain text and the search adds  w * log P(token text | what was emitted) + b
+ * to every non-blank logit -- on the GPU, where the arg-max reads the logit row (DESIGN.md section 20 has the contract).  The text is
+ * written the way the model's tokens are written (no case folding); lines are separate utterances; a line holding a byte that no token
+ * has is left out and counted.  No tokeniser is needed: the model works on bytes and is independent of the segmentation.
+ * AprilToken.logprob of a session with a model is the value the search compared, the LM term included.  Sessions without a model are not
+ * affected.  No accuracy is claimed: the default weight is a placeholder until real audio has been run. */
+typedef struct AprilxLm_i *AprilxLm;
+/* Builds a model for this model's token list (no GPU needed; works on aprilx_model_load_host models).  NULL and a message in err when
+ * refused: an order outside 2 .. 8, a token whose text holds the byte 0x0A, a vocabulary over 8192 tokens, a corpus over 64 MiB, more than
+ * 4 Mi nodes or 16 Mi arcs, no line left.  Dropped lines are counted (aprilx_lm_info; err then holds a note although the call succeeds). */
+APRIL_EXPORT AprilxLm aprilx_lm_create(AprilASRModel model, const void *text, size_t text_len, int order, char *err, size_t err_cap);
+/* Sessions still using the model keep it alive. */
+APRIL_EXPORT void aprilx_lm_free(AprilxLm lm);
+/* Order, nodes, arcs, start node and alphabet size; returns the number of corpus lines left out (-1: no model). */
+APRIL_EXPORT int aprilx_lm_info(AprilxLm lm, int32_t *order, int32_t *nodes, int64_t *arcs, int32_t *start, int32_t *alphabet);
+/* The automaton (no GPU): node_off [nodes + 1], back / bow [nodes], arc_byte / arc_logp / arc_next [arcs]; any pointer may be NULL.
+ * node_cap / arc_cap: the nodes / arcs the arrays hold (node_off one more).  0, or -1 when a capacity is too small. */
+APRIL_EXPORT int aprilx_lm_arrays(AprilxLm lm, int32_t *node_off, int32_t *back, float *bow, uint8_t *arc_byte, float *arc_logp, int32_t *arc_next,
+                                  float *unk_logp, size_t node_cap, size_t arc_cap);
+/* score(state, tok) of the contract as the host walks it: the fp32 sum over the bytes of the token's text and the node reached. */
+APRIL_EXPORT int aprilx_lm_score_host(AprilxLm lm, int32_t state, int32_t tok, float *score, int32_t *next);
+/* Extends aas_create_session: the session's search uses the model from now on, starting at its start node; NULL = off.  weight: finite,
+ * 0 .. 10; token_bonus: finite, |b| <= 100 (added per non-blank token: the counterweight, with the blank penalty, to the model's pull
+ * towards the blank).  0 on success; -1 and a logged message when a value is out of range, the model was built for another token list,
+ * the engine already holds 8 other models in use, or the session has audio queued or fed since its creation / last completed aas_flush
+ * (the rule of aprilx_session_set_input_rate).  A session with a model refuses aprilx_session_snapshot / aprilx_session_restore. */
+APRIL_EXPORT int aprilx_session_set_lm(AprilASRSession session, AprilxLm lm, float weight, float token_bonus);
+/* The model's node as the host's state machine holds it and as the device keeps it for the session's slot: derived independently, must
+ * agree; tests only.  Returns 1 when the session has a model, 0 when not. */
+APRIL_EXPORT int aprilx_session_lm_state(AprilASRSession session, int32_t *host_state, int32_t *device_state);
+/* Decision launches of the language-model forms issued so far (one captured into a graph counts once), models resident on the device now,
+ * model uploads so far: all zero while no session of the engine has had a model. */
+APRIL_EXPORT int aprilx_model_lm_stats(AprilASRModel model, int device_index, uint64_t *launches, int32_t *resident, uint64_t *uploads);
+/* Tests only: aprilx_run_decide_opts (bias and opts may be NULL) plus the model on the rows whose lm_state_io[i] >= 0 (the row's node, in
+ * and out); -1 = a row without a model.  op 1 returns those rows to the start node. */
+APRIL_EXPORT int aprilx_run_decide_lm(AprilASRModel model, int n, int op, const float *logits, float early_emit, const int32_t *now_ms, int round,
+                                      int32_t *state_io, void *records_out, AprilxBias bias, int32_t *bias_state_io, const AprilxSearchOptions *opts,
+                                      AprilxLm lm, int32_t *lm_state_io, float weight, float token_bonus);
+/* Tests only: aprilx_run_confidence_biased (bias may be NULL) plus the model on the rows whose lm_state[i] >= 0. */
+APRIL_EXPORT int aprilx_run_confidence_lm(AprilASRModel model, int n, const float *logits, int k, AprilxBias bias, const int32_t *bias_state, AprilxLm lm,
+                                          const int32_t *lm_state, float weight, float token_bonus, AprilxTokenInfo *out);
+
 /* ---- tracing / statistics ---------------------------------------------------------------*/
 /* every joiner evaluation of this session appends `vocab` floats to buf (tests only; chunk steps of a traced session are
    issued eagerly and waited for one by one) */
@@ -638,6 +682,9 @@ APRIL_EXPORT int aprilx_greedy_set_bias(AprilxGreedy g, AprilxBias bias);
 APRIL_EXPORT int aprilx_greedy_bias_state(AprilxGreedy g);
 /* the state machine with search options (NULL = none); -1 on a wrong size or a value out of range */
 APRIL_EXPORT int aprilx_greedy_set_search_options(AprilxGreedy g, const AprilxSearchOptions *options);
+/* the state machine's own copy of the language-model node: attach a model (NULL = off; the node returns to the model's start), read the node */
+APRIL_EXPORT int aprilx_greedy_set_lm(AprilxGreedy g, AprilxLm lm, float weight, float token_bonus);
+APRIL_EXPORT int aprilx_greedy_lm_state(AprilxGreedy g);
 
 /* A result handler implemented in C, for load generators and benchmarks (a Python or JNI callback costs more than
    the GPU step at thousands of sessions).  userdata -> uint64_t[6]: calls, partial, final, cant_keep_up, silence, tokens */
