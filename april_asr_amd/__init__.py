@@ -531,6 +531,14 @@ class Model:
             raise ValueError("aprilx_model_ramp_stats refused the call")
         return int(h.value), int(e.value)
 
+    def ramp_stats2(self, device_index: int = 0):
+        """dict: hosted, eligible, headless (layer graphs launched without their head), settled_wait / settled_other (deferred layer graphs enqueued
+        by the stepping thread's wait for a flight / by any other engine entry)"""
+        out = (C.c_uint64 * 5)()
+        if self._L.aprilx_model_ramp_stats2(self._handle, device_index, out) != 0:
+            raise ValueError("aprilx_model_ramp_stats2 refused the call")
+        return dict(zip(("hosted", "eligible", "headless", "settled_wait", "settled_other"), (int(v) for v in out)))
+
     def feed_latencies(self, device_index: int = 0, reset: bool = False) -> np.ndarray:
         """hand-over -> delivery latency (ms) of the last completed ticks of one GPU's stepping thread, oldest first"""
         n = int(self._L.aprilx_model_feed_latency(self._handle, device_index, None, 0, 0))

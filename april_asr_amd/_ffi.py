@@ -164,7 +164,7 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_run_decide_biased", "aprilx_greedy_set_bias", "aprilx_greedy_bias_state",
     "aprilx_bias_create_ex", "aprilx_bias_flags", "aprilx_run_confidence_biased",
     "aprilx_session_set_search_options", "aprilx_session_search_options", "aprilx_run_decide_opts", "aprilx_greedy_set_search_options",
-    "aprilx_ramp_window", "aprilx_model_ramp_stats",
+    "aprilx_ramp_window", "aprilx_model_ramp_stats", "aprilx_model_ramp_stats2",
     "aprilx_session_set_input_format", "aprilx_session_input_format", "aprilx_session_feed_bytes", "aprilx_feed_many_bytes",
     "aprilx_decode_host", "aprilx_decode", "aprilx_model_decode_stats",
     "aprilx_session_set_vad", "aprilx_session_vad", "aprilx_vad_plan_tables", "aprilx_vad_host", "aprilx_vad_events_host", "aprilx_run_vad",
@@ -228,6 +228,7 @@ def lib():
     L.aprilx_run_gemm.argtypes = [vp] * 5; L.aprilx_run_gemm.restype = C.c_int
     L.aprilx_ramp_window.argtypes = [C.c_int] * 3 + [vp, C.c_int]; L.aprilx_ramp_window.restype = C.c_int
     L.aprilx_model_ramp_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]; L.aprilx_model_ramp_stats.restype = C.c_int
+    L.aprilx_model_ramp_stats2.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64)]; L.aprilx_model_ramp_stats2.restype = C.c_int
     L.aprilx_stream_form.argtypes = [C.c_int] * 6; L.aprilx_stream_form.restype = C.c_int
     L.aprilx_run_decide.argtypes = [vp, C.c_int, C.c_int, vp, C.c_float, vp, C.c_int, vp, vp]; L.aprilx_run_decide.restype = C.c_int
     L.aprilx_session_trace_logits.argtypes = [vp, vp, sz, C.POINTER(sz)]; L.aprilx_session_trace_logits.restype = None

@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <thread>
 #include "common.h"
 #include "env.h"
 #include "rowepi_forms.h"
@@ -285,8 +286,12 @@ Engine::Engine(const EngineConfig &cfg, const PackedLayout &layout, const float 
     for (int p = 0; p < 2; ++p) { xb_buf_[p] = dmalloc<float>(MB * d.d_model); u_buf_[p] = dmalloc<float>(MB * d.hidden); ff_buf_[p] = dmalloc<float>(MB * d.ffn); }
     xb_ = xb_buf_[0]; u_ = u_buf_[0]; ff_ = ff_buf_[0];
     ramp_mode_ = env_int("APRIL_RAMP_MERGE", 1);
-    if (ramp_mode_ < 0 || ramp_mode_ > 2) ramp_mode_ = 1;
+    if (ramp_mode_ < 0 || ramp_mode_ > 3) ramp_mode_ = 1;
     ramp_d_ = dmalloc<RampState>(1); HIP_CHECK(hipMemset(ramp_d_, 0, sizeof(RampState)));
+    if (ramp_mode_ == 1) {      // the latch's report: coherent pinned memory, the device stores to it and the host polls it
+        HipLegacyLock legacy;
+        HIP_CHECK(hipHostMalloc((void **)&ramp_word_h_, sizeof *ramp_word_h_, hipHostMallocCoherent)); *ramp_word_h_ = 0;
+    }
     de_ = dmalloc<float>(MB * d.d_model);
     HIP_CHECK(hipMemset(de_, 0, MB * d.d_model * 4));            // rows whose context did not change are read (never stored) by the decoder projection
     logits_ = dmalloc<float>(3 * MB * d.vocab);
@@ -311,7 +316,7 @@ Engine::Engine(const EngineConfig &cfg, const PackedLayout &layout, const float 
     upload_tables(ft);
     use_graphs_ = env_int("APRIL_NO_GRAPHS", 0) == 0;
     if (const int n = env_int("APRIL_GRAPH_CACHE_CAP", 0))        // tests: every family of captured chains is emptied early (a both-parity capture inserts two entries)
-        step_graphs_.cap = lm_graphs_.cap = lm_search_graphs_.cap = sw_plan_cap_ = (size_t)std::max(n, 2), sw_graphs_.cap = 4 * sw_plan_cap_;
+        step_graphs_.cap = lm_graphs_.cap = lm_search_graphs_.cap = sw_plan_cap_ = (size_t)std::max(n, 2), sw_graphs_.cap = 5 * sw_plan_cap_;
     free_.reserve(S);
     for (int i = cfg_.max_slots - 1; i >= 0; --i) free_.push_back(i);
     LOGI("engine: device %d, %d slots, max batch %d, weights %.1f MB, kz(embed,hr,ff2,proj,out)=%d,%d,%d,%d,%d",
@@ -387,11 +392,14 @@ Engine::~Engine()
 {
     HipLegacyLock legacy;
     (void)hipSetDevice(cfg_.device);
+    settle_pending_layers(true, RampDefer::BY_OTHER);      // (a deferred layer graph, its search and its flight event: enqueued, then waited for like the rest)
     (void)hipStreamSynchronize(f_stream_); (void)hipStreamSynchronize(stream_); (void)hipStreamSynchronize(s_stream_);
     dump_stream_trace();
     if (ramp_d_ && ramp_eligible_.load() > 0) {
         unsigned h = 0;
         if (hipMemcpy(&h, &ramp_d_->hosted, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) LOGI("engine: ramp merge: %u of %llu hostable split feeds were hosted by their predecessor", h, (unsigned long long)ramp_eligible_.load());
+        if (defer_.deferred) LOGI("engine: ramp merge: %llu layer graphs deferred, %llu launched headless; settled by the flight wait %llu, by another entry %llu", (unsigned long long)defer_.deferred,
+                                  (unsigned long long)defer_.headless, (unsigned long long)defer_.settled_by[RampDefer::BY_WAIT], (unsigned long long)defer_.settled_by[RampDefer::BY_OTHER]);
     }
     for (StreamTrace &t : trace_) for (hipEvent_t e : t.ev) if (e) (void)hipEventDestroy(e);
     if (trace_base_) (void)hipEventDestroy(trace_base_);
@@ -424,6 +432,7 @@ Engine::~Engine()
                         (void *)xb16_buf_[p], (void *)u16_buf_[p], (void *)ff16_buf_[p], (void *)rec_off_buf_[p], (void *)flags_buf_[p], (void *)step_buf_[p]}) if (q) (void)hipFree(q);
     if (ws_fe_) (void)hipFree(ws_fe_);
     if (ws_sr_) (void)hipFree(ws_sr_);
+    if (ramp_word_h_) (void)hipHostFree(ramp_word_h_);
     for (void *p : {(void *)wx_, (void *)h16_, (void *)ramp_d_}) if (p) (void)hipFree(p);      // (fp16 tile path; ramp merge)
     for (void *p : {(void *)w_, (void *)wh_, (void *)h_, (void *)c_, (void *)ring_, (void *)eout_, (void *)dout_, (void *)gstate_, (void *)cls_, (void *)ws_, (void *)xin_,
                     (void *)a3_, (void *)de_, (void *)logits_, (void *)rec_d_, (void *)counter_d_,
@@ -512,6 +521,7 @@ void Engine::free_slot(int slot)
 // while the stepping thread keeps enqueueing).
 void Engine::sync_streams()
 {
+    settle_pending_layers(true, RampDefer::BY_OTHER);      // (what is deferred belongs to "everything enqueued so far")
     HIP_CHECK(hipStreamSynchronize(f_stream_)); HIP_CHECK(hipStreamSynchronize(stream_)); HIP_CHECK(hipStreamSynchronize(s_stream_));
 }
 
@@ -601,7 +611,7 @@ void Engine::dump_stream_trace()
     FILE *f = fopen(path, "w");
     if (!f) return;
     fprintf(f, "# one line per split feed; times in us since the first split feed; FE = index fetch + conv + embed on stream F, LY = layer wavefront on M, SR = encoder_proj + search on S\n");
-    fprintf(f, "# feed sessions chunks  FE_start FE_end  LY_start LY_end  SR_start SR_end   overlap: FE inside the previous feed's LY window? SR inside the next feed's LY window?\n");
+    fprintf(f, "# feed sessions chunks  FE_start FE_end  LY_start LY_end  SR_start SR_end   overlap: FE inside the previous feed's LY window? SR inside the next feed's LY window?  LY flavour: headless / head\n");
     std::vector<std::array<float, 6>> ts;
     for (StreamTrace &t : trace_) {
         std::array<float, 6> a{};
@@ -613,8 +623,8 @@ void Engine::dump_stream_trace()
         const auto &a = ts[i];
         const bool fe_in_prev = i > 0 && a[0] * 1e3f < ts[i - 1][3] * 1e3f && a[1] * 1e3f > ts[i - 1][2] * 1e3f;
         const bool sr_in_next = i + 1 < ts.size() && a[5] > ts[i + 1][2] && a[4] < ts[i + 1][3];
-        fprintf(f, "%4zu %5d %2d  %10.1f %10.1f  %10.1f %10.1f  %10.1f %10.1f   %s %s\n", i, trace_[i].m, trace_[i].T, a[0] * 1e3, a[1] * 1e3, a[2] * 1e3, a[3] * 1e3, a[4] * 1e3, a[5] * 1e3,
-                fe_in_prev ? "FE<prevLY" : "-", sr_in_next ? "SR<nextLY" : "-");
+        fprintf(f, "%4zu %5d %2d  %10.1f %10.1f  %10.1f %10.1f  %10.1f %10.1f   %s %s %s\n", i, trace_[i].m, trace_[i].T, a[0] * 1e3, a[1] * 1e3, a[2] * 1e3, a[3] * 1e3, a[4] * 1e3, a[5] * 1e3,
+                fe_in_prev ? "FE<prevLY" : "-", sr_in_next ? "SR<nextLY" : "-", trace_[i].headless ? "headless" : "head");
     }
     fclose(f);
 }
@@ -1403,6 +1413,7 @@ Engine::SwPlan &Engine::sw_plan(int m, int T)
     build_sw_chain(p, p.one, m, T, false);
     // (clocked runs never take the split flavour: run_feed_wavefront)
     if (ramp_mode_ != 0 && !gclk_) build_sw_chain(p, p.split, m, T, true);
+    if (ramp_mode_ == 1 && !gclk_ && L_.dims.n_layers > 2 * RAMP_R) build_sw_chain(p, p.headless, m, T, true, true);      // (L <= 2 R: nobody hosts, ramp_window)
     return p;
 }
 
@@ -1412,8 +1423,10 @@ Engine::SwPlan &Engine::sw_plan(int m, int T)
 // the tail [2, 1] of feed k and the head [1, 2] of feed k + 1 run as [3, 3]: the split-flavour plan of (m, T, parity p) carries, in
 // its last RAMP_R macro steps, GUEST argument blocks for the first RAMP_R macro steps of a feed of m sessions of the other parity
 // (their rows t * m in that parity's buffers: they depend on m only).  Guest blocks run only when the word the latch kernel wrote
-// for them holds 1; the own blocks of every split plan's first RAMP_R macro steps run only while head_live[p] holds 1.  The
-// decision is the device's (kernels_misc.hip, ramp_latch_kernel); the scheduler and the flight life cycle know nothing of it.
+// for them holds 1.  The decision is the device's (kernels_misc.hip, ramp_latch_kernel); the scheduler knows nothing of it.
+// APRIL_RAMP_MERGE=1: the latch reports the decision to the host, which enqueues the hosted feed's layer graph only then, and without the
+// head steps ("deferred enqueue", below).  =3 / =2, the guarded forms: the next feed's graph is enqueued at once, and the own blocks of
+// every split plan's first RAMP_R macro steps run only while head_live[p] holds 1.
 std::vector<RampStep> ramp_window(int L, int T, int R, int max_problems)
 {
     std::vector<RampStep> w;
@@ -1438,8 +1451,11 @@ void Engine::ramp_counts(uint64_t *hosted, uint64_t *eligible)
     *hosted = h; *eligible = ramp_eligible_.load(std::memory_order_relaxed);
 }
 
-void Engine::build_sw_chain(SwPlan &p, SwPlan::Chain &c, int m, int T, bool ramp)
+// ramp: the split flavour (latch, guest window).  Its head steps sit behind head_live in the guarded forms only (APRIL_RAMP_MERGE=3 / 2); with the deferred enqueue
+// the chain with the head is launched only where the head runs.  headless: the same chain from macro step RAMP_R + 1 on -- same blocks, forms and staging.
+void Engine::build_sw_chain(SwPlan &p, SwPlan::Chain &c, int m, int T, bool ramp, bool headless)
 {
+    const bool guard = ramp && ramp_mode_ != 1;
     const NetDims &d = L_.dims;
     const int L = d.n_layers;
     const int par = flight_parity_;
@@ -1462,7 +1478,7 @@ void Engine::build_sw_chain(SwPlan &p, SwPlan::Chain &c, int m, int T, bool ramp
     if (ramp) p.hosts = !window.empty();
     std::vector<GemmArgs> items;
     std::vector<RowArgs> rows;
-    for (int W = 0; W <= T + L; ++W) {
+    for (int W = headless ? RAMP_R + 1 : 0; W <= T + L; ++W) {
         const RampStep *host = nullptr; int wj = 0;
         for (size_t j = 0; j < window.size(); ++j) if (window[j].macro == W) { host = &window[j]; wj = (int)j; }
         if (host && wj == 0) { SwPlan::Batch b; b.off = c.host.size(); b.n = 0; b.macro = W; b.kind = 4; b.roff = c.rhost.size(); b.rn = 0; c.batches.push_back(b); }      // the latch
@@ -1492,7 +1508,7 @@ void Engine::build_sw_chain(SwPlan &p, SwPlan::Chain &c, int m, int T, bool ramp
             for (int l = 0; l < L; ++l) {
                 const int t = W - 1 - l;
                 if (t < 0 || t >= T) continue;
-                problem(l, t, ramp && W <= RAMP_R ? &ramp_d_->head_live[par] : nullptr);
+                problem(l, t, guard && W <= RAMP_R ? &ramp_d_->head_live[par] : nullptr);
             }
             if (host) {
                 select_parity(1 - par);
@@ -1544,12 +1560,12 @@ void Engine::build_sw_chain(SwPlan &p, SwPlan::Chain &c, int m, int T, bool ramp
 void Engine::free_sw_plans()
 {
     if (!sw_plans_.empty()) LOGI("engine: feed wavefront plans emptied (%zu plans)", sw_plans_.size());
-    for (auto &p : sw_plans_) for (SwPlan::Chain *c : {&p.second.one, &p.second.split}) { if (c->dev) (void)hipFree(c->dev); if (c->rdev) (void)hipFree(c->rdev); }
+    for (auto &p : sw_plans_) for (SwPlan::Chain *c : {&p.second.one, &p.second.split, &p.second.headless}) { if (c->dev) (void)hipFree(c->dev); if (c->rdev) (void)hipFree(c->rdev); }
     sw_graphs_.clear(); sw_plans_.clear();
 }
 
-// part 0: index fetch + front end (stream fe), 1: the layer wavefront + encoder_proj (stream ly), 2: the searches (stream sr);
-// parts < 0: all three in order on one stream
+// part 0: index fetch + front end (stream fe), 1: the layer wavefront (stream ly), 2: encoder_proj + the searches (stream sr), 3: the headless
+// layer wavefront (stream ly); parts < 0: the first three in order on one stream
 void Engine::run_sw_chain(int m, int T, bool dump_logits, const SwPlan &p, int part, hipStream_t st)
 {
     const NetDims &d = L_.dims;
@@ -1560,12 +1576,12 @@ void Engine::run_sw_chain(int m, int T, bool dump_logits, const SwPlan &p, int p
         // layer-major step), before the first and after the last macro step; the searches follow in time order.
         encoder_front(0, m * T, step_d_ + 3 * MB, nullptr, st, part == 0 ? ws_fe_ : ws_);
     }
-    if (part < 0 || part == 1) {
+    if (part < 0 || part == 1 || part == 3) {
         static const int cls_of[4] = {T_GATES, T_GEMM_OTHER, T_GEMM_OTHER, T_GEMM_OTHER};
-        const SwPlan::Chain &c = p.layers(part == 1);           // (a split feed's layer graph: the ramp-merge flavour, when it is on)
+        const SwPlan::Chain &c = part == 3 ? p.headless : p.layers(part == 1);      // (a split feed's layer graph: the ramp-merge flavour, when it is on)
         for (size_t bi = 0; bi < c.batches.size(); ++bi) {      // macro steps in order; inside one: gates, projection, FFN up, FFN down of the active layers
             const SwPlan::Batch &b = c.batches[bi];
-            if (b.kind == 4) { launch_ramp_latch(ramp_d_, flight_parity_, m, st); continue; }
+            if (b.kind == 4) { launch_ramp_latch(ramp_d_, flight_parity_, m, ramp_word_h_, ramp_mode_ != 1 ? 1 : 0, st); continue; }
             timed_begin(cls_of[b.kind]); launch_gemm_z(c.host.data() + b.off, b.n, c.dev + b.off, st); timed_end(cls_of[b.kind]);
             if (b.rn > 0) { timed_begin(T_ROW); launch_row_z(c.rhost.data() + b.roff, b.rn, c.rdev + b.roff, st); timed_end(T_ROW); }
         }
@@ -1622,8 +1638,10 @@ void Engine::run_feed_wavefront(int m, int T, bool dump_logits)
     if (graphs && !sw_graphs_.find(sw_key(m, T, split ? 1 : 0)))
         capture_both_parities([&]() {
             const SwPlan &pl = sw_plan(m, T);
-            if (split) for (int part = 0; part < 3; ++part) cached_graph(sw_graphs_, sw_key(m, T, 1 + part), on[part], [&]() { run_sw_chain(m, T, false, pl, part, on[part]); });
-            else cached_graph(sw_graphs_, sw_key(m, T), stream_, [&]() { run_sw_chain(m, T, false, pl, -1, stream_); });
+            if (split) {
+                for (int part = 0; part < 3; ++part) cached_graph(sw_graphs_, sw_key(m, T, 1 + part), on[part], [&]() { run_sw_chain(m, T, false, pl, part, on[part]); });
+                if (!pl.headless.batches.empty()) cached_graph(sw_graphs_, sw_key(m, T, 4), on[1], [&]() { run_sw_chain(m, T, false, pl, 3, on[1]); });
+            } else cached_graph(sw_graphs_, sw_key(m, T), stream_, [&]() { run_sw_chain(m, T, false, pl, -1, stream_); });
         });
     if (split) { launch_split_feed(m, T, on[0]); return; }
     general_prologue();
@@ -1634,31 +1652,117 @@ void Engine::run_feed_wavefront(int m, int T, bool dump_logits)
 // split feed: front end on F (`fe`; split_streams_ == 1 keeps it on M), layers on M, search on S, chained by events inside the feed (see "streams" above)
 void Engine::launch_split_feed(int m, int T, hipStream_t fe)
 {
+    settle_pending_layers(true, RampDefer::BY_OTHER);      // (begin_flight has: one deferral at a time)
     if (fe == f_stream_) {
         if (m_unseen_by_f_) { join(f_stream_, stream_); m_unseen_by_f_ = false; }
     } else if (f_unseen_by_m_) { join(stream_, f_stream_); f_unseen_by_m_ = false; }       // (the fbank launch of this flight)
     if (m_unseen_by_s_) { join(s_stream_, stream_); m_unseen_by_s_ = false; }
-    StreamTrace *tr = trace_slot();
-    auto part = [&](int i, hipStream_t st) {          // one of the feed's three graphs between its two trace events
-        if (tr) HIP_CHECK(hipEventRecord(tr->ev[2 * i], st));
-        HIP_CHECK(hipGraphLaunch(sw_graphs_.find(sw_key(m, T, 1 + i)), st));
-        if (tr) HIP_CHECK(hipEventRecord(tr->ev[2 * i + 1], st));
-    };
-    part(0, fe);
+    PendingFeed pf;
+    pf.m = m; pf.T = T; pf.parity = flight_parity_; pf.tr = trace_slot(); pf.hosts = sw_plan(m, T).hosts;
+    if (pf.tr) HIP_CHECK(hipEventRecord(pf.tr->ev[0], fe));
+    HIP_CHECK(hipGraphLaunch(sw_graphs_.find(sw_key(m, T, 1)), fe));
+    if (pf.tr) HIP_CHECK(hipEventRecord(pf.tr->ev[1], fe));
+    bool offered = false;
     if (ramp_mode_ != 0) {
-        // the feed's front end is through: arm its head and tell the previous feed's latch.  hostable: that feed's layer graph is still the last thing M was
-        // given (m_quiet_, engine.h), and the front end ran beside it on F.  Read before this feed's own enqueues on M.
-        const bool hostable = ramp_mode_ == 1 && fe == f_stream_ && m_quiet_.load(std::memory_order_acquire);
-        if (hostable) ramp_eligible_.fetch_add(1, std::memory_order_relaxed);
-        launch_ramp_ready(ramp_d_, flight_parity_, m, T, hostable ? 1 : 0, fe);
+        // the feed's front end is through: tell the previous feed's latch (guarded forms: and arm this feed's head).  hostable: that feed's layer graph is still
+        // the last thing M was given (m_quiet_, engine.h), and the front end ran beside it on F.  Read before this feed's own enqueues on M.
+        // Deferred enqueue: it also needs a latch in that graph -- only a latch reports, and a feed whose graph holds the head unguarded must not be hosted.
+        const bool quiet = fe == f_stream_ && m_quiet_.load(std::memory_order_acquire);
+        offered = ramp_mode_ == 3 ? quiet : ramp_mode_ == 1 && quiet && m_tail_latch_;
+        if (offered) ramp_eligible_.fetch_add(1, std::memory_order_relaxed);
+        launch_ramp_ready(ramp_d_, flight_parity_, m, T, offered ? 1 : 0, ramp_mode_ != 1 ? 1 : 0, fe);
+        ++ramp_gen_h_;
     }
-    if (fe == f_stream_) { join(stream_, f_stream_); f_unseen_by_m_ = false; }
-    part(1, stream_);
-    if (ramp_mode_ != 0) m_quiet_.store(true, std::memory_order_release);
-    join(s_stream_, stream_); part(2, s_stream_);
-    if (tr) { tr->m = m; tr->T = T; tr->used = true; }
+    if (fe == f_stream_) {          // M waits for the front end: the event is recorded here, behind the ready kernel; the wait is enqueued with the layers
+        pf.fe_done = join_ev_[join_pos_++ % join_ev_.size()];
+        HIP_CHECK(hipEventRecord(pf.fe_done, f_stream_));
+    } else m_unseen_by_f_ = true;   // (front-end kernels on M read ring rows: the next fbank waits for them)
+    // ---- deferred enqueue: offered to a chain with a latch, the feed's layer graph waits for that latch's report.  Everything
+    // behind the front end -- layers, search, and the record copy and flight event of close_flight() -- is enqueued by settle_pending_layers().
+    std::lock_guard<std::mutex> g(defer_mu_);
+    const bool defer = ramp_mode_ == 1 && offered;
+    if (defer) pend_ = pf;
+    const uint64_t word = ramp_word_h_ ? __atomic_load_n(ramp_word_h_, __ATOMIC_ACQUIRE) : 0;
+    const bool open = defer_.launch(ramp_gen_h_, defer, word, [&](RampDefer::Flavour f) { enqueue_split_layers(pf, f == RampDefer::HEADLESS); });
+    defer_open_.store(open, std::memory_order_release);
+}
+
+// (defer_mu_ held, or nothing deferred) the half of a split feed behind its front end: the layer graph on M -- with the head, or headless when the chain in
+// front ran the head --, the search on S behind it, and the flight's tail if close_flight() has come in between.  Calls nothing that settles.
+void Engine::enqueue_split_layers(const PendingFeed &f, bool headless)
+{
+    StreamTrace *tr = f.tr;
+    auto graph = [&](int part) {
+        const hipGraphExec_t g = sw_graphs_.find(GraphCache::Key{f.m, f.T, f.parity * 8 + part});
+        if (!g) { LOGE("engine: split feed %d x %d, parity %d: graph %d is missing", f.m, f.T, f.parity, part); abort(); }
+        return g;
+    };
+    if (f.fe_done) { HIP_CHECK(hipStreamWaitEvent(stream_, f.fe_done, 0)); f_unseen_by_m_ = false; }
+    if (tr) HIP_CHECK(hipEventRecord(tr->ev[2], stream_));
+    HIP_CHECK(hipGraphLaunch(graph(headless ? 4 : 2), stream_));
+    if (tr) HIP_CHECK(hipEventRecord(tr->ev[3], stream_));
+    if (ramp_mode_ != 0) { m_tail_latch_ = f.hosts; m_quiet_.store(true, std::memory_order_release); }
+    join(s_stream_, stream_);
+    if (tr) HIP_CHECK(hipEventRecord(tr->ev[4], s_stream_));
+    HIP_CHECK(hipGraphLaunch(graph(3), s_stream_));
+    if (tr) { HIP_CHECK(hipEventRecord(tr->ev[5], s_stream_)); tr->m = f.m; tr->T = f.T; tr->headless = headless; tr->used = true; }
     s_unseen_by_m_ = true; flight_tail_s_ = true;
-    if (fe != f_stream_) m_unseen_by_f_ = true;          // (front-end kernels on M read ring rows: the next fbank waits for them)
+    if (f.closed) {
+        if (f.pass_bytes) join(s_stream_, f_stream_);
+        enqueue_flight_tail(s_stream_, f.parity, f.rec_base, f.rec_pos, f.conf_spans);
+    }
+}
+
+// ---------------------------------------------------------------- deferred enqueue
+// The ONE place a deferred layer graph is enqueued.  Every entry that touches M, S, the flight state or the graph caches comes through here first:
+// m_touched() (general_prologue, sync, the uploads, slot zeroing, plan building, captures), sync_streams(), begin_flight, close_flight's readers
+// wait_flight / flight_done, the destructor.  wait == false (wait_flight / flight_done: the stepping thread's time between two launches goes there)
+// looks at the report once; wait == true polls it.  The report always comes: the chain whose latch writes it is already on M and waits for
+// nothing the host still has to enqueue.  Should M run dry without it the books are wrong, and that is fatal rather than a hang.
+static inline void cpu_relax()
+{
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#else
+    std::this_thread::yield();
+#endif
+}
+
+bool Engine::settle_pending_layers(bool wait, RampDefer::Who who)
+{
+    if (!defer_open_.load(std::memory_order_acquire)) return true;
+    std::lock_guard<std::mutex> g(defer_mu_);
+    if (!defer_.pending()) return true;
+    (void)hipSetDevice(cfg_.device);
+    bool m_idle = false;
+    for (unsigned spins = 0;; ++spins) {
+        const uint64_t word = __atomic_load_n(ramp_word_h_, __ATOMIC_ACQUIRE);
+        if (defer_.poll(word, who, [&](RampDefer::Flavour f) { enqueue_split_layers(pend_, f == RampDefer::HEADLESS); })) {
+            pend_ = PendingFeed();
+            defer_open_.store(false, std::memory_order_release);
+            return true;
+        }
+        if (!wait) return false;
+        if (m_idle) { LOGE("engine: the layer stream is idle and no latch reported generation %u (word %llx)", defer_.wanted(), (unsigned long long)word); abort(); }
+        if ((spins & 1023u) == 1023u) {
+            const hipError_t e = hipStreamQuery(stream_);
+            if (e == hipSuccess) m_idle = true; else if (e != hipErrorNotReady) HIP_CHECK(e); else (void)hipGetLastError();
+        }
+        for (int i = 0; i < 16; ++i) cpu_relax();
+    }
+}
+
+// the flight of this parity is closed and its event is part of what is deferred
+bool Engine::deferred_flight(int parity)
+{
+    std::lock_guard<std::mutex> g(defer_mu_);
+    return defer_.pending() && pend_.closed && pend_.parity == parity;
+}
+
+void Engine::ramp_defer_counts(uint64_t *headless, uint64_t *by_wait, uint64_t *by_other)
+{
+    std::lock_guard<std::mutex> g(defer_mu_);
+    *headless = defer_.headless; *by_wait = defer_.settled_by[RampDefer::BY_WAIT]; *by_other = defer_.settled_by[RampDefer::BY_OTHER];
 }
 
 // mode 0: layer-major; a long feed as a wavefront over blocks of time steps
@@ -1916,6 +2020,7 @@ void Engine::select_parity(int p)
 void Engine::begin_flight()
 {
     HIP_CHECK(hipSetDevice(cfg_.device));
+    settle_pending_layers(true, RampDefer::BY_OTHER);
     const int p = flight_parity_ = next_parity_; next_parity_ ^= 1;
     // the buffers of this parity (index ring half, record ring half, y / ssq / step tables, eout_lm) were lent to the flight before the
     // previous one: it must have completed -- the scheduler keeps at most two flights open and completes them in order, so the event
@@ -1988,6 +2093,18 @@ int Engine::close_flight()
 {
     HIP_CHECK(hipSetDevice(cfg_.device));
     std::lock_guard<std::mutex> cg(capture_mu_);
+    settle_pending_layers(false, RampDefer::BY_OTHER);
+    {
+        // the flight's last step is a split feed whose layers are deferred: its tail is on S behind a search that is not enqueued yet.  The copies and the
+        // event go out with it (enqueue_split_layers); wait_flight / flight_done settle before they look at the event.
+        std::lock_guard<std::mutex> g(defer_mu_);
+        if (defer_.pending()) {
+            pend_.closed = true; pend_.pass_bytes = pass_bytes_flight_; pend_.rec_base = rec_base_; pend_.rec_pos = rec_pos_; pend_.conf_spans.swap(conf_spans_);
+            pass_bytes_flight_ = false; conf_spans_.clear();
+            flight_open_[flight_parity_] = true;
+            return flight_parity_;
+        }
+    }
     // where the flight ends: on S when its last step was a split feed (layers on M, search on S: the record copy must not sit
     // in M's order, where it would hold the next flight's layers back until this search is through), else on M
     hipStream_t tail = s_stream_;
@@ -1997,19 +2114,27 @@ int Engine::close_flight()
         if (s_unseen_by_m_) { join(stream_, s_stream_); s_unseen_by_m_ = false; }
     } else if (pass_bytes_flight_) join(s_stream_, f_stream_);      // a pass's VAD / DTMF bytes are read after this flight's wait: their copy comes first
     pass_bytes_flight_ = false;
-    if (rec_pos_ > rec_base_) HIP_CHECK(hipMemcpyAsync(rec_h_ + rec_base_, rec_d_ + rec_base_, (rec_pos_ - rec_base_) * sizeof(StepRecord), hipMemcpyDeviceToHost, tail));
-    for (const auto &sp : conf_spans_) {          // side records: only the steps that hold a row of a session with confidences on
-        HIP_CHECK(hipMemcpyAsync(conf_h_ + sp.first, conf_d_ + sp.first, sp.second * sizeof(ConfRecord), hipMemcpyDeviceToHost, tail));
-        conf_copied_.fetch_add(sp.second, std::memory_order_relaxed);
-    }
+    enqueue_flight_tail(tail, flight_parity_, rec_base_, rec_pos_, conf_spans_);
     conf_spans_.clear();
-    HIP_CHECK(hipEventRecord(flight_done_[flight_parity_], tail));
     flight_open_[flight_parity_] = true;
     return flight_parity_;
 }
 
+// the record copy, the side records and the flight's event, at the end of the stream the flight ends on
+void Engine::enqueue_flight_tail(hipStream_t tail, int parity, size_t rec_base, size_t rec_pos, const std::vector<std::pair<size_t, size_t>> &conf_spans)
+{
+    if (rec_pos > rec_base) HIP_CHECK(hipMemcpyAsync(rec_h_ + rec_base, rec_d_ + rec_base, (rec_pos - rec_base) * sizeof(StepRecord), hipMemcpyDeviceToHost, tail));
+    for (const auto &sp : conf_spans) {          // side records: only the steps that hold a row of a session with confidences on
+        HIP_CHECK(hipMemcpyAsync(conf_h_ + sp.first, conf_d_ + sp.first, sp.second * sizeof(ConfRecord), hipMemcpyDeviceToHost, tail));
+        conf_copied_.fetch_add(sp.second, std::memory_order_relaxed);
+    }
+    HIP_CHECK(hipEventRecord(flight_done_[parity], tail));
+}
+
+// (both pollers look at the latch's report alongside the flight's event: this is where the stepping thread is while the hosting chain runs)
 bool Engine::flight_done(int parity)
 {
+    if (!settle_pending_layers(false, RampDefer::BY_WAIT) && deferred_flight(parity)) return false;      // (its event is not recorded yet)
     const hipError_t e = hipEventQuery(flight_done_[parity]);
     if (e == hipSuccess) return true;
     if (e != hipErrorNotReady) HIP_CHECK(e);
@@ -2020,6 +2145,15 @@ bool Engine::flight_done(int parity)
 void Engine::wait_flight(int parity)
 {
     HIP_CHECK(hipSetDevice(cfg_.device));
+    while (!settle_pending_layers(false, RampDefer::BY_WAIT)) {
+        // the deferred flight itself has no event to wait for until it is settled; an older flight may end before the report comes
+        if (deferred_flight(parity)) { settle_pending_layers(true, RampDefer::BY_WAIT); break; }
+        const hipError_t e = hipEventQuery(flight_done_[parity]);
+        if (e == hipSuccess) break;
+        if (e != hipErrorNotReady) HIP_CHECK(e);
+        (void)hipGetLastError();
+        for (int i = 0; i < 16; ++i) cpu_relax();
+    }
     HIP_CHECK(hipEventSynchronize(flight_done_[parity]));
     if (profiling_) sync();            // (profiled flights are completed one by one: every launch's event pair has run, collect them)
 }

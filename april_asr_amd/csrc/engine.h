@@ -33,6 +33,7 @@
 #include "input_format.h"
 #include "kernels.h"
 #include "host_pool.h"
+#include "ramp_defer.h"
 #include "slot_queue.h"
 #include "staging_layout.h"
 #include "model_loader.h"
@@ -83,7 +84,7 @@ struct KernelTiming { double ms = 0; long launches = 0; };
 // One family of captured launch chains: key -> instantiated graph, with a capacity.  A full family is emptied as a whole (its owner first drains the streams that may
 // still run one of its execs).  use() counts how often a batch shape has come by, for the families that capture at the SECOND use: a capture costs milliseconds.
 struct GraphCache {
-    using Key = std::array<int, 3>;          // {rows m (negated: built under the gates clock), chunks T / block length, flight parity * 4 + part}
+    using Key = std::array<int, 3>;          // {rows m (negated: built under the gates clock), chunks T / block length, flight parity * 8 + part}
     const char *name; size_t cap;
     bool full() const { return map_.size() >= cap; }
     hipGraphExec_t find(const Key &k) const { auto it = map_.find(k); return it == map_.end() ? nullptr : it->second; }
@@ -397,6 +398,8 @@ public:
     // ramp merge: feeds whose head a predecessor's layer graph ran (the device's count, read back: exact once the streams are idle) and
     // split feeds launched as hostable (any thread)
     void ramp_counts(uint64_t *hosted, uint64_t *eligible);
+    // ... and of the deferred enqueue (APRIL_RAMP_MERGE=1): headless layer graphs launched, deferrals settled by wait_flight / flight_done, by any other entry
+    void ramp_defer_counts(uint64_t *headless, uint64_t *by_wait, uint64_t *by_other);
     void reset_timing();
     enum { T_GATES = 0, T_GEMM_OTHER = 1, T_ROW = 2, T_CONV = 3, T_FBANK = 4, T_DEC = 5, T_RESAMPLE = 6, T_DECODE = 7, T_VAD = 8, T_DTMF = 9, T_TONE = 10,
            T_SNAP_GATHER = 11, T_SNAP_SCATTER = 12, T_COUNT = 13 };
@@ -435,23 +438,25 @@ private:
         struct Batch { size_t off; int n, macro, kind; size_t roff; int rn; };      // rn > 0: the GEMMs write partial planes, rn row problems finish them; kind 4: the ramp latch
         struct Chain { std::vector<GemmArgs> host; GemmArgs *dev = nullptr; std::vector<Batch> batches; std::vector<RowArgs> rhost; RowArgs *rdev = nullptr; };
         Chain one;                           // the one-stream graph and the eager path
-        Chain split;                         // the layer graph of a split feed while the ramp merge is on (else empty: `one` serves it); head steps behind head_live
-        bool hosts = false;                  // `split` carries guest blocks and the latch in its last RAMP_R macro steps
+        Chain split;                         // the layer graph of a split feed while the ramp merge is on (else empty: `one` serves it); guarded forms (APRIL_RAMP_MERGE=3 / 2): head steps behind head_live
+        Chain headless;                      // APRIL_RAMP_MERGE=1: `split` from macro step RAMP_R + 1 on, for a feed whose head the chain in front of it ran
+        bool hosts = false;                  // `split` and `headless` carry guest blocks and the latch in their last RAMP_R macro steps
         const Chain &layers(bool split_feed) const { return split_feed && !split.batches.empty() ? split : one; }
         std::vector<std::pair<int, long>> stamp_slots; std::vector<int> stamp_n;  // gates clock: (slot, rows) and problem count of every gates launch of a plan built while it was on
     };
-    // keys of the current flight parity (it selects buffers); plans built under the gates clock carry stamp slots: -m; part 0: the one-stream graph, 1..3: a split feed's
-    GraphCache::Key graph_key(int m, int T = 0, int part = 0) const { return {m, T, flight_parity_ * 4 + part}; }
+    // keys of the current flight parity (it selects buffers); plans built under the gates clock carry stamp slots: -m; part 0: the one-stream graph, 1..3: a split feed's,
+    // 4: its headless layer graph
+    GraphCache::Key graph_key(int m, int T = 0, int part = 0) const { return {m, T, flight_parity_ * 8 + part}; }
     GraphCache::Key sw_key(int m, int T, int part = 0) const { return graph_key(gclk_ ? -m : m, T, part); }
     SwPlan &sw_plan(int m, int T);
-    void build_sw_chain(SwPlan &p, SwPlan::Chain &c, int m, int T, bool ramp);
+    void build_sw_chain(SwPlan &p, SwPlan::Chain &c, int m, int T, bool ramp, bool headless = false);
     void free_sw_plans();                    // every plan's device blocks and graphs (streams drained, legacy lock held)
     void run_sw_chain(int m, int T, bool dump_logits, const SwPlan &p, int part, hipStream_t st);
     int stage_step(int m, int T, const int *slots, const int *ring_tails, const int *now_ms); void read_back_logits(int k, int rows, float *out);
     template <typename Chain> hipGraphExec_t cached_graph(GraphCache &cache, const GraphCache::Key &key, hipStream_t st, Chain &&chain);
     template <typename Capture> void capture_both_parities(Capture &&capture);
     void run_feed_wavefront(int m, int T, bool dump_logits); void run_layer_major(int m, int T, bool dump_logits); void launch_split_feed(int m, int T, hipStream_t fe);   // lm_step's paths
-    struct StreamTrace { hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; int m = 0, T = 0; bool used = false; };
+    struct StreamTrace { hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; int m = 0, T = 0; bool used = false, headless = false; };
     std::deque<StreamTrace> trace_; hipEvent_t trace_base_ = nullptr;
     StreamTrace *trace_slot();
     void dump_stream_trace();
@@ -535,15 +540,33 @@ private:
     bool f_unseen_by_m_ = false, s_unseen_by_m_ = false, m_unseen_by_f_ = false, m_unseen_by_s_ = false, flight_tail_s_ = false;
     bool overlap_hint_ = false;
     int split_streams_ = 2;                    // APRIL_SPLIT_STREAMS: 0 = one stream, 1 = search on S, 2 = search on S + front end on F
-    // ramp merge (engine.cc "ramp merge"): APRIL_RAMP_MERGE 0 = off, 1 = on, 2 = hosting plans and both kernels but never hostable
+    // ramp merge (engine.cc "ramp merge"): APRIL_RAMP_MERGE 0 = off, 1 = on with the deferred enqueue, 3 = on with the guarded head (the host does not look),
+    // 2 = the guarded hosting plans and both kernels but never hostable
     int ramp_mode_ = 1;
     RampState *ramp_d_ = nullptr;            // the device words (kernels.h)
     // INVARIANT: m_quiet_ is true exactly while the layer graph of a split feed is the LAST thing enqueued on stream_ (M).  launch_split_feed sets it
     // behind that graph; every other enqueue on M -- general_prologue() and the direct users: slot zeroing, plan / option / bias / confidence uploads, a
     // profiled fbank, the debug entry points through sync() -- clears it BEFORE it enqueues.  Only then may the previous feed's window run this
     // feed's head: the guest problems overtake nothing that M was given in between.  (atomic: aas_free resets slots from client threads)
+    // While a layer graph is deferred (below) it still holds -- the hosting chain IS the last thing on M --, and m_touched() settles the deferral first:
+    // the deferred graph goes in front of whatever the caller is about to enqueue, as it would have without the deferral.
     std::atomic<bool> m_quiet_{false};
-    void m_touched() { m_quiet_.store(false, std::memory_order_release); }
+    void m_touched() { settle_pending_layers(true, RampDefer::BY_OTHER); m_quiet_.store(false, std::memory_order_release); }
+    // Deferred enqueue (engine.cc "deferred enqueue"): a split feed offered to a chain with a latch has FE + ready kernel enqueued; its layer graph, search,
+    // record copy and flight event follow when the latch's report of its generation is read.  defer_mu_ (a leaf: taken under capture_mu_ or alone, nothing
+    // is locked under it) guards defer_, pend_ and the enqueue; defer_open_ mirrors defer_.pending() for the lock-free fast path.
+    struct PendingFeed {
+        int m = 0, T = 0, parity = 0; hipEvent_t fe_done = nullptr; StreamTrace *tr = nullptr; bool hosts = false;
+        bool closed = false, pass_bytes = false; size_t rec_base = 0, rec_pos = 0; std::vector<std::pair<size_t, size_t>> conf_spans;      // close_flight() came while pending
+    };
+    RampDefer defer_; PendingFeed pend_; std::mutex defer_mu_; std::atomic<bool> defer_open_{false};
+    unsigned long long *ramp_word_h_ = nullptr;      // the latch's report (pinned, coherent)
+    uint32_t ramp_gen_h_ = 0;                        // ready kernels launched = the device's generation once they have run
+    bool m_tail_latch_ = false;                      // the layer graph that m_quiet_ speaks of holds a latch (a hosting plan's)
+    bool settle_pending_layers(bool wait, RampDefer::Who who);      // true: nothing is pending (any more)
+    bool deferred_flight(int parity);
+    void enqueue_split_layers(const PendingFeed &f, bool headless);
+    void enqueue_flight_tail(hipStream_t tail, int parity, size_t rec_base, size_t rec_pos, const std::vector<std::pair<size_t, size_t>> &conf_spans);
     std::atomic<uint64_t> ramp_eligible_{0};
     float *xb_buf_[2] = {nullptr, nullptr}, *u_buf_[2] = {nullptr, nullptr}, *ff_buf_[2] = {nullptr, nullptr};      // per parity since guests of the other parity share a launch
     uint16_t *xb16_buf_[2] = {nullptr, nullptr}, *u16_buf_[2] = {nullptr, nullptr}, *ff16_buf_[2] = {nullptr, nullptr};
@@ -601,7 +624,7 @@ private:
     GraphCache step_graphs_{"chunk step", 256};          // {m, 0, parity}: second use, both parities
     GraphCache lm_graphs_{"layer-major chain", 32};      // {m, T, parity}: first use, this parity
     GraphCache lm_search_graphs_{"long-feed search", 64};  // {m, block length, parity}: first use, this parity
-    GraphCache sw_graphs_{"feed wavefront", 4 * 64};     // sw_key(): second use, both parities; at most four graphs per plan, so sw_plans_ is full first: emptied with it
+    GraphCache sw_graphs_{"feed wavefront", 5 * 64};     // sw_key(): second use, both parities; at most five graphs per plan, so sw_plans_ is full first: emptied with it
     size_t sw_plan_cap_ = 64;
     std::map<GraphCache::Key, SwPlan> sw_plans_;         // sw_key(m, T)
     // wavefront form of the layer-major step: its stream, events, per-launch argument blocks (pinned + device), the bookkeeping words of its search graphs

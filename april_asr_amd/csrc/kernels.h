@@ -202,7 +202,7 @@ void launch_row_z(const RowArgs *host_args, int n, const RowArgs *dev_args, hipS
 constexpr int RAMP_R = 2;
 struct RampState {
     unsigned long long ready[2];           // per parity: ramp_record(generation, m, T, hostable) of the last split feed whose front end is through
-    int head_live[2];                      // per parity: 1 = the feed's first RAMP_R macro steps run in its own layer graph, 0 = a host ran them
+    int head_live[2];                      // per parity: 1 = the feed's first RAMP_R macro steps run in its own layer graph, 0 = a host ran them (guarded forms only, see launch_ramp_latch)
     int guest_live[2][RAMP_R][RAMP_R];     // [host parity][j - 1][t]: 1 = guest problem (layer j - 1 - t, chunk t) runs in the host's window step j
     unsigned generation;                   // split feeds made ready so far (ramp_ready_kernel is its only writer)
     unsigned hosted;                       // feeds whose head a predecessor ran (ramp_latch_kernel is its only writer)
@@ -210,9 +210,12 @@ struct RampState {
 // a record: generation << 32 | m << 12 | T << 4 | hostable -- ONE 8-byte word, so a reader never sees a record half written
 constexpr int RAMP_MAX_M = 0xFFFFF, RAMP_MAX_T = 0xFF;
 // on the front-end stream, behind the front end of a split feed of parity q (never captured: `hostable` is the host's word of the moment)
-void launch_ramp_ready(RampState *rs, int q, int m, int T, int hostable, hipStream_t s);
-// on the layer stream, in front of the first window step of a hosting plan of parity p and m sessions
-void launch_ramp_latch(RampState *rs, int p, int m, hipStream_t s);
+// guard: the feed's layer graph is enqueued before the latch in front of it has run, with its head steps behind head_live[q] (APRIL_RAMP_MERGE=3 / 2):
+// the ready kernel arms the word and a hosting latch clears it.  0: the host enqueues the graph that fits the latch's report; head_live is not touched.
+void launch_ramp_ready(RampState *rs, int q, int m, int T, int hostable, int guard, hipStream_t s);
+// on the layer stream, in front of the first window step of a hosting plan of parity p and m sessions.  report: one word in pinned host
+// memory, ramp_outcome_word(generation looked for, hosted) (ramp_defer.h), stored with system scope after the device words; nobody on the device waits for a reader
+void launch_ramp_latch(RampState *rs, int p, int m, unsigned long long *report, int guard, hipStream_t s);
 
 // ---------------------------------------------------------------- greedy search on the device
 // Per-slot search state (reference AprilASRSession_i: context tensor, last_emission_time_ms, the class of the

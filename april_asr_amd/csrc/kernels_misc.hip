@@ -112,16 +112,21 @@ void launch_row_z(const RowArgs *host_args, int n, const RowArgs *dev_args, hipS
 //   hosted launches start after the latch kernel has ended: their kernel-start acquire comes after that release.  No event
 //   between F and M is involved, and none is needed.
 // - A stale record never matches: generations only grow, and the latch asks for exactly its own generation + 1.
-// - head_live[q] is set to 1 by every feed's own ready kernel, which M joins before that feed's layer graph starts; only a latch
-//   that has SEEN that very record (so: after the 1 was stored) sets it back to 0.  Both are write-through agent-scope stores.
 // - A latch that runs before the record appears does not host: the guest words are 0 and the successor's head runs in its own
 //   graph, as without the merge.  The latch looks once; nothing spins.
-// - Every later launch of M -- the window's guest problems and the successor's head steps -- reads the words the latch left
-//   (plain loads behind a kernel boundary on the same stream), so all of them see the same decision.
-__global__ __launch_bounds__(64) void ramp_ready_kernel(RampState *rs, int q, int m, int T, int hostable)
+// - The latch REPORTS what it decided -- ramp_outcome_word(generation it looked for, hosted), ramp_defer.h -- in one 8-byte
+//   system-scope store to pinned host memory, after the device words.  The host enqueues the successor's layer graph only when it
+//   has read the word of that generation: the headless graph if hosted, the one with the head steps if not (engine.cc, "deferred
+//   enqueue").  Nothing on the device reads the word or waits for the host.
+// - Guarded forms (`guard`, APRIL_RAMP_MERGE=3 / 2): the successor's graph is enqueued before the latch has run, so its head steps
+//   sit behind head_live[q]: set to 1 by the feed's own ready kernel, which M joins before that feed's layer graph starts; only a
+//   latch that has SEEN that very record (so: after the 1 was stored) sets it back to 0.  Both are write-through agent-scope stores.
+// - Every later launch of M -- the window's guest problems and, guarded, the successor's head steps -- reads the words the latch
+//   left (plain loads behind a kernel boundary on the same stream), so all of them see the same decision.
+__global__ __launch_bounds__(64) void ramp_ready_kernel(RampState *rs, int q, int m, int T, int hostable, int guard)
 {
     if (threadIdx.x != 0) return;
-    __hip_atomic_store(&rs->head_live[q], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (guard) __hip_atomic_store(&rs->head_live[q], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned g = __hip_atomic_load(&rs->generation, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
     __hip_atomic_store(&rs->generation, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -130,7 +135,7 @@ __global__ __launch_bounds__(64) void ramp_ready_kernel(RampState *rs, int q, in
     __hip_atomic_store(&rs->ready[q], rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ __launch_bounds__(64) void ramp_latch_kernel(RampState *rs, int p, int m)
+__global__ __launch_bounds__(64) void ramp_latch_kernel(RampState *rs, int p, int m, unsigned long long *report, int guard)
 {
     if (threadIdx.x != 0) return;
     const unsigned long long mine = __hip_atomic_load(&rs->ready[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -140,20 +145,21 @@ __global__ __launch_bounds__(64) void ramp_latch_kernel(RampState *rs, int p, in
     const bool host = (unsigned)(next >> 32) == g + 1u && next_m == m && (int)((mine >> 12) & RAMP_MAX_M) == m && (next & 1ull) != 0;
     if (host) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        __hip_atomic_store(&rs->head_live[1 - p], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (guard) __hip_atomic_store(&rs->head_live[1 - p], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         rs->hosted += 1u;
     }
     for (int j = 1; j <= RAMP_R; ++j)
         for (int t = 0; t < RAMP_R; ++t) rs->guest_live[p][j - 1][t] = (host && t < j && t < next_T) ? 1 : 0;
+    if (report) __hip_atomic_store(report, ((unsigned long long)(g + 1u) << 32) | (host ? 1ull : 0ull), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-void launch_ramp_ready(RampState *rs, int q, int m, int T, int hostable, hipStream_t s)
+void launch_ramp_ready(RampState *rs, int q, int m, int T, int hostable, int guard, hipStream_t s)
 {
-    hipLaunchKernelGGL(ramp_ready_kernel, dim3(1), dim3(64), 0, s, rs, q, m, T, hostable);
+    hipLaunchKernelGGL(ramp_ready_kernel, dim3(1), dim3(64), 0, s, rs, q, m, T, hostable, guard);
 }
-void launch_ramp_latch(RampState *rs, int p, int m, hipStream_t s)
+void launch_ramp_latch(RampState *rs, int p, int m, unsigned long long *report, int guard, hipStream_t s)
 {
-    hipLaunchKernelGGL(ramp_latch_kernel, dim3(1), dim3(64), 0, s, rs, p, m);
+    hipLaunchKernelGGL(ramp_latch_kernel, dim3(1), dim3(64), 0, s, rs, p, m, report, guard);
 }
 
 // ---------------------------------------------------------------- decoder front end (device function)

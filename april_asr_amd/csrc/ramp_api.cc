@@ -32,5 +32,12 @@ int aprilx_model_ramp_stats(AprilASRModel model, int device_index, uint64_t *ram
     model->m.engines[(size_t)device_index]->ramp_counts(ramp_hosted, ramp_eligible);
     return 0;
 }
+int aprilx_model_ramp_stats2(AprilASRModel model, int device_index, uint64_t out[5])
+{
+    if (!model || device_index < 0 || device_index >= (int)model->m.engines.size() || !out) return -1;
+    model->m.engines[(size_t)device_index]->ramp_counts(&out[0], &out[1]);
+    model->m.engines[(size_t)device_index]->ramp_defer_counts(&out[2], &out[3], &out[4]);
+    return 0;
+}
 
 }  // extern "C"

@@ -656,6 +656,11 @@ APRIL_EXPORT void aprilx_model_stats(AprilASRModel model, int device_index, Apri
  * feed's last two (counted on the device by the kernel that decides it; exact once the streams are idle).  Returns 0, -1 on bad
  * arguments.  (Not part of AprilxStats: that struct's layout is pinned.) */
 APRIL_EXPORT int aprilx_model_ramp_stats(AprilASRModel model, int device_index, uint64_t *ramp_hosted, uint64_t *ramp_eligible);
+/* The same two counters and those of the deferred enqueue (APRIL_RAMP_MERGE=1), out[0..4]: hosted, eligible (there: feeds
+ * whose layer graph waited for the latch's report), headless layer graphs launched (= hosted once the streams are idle), deferrals settled by
+ * the stepping thread's wait for a flight (wait_flight / flight_done), deferrals settled by any other engine entry (the launch itself when the
+ * report was already there, a slot reset, an upload, the next flight).  Returns 0, -1 on bad arguments. */
+APRIL_EXPORT int aprilx_model_ramp_stats2(AprilASRModel model, int device_index, uint64_t out[5]);
 /* Hand-over -> delivery latency of the last (up to 8192) completed ticks of one GPU's stepping thread, in ms, oldest first: from the
  * feed call (aas_feed_pcm16 / aprilx_feed_many / aprilx_feed_many_pipelined / flush) that queued the oldest work a flight served to
  * the moment that flight's results were delivered (asynchronous and pipelined sessions: their handlers have run; synchronous callers:
