@@ -24,6 +24,8 @@
 // Replaces the MatMul nodes of the encoder graph (reference call site src/april_session.c:131-148).
 #include "kernels.h"
 #include "device_utils.h"
+#include "env.h"
+#include "gemm_kw_asm.inc"
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -56,7 +58,11 @@ template <int MT, int NT> struct KwGeom {
     static constexpr int LX = NPIECE, LY = 2 * NT, GSZ = LX + LY;         // memory operations per stage: {DMA pieces}, {B of k blocks 0, 1}
 };
 
-template <int MT, int NT, int EPI, int CPW>
+// HAND: the K loop is the hand-placed instruction stream of gemm_kw_asm.inc (tools/gen_kw_asm.py) instead of the compiler-scheduled
+// stages below -- same memory operations in the same order, same chains, same fold; APRIL_KW_ASM=0 selects the compiler's loop (A/B)
+template <int MT, int NT> constexpr bool kw_has_hand(int cpw) { return NT == 2 && (MT == 1 || MT == 2) && cpw == 4; }
+
+template <int MT, int NT, int EPI, int CPW, bool HAND>
 __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, const int by, const unsigned wg_linear)
 {
     using G = KwGeom<MT, NT>;
@@ -64,6 +70,7 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
     constexpr bool ROW_EPI = EPI == EPI_HR || EPI == EPI_RESID_SSQ;
     static_assert(ROW_EPI, "no GM_KW form of this epilogue");
     static_assert(CPW == 1 || CPW == 4, "a wave owns one chunk or one slab");
+    static_assert(!HAND || kw_has_hand<MT, NT>(CPW), "no hand-placed loop for this form");
     constexpr bool DB1 = MT * NT >= 16;                    // 64 x 64 wave tiles: the register-lean form of the K loop (below)
     extern __shared__ __attribute__((aligned(1024))) float red[];
     char *lds = reinterpret_cast<char *>(red);
@@ -71,6 +78,12 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
     if (g.run_flag && gload<int>(g.run_flag) != g.run_gen) return;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+#ifdef APRIL_KW_ABLATE
+    // measurement only (tools/kw_bench_ablate, APRIL_GEMM_DEBUG): 3 .. 9 as at their uses below; 10 / 11 = 6 / 7 without the fold
+    // (profiles/kw_loop_ablation.txt: what the loop costs without its global-memory instructions, term by term)
+    const bool abl_nofold = g.debug == 10 || g.debug == 11;
+    const int abl = g.debug == 10 ? 6 : g.debug == 11 ? 7 : g.debug;
+#endif
     // measurement only (tools/kw_bench built with -DAPRIL_GEMM_TRACE): s_memtime stamps of wave 0 at the phase boundaries
 #ifdef APRIL_GEMM_TRACE
     auto stamp = [&](int i) { if (g.trace && wave == 0) g.trace[(size_t)wg_linear * 16 + i] = __builtin_amdgcn_s_memtime(); };
@@ -137,7 +150,7 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
     char *my = lds + wave * G::WAVE_BYTES;
     auto issue_dma = [&](int slot) {
 #ifdef APRIL_KW_ABLATE
-        if (g.debug == 4 || g.debug == 6 || g.debug == 7 || g.debug == 9) return;      // measurement: no DMA (stale LDS contents)
+        if (abl == 4 || abl == 6 || abl == 7 || abl == 9) return;      // measurement: no DMA (stale LDS contents)
 #endif
 #pragma unroll
         for (int i = 0; i < G::NPIECE; ++i) {
@@ -165,7 +178,7 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
 #endif
     auto load_b = [&](f32x4 (&b)[NT]) {
 #ifdef APRIL_KW_ABLATE
-        if (g.debug == 6 || g.debug == 7 || g.debug == 8) {      // measurement: no weight loads (the registers stay defined for the compiler)
+        if (abl == 6 || abl == 7 || abl == 8) {      // measurement: no weight loads (the registers stay defined for the compiler)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) asm volatile("" : "+v"(b[nt]));
             return;
@@ -210,7 +223,7 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
     for (int p = 0; p < 2; ++p) a_rd[p] = mrow * 128 + (((p * 4 + kq) ^ ((mrow >> 1) & 7)) << 4);
     auto read_frags = [&](int slot, int p, f32x4 (&a)[MT]) {
 #ifdef APRIL_KW_ABLATE
-        if (g.debug == 6) {
+        if (abl == 6) {
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) asm volatile("" : "+v"(a[mt]));
             return;
@@ -225,6 +238,9 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
     APRIL_KW_EACH(acc[mt][nt] = (f32x4{0.f, 0.f, 0.f, 0.f}))
     int chunk_i = 0, in_chunk = 0;
     auto fold = [&]() {                                   // a chunk chain is complete (CPW == 4: S = ((c0 + c1) + c2) + c3)
+#ifdef APRIL_KW_ABLATE
+        if (abl_nofold) return;
+#endif
         if constexpr (CPW == 4) {
             // one accumulator tile at a time (pinned): left alone, the scheduler computes all sums into fresh registers first, which at 64 x 64
             // per wave (64 + 64 registers) overflows the file
@@ -316,6 +332,28 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
                 }
                 if (more_b) load_b(bo[0]);
                 if constexpr (CPW == 4) { if (++in_chunk == cs) { in_chunk = 0; fold(); } }
+            }
+        }
+    } else if constexpr (HAND) {
+        // the whole loop, its priming loads and the folds in one statement: S comes back in the fixed registers of the generator's plan.
+        // Operands: the lanes' byte offsets (DMA pieces, weights, fragment reads with the wave's LDS base added), the wave's uniform bases
+        if (g.debug != 1) {
+            stamp(1);
+            const uint32_t lds_my = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)my);
+            const uint32_t rd0 = lds_my + (uint32_t)a_rd[0], rd1 = lds_my + (uint32_t)a_rd[1];
+            const char *bp1 = bp + bstride;
+            if constexpr (MT == 2) {
+                asm volatile(APRIL_KWLOOP_M2_TEXT
+                             : APRIL_KWLOOP_M2_S0(S[0][0]), APRIL_KWLOOP_M2_S1(S[0][1]), APRIL_KWLOOP_M2_S2(S[1][0]), APRIL_KWLOOP_M2_S3(S[1][1])
+                             : [ao0] "v"(aoff[0]), [ao1] "v"(aoff[1]), [ao2] "v"(aoff[2]), [ao3] "v"(aoff[3]), [bo] "v"(boff), [rd0] "v"(rd0), [rd1] "v"(rd1),
+                               [ap] "s"(abase), [bp0] "s"(bp), [bp1] "s"(bp1), [lds] "s"(lds_my), [nst] "s"(nstage), [cs] "s"(cs)
+                             : APRIL_KWLOOP_M2_CLOBBERS);
+            } else {
+                asm volatile(APRIL_KWLOOP_M1_TEXT
+                             : APRIL_KWLOOP_M1_S0(S[0][0]), APRIL_KWLOOP_M1_S1(S[0][1])
+                             : [ao0] "v"(aoff[0]), [ao1] "v"(aoff[1]), [bo] "v"(boff), [rd0] "v"(rd0), [rd1] "v"(rd1),
+                               [ap] "s"(abase), [bp0] "s"(bp), [bp1] "s"(bp1), [lds] "s"(lds_my), [nst] "s"(nstage), [cs] "s"(cs)
+                             : APRIL_KWLOOP_M1_CLOBBERS);
             }
         }
     } else
@@ -431,27 +469,32 @@ __device__ __forceinline__ void gemm_kw_body(const GemmArgs &g, const int bx, co
 #undef APRIL_KW_EACH
 }
 
-template <int MT, int NT, int EPI, int CPW>
+template <int MT, int NT, int EPI, int CPW, bool HAND>
 __global__ __launch_bounds__(64 * NW, (MT == 1 && EPI == EPI_HR) ? 6 : 2) void gemm_kw_kernel(GemmArgs g)
 {
-    gemm_kw_body<MT, NT, EPI, CPW>(g, (int)blockIdx.x, (int)blockIdx.y, blockIdx.x + gridDim.x * blockIdx.y);
+    gemm_kw_body<MT, NT, EPI, CPW, HAND>(g, (int)blockIdx.x, (int)blockIdx.y, blockIdx.x + gridDim.x * blockIdx.y);
 }
 
 // n independent same-shape problems in one launch (see gemm_f32_zkernel): blockIdx.z picks the argument block
-template <int MT, int NT, int EPI, int CPW>
+template <int MT, int NT, int EPI, int CPW, bool HAND>
 __global__ __launch_bounds__(64 * NW, (MT == 1 && EPI == EPI_HR) ? 6 : 2) void gemm_kw_zkernel(const GemmArgs *__restrict__ zargs)
 {
     const GemmArgs g = zargs[blockIdx.z];
-    gemm_kw_body<MT, NT, EPI, CPW>(g, (int)blockIdx.x, (int)blockIdx.y, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+    gemm_kw_body<MT, NT, EPI, CPW, HAND>(g, (int)blockIdx.x, (int)blockIdx.y, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
 }
 
 template <int MT, int NT, int EPI, int CPW>
 void launch_kw_one(const GemmArgs &g, const GemmArgs *dev_args, int n, hipStream_t s)
 {
     using G = KwGeom<MT, NT>;
+    static const int hand = env_int("APRIL_KW_ASM", 1);      // 0 = the compiler-scheduled K loop everywhere (A/B)
     dim3 grid((unsigned)(g.N / G::BN), (unsigned)((g.M + G::BM - 1) / G::BM), (unsigned)std::max(1, n));
     const size_t lds = (size_t)G::LDS_MAIN + scale_lds_floats(g, G::BM) * sizeof(float);
-    launch_gemm_pair<&gemm_kw_kernel<MT, NT, EPI, CPW>, &gemm_kw_zkernel<MT, NT, EPI, CPW>>(grid, dim3(G::NTH), lds, true, s, g, dev_args);
+    if constexpr (kw_has_hand<MT, NT>(CPW)) if (hand && g.debug == 0) {
+        launch_gemm_pair<&gemm_kw_kernel<MT, NT, EPI, CPW, true>, &gemm_kw_zkernel<MT, NT, EPI, CPW, true>>(grid, dim3(G::NTH), lds, true, s, g, dev_args);
+        return;
+    }
+    launch_gemm_pair<&gemm_kw_kernel<MT, NT, EPI, CPW, false>, &gemm_kw_zkernel<MT, NT, EPI, CPW, false>>(grid, dim3(G::NTH), lds, true, s, g, dev_args);
 }
 
 // (every GEMM gemm_kw_waves accepts has one of these: EPI_HR / EPI_RESID_SSQ, kz 8 / 2 = 4 / 1 chunks per wave)

@@ -1,6 +1,7 @@
 #!/bin/bash
-# builds tools/kw_bench (product objects) and tools/kw_bench_trace (kernels_gemm_kw.hip with -DAPRIL_GEMM_TRACE: s_memtime stamps + the
-# measurement-only debug modes) from the repository root
+# builds tools/kw_bench (product objects), tools/kw_bench_trace (kernels_gemm_kw.hip with -DAPRIL_GEMM_TRACE: s_memtime stamps) and
+# tools/kw_bench_ablate (the same with -DAPRIL_KW_ABLATE: the measurement-only forms APRIL_GEMM_DEBUG=3..11 of the compiler-scheduled
+# K loop) from the repository root
 set -e
 cd "$(dirname "$0")/.."
 C=april_asr_amd/csrc
@@ -13,4 +14,6 @@ OBJS="$C/build/kernels_gemm.o $C/build/kernels_gemm_tile.o $C/build/kernels_gemm
 $HIPCC --offload-arch=gfx950 $T/kw_bench.o $OBJS $C/build/kernels_gemm_kw.o -o tools/kw_bench
 $HIPCC -O3 --offload-arch=gfx950 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -DAPRIL_GEMM_TRACE -I$C -c $C/kernels_gemm_kw.hip -o $T/kw_trace.o
 $HIPCC --offload-arch=gfx950 $T/kw_bench.o $OBJS $T/kw_trace.o -o tools/kw_bench_trace
+$HIPCC -O3 --offload-arch=gfx950 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -DAPRIL_GEMM_TRACE -DAPRIL_KW_ABLATE -I$C -c $C/kernels_gemm_kw.hip -o $T/kw_ablate.o
+$HIPCC --offload-arch=gfx950 $T/kw_bench.o $OBJS $T/kw_ablate.o -o tools/kw_bench_ablate
 echo built
