@@ -155,7 +155,7 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_model_dims", "aprilx_model_token", "aprilx_model_blob_size", "aprilx_model_export_blob",
     "aprilx_model_from_blob", "aprilx_model_save_blob", "aprilx_model_save_blob_f16", "aprilx_model_load_blob",
     "aprilx_broadcast_get_id", "aprilx_model_broadcast", "aprilx_model_load_info", "aprilx_feed_many", "aprilx_flush_many", "aprilx_session_drain", "aprilx_feed_many_pipelined", "aprilx_drain_many",
-    "aprilx_run_encoder", "aprilx_run_decoder", "aprilx_run_joiner", "aprilx_run_fbank", "aprilx_run_decide", "aprilx_plan_gemm", "aprilx_gemm_plan_debug", "aprilx_run_gemm", "aprilx_stream_form",
+    "aprilx_run_encoder", "aprilx_run_decoder", "aprilx_run_joiner", "aprilx_run_fbank", "aprilx_run_decide", "aprilx_plan_gemm", "aprilx_gemm_plan_debug", "aprilx_run_gemm", "aprilx_stream_form", "aprilx_run_conv_front", "aprilx_conv_front_geometry",
     "aprilx_session_trace_logits", "aprilx_session_chunks", "aprilx_session_read_frames", "aprilx_session_context", "aprilx_model_stats", "aprilx_model_profile", "aprilx_model_feed_latency",
     "aprilx_greedy_create", "aprilx_greedy_step", "aprilx_greedy_finish", "aprilx_greedy_free", "aprilx_probe_file", "aprilx_model_load_host", "aprilx_model_fbank_tables", "aprilx_counting_handler",
     "aprilx_session_set_input_rate", "aprilx_session_input_rate", "aprilx_resampler_taps", "aprilx_resample",
@@ -226,6 +226,8 @@ def lib():
     L.aprilx_plan_gemm.argtypes = [C.c_int] * 6 + [vp]; L.aprilx_plan_gemm.restype = C.c_int
     L.aprilx_gemm_plan_debug.argtypes = [vp, vp]; L.aprilx_gemm_plan_debug.restype = C.c_int
     L.aprilx_run_gemm.argtypes = [vp] * 5; L.aprilx_run_gemm.restype = C.c_int
+    L.aprilx_run_conv_front.argtypes = [vp] * 4; L.aprilx_run_conv_front.restype = C.c_int
+    L.aprilx_conv_front_geometry.argtypes = [vp] * 2; L.aprilx_conv_front_geometry.restype = C.c_int
     L.aprilx_ramp_window.argtypes = [C.c_int] * 3 + [vp, C.c_int]; L.aprilx_ramp_window.restype = C.c_int
     L.aprilx_model_ramp_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]; L.aprilx_model_ramp_stats.restype = C.c_int
     L.aprilx_model_ramp_stats2.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64)]; L.aprilx_model_ramp_stats2.restype = C.c_int

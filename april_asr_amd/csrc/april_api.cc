@@ -277,13 +277,18 @@ bool parse_meta(const char *p, size_t n, Model &m)
     for (size_t t = 0; t < (size_t)P.token_count; ++t) P.tokens[(t + 1) * P.token_stride - 1] = 0;    // token text is NUL-terminated within its slot
     auto in = [](long v, long lo, long hi) { return v >= lo && v <= hi; };
     if (!in(d.d_model, 16, 1 << 16) || !in(d.hidden, 16, 1 << 16) || !in(d.ffn, 16, 1 << 18) || !in(d.joiner, 16, 1 << 16) ||
-        !in(d.vocab, 2, 1 << 20) || d.vocab != P.token_count || !in(d.mel, 8, 1024) || !in(d.seg, 3, 64) || d.context != 2 ||
+        !in(d.vocab, 2, 1 << 20) || d.vocab != P.token_count || !in(d.mel, 1, 255) || !in(d.seg, 3, 64) || d.context != 2 ||
         !in(d.dec_groups, 1, d.d_model) || d.d_model % d.dec_groups != 0 || !in(d.f_out, 1, 4096) || !in(d.embed_in, 16, 1 << 22) ||
         !in(d.conv_ch[0], 1, 4096) || !in(d.conv_ch[1], 1, 4096) || !in(d.conv_ch[2], 1, 4096) ||
         d.seg != P.segment_size || d.mel != P.mel_features ||                      // the network input is the PARAMS chunk (april_model.c:65-72)
         !in(d.conv_stride[0], 1, 8) || !in(d.conv_stride[1], 1, 8) || !in(d.conv_stride[2], 1, 8) ||
         d.embed_in != d.conv_ch[2] * d.f_out || !in(d.d_norm, 0, d.d_model))
         return false;
+    {   // the conv front end's own limits, as the file loader applies them (conv_front.h)
+        std::string why;
+        if (!conv_front_ok(d, why)) { LOGE("aprilx: blob %s", why.c_str()); return false; }
+        if (d.f_out != conv_front_geom(d).W3) { LOGE("aprilx: blob f_out %d does not follow from the conv stack", d.f_out); return false; }
+    }
     plan_layout(d, hb, m.layout);
     m.layout.embed_eps = r.val<float>();
     m.layout.norm_eps.resize((size_t)d.n_layers);

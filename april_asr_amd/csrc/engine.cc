@@ -1074,8 +1074,7 @@ void Engine::encoder_front(size_t r0, int rows, const int *row_slots, const floa
     ca.ring = ring_; ca.ring_frames = ring_frames_; ca.mel = d.mel; ca.seg = d.seg;
     ca.slot_idx = row_slots + r0; ca.ring_tail = step_d_ + cfg_.max_batch + r0; ca.x_direct = x_direct;
     for (int i = 0; i < 3; ++i) { ca.w[i] = w_ + L_.conv_w[i]; ca.b[i] = w_ + L_.conv_b[i]; ca.ch[i] = d.conv_ch[i]; ca.stride[i] = d.conv_stride[i]; }
-    ca.ch1_per_group = 1;                                 // largest divisor of the second conv's channel count that is <= 8
-    for (int k = 8; k > 1; --k) if (d.conv_ch[1] % k == 0) { ca.ch1_per_group = k; break; }
+    ca.ch1_per_group = conv_ch1_per_group(d.conv_ch[1]);
     ca.out = a3_ + r0 * d.f_out * L_.k3; ca.ldo = L_.k3; ca.M = rows;
     if (conv_wt_) { ca.w0t = conv_wt_; ca.w1t = conv_wt_ + (size_t)9 * d.conv_ch[0]; }
     timed_begin(T_CONV); launch_conv_embed(ca, st); timed_end(T_CONV);

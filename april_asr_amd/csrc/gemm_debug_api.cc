@@ -9,6 +9,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "rowepi_forms.h"
+#include "debug_arena.h"
 
 using namespace aprilx;
 
@@ -20,30 +21,6 @@ enum { D_N, D_M, D_NC, D_K, D_K0, D_K1, D_KZ, D_EPI, D_AOP, D_WT, D_WAVES, D_TIL
 enum { I_A0, I_A1, I_A0B, I_AIDX0, I_AIDX1, I_AIDX0B, I_SLOT, I_MASK, I_CTX, I_BIAS, I_RESID, I_PADD, I_XSSQ, I_RSSQ, I_CSTATE, I_RESERVED, I_W, N_IN };
 enum { O_OUT, O_OUT16, O_STATE, O_STATE16, O_CSTATE, O_SSQ, O_PLANES, N_OUT };
 constexpr int MAX_PLANES = 8;
-
-// device allocations of one call, freed together; `bad` latches the first failing HIP call
-struct Arena {
-    std::vector<void *> ptrs;
-    bool bad = false;
-    bool ok(hipError_t e) { if (e != hipSuccess) { if (!bad) LOGE("aprilx_run_gemm: HIP: %s", hipGetErrorString(e)); bad = true; } return !bad; }
-    void *raw(size_t bytes, int fill)
-    {
-        void *p = nullptr;
-        if (bad || !ok(hipMalloc(&p, bytes ? bytes : 4))) return nullptr;
-        ptrs.push_back(p);
-        ok(hipMemset(p, fill, bytes ? bytes : 4));
-        return p;
-    }
-    // `bytes` of device memory: the first `have` from the host array, the rest zero
-    void *upload(const void *host, size_t have, size_t bytes)
-    {
-        void *p = raw(bytes < have ? have : bytes, 0);
-        if (p && have) ok(hipMemcpy(p, host, have, hipMemcpyHostToDevice));
-        return p;
-    }
-    void download(void *host, const void *dev, size_t bytes) { if (host && dev && !bad) ok(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost)); }
-    ~Arena() { for (void *p : ptrs) (void)hipFree(p); }
-};
 
 struct Problem {
     GemmArgs g;
@@ -64,7 +41,7 @@ extern "C" int aprilx_run_gemm(const int32_t *d, const float *fd, const void *co
     const bool row_epi = epi == EPI_HR || epi == EPI_RESID_SSQ || epi == EPI_SLOT_STORE;
     const bool f16 = d[D_WT] == 1, f16_rows = f16 && d[D_TILE_OK] == 2;      // binary16 activation rows: the fp16 tile engines' forms
 
-    Arena A;
+    Arena A("aprilx_run_gemm");
     hipStream_t st = nullptr;
     int *run_flag = nullptr;
     if (d[D_RUN_FLAG] >= 0) { const int v = d[D_RUN_FLAG]; run_flag = (int *)A.upload(&v, sizeof v, sizeof v); }

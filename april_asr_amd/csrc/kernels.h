@@ -12,6 +12,7 @@
 #include "dtmf.h"
 #include "tone.h"
 #include "gemm_plan.h"
+#include "conv_front.h"
 
 namespace aprilx {
 
@@ -406,6 +407,9 @@ struct ConvEmbedArgs {
     const float *w0t = nullptr, *w1t = nullptr;      // optional: the first two convs' weights transposed (launch_conv_weight_transpose): [9][ch0], [ch0 * 9][ch1] -- the many-chunk form needs them
 };
 void launch_conv_embed(const ConvEmbedArgs &a, hipStream_t s);
+// which form launch_conv_embed runs: 1 = the many-chunk form (one workgroup per chunk, all channels), 0 = the grouped form.  The
+// second conv's channels per workgroup of the grouped form are conv_ch1_per_group (conv_front.h) of ch[1].
+int conv_embed_form(const ConvEmbedArgs &a);
 void launch_conv_weight_transpose(const float *w0, const float *w1, int c0, int c1, float *w0t, float *w1t, hipStream_t s);
 
 // fp32 -> fp16 (round to nearest even), elementwise; used once at load for the fp16 weight copies

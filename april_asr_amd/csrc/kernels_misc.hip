@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <type_traits>
 
 namespace aprilx {
@@ -693,32 +694,36 @@ void launch_conv_weight_transpose(const float *w0, const float *w1, int c0, int 
 
 // the wide form where it exists, from APRIL_CONV_WIDE_MIN (default 48; -1 = never) chunks per launch (below that the channel groups of
 // conv12_kernel are what fills the chip)
-static bool conv_wide_ok(const ConvEmbedArgs &a)
+static size_t conv_wide_lds(const ConvEmbedArgs &a, const ConvFrontGeom &g)
+{
+    return sizeof(float) * ((size_t)pad4(a.seg * a.mel) + pad4(a.ch[0] * g.H1 * g.W1) + pad4(a.ch[1] * g.NP));
+}
+int conv_embed_form(const ConvEmbedArgs &a)
 {
     static const int min_chunks = env_int("APRIL_CONV_WIDE_MIN", 48);
-    if (min_chunks < 0 || a.M < min_chunks || !a.w1t || !a.w0t) return false;
-    const int H1 = (a.seg - 3) / a.stride[0] + 1, W1 = (a.mel - 3) / a.stride[0] + 1;
-    const int H2 = (H1 - 3) / a.stride[1] + 1, W2 = (W1 - 3) / a.stride[1] + 1;
-    const int NP = H2 * W2;
-    const size_t lds = sizeof(float) * ((size_t)pad4(a.seg * a.mel) + pad4(a.ch[0] * H1 * W1) + pad4(a.ch[1] * NP));
+    if (min_chunks < 0 || a.M < min_chunks || !a.w1t || !a.w0t) return 0;
+    const ConvFrontGeom g = conv_front_geom(a.seg, a.mel, a.stride, a.ch[0], a.ch[1]);
     // the instantiated shape: 8 -> 32 channels, the second conv's positions in two waves (aprilv0 and the larger encoder: 80 mel bins, 9 frames)
-    return H2 == 3 && a.ch[0] == 8 && a.ch[1] == 32 && NP > 64 && NP <= 128 && a.seg <= a.ring_frames && a.ldo % 4 == 0 && a.seg * a.mel >= a.ch[1] * 9 && lds <= 64 * 1024;
+    return g.valid && g.H2 == 3 && a.ch[0] == 8 && a.ch[1] == 32 && g.NP > 64 && g.NP <= 128 && a.seg <= a.ring_frames && a.ldo % 4 == 0 &&
+           a.seg * a.mel >= a.ch[1] * 9 && conv_wide_lds(a, g) <= CONV_FRONT_LDS_LIMIT;
 }
 
 void launch_conv_embed(const ConvEmbedArgs &a, hipStream_t s)
 {
-    if (conv_wide_ok(a)) {
-        const int H1 = (a.seg - 3) / a.stride[0] + 1, W1 = (a.mel - 3) / a.stride[0] + 1;
-        const int H2 = (H1 - 3) / a.stride[1] + 1, W2 = (W1 - 3) / a.stride[1] + 1;
-        const size_t lds = sizeof(float) * ((size_t)pad4(a.seg * a.mel) + pad4(a.ch[0] * H1 * W1) + pad4(a.ch[1] * H2 * W2));
-        hipLaunchKernelGGL((conv12_wide_kernel<8, 32, 2>), dim3((unsigned)a.M), dim3(256), lds, s, a);
+    // (the loader and the blob import refuse such a network with the same words: conv_front.h)
+    const ConvFrontGeom g = conv_front_geom(a.seg, a.mel, a.stride, a.ch[0], a.ch[1]);
+    if (!g.valid || g.lds_bytes > CONV_FRONT_LDS_LIMIT) {
+        std::string why;
+        conv_front_ok(a.seg, a.mel, a.stride, a.ch[0], a.ch[1], why);
+        fprintf(stderr, "libapril(mi355x): %s\n", why.c_str());
+        abort();
+    }
+    if (conv_embed_form(a)) {
+        hipLaunchKernelGGL((conv12_wide_kernel<8, 32, 2>), dim3((unsigned)a.M), dim3(256), conv_wide_lds(a, g), s, a);
         return;
     }
-    const int H1 = (a.seg - 3) / a.stride[0] + 1, W1 = (a.mel - 3) / a.stride[0] + 1;
-    const int H2 = (H1 - 3) / a.stride[1] + 1, W2 = (W1 - 3) / a.stride[1] + 1;
-    const size_t lds = sizeof(float) * ((size_t)a.seg * a.mel + (size_t)a.ch[0] * H1 * W1 + (size_t)a.ch1_per_group * H2 * W2);
-    if (a.ch1_per_group > 8 || a.ch[1] % a.ch1_per_group) { fprintf(stderr, "libapril(mi355x): conv front end: channels per workgroup must divide the second conv and be <= 8\n"); abort(); }
-    hipLaunchKernelGGL(conv12_kernel, dim3((unsigned)a.M, (unsigned)(a.ch[1] / a.ch1_per_group)), dim3(256), lds, s, a);
+    if (a.ch1_per_group != g.cg) { fprintf(stderr, "libapril(mi355x): conv front end: channels per workgroup must be conv_ch1_per_group of the second conv\n"); abort(); }
+    hipLaunchKernelGGL(conv12_kernel, dim3((unsigned)a.M, (unsigned)(a.ch[1] / g.cg)), dim3(256), g.lds_bytes, s, a);
 }
 
 // ---------------------------------------------------------------- fp16 weight copies

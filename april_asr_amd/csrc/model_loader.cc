@@ -18,6 +18,7 @@
 // constants as initializers / Constant nodes / behind Identity, Cast, Transpose, and
 // Identity / Cast / Dropout nodes anywhere on the activation path.
 #include "model_loader.h"
+#include "conv_front.h"
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -477,6 +478,10 @@ bool extract_encoder(const OGraph &g, const ModelParams &P, HostModel &M, std::s
         if (!v.double_swish(n.out[0], cur)) return fail(err, "encoder embed: " + v.err);
     }
     if (H != 1) return fail(err, "embed stack must reduce the segment to one frame (got " + std::to_string(H) + ")");
+    {   // what the front-end kernels can run (conv_front.h): refused here, with the geometry, not at the first feed
+        std::string why;
+        if (!conv_front_ok(D, why)) return fail(err, "encoder: " + why);
+    }
     D.f_out = W; D.embed_in = C * W;
 
     Linear lin;

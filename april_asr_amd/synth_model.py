@@ -168,6 +168,13 @@ LARGE_DIMS = dict(n_layers=16, d_model=768, hidden=1536, ffn=3072, joiner=768, v
                   context=2, dec_groups=192, conv_ch=(8, 32, 128))
 
 
+def conv_out_size(n, dims):
+    """Rows or columns left of n after the three 3 x 3 convolutions (no padding) at dims["conv_strides"], default (1, 2, 2)."""
+    for st in dims.get("conv_strides", (1, 2, 2)):
+        n = (n - 3) // st + 1
+    return n
+
+
 def _uniform(rng, shape, fan_in, gain=1.0):
     b = gain / np.sqrt(float(fan_in))
     return rng.uniform(-b, b, size=shape).astype(np.float32)
@@ -178,8 +185,7 @@ def make_weights(dims, seed=2023, joiner_gain=6.0, blank_bias=4.7, blank_id=0):
     rng = np.random.RandomState(seed)
     d, H, F, J, V = dims["d_model"], dims["hidden"], dims["ffn"], dims["joiner"], dims["vocab"]
     c1, c2, c3 = dims["conv_ch"]
-    mel = dims["mel"]
-    f_out = ((mel - 3) // 2 - 1) // 2
+    f_out = conv_out_size(dims["mel"], dims)
     w = {}
     w["conv0.w"] = _uniform(rng, (c1, 1, 3, 3), 9);          w["conv0.b"] = _uniform(rng, (c1,), 9)
     w["conv1.w"] = _uniform(rng, (c2, c1, 3, 3), c1 * 9);    w["conv1.b"] = _uniform(rng, (c2,), c1 * 9)
@@ -294,14 +300,14 @@ def build_encoder(dims, w, variant):
                  value_info("next_c", FLOAT, (L, 1, H))]
     fold = variant.get("fold_eps", True)
     t = g.node("Unsqueeze", ["x"], axes=[1])
-    for i, stride in enumerate((1, 2, 2)):
+    for i, stride in enumerate(dims.get("conv_strides", (1, 2, 2))):
         attrs = dict(dilations=[1, 1], group=1, kernel_shape=[3, 3], pads=[0, 0, 0, 0], strides=[stride, stride])
         cw = g.const(w["conv%d.w" % i]) if _V.get("const_nodes") else g.init("encoder.encoder_embed.conv.%d.weight" % (3 * i), w["conv%d.w" % i])
         t = g.node("Conv", [t, cw, _small(g, "encoder.encoder_embed.conv.%d.bias" % (3 * i), w["conv%d.b" % i])], **attrs)
         t = _double_swish(g, _pt(g, t))
     c3 = dims["conv_ch"][2]
-    f_out = ((mel - 3) // 2 - 1) // 2
-    t_out = ((T - 3) // 2 - 1) // 2
+    f_out = conv_out_size(mel, dims)
+    t_out = conv_out_size(T, dims)
     t = g.node("Transpose", [t], perm=[0, 2, 1, 3])
     t = g.node("Reshape", [t, g.const(np.array([1, t_out, c3 * f_out], np.int64))])
     t = _linear3d(g, t, w["embed.w"], w["embed.b"], "encoder.encoder_embed.out")

@@ -143,6 +143,24 @@ APRIL_EXPORT int aprilx_gemm_plan_debug(const int32_t *in, int32_t *out);
  * Returns 0; -1 bad arguments; -2 a HIP call failed; -3 the plan carries an error (nothing launched). */
 APRIL_EXPORT int aprilx_run_gemm(const int32_t *desc, const float *fdesc, const void *const *in, void *const *out, int32_t *plan_out);
 
+/* ONE launch of the conv front end (csrc/kernels_misc.hip: conv 1 + 2 with DoubleSwish, then the im2col rows of conv 3) against host
+ * arrays, the way the engine launches it (csrc/conv_debug_api.cc; needs a GPU, no model; tests only: tests/conv_ref.py states the
+ * mathematics it is compared with).  The weights are transposed on the device first (launch_conv_weight_transpose), as at load.
+ * desc[16], int32: 0 segment rows, 1 mel bins, 2..4 the three strides, 5 channels of conv 1, 6 channels of conv 2, 7 M (chunks),
+ *   8 ldo (>= 9 x channels of conv 2), 9 rows of the output array (>= M x W3), 10 slots of the ring (0: x is given chunk by chunk),
+ *   11 ring_frames (>= segment rows; also with slots == 0, where the engine has a ring all the same); the rest 0.
+ * in[8], host pointers: 0 w0 [c0][9], 1 b0 [c0], 2 w1 [c1][c0][9], 3 b1 [c1], 4 x [M][seg][mel] (slots == 0), 5 ring
+ *   [slots][ring_frames][mel], 6 slot_idx [M] (each < slots), 7 ring_tail [M] (each < ring_frames).
+ * out[3], host pointers: 0 out [rows][ldo], filled with 0xFF bytes before the launch, 1 w0t [9][c0] or NULL, 2 w1t [c0 x 9][c1] or NULL.
+ * info[12]: H1 W1 H2 W2 W3 (rows and columns after conv 1 and 2, columns after conv 3), NP = H2 x W2, the second conv's channels per
+ *   workgroup of the grouped form, its dynamic shared memory in bytes, the form that runs (1: the many-chunk form, 0: the grouped
+ *   form), 1 when the geometry can be launched; the rest 0.
+ * Returns 0; -1 bad arguments or a geometry the front end refuses (csrc/conv_front.h: nothing launched); -2 a HIP call failed. */
+APRIL_EXPORT int aprilx_run_conv_front(const int32_t *desc, const void *const *in, void *const *out, int32_t *info);
+/* The host part of aprilx_run_conv_front alone: fills info[12] from desc[16] and returns 0, or -1 where aprilx_run_conv_front would
+ * launch nothing.  No GPU needed; tests only. */
+APRIL_EXPORT int aprilx_conv_front_geometry(const int32_t *desc, int32_t *info);
+
 /* Ramp merge, the pure host part: which problems of the NEXT feed's first R macro steps the last R macro steps
  * of a feed of T chunks over L layers can hold.  Writes one record of 3 + 2 R words per window step to out (cap words): own macro step
  * (1-based, L + T - 1 - R + j), own problems in it, guests in it, then the guests as (layer, chunk) pairs, unused words -1.  Returns the

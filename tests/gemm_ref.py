@@ -95,6 +95,16 @@ def tanh_abs(x):
     return 2.0 * sigmoid(2 * x) * sig_rel(2 * x) + U * np.abs(np.tanh(x))
 
 
+def dswish_of(y, tol_y, a=1.0):
+    """(value, tolerance) of DoubleSwish y sigma(y - a) behind a bias add, for y = sum + bias known to tol_y before that add's own
+    rounding: 2 |dv/dy| tol_y + 4 hw, hw = what the fp32 add, the subtraction, fast_sigmoid and the product add (module docstring)."""
+    sg = sigmoid(y - a)
+    v = y * sg
+    dy = np.abs(sg + y * sg * (1 - sg))
+    hw = np.abs(v) * sig_rel(y - a) + dy * U * np.abs(y) + np.abs(y * sg * (1 - sg)) * U * np.abs(y - a) + U * np.abs(v)
+    return v, 2 * dy * tol_y + 4 * hw
+
+
 def scale_rel(G):
     return 2 * U + (G + 2) * U / 2
 
@@ -295,13 +305,7 @@ def evaluate(s, p, mut=None, override=None):
     if s.epi in ROW_EPIS:
         out["planes"] = (acc, tl)                        # the planes + row kernel form: the planes summed are the plain product
     if s.epi == EPI_BIAS_DSWISH:
-        y = acc + bias
-        a = 0.0 if mut == "sig_y" else 1.0
-        sg = sigmoid(y - a)
-        v = y * sg
-        dy = np.abs(sg + y * sg * (1 - sg))
-        hw = np.abs(v) * sig_rel(y - a) + dy * U * np.abs(y) + np.abs(y * sg * (1 - sg)) * U * np.abs(y - a) + U * np.abs(v)
-        out["out"] = (v, 2 * dy * tl + 4 * hw)
+        out["out"] = dswish_of(acc + bias, tl, 0.0 if mut == "sig_y" else 1.0)
     elif s.epi == EPI_HR:
         rs = row_scale(p.r_ssq, 1.0 / s.n_norm, s.eps_r)[:, None]
         x = p.resid[:, :N].astype(np.float64) * rs
