@@ -23,6 +23,7 @@ from . import _ffi
 __all__ = ["Result", "Token", "Model", "Session", "SessionGroup", "Bias", "Lm", "lm_info", "VadEvent", "resampler_taps", "decode_host", "vad_plan", "vad_host", "vad_events_host",
            "DtmfEvent", "dtmf_plan", "dtmf_tables", "dtmf_host", "dtmf_decide_host", "dtmf_events_host",
            "ToneEvent", "tone_plan", "tone_tables", "tone_host", "tone_decide_host", "tone_events_host", "tone_name",
+           "QualityEvent", "quality_plan", "quality_host", "quality_events_host",
            "snapshot_info"]
 
 
@@ -66,6 +67,56 @@ class DtmfEvent:
 
     def __repr__(self):
         return "DtmfEvent(%s, %r, %d)" % ("DOWN" if self.kind == 1 else "UP", self.digit, self.time_ms)
+
+
+class QualityEvent:
+    """A line-quality event of a session (Session(quality=...)): `kind` is QualityEvent.REPORT, CLIPPING_ON,
+    CLIPPING_OFF, DROPOUT_ON or DROPOUT_OFF, `time_ms` the position in the session's audio on the frame clock.  A REPORT carries the
+    integers of its interval -- frames, sum, sumsq, min, max, clip_samples, clipped_frames, dead_frames, quiet_sumsq, loud_sumsq -- ;
+    `hop` is the samples per frame.  The levels in dB are derived from them in float64: rms_dbfs, peak_dbfs, dc, snr_db (None when a
+    term is zero)."""
+    REPORT, CLIPPING_ON, CLIPPING_OFF, DROPOUT_ON, DROPOUT_OFF = 1, 2, 3, 4, 5
+    FIELDS = ("kind", "frames", "time_ms", "sum", "sumsq", "min", "max", "clip_samples", "clipped_frames", "dead_frames", "quiet_sumsq", "loud_sumsq", "hop")
+    __slots__ = FIELDS
+
+    def __init__(self, *values, **kw):
+        for n in self.FIELDS:
+            setattr(self, n, 0)
+        for n, v in list(zip(self.FIELDS, values)) + list(kw.items()):
+            setattr(self, n, int(v))
+
+    @classmethod
+    def from_struct(cls, e):
+        return cls(*[getattr(e, n) for n in cls.FIELDS])
+
+    def astuple(self):
+        return tuple(getattr(self, n) for n in self.FIELDS)
+
+    @property
+    def rms_dbfs(self):
+        n = self.frames * self.hop
+        return 10.0 * math.log10(self.sumsq / float(n) / 32768.0 ** 2) if n and self.sumsq else None
+
+    @property
+    def peak_dbfs(self):
+        peak = max(abs(self.min), abs(self.max))
+        return 20.0 * math.log10(peak / 32768.0) if self.frames and peak else None
+
+    @property
+    def dc(self):
+        n = self.frames * self.hop
+        return self.sum / float(n) if n else None
+
+    @property
+    def snr_db(self):
+        return 10.0 * math.log10(self.loud_sumsq / float(self.quiet_sumsq)) if self.loud_sumsq and self.quiet_sumsq else None
+
+    def __eq__(self, other):
+        return isinstance(other, QualityEvent) and self.astuple() == other.astuple()
+
+    def __repr__(self):
+        name = ("?", "REPORT", "CLIPPING_ON", "CLIPPING_OFF", "DROPOUT_ON", "DROPOUT_OFF")[self.kind if 0 < self.kind < 6 else 0]
+        return "QualityEvent(%s, %d ms%s)" % (name, self.time_ms, ", %d frames" % self.frames if self.kind == 1 else "")
 
 
 class ToneEvent:
@@ -494,6 +545,24 @@ class Model:
             raise ValueError("aprilx_run_tone_decide refused its arguments")
         return rec
 
+    def run_quality(self, clip_levels, frames_list):
+        """quality_kernel alone (aprilx_run_quality; tests): run r with clip level clip_levels[r] over frames_list[r] [n][fft_size] int16,
+        all in ONE launch.  Returns [records [n][8] uint32]."""
+        k = len(frames_list)
+        lv = np.array([int(x) for x in clip_levels], np.int32)
+        n = np.array([len(f) for f in frames_list], np.int32)
+        fr = np.ascontiguousarray(np.concatenate([np.asarray(f, np.int16).reshape(len(f), -1) for f in frames_list]), np.int16)
+        if len(lv) != k or fr.shape[1] != self.dims.fft_size:
+            raise ValueError("run_quality: one clip level per run, frames of fft_size samples")
+        rec = np.zeros((int(n.sum()), 8), np.uint32)
+        if self._L.aprilx_run_quality(self._handle, lv.ctypes.data, k, n.ctypes.data, fr.ctypes.data, rec.ctypes.data) != 0:
+            raise ValueError("aprilx_run_quality refused its arguments")
+        return np.split(rec, np.cumsum(n)[:-1])
+
+    def quality_stats(self, device_index: int = 0):
+        """(launches, frames, ms): quality launches of one GPU's engine, the frames they covered, and (while profiling) the kernel's time"""
+        return self._detector_stats(self._L.aprilx_model_quality_stats, device_index)
+
     def tone_stats(self, device_index: int = 0):
         """(launches, frames, ms): tone launches of one GPU's engine, the frames they covered, and (while profiling) the kernel's time"""
         return self._detector_stats(self._L.aprilx_model_tone_stats, device_index)
@@ -696,12 +765,22 @@ def _dispatch_tone(userdata, kind, f1_hz, f2_hz, time_ms):
 _TONE_HANDLER = _ffi.TONE_HANDLER(_dispatch_tone)
 
 
+def _dispatch_quality(userdata, event):
+    sess = C.cast(userdata, C.py_object).value
+    if sess.quality_callback is not None:
+        sess.quality_callback(QualityEvent.from_struct(event.contents))
+
+
+_QUALITY_HANDLER = _ffi.QUALITY_HANDLER(_dispatch_quality)
+
+
 class Session:
     def __init__(self, model: Model, callback: Callable[[Result, List[Token]], None], asynchronous: bool = False,
                  no_rt: bool = False, speaker_name: str = "", raw_events: bool = False, counters=None, input_sample_rate=None,
                  alternatives=None, bias=None, endpoint_silence_ms=None, blank_penalty=None, max_utterance_ms=None,
                  input_format=None, channels: int = 1, channel: int = 0, vad=None, vad_callback=None,
-                 dtmf=None, dtmf_callback=None, tones=None, tone_callback=None, lm=None, lm_weight: float = 0.3, lm_token_bonus: float = 0.0):
+                 dtmf=None, dtmf_callback=None, tones=None, tone_callback=None, lm=None, lm_weight: float = 0.3, lm_token_bonus: float = 0.0,
+                 quality=None, quality_callback=None):
         """`counters`: a uint64 ndarray of 6 entries; when given, results are only counted by a C handler inside the
         library (calls, partial, final, cant_keep_up, silence, tokens) and `callback` is never invoked.
         `input_sample_rate`: the rate of the PCM this session will receive (converted to the model's rate on the GPU); None: the
@@ -719,8 +798,11 @@ class Session:
         `dtmf`, `dtmf_callback`: True or a dict of options (set_dtmf) switches the DTMF detector on; `dtmf_callback` receives one DtmfEvent
         per key down / key up, on the same thread.
         `tones`, `tone_callback`: True or a dict of options (set_tones) switches the tone detector on; `tone_callback` receives one ToneEvent
-        per tone on / tone off, on the same thread."""
+        per tone on / tone off, on the same thread.
+        `quality`, `quality_callback`: True or a dict of options (set_quality) switches the line-quality observer on; `quality_callback`
+        receives one QualityEvent per report and per clipping / dropout on / off, on the same thread."""
         self.dtmf_callback = dtmf_callback
+        self.quality_callback = quality_callback
         self.tone_callback = tone_callback
         self._L = model._L
         self.vad_callback = vad_callback
@@ -766,6 +848,33 @@ class Session:
             self.set_dtmf(dtmf)
         if tones:
             self.set_tones(tones)
+        if quality:
+            self.set_quality(quality)
+
+    def set_quality(self, options=True, callback=None) -> None:
+        """Line-quality reports and events for this session (aprilx_session_set_quality): True for the defaults, or
+        a dict with any of clip_level (32124 for mu-law lines, 32256 for A-law), clip_run_min, clip_hold_ms, dropout_ms, report_ms;
+        None / False switches it off.  `callback` replaces the session's quality_callback.  Allowed right after creation and after a
+        completed flush; the machine and its counters start afresh."""
+        if callback is not None:
+            self.quality_callback = callback
+        if not options:
+            rc = self._L.aprilx_session_set_quality(self._handle, None, C.cast(None, _ffi.QUALITY_HANDLER), None)
+        else:
+            rc = self._L.aprilx_session_set_quality(self._handle, C.byref(_quality_options(options)), _QUALITY_HANDLER, id(self))
+        if rc != 0:
+            raise ValueError("quality options %r refused (a value out of range, or audio fed since the last flush)" % (options,))
+
+    def quality(self):
+        """None when the observer is off, else a dict: the options in force, hop, hold_frames, dropout_frames, report_frames, clipping,
+        dropout (what is on after the last frame read), frames_seen, frames, clipped_frames, dead_frames, clip_samples, reports
+        (aprilx_session_quality).  Waits for the session to be idle."""
+        o, i = _ffi.AprilxQualityOptions(), _ffi.AprilxQualityInfo()
+        if self._L.aprilx_session_quality(self._handle, C.byref(o), C.byref(i)) != 1:
+            return None
+        d = {n: int(getattr(o, n)) for n in _QUALITY_FIELDS}
+        d.update({n: int(getattr(i, n)) for n, _ in _ffi.AprilxQualityInfo._fields_})
+        return d
 
     def set_tones(self, options=True, callback=None) -> None:
         """Tone events for this session (aprilx_session_set_tones): True for the defaults, or a dict with any of
@@ -1252,6 +1361,55 @@ def tone_events_host(plan, frame_shift_ms: int, t0: int, records, machine=None, 
     if n < 0:
         raise ValueError("aprilx_tone_events_host refused its arguments")
     return [ToneEvent(kinds[i], f1[i], f2[i], times[i]) for i in range(n)], m
+
+
+_QUALITY_FIELDS = ("clip_level", "clip_run_min", "clip_hold_ms", "dropout_ms", "report_ms")
+_QUALITY_DEFAULTS = dict(clip_level=32767, clip_run_min=3, clip_hold_ms=1000, dropout_ms=200, report_ms=1000)
+
+
+def _quality_options(options):
+    """the public options struct (size, flags, then the fields) from True / a dict over the defaults / the struct itself"""
+    if isinstance(options, _ffi.AprilxQualityOptions):
+        return options
+    d = dict(_QUALITY_DEFAULTS)
+    if isinstance(options, dict):
+        unknown = set(options) - set(_QUALITY_FIELDS)
+        if unknown:
+            raise ValueError("unknown quality options %r" % (sorted(unknown),))
+        d.update(options)
+    return _ffi.AprilxQualityOptions(C.sizeof(_ffi.AprilxQualityOptions), 0, *[int(d[n]) for n in _QUALITY_FIELDS])
+
+
+def quality_plan(sample_rate: int, frame_samples: int, frame_shift_ms: int, options=True):
+    """The observer's plan (AprilxQualityPlan) of a model with this rate, frame length in samples and frame shift, on the host
+    (aprilx_quality_plan); ValueError when the options or the model are refused."""
+    plan = _ffi.AprilxQualityPlan()
+    if _ffi.lib().aprilx_quality_plan(int(sample_rate), int(frame_samples), int(frame_shift_ms), C.byref(_quality_options(options)), C.byref(plan)) != 0:
+        raise ValueError("quality options %r refused" % (options,))
+    return plan
+
+
+def quality_host(hop: int, clip_level: int, frames):
+    """The records on the host (aprilx_quality_host): frames [n][>= hop] int16 -> records [n][8] uint32"""
+    f = np.ascontiguousarray(frames, np.int16)
+    f = f.reshape(len(f), -1)
+    rec = np.zeros((len(f), 8), np.uint32)
+    if _ffi.lib().aprilx_quality_host(int(hop), int(clip_level), len(f), f.ctypes.data, f.shape[1] if len(f) else int(hop), rec.ctypes.data) != 0:
+        raise ValueError("aprilx_quality_host refused its arguments")
+    return rec
+
+
+def quality_events_host(plan, frame_shift_ms: int, t0: int, records, machine=None, flush: bool = False):
+    """The events that follow from the records [n][8] of frames [t0, t0 + n) (aprilx_quality_events_host) from `machine`
+    (AprilxQualityMachine, updated in place; None: a fresh one); `flush`: a flush completes behind them.  Returns ([QualityEvent], machine)."""
+    b = np.ascontiguousarray(records, np.uint32).reshape(-1, 8)
+    cap = 3 * len(b) + 3              # (a frame gives at most one clipping event, one dropout event and a report; a flush two OFFs and a report)
+    ev = (_ffi.AprilxQualityEvent * cap)()
+    m = machine if machine is not None else _ffi.AprilxQualityMachine()
+    n = _ffi.lib().aprilx_quality_events_host(C.byref(plan), int(frame_shift_ms), int(t0), b.ctypes.data, len(b), 1 if flush else 0, C.byref(m), C.addressof(ev), cap)
+    if n < 0:
+        raise ValueError("aprilx_quality_events_host refused its arguments")
+    return [QualityEvent.from_struct(ev[i]) for i in range(n)], m
 
 
 def tone_name(f1_hz: int, f2_hz: int = 0, tol_hz: int = 20):

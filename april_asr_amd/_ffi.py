@@ -130,6 +130,37 @@ class AprilxToneMachine(C.Structure):
 TONE_HANDLER = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64)
 
 
+class AprilxQualityOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("clip_level", C.c_uint32), ("clip_run_min", C.c_uint32), ("clip_hold_ms", C.c_uint32),
+                ("dropout_ms", C.c_uint32), ("report_ms", C.c_uint32)]
+
+
+class AprilxQualityEvent(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("frames", C.c_uint32), ("time_ms", C.c_uint64), ("sum", C.c_int64), ("sumsq", C.c_uint64), ("min", C.c_int32), ("max", C.c_int32),
+                ("clip_samples", C.c_uint64), ("clipped_frames", C.c_uint32), ("dead_frames", C.c_uint32), ("quiet_sumsq", C.c_uint64), ("loud_sumsq", C.c_uint64),
+                ("hop", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AprilxQualityInfo(C.Structure):
+    _fields_ = [("hop", C.c_int32), ("hold_frames", C.c_int32), ("dropout_frames", C.c_int32), ("report_frames", C.c_int32), ("clipping", C.c_uint32), ("dropout", C.c_uint32),
+                ("frames_seen", C.c_uint64), ("frames", C.c_uint64), ("clipped_frames", C.c_uint64), ("dead_frames", C.c_uint64), ("clip_samples", C.c_uint64),
+                ("reports", C.c_uint64)]
+
+
+class AprilxQualityPlan(C.Structure):
+    _fields_ = [("hop", C.c_int32), ("clip_level", C.c_int32), ("clip_run_min", C.c_int32), ("hold_frames", C.c_int32), ("dropout_frames", C.c_int32),
+                ("report_frames", C.c_int32)]
+
+
+class AprilxQualityMachine(C.Structure):
+    _fields_ = [("clipping", C.c_int32), ("dropout", C.c_int32), ("quiet_run", C.c_int32), ("dead_run", C.c_int32), ("frames", C.c_uint32), ("have_live", C.c_int32),
+                ("first_frame", C.c_uint64), ("sum", C.c_int64), ("sumsq", C.c_uint64), ("min", C.c_int32), ("max", C.c_int32), ("clip_samples", C.c_uint64),
+                ("clipped_frames", C.c_uint32), ("dead_frames", C.c_uint32), ("quiet_sumsq", C.c_uint64), ("loud_sumsq", C.c_uint64)]
+
+
+QUALITY_HANDLER = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(AprilxQualityEvent))
+
+
 class AprilxInputFormat(C.Structure):
     _fields_ = [("size", C.c_uint32), ("encoding", C.c_uint32), ("channels", C.c_uint32), ("channel", C.c_int32)]
 
@@ -173,6 +204,8 @@ EXPORTED_ENGINE_SYMBOLS = [
     "aprilx_dtmf_events_host", "aprilx_run_dtmf", "aprilx_run_dtmf_decide", "aprilx_model_dtmf_stats",
     "aprilx_session_set_tones", "aprilx_session_tones", "aprilx_tone_plan", "aprilx_tone_tables", "aprilx_tone_host", "aprilx_tone_decide_host",
     "aprilx_tone_events_host", "aprilx_tone_name", "aprilx_run_tones", "aprilx_run_tone_decide", "aprilx_model_tone_stats",
+    "aprilx_session_set_quality", "aprilx_session_quality", "aprilx_quality_plan", "aprilx_quality_host", "aprilx_quality_events_host", "aprilx_run_quality",
+    "aprilx_model_quality_stats",
     "aprilx_session_snapshot", "aprilx_session_restore", "aprilx_snapshot_info", "aprilx_snapshot_many", "aprilx_restore_many", "aprilx_model_snapshot_stats",
     "aprilx_lm_create", "aprilx_lm_free", "aprilx_lm_info", "aprilx_lm_arrays", "aprilx_lm_score_host", "aprilx_session_set_lm", "aprilx_session_lm_state",
     "aprilx_greedy_set_lm", "aprilx_greedy_lm_state", "aprilx_model_lm_stats", "aprilx_run_decide_lm", "aprilx_run_confidence_lm",
@@ -327,6 +360,14 @@ def lib():
     L.aprilx_restore_many.argtypes = [sz, vp, vp, vp, vp]; L.aprilx_restore_many.restype = C.c_int
     L.aprilx_model_snapshot_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.aprilx_model_snapshot_stats.restype = C.c_int
+    L.aprilx_session_set_quality.argtypes = [vp, C.POINTER(AprilxQualityOptions), QUALITY_HANDLER, vp]; L.aprilx_session_set_quality.restype = C.c_int
+    L.aprilx_session_quality.argtypes = [vp, C.POINTER(AprilxQualityOptions), C.POINTER(AprilxQualityInfo)]; L.aprilx_session_quality.restype = C.c_int
+    L.aprilx_quality_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(AprilxQualityOptions), C.POINTER(AprilxQualityPlan)]; L.aprilx_quality_plan.restype = C.c_int
+    L.aprilx_quality_host.argtypes = [C.c_int, C.c_int, C.c_int, vp, sz, vp]; L.aprilx_quality_host.restype = C.c_int
+    L.aprilx_quality_events_host.argtypes = [C.POINTER(AprilxQualityPlan), C.c_int, C.c_uint64, vp, sz, C.c_int, C.POINTER(AprilxQualityMachine), vp, C.c_int]
+    L.aprilx_quality_events_host.restype = C.c_int
+    L.aprilx_run_quality.argtypes = [vp, vp, C.c_int, vp, vp, vp]; L.aprilx_run_quality.restype = C.c_int
+    L.aprilx_model_quality_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]; L.aprilx_model_quality_stats.restype = C.c_int
     _lib = L
     return L
 

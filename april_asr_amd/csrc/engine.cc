@@ -714,17 +714,20 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
 {
     if (n_frames <= 0) return nullptr;
     const int n_rs = std::max(pass.n_rs, 0), n_dc = std::max(pass.n_dc, 0), n_vd = std::max(pass.n_vd, 0), n_dt = std::max(pass.n_dt, 0);
-    const int n_tn = std::max(pass.n_tn, 0);
+    const int n_tn = std::max(pass.n_tn, 0), n_qa = std::max(pass.n_qa, 0);
     ResampleDesc *rs = pass.rs;
     const DecodeDesc *dc = pass.dc;
     const size_t n_in_parts = n_rs ? pass.n_in_parts : 0, n_raw_parts = n_dc ? pass.n_raw_parts : 0, vd_frames = n_vd ? pass.vad_bytes : 0;
     const size_t dt_frames = n_dt ? pass.dtmf_bytes : 0;
     // the pass's bytes: VAD, then DTMF, then (4-byte aligned) the tone records
-    const size_t tn_at = (vd_frames + dt_frames + 3) / 4 * 4, tn_frames = n_tn ? pass.tone_bytes / 4 : 0, out_bytes = n_tn ? tn_at + tn_frames * 4 : vd_frames + dt_frames;
+    const size_t tn_at = (vd_frames + dt_frames + 3) / 4 * 4, tn_frames = n_tn ? pass.tone_bytes / 4 : 0, tn_end = n_tn ? tn_at + tn_frames * 4 : vd_frames + dt_frames;
+    // ... then (16-byte aligned) the quality records
+    const size_t qa_at = FrontPass::quality_at_of(vd_frames, dt_frames, tn_frames * 4), qa_frames = n_qa ? pass.quality_bytes / (kQualityWords * 4) : 0;
+    const size_t out_bytes = n_qa ? qa_at + qa_frames * kQualityWords * 4 : tn_end;
     StagingCounts cnt;
     cnt.n_pcm = n_pcm; cnt.n_in = n_rs ? pass.n_in : 0; cnt.n_raw = n_dc ? pass.n_raw : 0;
-    cnt.n_frames = (size_t)n_frames; cnt.n_rs = (size_t)n_rs; cnt.n_dc = (size_t)n_dc; cnt.n_vd = (size_t)n_vd; cnt.n_dt = (size_t)n_dt; cnt.n_tn = (size_t)n_tn;
-    const StagingSizes el{sizeof(FbankFrameDesc), sizeof(ResampleDesc), sizeof(DecodeDesc), sizeof(VadDesc), sizeof(DtmfDesc), sizeof(ToneDesc)};
+    cnt.n_frames = (size_t)n_frames; cnt.n_rs = (size_t)n_rs; cnt.n_dc = (size_t)n_dc; cnt.n_vd = (size_t)n_vd; cnt.n_dt = (size_t)n_dt; cnt.n_tn = (size_t)n_tn; cnt.n_qa = (size_t)n_qa;
+    const StagingSizes el{sizeof(FbankFrameDesc), sizeof(ResampleDesc), sizeof(DecodeDesc), sizeof(VadDesc), sizeof(DtmfDesc), sizeof(ToneDesc), sizeof(QualityDesc)};
     const StagingLayout lay = staging_layout(cnt, el);
     HIP_CHECK(hipSetDevice(cfg_.device));
     for (int i = 0; i < n_rs; ++i) rs[i].taps = resample_table(pass.rs_specs[i]);      // (uploaded at a conversion's first use)
@@ -742,9 +745,9 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
     PassBlock *block = nullptr;
     const float *dt_tables = n_dt ? dtmf_tables() : nullptr;      // (sets dt_wd_)
     const float *tn_tables = n_tn ? tone_tables() : nullptr;      // (sets tn_w_, tn_f_)
-    if (n_vd || n_dt || n_tn) {
-        // a pass with VAD, DTMF or tone descriptors: the first VAD pass of the engine allocates the per-slot records; the device's byte buffer
-        // (the pass's VAD bytes, then its DTMF bytes, then its tone records) grows behind a sync (earlier passes' copies read it); a pass takes a pinned block
+    if (n_vd || n_dt || n_tn || n_qa) {
+        // a pass with VAD, DTMF, tone or quality descriptors: the first VAD pass of the engine allocates the per-slot records; the device's byte buffer
+        // (the pass's VAD bytes, then its DTMF bytes, then its tone records, then its quality records) grows behind a sync (earlier passes' copies read it); a pass takes a pinned block
         // nobody holds, or a new one (warm-up only)
         if (n_vd && !vad_state_d_) vad_state_d_ = dmalloc<VadState>((size_t)cfg_.max_slots);
         if (out_bytes > pass_out_cap_) {
@@ -767,7 +770,7 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
     const int b = fb_flip_;
     fb_flip_ ^= 1;
     HIP_CHECK(hipEventSynchronize(fb_done_[b]));          // the launch that used this pair two calls ago has consumed it
-    const size_t woff = lay.raw, doff = lay.frames, roff = lay.rs, coff = lay.dc, voff = lay.vd, toff = lay.dt, noff = lay.tn, bytes = lay.bytes;      // (staging_layout.h)
+    const size_t woff = lay.raw, doff = lay.frames, roff = lay.rs, coff = lay.dc, voff = lay.vd, toff = lay.dt, noff = lay.tn, qoff = lay.qa, bytes = lay.bytes;      // (staging_layout.h)
     char *hs = reinterpret_cast<char *>(hs_pcm_[b]);
     memcpy(hs + doff, desc, (size_t)n_frames * sizeof(FbankFrameDesc));
     if (n_vd) memcpy(hs + voff, pass.vd, (size_t)n_vd * sizeof(VadDesc));
@@ -800,6 +803,22 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
         const char *dev = reinterpret_cast<const char *>(ds_pcm_[b]);
         na.pcm = ds_pcm_[b]; na.frames = reinterpret_cast<const FbankFrameDesc *>(dev + doff); na.out = reinterpret_cast<uint32_t *>(pass_out_d_ + tn_at);
         na.desc = reinterpret_cast<const ToneDesc *>(dev + noff); na.n_desc = n_tn; na.tables = tn_tables; na.w = tn_w_; na.f = tn_f_;
+    }
+    QualityArgs qa;
+    if (n_qa) {
+        memcpy(hs + qoff, pass.qa, (size_t)n_qa * sizeof(QualityDesc));
+        if (pass.quality_hop <= 0 || pass.quality_hop > ft_.padded) { LOGE("fbank: a quality hop of %d samples is not inside the frame", pass.quality_hop); abort(); }
+        for (int i = 0; i < n_qa; ++i) {
+            const QualityDesc &t = pass.qa[i];
+            if (t.n <= 0 || t.first < 0 || t.first + t.n > n_frames || t.out_off < 0 || (size_t)t.out_off + (size_t)t.n > qa_frames) {
+                LOGE("fbank: quality descriptor %d outside the pass", i); abort();
+            }
+            for (int k = 0; k < t.n; ++k) if (desc[t.first + k].pcm_off < 0) { LOGE("fbank: a padding row inside quality run %d", i); abort(); }
+            qa.max_n = std::max(qa.max_n, t.n);
+        }
+        const char *dev = reinterpret_cast<const char *>(ds_pcm_[b]);
+        qa.pcm = ds_pcm_[b]; qa.frames = reinterpret_cast<const FbankFrameDesc *>(dev + doff); qa.out = reinterpret_cast<uint32_t *>(pass_out_d_ + qa_at);
+        qa.desc = reinterpret_cast<const QualityDesc *>(dev + qoff); qa.n_desc = n_qa; qa.hop = pass.quality_hop;
     }
     ResampleArgs ra;
     if (n_rs) {
@@ -866,6 +885,7 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
         if (n_rs) { timed_begin(T_RESAMPLE); launch_resample(ra, stream_); timed_end(T_RESAMPLE); }
         if (n_dt) { timed_begin(T_DTMF); launch_dtmf(ta, stream_); timed_end(T_DTMF); }
         if (n_tn) { timed_begin(T_TONE); launch_tone(na, stream_); timed_end(T_TONE); }
+        if (n_qa) { timed_begin(T_QUALITY); launch_quality(qa, stream_); timed_end(T_QUALITY); }
         timed_begin(T_FBANK); launch_fbank(a, stream_); timed_end(T_FBANK);
         if (n_vd) { timed_begin(T_VAD); launch_vad(va, stream_); timed_end(T_VAD); }
         join(f_stream_, stream_);
@@ -874,15 +894,17 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
         if (n_rs) launch_resample(ra, f_stream_);
         if (n_dt) launch_dtmf(ta, f_stream_);          // (reads the samples fbank_kernel reads; the staging pair is recycled after fb_done_)
         if (n_tn) launch_tone(na, f_stream_);          // (likewise)
+        if (n_qa) launch_quality(qa, f_stream_);       // (likewise)
         launch_fbank(a, f_stream_);
         if (n_vd) launch_vad(va, f_stream_);
     }
-    if (n_vd || n_dt || n_tn) {       // the pass's bytes -> its pinned block, in front of fb_done_; read after the flight's wait (close_flight)
+    if (n_vd || n_dt || n_tn || n_qa) {       // the pass's bytes -> its pinned block, in front of fb_done_; read after the flight's wait (close_flight)
         HIP_CHECK(hipMemcpyAsync(block->h, pass_out_d_, out_bytes, hipMemcpyDeviceToHost, f_stream_));
         pass_bytes_flight_ = true;
         if (n_vd) { vad_launches_.fetch_add(1, std::memory_order_relaxed); vad_frames_.fetch_add(vd_frames, std::memory_order_relaxed); }
         if (n_dt) { dt_launches_.fetch_add(1, std::memory_order_relaxed); dt_frames_.fetch_add(dt_frames, std::memory_order_relaxed); }
         if (n_tn) { tn_launches_.fetch_add(1, std::memory_order_relaxed); tn_frames_.fetch_add(tn_frames, std::memory_order_relaxed); }
+        if (n_qa) { qa_launches_.fetch_add(1, std::memory_order_relaxed); qa_frames_.fetch_add(qa_frames, std::memory_order_relaxed); }
     }
     HIP_CHECK(hipEventRecord(fb_done_[b], f_stream_));       // no host wait here: the encoder launches queue right behind
     f_unseen_by_m_ = true;
@@ -2495,6 +2517,32 @@ void Engine::debug_tones(int n_runs, const TonePlan *plans, const int32_t *n, co
     run_on_private_stream([&](hipStream_t st) { launch_tone(a, st); });
     HIP_CHECK(hipMemcpy(records_out, a.out, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (powers_out) HIP_CHECK(hipMemcpy(powers_out, a.powers, total * row * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+void Engine::debug_quality(int hop, int n_runs, const int32_t *clip_levels, const int32_t *n, const int16_t *frames, uint32_t *records_out)
+{
+    // frame i of the call sits at sample i * padded of a scratch staging buffer, as in debug_dtmf
+    const size_t padded = (size_t)ft_.padded;
+    if (hop <= 0 || hop > ft_.padded) { LOGE("a quality hop of %d samples is not inside the frame", hop); abort(); }
+    std::vector<QualityDesc> desc((size_t)n_runs);
+    size_t total = 0;
+    int max_n = 0;
+    for (int r = 0; r < n_runs; ++r) {
+        QualityDesc &d = desc[(size_t)r];
+        d.first = (int32_t)total; d.n = n[r]; d.out_off = (int32_t)total; d.clip_level = clip_levels[r];
+        total += (size_t)n[r]; max_n = std::max(max_n, n[r]);
+    }
+    std::vector<FbankFrameDesc> fd(total);
+    for (size_t i = 0; i < total; ++i) { fd[i].slot = 0; fd[i].ring_row = 0; fd[i].pcm_off = (int32_t)(i * padded); }
+    HipLegacyLock legacy;
+    HIP_CHECK(hipSetDevice(cfg_.device));
+    DeviceScratch ds;
+    QualityArgs a;
+    a.pcm = ds.upload(frames, total * padded); a.frames = ds.upload(fd.data(), fd.size()); a.desc = ds.upload(desc.data(), desc.size()); a.n_desc = n_runs;
+    a.max_n = max_n; a.hop = hop;
+    a.out = ds.alloc<uint32_t>(total * kQualityWords);
+    run_on_private_stream([&](hipStream_t st) { launch_quality(a, st); });
+    HIP_CHECK(hipMemcpy(records_out, a.out, total * kQualityWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
 }
 
 void Engine::debug_tone_decide(const TonePlan &plan, int n, const float *powers, uint32_t *records_out)

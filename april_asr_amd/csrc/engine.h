@@ -137,6 +137,17 @@ struct FrontPass {
     // per frame, `tone_bytes` in all) are the third part of the block, at the 4-byte aligned offset tone_at(); out_off counts records.
     int n_tn = 0; const ToneDesc *tn = nullptr; size_t tone_bytes = 0;
     size_t tone_at() const { return (vad_bytes + dtmf_bytes + 3) / 4 * 4; }
+    // Line quality: the n_qa descriptors (`first` as DTMF's); quality_kernel runs behind tone_kernel.  Its records
+    // (32 bytes per frame, `quality_bytes` in all) are the fourth part of the block, at the 16-byte aligned offset quality_at(); out_off
+    // counts records.
+    int n_qa = 0; const QualityDesc *qa = nullptr; size_t quality_bytes = 0;
+    int quality_hop = 0;                       // H of the plans behind the descriptors: the model's frame shift in samples
+    static size_t quality_at_of(size_t vad_bytes, size_t dtmf_bytes, size_t tone_bytes)
+    {
+        const size_t end = tone_bytes ? (vad_bytes + dtmf_bytes + 3) / 4 * 4 + tone_bytes : vad_bytes + dtmf_bytes;
+        return (end + 15) / 16 * 16;
+    }
+    size_t quality_at() const { return quality_at_of(vad_bytes, dtmf_bytes, tone_bytes); }
 };
 
 // One call of the decision kernel on GIVEN rows (the parity tests' entry point, Engine::debug_decide): slots 0..n-1, row i = slot i.
@@ -189,8 +200,8 @@ public:
     // chunk steps (encoder + the three joiner/decision/decoder rounds, all on the device) and decoder refreshes are queued
     // back to back, and the host reads the 16-byte-per-round records once, at end_flight().
     // pcm arrives as `n_parts` windows that are gathered straight into pinned staging (total n_pcm samples)
-    // `pass`: the resample / decode / VAD / DTMF / tone work of this call.  Returns the pinned block that receives the pass's VAD bytes, behind
-    // them its DTMF bytes and behind those its tone records (null: no descriptors of the three): its bytes are complete once the flight that was open during the call
+    // `pass`: the resample / decode / VAD / DTMF / tone / line-quality work of this call.  Returns the pinned block that receives the pass's VAD bytes, behind
+    // them its DTMF bytes, behind those its tone records and behind those its quality records (null: no descriptors of the four): its bytes are complete once the flight that was open during the call
     // has been waited for (close_flight() puts the copy in front of the flight's event), and the block is lent until
     // release_pass_block().  Stepping thread only.
     const uint8_t *fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<const int16_t *, size_t> *parts, size_t n_parts, size_t n_pcm,
@@ -228,6 +239,14 @@ public:
     }
     // aprilx_run_tones: n_runs runs in ONE launch, as debug_dtmf; records_out [sum n] (lo | hi << 16), powers_out (may be null) [sum n][F + 1]
     void debug_tones(int n_runs, const TonePlan *plans, const int32_t *n, const int16_t *frames, uint32_t *records_out, float *powers_out);
+    // ---- line quality.  Launches and the frames they covered so far (any thread); nothing is allocated until a
+    // pass carries a quality descriptor.
+    void quality_counts(uint64_t *launches, uint64_t *frames) const
+    {
+        *launches = qa_launches_.load(std::memory_order_relaxed); *frames = qa_frames_.load(std::memory_order_relaxed);
+    }
+    // aprilx_run_quality: n_runs runs in ONE launch, as debug_dtmf, run r with clip level clip_levels[r] over hops of `hop` samples; records_out [sum n][8]
+    void debug_quality(int hop, int n_runs, const int32_t *clip_levels, const int32_t *n, const int16_t *frames, uint32_t *records_out);
     // aprilx_run_tone_decide: the decision alone on n given rows of P[0..F), E
     void debug_tone_decide(const TonePlan &plan, int n, const float *powers, uint32_t *records_out);
     // aprilx_run_vad: n_runs runs in ONE launch over a scratch ring of ring_rows rows per run; run r's n[r] rows (consecutive in `rows`)
@@ -402,7 +421,7 @@ public:
     void ramp_defer_counts(uint64_t *headless, uint64_t *by_wait, uint64_t *by_other);
     void reset_timing();
     enum { T_GATES = 0, T_GEMM_OTHER = 1, T_ROW = 2, T_CONV = 3, T_FBANK = 4, T_DEC = 5, T_RESAMPLE = 6, T_DECODE = 7, T_VAD = 8, T_DTMF = 9, T_TONE = 10,
-           T_SNAP_GATHER = 11, T_SNAP_SCATTER = 12, T_COUNT = 13 };
+           T_SNAP_GATHER = 11, T_SNAP_SCATTER = 12, T_QUALITY = 13, T_COUNT = 14 };
     long kernels_per_step() const { return kernels_per_step_.load(std::memory_order_relaxed); }    // launches of the last eagerly issued chunk chain
 
 private:
@@ -585,7 +604,7 @@ private:
     std::atomic<uint64_t> dc_launches_{0}, dc_frames_{0};
     // voice activity: nothing below is allocated until a pass carries a VAD descriptor
     VadState *vad_state_d_ = nullptr;          // [slots] (a session's first descriptor carries VAD_RESET: never initialised by the host)
-    uint8_t *pass_out_d_ = nullptr; size_t pass_out_cap_ = 0;      // one pass's bytes on the device, VAD, DTMF, then the tone records (stream order keeps the passes apart)
+    uint8_t *pass_out_d_ = nullptr; size_t pass_out_cap_ = 0;      // one pass's bytes on the device, VAD, DTMF, the tone records, then the quality records (stream order keeps the passes apart)
     struct PassBlock { uint8_t *h = nullptr; size_t cap = 0; bool busy = false; };
     std::vector<PassBlock> pass_blocks_;         // pinned blocks, one per pass whose bytes (VAD, then DTMF) the scheduler has not read yet: lent by fbank(), busy until release_pass_block()
     bool pass_bytes_flight_ = false;                  // the open flight holds a pass with VAD or DTMF bytes: its event must follow their copy on the front-end stream
@@ -598,6 +617,8 @@ private:
     const float *tn_tables_ = nullptr; int tn_w_ = 0, tn_f_ = 0;      // [2F][W] on the device, uploaded once (freed with table_allocs_)
     std::atomic<uint64_t> tn_launches_{0}, tn_frames_{0};
     const float *tone_tables();
+    // line quality: no table, no per-slot record; the counters of quality_counts()
+    std::atomic<uint64_t> qa_launches_{0}, qa_frames_{0};
     // snapshot / restore: nothing below is allocated until the first call
     bool snapshot_copy(int n, SnapRec *recs, uint8_t *const *blocks, bool scatter);
     char *snap_d_ = nullptr, *snap_h_ = nullptr; size_t snap_cap_ = 0;      // device staging and its pinned twin: the records, then the blocks

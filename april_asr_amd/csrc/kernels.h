@@ -11,6 +11,7 @@
 #include "vad.h"
 #include "dtmf.h"
 #include "tone.h"
+#include "quality.h"
 #include "gemm_plan.h"
 #include "conv_front.h"
 
@@ -557,5 +558,25 @@ struct ToneArgs {
 void launch_tone(const ToneArgs &a, hipStream_t s);
 // (tests) the decision alone on GIVEN rows of P[0..F), E: records_out[i] = tone_decide(plan, powers + (F + 1) i)
 void launch_tone_decide(const TonePlan &plan, int n, const float *powers, uint32_t *records_out, hipStream_t s);
+
+// ---------------------------------------------------------------- line quality (sessions that opted in; contract in quality.h)
+// One descriptor per run of consecutive real frames of a session in this pass, laid out as DtmfDesc: frame i of the run is frame
+// descriptor first + i of the SAME pass, its record (eight uint32, 32 bytes) goes to out + 8 (out_off + i).  The descriptor carries the
+// session's clip level; the kernel keeps no state.  One wave per frame, kQualityBlock / 64 waves per workgroup, a wave walks every
+// (waves of its descriptor)-th frame of the run.
+constexpr int kQualityBlock = 256, kQualityLanes = 64, kQualityWaveFrames = 4, kQualityMaxBlocks = 64;      // lanes per workgroup and wave; frames a wave walks before another workgroup is worth it
+struct QualityDesc {
+    int32_t first = 0, n = 0, out_off = 0, clip_level = 32767;
+};
+static_assert(sizeof(QualityDesc) == 16, "staged behind the tone descriptors, 16-byte aligned");
+struct QualityArgs {
+    const int16_t *pcm = nullptr;          // staged samples
+    const FbankFrameDesc *frames = nullptr;
+    const QualityDesc *desc = nullptr; int n_desc = 0;
+    int max_n = 0;                         // max over descriptors of n
+    int hop = 0;                           // H: samples of a frame the record covers (at most the staged frame's length)
+    uint32_t *out = nullptr;               // the pass's records (16-byte aligned)
+};
+void launch_quality(const QualityArgs &a, hipStream_t s);
 
 }  // namespace aprilx

@@ -585,6 +585,16 @@ bool Scheduler::set_tones(Session *s, const ToneOptions *o, const TonePlan *plan
     });
 }
 
+bool Scheduler::set_quality(Session *s, const QualityOptions *o, const QualityPlan *plan, AprilxQualityHandler handler, void *userdata)
+{
+    return configure(s, [&] {
+        s->quality = Session::Quality();
+        if (plan) { s->quality.on = true; s->quality.opt = *o; s->quality.plan = *plan; }
+        s->handlers.quality = plan ? handler : nullptr; s->handlers.quality_userdata = plan ? userdata : nullptr;
+        return true;
+    });
+}
+
 bool Scheduler::set_bias(Session *s, std::shared_ptr<const BiasSet> set)
 {
     return configure(s, [&] {
@@ -643,7 +653,8 @@ void Scheduler::wait_backlog(Session *const *ss, int n, uint64_t max_open)
 void deliver_events(std::vector<Event> &ev, const Handlers &to)
 {
     for (auto &e : ev) {
-        if (e.type >= kToneEventBase) { if (to.tone) to.tone(to.tone_userdata, e.type - kToneEventBase, e.f1, e.f2, e.time_ms); }
+        if (e.type >= kQualityEventBase) { if (to.quality && e.quality) to.quality(to.quality_userdata, reinterpret_cast<const AprilxQualityEvent *>(e.quality.get())); }
+        else if (e.type >= kToneEventBase) { if (to.tone) to.tone(to.tone_userdata, e.type - kToneEventBase, e.f1, e.f2, e.time_ms); }
         else if (e.type >= kDtmfEventBase) { if (to.dtmf) to.dtmf(to.dtmf_userdata, e.type - kDtmfEventBase, e.digit, e.time_ms); }
         else if (e.type >= kVadEventBase) { if (to.vad) to.vad(to.vad_userdata, e.type - kVadEventBase, e.time_ms); }
         else to.result(to.userdata, (AprilResultType)e.type, e.tokens.size(), e.tokens.empty() ? nullptr : e.tokens.data());
@@ -972,10 +983,11 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
 {
     Lap lap;
     desc_.clear(); pcm_parts_.clear(); in_parts_.clear(); rdesc_.clear(); rspec_.clear(); ddesc_.clear(); raw_parts_.clear(); staged_raw_ = 0;
-    vdesc_.clear(); tdesc_.clear(); ndesc_.clear();
+    vdesc_.clear(); tdesc_.clear(); ndesc_.clear(); qdesc_.clear();
     PassPending rec{flight_seq_, nullptr, 0, 0, {}, {}, {}};      // this pass's record in the pass queue: its runs and flush markers, then its block
     int32_t vad_frames = 0, dtmf_frames = 0;    // bytes of this pass's VAD / DTMF output so far
     int32_t tone_frames = 0;                    // records of its tone output so far
+    int32_t quality_frames = 0, quality_hop = 0;      // records of its quality output so far; the hop of the plans behind them
     size_t staged = 0, staged_in = 0;           // model-rate samples (windows), input-rate samples (spans of resampled windows)
     auto used = [&] { return staged + staged_in + (staged_raw_ + 1) / 2; };      // what the pass has staged so far, raw bytes of formatted sessions in sample units
     std::vector<Session *> finishers;
@@ -1038,6 +1050,13 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
                 rec.tone.push_back(PassRun{s, s->real_frames, cut, tone_frames});
                 tone_frames += cut;
             }
+            if (s->quality.on) {                       // likewise
+                QualityDesc q;
+                q.first = (int32_t)(desc_.size() - (size_t)cut); q.n = cut; q.out_off = quality_frames; q.clip_level = s->quality.plan.clip_level;
+                qdesc_.push_back(q);
+                rec.quality.push_back(PassRun{s, s->real_frames, cut, quality_frames});
+                quality_frames += cut; quality_hop = s->quality.plan.hop;
+            }
             s->real_frames += (uint64_t)cut;
             s->compact_pending = true;                 // the fifo must not move until the window has been staged
             progressed = true;
@@ -1084,6 +1103,7 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
             if (s->vad.on) { rec.vad.push_back(PassRun{s, s->real_frames, -1, 0}); s->vad.reset = true; }      // closes an open segment; the detector starts afresh
             if (s->dtmf.on) rec.dtmf.push_back(PassRun{s, s->real_frames, -1, 0});                              // closes a held digit; the machine starts afresh
             if (s->tones.on) rec.tone.push_back(PassRun{s, s->real_frames, -1, 0});                             // closes a held tone likewise
+            if (s->quality.on) rec.quality.push_back(PassRun{s, s->real_frames, -1, 0});                        // closes the open interval and what is on
             s->flush_phase = 0;
             progressed = true;
             break;
@@ -1098,6 +1118,7 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
         pass.n_vd = (int)vdesc_.size(); pass.vd = vdesc_.data(); pass.vad_bytes = (size_t)vad_frames;
         pass.n_dt = (int)tdesc_.size(); pass.dt = tdesc_.data(); pass.dtmf_bytes = (size_t)dtmf_frames;
         pass.n_tn = (int)ndesc_.size(); pass.tn = ndesc_.data(); pass.tone_bytes = (size_t)tone_frames * 4;
+        pass.n_qa = (int)qdesc_.size(); pass.qa = qdesc_.data(); pass.quality_bytes = (size_t)quality_frames * kQualityWords * 4; pass.quality_hop = quality_hop;
         rec.block = eng_->fbank((int)desc_.size(), desc_.data(), pcm_parts_.data(), pcm_parts_.size(), staged, &pool_, pass);
         pool_.run(work.size(), 64, [&](size_t i) { Session *s = work[i]; if (s->compact_pending) { s->fb.compact(); s->compact_pending = false; } });
         tick_.frames += desc_.size();
@@ -1106,7 +1127,8 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
     // the block is lent until this flight has been waited for and harvest() has read it
     rec.dtmf_at = (size_t)vad_frames;
     rec.tone_at = ((size_t)vad_frames + (size_t)dtmf_frames + 3) / 4 * 4;      // (FrontPass::tone_at())
-    if (rec.block || !rec.vad.empty() || !rec.dtmf.empty() || !rec.tone.empty()) pass_pending_.push_back(std::move(rec));
+    rec.quality_at = FrontPass::quality_at_of((size_t)vad_frames, (size_t)dtmf_frames, (size_t)tone_frames * 4);
+    if (rec.block || !rec.vad.empty() || !rec.dtmf.empty() || !rec.tone.empty() || !rec.quality.empty()) pass_pending_.push_back(std::move(rec));
     if (!finishers.empty()) {
         slots_.clear();
         for (Session *s : finishers) slots_.push_back(s->slot);
@@ -1227,7 +1249,7 @@ bool Scheduler::step_chunks(std::vector<Session *> &ready)
 }
 
 // After the flight's wait: the bytes of every pass cut under it (and under the flights before it) are on the host.  The records up to
-// the flight are walked three times -- all VAD runs of all of them, then all DTMF runs, then all tone runs: the order of a session's detector events in front of
+// the flight are walked four times -- all VAD runs of all of them, then all DTMF runs, then all tone runs, then all quality runs: the order of a session's detector events in front of
 // the flight's token events --, then each gives its block back and goes.  The sessions are alive: they stay busy until their flight
 // completes.  An engine that lent no block to a pass with descriptors: that pass's bytes are skipped by all detectors alike.
 void Scheduler::harvest(uint64_t flight)
@@ -1237,6 +1259,7 @@ void Scheduler::harvest(uint64_t flight)
     for (size_t i = 0; i < n; ++i) for (const PassRun &r : pass_pending_[i].vad) harvest_vad(pass_pending_[i], r);
     for (size_t i = 0; i < n; ++i) for (const PassRun &r : pass_pending_[i].dtmf) harvest_dtmf(pass_pending_[i], r);
     for (size_t i = 0; i < n; ++i) for (const PassRun &r : pass_pending_[i].tone) harvest_tone(pass_pending_[i], r);
+    for (size_t i = 0; i < n; ++i) for (const PassRun &r : pass_pending_[i].quality) harvest_quality(pass_pending_[i], r);
     for (; n; --n) {
         if (pass_pending_.front().block) eng_->release_pass_block(pass_pending_.front().block);
         pass_pending_.pop_front();
@@ -1289,6 +1312,27 @@ void Scheduler::harvest_tone(const PassPending &p, const PassRun &r)
     const uint32_t *b = reinterpret_cast<const uint32_t *>(p.block + p.tone_at) + r.off;      // (the block is pinned memory, tone_at a multiple of 4)
     tone_events(s->tones.plan, shift_ms_, r.t0, b, (size_t)r.n, s->tones.m, emit);
     for (int32_t i = 0; i < r.n; ++i) s->tones.tonal += (b[i] & 0xffffu) ? 1u : 0u;
+}
+
+// One quality run: the records of consecutive real frames go through the session's machine (quality.h); a completed flush closes the open
+// interval and whatever is on.
+void Scheduler::harvest_quality(const PassPending &p, const PassRun &r)
+{
+    Session *s = r.s;
+    auto emit = [&](const QualityEvent &q) {
+        Event e; e.type = kQualityEventBase + q.kind; e.time_ms = q.time_ms; e.quality.reset(new QualityEvent(q));
+        s->events.push_back(std::move(e));
+        if (q.kind == QUALITY_REPORT) s->quality.reports++;
+    };
+    if (r.n < 0) { quality_flush(s->quality.plan, shift_ms_, r.t0, s->quality.m, emit); return; }
+    if (!p.block) return;
+    const uint32_t *b = reinterpret_cast<const uint32_t *>(p.block + p.quality_at) + (size_t)r.off * kQualityWords;      // (the block is pinned memory, quality_at a multiple of 16)
+    quality_events(s->quality.plan, shift_ms_, r.t0, b, (size_t)r.n, s->quality.m, emit);
+    for (int32_t i = 0; i < r.n; ++i) {
+        const uint32_t *w = b + (size_t)i * kQualityWords;
+        s->quality.frames++; s->quality.clip_samples += w[4] & 0xffffu;
+        s->quality.clipped += (w[4] >> 16) >= (uint32_t)s->quality.plan.clip_run_min ? 1u : 0u; s->quality.dead += w[5] & 1u;
+    }
 }
 
 // After the flight: per session, in the order things happened, feed the device's per-round records to the search state

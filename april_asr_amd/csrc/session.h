@@ -58,8 +58,10 @@ struct Event {
     uint64_t time_ms = 0;
     char digit = 0;
     uint32_t f1 = 0, f2 = 0;
+    // a line-quality event (section 21): type = kQualityEventBase + kind, and the event as its handler receives it
+    std::unique_ptr<QualityEvent> quality;
 };
-constexpr int kVadEventBase = 0x100, kDtmfEventBase = 0x200, kToneEventBase = 0x300;
+constexpr int kVadEventBase = 0x100, kDtmfEventBase = 0x200, kToneEventBase = 0x300, kQualityEventBase = 0x400;
 // where a session's events go: token events to `result`, voice-activity events to `vad`, DTMF events to `dtmf`, tone events to `tone`
 // (null: dropped)
 struct Handlers {
@@ -67,6 +69,7 @@ struct Handlers {
     AprilxVadHandler vad = nullptr; void *vad_userdata = nullptr;
     AprilxDtmfHandler dtmf = nullptr; void *dtmf_userdata = nullptr;
     AprilxToneHandler tone = nullptr; void *tone_userdata = nullptr;
+    AprilxQualityHandler quality = nullptr; void *quality_userdata = nullptr;
 };
 // the handler once per event, in order (null token pointer when an event has no tokens); `ev` is empty afterwards
 void deliver_events(std::vector<Event> &ev, const Handlers &to);
@@ -265,6 +268,11 @@ struct Session {
         ToneMachine m;                        // (the device keeps nothing)
         uint64_t tonal = 0, tones = 0;        // frames with a tonal record, ON events, since the detector was last set
     } tones;
+    struct Quality {                          // 
+        bool on = false; QualityOptions opt; QualityPlan plan;
+        QualityMachine m;                     // (the device keeps nothing)
+        uint64_t frames = 0, clipped = 0, dead = 0, clip_samples = 0, reports = 0;      // records read, clipped and dead frames, clipped samples, REPORT events, since the observer was last set
+    } quality;
     // tracing (tests): every joiner call appends `vocab` floats
     float *trace_buf = nullptr; size_t trace_cap = 0; size_t *trace_used = nullptr;
 };
@@ -314,6 +322,8 @@ public:
     bool set_dtmf(Session *s, const DtmfOptions *o, const DtmfPlan *plan, AprilxDtmfHandler handler, void *userdata);
     // aprilx_session_set_tones: the same rule; plan null = off.  The machine and its counters start afresh
     bool set_tones(Session *s, const ToneOptions *o, const TonePlan *plan, AprilxToneHandler handler, void *userdata);
+    // aprilx_session_set_quality: the same rule; plan null = off.  The machine and its counters start afresh
+    bool set_quality(Session *s, const QualityOptions *o, const QualityPlan *plan, AprilxQualityHandler handler, void *userdata);
     void wait_idle_many(Session *const *ss, int n);
     // until every listed session has at most `max_open` feeds that were submitted and not completed yet (pipelined group feeds)
     void wait_backlog(Session *const *ss, int n, uint64_t max_open);
@@ -364,16 +374,17 @@ private:
     // for, turns the runs into events, gives the block back to the engine and pops the record.  The record is the block's one owner.
     struct PassRun { Session *s; uint64_t t0; int32_t n, off; };      // frames [t0, t0 + n) at off in its detector's part; n < 0: a flush completed at frame t0
     // block: Engine::fbank()'s, the pass's VAD bytes, from dtmf_at its DTMF bytes and from tone_at its tone records (a tone run's off
-    // counts records); null: a pass of flush markers only
-    struct PassPending { uint64_t flight; const uint8_t *block; size_t dtmf_at, tone_at; std::vector<PassRun> vad, dtmf, tone; };
+    // counts records) and from quality_at its quality records (likewise); null: a pass of flush markers only
+    struct PassPending { uint64_t flight; const uint8_t *block; size_t dtmf_at, tone_at; std::vector<PassRun> vad, dtmf, tone; size_t quality_at = 0; std::vector<PassRun> quality; };
     std::deque<PassPending> pass_pending_;
-    std::vector<VadDesc> vdesc_; std::vector<DtmfDesc> tdesc_; std::vector<ToneDesc> ndesc_;       // scratch of cut_frames()
+    std::vector<VadDesc> vdesc_; std::vector<DtmfDesc> tdesc_; std::vector<ToneDesc> ndesc_; std::vector<QualityDesc> qdesc_;       // scratch of cut_frames()
     uint64_t flight_seq_ = 0;
     const int shift_ms_;
     void harvest(uint64_t flight);
     void harvest_vad(const PassPending &p, const PassRun &r);
     void harvest_dtmf(const PassPending &p, const PassRun &r);
     void harvest_tone(const PassPending &p, const PassRun &r);
+    void harvest_quality(const PassPending &p, const PassRun &r);
     int split_sticky_ = 0;
     int pipeline_depth_ = 2;                             // APRIL_PIPELINE: 2 = launch the next flight before completing the current one, 1 = one flight at a time
 

@@ -114,6 +114,8 @@ static void snapshot_group(Scheduler *sched, Session *const *ss, int n, std::vec
     for (int i = 0; i < n; ++i) ok[i] = !sched->in_own_handler(ss[i]);
     // a session with a language model is refused: the format does not carry the model's node (DESIGN.md sections 19 and 20)
     for (int i = 0; i < n; ++i) if (ss[i]->greedy.lm()) { ok[i] = false; LOGW("snapshot: refused: the session has a language model, whose node a snapshot does not carry"); }
+    // ... and so is a session with the line-quality observer: the format does not carry its machine
+    for (int i = 0; i < n; ++i) if (ss[i]->quality.on) { ok[i] = false; LOGW("snapshot: refused: the session has the line-quality observer on, whose machine a snapshot does not carry"); }
     if (sched->on_loop_thread()) return;                       // (a handler on the stepping thread: it would wait for itself)
     sched->submit(0, nullptr, nullptr, nullptr, false, false);   // wake-up only (aprilx_session_drain)
     sched->wait_idle_many(ss, n);
@@ -245,6 +247,7 @@ static void restore_group(Scheduler *sched, Session *const *ss, int n, const voi
         if (status[i]) continue;
         if (!fresh(*ss[i])) { refuse(i, "the target session has been fed (or has work queued): only a fresh session can be restored into"); continue; }
         if (ss[i]->greedy.lm()) { refuse(i, "the target session has a language model: a snapshot does not carry the model's node"); continue; }
+        if (ss[i]->quality.on) { refuse(i, "the target session has the line-quality observer on: a snapshot does not carry its machine"); continue; }
         if (const char *why = parse_for(*ss[i], lay, blobs[i], sizes[i], &parsed[(size_t)i])) refuse(i, why);
     }
     const bool ran = sched->run_on_loop([&] {

@@ -5,7 +5,7 @@
 //
 //   g++ -O2 -std=c++17 examples/serve_many.cpp -I include -L april_asr_amd -laprilasr -Wl,-rpath,$PWD/april_asr_amd -o serve_many
 //   ./serve_many model.april audio.raw [sessions=64] [mode=pipelined|lockstep] [input_rate] [--alternatives K] [--bias FILE [--bias-strict]]
-//               [--endpoint-ms N] [--blank-penalty X] [--vad] [--dtmf] [--tones] [--migrate S] [--lm FILE [--lm-weight W]]
+//               [--endpoint-ms N] [--blank-penalty X] [--vad] [--dtmf] [--tones] [--quality] [--migrate S] [--lm FILE [--lm-weight W]]
 //
 // Every session gets the same PCM16 file, rotated by (session index x 0.37 s) so that the streams differ.  With `input_rate` the file
 // is PCM16 at that rate and every session is told so (aprilx_session_set_input_rate): the library converts it to the model's rate on
@@ -30,8 +30,12 @@
 // ends with " dtmf <digits>" ("-" when no key was found).
 // `--tones` (anywhere on the line): every session gets the tone detector with its default options (aprilx_session_set_tones); its line then
 // ends with " tones" and one "<name or f1[+f2]>@<on ms>-<off ms>" per tone ("-" when none was found), the names aprilx_tone_name()'s.
+// `--quality` (anywhere on the line): every session gets the line-quality observer with its default options (aprilx_session_set_quality); its
+// line then ends with " quality rms <dBFS> peak <dBFS> clipped <frames> dropout <seconds>" over the whole stream ("-inf" for digital
+// silence).  A session with the observer cannot be snapshotted: `--quality` with `--migrate` is refused.
 // `--migrate S` (anywhere on the line): after S feeds every stream is snapshotted (aprilx_snapshot_many), freed, and restored into a new
 // session configured the same way (aprilx_restore_many), then the feeds go on: the printed lines equal those of a run without the flag.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -48,7 +52,18 @@ struct Stream {
     size_t vad_segments = 0; uint64_t vad_open_ms = 0, vad_speech_ms = 0;
     std::string dtmf_digits;
     std::string tones; size_t tone_count = 0;
+    uint64_t q_sumsq = 0, q_samples = 0, q_clipped = 0, q_drop_open_ms = 0, q_drop_ms = 0; int q_peak = 0;
 };
+
+static void on_quality(void *ud, const AprilxQualityEvent *e)
+{
+    Stream *s = static_cast<Stream *>(ud);
+    if (e->kind == APRILX_QUALITY_REPORT) {
+        s->q_sumsq += e->sumsq; s->q_samples += (uint64_t)e->frames * e->hop; s->q_clipped += e->clipped_frames;
+        s->q_peak = std::max(s->q_peak, std::max(std::abs(e->min), std::abs(e->max)));
+    } else if (e->kind == APRILX_QUALITY_DROPOUT_ON) s->q_drop_open_ms = e->time_ms;
+    else if (e->kind == APRILX_QUALITY_DROPOUT_OFF) s->q_drop_ms += e->time_ms - s->q_drop_open_ms;
+}
 
 static void on_tone(void *ud, int kind, uint32_t f1_hz, uint32_t f2_hz, uint64_t time_ms)
 {
@@ -99,7 +114,7 @@ int main(int argc, char **argv)
     bool bias_strict = false;
     long endpoint_ms = -1;
     const char *blank_penalty = nullptr;
-    bool vad = false, dtmf = false, tones = false;
+    bool vad = false, dtmf = false, tones = false, quality = false;
     long migrate = -1;
     for (int i = 1; i + 1 < argc; ++i)
         if (!strcmp(argv[i], "--lm") || !strcmp(argv[i], "--lm-weight") || !strcmp(argv[i], "--lm-bonus") || !strcmp(argv[i], "--lm-sessions")) {
@@ -116,6 +131,13 @@ int main(int argc, char **argv)
             migrate = atol(argv[i + 1]);
             for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
             argc -= 2;
+            break;
+        }
+    for (int i = 1; i < argc; ++i)
+        if (!strcmp(argv[i], "--quality")) {
+            quality = true;
+            for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+            argc -= 1;
             break;
         }
     for (int i = 1; i < argc; ++i)
@@ -221,6 +243,7 @@ int main(int argc, char **argv)
         const int dropped = aprilx_bias_info(bias, &states, &edges);
         fprintf(stderr, "bias set%s: %zu phrases (%d left out as unspellable), %d states, %lld token edges\n", bias_strict ? " (strict)" : "", phrases.size(), dropped, states, (long long)edges);
     }
+    if (quality && migrate >= 0) { fprintf(stderr, "--quality and --migrate exclude each other: a snapshot does not carry the observer's machine\n"); return 1; }
     AprilxLm lm = nullptr;
     if (lm_file) {
         if (migrate >= 0) { fprintf(stderr, "--lm and --migrate exclude each other: a snapshot does not carry the language model's node\n"); return 1; }
@@ -271,6 +294,10 @@ int main(int argc, char **argv)
             AprilxToneOptions topt = {(uint32_t)sizeof topt, -40.0f, 10.0f, 0.7f, 20u, 60u, 30u, 0u};
             if (aprilx_session_set_tones(sessions[(size_t)i], &topt, on_tone, &streams[(size_t)i]) != 0) { fprintf(stderr, "tone options refused\n"); return 1; }
         }
+        if (quality) {
+            AprilxQualityOptions qopt = {(uint32_t)sizeof qopt, 0u, 32767u, 3u, 1000u, 200u, 1000u};
+            if (aprilx_session_set_quality(sessions[(size_t)i], &qopt, on_quality, &streams[(size_t)i]) != 0) { fprintf(stderr, "quality options refused\n"); return 1; }
+        }
         return 0;
     };
     for (int i = 0; i < n; ++i) {
@@ -312,6 +339,11 @@ int main(int argc, char **argv)
         if (vad) printf(" vad %zu %.2f", s.vad_segments, (double)s.vad_speech_ms * 1e-3);      // (the flush has closed every open segment)
         if (dtmf) printf(" dtmf %s", s.dtmf_digits.empty() ? "-" : s.dtmf_digits.c_str());
         if (tones) printf(" tones%s", s.tones.empty() ? " -" : s.tones.c_str());      // (the flush has closed every held tone)
+        if (quality) {                                 // (the flush has closed the last interval and an open dropout)
+            const double rms = s.q_samples && s.q_sumsq ? 10.0 * std::log10((double)s.q_sumsq / (double)s.q_samples / (32768.0 * 32768.0)) : -INFINITY;
+            const double peak = s.q_peak ? 20.0 * std::log10((double)s.q_peak / 32768.0) : -INFINITY;
+            printf(" quality rms %.1f peak %.1f clipped %llu dropout %.2f", rms, peak, (unsigned long long)s.q_clipped, (double)s.q_drop_ms * 1e-3);
+        }
         printf("\n");
     }
     fprintf(stderr, "%d streams x %.1f s of audio in %.1f ms (%s feed): %.0f audio-seconds per second\n", n, steps * 0.1, ms, pipelined ? "pipelined" : "lock-step",
@@ -344,6 +376,12 @@ int main(int argc, char **argv)
         for (const Stream &s : streams) keys += s.dtmf_digits.size();
         fprintf(stderr, "DTMF: %.3f ms per 100 ms step, %zu keys, %llu launches over %llu frames on device 0\n", ms / (double)steps, keys,
                 (unsigned long long)launches, (unsigned long long)frames);
+    }
+    if (quality) {
+        uint64_t launches = 0, frames = 0; double kms = 0;
+        aprilx_model_quality_stats(model, 0, &launches, &frames, &kms);
+        fprintf(stderr, "quality: %.3f ms per 100 ms step, %llu launches over %llu frames on device 0\n", ms / (double)steps, (unsigned long long)launches,
+                (unsigned long long)frames);
     }
     if (tones) {
         uint64_t launches = 0, frames = 0; double kms = 0; size_t found = 0;

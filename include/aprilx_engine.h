@@ -590,6 +590,88 @@ APRIL_EXPORT int aprilx_run_tone_decide(AprilASRModel model, const AprilxToneOpt
 /* Tone launches and the frames they covered on one GPU's engine, and (while profiling) the kernel's accumulated ms.  0, or -1. */
 APRIL_EXPORT int aprilx_model_tone_stats(AprilASRModel model, int device_index, uint64_t *launches, uint64_t *frames, double *ms);
 
+/* ---- Line quality.  Why is this stream's transcript bad?  Usually the signal: a caller 30 dB too quiet, a gateway
+ * that clips, a one-way leg (digital silence, or a stuck value a concealer filled in), a large DC offset, a noise floor a few dB under the
+ * speech.  A session that opts in gets periodic REPORTs and CLIPPING / DROPOUT ON / OFF events from an observer that runs on the GPU, on
+ * the model-rate int16 samples the filterbank reads -- which the host never sees for a stream that feeds mu-law at 8 kHz.  Real frame t
+ * owns the hop x[0 .. H), the first H = frame_shift_ms * rate / 1000 samples of its frame: hops do not overlap, sums over frames are sums
+ * over the audio.  Per frame the device writes one record of eight little-endian uint32, integers only: sumsq (64 bits, low word
+ * first), sum (int32), (uint16)min | (uint16)max << 16, clip_count | clip_run << 16 (samples with x >= L or x <= -L, and the longest
+ * run of consecutive such samples INSIDE the hop; L the session's clip level), 1 if min == max (a dead frame) else 0, and two zero
+ * words.  The host turns consecutive records into events:
+ *   CLIPPING  a frame is clipped when clip_run >= clip_run_min.  ON at the first clipped frame (time t * shift); OFF once
+ *             clip_hold_ms / shift consecutive unclipped frames have passed, at the time of the first of them.
+ *   DROPOUT   ON once dropout_ms / shift consecutive dead frames have passed, at the time of the first of them; OFF at the first live frame.
+ *   REPORT    one per report_ms / shift frames, from frame 0 of the options' life, at the time of its first frame, with the sums below.
+ * A frame's events come in that order.  A flush that completes closes whatever is on with an OFF at frames_seen * frame_shift, then the
+ * open interval with a short REPORT, and resets the machine.  Levels in dB are derived from the integers by the caller
+ * (rms_dbfs = 10 log10(sumsq / (frames * hop) / 32768^2)).  The figures describe the MODEL-RATE stream: clipping in a source at another
+ * rate is smeared by the resampler; a G.711 line never reaches 32767 -- set clip_level 32124 for mu-law, 32256 for A-law.  Runs are not
+ * followed across a hop boundary.  loud_sumsq / quiet_sumsq is a loudest-to-quietest-frame ratio inside one interval, not a speech SNR.
+ * The feature only observes, as the detectors do, and an engine none of whose sessions has opted in launches, copies and allocates
+ * nothing new.  Times are on the FRAME clock of the voice-activity events; delivery follows their rules. */
+typedef struct AprilxQualityOptions {
+    uint32_t size;                      /* sizeof(AprilxQualityOptions) */
+    uint32_t flags;                     /* 0 */
+    uint32_t clip_level;                /* 32767: 1024..32767; a sample is clipped when x >= clip_level or x <= -clip_level */
+    uint32_t clip_run_min;              /* 3: 1..64; a frame is clipped when its longest run has at least this many samples */
+    uint32_t clip_hold_ms;              /* 1000: 100..60000 */
+    uint32_t dropout_ms;                /* 200: 20..60000 */
+    uint32_t report_ms;                 /* 1000: 0 (no reports) or 100..60000 */
+} AprilxQualityOptions;
+enum { APRILX_QUALITY_REPORT = 1, APRILX_QUALITY_CLIPPING_ON = 2, APRILX_QUALITY_CLIPPING_OFF = 3, APRILX_QUALITY_DROPOUT_ON = 4, APRILX_QUALITY_DROPOUT_OFF = 5 };
+/* one event (80 bytes); the fields behind time_ms are a REPORT's and zero otherwise */
+typedef struct AprilxQualityEvent {
+    int32_t kind;
+    uint32_t frames;                    /* frames of the interval */
+    uint64_t time_ms;
+    int64_t sum;                        /* of all samples of the interval */
+    uint64_t sumsq;
+    int32_t min, max;
+    uint64_t clip_samples;
+    uint32_t clipped_frames, dead_frames;
+    uint64_t quiet_sumsq, loud_sumsq;   /* the smallest frame sumsq among the interval's live frames (0: none), the largest of all its frames */
+    uint32_t hop, reserved;             /* samples per frame (every event carries it) */
+} AprilxQualityEvent;
+/* the event is valid during the call only */
+typedef void (*AprilxQualityHandler)(void *userdata, const AprilxQualityEvent *event);
+typedef struct AprilxQualityInfo {
+    int32_t hop, hold_frames, dropout_frames, report_frames;
+    uint32_t clipping, dropout;         /* what is on after the last frame read */
+    uint64_t frames_seen;               /* real frames of the session since its creation */
+    uint64_t frames, clipped_frames, dead_frames, clip_samples, reports;      /* since the observer was last set */
+} AprilxQualityInfo;
+/* what kernel and machine work from (24 bytes); tests and users of aprilx_quality_events_host */
+typedef struct AprilxQualityPlan { int32_t hop, clip_level, clip_run_min, hold_frames, dropout_frames, report_frames; } AprilxQualityPlan;
+/* the machine's state between calls of aprilx_quality_events_host (88 bytes): all zero at the start and after a flush */
+typedef struct AprilxQualityMachine {
+    int32_t clipping, dropout, quiet_run, dead_run; uint32_t frames; int32_t have_live; uint64_t first_frame; int64_t sum; uint64_t sumsq;
+    int32_t min, max; uint64_t clip_samples; uint32_t clipped_frames, dead_frames; uint64_t quiet_sumsq, loud_sumsq;
+} AprilxQualityMachine;
+/* options = NULL: off.  0, or -1 and nothing changes: a wrong size, a value out of range, non-zero flags, a NULL handler with options, a
+ * model whose hop is longer than its frame or than 32767 samples, or a session with audio fed since its last completed flush (the rule
+ * of aprilx_session_set_input_rate).  Setting resets the machine and its counters.  A session with the observer on is refused by
+ * aprilx_session_snapshot and as a target of aprilx_session_restore: the snapshot format does not carry the machine. */
+APRIL_EXPORT int aprilx_session_set_quality(AprilASRSession session, const AprilxQualityOptions *options, AprilxQualityHandler handler, void *userdata);
+/* 1 and the options / info when the observer is on, 0 (info: frames_seen only) when it is off, -1 on bad arguments; either pointer may
+ * be NULL.  Waits for the session to be idle. */
+APRIL_EXPORT int aprilx_session_quality(AprilASRSession session, AprilxQualityOptions *options_out, AprilxQualityInfo *out);
+/* The plan of a model with this rate, frame length (samples the filterbank reads per frame) and frame shift: 0, or -1 as above.  No GPU. */
+APRIL_EXPORT int aprilx_quality_plan(int sample_rate, int frame_samples, int frame_shift_ms, const AprilxQualityOptions *options, AprilxQualityPlan *plan_out);
+/* The records on the host: hop i is the first `hop` samples at frames + i * ld (ld >= hop); records_out [n][8] uint32.  hop 1..32767,
+ * clip_level 1024..32767.  0, or -1.  No GPU. */
+APRIL_EXPORT int aprilx_quality_host(int hop, int clip_level, int n, const int16_t *frames, size_t ld, uint32_t *records_out);
+/* Events from the records ([n][8] uint32) of frames [t0, t0 + n) from *machine: events_out (cap entries) receives them in order;
+ * flush != 0: a flush then completes at frame t0 + n.  Returns their number (may exceed cap: nothing is written past it), or -1.  No GPU. */
+APRIL_EXPORT int aprilx_quality_events_host(const AprilxQualityPlan *plan, int frame_shift_ms, uint64_t t0, const uint32_t *records, size_t n, int flush,
+                                            AprilxQualityMachine *machine, AprilxQualityEvent *events_out, int cap);
+/* Tests only: quality_kernel on n_runs runs in ONE launch.  Run r has its own clip level and n[r] frames, consecutive in
+ * frames[sum n][fft_size] as for aprilx_run_fbank; records_out [sum n][8].  0, or -1 on bad arguments. */
+APRIL_EXPORT int aprilx_run_quality(AprilASRModel model, const int32_t *clip_levels, int n_runs, const int32_t *n, const int16_t *frames, uint32_t *records_out);
+/* Quality launches and the frames they covered on one GPU's engine, and (while profiling) the kernel's accumulated ms: all zero in an
+ * engine without an opted-in session.  0, or -1. */
+APRIL_EXPORT int aprilx_model_quality_stats(AprilASRModel model, int device_index, uint64_t *launches, uint64_t *frames, double *ms);
+
 /* ---- session snapshot and restore.  A stream is otherwise pinned to the slot, engine and process that created
  * it.  A snapshot is a self-contained blob of everything dynamic a session holds at an IDLE point -- the slot's recurrent state, the
  * encoder / decoder outputs, the search and trie state, the detectors' state, the feature-ring rows not yet consumed, the host's result
