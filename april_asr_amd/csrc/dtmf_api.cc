@@ -141,7 +141,7 @@ int aprilx_model_dtmf_stats(AprilASRModel model, int device_index, uint64_t *lau
 {
     if (!model || device_index < 0 || device_index >= (int)model->m.engines.size() || !launches || !frames || !ms) return -1;
     const Engine *e = model->m.engines[(size_t)device_index];
-    e->dtmf_counts(launches, frames);
+    e->observer_counts(OBS_DTMF, launches, frames);
     *ms = e->timing(Engine::T_DTMF).ms;
     return 0;
 }

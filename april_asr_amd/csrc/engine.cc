@@ -709,26 +709,36 @@ void Engine::collect_timing()
 }
 
 // ---------------------------------------------------------------- fbank
+// bytes per descriptor of the staged arrays; the observers' arrays follow the block's order (staging_layout.h, pass_layout.h)
+static_assert(ST_VD + OBS_DTMF == ST_DT && ST_VD + OBS_TONE == ST_TN && ST_VD + OBS_QUALITY == ST_QA && ST_VD + OBS_COUNT == ST_COUNT, "observer o stages array ST_VD + o");
+static const StagingSizes kStagingEl = [] {
+    StagingSizes el{};
+    el[ST_FRAMES] = sizeof(FbankFrameDesc); el[ST_RS] = sizeof(ResampleDesc); el[ST_DC] = sizeof(DecodeDesc);
+    el[ST_VD] = sizeof(VadDesc); el[ST_DT] = sizeof(DtmfDesc); el[ST_TN] = sizeof(ToneDesc); el[ST_QA] = sizeof(QualityDesc);
+    return el;
+}();
+
 const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<const int16_t *, size_t> *parts, size_t n_parts, size_t n_pcm, HostPool *pool,
                              const FrontPass &pass)
 {
     if (n_frames <= 0) return nullptr;
-    const int n_rs = std::max(pass.n_rs, 0), n_dc = std::max(pass.n_dc, 0), n_vd = std::max(pass.n_vd, 0), n_dt = std::max(pass.n_dt, 0);
-    const int n_tn = std::max(pass.n_tn, 0), n_qa = std::max(pass.n_qa, 0);
+    const int n_rs = std::max(pass.n_rs, 0), n_dc = std::max(pass.n_dc, 0);
     ResampleDesc *rs = pass.rs;
     const DecodeDesc *dc = pass.dc;
-    const size_t n_in_parts = n_rs ? pass.n_in_parts : 0, n_raw_parts = n_dc ? pass.n_raw_parts : 0, vd_frames = n_vd ? pass.vad_bytes : 0;
-    const size_t dt_frames = n_dt ? pass.dtmf_bytes : 0;
-    // the pass's bytes: VAD, then DTMF, then (4-byte aligned) the tone records
-    const size_t tn_at = (vd_frames + dt_frames + 3) / 4 * 4, tn_frames = n_tn ? pass.tone_bytes / 4 : 0, tn_end = n_tn ? tn_at + tn_frames * 4 : vd_frames + dt_frames;
-    // ... then (16-byte aligned) the quality records
-    const size_t qa_at = FrontPass::quality_at_of(vd_frames, dt_frames, tn_frames * 4), qa_frames = n_qa ? pass.quality_bytes / (kQualityWords * 4) : 0;
-    const size_t out_bytes = n_qa ? qa_at + qa_frames * kQualityWords * 4 : tn_end;
+    const size_t n_in_parts = n_rs ? pass.n_in_parts : 0, n_raw_parts = n_dc ? pass.n_raw_parts : 0;
+    // the observers: descriptors and frames per observer, and where their records go (pass_layout.h)
+    int n_obs[OBS_COUNT]; PassFrames obs_frames; bool observed = false;
+    for (int o = 0; o < OBS_COUNT; ++o) {
+        n_obs[o] = std::max(pass.obs[o].n, 0); obs_frames[(size_t)o] = n_obs[o] ? pass.obs[o].frames : 0;
+        observed = observed || n_obs[o];
+    }
+    const int n_vd = n_obs[OBS_VAD], n_dt = n_obs[OBS_DTMF], n_tn = n_obs[OBS_TONE], n_qa = n_obs[OBS_QUALITY];
+    const PassLayout out = pass_layout(obs_frames);
     StagingCounts cnt;
     cnt.n_pcm = n_pcm; cnt.n_in = n_rs ? pass.n_in : 0; cnt.n_raw = n_dc ? pass.n_raw : 0;
-    cnt.n_frames = (size_t)n_frames; cnt.n_rs = (size_t)n_rs; cnt.n_dc = (size_t)n_dc; cnt.n_vd = (size_t)n_vd; cnt.n_dt = (size_t)n_dt; cnt.n_tn = (size_t)n_tn; cnt.n_qa = (size_t)n_qa;
-    const StagingSizes el{sizeof(FbankFrameDesc), sizeof(ResampleDesc), sizeof(DecodeDesc), sizeof(VadDesc), sizeof(DtmfDesc), sizeof(ToneDesc), sizeof(QualityDesc)};
-    const StagingLayout lay = staging_layout(cnt, el);
+    cnt.n[ST_FRAMES] = (size_t)n_frames; cnt.n[ST_RS] = (size_t)n_rs; cnt.n[ST_DC] = (size_t)n_dc;
+    for (int o = 0; o < OBS_COUNT; ++o) cnt.n[(size_t)(ST_VD + o)] = (size_t)n_obs[o];
+    const StagingLayout lay = staging_layout(cnt, kStagingEl);
     HIP_CHECK(hipSetDevice(cfg_.device));
     for (int i = 0; i < n_rs; ++i) rs[i].taps = resample_table(pass.rs_specs[i]);      // (uploaded at a conversion's first use)
     if (!fb_caps_.holds(cnt, lay)) {
@@ -736,7 +746,7 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
         HipLegacyLock regrow_guard;                   // (frees imply a device synchronisation: not beside another engine's capture; order: capture_mu_, then this)
         for (int b = 0; b < 2; ++b) if (hs_pcm_[b]) { (void)hipHostFree(hs_pcm_[b]); (void)hipFree(ds_pcm_[b]); }
         fb_caps_.grow(cnt, lay);
-        const size_t units = fb_caps_.units(el);
+        const size_t units = fb_caps_.units(kStagingEl);
         for (int b = 0; b < 2; ++b) {
             hs_pcm_[b] = hmalloc<int16_t>(units); ds_pcm_[b] = dmalloc<int16_t>(units);
             if (!fb_done_[b]) HIP_CHECK(hipEventCreateWithFlags(&fb_done_[b], hipEventDisableTiming));
@@ -745,22 +755,21 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
     PassBlock *block = nullptr;
     const float *dt_tables = n_dt ? dtmf_tables() : nullptr;      // (sets dt_wd_)
     const float *tn_tables = n_tn ? tone_tables() : nullptr;      // (sets tn_w_, tn_f_)
-    if (n_vd || n_dt || n_tn || n_qa) {
-        // a pass with VAD, DTMF, tone or quality descriptors: the first VAD pass of the engine allocates the per-slot records; the device's byte buffer
-        // (the pass's VAD bytes, then its DTMF bytes, then its tone records, then its quality records) grows behind a sync (earlier passes' copies read it); a pass takes a pinned block
-        // nobody holds, or a new one (warm-up only)
+    if (observed) {
+        // a pass with observers' descriptors: the first VAD pass of the engine allocates the per-slot records; the device's block grows
+        // behind a sync (earlier passes' copies read it); a pass takes a pinned block nobody holds, or a new one (warm-up only)
         if (n_vd && !vad_state_d_) vad_state_d_ = dmalloc<VadState>((size_t)cfg_.max_slots);
-        if (out_bytes > pass_out_cap_) {
+        if (out.bytes > pass_out_cap_) {
             sync();
             HipLegacyLock guard;
             if (pass_out_d_) (void)hipFree(pass_out_d_);
-            pass_out_cap_ = std::max<size_t>(out_bytes * 2, 4096);
+            pass_out_cap_ = std::max<size_t>(out.bytes * 2, 4096);
             pass_out_d_ = dmalloc<uint8_t>(pass_out_cap_);
         }
-        for (PassBlock &k : pass_blocks_) if (!k.busy && k.cap >= out_bytes && (!block || k.cap < block->cap)) block = &k;
+        for (PassBlock &k : pass_blocks_) if (!k.busy && k.cap >= out.bytes && (!block || k.cap < block->cap)) block = &k;
         if (!block) {
             PassBlock k;
-            k.cap = 4096; while (k.cap < out_bytes) k.cap *= 2;
+            k.cap = 4096; while (k.cap < out.bytes) k.cap *= 2;
             k.h = hmalloc<uint8_t>(k.cap);
             pass_blocks_.push_back(k);
             block = &pass_blocks_.back();
@@ -770,55 +779,41 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
     const int b = fb_flip_;
     fb_flip_ ^= 1;
     HIP_CHECK(hipEventSynchronize(fb_done_[b]));          // the launch that used this pair two calls ago has consumed it
-    const size_t woff = lay.raw, doff = lay.frames, roff = lay.rs, coff = lay.dc, voff = lay.vd, toff = lay.dt, noff = lay.tn, qoff = lay.qa, bytes = lay.bytes;      // (staging_layout.h)
+    const size_t woff = lay.raw, doff = lay.off[ST_FRAMES], roff = lay.off[ST_RS], coff = lay.off[ST_DC], voff = lay.off[ST_VD], bytes = lay.bytes;      // (staging_layout.h)
     char *hs = reinterpret_cast<char *>(hs_pcm_[b]);
+    const char *dev = reinterpret_cast<const char *>(ds_pcm_[b]);
     memcpy(hs + doff, desc, (size_t)n_frames * sizeof(FbankFrameDesc));
-    if (n_vd) memcpy(hs + voff, pass.vd, (size_t)n_vd * sizeof(VadDesc));
+    if (n_vd) memcpy(hs + voff, pass.descs<VadDesc>(), (size_t)n_vd * sizeof(VadDesc));
+    // The runs of an observer that reads staged samples (DTMF, tones, line quality): its descriptors go into the staging buffer; every run
+    // lies inside the frames of this call and inside the observer's part of the block, `ok` holds for it and no padding row is among its
+    // frames (else abort); then what the observers' args share -- samples, frame descriptors, descriptors, max_n, the part of the block
+    auto stage_runs = [&](auto &a, const char *what, auto ok) {
+        typedef std::remove_cv_t<std::remove_pointer_t<decltype(a.desc)>> Desc;
+        const Observer o = FrontPass::observer_of(a.desc);
+        const Desc *runs = pass.descs<Desc>();
+        const size_t at = lay.off[(size_t)(ST_VD + o)];
+        memcpy(hs + at, runs, (size_t)n_obs[o] * sizeof(Desc));
+        for (int i = 0; i < n_obs[o]; ++i) {
+            const Desc &t = runs[i];
+            if (t.n <= 0 || t.first < 0 || t.first + t.n > n_frames || t.out_off < 0 || (size_t)t.out_off + (size_t)t.n > obs_frames[(size_t)o] || !ok(t)) {
+                LOGE("fbank: %s descriptor %d outside the pass", what, i); abort();
+            }
+            for (int k = 0; k < t.n; ++k) if (desc[t.first + k].pcm_off < 0) { LOGE("fbank: a padding row inside %s run %d", what, i); abort(); }
+            a.max_n = std::max(a.max_n, t.n);
+        }
+        a.pcm = ds_pcm_[b]; a.frames = reinterpret_cast<const FbankFrameDesc *>(dev + doff);
+        a.desc = reinterpret_cast<const Desc *>(dev + at); a.n_desc = n_obs[o];
+        a.out = reinterpret_cast<decltype(a.out)>(pass_out_d_ + out.at[o]);
+    };
     DtmfArgs ta;
-    if (n_dt) {
-        memcpy(hs + toff, pass.dt, (size_t)n_dt * sizeof(DtmfDesc));
-        for (int i = 0; i < n_dt; ++i) {
-            const DtmfDesc &t = pass.dt[i];
-            if (t.n <= 0 || t.first < 0 || t.first + t.n > n_frames || t.out_off < 0 || (size_t)t.out_off + (size_t)t.n > dt_frames || t.plan.Wd != dt_wd_) {
-                LOGE("fbank: DTMF descriptor %d outside the pass", i); abort();
-            }
-            for (int k = 0; k < t.n; ++k) if (desc[t.first + k].pcm_off < 0) { LOGE("fbank: a padding row inside DTMF run %d", i); abort(); }
-            ta.max_n = std::max(ta.max_n, t.n);
-        }
-        const char *dev = reinterpret_cast<const char *>(ds_pcm_[b]);
-        ta.pcm = ds_pcm_[b]; ta.frames = reinterpret_cast<const FbankFrameDesc *>(dev + doff); ta.out = pass_out_d_ + vd_frames;
-        ta.desc = reinterpret_cast<const DtmfDesc *>(dev + toff); ta.n_desc = n_dt; ta.tables = dt_tables; ta.wd = dt_wd_;
-    }
+    if (n_dt) { stage_runs(ta, "DTMF", [&](const DtmfDesc &t) { return t.plan.Wd == dt_wd_; }); ta.tables = dt_tables; ta.wd = dt_wd_; }
     ToneArgs na;
-    if (n_tn) {
-        memcpy(hs + noff, pass.tn, (size_t)n_tn * sizeof(ToneDesc));
-        for (int i = 0; i < n_tn; ++i) {
-            const ToneDesc &t = pass.tn[i];
-            if (t.n <= 0 || t.first < 0 || t.first + t.n > n_frames || t.out_off < 0 || (size_t)t.out_off + (size_t)t.n > tn_frames || t.plan.W != tn_w_ || t.plan.F != tn_f_) {
-                LOGE("fbank: tone descriptor %d outside the pass", i); abort();
-            }
-            for (int k = 0; k < t.n; ++k) if (desc[t.first + k].pcm_off < 0) { LOGE("fbank: a padding row inside tone run %d", i); abort(); }
-            na.max_n = std::max(na.max_n, t.n);
-        }
-        const char *dev = reinterpret_cast<const char *>(ds_pcm_[b]);
-        na.pcm = ds_pcm_[b]; na.frames = reinterpret_cast<const FbankFrameDesc *>(dev + doff); na.out = reinterpret_cast<uint32_t *>(pass_out_d_ + tn_at);
-        na.desc = reinterpret_cast<const ToneDesc *>(dev + noff); na.n_desc = n_tn; na.tables = tn_tables; na.w = tn_w_; na.f = tn_f_;
-    }
+    if (n_tn) { stage_runs(na, "tone", [&](const ToneDesc &t) { return t.plan.W == tn_w_ && t.plan.F == tn_f_; }); na.tables = tn_tables; na.w = tn_w_; na.f = tn_f_; }
     QualityArgs qa;
     if (n_qa) {
-        memcpy(hs + qoff, pass.qa, (size_t)n_qa * sizeof(QualityDesc));
         if (pass.quality_hop <= 0 || pass.quality_hop > ft_.padded) { LOGE("fbank: a quality hop of %d samples is not inside the frame", pass.quality_hop); abort(); }
-        for (int i = 0; i < n_qa; ++i) {
-            const QualityDesc &t = pass.qa[i];
-            if (t.n <= 0 || t.first < 0 || t.first + t.n > n_frames || t.out_off < 0 || (size_t)t.out_off + (size_t)t.n > qa_frames) {
-                LOGE("fbank: quality descriptor %d outside the pass", i); abort();
-            }
-            for (int k = 0; k < t.n; ++k) if (desc[t.first + k].pcm_off < 0) { LOGE("fbank: a padding row inside quality run %d", i); abort(); }
-            qa.max_n = std::max(qa.max_n, t.n);
-        }
-        const char *dev = reinterpret_cast<const char *>(ds_pcm_[b]);
-        qa.pcm = ds_pcm_[b]; qa.frames = reinterpret_cast<const FbankFrameDesc *>(dev + doff); qa.out = reinterpret_cast<uint32_t *>(pass_out_d_ + qa_at);
-        qa.desc = reinterpret_cast<const QualityDesc *>(dev + qoff); qa.n_desc = n_qa; qa.hop = pass.quality_hop;
+        stage_runs(qa, "quality", [](const QualityDesc &) { return true; });
+        qa.hop = pass.quality_hop;
     }
     ResampleArgs ra;
     if (n_rs) {
@@ -867,44 +862,35 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
     if (m_unseen_by_f_) { join(f_stream_, stream_); m_unseen_by_f_ = false; }      // (general-path work may still read ring rows this call overwrites)
     HIP_CHECK(hipMemcpyAsync(ds_pcm_[b], hs_pcm_[b], bytes, hipMemcpyHostToDevice, f_stream_));
     FbankArgs a;
-    a.t = ft_; a.pcm = ds_pcm_[b]; a.desc = reinterpret_cast<const FbankFrameDesc *>(reinterpret_cast<const char *>(ds_pcm_[b]) + doff); a.n_frames = n_frames; a.ring = ring_; a.ring_frames = ring_frames_; a.pad_value = pad_value_;
-    if (n_rs) { ra.in = ds_pcm_[b]; ra.out = ds_pcm_[b]; ra.desc = reinterpret_cast<const ResampleDesc *>(reinterpret_cast<const char *>(ds_pcm_[b]) + roff); }
+    a.t = ft_; a.pcm = ds_pcm_[b]; a.desc = reinterpret_cast<const FbankFrameDesc *>(dev + doff); a.n_frames = n_frames; a.ring = ring_; a.ring_frames = ring_frames_; a.pad_value = pad_value_;
+    if (n_rs) { ra.in = ds_pcm_[b]; ra.out = ds_pcm_[b]; ra.desc = reinterpret_cast<const ResampleDesc *>(dev + roff); }
     if (n_dc) {
         da.raw = reinterpret_cast<const uint8_t *>(ds_pcm_[b]) + woff; da.out = ds_pcm_[b];
-        da.desc = reinterpret_cast<const DecodeDesc *>(reinterpret_cast<const char *>(ds_pcm_[b]) + coff);
+        da.desc = reinterpret_cast<const DecodeDesc *>(dev + coff);
     }
     VadArgs va;
     if (n_vd) {
-        va.ring = ring_; va.ring_frames = ring_frames_; va.nbins = ft_.nbins; va.state = vad_state_d_; va.out = pass_out_d_;
-        va.desc = reinterpret_cast<const VadDesc *>(reinterpret_cast<const char *>(ds_pcm_[b]) + voff); va.n_desc = n_vd;
+        va.ring = ring_; va.ring_frames = ring_frames_; va.nbins = ft_.nbins; va.state = vad_state_d_; va.out = pass_out_d_ + out.at[OBS_VAD];
+        va.desc = reinterpret_cast<const VadDesc *>(dev + voff); va.n_desc = n_vd;
     }
-    if (profiling_) {        // (the per-class hipEvents live on M: a profiled fbank runs there, behind its upload)
-        m_touched();
-        join(stream_, f_stream_);
-        if (n_dc) { timed_begin(T_DECODE); launch_decode(da, stream_); timed_end(T_DECODE); }      // (decode feeds both)
-        if (n_rs) { timed_begin(T_RESAMPLE); launch_resample(ra, stream_); timed_end(T_RESAMPLE); }
-        if (n_dt) { timed_begin(T_DTMF); launch_dtmf(ta, stream_); timed_end(T_DTMF); }
-        if (n_tn) { timed_begin(T_TONE); launch_tone(na, stream_); timed_end(T_TONE); }
-        if (n_qa) { timed_begin(T_QUALITY); launch_quality(qa, stream_); timed_end(T_QUALITY); }
-        timed_begin(T_FBANK); launch_fbank(a, stream_); timed_end(T_FBANK);
-        if (n_vd) { timed_begin(T_VAD); launch_vad(va, stream_); timed_end(T_VAD); }
-        join(f_stream_, stream_);
-    } else {
-        if (n_dc) launch_decode(da, f_stream_);
-        if (n_rs) launch_resample(ra, f_stream_);
-        if (n_dt) launch_dtmf(ta, f_stream_);          // (reads the samples fbank_kernel reads; the staging pair is recycled after fb_done_)
-        if (n_tn) launch_tone(na, f_stream_);          // (likewise)
-        if (n_qa) launch_quality(qa, f_stream_);       // (likewise)
-        launch_fbank(a, f_stream_);
-        if (n_vd) launch_vad(va, f_stream_);
-    }
-    if (n_vd || n_dt || n_tn || n_qa) {       // the pass's bytes -> its pinned block, in front of fb_done_; read after the flight's wait (close_flight)
-        HIP_CHECK(hipMemcpyAsync(block->h, pass_out_d_, out_bytes, hipMemcpyDeviceToHost, f_stream_));
+    // The launches, in stream order.  A profiled pass runs on M, behind its upload, each launch between the hipEvents of its class (they live on M).
+    const bool timed = profiling_;
+    const hipStream_t st = timed ? stream_ : f_stream_;
+    if (timed) { m_touched(); join(stream_, f_stream_); }
+    auto run = [&](int cls, auto launch) { if (timed) timed_begin(cls); launch(); if (timed) timed_end(cls); };
+    if (n_dc) run(T_DECODE, [&] { launch_decode(da, st); });            // (decode feeds both)
+    if (n_rs) run(T_RESAMPLE, [&] { launch_resample(ra, st); });
+    if (n_dt) run(T_DTMF, [&] { launch_dtmf(ta, st); });                // (reads the samples fbank_kernel reads; the staging pair is recycled after fb_done_)
+    if (n_tn) run(T_TONE, [&] { launch_tone(na, st); });                // (likewise)
+    if (n_qa) run(T_QUALITY, [&] { launch_quality(qa, st); });          // (likewise)
+    run(T_FBANK, [&] { launch_fbank(a, st); });
+    if (n_vd) run(T_VAD, [&] { launch_vad(va, st); });
+    if (timed) join(f_stream_, stream_);
+    if (observed) {       // the pass's block -> its pinned block, in front of fb_done_; read after the flight's wait (close_flight)
+        HIP_CHECK(hipMemcpyAsync(block->h, pass_out_d_, out.bytes, hipMemcpyDeviceToHost, f_stream_));
         pass_bytes_flight_ = true;
-        if (n_vd) { vad_launches_.fetch_add(1, std::memory_order_relaxed); vad_frames_.fetch_add(vd_frames, std::memory_order_relaxed); }
-        if (n_dt) { dt_launches_.fetch_add(1, std::memory_order_relaxed); dt_frames_.fetch_add(dt_frames, std::memory_order_relaxed); }
-        if (n_tn) { tn_launches_.fetch_add(1, std::memory_order_relaxed); tn_frames_.fetch_add(tn_frames, std::memory_order_relaxed); }
-        if (n_qa) { qa_launches_.fetch_add(1, std::memory_order_relaxed); qa_frames_.fetch_add(qa_frames, std::memory_order_relaxed); }
+        for (int o = 0; o < OBS_COUNT; ++o)
+            if (n_obs[o]) { obs_counts_[o].launches.fetch_add(1, std::memory_order_relaxed); obs_counts_[o].frames.fetch_add(obs_frames[(size_t)o], std::memory_order_relaxed); }
     }
     HIP_CHECK(hipEventRecord(fb_done_[b], f_stream_));       // no host wait here: the encoder launches queue right behind
     f_unseen_by_m_ = true;
@@ -912,6 +898,17 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
 }
 
 void Engine::release_pass_block(const uint8_t *p) { for (PassBlock &b : pass_blocks_) if (b.h == p) b.busy = false; }
+
+// a table's upload: allocated, copied under the legacy lock, freed with table_allocs_ (rs_mu_ held by the caller)
+const float *Engine::upload_table(const std::vector<float> &t)
+{
+    HIP_CHECK(hipSetDevice(cfg_.device));
+    float *d = dmalloc<float>(t.size());
+    HipLegacyLock legacy;
+    if (!t.empty()) HIP_CHECK(hipMemcpy(d, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    table_allocs_.push_back(d);
+    return d;
+}
 
 // the DTMF tables of this engine's model (dtmf.h), uploaded at the first DTMF pass or debug call
 const float *Engine::dtmf_tables()
@@ -922,15 +919,8 @@ const float *Engine::dtmf_tables()
     if (!wd) { LOGE("DTMF on a model it refuses"); abort(); }
     std::vector<float> t((size_t)kDtmfRows * (size_t)wd);
     dtmf_make_tables(P_.sample_rate, wd, t.data());
-    HIP_CHECK(hipSetDevice(cfg_.device));
-    float *d = dmalloc<float>(t.size());
-    {
-        HipLegacyLock legacy;
-        HIP_CHECK(hipMemcpy(d, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
-        table_allocs_.push_back(d);
-    }
-    dt_wd_ = wd; dt_tables_ = d;
-    return d;
+    dt_wd_ = wd; dt_tables_ = upload_table(t);
+    return dt_tables_;
 }
 
 // the tone tables of this engine's model (tone.h), uploaded at the first tone pass or debug call
@@ -942,15 +932,8 @@ const float *Engine::tone_tables()
     if (!tone_grid(P_.sample_rate, ft_.padded, &w, &k_lo, &f)) { LOGE("tones on a model the detector refuses"); abort(); }
     std::vector<float> t((size_t)2 * (size_t)f * (size_t)w);
     tone_make_tables(w, k_lo, f, t.data());
-    HIP_CHECK(hipSetDevice(cfg_.device));
-    float *d = dmalloc<float>(t.size());
-    {
-        HipLegacyLock legacy;
-        HIP_CHECK(hipMemcpy(d, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
-        table_allocs_.push_back(d);
-    }
-    tn_w_ = w; tn_f_ = f; tn_tables_ = d;
-    return d;
+    tn_w_ = w; tn_f_ = f; tn_tables_ = upload_table(t);
+    return tn_tables_;
 }
 
 const float *Engine::resample_table(const ResampleSpec *spec)
@@ -958,15 +941,7 @@ const float *Engine::resample_table(const ResampleSpec *spec)
     std::lock_guard<std::mutex> g(rs_mu_);
     auto it = rs_tables_.find(spec);
     if (it != rs_tables_.end()) return it->second;
-    HIP_CHECK(hipSetDevice(cfg_.device));
-    float *d = dmalloc<float>(spec->taps.size());
-    {
-        HipLegacyLock legacy;
-        if (!spec->taps.empty()) HIP_CHECK(hipMemcpy(d, spec->taps.data(), spec->taps.size() * sizeof(float), hipMemcpyHostToDevice));
-        table_allocs_.push_back(d);
-    }
-    rs_tables_[spec] = d;
-    return d;
+    return rs_tables_[spec] = upload_table(spec->taps);
 }
 
 // ---------------------------------------------------------------- encoder
@@ -2453,27 +2428,34 @@ void Engine::debug_vad(int n_runs, const VadPlan *plans, const int32_t *n, const
     if (total && energy_out) HIP_CHECK(hipMemcpy(energy_out, en_d, total * sizeof(float), hipMemcpyDeviceToHost));
 }
 
-void Engine::debug_dtmf(int n_runs, const DtmfPlan *plans, const int32_t *n, const int16_t *frames, uint8_t *codes_out, float *powers_out)
+// The scratch staging the debug entry points of the sample-reading observers share: frame i of the call sits at sample i * padded, as in
+// debug_fbank; run r covers the next n[r] frames and writes its records where its frames are.  Fills first / n / out_off of the runs'
+// descriptors (the caller has filled the rest) and the args' samples, frame descriptors, descriptors and max_n; returns the frames in all.
+template <typename Args, typename Desc>
+static size_t debug_stage_runs(Args &a, std::vector<Desc> &desc, const int32_t *n, const int16_t *frames, size_t padded, DeviceScratch &ds)
 {
-    // frame i of the call sits at sample i * padded of a scratch staging buffer, as in debug_fbank
-    const size_t padded = (size_t)ft_.padded;
-    const float *tables = dtmf_tables();
-    std::vector<DtmfDesc> desc((size_t)n_runs);
     size_t total = 0;
-    int max_n = 0;
-    for (int r = 0; r < n_runs; ++r) {
-        DtmfDesc &d = desc[(size_t)r];
-        d.first = (int32_t)total; d.n = n[r]; d.out_off = (int32_t)total; d.plan = plans[r];
-        total += (size_t)n[r]; max_n = std::max(max_n, n[r]);
+    for (size_t r = 0; r < desc.size(); ++r) {
+        desc[r].first = (int32_t)total; desc[r].n = n[r]; desc[r].out_off = (int32_t)total;
+        total += (size_t)n[r]; a.max_n = std::max(a.max_n, n[r]);
     }
     std::vector<FbankFrameDesc> fd(total);
     for (size_t i = 0; i < total; ++i) { fd[i].slot = 0; fd[i].ring_row = 0; fd[i].pcm_off = (int32_t)(i * padded); }
+    a.pcm = ds.upload(frames, total * padded); a.frames = ds.upload(fd.data(), fd.size()); a.desc = ds.upload(desc.data(), desc.size()); a.n_desc = (int)desc.size();
+    return total;
+}
+
+void Engine::debug_dtmf(int n_runs, const DtmfPlan *plans, const int32_t *n, const int16_t *frames, uint8_t *codes_out, float *powers_out)
+{
+    const float *tables = dtmf_tables();
+    std::vector<DtmfDesc> desc((size_t)n_runs);
+    for (int r = 0; r < n_runs; ++r) desc[(size_t)r].plan = plans[r];
     HipLegacyLock legacy;
     HIP_CHECK(hipSetDevice(cfg_.device));
     DeviceScratch ds;
     DtmfArgs a;
-    a.pcm = ds.upload(frames, total * padded); a.frames = ds.upload(fd.data(), fd.size()); a.desc = ds.upload(desc.data(), desc.size()); a.n_desc = n_runs;
-    a.max_n = max_n; a.tables = tables; a.wd = dt_wd_;
+    const size_t total = debug_stage_runs(a, desc, n, frames, (size_t)ft_.padded, ds);
+    a.tables = tables; a.wd = dt_wd_;
     a.out = ds.alloc<uint8_t>(total); a.powers = ds.alloc<float>(total * 9);
     run_on_private_stream([&](hipStream_t st) { launch_dtmf(a, st); });
     HIP_CHECK(hipMemcpy(codes_out, a.out, total, hipMemcpyDeviceToHost));
@@ -2493,26 +2475,16 @@ void Engine::debug_dtmf_decide(const DtmfPlan &plan, int n, const float *powers9
 
 void Engine::debug_tones(int n_runs, const TonePlan *plans, const int32_t *n, const int16_t *frames, uint32_t *records_out, float *powers_out)
 {
-    // frame i of the call sits at sample i * padded of a scratch staging buffer, as in debug_dtmf
-    const size_t padded = (size_t)ft_.padded;
     const float *tables = tone_tables();
     std::vector<ToneDesc> desc((size_t)n_runs);
-    size_t total = 0;
-    int max_n = 0;
-    for (int r = 0; r < n_runs; ++r) {
-        ToneDesc &d = desc[(size_t)r];
-        d.first = (int32_t)total; d.n = n[r]; d.out_off = (int32_t)total; d.plan = plans[r];
-        total += (size_t)n[r]; max_n = std::max(max_n, n[r]);
-    }
-    std::vector<FbankFrameDesc> fd(total);
-    for (size_t i = 0; i < total; ++i) { fd[i].slot = 0; fd[i].ring_row = 0; fd[i].pcm_off = (int32_t)(i * padded); }
+    for (int r = 0; r < n_runs; ++r) desc[(size_t)r].plan = plans[r];
     const size_t row = (size_t)tn_f_ + 1;
     HipLegacyLock legacy;
     HIP_CHECK(hipSetDevice(cfg_.device));
     DeviceScratch ds;
     ToneArgs a;
-    a.pcm = ds.upload(frames, total * padded); a.frames = ds.upload(fd.data(), fd.size()); a.desc = ds.upload(desc.data(), desc.size()); a.n_desc = n_runs;
-    a.max_n = max_n; a.tables = tables; a.w = tn_w_; a.f = tn_f_;
+    const size_t total = debug_stage_runs(a, desc, n, frames, (size_t)ft_.padded, ds);
+    a.tables = tables; a.w = tn_w_; a.f = tn_f_;
     a.out = ds.alloc<uint32_t>(total); a.powers = ds.alloc<float>(total * row);
     run_on_private_stream([&](hipStream_t st) { launch_tone(a, st); });
     HIP_CHECK(hipMemcpy(records_out, a.out, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -2521,25 +2493,15 @@ void Engine::debug_tones(int n_runs, const TonePlan *plans, const int32_t *n, co
 
 void Engine::debug_quality(int hop, int n_runs, const int32_t *clip_levels, const int32_t *n, const int16_t *frames, uint32_t *records_out)
 {
-    // frame i of the call sits at sample i * padded of a scratch staging buffer, as in debug_dtmf
-    const size_t padded = (size_t)ft_.padded;
     if (hop <= 0 || hop > ft_.padded) { LOGE("a quality hop of %d samples is not inside the frame", hop); abort(); }
     std::vector<QualityDesc> desc((size_t)n_runs);
-    size_t total = 0;
-    int max_n = 0;
-    for (int r = 0; r < n_runs; ++r) {
-        QualityDesc &d = desc[(size_t)r];
-        d.first = (int32_t)total; d.n = n[r]; d.out_off = (int32_t)total; d.clip_level = clip_levels[r];
-        total += (size_t)n[r]; max_n = std::max(max_n, n[r]);
-    }
-    std::vector<FbankFrameDesc> fd(total);
-    for (size_t i = 0; i < total; ++i) { fd[i].slot = 0; fd[i].ring_row = 0; fd[i].pcm_off = (int32_t)(i * padded); }
+    for (int r = 0; r < n_runs; ++r) desc[(size_t)r].clip_level = clip_levels[r];
     HipLegacyLock legacy;
     HIP_CHECK(hipSetDevice(cfg_.device));
     DeviceScratch ds;
     QualityArgs a;
-    a.pcm = ds.upload(frames, total * padded); a.frames = ds.upload(fd.data(), fd.size()); a.desc = ds.upload(desc.data(), desc.size()); a.n_desc = n_runs;
-    a.max_n = max_n; a.hop = hop;
+    const size_t total = debug_stage_runs(a, desc, n, frames, (size_t)ft_.padded, ds);
+    a.hop = hop;
     a.out = ds.alloc<uint32_t>(total * kQualityWords);
     run_on_private_stream([&](hipStream_t st) { launch_quality(a, st); });
     HIP_CHECK(hipMemcpy(records_out, a.out, total * kQualityWords * sizeof(uint32_t), hipMemcpyDeviceToHost));

@@ -36,6 +36,7 @@
 #include "ramp_defer.h"
 #include "slot_queue.h"
 #include "staging_layout.h"
+#include "pass_layout.h"
 #include "model_loader.h"
 
 namespace aprilx {
@@ -127,27 +128,19 @@ struct FrontPass {
     // regions that were only reserved, in one decode launch before the resample and the fbank launch.
     int n_dc = 0; const DecodeDesc *dc = nullptr;
     const std::pair<const uint8_t *, size_t> *raw_parts = nullptr; size_t n_raw_parts = 0, n_raw = 0;
-    // The two detectors (DESIGN.md sections 16 and 17) write one byte per real frame of an opted-in session into the block fbank() returns:
-    // the pass's `vad_bytes` VAD bytes, then its `dtmf_bytes` DTMF bytes; a descriptor's out_off counts from the start of its detector's part.
-    // Voice activity: the n_vd descriptors name ring rows; vad_kernel runs right behind the fbank launch.
-    int n_vd = 0; const VadDesc *vd = nullptr; size_t vad_bytes = 0;
-    // DTMF: the n_dt descriptors (`first` indexes the frame descriptors of this call); dtmf_kernel runs behind the resample launch.
-    int n_dt = 0; const DtmfDesc *dt = nullptr; size_t dtmf_bytes = 0;
-    // Tones: the n_tn descriptors (`first` as DTMF's); tone_kernel runs beside dtmf_kernel.  Its records (four bytes
-    // per frame, `tone_bytes` in all) are the third part of the block, at the 4-byte aligned offset tone_at(); out_off counts records.
-    int n_tn = 0; const ToneDesc *tn = nullptr; size_t tone_bytes = 0;
-    size_t tone_at() const { return (vad_bytes + dtmf_bytes + 3) / 4 * 4; }
-    // Line quality: the n_qa descriptors (`first` as DTMF's); quality_kernel runs behind tone_kernel.  Its records
-    // (32 bytes per frame, `quality_bytes` in all) are the fourth part of the block, at the 16-byte aligned offset quality_at(); out_off
-    // counts records.
-    int n_qa = 0; const QualityDesc *qa = nullptr; size_t quality_bytes = 0;
-    int quality_hop = 0;                       // H of the plans behind the descriptors: the model's frame shift in samples
-    static size_t quality_at_of(size_t vad_bytes, size_t dtmf_bytes, size_t tone_bytes)
-    {
-        const size_t end = tone_bytes ? (vad_bytes + dtmf_bytes + 3) / 4 * 4 + tone_bytes : vad_bytes + dtmf_bytes;
-        return (end + 15) / 16 * 16;
-    }
-    size_t quality_at() const { return quality_at_of(vad_bytes, dtmf_bytes, tone_bytes); }
+    // The frame observers (voice activity, DTMF, tones, line quality), indexed by Observer: the descriptors of the
+    // observer's runs and the frames they cover in all.  Each writes one record per frame into its part of the block fbank() returns
+    // (pass_layout.h); a descriptor's out_off counts records from the start of its observer's part.  A VAD descriptor names ring rows:
+    // vad_kernel runs right behind the fbank launch.  The others read staged samples (`first` indexes the frame descriptors of this call):
+    // dtmf_kernel, tone_kernel and quality_kernel run behind the resample launch, in front of the fbank launch.
+    struct Observed { int n = 0; const void *desc = nullptr; size_t frames = 0; } obs[OBS_COUNT];
+    int quality_hop = 0;                       // H of the plans behind the quality descriptors: the model's frame shift in samples
+    static constexpr Observer observer_of(const VadDesc *) { return OBS_VAD; }
+    static constexpr Observer observer_of(const DtmfDesc *) { return OBS_DTMF; }
+    static constexpr Observer observer_of(const ToneDesc *) { return OBS_TONE; }
+    static constexpr Observer observer_of(const QualityDesc *) { return OBS_QUALITY; }
+    template <typename Desc> void observe(const Desc *d, size_t n, size_t frames) { obs[observer_of(d)] = Observed{(int)n, d, frames}; }
+    template <typename Desc> const Desc *descs() const { return static_cast<const Desc *>(obs[observer_of((const Desc *)nullptr)].desc); }
 };
 
 // One call of the decision kernel on GIVEN rows (the parity tests' entry point, Engine::debug_decide): slots 0..n-1, row i = slot i.
@@ -200,8 +193,8 @@ public:
     // chunk steps (encoder + the three joiner/decision/decoder rounds, all on the device) and decoder refreshes are queued
     // back to back, and the host reads the 16-byte-per-round records once, at end_flight().
     // pcm arrives as `n_parts` windows that are gathered straight into pinned staging (total n_pcm samples)
-    // `pass`: the resample / decode / VAD / DTMF / tone / line-quality work of this call.  Returns the pinned block that receives the pass's VAD bytes, behind
-    // them its DTMF bytes, behind those its tone records and behind those its quality records (null: no descriptors of the four): its bytes are complete once the flight that was open during the call
+    // `pass`: the resample / decode work and the frame observers of this call.  Returns the pinned block that receives the observers' records, laid
+    // out by pass_layout.h (null: no descriptors of the four): its bytes are complete once the flight that was open during the call
     // has been waited for (close_flight() puts the copy in front of the flight's event), and the block is lent until
     // release_pass_block().  Stepping thread only.
     const uint8_t *fbank(int n_frames, const FbankFrameDesc *desc, const std::pair<const int16_t *, size_t> *parts, size_t n_parts, size_t n_pcm,
@@ -213,38 +206,20 @@ public:
     }
     // gives back the block a fbank() call lent; the scheduler calls it once per block, when it has read the pass's bytes.  Stepping thread only.
     void release_pass_block(const uint8_t *p);
-    // ---- voice activity.  The counters are inline over plain members: the scheduler harness links session.cc
-    // against an engine of its own.  Nothing is allocated until a pass carries a VAD descriptor.
-    // VAD launches and the frames they covered so far (any thread)
-    void vad_counts(uint64_t *launches, uint64_t *frames) const
+    // ---- the frame observers (DESIGN.md sections 16, 17, 18, 21 and 22).  Launches of one observer's kernel and the frames they covered so far
+    // (any thread; inline over plain members: the scheduler harness links session.cc against an engine of its own).  Nothing is allocated
+    // for an observer until a pass carries one of its descriptors.
+    void observer_counts(int id, uint64_t *launches, uint64_t *frames) const
     {
-        *launches = vad_launches_.load(std::memory_order_relaxed); *frames = vad_frames_.load(std::memory_order_relaxed);
-    }
-    // ---- DTMF.  Launches and the frames they covered so far (any thread); nothing is allocated until a pass
-    // carries a DTMF descriptor.
-    void dtmf_counts(uint64_t *launches, uint64_t *frames) const
-    {
-        *launches = dt_launches_.load(std::memory_order_relaxed); *frames = dt_frames_.load(std::memory_order_relaxed);
+        *launches = obs_counts_[id].launches.load(std::memory_order_relaxed); *frames = obs_counts_[id].frames.load(std::memory_order_relaxed);
     }
     // aprilx_run_dtmf: n_runs runs in ONE launch; run r's n[r] frames (consecutive in `frames`, `padded` samples each) with plans[r].
     // powers_out (may be null): [sum n][9]
     void debug_dtmf(int n_runs, const DtmfPlan *plans, const int32_t *n, const int16_t *frames, uint8_t *codes_out, float *powers_out);
     // aprilx_run_dtmf_decide: the decision alone on n given rows of P[0..8), E
     void debug_dtmf_decide(const DtmfPlan &plan, int n, const float *powers9, uint8_t *codes_out);
-    // ---- tones.  Launches and the frames they covered so far (any thread); nothing is allocated until a pass
-    // carries a tone descriptor.
-    void tone_counts(uint64_t *launches, uint64_t *frames) const
-    {
-        *launches = tn_launches_.load(std::memory_order_relaxed); *frames = tn_frames_.load(std::memory_order_relaxed);
-    }
     // aprilx_run_tones: n_runs runs in ONE launch, as debug_dtmf; records_out [sum n] (lo | hi << 16), powers_out (may be null) [sum n][F + 1]
     void debug_tones(int n_runs, const TonePlan *plans, const int32_t *n, const int16_t *frames, uint32_t *records_out, float *powers_out);
-    // ---- line quality.  Launches and the frames they covered so far (any thread); nothing is allocated until a
-    // pass carries a quality descriptor.
-    void quality_counts(uint64_t *launches, uint64_t *frames) const
-    {
-        *launches = qa_launches_.load(std::memory_order_relaxed); *frames = qa_frames_.load(std::memory_order_relaxed);
-    }
     // aprilx_run_quality: n_runs runs in ONE launch, as debug_dtmf, run r with clip level clip_levels[r] over hops of `hop` samples; records_out [sum n][8]
     void debug_quality(int hop, int n_runs, const int32_t *clip_levels, const int32_t *n, const int16_t *frames, uint32_t *records_out);
     // aprilx_run_tone_decide: the decision alone on n given rows of P[0..F), E
@@ -604,21 +579,19 @@ private:
     std::atomic<uint64_t> dc_launches_{0}, dc_frames_{0};
     // voice activity: nothing below is allocated until a pass carries a VAD descriptor
     VadState *vad_state_d_ = nullptr;          // [slots] (a session's first descriptor carries VAD_RESET: never initialised by the host)
-    uint8_t *pass_out_d_ = nullptr; size_t pass_out_cap_ = 0;      // one pass's bytes on the device, VAD, DTMF, the tone records, then the quality records (stream order keeps the passes apart)
+    uint8_t *pass_out_d_ = nullptr; size_t pass_out_cap_ = 0;      // one pass's block on the device (pass_layout.h; stream order keeps the passes apart)
     struct PassBlock { uint8_t *h = nullptr; size_t cap = 0; bool busy = false; };
-    std::vector<PassBlock> pass_blocks_;         // pinned blocks, one per pass whose bytes (VAD, then DTMF) the scheduler has not read yet: lent by fbank(), busy until release_pass_block()
-    bool pass_bytes_flight_ = false;                  // the open flight holds a pass with VAD or DTMF bytes: its event must follow their copy on the front-end stream
-    std::atomic<uint64_t> vad_launches_{0}, vad_frames_{0};
+    std::vector<PassBlock> pass_blocks_;         // pinned blocks, one per pass whose records (pass_layout.h) the scheduler has not read yet: lent by fbank(), busy until release_pass_block()
+    bool pass_bytes_flight_ = false;                  // the open flight holds a pass with observers' records: its event must follow their copy on the front-end stream
+    struct ObserverCount { std::atomic<uint64_t> launches{0}, frames{0}; } obs_counts_[OBS_COUNT];      // observer_counts()
     // DTMF: nothing below is allocated until a pass carries a DTMF descriptor
     const float *dt_tables_ = nullptr; int dt_wd_ = 0;      // [16][Wd] on the device, uploaded once (freed with table_allocs_)
-    std::atomic<uint64_t> dt_launches_{0}, dt_frames_{0};
     const float *dtmf_tables();
     // tones: nothing below is allocated until a pass carries a tone descriptor
     const float *tn_tables_ = nullptr; int tn_w_ = 0, tn_f_ = 0;      // [2F][W] on the device, uploaded once (freed with table_allocs_)
-    std::atomic<uint64_t> tn_launches_{0}, tn_frames_{0};
     const float *tone_tables();
-    // line quality: no table, no per-slot record; the counters of quality_counts()
-    std::atomic<uint64_t> qa_launches_{0}, qa_frames_{0};
+    // (line quality: no table, no per-slot record)
+    const float *upload_table(const std::vector<float> &t);      // a table to the device, kept until the engine goes (rs_mu_ held)
     // snapshot / restore: nothing below is allocated until the first call
     bool snapshot_copy(int n, SnapRec *recs, uint8_t *const *blocks, bool scatter);
     char *snap_d_ = nullptr, *snap_h_ = nullptr; size_t snap_cap_ = 0;      // device staging and its pinned twin: the records, then the blocks

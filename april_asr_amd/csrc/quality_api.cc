@@ -129,7 +129,7 @@ int aprilx_model_quality_stats(AprilASRModel model, int device_index, uint64_t *
 {
     if (!model || device_index < 0 || device_index >= (int)model->m.engines.size() || !launches || !frames || !ms) return -1;
     const Engine *e = model->m.engines[(size_t)device_index];
-    e->quality_counts(launches, frames);
+    e->observer_counts(OBS_QUALITY, launches, frames);
     *ms = e->timing(Engine::T_QUALITY).ms;
     return 0;
 }

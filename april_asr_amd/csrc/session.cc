@@ -555,45 +555,21 @@ bool Scheduler::set_search_options(Session *s, const AprilxSearchOptions *o)
     });
 }
 
-bool Scheduler::set_vad(Session *s, const VadOptions *o, const VadPlan *plan, AprilxVadHandler handler, void *userdata)
+template <class Obs, class Opt, class Plan, class Handler>
+bool Scheduler::set_observer(Session *s, Obs Session::*obs, Handler Handlers::*slot, void *Handlers::*slot_userdata, const Opt *o, const Plan *plan, Handler handler, void *userdata)
 {
     return configure(s, [&] {
-        s->vad = Session::Vad();
-        if (plan) { s->vad.on = true; s->vad.opt = *o; s->vad.plan = *plan; }
-        s->handlers.vad = plan ? handler : nullptr; s->handlers.vad_userdata = plan ? userdata : nullptr;
+        Obs &x = s->*obs;
+        x = Obs();
+        if (plan) { x.on = true; x.opt = *o; x.plan = *plan; }
+        s->handlers.*slot = plan ? handler : nullptr; s->handlers.*slot_userdata = plan ? userdata : nullptr;
         return true;
     });
 }
-
-bool Scheduler::set_dtmf(Session *s, const DtmfOptions *o, const DtmfPlan *plan, AprilxDtmfHandler handler, void *userdata)
-{
-    return configure(s, [&] {
-        s->dtmf = Session::Dtmf();
-        if (plan) { s->dtmf.on = true; s->dtmf.opt = *o; s->dtmf.plan = *plan; }
-        s->handlers.dtmf = plan ? handler : nullptr; s->handlers.dtmf_userdata = plan ? userdata : nullptr;
-        return true;
-    });
-}
-
-bool Scheduler::set_tones(Session *s, const ToneOptions *o, const TonePlan *plan, AprilxToneHandler handler, void *userdata)
-{
-    return configure(s, [&] {
-        s->tones = Session::Tones();
-        if (plan) { s->tones.on = true; s->tones.opt = *o; s->tones.plan = *plan; }
-        s->handlers.tone = plan ? handler : nullptr; s->handlers.tone_userdata = plan ? userdata : nullptr;
-        return true;
-    });
-}
-
-bool Scheduler::set_quality(Session *s, const QualityOptions *o, const QualityPlan *plan, AprilxQualityHandler handler, void *userdata)
-{
-    return configure(s, [&] {
-        s->quality = Session::Quality();
-        if (plan) { s->quality.on = true; s->quality.opt = *o; s->quality.plan = *plan; }
-        s->handlers.quality = plan ? handler : nullptr; s->handlers.quality_userdata = plan ? userdata : nullptr;
-        return true;
-    });
-}
+bool Scheduler::set_vad(Session *s, const VadOptions *o, const VadPlan *plan, AprilxVadHandler handler, void *userdata) { return set_observer(s, &Session::vad, &Handlers::vad, &Handlers::vad_userdata, o, plan, handler, userdata); }
+bool Scheduler::set_dtmf(Session *s, const DtmfOptions *o, const DtmfPlan *plan, AprilxDtmfHandler handler, void *userdata) { return set_observer(s, &Session::dtmf, &Handlers::dtmf, &Handlers::dtmf_userdata, o, plan, handler, userdata); }
+bool Scheduler::set_tones(Session *s, const ToneOptions *o, const TonePlan *plan, AprilxToneHandler handler, void *userdata) { return set_observer(s, &Session::tones, &Handlers::tone, &Handlers::tone_userdata, o, plan, handler, userdata); }
+bool Scheduler::set_quality(Session *s, const QualityOptions *o, const QualityPlan *plan, AprilxQualityHandler handler, void *userdata) { return set_observer(s, &Session::quality, &Handlers::quality, &Handlers::quality_userdata, o, plan, handler, userdata); }
 
 bool Scheduler::set_bias(Session *s, std::shared_ptr<const BiasSet> set)
 {
@@ -984,10 +960,17 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
     Lap lap;
     desc_.clear(); pcm_parts_.clear(); in_parts_.clear(); rdesc_.clear(); rspec_.clear(); ddesc_.clear(); raw_parts_.clear(); staged_raw_ = 0;
     vdesc_.clear(); tdesc_.clear(); ndesc_.clear(); qdesc_.clear();
-    PassPending rec{flight_seq_, nullptr, 0, 0, {}, {}, {}};      // this pass's record in the pass queue: its runs and flush markers, then its block
-    int32_t vad_frames = 0, dtmf_frames = 0;    // bytes of this pass's VAD / DTMF output so far
-    int32_t tone_frames = 0;                    // records of its tone output so far
-    int32_t quality_frames = 0, quality_hop = 0;      // records of its quality output so far; the hop of the plans behind them
+    PassPending rec;                            // this pass's record in the pass queue: its runs and flush markers, then its block
+    rec.flight = flight_seq_;
+    PassFrames obs_frames{};                    // records of this pass's output so far, per observer
+    int32_t quality_hop = 0;                    // the hop of the plans behind the quality descriptors
+    // one more run of observer o: the `cut` real frames just cut for s, at the next free records of the observer's part (returned)
+    auto add_run = [&](Observer o, Session *s, int cut) {
+        const int32_t off = (int32_t)obs_frames[o];
+        rec.runs[o].push_back(PassRun{s, s->real_frames, cut, off});
+        obs_frames[o] += (size_t)cut;
+        return off;
+    };
     size_t staged = 0, staged_in = 0;           // model-rate samples (windows), input-rate samples (spans of resampled windows)
     auto used = [&] { return staged + staged_in + (staged_raw_ + 1) / 2; };      // what the pass has staged so far, raw bytes of formatted sessions in sample units
     std::vector<Session *> finishers;
@@ -1028,34 +1011,29 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
             else if (fb.fmt) stage_decoded(fb, (int64_t)first, (int64_t)last_end, base);
             else fb.append_span(first, last_end, pcm_parts_);                 // (contiguous in staging)
             staged += last_end - first;
+            const int32_t first_desc = (int32_t)(desc_.size() - (size_t)cut);      // the run's frame descriptors are the last `cut` of this pass
             if (s->vad.on) {                           // the run of real rows just cut: one descriptor, one byte per row
                 VadDesc v;
-                v.slot = s->slot; v.first_row = desc_[desc_.size() - (size_t)cut].ring_row; v.n = cut; v.out_off = vad_frames;
+                v.slot = s->slot; v.first_row = desc_[(size_t)first_desc].ring_row; v.n = cut; v.out_off = add_run(OBS_VAD, s, cut);
                 v.flags = s->vad.reset ? VAD_RESET : 0; v.plan = s->vad.plan;
                 vdesc_.push_back(v);
-                rec.vad.push_back(PassRun{s, s->real_frames, cut, vad_frames});
-                vad_frames += cut; s->vad.reset = false;
+                s->vad.reset = false;
             }
-            if (s->dtmf.on) {                          // the same run: its frames' descriptors are the last `cut` of this pass
+            if (s->dtmf.on) {
                 DtmfDesc t;
-                t.first = (int32_t)(desc_.size() - (size_t)cut); t.n = cut; t.out_off = dtmf_frames; t.plan = s->dtmf.plan;
+                t.first = first_desc; t.n = cut; t.out_off = add_run(OBS_DTMF, s, cut); t.plan = s->dtmf.plan;
                 tdesc_.push_back(t);
-                rec.dtmf.push_back(PassRun{s, s->real_frames, cut, dtmf_frames});
-                dtmf_frames += cut;
             }
-            if (s->tones.on) {                         // likewise
+            if (s->tones.on) {
                 ToneDesc t;
-                t.first = (int32_t)(desc_.size() - (size_t)cut); t.n = cut; t.out_off = tone_frames; t.plan = s->tones.plan;
+                t.first = first_desc; t.n = cut; t.out_off = add_run(OBS_TONE, s, cut); t.plan = s->tones.plan;
                 ndesc_.push_back(t);
-                rec.tone.push_back(PassRun{s, s->real_frames, cut, tone_frames});
-                tone_frames += cut;
             }
-            if (s->quality.on) {                       // likewise
+            if (s->quality.on) {
                 QualityDesc q;
-                q.first = (int32_t)(desc_.size() - (size_t)cut); q.n = cut; q.out_off = quality_frames; q.clip_level = s->quality.plan.clip_level;
+                q.first = first_desc; q.n = cut; q.out_off = add_run(OBS_QUALITY, s, cut); q.clip_level = s->quality.plan.clip_level;
                 qdesc_.push_back(q);
-                rec.quality.push_back(PassRun{s, s->real_frames, cut, quality_frames});
-                quality_frames += cut; quality_hop = s->quality.plan.hop;
+                quality_hop = s->quality.plan.hop;
             }
             s->real_frames += (uint64_t)cut;
             s->compact_pending = true;                 // the fifo must not move until the window has been staged
@@ -1100,10 +1078,9 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
             // records of this flight; the device part (context reset + decoder refresh) is queued here
             s->replay.push_back(Session::Replay{-1, 0, 0, (uint32_t)s->now_ms, 1, 0});
             finishers.push_back(s);
-            if (s->vad.on) { rec.vad.push_back(PassRun{s, s->real_frames, -1, 0}); s->vad.reset = true; }      // closes an open segment; the detector starts afresh
-            if (s->dtmf.on) rec.dtmf.push_back(PassRun{s, s->real_frames, -1, 0});                              // closes a held digit; the machine starts afresh
-            if (s->tones.on) rec.tone.push_back(PassRun{s, s->real_frames, -1, 0});                             // closes a held tone likewise
-            if (s->quality.on) rec.quality.push_back(PassRun{s, s->real_frames, -1, 0});                        // closes the open interval and what is on
+            // every observer of the session closes what is open (a segment, a held digit or tone, the interval) and starts afresh
+            for (int o = 0; o < OBS_COUNT; ++o) if (s->observes(o)) rec.runs[o].push_back(PassRun{s, s->real_frames, -1, 0});
+            if (s->vad.on) s->vad.reset = true;
             s->flush_phase = 0;
             progressed = true;
             break;
@@ -1115,20 +1092,19 @@ void Scheduler::cut_frames(std::vector<Session *> &work, bool &progressed)
         FrontPass pass;
         pass.n_dc = (int)ddesc_.size(); pass.dc = ddesc_.data(); pass.raw_parts = raw_parts_.data(); pass.n_raw_parts = raw_parts_.size(); pass.n_raw = staged_raw_;
         pass.n_rs = (int)rdesc_.size(); pass.rs = rdesc_.data(); pass.rs_specs = rspec_.data(); pass.in_parts = in_parts_.data(); pass.n_in_parts = in_parts_.size(); pass.n_in = staged_in;
-        pass.n_vd = (int)vdesc_.size(); pass.vd = vdesc_.data(); pass.vad_bytes = (size_t)vad_frames;
-        pass.n_dt = (int)tdesc_.size(); pass.dt = tdesc_.data(); pass.dtmf_bytes = (size_t)dtmf_frames;
-        pass.n_tn = (int)ndesc_.size(); pass.tn = ndesc_.data(); pass.tone_bytes = (size_t)tone_frames * 4;
-        pass.n_qa = (int)qdesc_.size(); pass.qa = qdesc_.data(); pass.quality_bytes = (size_t)quality_frames * kQualityWords * 4; pass.quality_hop = quality_hop;
+        pass.observe(vdesc_.data(), vdesc_.size(), obs_frames[OBS_VAD]); pass.observe(tdesc_.data(), tdesc_.size(), obs_frames[OBS_DTMF]);
+        pass.observe(ndesc_.data(), ndesc_.size(), obs_frames[OBS_TONE]); pass.observe(qdesc_.data(), qdesc_.size(), obs_frames[OBS_QUALITY]);
+        pass.quality_hop = quality_hop;
         rec.block = eng_->fbank((int)desc_.size(), desc_.data(), pcm_parts_.data(), pcm_parts_.size(), staged, &pool_, pass);
         pool_.run(work.size(), 64, [&](size_t i) { Session *s = work[i]; if (s->compact_pending) { s->fb.compact(); s->compact_pending = false; } });
         tick_.frames += desc_.size();
         tick_.host_ms[2] += lap();
     }
     // the block is lent until this flight has been waited for and harvest() has read it
-    rec.dtmf_at = (size_t)vad_frames;
-    rec.tone_at = ((size_t)vad_frames + (size_t)dtmf_frames + 3) / 4 * 4;      // (FrontPass::tone_at())
-    rec.quality_at = FrontPass::quality_at_of((size_t)vad_frames, (size_t)dtmf_frames, (size_t)tone_frames * 4);
-    if (rec.block || !rec.vad.empty() || !rec.dtmf.empty() || !rec.tone.empty() || !rec.quality.empty()) pass_pending_.push_back(std::move(rec));
+    rec.at = pass_layout(obs_frames);
+    bool runs = false;
+    for (int o = 0; o < OBS_COUNT; ++o) runs = runs || !rec.runs[o].empty();
+    if (rec.block || runs) pass_pending_.push_back(std::move(rec));
     if (!finishers.empty()) {
         slots_.clear();
         for (Session *s : finishers) slots_.push_back(s->slot);
@@ -1249,17 +1225,29 @@ bool Scheduler::step_chunks(std::vector<Session *> &ready)
 }
 
 // After the flight's wait: the bytes of every pass cut under it (and under the flights before it) are on the host.  The records up to
-// the flight are walked four times -- all VAD runs of all of them, then all DTMF runs, then all tone runs, then all quality runs: the order of a session's detector events in front of
-// the flight's token events --, then each gives its block back and goes.  The sessions are alive: they stay busy until their flight
-// completes.  An engine that lent no block to a pass with descriptors: that pass's bytes are skipped by all detectors alike.
+// the flight are walked once per observer, in the block's order -- all VAD runs of all of them, then all DTMF runs, then all tone runs,
+// then all quality runs: the order of a session's observer events in front of the flight's token events --, then each gives its block
+// back and goes.  The sessions are alive: they stay busy until their flight completes.  A flush marker reaches its observer without
+// records; a run of an engine that lent no block to its pass is skipped, by all observers alike; else the observer gets the run's
+// records in the block (pinned memory, every part at its alignment: pass_layout.h).
 void Scheduler::harvest(uint64_t flight)
 {
     size_t n = 0;
     while (n < pass_pending_.size() && pass_pending_[n].flight <= flight) ++n;
-    for (size_t i = 0; i < n; ++i) for (const PassRun &r : pass_pending_[i].vad) harvest_vad(pass_pending_[i], r);
-    for (size_t i = 0; i < n; ++i) for (const PassRun &r : pass_pending_[i].dtmf) harvest_dtmf(pass_pending_[i], r);
-    for (size_t i = 0; i < n; ++i) for (const PassRun &r : pass_pending_[i].tone) harvest_tone(pass_pending_[i], r);
-    for (size_t i = 0; i < n; ++i) for (const PassRun &r : pass_pending_[i].quality) harvest_quality(pass_pending_[i], r);
+    for (int o = 0; o < OBS_COUNT; ++o)
+        for (size_t i = 0; i < n; ++i) {
+            const PassPending &p = pass_pending_[i];
+            for (const PassRun &r : p.runs[o]) {
+                if (r.n >= 0 && !p.block) continue;
+                const uint8_t *b = r.n < 0 ? nullptr : p.block + p.at.record_at(o, (size_t)r.off);
+                switch (o) {
+                case OBS_VAD: harvest_vad(r, b); break;
+                case OBS_DTMF: harvest_dtmf(r, b); break;
+                case OBS_TONE: harvest_tone(r, reinterpret_cast<const uint32_t *>(b)); break;
+                default: harvest_quality(r, reinterpret_cast<const uint32_t *>(b)); break;
+                }
+            }
+        }
     for (; n; --n) {
         if (pass_pending_.front().block) eng_->release_pass_block(pass_pending_.front().block);
         pass_pending_.pop_front();
@@ -1267,7 +1255,7 @@ void Scheduler::harvest(uint64_t flight)
 }
 
 // One VAD run: the events that follow from bit 0 of consecutive bytes go to the session's event list; a completed flush closes an open segment.
-void Scheduler::harvest_vad(const PassPending &p, const PassRun &r)
+void Scheduler::harvest_vad(const PassRun &r, const uint8_t *b)
 {
     Session *s = r.s;
     auto emit = [&](int kind, uint64_t ms) {
@@ -1275,15 +1263,13 @@ void Scheduler::harvest_vad(const PassPending &p, const PassRun &r)
         s->events.push_back(std::move(e));
         if (kind == VAD_SPEECH_START) s->vad.segments++;
     };
-    if (r.n < 0) { if (s->vad.last) emit(VAD_SPEECH_END, r.t0 * (uint64_t)shift_ms_); s->vad.last = 0; return; }
-    if (!p.block) return;
-    const uint8_t *b = p.block + r.off;
+    if (!b) { if (s->vad.last) emit(VAD_SPEECH_END, r.t0 * (uint64_t)shift_ms_); s->vad.last = 0; return; }
     s->vad.last = vad_events(s->vad.plan, shift_ms_, r.t0, b, (size_t)r.n, s->vad.last, emit);
     for (int32_t i = 0; i < r.n; ++i) s->vad.speech += b[i] & 1u;
 }
 
 // One DTMF run: the codes of consecutive real frames go through the session's event machine (dtmf.h); a completed flush closes a held digit.
-void Scheduler::harvest_dtmf(const PassPending &p, const PassRun &r)
+void Scheduler::harvest_dtmf(const PassRun &r, const uint8_t *b)
 {
     Session *s = r.s;
     auto emit = [&](int kind, char digit, uint64_t ms) {
@@ -1291,15 +1277,13 @@ void Scheduler::harvest_dtmf(const PassPending &p, const PassRun &r)
         s->events.push_back(std::move(e));
         if (kind == DTMF_DOWN) s->dtmf.digits++;
     };
-    if (r.n < 0) { dtmf_flush(shift_ms_, r.t0, s->dtmf.m, emit); return; }
-    if (!p.block) return;
-    const uint8_t *b = p.block + p.dtmf_at + r.off;
+    if (!b) { dtmf_flush(shift_ms_, r.t0, s->dtmf.m, emit); return; }
     dtmf_events(s->dtmf.plan, shift_ms_, r.t0, b, (size_t)r.n, s->dtmf.m, emit);
     for (int32_t i = 0; i < r.n; ++i) s->dtmf.tone += b[i] ? 1u : 0u;
 }
 
 // One tone run: the records of consecutive real frames go through the session's event machine (tone.h); a completed flush closes a held tone.
-void Scheduler::harvest_tone(const PassPending &p, const PassRun &r)
+void Scheduler::harvest_tone(const PassRun &r, const uint32_t *b)
 {
     Session *s = r.s;
     auto emit = [&](int kind, uint32_t f1, uint32_t f2, uint64_t ms) {
@@ -1307,16 +1291,14 @@ void Scheduler::harvest_tone(const PassPending &p, const PassRun &r)
         s->events.push_back(std::move(e));
         if (kind == TONE_ON) s->tones.tones++;
     };
-    if (r.n < 0) { tone_flush(shift_ms_, r.t0, s->tones.m, emit); return; }
-    if (!p.block) return;
-    const uint32_t *b = reinterpret_cast<const uint32_t *>(p.block + p.tone_at) + r.off;      // (the block is pinned memory, tone_at a multiple of 4)
+    if (!b) { tone_flush(shift_ms_, r.t0, s->tones.m, emit); return; }
     tone_events(s->tones.plan, shift_ms_, r.t0, b, (size_t)r.n, s->tones.m, emit);
     for (int32_t i = 0; i < r.n; ++i) s->tones.tonal += (b[i] & 0xffffu) ? 1u : 0u;
 }
 
 // One quality run: the records of consecutive real frames go through the session's machine (quality.h); a completed flush closes the open
 // interval and whatever is on.
-void Scheduler::harvest_quality(const PassPending &p, const PassRun &r)
+void Scheduler::harvest_quality(const PassRun &r, const uint32_t *b)
 {
     Session *s = r.s;
     auto emit = [&](const QualityEvent &q) {
@@ -1324,9 +1306,7 @@ void Scheduler::harvest_quality(const PassPending &p, const PassRun &r)
         s->events.push_back(std::move(e));
         if (q.kind == QUALITY_REPORT) s->quality.reports++;
     };
-    if (r.n < 0) { quality_flush(s->quality.plan, shift_ms_, r.t0, s->quality.m, emit); return; }
-    if (!p.block) return;
-    const uint32_t *b = reinterpret_cast<const uint32_t *>(p.block + p.quality_at) + (size_t)r.off * kQualityWords;      // (the block is pinned memory, quality_at a multiple of 16)
+    if (!b) { quality_flush(s->quality.plan, shift_ms_, r.t0, s->quality.m, emit); return; }
     quality_events(s->quality.plan, shift_ms_, r.t0, b, (size_t)r.n, s->quality.m, emit);
     for (int32_t i = 0; i < r.n; ++i) {
         const uint32_t *w = b + (size_t)i * kQualityWords;

@@ -273,6 +273,7 @@ struct Session {
         QualityMachine m;                     // (the device keeps nothing)
         uint64_t frames = 0, clipped = 0, dead = 0, clip_samples = 0, reports = 0;      // records read, clipped and dead frames, clipped samples, REPORT events, since the observer was last set
     } quality;
+    bool observes(int o) const { const bool on[OBS_COUNT] = {vad.on, dtmf.on, tones.on, quality.on}; return on[o]; }      // (by Observer)
     // tracing (tests): every joiner call appends `vocab` floats
     float *trace_buf = nullptr; size_t trace_cap = 0; size_t *trace_used = nullptr;
 };
@@ -316,13 +317,11 @@ public:
     bool set_lm(Session *s, std::shared_ptr<const LmSet> lm, float weight, float token_bonus);
     // aprilx_session_set_search_options: the same rule; null = back to no options
     bool set_search_options(Session *s, const AprilxSearchOptions *o);
-    // aprilx_session_set_vad: the same rule; plan null = off.  The detector and its counters start afresh
+    // aprilx_session_set_vad / _dtmf / _tones / _quality: the same rule; plan null = off.  The observer's state (VAD: on the device, from the
+    // session's next descriptor on; the others: the machine) and its counters start afresh
     bool set_vad(Session *s, const VadOptions *o, const VadPlan *plan, AprilxVadHandler handler, void *userdata);
-    // aprilx_session_set_dtmf: the same rule; plan null = off.  The machine and its counters start afresh
     bool set_dtmf(Session *s, const DtmfOptions *o, const DtmfPlan *plan, AprilxDtmfHandler handler, void *userdata);
-    // aprilx_session_set_tones: the same rule; plan null = off.  The machine and its counters start afresh
     bool set_tones(Session *s, const ToneOptions *o, const TonePlan *plan, AprilxToneHandler handler, void *userdata);
-    // aprilx_session_set_quality: the same rule; plan null = off.  The machine and its counters start afresh
     bool set_quality(Session *s, const QualityOptions *o, const QualityPlan *plan, AprilxQualityHandler handler, void *userdata);
     void wait_idle_many(Session *const *ss, int n);
     // until every listed session has at most `max_open` feeds that were submitted and not completed yet (pipelined group feeds)
@@ -367,24 +366,27 @@ private:
     // how advance() runs its T chunks: one chunk step (T == 1, Engine::step), or Engine::lm_step as a feed wavefront / layer-major
     enum StepPath { STEP_CHUNK, STEP_WAVE, STEP_LAYER_MAJOR };
     bool advance(Session *const *group, int m, int T, StepPath path);
-    template <class Apply> bool configure(Session *s, Apply apply);     // the three set_* calls: wait_idle, lock, refuse unless settable, apply
+    template <class Apply> bool configure(Session *s, Apply apply);     // the set_* calls: wait_idle, lock, refuse unless settable, apply
+    // the four observers' set_* calls: the session's member `obs` afresh (on, with options and plan, or off) and its two handler slots
+    template <class Obs, class Opt, class Plan, class Handler>
+    bool set_observer(Session *s, Obs Session::*obs, Handler Handlers::*slot, void *Handlers::*slot_userdata, const Opt *o, const Plan *plan, Handler handler, void *userdata);
     void replay(Flight &f);
-    // The pass queue: what the detectors' kernels wrote for the passes of the open flights ("the pass's bytes").
+    // The pass queue: what the observers' kernels wrote for the passes of the open flights ("the pass's bytes").
     // cut_frames() pushes one record per pass that has runs, under the flight that is open; harvest(), once that flight has been waited
     // for, turns the runs into events, gives the block back to the engine and pops the record.  The record is the block's one owner.
-    struct PassRun { Session *s; uint64_t t0; int32_t n, off; };      // frames [t0, t0 + n) at off in its detector's part; n < 0: a flush completed at frame t0
-    // block: Engine::fbank()'s, the pass's VAD bytes, from dtmf_at its DTMF bytes and from tone_at its tone records (a tone run's off
-    // counts records) and from quality_at its quality records (likewise); null: a pass of flush markers only
-    struct PassPending { uint64_t flight; const uint8_t *block; size_t dtmf_at, tone_at; std::vector<PassRun> vad, dtmf, tone; size_t quality_at = 0; std::vector<PassRun> quality; };
+    struct PassRun { Session *s; uint64_t t0; int32_t n, off; };      // frames [t0, t0 + n) at record `off` of its observer's part; n < 0: a flush completed at frame t0
+    // block: Engine::fbank()'s, laid out by `at` (null: a pass of flush markers only); runs: by Observer
+    struct PassPending { uint64_t flight = 0; const uint8_t *block = nullptr; PassLayout at; std::vector<PassRun> runs[OBS_COUNT]; };
     std::deque<PassPending> pass_pending_;
     std::vector<VadDesc> vdesc_; std::vector<DtmfDesc> tdesc_; std::vector<ToneDesc> ndesc_; std::vector<QualityDesc> qdesc_;       // scratch of cut_frames()
     uint64_t flight_seq_ = 0;
     const int shift_ms_;
+    // records == null: the run is a flush marker; else the run's r.n records in the pass's block
     void harvest(uint64_t flight);
-    void harvest_vad(const PassPending &p, const PassRun &r);
-    void harvest_dtmf(const PassPending &p, const PassRun &r);
-    void harvest_tone(const PassPending &p, const PassRun &r);
-    void harvest_quality(const PassPending &p, const PassRun &r);
+    void harvest_vad(const PassRun &r, const uint8_t *records);
+    void harvest_dtmf(const PassRun &r, const uint8_t *records);
+    void harvest_tone(const PassRun &r, const uint32_t *records);
+    void harvest_quality(const PassRun &r, const uint32_t *records);
     int split_sticky_ = 0;
     int pipeline_depth_ = 2;                             // APRIL_PIPELINE: 2 = launch the next flight before completing the current one, 1 = one flight at a time
 

@@ -114,7 +114,7 @@ int aprilx_model_vad_stats(AprilASRModel model, int device_index, uint64_t *laun
 {
     if (!model || device_index < 0 || device_index >= (int)model->m.engines.size() || !launches || !frames || !ms) return -1;
     const Engine *e = model->m.engines[(size_t)device_index];
-    e->vad_counts(launches, frames);
+    e->observer_counts(OBS_VAD, launches, frames);
     *ms = e->timing(Engine::T_VAD).ms;
     return 0;
 }

@@ -66,7 +66,7 @@ struct New {
         n_rs = std::max(n_rs, 0); n_dc = std::max(n_dc, 0); n_vd = std::max(n_vd, 0); n_dt = std::max(n_dt, 0);
         cnt = StagingCounts();
         cnt.n_pcm = n_pcm; cnt.n_in = n_rs ? n_in : 0; cnt.n_raw = n_dc ? n_raw : 0;
-        cnt.n_frames = (size_t)n_frames; cnt.n_rs = (size_t)n_rs; cnt.n_dc = (size_t)n_dc; cnt.n_vd = (size_t)n_vd; cnt.n_dt = (size_t)n_dt;
+        cnt.n[ST_FRAMES] = (size_t)n_frames; cnt.n[ST_RS] = (size_t)n_rs; cnt.n[ST_DC] = (size_t)n_dc; cnt.n[ST_VD] = (size_t)n_vd; cnt.n[ST_DT] = (size_t)n_dt;
         const StagingSizes el{S_FbankFrameDesc, S_ResampleDesc, S_DecodeDesc, S_VadDesc, S_DtmfDesc};
         lay = staging_layout(cnt, el);
         regrew = !caps.holds(cnt, lay);
@@ -76,33 +76,33 @@ struct New {
 
 static void compare(const Old &o, const New &n)
 {
-    CHECK(o.woff == n.lay.raw); CHECK(o.doff == n.lay.frames); CHECK(o.roff == n.lay.rs); CHECK(o.coff == n.lay.dc); CHECK(o.voff == n.lay.vd);
+    CHECK(o.woff == n.lay.raw); CHECK(o.doff == n.lay.off[ST_FRAMES]); CHECK(o.roff == n.lay.off[ST_RS]); CHECK(o.coff == n.lay.off[ST_DC]); CHECK(o.voff == n.lay.off[ST_VD]);
     CHECK(o.bytes == n.lay.bytes);
     CHECK(o.regrew == n.regrew); CHECK(o.units == n.units);
-    CHECK((size_t)o.desc_cap_ == n.caps.frames); CHECK(o.pcm_cap_ == n.caps.pcm_units); CHECK(o.rs_cap_ == n.caps.rs); CHECK(o.dc_cap_ == n.caps.dc); CHECK(o.vd_cap_ == n.caps.vd);
+    CHECK((size_t)o.desc_cap_ == n.caps.n[ST_FRAMES]); CHECK(o.pcm_cap_ == n.caps.pcm_units); CHECK(o.rs_cap_ == n.caps.n[ST_RS]); CHECK(o.dc_cap_ == n.caps.n[ST_DC]); CHECK(o.vd_cap_ == n.caps.n[ST_VD]);
     CHECK(n.lay.bytes <= n.units * 2);                  // the upload fits the buffers
-    CHECK(n.lay.raw % 16 == 0 && n.lay.frames % 16 == 0 && n.lay.rs % 16 == 0 && n.lay.dc % 16 == 0 && n.lay.vd % 16 == 0);
+    CHECK(n.lay.raw % 16 == 0 && n.lay.off[ST_FRAMES] % 16 == 0 && n.lay.off[ST_RS] % 16 == 0 && n.lay.off[ST_DC] % 16 == 0 && n.lay.off[ST_VD] % 16 == 0);
 }
 
 // a call with DTMF descriptors, `before` the capacities it met
 static void check_dt(const New &n, const StagingCaps &before)
 {
     const StagingCounts &c = n.cnt;
-    CHECK(c.n_dt > 0);
-    CHECK(n.lay.dt % 16 == 0 && n.lay.dt >= n.lay.vd + c.n_vd * S_VadDesc && n.lay.dt < n.lay.vd + c.n_vd * S_VadDesc + 16);
-    CHECK(n.lay.bytes == n.lay.dt + c.n_dt * S_DtmfDesc);
+    CHECK(c.n[ST_DT] > 0);
+    CHECK(n.lay.off[ST_DT] % 16 == 0 && n.lay.off[ST_DT] >= n.lay.off[ST_VD] + c.n[ST_VD] * S_VadDesc && n.lay.off[ST_DT] < n.lay.off[ST_VD] + c.n[ST_VD] * S_VadDesc + 16);
+    CHECK(n.lay.bytes == n.lay.off[ST_DT] + c.n[ST_DT] * S_DtmfDesc);
     CHECK(n.lay.bytes <= n.lay.units * 2);              // a buffer of exactly these counts holds the upload ...
     CHECK(n.lay.bytes <= n.units * 2);                  // ... and so do the buffers as they are after the call
-    const bool exceeds = c.n_frames > before.frames || n.lay.pcm_units > before.pcm_units || c.n_rs > before.rs || c.n_dc > before.dc ||
-                         c.n_vd > before.vd || c.n_dt > before.dt;
+    const bool exceeds = c.n[ST_FRAMES] > before.n[ST_FRAMES] || n.lay.pcm_units > before.pcm_units || c.n[ST_RS] > before.n[ST_RS] || c.n[ST_DC] > before.n[ST_DC] ||
+                         c.n[ST_VD] > before.n[ST_VD] || c.n[ST_DT] > before.n[ST_DT];
     CHECK(n.regrew == exceeds);
     CHECK(n.caps.holds(c, n.lay));
     if (!n.regrew)
-        CHECK(n.caps.frames == before.frames && n.caps.pcm_units == before.pcm_units && n.caps.rs == before.rs && n.caps.dc == before.dc &&
-              n.caps.vd == before.vd && n.caps.dt == before.dt);
+        CHECK(n.caps.n[ST_FRAMES] == before.n[ST_FRAMES] && n.caps.pcm_units == before.pcm_units && n.caps.n[ST_RS] == before.n[ST_RS] && n.caps.n[ST_DC] == before.n[ST_DC] &&
+              n.caps.n[ST_VD] == before.n[ST_VD] && n.caps.n[ST_DT] == before.n[ST_DT]);
     else
-        CHECK(n.caps.frames >= before.frames && n.caps.pcm_units >= before.pcm_units && n.caps.rs >= before.rs && n.caps.dc >= before.dc &&
-              n.caps.vd >= before.vd && n.caps.dt >= std::max(before.dt, c.n_dt));
+        CHECK(n.caps.n[ST_FRAMES] >= before.n[ST_FRAMES] && n.caps.pcm_units >= before.pcm_units && n.caps.n[ST_RS] >= before.n[ST_RS] && n.caps.n[ST_DC] >= before.n[ST_DC] &&
+              n.caps.n[ST_VD] >= before.n[ST_VD] && n.caps.n[ST_DT] >= std::max(before.n[ST_DT], c.n[ST_DT]));
 }
 
 int main()
@@ -127,8 +127,8 @@ int main()
                     New d;
                     d.call(n_frames, n_pcm, n_rs, n_in, n_dc, n_raw, n_vd, n_dt);
                     check_dt(d, StagingCaps());
-                    CHECK(d.lay.raw == n.lay.raw && d.lay.frames == n.lay.frames && d.lay.rs == n.lay.rs && d.lay.dc == n.lay.dc && d.lay.vd == n.lay.vd);
-                    CHECK(d.lay.pcm_units == n.lay.pcm_units && d.caps.dt == 256 && d.units > n.units);
+                    CHECK(d.lay.raw == n.lay.raw && d.lay.off[ST_FRAMES] == n.lay.off[ST_FRAMES] && d.lay.off[ST_RS] == n.lay.off[ST_RS] && d.lay.off[ST_DC] == n.lay.off[ST_DC] && d.lay.off[ST_VD] == n.lay.off[ST_VD]);
+                    CHECK(d.lay.pcm_units == n.lay.pcm_units && d.caps.n[ST_DT] == 256 && d.units > n.units);
                 }
             }
         // one pair of buffers through a sequence of calls: passes come and go, counts cross the floors and the doubled capacities
@@ -160,10 +160,10 @@ int main()
             const size_t n_in = rnd(900u * (unsigned)scale), n_raw = rnd(1700u * (unsigned)scale);
             const StagingCaps before = d.caps;
             d.call(n_frames, n_pcm, n_rs, n_in, n_dc, n_raw, n_vd, n_dt);
-            if (n_dt) { check_dt(d, before); ++dt_calls; dt_regrows += d.regrew && (size_t)n_dt > before.dt; }
+            if (n_dt) { check_dt(d, before); ++dt_calls; dt_regrows += d.regrew && (size_t)n_dt > before.n[ST_DT]; }
             else {
                 od.call(n_frames, n_pcm, n_rs, n_in, n_dc, n_raw, n_vd);
-                CHECK(od.woff == d.lay.raw && od.doff == d.lay.frames && od.roff == d.lay.rs && od.coff == d.lay.dc && od.voff == d.lay.vd && od.bytes == d.lay.bytes);
+                CHECK(od.woff == d.lay.raw && od.doff == d.lay.off[ST_FRAMES] && od.roff == d.lay.off[ST_RS] && od.coff == d.lay.off[ST_DC] && od.voff == d.lay.off[ST_VD] && od.bytes == d.lay.bytes);
                 CHECK(d.lay.bytes <= d.units * 2);
             }
         }

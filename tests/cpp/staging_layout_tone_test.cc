@@ -51,9 +51,9 @@ struct Six {
     {
         cnt = StagingCounts();
         cnt.n_pcm = n_pcm; cnt.n_in = n_in; cnt.n_raw = n_raw;
-        cnt.n_frames = n[0]; cnt.n_rs = n[1]; cnt.n_dc = n[2]; cnt.n_vd = n[3]; cnt.n_dt = n[4]; cnt.n_tn = n_tn;
-        StagingSizes s;
-        s.frame = el[0]; s.rs = el[1]; s.dc = el[2]; s.vd = el[3]; s.dt = el[4]; s.tn = el[5];
+        cnt.n[ST_FRAMES] = n[0]; cnt.n[ST_RS] = n[1]; cnt.n[ST_DC] = n[2]; cnt.n[ST_VD] = n[3]; cnt.n[ST_DT] = n[4]; cnt.n[ST_TN] = n_tn;
+        StagingSizes s{};
+        s[ST_FRAMES] = el[0]; s[ST_RS] = el[1]; s[ST_DC] = el[2]; s[ST_VD] = el[3]; s[ST_DT] = el[4]; s[ST_TN] = el[5];
         lay = staging_layout(cnt, s);
         regrew = !caps.holds(cnt, lay);
         if (regrew) { caps.grow(cnt, lay); units = caps.units(s); }
@@ -62,11 +62,11 @@ struct Six {
 
 static void same(const Five &o, const Six &n)
 {
-    CHECK(o.raw == n.lay.raw && o.off[0] == n.lay.frames && o.off[1] == n.lay.rs && o.off[2] == n.lay.dc && o.off[3] == n.lay.vd && o.off[4] == n.lay.dt);
+    CHECK(o.raw == n.lay.raw && o.off[0] == n.lay.off[ST_FRAMES] && o.off[1] == n.lay.off[ST_RS] && o.off[2] == n.lay.off[ST_DC] && o.off[3] == n.lay.off[ST_VD] && o.off[4] == n.lay.off[ST_DT]);
     CHECK(o.bytes == n.lay.bytes && o.pcm_units == n.lay.pcm_units && o.units == n.lay.units);
     CHECK(o.regrew == n.regrew && o.cap_units == n.units);
-    CHECK(o.cap[0] == n.caps.frames && o.cap_pcm == n.caps.pcm_units && o.cap[1] == n.caps.rs && o.cap[2] == n.caps.dc && o.cap[3] == n.caps.vd && o.cap[4] == n.caps.dt);
-    CHECK(n.caps.tn == 0);
+    CHECK(o.cap[0] == n.caps.n[ST_FRAMES] && o.cap_pcm == n.caps.pcm_units && o.cap[1] == n.caps.n[ST_RS] && o.cap[2] == n.caps.n[ST_DC] && o.cap[3] == n.caps.n[ST_VD] && o.cap[4] == n.caps.n[ST_DT]);
+    CHECK(n.caps.n[ST_TN] == 0);
 }
 
 int main()
@@ -89,15 +89,15 @@ int main()
                 for (size_t n_tn : {(size_t)1, (size_t)5}) {
                     Six t;
                     t.call(n, n_tn, el, n_pcm, use_in, use_raw);
-                    CHECK(t.lay.raw == s.lay.raw && t.lay.frames == s.lay.frames && t.lay.rs == s.lay.rs && t.lay.dc == s.lay.dc && t.lay.vd == s.lay.vd && t.lay.dt == s.lay.dt);
-                    const size_t end5 = t.lay.dt + n_dt * el[4];
-                    CHECK(t.lay.tn % 16 == 0 && t.lay.tn >= end5 && t.lay.tn < end5 + 16);
-                    CHECK(t.lay.bytes == t.lay.tn + n_tn * el[5]);
+                    CHECK(t.lay.raw == s.lay.raw && t.lay.off[ST_FRAMES] == s.lay.off[ST_FRAMES] && t.lay.off[ST_RS] == s.lay.off[ST_RS] && t.lay.off[ST_DC] == s.lay.off[ST_DC] && t.lay.off[ST_VD] == s.lay.off[ST_VD] && t.lay.off[ST_DT] == s.lay.off[ST_DT]);
+                    const size_t end5 = t.lay.off[ST_DT] + n_dt * el[4];
+                    CHECK(t.lay.off[ST_TN] % 16 == 0 && t.lay.off[ST_TN] >= end5 && t.lay.off[ST_TN] < end5 + 16);
+                    CHECK(t.lay.bytes == t.lay.off[ST_TN] + n_tn * el[5]);
                     CHECK(t.lay.pcm_units == s.lay.pcm_units && t.lay.units > s.lay.units);
                     CHECK(t.lay.bytes <= t.lay.units * 2 && t.lay.bytes <= t.units * 2);
-                    CHECK(t.regrew && t.caps.tn == 256 && t.caps.holds(t.cnt, t.lay) && t.units > s.units);
-                    CHECK(t.caps.frames == s.caps.frames && t.caps.pcm_units == s.caps.pcm_units && t.caps.rs == s.caps.rs && t.caps.dc == s.caps.dc &&
-                          t.caps.vd == s.caps.vd && t.caps.dt == s.caps.dt);
+                    CHECK(t.regrew && t.caps.n[ST_TN] == 256 && t.caps.holds(t.cnt, t.lay) && t.units > s.units);
+                    CHECK(t.caps.n[ST_FRAMES] == s.caps.n[ST_FRAMES] && t.caps.pcm_units == s.caps.pcm_units && t.caps.n[ST_RS] == s.caps.n[ST_RS] && t.caps.n[ST_DC] == s.caps.n[ST_DC] &&
+                          t.caps.n[ST_VD] == s.caps.n[ST_VD] && t.caps.n[ST_DT] == s.caps.n[ST_DT]);
                 }
             }
         // one pair of buffers through a sequence of calls in which tone passes come and go: a call without one uploads what the
@@ -114,13 +114,13 @@ int main()
             const StagingCaps before = s.caps;
             s.call(n, n_tn, el, n_pcm, n_in, n_raw);
             o.call(n, el, n_pcm, n_in, n_raw);
-            CHECK(o.raw == s.lay.raw && o.off[0] == s.lay.frames && o.off[1] == s.lay.rs && o.off[2] == s.lay.dc && o.off[3] == s.lay.vd && o.off[4] == s.lay.dt);
+            CHECK(o.raw == s.lay.raw && o.off[0] == s.lay.off[ST_FRAMES] && o.off[1] == s.lay.off[ST_RS] && o.off[2] == s.lay.off[ST_DC] && o.off[3] == s.lay.off[ST_VD] && o.off[4] == s.lay.off[ST_DT]);
             CHECK(s.lay.bytes <= s.units * 2 && s.caps.holds(s.cnt, s.lay));
             if (!n_tn) CHECK(o.bytes == s.lay.bytes);
             else {
-                ++tone_calls; tone_regrows += s.regrew && n_tn > before.tn;
-                CHECK(s.lay.tn % 16 == 0 && s.lay.tn >= o.off[4] + n[4] * el[4] && s.lay.bytes == s.lay.tn + n_tn * el[5]);
-                CHECK(s.caps.tn >= std::max(before.tn, n_tn));
+                ++tone_calls; tone_regrows += s.regrew && n_tn > before.n[ST_TN];
+                CHECK(s.lay.off[ST_TN] % 16 == 0 && s.lay.off[ST_TN] >= o.off[4] + n[4] * el[4] && s.lay.bytes == s.lay.off[ST_TN] + n_tn * el[5]);
+                CHECK(s.caps.n[ST_TN] >= std::max(before.n[ST_TN], n_tn));
             }
         }
         CHECK(tone_calls > 1000 && tone_regrows > 2);

@@ -139,31 +139,35 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
     const size_t total = read_all(parts, n_parts);
     if (total != n_pcm) { LOGE("fake engine: fbank: windows hold %zu samples, caller says %zu", total, n_pcm); abort(); }
     // a pass without descriptors carries nothing, and its spans hold what the caller says they hold
-    if (pass.n_rs < 0 || pass.n_dc < 0 || pass.n_vd < 0 || pass.n_dt < 0 || (!pass.n_rs && (pass.n_in_parts || pass.n_in)) || (!pass.n_dc && (pass.n_raw_parts || pass.n_raw)) ||
-        (!pass.n_vd && pass.vad_bytes) || (!pass.n_dt && pass.dtmf_bytes) || (pass.n_rs && (!pass.rs || !pass.rs_specs)) || (pass.n_dc && !pass.dc) || (pass.n_vd && !pass.vd) ||
-        (pass.n_dt && !pass.dt) ||
+    const FrontPass::Observed &vad = pass.obs[OBS_VAD], &dtmf = pass.obs[OBS_DTMF];
+    const VadDesc *vd = pass.descs<VadDesc>();
+    const DtmfDesc *dt = pass.descs<DtmfDesc>();
+    if (pass.n_rs < 0 || pass.n_dc < 0 || vad.n < 0 || dtmf.n < 0 || (!pass.n_rs && (pass.n_in_parts || pass.n_in)) || (!pass.n_dc && (pass.n_raw_parts || pass.n_raw)) ||
+        (!vad.n && vad.frames) || (!dtmf.n && dtmf.frames) || (pass.n_rs && (!pass.rs || !pass.rs_specs)) || (pass.n_dc && !pass.dc) || (vad.n && !vd) ||
+        (dtmf.n && !dt) ||
         read_all(pass.in_parts, pass.n_in_parts) != pass.n_in || read_all(pass.raw_parts, pass.n_raw_parts) != pass.n_raw) {
         LOGE("fake engine: fbank: inconsistent front-end pass"); abort();
     }
     size_t vad_rows = 0;
-    for (int i = 0; i < pass.n_vd; ++i) vad_rows += (size_t)pass.vd[i].n;
-    if (vad_rows != pass.vad_bytes) { LOGE("fake engine: fbank: VAD descriptors cover %zu rows, caller says %zu", vad_rows, pass.vad_bytes); abort(); }
+    for (int i = 0; i < vad.n; ++i) vad_rows += (size_t)vd[i].n;
+    if (vad_rows != vad.frames) { LOGE("fake engine: fbank: VAD descriptors cover %zu rows, caller says %zu", vad_rows, vad.frames); abort(); }
     size_t dtmf_rows = 0;
-    for (int i = 0; i < pass.n_dt; ++i) dtmf_rows += (size_t)pass.dt[i].n;
-    if (dtmf_rows != pass.dtmf_bytes) { LOGE("fake engine: fbank: DTMF descriptors cover %zu frames, caller says %zu", dtmf_rows, pass.dtmf_bytes); abort(); }
+    for (int i = 0; i < dtmf.n; ++i) dtmf_rows += (size_t)dt[i].n;
+    if (dtmf_rows != dtmf.frames) { LOGE("fake engine: fbank: DTMF descriptors cover %zu frames, caller says %zu", dtmf_rows, dtmf.frames); abort(); }
     for (int i = 0; i < n_frames; ++i) {
         if (desc[i].slot < 0 || desc[i].slot >= cfg_.max_slots || desc[i].ring_row < 0 || desc[i].ring_row >= ring_frames_) { LOGE("fake engine: fbank: bad descriptor"); abort(); }
         if (desc[i].pcm_off >= 0 && (size_t)desc[i].pcm_off + (size_t)1 > n_pcm) { LOGE("fake engine: fbank: frame window outside the staged samples"); abort(); }
     }
     f.pcm_sum.fetch_add(sum, std::memory_order_relaxed);
     f.frames += (uint64_t)n_frames;
-    if (!pass.n_vd && !pass.n_dt) return nullptr;
+    if (!vad.n && !dtmf.n) return nullptr;
     // the pass's block: one byte per frame of every run, from the frame's own samples; every byte written exactly once
     std::vector<int16_t> flat;
     flat.reserve(n_pcm);
     for (size_t p = 0; p < n_parts; ++p)
         if (parts[p].first) flat.insert(flat.end(), parts[p].first, parts[p].first + parts[p].second); else flat.resize(flat.size() + parts[p].second, 0);
-    const size_t bytes = pass.vad_bytes + pass.dtmf_bytes;
+    const PassLayout lay = pass_layout(PassFrames{{vad.frames, dtmf.frames, 0, 0}});      // (the two parts this engine knows)
+    const size_t bytes = lay.bytes;
     uint8_t *block = new uint8_t[bytes];
     std::vector<uint8_t> written(bytes, 0);
     auto put = [&](size_t at, int frame, bool dtmf) {
@@ -173,20 +177,20 @@ const uint8_t *Engine::fbank(int n_frames, const FbankFrameDesc *desc, const std
         const uint32_t h = mix((uint16_t)flat[o], o + 1 < flat.size() ? (uint16_t)flat[o + 1] : 0u, 5u);
         block[at] = dtmf ? (uint8_t)((h >> 8) % 17u) : (uint8_t)(h & 3u);
     };
-    for (int i = 0; i < pass.n_vd; ++i) {        // (a VAD descriptor names ring rows: its frames are the run that starts at that row of that slot)
-        const VadDesc &v = pass.vd[i];
+    for (int i = 0; i < vad.n; ++i) {        // (a VAD descriptor names ring rows: its frames are the run that starts at that row of that slot)
+        const VadDesc &v = vd[i];
         int first = 0;
         while (first < n_frames && !(desc[first].slot == v.slot && desc[first].ring_row == v.first_row && desc[first].pcm_off >= 0)) ++first;
-        if (v.n <= 0 || first + v.n > n_frames || v.out_off < 0 || (size_t)v.out_off + (size_t)v.n > pass.vad_bytes) { LOGE("fake engine: fbank: VAD descriptor %d outside the pass", i); abort(); }
+        if (v.n <= 0 || first + v.n > n_frames || v.out_off < 0 || (size_t)v.out_off + (size_t)v.n > vad.frames) { LOGE("fake engine: fbank: VAD descriptor %d outside the pass", i); abort(); }
         for (int k = 0; k < v.n; ++k) {
             if (desc[first + k].slot != v.slot) { LOGE("fake engine: fbank: VAD run %d crosses sessions", i); abort(); }
-            put((size_t)v.out_off + (size_t)k, first + k, false);
+            put(lay.record_at(OBS_VAD, (size_t)v.out_off + (size_t)k), first + k, false);
         }
     }
-    for (int i = 0; i < pass.n_dt; ++i) {
-        const DtmfDesc &t = pass.dt[i];
-        if (t.n <= 0 || t.first < 0 || t.first + t.n > n_frames || t.out_off < 0 || (size_t)t.out_off + (size_t)t.n > pass.dtmf_bytes) { LOGE("fake engine: fbank: DTMF descriptor %d outside the pass", i); abort(); }
-        for (int k = 0; k < t.n; ++k) put(pass.vad_bytes + (size_t)t.out_off + (size_t)k, t.first + k, true);
+    for (int i = 0; i < dtmf.n; ++i) {
+        const DtmfDesc &t = dt[i];
+        if (t.n <= 0 || t.first < 0 || t.first + t.n > n_frames || t.out_off < 0 || (size_t)t.out_off + (size_t)t.n > dtmf.frames) { LOGE("fake engine: fbank: DTMF descriptor %d outside the pass", i); abort(); }
+        for (int k = 0; k < t.n; ++k) put(lay.record_at(OBS_DTMF, (size_t)t.out_off + (size_t)k), t.first + k, true);
     }
     for (size_t i = 0; i < bytes; ++i) if (!written[i]) { LOGE("fake engine: fbank: byte %zu of the pass's block belongs to no run", i); abort(); }
     if (!f.lent.insert(block).second) { LOGE("fake engine: fbank: a lent block lent again"); abort(); }
